@@ -73,6 +73,32 @@ def synth_u8(seed, h, w, n=None):
     return s if n else s[0]
 
 
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(dirname, out, rank=0, world=1):
+    """--dump-outputs: what the timed call returned in its last step (out: (3H, 3W, C) on the host) as float32 DIR/output.npy
+    (DIR/output_rank<r>.npy per rank at N > 1).  An output larger than its share of DUMP_LIMIT_BYTES is written as a fixed sample
+    of whole rows -- the same rows in every run (seed 0), in order -- and their indices as float64 DIR/output_rows.npy.  Returns
+    the names written."""
+    tag = f"_rank{rank}" if world > 1 else ""
+    budget = DUMP_LIMIT_BYTES // world - 65536  # (room for the .npy headers)
+    arrays = {}
+    if out.size * 4 > budget:
+        k = budget // (out[0].size * 4 + 8)
+        if k == 0:
+            raise ValueError(f"--dump-outputs: one output row ({out[0].size * 4} bytes as float32) exceeds this rank's share of "
+                             f"{DUMP_LIMIT_BYTES} bytes")
+        rows = np.sort(np.random.default_rng(0).choice(out.shape[0], k, replace=False))
+        out = out[rows]
+        arrays["output_rows" + tag] = rows.astype(np.float64)
+    arrays["output" + tag] = out.astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(arrays)
+
+
 STAGE_SHAPE = {1: (1, 5), 2: (2, 5), 3: (3, 5), 4: (3, 3)}  # stage -> (sources, first kernel size)
 
 
@@ -329,7 +355,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-configs", action="store_true", help="skip the config_A / config_C / config_D entries")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/output.npy (float32; an output over "
+                         "64 MB as a fixed, seeded sample of whole rows, their indices in DIR/output_rows.npy): the inputs are seeded, "
+                         "so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # (before the HSA runtime comes up: the host driver only supports dmabuf IPC, RCCL's peer connections need this)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -515,6 +547,12 @@ def main():
         main_band.step()
     torch.cuda.synchronize()
     ms_per_step = timed(main_band.step, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs:
+        dumped = [dump_outputs(args.dump_outputs, main_band.out.cpu().numpy(), rank, world)]
+        if world > 1:  # (every rank writes its own files; the line rank 0 prints lists them all)
+            mine, dumped = dumped[0], [None] * world
+            dist.all_gather_object(dumped, mine)
     out_mp_total = world * (3 * H) * (3 * W) / 1e6
     value = out_mp_total / (ms_per_step / 1e3)
 
@@ -537,6 +575,8 @@ def main():
         "whole_call_frac": round(H * W * FLOP_PER_PX / (ms_per_step / 1e3) / 1e12 /
                                  (PEAK_F32_MFMA_TFLOPS if args.precision == "f32" else PEAK_F16_MFMA_TFLOPS), 4),
     }
+    if dumped:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "files": [n + ".npy" for names in dumped for n in names]}
 
     if world == 1 and not args.no_roofline:
         # ---- sustained: the same step looped for >= 3 s of wall time, every step bracketed by its own pair of events on the
@@ -1085,8 +1125,11 @@ def main():
                 result["host_call"] = {"error": str(ex)[:300]}
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result["cpu_baseline"] = cpu_baseline(params, px)
-        result["speedup_vs_cpu_baseline"] = round(value / result["cpu_baseline"]["value"], 1)
+        try:
+            result["cpu_baseline"] = cpu_baseline(params, px)
+            result["speedup_vs_cpu_baseline"] = round(value / result["cpu_baseline"]["value"], 1)
+        except Exception as ex:  # noqa: BLE001 -- never let the CPU leg cost the run its line
+            result["cpu_baseline"] = {"error": str(ex)[:300]}
 
     if world > 1:
         dist.barrier()

@@ -1,4 +1,4 @@
-"""bench.py's one-line JSON contract, on the GPU: N=1 with roofline + cpu_baseline objects, and a
+"""bench.py's one-line JSON contract, on the GPU: N=1 with roofline + cpu_baseline objects, the files of --dump-outputs, and a
 2-rank rehearsal of the sharded path (gloo, both ranks folded onto the one GPU of the test box --
 RCCL refuses two ranks per device; the driver's real N>1 runs use RCCL)."""
 import json
@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -67,6 +68,24 @@ def test_bench_single_gpu_contract():
     assert orf["peak_nominal"] == 2500.0 and 0 < orf["peak_measured_random_operands"] < orf["peak_nominal"] and "profiles/" in orf["source"]
     assert abs(orf["issued"] - 3 * orf["algorithmic"]) < 0.05 and 0 < orf["frac_of_nominal_issued"] < orf["frac_of_measured_issued"] < 1
     assert d["config_D"]["images_per_rank"] == 64 and d["config_D"]["data_path_collectives"] == 0 and "host_pipelined" in d["config_D"]
+
+
+def test_bench_dump_outputs(tmp_path, params):
+    """--dump-outputs: the last timed step's output, written whole at this size, is the oracle's upscale of bench.py's seeded input
+    frame (u8: within 1, only on rounding knife-edges); --steps sets the steps the line reports."""
+    import bench
+    import oracle
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "0", "--height", "360", "--width", "640", "--no-roofline",
+                        "--no-configs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dump_outputs"]["files"] == ["output.npy"]
+    got = np.load(tmp_path / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 4)
+    want = oracle.upscale_rgba8(params["imagenet"], bench.synth_u8(2, 360, 640))[0].astype(np.float32)
+    diff = np.abs(got - want)
+    assert diff.max() <= 1 and (diff != 0).mean() < 1e-3, (diff.max(), (diff != 0).mean())
 
 
 def test_bench_two_rank_rehearsal():
