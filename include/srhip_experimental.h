@@ -37,6 +37,16 @@ int sr_set_experiment(sr_ctx* ctx, const char* key, const char* value);
 
 /* What a switch has learned, as text (NUL-terminated, into buf[cap]).  key "forktune": one line per shape the fork tuner has met,
  * "HxW+halo_top+halo_bot precision io state undivided_ms forked_ms" with state measuring | undivided | forked (0.0000: not measured yet).
+ * key "plan" (a test hook): what the last call of an entry point on this context ran -- every sr_upscale_* / sr_reserve_* call clears it,
+ * the calls over several contexts clear each of theirs.  One line per decision, in the order they were made:
+ *   "host KIND s0,s1,... [rows=y0:y1]"  the host pipeline's chunk plan: KIND one | batch (s: images per chunk) | inorder | alternating
+ *                                       (s: the row bands' heights, computed in order on one stream / on alternating streams); rows=: the
+ *                                       share of the image a multi-context call gave this context;
+ *   "fork 0" | "fork 1 a,b"             a device call undivided, or as two bands of a and b rows ("fork 0 nomem": no room for the second);
+ *   "launch st=S form=first|pipe ty8=A ty4=B grid=G prec=f32|split_f16 f=F img=u8|f32 out=u8|f32 ch=C"
+ *                                       one launch of stage S (0: conv0, 4: the final stage): A rows of 8-row tiles then B rows of 4-row
+ *                                       tiles, G workgroups; C: channels of the input image.
+ * Identical lines in a row are one, followed by " xN".  Host-side text written where the decisions are made: no result depends on it.
  * Unknown key, or a buffer too small: SR_E_INVALID. */
 int sr_get_experiment(sr_ctx* ctx, const char* key, char* buf, size_t cap);
 

@@ -529,6 +529,8 @@ int sr_get_experiment(sr_ctx* c, const char* key, char* buf, size_t cap) {
                      t.best[0] < 1e29f ? t.best[0] : 0.f, t.best[1] < 1e29f ? t.best[1] : 0.f);
             out += line;
         }
+    } else if (!strcmp(key, "plan")) {  // what the last public call ran: "host ...", "fork ...", "launch ..." lines; " xN": N identical ones in a row
+        for (const auto& r : c->plan_rec) out += r.first + (r.second > 1 ? " x" + std::to_string(r.second) : std::string()) + "\n";
     } else {
         return SR_E_INVALID;
     }
@@ -746,6 +748,13 @@ int StackJob::launch(int st) const {
     const int bw = c->env_bw >= 0 ? c->env_bw : kAutoBlockWidth;
     const Launch& l = L[st];
     const int y0 = l.y0, y1 = l.y1;
+    {
+        char line[160];
+        snprintf(line, sizeof line, "launch st=%d form=%s ty8=%d ty4=%d grid=%d prec=%s f=%d img=%s out=%s ch=%d", st, l.pipe ? "pipe" : "first", l.ty8,
+                 l.ty4, l.grid, c->precision == SR_PRECISION_SPLIT_F16 ? "split_f16" : "f32", c->factor, img_u8 ? "u8" : "f32", out_u8 ? "u8" : "f32",
+                 img_u8 ? img_ch : 3);
+        sr_plan_note(c, line);
+    }
     if (st == 0) {
         auto rows = [&](int ya, int yb) -> int {  // f rows [ya, yb)
             if (ya >= yb) return SR_OK;
@@ -1065,6 +1074,7 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
     };
     if (!plan_fork(c, mode, img_u8, img_ch, n, H, W, halo_top, halo_bot, &rows_a)) {
         if (tune && tune->decided < 0 && mode == 1) tune->decided = 0;  // (cannot be forked at all)
+        if (c->graph == SR_GRAPH_SR_NET) sr_plan_note(c, "fork 0");
         return sampled(sr_run_stack(c, d_img, img_u8, img_ch, n, H, W, halo_top, halo_bot, d_out, out_u8, s, 0, gate));
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1099,8 +1109,10 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
         c->ws[1].feat_cap_px = 0; c->ws[1].geo_n = 0;
         if (tune && tune->decided < 0) tune->decided = 0;  // (no room for the fork's second workspace)
         sample = false;
+        sr_plan_note(c, "fork 0 nomem");
         return sr_run_stack(c, d_img, img_u8, img_ch, n, H, W, halo_top, halo_bot, d_out, out_u8, s, 0, gate);
     }
+    sr_plan_note(c, "fork 1 " + std::to_string(rows_a) + "," + std::to_string(H - halo_top - halo_bot - rows_a));
     for (int st = 0; st < 5 && rc == SR_OK; ++st) {
         rc = a.launch(st);
         if (rc == SR_OK) rc = b.launch(st);
@@ -1327,6 +1339,15 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     const int nch = (int)plan.size();
     const int slots = nch > 1 ? 2 : 1;
     {
+        // one | batch (images per chunk) | inorder / alternating (band rows, top to bottom); rows=: a share of the image (multi-context calls)
+        const bool bands = nch > 1 && (plan[0].halo_top > 0 || plan[0].halo_bot > 0);
+        std::string line = std::string("host ") + (nch == 1 ? "one" : !bands ? "batch" : in_order ? "inorder" : "alternating");
+        for (int i = 0; i < nch; ++i)
+            line += (i ? "," : " ") + std::to_string(bands ? (int)(plan[i].out_bytes / ((size_t)c->factor * c->factor * w * out_px)) : plan[i].n);
+        if (y_lo > 0 || y_hi < h) line += " rows=" + std::to_string(y_lo) + ":" + std::to_string(y_hi);
+        if (c->graph == SR_GRAPH_SR_NET) sr_plan_note(c, line);
+    }
+    {
         const int rc = sr_ensure_streams(c, nch > 1);
         if (rc != SR_OK) return rc;
     }
@@ -1476,21 +1497,25 @@ int sr_check_context_set(sr_ctx* const* ctxs, int n_ctx) { return check_context_
 extern "C" {
 
 int sr_upscale_f32_dev(sr_ctx* c, const float* d_in, int n, int h, int w, float* d_out, void* stream) {
+    sr_plan_clear(c);
     return sr_run_stack_auto(c, d_in, false, 3, n, h, w, 0, 0, d_out, false, (hipStream_t)stream);
 }
 
 int sr_upscale_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int n, int h, int w,
                          uint8_t* d_out, void* stream) {
+    sr_plan_clear(c);
     return sr_run_stack_auto(c, d_in, true, in_channels, n, h, w, 0, 0, d_out, true, (hipStream_t)stream);
 }
 
 int sr_upscale_band_f32_dev(sr_ctx* c, const float* d_in, int h_ext, int w, int halo_top, int halo_bot,
                             float* d_out, void* stream) {
+    sr_plan_clear(c);
     return sr_run_stack_auto(c, d_in, false, 3, 1, h_ext, w, halo_top, halo_bot, d_out, false, (hipStream_t)stream);
 }
 
 int sr_upscale_band_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int h_ext, int w,
                               int halo_top, int halo_bot, uint8_t* d_out, void* stream) {
+    sr_plan_clear(c);
     return sr_run_stack_auto(c, d_in, true, in_channels, 1, h_ext, w, halo_top, halo_bot, d_out, true,
                              (hipStream_t)stream);
 }
@@ -1521,20 +1546,24 @@ static int reserve_fork(sr_ctx* c, bool img_u8, int img_ch, int n, int h, int w)
 }
 
 int sr_reserve_f32(sr_ctx* c, int n, int h, int w) {
+    sr_plan_clear(c);
     const int rc = run_host(c, nullptr, false, 3, Deal{0, 1, n}, h, w, nullptr, false, 0, -1, true);
     return rc == SR_OK ? reserve_fork(c, false, 3, n, h, w) : rc;
 }
 
 int sr_reserve_rgba8(sr_ctx* c, int in_channels, int n, int h, int w) {
+    sr_plan_clear(c);
     const int rc = run_host(c, nullptr, true, in_channels, Deal{0, 1, n}, h, w, nullptr, true, 0, -1, true);
     return rc == SR_OK ? reserve_fork(c, true, in_channels, n, h, w) : rc;
 }
 
 int sr_upscale_f32(sr_ctx* c, const float* in, int n, int h, int w, float* out) {
+    sr_plan_clear(c);
     return run_host(c, in, false, 3, Deal{0, 1, n}, h, w, out, false);
 }
 
 int sr_upscale_rgba8(sr_ctx* c, const uint8_t* in, int in_channels, int n, int h, int w, uint8_t* out) {
+    sr_plan_clear(c);
     return run_host(c, in, true, in_channels, Deal{0, 1, n}, h, w, out, true);
 }
 
@@ -1545,6 +1574,7 @@ static int run_multi(sr_ctx* const* ctxs, int n_ctx, const void* in, bool img_u8
     if (!in || !out || h <= 0 || w <= 0) return SR_E_INVALID;
     const int chk = check_context_set(ctxs, n_ctx);
     if (chk != SR_OK) return chk;
+    for (int k = 0; k < n_ctx; ++k) sr_plan_clear(ctxs[k]);
     int rows = (h + n_ctx - 1) / n_ctx;
     rows = std::max(8, (rows + 7) / 8 * 8);
     const int used = (h + rows - 1) / rows;
@@ -1581,6 +1611,7 @@ static int run_batch_multi(sr_ctx* const* ctxs, int n_ctx, const void* in, bool 
     if (!in || !out || n <= 0 || h <= 0 || w <= 0) return SR_E_INVALID;
     const int chk = check_context_set(ctxs, n_ctx);
     if (chk != SR_OK) return chk;
+    for (int k = 0; k < n_ctx; ++k) sr_plan_clear(ctxs[k]);
     const int used = std::min(n_ctx, n);
     if (used == 1) return run_host(ctxs[0], in, img_u8, img_ch, Deal{0, 1, n}, h, w, out, out_u8);
     std::vector<int> rc(used, SR_OK);

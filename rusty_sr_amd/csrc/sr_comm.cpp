@@ -572,21 +572,25 @@ int sr_last_comm_exposed_ms(sr_ctx* c, double* exposed_ms) {
 }
 
 int sr_upscale_sharded_f32_dev(sr_ctx* c, const float* d_band, int h_band, int w, float* d_out, void* stream) {
+    sr_plan_clear(c);
     return run_sharded(c, d_band, false, 3, h_band, w, d_out, (hipStream_t)stream);
 }
 
 int sr_upscale_sharded_rgba8_dev(sr_ctx* c, const uint8_t* d_band, int in_channels, int h_band, int w, uint8_t* d_out,
                                  void* stream) {
+    sr_plan_clear(c);
     return run_sharded(c, d_band, true, in_channels, h_band, w, d_out, (hipStream_t)stream);
 }
 
 int sr_upscale_sharded_f32_all(sr_ctx* const* ctxs, int n, const float* const* d_bands, const int* h_bands, int w,
                                float* const* d_outs) {
+    for (int k = 0; ctxs && k < n; ++k) sr_plan_clear(ctxs[k]);
     return run_sharded_all(ctxs, n, (const void* const*)d_bands, h_bands, false, 3, w, (void* const*)d_outs);
 }
 
 int sr_upscale_sharded_rgba8_all(sr_ctx* const* ctxs, int n, const uint8_t* const* d_bands, int in_channels,
                                  const int* h_bands, int w, uint8_t* const* d_outs) {
+    for (int k = 0; ctxs && k < n; ++k) sr_plan_clear(ctxs[k]);
     return run_sharded_all(ctxs, n, (const void* const*)d_bands, h_bands, true, in_channels, w, (void* const*)d_outs);
 }
 

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/srhip.h"
@@ -103,7 +105,20 @@ struct sr_ctx {
     bool comm_broken = false;         // an exchange failed half-posted: the communicator was aborted, sharded calls return SR_E_COMM
     bool layer_halos = false;         // sharded calls exchange FEATURE rows after every stage instead of recomputing the overlap (sr_set_experiment "halo")
     hipEvent_t ev_layer[4] = {nullptr, nullptr, nullptr, nullptr};  // one-process sharded call in that mode: "stage st of this context is done"
+    // What the last public call ran (sr_get_experiment "plan", a test hook): the host pipeline's chunk plan, the fork decision of a device
+    // call, one line per stage launch -- identical consecutive lines as one, with a count.  Host-side text written where the decisions are
+    // made; cleared by every public entry point.
+    std::vector<std::pair<std::string, int>> plan_rec;
 };
+
+inline void sr_plan_clear(sr_ctx* c) {
+    if (c) c->plan_rec.clear();
+}
+
+inline void sr_plan_note(sr_ctx* c, const std::string& line) {
+    if (!c->plan_rec.empty() && c->plan_rec.back().first == line) ++c->plan_rec.back().second;
+    else c->plan_rec.emplace_back(line, 1);
+}
 
 // The library never leaves the calling thread on another device than it found it on: torch (and any HIP host) takes
 // "the current device" from hipGetDevice, and the one-process multi-GPU calls walk over every context's device.

@@ -259,10 +259,47 @@ class Engine:
         _lib.check(self._L.sr_set_experiment(self._ctx, key.encode(), value.encode()))
 
     def get_experiment(self, key: str) -> str:
-        """sr_get_experiment: what a switch has learned ("forktune": one line per shape the fork tuner has met)."""
-        buf = C.create_string_buffer(4096)
-        _lib.check(self._L.sr_get_experiment(self._ctx, key.encode(), buf, len(buf)))
+        """sr_get_experiment: what a switch has learned ("forktune": one line per shape the fork tuner has met; "plan": what the
+        last call ran).  A buffer that is too small is refused like an unknown key: retried with larger ones up to 16 MB."""
+        cap = 4096
+        while True:
+            buf = C.create_string_buffer(cap)
+            st = self._L.sr_get_experiment(self._ctx, key.encode(), buf, len(buf))
+            if st != _lib.SR_E_INVALID or cap >= 1 << 24:
+                break
+            cap *= 4
+        _lib.check(st)
         return buf.value.decode()
+
+    def last_plan(self) -> dict:
+        """What the last call on this context ran (sr_get_experiment "plan"), as data:
+        {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...]}.
+        host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
+        st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row)."""
+        rec = {"host": [], "fork": [], "launches": []}
+        for line in self.get_experiment("plan").splitlines():
+            words = line.split()
+            count = 1
+            if words[-1].startswith("x") and words[-1][1:].isdigit():
+                count = int(words.pop()[1:])
+            if words[0] == "host":
+                rows = None
+                if words[-1].startswith("rows="):
+                    a, b = words.pop()[5:].split(":")
+                    rows = (int(a), int(b))
+                for _ in range(count):
+                    rec["host"].append((words[1], [int(v) for v in words[2].split(",")], rows))
+            elif words[0] == "fork":
+                sizes = [int(v) for v in words[2].split(",")] if len(words) > 2 and words[2][0].isdigit() else [0, 0]
+                for _ in range(count):
+                    rec["fork"].append((words[1] == "1", sizes[0], sizes[1]))
+            elif words[0] == "launch":
+                d = dict(w.split("=", 1) for w in words[1:])
+                for k in ("st", "ty8", "ty4", "grid", "f", "ch"):
+                    d[k] = int(d[k])
+                d["count"] = count
+                rec["launches"].append(d)
+        return rec
 
     def set_profiling(self, on: bool):
         _lib.check(self._L.sr_set_profiling(self._ctx, int(on)))

@@ -113,15 +113,31 @@ def test_batch_equals_single(engines, params):
 
 
 def test_config_A_256x256_both_tile_heights(engines, params):
-    """BASELINE configs[1]: 256x256 RGB, bundled weights, single tile height 4 path;
-    512x512 exercises the 8-row tile path (>= 2 workgroups per CU)."""
+    """BASELINE configs[1]: 256x256 RGB, bundled weights, single tile height 4 path (exact f32: small launches run 4-row tiles).
+    512x512: the host-pointer calls run it as two bands in order (sr_api.cpp plan_chunks, mid-size frames), whose launches are small
+    too; undivided (set_pipeline(False)) it is 1024 8-row tiles, two per resident workgroup -- every stage in the pipe form on 8-row
+    tiles, the exact mode's final stage on the quad path -- which the plan record confirms."""
+    eng = engines["imagenet"]
     for seed, n, h, w in ((1, 1, 256, 256), (4, 1, 512, 512)):
         px = synth_u8(seed, n, h, w)
         x = oracle.img_to_data(px)
         want = oracle.forward(params["imagenet"], x)
-        got = engines["imagenet"].upscale_f32(x)
+        got = eng.upscale_f32(x)
         assert np.abs(got - want).max() < TIGHT
-        _check_u8(engines["imagenet"].upscale_rgba8(px), want)
+        _check_u8(eng.upscale_rgba8(px), want)
+    try:
+        eng.set_pipeline(False)
+        got = eng.upscale_f32(x)
+        stages = [l for l in eng.last_plan()["launches"] if l["st"] > 0]
+        assert [l["st"] for l in stages] == [1, 2, 3, 4]
+        assert all(l["form"] == "pipe" and l["ty8"] == 64 and l["ty4"] == 0 for l in stages), eng.get_experiment("plan")
+        assert np.abs(got - want).max() < TIGHT
+        got8 = eng.upscale_rgba8(px)
+        stages = [l for l in eng.last_plan()["launches"] if l["st"] > 0]
+        assert all(l["form"] == "pipe" and l["ty8"] == 64 and l["ty4"] == 0 and l["out"] == "u8" for l in stages), eng.get_experiment("plan")
+        _check_u8(got8, want)
+    finally:
+        eng.set_pipeline(True)
 
 
 def test_rgba8_fused_path(engines, params):
@@ -661,12 +677,35 @@ def test_other_factors_against_the_restatement(factor, precision):
     out = eng.upscale_band_f32_dev(xt[20 - 7:33 + 7].contiguous(), 7, 7)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(out.cpu().numpy(), full[factor * 20:factor * 33])
-    # an image with more 8-row tiles than resident workgroups: persistent pipe-form stages (1-3, and the final
-    # stage unless it needs two N-tiles) feeding / fed by first-form ones; whole output against the restatement
+    # 296x1100: the host-pointer call with f32 output runs it as bands in order (sr_api.cpp plan_chunks: 176 + 120 rows in exact f32, three
+    # in the split-half mode), whose launches are small -- in exact f32 4-row tiles and the first form of the final stage; whole output
+    # against the restatement
     px = synth_u8(91, 1, 296, 1100)
     x = oracle.img_to_data(px)
     got = eng.upscale_f32(x)
-    assert np.abs(got - oracle.forward_factor(p, x, factor)).max() < TIGHT
+    want = oracle.forward_factor(p, x, factor)
+    assert np.abs(got - want).max() < TIGHT
+    # ... undivided, more 8-row tiles than resident workgroups (1295 against 512): persistent pipe-form stages 1-3 on 8-row tiles, and
+    # the final stage too -- on the quad path in exact f32; in the split-half mode on 8-row tiles at factor 2, on 4-row ones at factor 4
+    # (two N-tiles of accumulators: sr_kernels.hip kBigTiles)
+    try:
+        eng.set_pipeline(False)
+        for io in ("f32", "u8"):
+            got = eng.upscale_f32(x) if io == "f32" else eng.upscale_rgba8(px)
+            stages = [l for l in eng.last_plan()["launches"] if l["st"] > 0]
+            assert [l["st"] for l in stages] == [1, 2, 3, 4] and all(l["form"] == "pipe" and l["out"] == io for l in stages)
+            assert all(l["ty8"] == 37 and l["ty4"] == 0 for l in stages[:3]), eng.get_experiment("plan")
+            four = precision == "split_f16" and factor == 4
+            assert (stages[3]["ty8"], stages[3]["ty4"]) == ((0, 74) if four else (37, 0)), eng.get_experiment("plan")
+            if io == "f32":
+                assert np.abs(got - want).max() < TIGHT
+                got32 = got
+            else:
+                _check_u8(got, want)
+                q = np.clip(np.floor(got32 * np.float32(255.0) + np.float32(0.5)), 0, 255).astype(np.uint8)
+                np.testing.assert_array_equal(got[..., :3], q)
+    finally:
+        eng.set_pipeline(True)
     eng.close()
 
 
