@@ -164,7 +164,11 @@ void sr_host_free(void* p);
  * After such a call sr_read_feature refuses (each workspace holds one band), as it does after a pipelined host call.
  * u8 device images are READ as whole aligned 32-bit words by the parameter-free graphs' kernels: up to 3 bytes in front of the
  * image's first byte and behind its last one -- bytes of the same aligned word, hence of the same allocation granule -- may be
- * read (never written, never used). */
+ * read (never written, never used).
+ * Alignment: d_out_rgba, and every float* buffer (d_in and d_out of the f32 forms), must be 4-byte aligned -- the kernels store the
+ * RGBA output as whole 32-bit words and address f32 buffers as floats.  A pointer that is not is refused with SR_E_INVALID before
+ * anything is launched, and the output is left untouched.  No larger alignment is needed (views into a larger allocation are fine),
+ * and u8 inputs may start at any byte.  The same holds for the band and sharded forms below. */
 int sr_upscale_f32_dev(sr_ctx* ctx, const float* d_in, int n, int h, int w, float* d_out,
                        void* stream);
 int sr_upscale_rgba8_dev(sr_ctx* ctx, const uint8_t* d_in, int in_channels, int n, int h, int w,

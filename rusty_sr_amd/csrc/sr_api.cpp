@@ -1498,24 +1498,28 @@ extern "C" {
 
 int sr_upscale_f32_dev(sr_ctx* c, const float* d_in, int n, int h, int w, float* d_out, void* stream) {
     sr_plan_clear(c);
+    if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, false, 3, n, h, w, 0, 0, d_out, false, (hipStream_t)stream);
 }
 
 int sr_upscale_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int n, int h, int w,
                          uint8_t* d_out, void* stream) {
     sr_plan_clear(c);
+    if (!sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, true, in_channels, n, h, w, 0, 0, d_out, true, (hipStream_t)stream);
 }
 
 int sr_upscale_band_f32_dev(sr_ctx* c, const float* d_in, int h_ext, int w, int halo_top, int halo_bot,
                             float* d_out, void* stream) {
     sr_plan_clear(c);
+    if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, false, 3, 1, h_ext, w, halo_top, halo_bot, d_out, false, (hipStream_t)stream);
 }
 
 int sr_upscale_band_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int h_ext, int w,
                               int halo_top, int halo_bot, uint8_t* d_out, void* stream) {
     sr_plan_clear(c);
+    if (!sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, true, in_channels, 1, h_ext, w, halo_top, halo_bot, d_out, true,
                              (hipStream_t)stream);
 }

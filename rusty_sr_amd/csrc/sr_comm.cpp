@@ -224,7 +224,7 @@ int run_layers_rank(sr_ctx* c, Rccl* R, bool u8, int img_ch, int h_band, int w, 
 
 // one process per GPU: exchange + band pass of this rank, asynchronous on `s`
 int run_sharded(sr_ctx* c, const void* d_band, bool u8, int img_ch, int h_band, int w, void* d_out, hipStream_t s) {
-    if (!d_out) return SR_E_INVALID;
+    if (!d_out || !sr_dword_aligned(d_out) || (!u8 && !sr_dword_aligned(d_band))) return SR_E_INVALID;
     if (u8 && img_ch != 3 && img_ch != 4) return SR_E_INVALID;
     if (c && c->comm_nranks > 1 && c->comm_local) return SR_E_COMM;  // the neighbours' rows are only known to sr_upscale_sharded_*_all
     sr_device_guard restore_device;
@@ -267,7 +267,9 @@ int run_sharded_all(sr_ctx* const* ctxs, int n, const void* const* d_bands, cons
     if (rc != SR_OK) return rc;
     if (u8 && img_ch != 3 && img_ch != 4) return SR_E_INVALID;
     for (int k = 0; k < n; ++k)
-        if (ctxs[k]->comm_nranks != n || ctxs[k]->comm_rank != k || !d_outs[k]) return SR_E_INVALID;
+        if (ctxs[k]->comm_nranks != n || ctxs[k]->comm_rank != k || !d_outs[k] || !sr_dword_aligned(d_outs[k]) ||
+            (!u8 && !sr_dword_aligned(d_bands[k])))
+            return SR_E_INVALID;
     const bool local = ctxs[0]->comm_local;
     for (int k = 1; k < n; ++k)
         if (ctxs[k]->comm_local != local || ctxs[k]->layer_halos != ctxs[0]->layer_halos) return SR_E_INVALID;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <string>
 #include <utility>
 #include <vector>
@@ -118,6 +119,12 @@ inline void sr_plan_clear(sr_ctx* c) {
 inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     if (!c->plan_rec.empty() && c->plan_rec.back().first == line) ++c->plan_rec.back().second;
     else c->plan_rec.emplace_back(line, 1);
+}
+
+// The device entry points' buffers that the kernels address as 32-bit words (include/srhip.h): every RGBA output -- the final stage
+// stores whole dwords (sr_kernels.hip DwordRun) -- and every f32 input and output.  Null passes here: the callers refuse it themselves.
+inline bool sr_dword_aligned(const void* p) {
+    return ((uintptr_t)p & 3u) == 0;
 }
 
 // The library never leaves the calling thread on another device than it found it on: torch (and any HIP host) takes
