@@ -266,6 +266,37 @@ int sr_check_domain(sr_ctx* ctx);
  * as bands -- a pipelined host call, a forked device call: sr_set_pipeline(ctx, 0) / the undivided device call leave whole maps. */
 int sr_read_feature(sr_ctx* ctx, int which, float* out_host, size_t cap_floats);
 
+/* ---- Validation: the loss of a parameter set on an HR image ----
+ * Replaces the validation pass of the reference's `train` (main.rs:220-247): the forward half of sr_net(f, Some((0.0, linear_loss)))
+ * (network.rs:88-102) on one HR image, and the sums its PSNR is made of.  For the context's factor f (2, 3 or 4):
+ *   input  = LinearToSrgb(mean over f x f blocks of SrgbToLinear(hr)), f32 -- NOT quantised to u8 (unlike the downsample graph's output)
+ *   output = sr_net(f)(input), f32, no clamp, no quantisation
+ *   err    = sum over the compared elements of (output - hr)^2, or with linear_loss != 0 (`-l`, --linearLoss) of
+ *            (SrgbToLinear(output) - SrgbToLinear(hr))^2 (the same formula outside [0, 1])
+ * hr is what img_to_data makes of the image (byte / 255, RGB, alpha dropped) or an f32 RGB image taken as is.  Each difference is formed
+ * in f32, its square summed in f64 (the reference sums in f32).  *n_elems counts the compared elements (pixels x 3): the PSNR of a set of
+ * images is -10 log10(sum err_i / sum n_i), the reference's weighting of each image's mean error by flat_size_single (main.rs:236-245).
+ * UNPINNED (alumina's source is not at hand): sizes not divisible by f follow the downsample graph -- the LR image is floor(h/f) x
+ * floor(w/f), the loss compares the output with the top-left f floor(h/f) x f floor(w/f) crop of hr, and n_elems counts that crop; h < f
+ * or w < f is SR_E_INVALID.  alumina's MseLoss normalisation is not reproduced: the sum and the count are what the PSNR needs.
+ * SR_GRAPH_SR_NET contexts only (others: SR_E_INVALID); the context's precision applies, and in SR_PRECISION_SPLIT_F16 the host-pointer
+ * forms recompute in exact f32 where a value leaves that mode's domain, like sr_upscale_f32.  The result is the same bits from run to
+ * run, context to context and device to device (a fixed reduction order, no atomics).  A job that does not fit is SR_E_NOMEM and leaves
+ * the context usable.  With sr_set_profiling on, sr_last_timing's total_ms is then the whole host-pointer call on the device (upload,
+ * pool, network, loss, download).  Synchronous, host memory: */
+int sr_validation_error_rgba8(sr_ctx* ctx, const uint8_t* hr, int in_channels, int h, int w, int linear_loss,
+                              double* err_sum, size_t* n_elems);
+int sr_validation_error_f32(sr_ctx* ctx, const float* hr, int h, int w, int linear_loss,
+                            double* err_sum, size_t* n_elems);
+/* ... device memory: ordered on `stream` alone, like every *_dev call; the sum is written to d_err_sum (device memory, 4-byte aligned).
+ * d_hr may start at any byte (read as whole aligned 32-bit words, like the parameter-free graphs' u8 inputs).  The element count is
+ * 3 f floor(h/f) f floor(w/f). */
+int sr_validation_error_rgba8_dev(sr_ctx* ctx, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss,
+                                  double* d_err_sum, void* stream);
+/* Test hook, like sr_read_feature: the training graph's `input` node (the pooled LR image, floor(h/f) x floor(w/f) x 3 f32) and `output`
+ * node (the f32 network output, f times that size) of the most recent validation call, image 0.  Either pointer may be NULL. */
+int sr_read_validation_nodes(sr_ctx* ctx, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

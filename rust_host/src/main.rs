@@ -1,10 +1,11 @@
 //! rusty_sr -- Rust host over libsrhip (the MI355X engine).
 //!
 //!     rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
+//!     rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] <VALIDATION_FOLDER>
 //!
 //! Same arguments, progress text and failure text as millardjn/rusty_sr v1; decoding and encoding
 //! of image files stay with the `image` crate as in the reference, everything between the decoded
-//! pixels and the pixels to encode runs on the GPU.  `train` is not part of this host.
+//! pixels and the pixels to encode runs on the GPU.  `train` is not part of this host; its validation pass is (`validate`).
 //! This file is not compiled in the repository's image (no Rust toolchain); the C++ twin
 //! `rusty_sr_amd/host/main.cpp` is what the tests drive, and `tests/test_rust_host.py` keeps the
 //! two in step (same option names, same strings, every FFI symbol exported).
@@ -115,11 +116,173 @@ fn parse_args() -> Options {
     o
 }
 
+fn validate_usage_error(msg: &str) -> ! {
+    let _ = writeln!(std::io::stderr(),
+        "error: {}\n\nUSAGE:\n    rusty_sr validate [FLAGS] [OPTIONS] <VALIDATION_FOLDER>\n\nFor more information try --help", msg);
+    exit(2)
+}
+
+const DECODABLE: [&'static str; 13] = ["png", "jpg", "jpeg", "gif", "tif", "tiff", "bmp", "ico", "tga", "ppm", "pgm", "pbm", "pnm"];
+
+fn collect_files(dir: &Path, recurse: bool, out: &mut Vec<std::path::PathBuf>) {
+    let entries = match std::fs::read_dir(dir) {
+        Ok(e) => e,
+        Err(_) => die("could not read the validation folder"),
+    };
+    for entry in entries.filter_map(|e| e.ok()) {
+        let path = entry.path();
+        if path.is_dir() {
+            if recurse {
+                collect_files(&path, recurse, out);
+            }
+        } else if let Some(ext) = path.extension().and_then(|e| e.to_str()) {
+            if DECODABLE.contains(&ext.to_lowercase().as_str()) {
+                out.push(path);
+            }
+        }
+    }
+}
+
+/// `rusty_sr validate`: the validation pass of the reference's `train` (main.rs:220-247) on its own, with `train`'s options
+/// (main.rs:83-114).  Files are decoded on a second thread ahead of the GPU; PSNR = -10 log10(sum err / sum n) (main.rs:236-246).
+fn validate(args: Vec<String>) {
+    let (mut parameters, mut custom, mut folder): (Option<String>, Option<String>, Option<String>) = (None, None, None);
+    let (mut linear, mut recurse, mut split_f16, mut timing) = (false, false, false, false);
+    let mut val_max: Option<usize> = None;
+    let mut devices: Vec<i32> = Vec::new();
+    let mut it = args.into_iter();
+    while let Some(a) = it.next() {
+        let mut value = |name: &str| -> String {
+            match it.next() {
+                Some(v) => v,
+                None => validate_usage_error(&format!("The argument '{}' requires a value but none was supplied", name)),
+            }
+        };
+        match a.as_str() {
+            "-h" | "--help" => {
+                println!("USAGE:\n    rusty_sr validate [-l|--linearLoss] [-r|--recurse] [-m|--val_max N] [-p PARAMETERS | -c PARAMETER_FILE] \
+                          [--precision f32|split_f16] [--devices N,N,...] [--timing] <VALIDATION_FOLDER>");
+                exit(0)
+            }
+            "-l" | "--linearLoss" => linear = true,
+            "-r" | "--recurse" => recurse = true,
+            "--timing" => timing = true,
+            "-d" | "--downsample" => validate_usage_error("The argument '--downsample' cannot be used with 'validate'"),
+            "-p" | "--parameters" => parameters = Some(value("--parameters <PARAMETERS>")),
+            "-c" | "--custom" => custom = Some(value("--custom <PARAMETER_FILE>")),
+            "-m" | "--val_max" => {
+                let v = value("--val_max <N>");
+                match v.parse::<usize>() {
+                    Ok(n) if n > 0 => val_max = Some(n),
+                    _ => validate_usage_error("-val_max N must be a positive integer"),
+                }
+            }
+            "--devices" => {
+                let v = value("--devices <N,N,...>");
+                for d in v.split(',') {
+                    devices.push(d.parse().unwrap_or_else(|_| validate_usage_error(&format!("'{}' isn't a valid value for '--devices <N,N,...>'", v))));
+                }
+            }
+            "--precision" => {
+                let v = value("--precision <MODE>");
+                match v.as_str() {
+                    "f32" => split_f16 = false,
+                    "split_f16" => split_f16 = true,
+                    _ => validate_usage_error(&format!("'{}' isn't a valid value for '--precision <MODE>'", v)),
+                }
+            }
+            s if s.len() > 1 && s.starts_with('-') => {
+                validate_usage_error(&format!("Found argument '{}' which wasn't expected, or isn't valid in this context", s))
+            }
+            _ if folder.is_none() => folder = Some(a.clone()),
+            _ => validate_usage_error(&format!("Found argument '{}' which wasn't expected, or isn't valid in this context", a)),
+        }
+    }
+    if let Some(ref p) = parameters {
+        if p != "imagenet" && p != "imagenetlinear" && p != "anime" {
+            validate_usage_error(&format!("'{}' isn't a valid value for '--parameters <PARAMETERS>'\n\t[values: anime, imagenet, imagenetlinear]", p));
+        }
+    }
+    if custom.is_some() && parameters.is_some() {
+        validate_usage_error("The argument '--custom <PARAMETER_FILE>' cannot be used with '--parameters <PARAMETERS>'");
+    }
+    let folder = folder.unwrap_or_else(|| validate_usage_error("The following required arguments were not provided:\n    <VALIDATION_FOLDER>"));
+    if !Path::new(&folder).is_dir() {
+        validate_usage_error(&format!("'{}' is not a folder", folder));
+    }
+    let mut files = Vec::new();
+    collect_files(Path::new(&folder), recurse, &mut files);
+    files.sort_by(|a, b| a.as_os_str().to_string_lossy().as_bytes().cmp(b.as_os_str().to_string_lossy().as_bytes()));
+    if let Some(n) = val_max {
+        files.truncate(n);
+    }
+    if files.is_empty() {
+        validate_usage_error(&format!("no image files in '{}'", folder));
+    }
+    if devices.is_empty() {
+        devices.push(0);
+    }
+
+    let (params, banner): (Vec<f32>, &str) = if let Some(ref file) = custom {
+        let mut data = Vec::new();
+        File::open(Path::new(file)).and_then(|mut f| f.read_to_end(&mut data)).unwrap_or_else(|_| die("Error opening parameter file"));
+        (decode_or_die(&data), "Validating using custom neural net parameters...")
+    } else {
+        match parameters.as_ref().map(|s| s.as_str()).unwrap_or("imagenet") {
+            "imagenetlinear" => (decode_or_die(IMAGENETLINEAR), "Validating using linear loss imagenet neural net parameters..."),
+            "anime" => (decode_or_die(ANIME), "Validating using anime neural net parameters..."),
+            _ => (decode_or_die(IMAGENET), "Validating using imagenet neural net parameters..."),
+        }
+    };
+    println!("{} {} image{}{}", banner, files.len(), if files.len() == 1 { "" } else { "s" }, if linear { ", linear loss" } else { "" });
+    let factor = [3, 2, 4].iter().cloned().find(|&f| unsafe { srhip::sr_num_params_factor(f) } as usize == params.len()).unwrap_or(3);
+    let mut engines: Vec<Engine> = devices.iter().map(|&d| Engine::new_factor(&params, factor, d).unwrap_or_else(|e| die(&e))).collect();
+    for e in engines.iter_mut() {
+        if split_f16 {
+            e.set_precision(srhip::SR_PRECISION_SPLIT_F16).unwrap_or_else(|err| die(&err));
+        }
+    }
+
+    // decode ahead of the GPU on a second thread, in path order
+    let (tx, rx) = std::sync::mpsc::sync_channel(4);
+    let names = files.clone();
+    let decoder = std::thread::spawn(move || {
+        for f in names {
+            let img = image::open(&f).map(|i| i.to_rgba());
+            if tx.send((f, img)).is_err() {
+                return;
+            }
+        }
+    });
+    let t0 = std::time::Instant::now();
+    let (mut err_sum, mut n_sum) = (0f64, 0f64);
+    for (i, (path, img)) in rx.iter().enumerate() {
+        let rgba = img.unwrap_or_else(|_| die(&format!("Error opening validation image file {}", path.display())));
+        let (w, h) = rgba.dimensions();
+        let k = i % engines.len();
+        let (e, n) = engines[k].validation_error(&rgba.into_raw(), w, h, linear).unwrap_or_else(|err| die(&format!("{}: {}", path.display(), err)));
+        err_sum += e;
+        n_sum += n as f64;
+    }
+    let _ = decoder.join();
+    let psnr = if err_sum == 0.0 { std::f32::INFINITY } else { (-10.0 * (err_sum / n_sum).log10()) as f32 };
+    println!("Validation PSNR:\t{}", psnr);  // main.rs:246
+    if timing {
+        let s = t0.elapsed().as_secs_f64();
+        let _ = writeln!(std::io::stderr(), "[timing] {} images in {:.3} s: {:.2} images/s", files.len(), s, files.len() as f64 / s);
+    }
+}
+
 fn decode_or_die(blob: &[u8]) -> Vec<f32> {
     srhip::rsr_decode(blob).unwrap_or_else(|_| die("ByteVec conversion failed"))
 }
 
 fn main() {
+    let argv: Vec<String> = env::args().collect();
+    if argv.len() >= 2 && argv[1] == "validate" {
+        validate(argv[2..].to_vec());
+        return;
+    }
     let o = parse_args();
 
     // which graph, which parameters -- and the line the reference prints for each choice

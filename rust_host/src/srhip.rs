@@ -83,6 +83,10 @@ extern "C" {
     pub fn sr_device_info(ctx: *mut SrCtx, name: *mut c_char, cap: usize, cus: *mut c_int, mhz: *mut c_int) -> c_int;
     pub fn sr_last_hip_error(ctx: *mut SrCtx) -> c_int;
     pub fn sr_strerror(status: c_int) -> *const c_char;
+    pub fn sr_validation_error_rgba8(ctx: *mut SrCtx, hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
+    pub fn sr_validation_error_f32(ctx: *mut SrCtx, hr: *const f32, h: c_int, w: c_int, linear_loss: c_int, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
+    pub fn sr_validation_error_rgba8_dev(ctx: *mut SrCtx, d_hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, d_err_sum: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn sr_read_validation_nodes(ctx: *mut SrCtx, lr_out: *mut f32, cap_lr: usize, out_out: *mut f32, cap_out: usize) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.
@@ -127,6 +131,26 @@ impl Engine {
             return Err(strerror(rc));
         }
         Ok(Engine { ctx: ctx, graph: graph })
+    }
+
+    /// An sr_net context at factor 2, 3 or 4 (the parameter count must be sr_num_params_factor(factor)).
+    pub fn new_factor(params: &[f32], factor: c_int, device: c_int) -> Result<Engine, String> {
+        let mut ctx = ptr::null_mut();
+        let rc = unsafe { sr_create(&mut ctx, params.as_ptr(), params.len(), factor, device) };
+        if rc != SR_OK {
+            return Err(strerror(rc));
+        }
+        Ok(Engine { ctx: ctx, graph: SR_GRAPH_SR_NET })
+    }
+
+    /// The validation pass of the reference's `train` (main.rs:220-247) on one RGBA8 HR image: (err_sum, n_elems).
+    pub fn validation_error(&mut self, rgba: &[u8], w: u32, h: u32, linear_loss: bool) -> Result<(f64, usize), String> {
+        assert_eq!(rgba.len(), w as usize * h as usize * 4);
+        let (mut err, mut n) = (0f64, 0usize);
+        let rc = unsafe {
+            sr_validation_error_rgba8(self.ctx, rgba.as_ptr(), 4, h as c_int, w as c_int, linear_loss as c_int, &mut err, &mut n)
+        };
+        if rc == SR_OK { Ok((err, n)) } else { Err(strerror(rc)) }
     }
 
     pub fn set_precision(&mut self, mode: c_int) -> Result<(), String> {

@@ -64,6 +64,10 @@ SYMBOLS = {
     "sr_device_info": (_i, [_vp, C.c_char_p, _sz, C.POINTER(_i), C.POINTER(_i)]),
     "sr_last_hip_error": (_i, [_vp]),
     "sr_strerror": (C.c_char_p, [_i]),
+    "sr_validation_error_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, _dp, C.POINTER(_sz)]),
+    "sr_validation_error_f32": (_i, [_vp, _fp, _i, _i, _i, _dp, C.POINTER(_sz)]),
+    "sr_validation_error_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_read_validation_nodes": (_i, [_vp, _fp, _sz, _fp, _sz]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -110,6 +110,13 @@ struct sr_ctx {
     // call, one line per stage launch -- identical consecutive lines as one, with a count.  Host-side text written where the decisions are
     // made; cleared by every public entry point.
     std::vector<std::pair<std::string, int>> plan_rec;
+    // ---- validation pass (sr_valid.cpp): the forward half of the training graph, grown on demand, freed by sr_destroy
+    void* d_vhr = nullptr; size_t vhr_cap = 0;      // the HR image of a host-pointer call
+    void* d_vlr = nullptr; size_t vlr_cap = 0;      // the pooled LR image (the graph's `input` node), f32
+    void* d_vout = nullptr; size_t vout_cap = 0;    // the network's f32 output (`output` node)
+    void* d_vpart = nullptr; size_t vpart_cap = 0;  // the loss kernel's f64 partials, then the host-pointer calls' result
+    float* d_vtab = nullptr;                        // 512 floats: byte / 255, then SrgbToLinear of those (sr_valid.cpp)
+    int vnode_h = 0, vnode_w = 0;                   // LR size of the last validation call (0: none yet)
 };
 
 inline void sr_plan_clear(sr_ctx* c) {
@@ -184,3 +191,13 @@ void sr_band_pass_end(sr_band_pass* p);
 int sr_ensure_buf(sr_ctx* c, void** p, size_t* cap, size_t bytes);
 int sr_ensure_streams(sr_ctx* c, bool pipelined);  // the context's own streams are created on first use
 void sr_comm_release(sr_ctx* c);  // sr_comm.cpp: destroy the communicator and its buffers (called by sr_destroy)
+
+// ---- validation pass (sr_valid.hip kernels, sr_valid.cpp host side)
+void sr_valid_release(sr_ctx* c);  // sr_valid.cpp: free the validation buffers (called by sr_destroy)
+int sr_valid_loss_grid(int HC, int WC);  // workgroups (= f64 partials) of the loss kernel for an HC x WC crop: a function of the shape alone
+// HR (W px per row, u8 with ch channels or f32 RGB) -> LR image OH x OW x 3 f32 = LinearToSrgb(mean_{f x f}(SrgbToLinear(hr)))
+hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch, int W, int OH, int OW, float* d_lr, const float* d_tab,
+                                hipStream_t s);
+// sum over the HC x WC crop of (out - hr)^2 (linear: of SrgbToLinear of both) -> one double at d_result (4-byte aligned)
+hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,
+                                double* d_partial, void* d_result, hipStream_t s);

@@ -1,0 +1,168 @@
+// sr_valid.cpp -- the validation pass of the reference's `train` (main.rs:220-247): the forward half of
+// sr_net(f, Some((0.0, linear_loss))) (network.rs:88-102) on one HR image -- pool, network, loss -- returning the loss as a sum
+// and an element count (include/srhip.h sr_validation_error_*).  Kernels: sr_valid.hip; the network: sr_run_stack_auto.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "sr_internal.h"
+
+namespace {
+
+// 512 floats: img_to_data (main.rs:170: byte / 255, an f32 division), then SrgbToLinear of those as the correctly rounded f32 of the
+// f64 formula -- computed here, so that every device holds the same table and the tests can restate it bit for bit
+int ensure_table(sr_ctx* c) {
+    if (c->d_vtab) return SR_OK;
+    float tab[512];
+    for (int b = 0; b < 256; ++b) {
+        const float s = (float)b / 255.0f;
+        tab[b] = s;
+        tab[256 + b] = (float)(s <= 0.04045f ? (double)s / 12.92 : std::pow(((double)s + 0.055) / 1.055, 2.4));
+    }
+    float* d = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d, sizeof tab));
+    const hipError_t e = hipMemcpy(d, tab, sizeof tab, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    c->d_vtab = d;
+    return SR_OK;
+}
+
+void free_buf(void*& p, size_t& cap) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
+
+// Arguments of every entry point, checked before the GPU is touched.
+int check_args(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w) {
+    if (!c || !hr) return SR_E_INVALID;
+    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    if (hr_u8 ? (ch != 3 && ch != 4) : ch != 3) return SR_E_INVALID;
+    if (h < c->factor || w < c->factor) return SR_E_INVALID;  // not one f x f pooling block
+    return SR_OK;
+}
+
+// Pool, network, loss on device buffers, queued on s; the sum lands at d_result (nullptr: the slot behind the partials, for the
+// host-pointer calls).  The context's device is current.
+int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w, bool linear, void* d_result, hipStream_t s) {
+    const int f = c->factor, OH = h / f, OW = w / f, HC = f * OH, WC = f * OW;
+    const int grid = sr_valid_loss_grid(HC, WC);
+    const size_t lr_bytes = (size_t)OH * OW * 3 * sizeof(float), out_bytes = (size_t)HC * WC * 3 * sizeof(float);
+    int rc = ensure_table(c);
+    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vlr, &c->vlr_cap, lr_bytes);
+    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vout, &c->vout_cap, out_bytes);
+    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vpart, &c->vpart_cap, (size_t)(grid + 1) * sizeof(double));
+    c->vnode_h = c->vnode_w = 0;
+    if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
+        free_buf(c->d_vlr, c->vlr_cap);
+        free_buf(c->d_vout, c->vout_cap);
+        return rc;
+    }
+    if (!d_result) d_result = (double*)c->d_vpart + grid;
+    HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, OH, OW, (float*)c->d_vlr, c->d_vtab + 256, s));  // (SrgbToLinear of the bytes)
+    rc = sr_run_stack_auto(c, c->d_vlr, false, 3, 1, OH, OW, 0, 0, c->d_vout, false, s);
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, sr_launch_valid_loss((const float*)c->d_vout, d_hr, hr_u8, ch, linear, w, HC, WC, c->d_vtab, (double*)c->d_vpart, d_result, s));
+    c->vnode_h = OH; c->vnode_w = OW;
+    return SR_OK;
+}
+
+// The host-pointer calls: upload, run, download 8 bytes, on the context's own stream; synchronous.  In the split-half mode a value that
+// left its domain makes the whole call run again in exact f32, as the host-pointer upscale calls do (include/srhip.h sr_set_precision).
+int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w, int linear, double* err_sum, size_t* n_elems) {
+    sr_plan_clear(c);
+    int rc = check_args(c, hr, hr_u8, ch, h, w);
+    if (rc != SR_OK) return rc;
+    if (!err_sum || !n_elems) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = sr_ensure_streams(c, false);
+    if (rc != SR_OK) return rc;
+    // a fault an earlier unchecked *_dev call left is that call's to report (sr_check_domain), not a reason to recompute this one
+    if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
+    const size_t hr_bytes = (size_t)h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
+    rc = sr_ensure_buf(c, &c->d_vhr, &c->vhr_cap, hr_bytes);
+    if (rc != SR_OK) {
+        free_buf(c->d_vhr, c->vhr_cap);
+        return rc;
+    }
+    hipStream_t s = c->stream;
+    const int f = c->factor;
+    const int grid = sr_valid_loss_grid(f * (h / f), f * (w / f));
+    bool profiled = false;
+    if (c->profiling) profiled = hipEventRecord(c->ev[6], s) == hipSuccess;
+    HIPCHK(c, hipMemcpyAsync(c->d_vhr, hr, hr_bytes, hipMemcpyHostToDevice, s));
+    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s);
+    double sum = 0.0;
+    const hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(&sum, (double*)c->d_vpart + grid, sizeof sum, hipMemcpyDeviceToHost, s) : hipSuccess;
+    if (profiled && e1 == hipSuccess && rc == SR_OK) profiled = hipEventRecord(c->ev[7], s) == hipSuccess;
+    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, e1);
+    HIPCHK(c, e2);
+    if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
+        *(volatile int*)c->h_domain = 0;
+        (void)sr_set_precision(c, SR_PRECISION_F32);
+        rc = validation_host(c, hr, hr_u8, ch, h, w, linear, err_sum, n_elems);
+        (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
+        ++c->domain_fallbacks;
+        return rc;
+    }
+    if (profiled) {  // sr_last_timing: total = the whole call on the device (upload, pool, network, loss, download); stages: the network's
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->ev[6], c->ev[7]) == hipSuccess) c->total_ms = ms; else (void)hipGetLastError();
+    }
+    *err_sum = sum;
+    *n_elems = (size_t)f * (h / f) * f * (w / f) * 3;
+    return SR_OK;
+}
+
+}  // namespace
+
+void sr_valid_release(sr_ctx* c) {
+    free_buf(c->d_vhr, c->vhr_cap);
+    free_buf(c->d_vlr, c->vlr_cap);
+    free_buf(c->d_vout, c->vout_cap);
+    free_buf(c->d_vpart, c->vpart_cap);
+    if (c->d_vtab) (void)hipFree(c->d_vtab);
+    c->d_vtab = nullptr;
+    c->vnode_h = c->vnode_w = 0;
+}
+
+extern "C" {
+
+int sr_validation_error_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, double* err_sum, size_t* n_elems) {
+    return validation_host(c, hr, true, in_channels, h, w, linear_loss, err_sum, n_elems);
+}
+
+int sr_validation_error_f32(sr_ctx* c, const float* hr, int h, int w, int linear_loss, double* err_sum, size_t* n_elems) {
+    return validation_host(c, hr, false, 3, h, w, linear_loss, err_sum, n_elems);
+}
+
+int sr_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss, double* d_err_sum, void* stream) {
+    sr_plan_clear(c);
+    const int rc = check_args(c, d_hr, true, in_channels, h, w);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_validation(c, d_hr, true, in_channels, h, w, linear_loss != 0, d_err_sum, (hipStream_t)stream);
+}
+
+int sr_read_validation_nodes(sr_ctx* c, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out) {
+    if (!c || (!lr_out && !out_out)) return SR_E_INVALID;
+    const size_t n_lr = (size_t)c->vnode_h * c->vnode_w * 3, n_out = n_lr * c->factor * c->factor;
+    if (n_lr == 0 || (lr_out && cap_lr < n_lr) || (out_out && cap_out < n_out)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceSynchronize());
+    if (lr_out) HIPCHK(c, hipMemcpy(lr_out, c->d_vlr, n_lr * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_out) HIPCHK(c, hipMemcpy(out_out, c->d_vout, n_out * sizeof(float), hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,268 @@
+// sr_valid.hip -- the forward half of the reference's training graph, for its validation pass (reference main.rs:220-247,
+// network.rs:88-102), on gfx950:
+//
+//   input  = LinearToSrgb(mean_{f x f}(SrgbToLinear(hr)))       valid_pool_kernel    (the network's LR input, f32, not quantised)
+//   output = sr_net(f)(input)                                     the stage kernels (sr_kernels.hip), f32 output
+//   err    = sum (output - hr)^2                                  valid_loss_kernel + valid_sum_kernel
+//         or sum (SrgbToLinear(output) - SrgbToLinear(hr))^2     (-l / --linearLoss)
+//
+// over the top-left f*floor(h/f) x f*floor(w/f) crop of the HR image (UNPINNED: the remainder rule of the downsample graph).
+//
+// Pool: one thread per LR pixel, nothing staged.  Each of its f rows is read as the aligned dwords that hold the row's f*CH bytes (u8,
+// shifted into place with v_alignbyte, as downsample_net's kernel in sr_aux.hip does) or as 3f floats; SrgbToLinear of a byte is the
+// context's 256-entry table (LDS), of a float the hardware log2 / exp2 form; LinearToSrgb likewise on v_log_f32 / v_exp_f32.  Error of
+// the LR image against an f64 restatement: below 2e-6 absolute (tests/test_gpu_validation.py), the same class as the aux graphs'
+// f32 entry points (1.8e-7 measured there, tests/measure_aux_error.py), plus the f32 sum of f*f samples.
+//
+// Loss: memory-bound (a 4K HR image: 100 MB of f32 output + 33 MB of RGBA8), so the kernel is sized against the measured 6.29 TB/s copy
+// rate: a thread takes 4 output pixels at a time -- three 16-byte loads of the output, the 4 HR pixels as the aligned dwords that hold
+// them -- and every difference is formed in f32 and squared and summed in f64.  One f64 partial per workgroup; the grid depends on
+// the shape alone (never on the CU count), and valid_sum_kernel adds the partials in a fixed order in one workgroup: the result is
+// the same bits on every run, context and device.  No atomics.
+// In linear-loss mode SrgbToLinear must be a function the tests can restate bit for bit: it is the correctly rounded f32 of the
+// formula (an f32 estimate on the hardware pow, two Newton steps for the fifth root in f64 -- x^2.4 = x^2 * (x^2)^(1/5) -- then one
+// rounding), and the HR bytes' table holds the same rounding of the same formula, computed on the host.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "sr_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ---- the transfer functions, with the constants of sr_aux.hip (alumina SrgbToLinear / LinearToSrgb: IEC 61966-2-1)
+__device__ __forceinline__ float fast_pow(float x, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(x)); }
+__device__ __forceinline__ float srgb_to_linear_fast(float s) { return s <= 0.04045f ? s / 12.92f : fast_pow((s + 0.055f) / 1.055f, 2.4f); }
+__device__ __forceinline__ float linear_to_srgb_fast(float l) { return l <= 0.0031308f ? 12.92f * l : 1.055f * fast_pow(l, 1.0f / 2.4f) - 0.055f; }
+
+// SrgbToLinear(s), correctly rounded to f32 but for inputs within ~1e-16 relative of a rounding boundary: the f64 formula
+// ((s + 0.055) / 1.055)^2.4, with the power as a^2 * y, y = (a^2)^(1/5) refined by two Newton steps from the hardware estimate
+// (relative error ~3e-7 -> ~1e-13 -> below f64 rounding).  The same formula holds outside [0, 1] (s > 1; s <= 0.04045: s / 12.92).
+__device__ __forceinline__ float srgb_to_linear_cr(float s) {
+    if (s <= 0.04045f) return (float)((double)s * (1.0 / 12.92));
+    const double a = ((double)s + 0.055) * (1.0 / 1.055);
+    const double t = a * a;
+    double y = (double)fast_pow((float)a, 0.4f);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {  // y <- y + y (t / y^5 - 1) / 5
+        const double y2 = y * y, y5 = y2 * y2 * y;
+        double r = __builtin_amdgcn_rcp(y5);
+        r = fma(r, fma(-y5, r, 1.0), r);
+        r = fma(r, fma(-y5, r, 1.0), r);
+        const double e = fma(t, r, -1.0);
+        y = fma(y * 0.2, e, y);
+    }
+    return (float)(t * y);
+}
+
+// the aligned dwords that hold `len` bytes starting at p (all of them hold a byte of the piece: nothing outside the words of the
+// image is read), then the piece's bytes 0 .. 4 NW - 1 in place
+template <int LEN>
+struct BytePiece {
+    static constexpr int NW = (LEN + 3) / 4;
+    uint32_t w[NW + 1];
+    uint32_t mis;
+    __device__ __forceinline__ void load(const uint8_t* p) {
+        mis = (uint32_t)(uintptr_t)p & 3u;
+        const uint32_t* src = (const uint32_t*)(p - mis);
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = src[k];
+        w[NW] = (mis + LEN > 4 * NW) ? src[NW] : 0u;
+    }
+    __device__ __forceinline__ uint32_t byte(int b) const {  // b a compile-time constant after unrolling
+        const uint32_t al = __builtin_amdgcn_alignbyte(w[(b >> 2) + 1], w[b >> 2], mis);
+        return (al >> (8 * (b & 3))) & 0xffu;
+    }
+};
+
+struct __attribute__((packed, aligned(4))) F3 { float v[3]; };
+
+// HR (n = 1, h x w x CH u8, or h x w x 3 f32) -> LR (h/f x w/f x 3 f32).  tab: 256 floats SrgbToLinear(byte / 255) (u8 only).
+template <int F, bool HR_U8, int CH>
+__global__ __launch_bounds__(256) void valid_pool_kernel(const void* __restrict__ hr, float* __restrict__ lr, const float* __restrict__ tab,
+                                                         int W, int OH, int OW) {
+    __shared__ float s_lin[HR_U8 ? 256 : 1];
+    if constexpr (HR_U8) {
+        s_lin[threadIdx.x] = tab[threadIdx.x];
+        __syncthreads();
+    }
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)OH * OW) return;
+    const int oy = (int)(idx / OW), ox = (int)(idx - (long)oy * OW);
+    float acc[3] = {0.f, 0.f, 0.f};
+    if constexpr (HR_U8) {
+        BytePiece<F * CH> piece[F];
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy)
+            piece[dy].load((const uint8_t*)hr + ((size_t)(F * oy + dy) * W + (size_t)F * ox) * CH);
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy)  // rows, then columns: the reference's order
+#pragma unroll
+            for (int dx = 0; dx < F; ++dx)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += s_lin[piece[dy].byte(CH * dx + c)];
+    } else {
+        float v[F][3 * F];
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy) {
+            const float* src = (const float*)hr + ((size_t)(F * oy + dy) * W + (size_t)F * ox) * 3;
+#pragma unroll
+            for (int k = 0; k < 3 * F; ++k) v[dy][k] = src[k];
+        }
+#pragma unroll
+        for (int dy = 0; dy < F; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < F; ++dx)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += srgb_to_linear_fast(v[dy][3 * dx + c]);
+    }
+    F3 o;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o.v[c] = linear_to_srgb_fast(acc[c] / (float)(F * F));
+    ((F3*)lr)[idx] = o;
+}
+
+// sum over the 64 lanes of a wave by butterfly shuffles: every lane ends with the same bits
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// workgroup of 256: every wave's sum, then the four in order; the result in thread 0
+__device__ __forceinline__ double block_sum(double v, double* s_part) {
+    v = wave_sum(v);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) s_part[wave] = v;
+    __syncthreads();
+    return ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+}
+
+constexpr int kLossMaxGrid = 2048;   // workgroups of valid_loss_kernel at most (the number of f64 partials)
+
+// out: the network's f32 output, HC x WC x 3, contiguous and 16-byte aligned (a context buffer); hr: the HR image, row pitch W pixels;
+// tab: [0, 256) byte / 255 (img_to_data), [256, 512) srgb_to_linear_cr of those.  A work item is 4 consecutive output pixels.
+template <bool HR_U8, int CH, bool LINEAR>
+__global__ __launch_bounds__(256) void valid_loss_kernel(const float* __restrict__ out, const void* __restrict__ hr, const float* __restrict__ tab,
+                                                         int W, int HC, int WC, double* __restrict__ partial) {
+    __shared__ float s_tab[HR_U8 ? 256 : 1];
+    __shared__ double s_part[4];
+    if constexpr (HR_U8) {
+        s_tab[threadIdx.x] = tab[(LINEAR ? 256 : 0) + threadIdx.x];
+        __syncthreads();
+    }
+    const long npx = (long)HC * WC, items = (npx + 3) / 4;
+    auto hr_value = [&](uint32_t byte_or_bits) -> float {
+        if constexpr (HR_U8) return s_tab[byte_or_bits];
+        else return LINEAR ? srgb_to_linear_cr(__uint_as_float(byte_or_bits)) : __uint_as_float(byte_or_bits);
+    };
+    auto out_value = [&](float v) -> float { return LINEAR ? srgb_to_linear_cr(v) : v; };
+    double acc = 0.0;
+    for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < items; it += (long)gridDim.x * 256) {
+        const long p0 = 4 * it;
+        const int y = (int)(p0 / WC), x = (int)(p0 - (long)y * WC);
+        if (p0 + 4 <= npx && x + 4 <= WC) {  // four pixels of one row: contiguous in both images
+            const f32x4* o4 = (const f32x4*)(out + 3 * p0);
+            const f32x4 a = o4[0], b = o4[1], c = o4[2];
+            const float o[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+            uint32_t h[12];
+            if constexpr (HR_U8) {
+                BytePiece<4 * CH> piece;
+                piece.load((const uint8_t*)hr + ((size_t)y * W + x) * CH);
+#pragma unroll
+                for (int k = 0; k < 12; ++k) h[k] = piece.byte(CH * (k / 3) + k % 3);
+            } else {
+                const uint32_t* src = (const uint32_t*)hr + ((size_t)y * W + x) * 3;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) h[k] = src[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 12; ++k) {
+                const double d = (double)(out_value(o[k]) - hr_value(h[k]));
+                acc += d * d;
+            }
+        } else {  // a row seam (WC % 4 != 0) or the last, partial item: pixel by pixel
+            for (int i = 0; i < 4 && p0 + i < npx; ++i) {
+                const long p = p0 + i;
+                const int py = (int)(p / WC), px = (int)(p - (long)py * WC);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    uint32_t hv;
+                    if constexpr (HR_U8) hv = ((const uint8_t*)hr)[((size_t)py * W + px) * CH + k];
+                    else hv = ((const uint32_t*)hr)[((size_t)py * W + px) * 3 + k];
+                    const double d = (double)(out_value(out[3 * p + k]) - hr_value(hv));
+                    acc += d * d;
+                }
+            }
+        }
+    }
+    acc = block_sum(acc, s_part);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+// one workgroup: partials t, t + 256, ... per thread, then the workgroup's sum; stored as two dwords (the caller's pointer is only
+// 4-byte aligned)
+__global__ __launch_bounds__(256) void valid_sum_kernel(const double* __restrict__ partial, int n, uint32_t* __restrict__ result) {
+    __shared__ double s_part[4];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+    acc = block_sum(acc, s_part);
+    if (threadIdx.x == 0) {
+        const uint64_t bits = (uint64_t)__double_as_longlong(acc);
+        result[0] = (uint32_t)bits;
+        result[1] = (uint32_t)(bits >> 32);
+    }
+}
+
+template <int F>
+void launch_pool(const void* hr, bool hr_u8, int ch, float* lr, const float* tab, int W, int OH, int OW, hipStream_t s) {
+    const long px = (long)OH * OW;
+    const dim3 grid((unsigned)((px + 255) / 256));
+    if (hr_u8 && ch == 3) hipLaunchKernelGGL((valid_pool_kernel<F, true, 3>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
+    else if (hr_u8) hipLaunchKernelGGL((valid_pool_kernel<F, true, 4>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
+    else hipLaunchKernelGGL((valid_pool_kernel<F, false, 3>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
+}
+
+template <bool HR_U8, int CH>
+void launch_loss(bool linear, int grid, const float* out, const void* hr, const float* tab, int W, int HC, int WC, double* partial, hipStream_t s) {
+    if (linear) hipLaunchKernelGGL((valid_loss_kernel<HR_U8, CH, true>), dim3(grid), dim3(256), 0, s, out, hr, tab, W, HC, WC, partial);
+    else hipLaunchKernelGGL((valid_loss_kernel<HR_U8, CH, false>), dim3(grid), dim3(256), 0, s, out, hr, tab, W, HC, WC, partial);
+}
+
+}  // namespace
+
+int sr_valid_loss_grid(int HC, int WC) {
+    const long items = ((long)HC * WC + 3) / 4;
+    return (int)std::min<long>(kLossMaxGrid, std::max<long>(1, (items + 255) / 256));
+}
+
+hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch, int W, int OH, int OW, float* d_lr, const float* d_tab,
+                                hipStream_t s) {
+    if (OH <= 0 || OW <= 0 || (hr_u8 ? (ch != 3 && ch != 4) : ch != 3)) return hipErrorInvalidValue;
+    switch (factor) {
+        case 2: launch_pool<2>(d_hr, hr_u8, ch, d_lr, d_tab, W, OH, OW, s); break;
+        case 3: launch_pool<3>(d_hr, hr_u8, ch, d_lr, d_tab, W, OH, OW, s); break;
+        case 4: launch_pool<4>(d_hr, hr_u8, ch, d_lr, d_tab, W, OH, OW, s); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,
+                                double* d_partial, void* d_result, hipStream_t s) {
+    if (HC <= 0 || WC <= 0 || (hr_u8 ? (ch != 3 && ch != 4) : ch != 3)) return hipErrorInvalidValue;
+    const int grid = sr_valid_loss_grid(HC, WC);
+    if (hr_u8 && ch == 3) launch_loss<true, 3>(linear, grid, d_out, d_hr, d_tab, W, HC, WC, d_partial, s);
+    else if (hr_u8) launch_loss<true, 4>(linear, grid, d_out, d_hr, d_tab, W, HC, WC, d_partial, s);
+    else launch_loss<false, 3>(linear, grid, d_out, d_hr, d_tab, W, HC, WC, d_partial, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(valid_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)d_partial, grid, (uint32_t*)d_result);
+    return hipGetLastError();
+}

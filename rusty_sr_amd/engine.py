@@ -242,6 +242,53 @@ class Engine:
         _lib.check(st, self._ctx)
         return out
 
+    # ---- validation: the forward half of the training graph (reference main.rs:220-247, network.rs:88-102) ----
+    def validation_error(self, hr: np.ndarray, linear_loss: bool = False):
+        """HR image (H,W,3|4) u8 (img_to_data: byte / 255, alpha dropped) or (H,W,3) f32 -> (err_sum, n_elems): the squared error of
+        sr_net(f)(LinearToSrgb(mean_fxf(SrgbToLinear(hr)))) against hr (of SrgbToLinear of both with linear_loss) over the top-left
+        f*(H//f) x f*(W//f) crop, and the number of elements compared (sr_validation_error_*)."""
+        hr = np.asarray(hr)
+        if hr.ndim != 3:
+            raise ValueError("expected one (H, W, C) image")
+        h, w, c = hr.shape
+        err, n = C.c_double(), C.c_size_t()
+        if hr.dtype == np.uint8:
+            hr = np.ascontiguousarray(hr)
+            st = self._L.sr_validation_error_rgba8(self._ctx, hr.ctypes.data_as(C.POINTER(C.c_uint8)), c, h, w, int(bool(linear_loss)),
+                                                   C.byref(err), C.byref(n))
+        elif hr.dtype == np.float32:
+            if c != 3:
+                raise ValueError("an f32 HR image has 3 channels")
+            hr = np.ascontiguousarray(hr)
+            st = self._L.sr_validation_error_f32(self._ctx, hr.ctypes.data_as(C.POINTER(C.c_float)), h, w, int(bool(linear_loss)),
+                                                 C.byref(err), C.byref(n))
+        else:
+            raise ValueError("expected u8 or f32 pixels")
+        _lib.check(st, self._ctx)
+        return err.value, n.value
+
+    def validation_error_dev(self, hr, linear_loss: bool = False, out=None, stream=None):
+        """(H,W,3|4) u8 torch tensor on this engine's device -> a float64 tensor of one element holding err_sum, asynchronous on the
+        stream (sr_validation_error_rgba8_dev); the element count is 3 * f*(H//f) * f*(W//f)."""
+        import torch
+        assert hr.is_cuda and hr.dtype == torch.uint8 and hr.is_contiguous() and hr.dim() == 3
+        h, w, c = hr.shape
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=hr.device)
+        _lib.check(self._L.sr_validation_error_rgba8_dev(self._ctx, C.c_void_p(hr.data_ptr()), c, h, w, int(bool(linear_loss)),
+                                                         C.c_void_p(out.data_ptr()), self._stream_ptr(stream, hr.device)), self._ctx)
+        return out
+
+    def validation_nodes(self, h: int, w: int):
+        """The last validation call's `input` node (the pooled LR image, (h//f, w//f, 3)) and `output` node (the f32 network output,
+        (f*(h//f), f*(w//f), 3)), for an HR image of h x w (sr_read_validation_nodes)."""
+        f = self.factor
+        lr = np.empty((h // f, w // f, 3), dtype=np.float32)
+        out = np.empty((f * (h // f), f * (w // f), 3), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._L.sr_read_validation_nodes(self._ctx, lr.ctypes.data_as(fp), lr.size, out.ctypes.data_as(fp), out.size), self._ctx)
+        return lr, out
+
     # ---- introspection ------------------------------------------------------
     def read_feature(self, which: int, h: int, w: int) -> np.ndarray:
         """Post-activation node data of the last call: 0..3 = f, l1, l2, l3."""
@@ -400,6 +447,33 @@ def upscale_sharded_all(engines, bands, outs=None):
     else:
         _lib.check(L.sr_upscale_sharded_f32_all(ctxs, n, bp, hb, w, op), engines[0]._ctx)
     return outs
+
+
+def validation_psnr(engines, images, linear_loss: bool = False) -> float:
+    """The reference's validation PSNR (main.rs:236-246) of a set of HR images: -10 log10(sum err_i / sum n_i).  Images are dealt
+    round-robin over the engines (one host thread each); the sums are taken in image order, so the value does not depend on how many
+    engines there are.  A zero error is +inf."""
+    import math
+    from concurrent.futures import ThreadPoolExecutor
+    if isinstance(engines, Engine):
+        engines = [engines]
+    images = list(images)
+    if not engines or not images:
+        raise ValueError("validation_psnr needs at least one engine and one image")
+    res = [None] * len(images)
+
+    def run(k):
+        for i in range(k, len(images), len(engines)):
+            res[i] = engines[k].validation_error(images[i], linear_loss)
+
+    with ThreadPoolExecutor(max_workers=len(engines)) as pool:
+        for fut in [pool.submit(run, k) for k in range(len(engines))]:
+            fut.result()
+    err = n = 0.0
+    for e, m in res:
+        err += e
+        n += m
+    return math.inf if err == 0.0 else -10.0 * math.log10(err / n)
 
 
 class PinnedBuffer:
