@@ -297,6 +297,38 @@ int sr_validation_error_rgba8_dev(sr_ctx* ctx, const uint8_t* d_hr, int in_chann
  * node (the f32 network output, f times that size) of the most recent validation call, image 0.  Either pointer may be NULL. */
 int sr_read_validation_nodes(sr_ctx* ctx, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out);
 
+/* Backpropagation through the reference's training graph sr_net(f, Some((l2, linear_loss))) (network.rs:78-103; `g.backprop` inside
+ * Adam::optimise_from, main.rs:181-257), for a batch of n HR images of h x w -- SR_GRAPH_SR_NET contexts only (else SR_E_INVALID),
+ * h, w >= the context's factor f (else SR_E_INVALID):
+ *   input  = the validation pass's pooled LR batch (f32, not quantised; the top-left f floor(h/f) x f floor(w/f) crop of each image)
+ *   output = sr_net(f)(input), f32;  e = output - hr, or SrgbToLinear(output) - SrgbToLinear(hr) with linear_loss (the formula of
+ *            sr_validation_error_*, outside [0, 1] too); hr is byte / 255 (alpha dropped) or the f32 values as they are
+ *   err_sum = sum of e^2 over the batch: each difference in f32, the squares summed in f64 -- per image the same as
+ *             sr_validation_error_*; n_elems = n 3 f floor(h/f) f floor(w/f)
+ *   grad   = d/dp of  loss_scale sum e^2 + l2 sum p^2,  at p = `params` (NOT the context's inference weights: like
+ *            backprop(n, input, training_input, params), main.rs:240), sr_num_params_factor(f) floats in the .rsr segment order.
+ * UNPINNED (alumina's source is not at hand): MseLoss's normalisation is the caller's `loss_scale` (the Python helper passes
+ * 1 / n_elems, alumina's mean over flat_size_all as far as can be told); L2Regularisation is strength x sum p^2 over every parameter.
+ * Always exact f32 (v_mfma_f32_32x32x2_f32), whatever sr_set_precision says; no float atomics: the same bits on every run, context and
+ * device.  A wrong n_params is SR_E_PARAM_COUNT; with no HIP device present every backprop entry point returns SR_E_NO_DEVICE.  A batch
+ * that does not fit returns SR_E_NOMEM and leaves the context usable.  Synchronous, host memory (`hr` n x h x w x in_channels bytes, or
+ * n x h x w x 3 floats; `grad` n_params floats): */
+int sr_backprop_f32(sr_ctx* ctx, const float* params, size_t n_params, const float* hr, int n, int h, int w, int linear_loss,
+                    float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad);
+int sr_backprop_rgba8(sr_ctx* ctx, const float* params, size_t n_params, const uint8_t* hr, int in_channels, int n, int h, int w,
+                      int linear_loss, float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad);
+/* ... device memory, ordered on `stream` alone; no host synchronisation (but for the first call of a larger batch, which grows the
+ * context's workspace).  d_params and d_grad hold sr_num_params_factor(f) floats and, like d_err_sum (one double), must be 4-byte
+ * aligned: a misaligned pointer is SR_E_INVALID before any launch.  16 kernel launches per call (n + 15 when h is not a multiple of f). */
+int sr_backprop_rgba8_dev(sr_ctx* ctx, const float* d_params, const uint8_t* d_hr, int in_channels, int n, int h, int w, int linear_loss,
+                          float loss_scale, float l2, double* d_err_sum, float* d_grad, void* stream);
+/* One Adam step over n parameters in device memory (4-byte aligned), step = 1, 2, ... (UNPINNED: the textbook form, in f32):
+ *   m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;  p <- p - lr m^ / (sqrt(v^) + eps),
+ *   m^ = m / (1 - beta1^step), v^ = v / (1 - beta2^step).
+ * The reference's values: lr 2e-3, beta1 0.95, beta2 0.995, eps 1e-7 (main.rs:199-205).  One launch on `stream`. */
+int sr_adam_step_dev(sr_ctx* ctx, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr,
+                     float beta1, float beta2, float eps, void* stream);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

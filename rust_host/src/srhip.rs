@@ -87,6 +87,10 @@ extern "C" {
     pub fn sr_validation_error_f32(ctx: *mut SrCtx, hr: *const f32, h: c_int, w: c_int, linear_loss: c_int, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
     pub fn sr_validation_error_rgba8_dev(ctx: *mut SrCtx, d_hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, d_err_sum: *mut f64, stream: *mut c_void) -> c_int;
     pub fn sr_read_validation_nodes(ctx: *mut SrCtx, lr_out: *mut f32, cap_lr: usize, out_out: *mut f32, cap_out: usize) -> c_int;
+    pub fn sr_backprop_f32(ctx: *mut SrCtx, params: *const f32, n_params: usize, hr: *const f32, n: c_int, h: c_int, w: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, err_sum: *mut f64, n_elems: *mut usize, grad: *mut f32) -> c_int;
+    pub fn sr_backprop_rgba8(ctx: *mut SrCtx, params: *const f32, n_params: usize, hr: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, err_sum: *mut f64, n_elems: *mut usize, grad: *mut f32) -> c_int;
+    pub fn sr_backprop_rgba8_dev(ctx: *mut SrCtx, d_params: *const f32, d_hr: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, d_err_sum: *mut f64, d_grad: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_adam_step_dev(ctx: *mut SrCtx, d_params: *mut f32, d_m: *mut f32, d_v: *mut f32, d_grad: *const f32, n: usize, step: c_int, lr: f32, beta1: f32, beta2: f32, eps: f32, stream: *mut c_void) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

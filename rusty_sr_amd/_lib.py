@@ -68,6 +68,10 @@ SYMBOLS = {
     "sr_validation_error_f32": (_i, [_vp, _fp, _i, _i, _i, _dp, C.POINTER(_sz)]),
     "sr_validation_error_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_read_validation_nodes": (_i, [_vp, _fp, _sz, _fp, _sz]),
+    "sr_backprop_f32": (_i, [_vp, _fp, _sz, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _dp, C.POINTER(_sz), _fp]),
+    "sr_backprop_rgba8": (_i, [_vp, _fp, _sz, _u8p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _dp, C.POINTER(_sz), _fp]),
+    "sr_backprop_rgba8_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "sr_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -1,0 +1,169 @@
+// sr_grad.cpp -- host side of backpropagation through the reference's training graph (network.rs:78-103, `g.backprop` in
+// Adam::optimise_from, main.rs:181-257) and of one Adam step (include/srhip.h sr_backprop_*, sr_adam_step_dev).  Kernels: sr_grad.hip;
+// the pool: sr_valid.hip.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "sr_internal.h"
+
+namespace {
+
+bool no_device() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return n <= 0;
+}
+
+void free_buf(void*& p, size_t& cap) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
+
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }
+
+// Arguments of every backprop entry point, checked before the GPU is touched.
+int check_args(sr_ctx* c, const void* params, const void* hr, bool hr_u8, int ch, int n, int h, int w, const void* grad) {
+    if (!c || !params || !hr || !grad) return SR_E_INVALID;
+    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    if (hr_u8 ? (ch != 3 && ch != 4) : ch != 3) return SR_E_INVALID;
+    if (n < 1 || h < c->factor || w < c->factor) return SR_E_INVALID;  // not one f x f pooling block
+    return SR_OK;
+}
+
+size_t lr_floats(int f, int n, int h, int w) { return (size_t)n * (h / f) * (w / f) * 3; }
+
+// Pool, then the backward pass, on device buffers, queued on s.  The context's device is current; the workspace is grown here.
+int run_backprop(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8, int ch, int n, int h, int w, bool linear, float loss_scale,
+                 float l2, void* d_err, float* d_grad, hipStream_t s, double** result_slot) {
+    const int f = c->factor, OH = h / f, OW = w / f;
+    const size_t x_bytes = round256(lr_floats(f, n, h, w) * sizeof(float));
+    int rc = sr_valid_ensure_table(c);
+    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_gws, &c->gws_cap, x_bytes + sr_grad_workspace_bytes(f, n, OH, OW));
+    if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
+        free_buf(c->d_gws, c->gws_cap);
+        free_buf(c->d_gin, c->gin_cap);
+        return rc;
+    }
+    float* x = (float*)c->d_gws;
+    const float* tab_lin = c->d_vtab + 256;
+    if (h % f == 0) {  // the batch is one image of n h rows
+        HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, n * OH, OW, x, tab_lin, s));
+    } else {  // each image drops its own last h % f rows
+        const size_t img_bytes = (size_t)h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
+        for (int b = 0; b < n; ++b)
+            HIPCHK(c, sr_launch_valid_pool(f, (const uint8_t*)d_hr + b * img_bytes, hr_u8, ch, w, OH, OW, x + (size_t)b * OH * OW * 3,
+                                           tab_lin, s));
+    }
+    sr_grad_plan p;
+    p.factor = f; p.n = n; p.H = OH; p.W = OW;
+    p.params = d_params;
+    p.x = x;
+    p.hr = d_hr; p.hr_u8 = hr_u8; p.hr_ch = ch; p.hr_h = h; p.hr_w = w;
+    p.tab = c->d_vtab;
+    p.linear = linear; p.loss_scale = loss_scale; p.l2 = l2;
+    p.ws = (float*)((char*)c->d_gws + x_bytes);
+    p.err_out = d_err;
+    p.grad = d_grad;
+    if (result_slot) *result_slot = sr_grad_result_slot(p);
+    HIPCHK(c, sr_launch_grad(p, s));
+    return SR_OK;
+}
+
+// The host-pointer calls: upload parameters and HR batch, run, download err_sum and the gradient, on the context's own stream; synchronous.
+int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* hr, bool hr_u8, int ch, int n, int h, int w, int linear,
+                  float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad) {
+    if (!c && no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    int rc = check_args(c, params, hr, hr_u8, ch, n, h, w, grad);
+    if (rc != SR_OK) return rc;
+    if (!err_sum || !n_elems) return SR_E_INVALID;
+    const int np = sr_num_params_factor(c->factor);
+    if (np < 0 || n_params != (size_t)np) return SR_E_PARAM_COUNT;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = sr_ensure_streams(c, false);
+    if (rc != SR_OK) return rc;
+    const size_t p_bytes = round256((size_t)np * sizeof(float));
+    const size_t hr_bytes = (size_t)n * h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
+    rc = sr_ensure_buf(c, &c->d_gin, &c->gin_cap, 2 * p_bytes + round256(hr_bytes));
+    if (rc != SR_OK) {
+        free_buf(c->d_gin, c->gin_cap);
+        free_buf(c->d_gws, c->gws_cap);
+        return rc;
+    }
+    float* d_params = (float*)c->d_gin;
+    float* d_grad = (float*)((char*)c->d_gin + p_bytes);
+    void* d_hr = (char*)c->d_gin + 2 * p_bytes;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_params, params, (size_t)np * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_hr, hr, hr_bytes, hipMemcpyHostToDevice, s));
+    double* slot = nullptr;
+    rc = run_backprop(c, d_params, d_hr, hr_u8, ch, n, h, w, linear != 0, loss_scale, l2, nullptr, d_grad, s, &slot);
+    double sum = 0.0;
+    hipError_t e1 = hipSuccess;
+    if (rc == SR_OK) {
+        e1 = hipMemcpyAsync(&sum, slot, sizeof sum, hipMemcpyDeviceToHost, s);
+        if (e1 == hipSuccess) e1 = hipMemcpyAsync(grad, d_grad, (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, e1);
+    HIPCHK(c, e2);
+    *err_sum = sum;
+    *n_elems = (size_t)n * 3 * ((size_t)c->factor * (h / c->factor)) * ((size_t)c->factor * (w / c->factor));
+    return SR_OK;
+}
+
+}  // namespace
+
+void sr_grad_release(sr_ctx* c) {
+    free_buf(c->d_gws, c->gws_cap);
+    free_buf(c->d_gin, c->gin_cap);
+}
+
+extern "C" {
+
+int sr_backprop_f32(sr_ctx* c, const float* params, size_t n_params, const float* hr, int n, int h, int w, int linear_loss, float loss_scale,
+                    float l2, double* err_sum, size_t* n_elems, float* grad) {
+    return backprop_host(c, params, n_params, hr, false, 3, n, h, w, linear_loss, loss_scale, l2, err_sum, n_elems, grad);
+}
+
+int sr_backprop_rgba8(sr_ctx* c, const float* params, size_t n_params, const uint8_t* hr, int in_channels, int n, int h, int w, int linear_loss,
+                      float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad) {
+    return backprop_host(c, params, n_params, hr, true, in_channels, n, h, w, linear_loss, loss_scale, l2, err_sum, n_elems, grad);
+}
+
+int sr_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_hr, int in_channels, int n, int h, int w, int linear_loss,
+                          float loss_scale, float l2, double* d_err_sum, float* d_grad, void* stream) {
+    if (!c && no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    const int rc = check_args(c, d_params, d_hr, true, in_channels, n, h, w, d_grad);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_backprop(c, d_params, d_hr, true, in_channels, n, h, w, linear_loss != 0, loss_scale, l2, d_err_sum, d_grad,
+                        (hipStream_t)stream, nullptr);
+}
+
+int sr_adam_step_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr, float beta1,
+                     float beta2, float eps, void* stream) {
+    if (!c && no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    if (!c || !d_params || !d_m || !d_v || !d_grad || n == 0 || step < 1) return SR_E_INVALID;
+    if (!sr_dword_aligned(d_params) || !sr_dword_aligned(d_m) || !sr_dword_aligned(d_v) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
+    // bias corrections 1 - beta^t, in f32
+    const float bc1 = 1.0f - std::pow(beta1, (float)step), bc2 = 1.0f - std::pow(beta2, (float)step);
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, sr_launch_grad_adam(d_params, d_m, d_v, d_grad, n, lr, beta1, beta2, eps, bc1, bc2, (hipStream_t)stream));
+    return SR_OK;
+}
+
+}  // extern "C"

@@ -117,6 +117,9 @@ struct sr_ctx {
     void* d_vpart = nullptr; size_t vpart_cap = 0;  // the loss kernel's f64 partials, then the host-pointer calls' result
     float* d_vtab = nullptr;                        // 512 floats: byte / 255, then SrgbToLinear of those (sr_valid.cpp)
     int vnode_h = 0, vnode_w = 0;                   // LR size of the last validation call (0: none yet)
+    // ---- backpropagation (sr_grad.cpp): grown on demand, freed by sr_destroy
+    void* d_gws = nullptr; size_t gws_cap = 0;      // saved forward state, gradients of the nodes, partials (sr_grad_workspace_bytes)
+    void* d_gin = nullptr; size_t gin_cap = 0;      // host-pointer calls: params, HR batch, pooled LR batch, gradient
 };
 
 inline void sr_plan_clear(sr_ctx* c) {
@@ -201,3 +204,27 @@ hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch
 // sum over the HC x WC crop of (out - hr)^2 (linear: of SrgbToLinear of both) -> one double at d_result (4-byte aligned)
 hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,
                                 double* d_partial, void* d_result, hipStream_t s);
+
+// ---- backpropagation (sr_grad.hip kernels, sr_grad.cpp host side)
+void sr_grad_release(sr_ctx* c);  // sr_grad.cpp: free the backprop buffers (called by sr_destroy)
+// Everything sr_launch_grad reads and writes for one call: a batch of n HR images pooled to n LR images of H x W (already at x).
+struct sr_grad_plan {
+    int factor = 3, n = 0, H = 0, W = 0;
+    const float* params = nullptr;  // the parameters the gradient is taken at, sr_num_params_factor(factor) floats
+    const float* x = nullptr;       // the pooled LR batch, n x H x W x 3 f32
+    const void* hr = nullptr;       // the HR batch, n images of hr_h x hr_w x hr_ch (u8) or x 3 (f32)
+    bool hr_u8 = true;
+    int hr_ch = 3, hr_h = 0, hr_w = 0;
+    const float* tab = nullptr;     // the validation pass's 512-float table (sr_valid.cpp)
+    bool linear = false;
+    float loss_scale = 1.0f, l2 = 0.0f;
+    float* ws = nullptr;            // sr_grad_workspace_bytes(factor, n, H, W), 256-byte aligned
+    void* err_out = nullptr;        // sum of squared errors, one double at a 4-byte aligned address (nullptr: sr_grad_result_slot)
+    float* grad = nullptr;          // the gradient, .rsr order
+};
+size_t sr_grad_workspace_bytes(int factor, int n, int H, int W);
+double* sr_grad_result_slot(const sr_grad_plan& p);  // the workspace's own slot for err_sum
+hipError_t sr_launch_grad(const sr_grad_plan& p, hipStream_t s);
+hipError_t sr_launch_grad_adam(float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, float lr, float beta1, float beta2,
+                               float eps, float bc1, float bc2, hipStream_t s);
+int sr_valid_ensure_table(sr_ctx* c);  // sr_valid.cpp: the 512-float table behind d_vtab, uploaded on first use

@@ -123,6 +123,10 @@ int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w,
 
 }  // namespace
 
+int sr_valid_ensure_table(sr_ctx* c) {
+    return ensure_table(c);
+}
+
 void sr_valid_release(sr_ctx* c) {
     free_buf(c->d_vhr, c->vhr_cap);
     free_buf(c->d_vlr, c->vlr_cap);

@@ -289,6 +289,74 @@ class Engine:
         _lib.check(self._L.sr_read_validation_nodes(self._ctx, lr.ctypes.data_as(fp), lr.size, out.ctypes.data_as(fp), out.size), self._ctx)
         return lr, out
 
+    # ---- training: backpropagation of the training graph (reference main.rs:181-257, network.rs:78-103) and one Adam step ----
+    def num_params(self) -> int:
+        return self._L.sr_num_params_factor(self.factor)
+
+    def backprop(self, hr: np.ndarray, params, linear_loss: bool = False, loss_scale: Optional[float] = None, l2: float = 0.0):
+        """HR batch (n,H,W,3|4) u8 (byte / 255, alpha dropped) or (n,H,W,3) f32 -> (err_sum, n_elems, grad): the squared error of
+        sr_net(f) on the pooled batch against its f*(H//f) x f*(W//f) crop (of SrgbToLinear of both with linear_loss) and the gradient
+        of loss_scale * err_sum + l2 * sum(p^2) at `params` (sr_backprop_*).  loss_scale None: 1 / n_elems (MseLoss's mean; UNPINNED)."""
+        hr = np.asarray(hr)
+        if hr.ndim == 3:
+            hr = hr[None]
+        if hr.ndim != 4:
+            raise ValueError("expected (n, H, W, C) images")
+        n, h, w, c = hr.shape
+        f = self.factor
+        if loss_scale is None:
+            loss_scale = 1.0 / (n * 3 * (f * (h // f)) * (f * (w // f))) if h >= f and w >= f else 1.0
+        p = np.ascontiguousarray(params, dtype=np.float32)
+        grad = np.empty(max(self.num_params(), 1), dtype=np.float32)
+        err, ne = C.c_double(), C.c_size_t()
+        fp = C.POINTER(C.c_float)
+        if hr.dtype == np.uint8:
+            hr = np.ascontiguousarray(hr)
+            st = self._L.sr_backprop_rgba8(self._ctx, p.ctypes.data_as(fp), p.size, hr.ctypes.data_as(C.POINTER(C.c_uint8)), c, n, h, w,
+                                           int(bool(linear_loss)), float(loss_scale), float(l2), C.byref(err), C.byref(ne),
+                                           grad.ctypes.data_as(fp))
+        elif hr.dtype == np.float32:
+            if c != 3:
+                raise ValueError("an f32 HR batch has 3 channels")
+            hr = np.ascontiguousarray(hr)
+            st = self._L.sr_backprop_f32(self._ctx, p.ctypes.data_as(fp), p.size, hr.ctypes.data_as(fp), n, h, w, int(bool(linear_loss)),
+                                         float(loss_scale), float(l2), C.byref(err), C.byref(ne), grad.ctypes.data_as(fp))
+        else:
+            raise ValueError("expected u8 or f32 pixels")
+        _lib.check(st, self._ctx)
+        return err.value, ne.value, grad
+
+    def backprop_dev(self, hr, params, linear_loss: bool = False, loss_scale: Optional[float] = None, l2: float = 0.0,
+                     grad=None, err=None, stream=None):
+        """(n,H,W,3|4) u8 torch tensor and an f32 parameter tensor on this engine's device -> (err, grad): a float64 tensor of one
+        element (err_sum) and the f32 gradient, asynchronous on the stream (sr_backprop_rgba8_dev)."""
+        import torch
+        assert hr.is_cuda and hr.dtype == torch.uint8 and hr.is_contiguous() and hr.dim() == 4
+        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == self.num_params()
+        n, h, w, c = hr.shape
+        f = self.factor
+        if loss_scale is None:
+            loss_scale = 1.0 / (n * 3 * (f * (h // f)) * (f * (w // f))) if h >= f and w >= f else 1.0
+        if grad is None:
+            grad = torch.empty_like(params)
+        if err is None:
+            err = torch.empty(1, dtype=torch.float64, device=hr.device)
+        _lib.check(self._L.sr_backprop_rgba8_dev(self._ctx, C.c_void_p(params.data_ptr()), C.c_void_p(hr.data_ptr()), c, n, h, w,
+                                                 int(bool(linear_loss)), float(loss_scale), float(l2), C.c_void_p(err.data_ptr()),
+                                                 C.c_void_p(grad.data_ptr()), self._stream_ptr(stream, hr.device)), self._ctx)
+        return err, grad
+
+    def adam_step_dev(self, params, m, v, grad, step: int, lr: float = 2e-3, beta1: float = 0.95, beta2: float = 0.995,
+                      eps: float = 1e-7, stream=None):
+        """One Adam step in place on f32 torch tensors of one size (sr_adam_step_dev; defaults: the reference's, main.rs:199-205)."""
+        import torch
+        for t in (params, m, v, grad):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == params.numel()
+        vp = C.c_void_p
+        _lib.check(self._L.sr_adam_step_dev(self._ctx, vp(params.data_ptr()), vp(m.data_ptr()), vp(v.data_ptr()), vp(grad.data_ptr()),
+                                            params.numel(), int(step), float(lr), float(beta1), float(beta2), float(eps),
+                                            self._stream_ptr(stream, params.device)), self._ctx)
+
     # ---- introspection ------------------------------------------------------
     def read_feature(self, which: int, h: int, w: int) -> np.ndarray:
         """Post-activation node data of the last call: 0..3 = f, l1, l2, l3."""
@@ -474,6 +542,48 @@ def validation_psnr(engines, images, linear_loss: bool = False) -> float:
         err += e
         n += m
     return math.inf if err == 0.0 else -10.0 * math.log10(err / n)
+
+
+class Trainer:
+    """Minibatch Adam on the GPU (the optimisation loop of the reference's `train`, main.rs:181-257, without its data supply): parameters,
+    first and second moments live on the engine's device.  step(hr_batch) -> err_sum of that batch at the parameters before the step."""
+
+    def __init__(self, engine: Engine, start_params, linear_loss: bool = False, l2: float = 1e-6, lr: float = 2e-3,
+                 beta1: float = 0.95, beta2: float = 0.995, eps: float = 1e-7):
+        import torch
+        p = np.ascontiguousarray(start_params, dtype=np.float32)
+        if p.size != engine.num_params():
+            raise ValueError(f"expected {engine.num_params()} parameters, got {p.size}")
+        self.engine = engine
+        self.device = torch.device("cuda", engine.device)
+        self._p = torch.from_numpy(p.copy()).to(self.device)
+        self._m = torch.zeros_like(self._p)
+        self._v = torch.zeros_like(self._p)
+        self._g = torch.empty_like(self._p)
+        self._err = torch.empty(1, dtype=torch.float64, device=self.device)
+        self.linear_loss, self.l2, self.lr, self.beta1, self.beta2, self.eps = linear_loss, l2, lr, beta1, beta2, eps
+        self.steps = 0
+
+    def step(self, hr_batch) -> float:
+        """One backprop (loss_scale 1 / n_elems) and one Adam step.  hr_batch: (n,H,W,3|4) u8, numpy or a torch tensor."""
+        import torch
+        hr = hr_batch if isinstance(hr_batch, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(hr_batch))
+        hr = hr.to(self.device).contiguous()
+        if hr.dim() == 3:
+            hr = hr[None]
+        self.engine.backprop_dev(hr, self._p, self.linear_loss, None, self.l2, grad=self._g, err=self._err)
+        self.steps += 1
+        self.engine.adam_step_dev(self._p, self._m, self._v, self._g, self.steps, self.lr, self.beta1, self.beta2, self.eps)
+        return float(self._err.item())
+
+    def params(self) -> np.ndarray:
+        return self._p.cpu().numpy()
+
+    def save(self, path: str):
+        """Write the parameters as a .rsr file (bytevec, as the reference's train writes them, main.rs:213)."""
+        from . import rsr
+        with open(path, "wb") as f:
+            f.write(rsr.encode(self.params()))
 
 
 class PinnedBuffer:
