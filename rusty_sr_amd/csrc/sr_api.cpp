@@ -114,6 +114,33 @@ void pack_steps(std::vector<float>& dst, const float* w, int ks, int ntn, bool s
             }
 }
 
+// Stage 1's 5x5 weights for the exact mode's Winograd form (sr_kernels.hip half_steps_wino): per 16-channel half, operand groups
+// g = (kernel row ky, position k, 8-channel group rr) = 14 ky + 2 k + rr, four to a 4 KB chunk (the last chunk of a half two):
+//   [q = g % 4][h 2][lane 32][4]    channel = 16 half + 8 rr + 4 h + e
+// Position k < 4 is position k of chunk A (taps 0, 1, 2 of the row), k = 4..6 position k - 3 of chunk B (a zero tap, then taps 3, 4);
+// V = (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2), computed in double and rounded once.
+void pack_steps_wino(std::vector<float>& dst, const float* w) {
+    constexpr int kGroups = 5 * 7 * 2, kSteps = (kGroups + 3) / 4;
+    for (int half = 0; half < 2; ++half) {
+        const size_t base = dst.size();
+        dst.resize(base + (size_t)kSteps * kChunk, 0.0f);
+        for (int g = 0; g < kGroups; ++g) {
+            const int rr = g & 1, k = (g >> 1) % 7, ky = (g >> 1) / 7;
+            float* chunk = dst.data() + base + (size_t)(g / 4) * kChunk + (g % 4) * 256;
+            for (int j = 0; j < 32; ++j)
+                for (int h = 0; h < 2; ++h)
+                    for (int e = 0; e < 4; ++e) {
+                        const int c = 16 * half + 8 * rr + 4 * h + e;
+                        auto tap = [&](int kx) { return (double)w[((size_t)j * 25 + ky * 5 + kx) * 32 + c]; };
+                        const double g0 = k < 4 ? tap(0) : 0.0, g1 = k < 4 ? tap(1) : tap(3), g2 = k < 4 ? tap(2) : tap(4);
+                        const int pos = k < 4 ? k : k - 3;
+                        const double v = pos == 0 ? g0 : pos == 1 ? (g0 + g1 + g2) * 0.5 : pos == 2 ? (g0 - g1 + g2) * 0.5 : g2;
+                        chunk[(h * 32 + j) * 4 + e] = (float)v;
+                    }
+        }
+    }
+}
+
 // Split-half weight chunks of stages 1-3 for the 16x16x32 step loop (sr_kernels.hip half_steps_h16): one 4 KB chunk per STEP,
 //   [hi | lo][output-channel half 2][lane 64][8 halves],  lane = 16 g + n:  output channel 16 ch + n,  K block g: taps[g >> 1],
 //   input channels 16 half + 8 (g & 1) + e  -- a step's K = 32 is two taps x the half's 16 channels.
@@ -310,7 +337,7 @@ int sr_create_graph(sr_ctx** out, int graph, const float* params, size_t n_param
     c->graph = graph;
     c->factor = factor;
     // experiment switches: the environment gives the defaults, read here once; sr_set_experiment changes them
-    static const char* const kSwitch[12][2] = {{"th", "SRHIP_TH"}, {"pipe", "SRHIP_PIPE"}, {"bw", "SRHIP_BW"}, {"tail", "SRHIP_TAIL"},
+    static const char* const kSwitch[13][2] = {{"wino", "SRHIP_WINO"}, {"th", "SRHIP_TH"}, {"pipe", "SRHIP_PIPE"}, {"bw", "SRHIP_BW"}, {"tail", "SRHIP_TAIL"},
                                                {"bands", "SRHIP_BANDS"}, {"geo", "SRHIP_GEO"}, {"rows", "SRHIP_ROWS"}, {"fork", "SRHIP_FORK"},
                                                {"forkshare", "SRHIP_FORKSHARE"}, {"forkmin", "SRHIP_FORKMIN"}, {"forktune", "SRHIP_FORKTUNE"}, {"halo", "SRHIP_HALO"}};
     for (const auto& sw : kSwitch)
@@ -390,6 +417,8 @@ int sr_create_graph(sr_ctx** out, int graph, const float* params, size_t n_param
             else pack_lin(w, factor);
             off[4] = push(w);
         }
+        w.clear(); pack_steps_wino(w, params + L.conv1);
+        c->off_wino1 = push(w);
         const size_t boff[4] = {L.f_bias, L.l_bias[0], L.l_bias[1], L.l_bias[2]};
         const size_t aoff[4] = {L.f_activ, L.l_activ[0], L.l_activ[1], L.l_activ[2]};
         for (int s = 0; s < 4; ++s) c->off_bias[s] = push(vec32(boff[s], 32));
@@ -512,6 +541,8 @@ int sr_set_experiment(sr_ctx* c, const char* key, const char* value) {
         sr_fork_tune_clear(c);
     } else if (!strcmp(key, "halo")) {  // sharded calls: "" / "input": 7 input rows per neighbour, the overlap recomputed; "layers": feature rows after every stage
         c->layer_halos = !strcmp(v, "layers");
+    } else if (!strcmp(key, "wino")) {  // exact mode, stage 1: "" / "1": Winograd F(2,3) rows, "0": the direct form (same bar, other last bits)
+        c->wino = strcmp(v, "0") != 0;
     } else if (!strcmp(key, "bw")) {   // tile-order column-block width in tiles; "" / negative: automatic, 0: plain row-major
         c->env_bw = *v ? atoi(v) : -1;
     } else {
@@ -696,6 +727,10 @@ int StackJob::prepare() {
         //  conv0 and the first form run one class.
         const long tiles8 = (long)n * tiles_x * ((rows + 7) / 8);
         // (the last stage of factor 4 in the split-half mode exists with 4-row tiles only: two N-tiles of accumulators, sr_kernels.hip kBigTiles)
+        // (the exact mode's stage 1 in its Winograd form: a 4-row tile half-fills the pair dimension, 7 MFMAs per 16 pixels where the direct form
+        // issues 5, so a small launch keeps 8-row tiles instead of switching to 4-row ones -- 256x256 stage 1 0.0488 ms with 4-row tiles, 0.0314
+        // with 8-row ones, direct 0.0368; 360x640 0.1515 / 0.0853 / 0.1080: profiles/r7_ab_wino_stage1.txt.  Tile plans change no bit.)
+        const bool wino8 = st == 1 && c->precision == SR_PRECISION_F32 && c->wino;
         const int forced = (st == 4 && c->factor == 4 && c->precision == SR_PRECISION_SPLIT_F16) ? 4 : c->env_th[st];
         const bool small_launch = tiles8 < 2L * resident;
         const bool split = c->precision == SR_PRECISION_SPLIT_F16;
@@ -706,7 +741,7 @@ int StackJob::prepare() {
         const bool one_small_round = small_launch && (long)n * tiles_x * ((rows + 3) / 4) <= resident;
         l.pipe = st > 0 && c->env_pipe != 0 && (c->env_pipe == 2 || !small_launch || split || (st >= 2 && one_small_round));
         l.ty8 = (rows + 7) / 8; l.ty4 = 0;
-        if (forced == 4 || (!forced && small_launch && (!split || tiles8 < cus))) {
+        if (forced == 4 || (!forced && small_launch && !wino8 && (!split || tiles8 < cus))) {
             l.ty8 = 0; l.ty4 = (rows + 3) / 4;
         } else if (!forced && l.pipe && !small_launch) {
             const double rounds = (double)tiles8 / resident;
@@ -798,15 +833,16 @@ int StackJob::launch(int st) const {
         case 3: a.src[0] = f; a.src[1] = l1; a.src[2] = l2; a.dst = l3; break;
         case 4: a.src[0] = l1; a.src[1] = l2; a.src[2] = l3; a.img = d_img; a.out = d_out; break;
     }
-    a.wpack = P + (c->precision ? c->off_wh[st] : c->off_w[st]); a.bias = P + c->off_bias[st];
+    const bool wino = st == 1 && c->precision == SR_PRECISION_F32 && c->wino;
+    a.wpack = P + (c->precision ? c->off_wh[st] : wino ? c->off_wino1 : c->off_w[st]); a.bias = P + c->off_bias[st];
     a.beta = st < 4 ? P + c->off_beta[st] : nullptr;
     a.H = H; a.W = W; a.img_ch = img_ch;
     a.y_begin = y0; a.y_end = y1; a.tiles_x = tiles_x;
     a.n_img = n; a.queue = ws->d_queue + st * 8; a.domain = c->d_domain;
     a.grid[0] = make_tile_grid(8, y0, l.ty8, tiles_x, n, bw);
     a.grid[1] = make_tile_grid(4, y0 + 8 * l.ty8, l.ty4, tiles_x, n, bw);
-    if (l.pipe) HIPCHK(c, sr_launch_stage_pipe(st, c->factor, a, c->precision, l.grid, img_u8, out_u8, s));
-    else HIPCHK(c, sr_launch_stage(st, c->factor, a, l.th, c->precision, l.grid, img_u8, out_u8, s));
+    if (l.pipe) HIPCHK(c, sr_launch_stage_pipe(st, c->factor, a, c->precision, l.grid, img_u8, out_u8, wino, s));
+    else HIPCHK(c, sr_launch_stage(st, c->factor, a, l.th, c->precision, l.grid, img_u8, out_u8, wino, s));
     return SR_OK;
 }
 

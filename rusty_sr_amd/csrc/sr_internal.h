@@ -18,6 +18,8 @@ struct sr_ctx {
     float* d_params = nullptr;  // all packed parameters, one allocation
     void* d_qtab = nullptr;     // bilinear_net / downsample_net: data_to_img(LinearToSrgb(l)) as a step table (sr_aux.hip)
     size_t off_w0 = 0, off_w0h = 0, off_w[5] = {0}, off_wh[5] = {0}, off_bias[5] = {0}, off_beta[5] = {0};
+    size_t off_wino1 = 0;  // stage 1's weights as Winograd F(2,3) chunks (sr_api.cpp pack_steps_wino)
+    bool wino = true;      // exact mode, stage 1: Winograd F(2,3) rows ("wino" switch; "0": the direct form -- last bits differ)
     int precision = 0;  // SR_PRECISION_F32 / SR_PRECISION_SPLIT_F16
     // Domain of the split-half mode (include/srhip.h, sr_set_precision): values are carried as pairs of HALVES, so every weight, input
     // and activation must be finite and below 65504 in magnitude.  Weights are checked once (split_ok); inputs and activations by the
@@ -55,7 +57,7 @@ struct sr_ctx {
     double total_ms = 0, stage_ms[5] = {0}, h2d_ms = 0, d2h_ms = 0;
     int last_h = 0, last_w = 0;
     int last_hip = 0;
-    // experiment switches, read once at sr_create (none changes results): SRHIP_TH, SRHIP_PIPE, SRHIP_BW, SRHIP_TAIL
+    // experiment switches, read once at sr_create (none changes results but "wino", see wino above): SRHIP_TH, SRHIP_PIPE, SRHIP_BW, SRHIP_TAIL
     int env_th[5] = {0, 0, 0, 0, 0};  // 0: automatic
     int env_pipe = 1;                 // 0: first form everywhere, 1: pipe form except for small launches, 2: pipe form everywhere
     int env_bw = -1;                  // tile-order column-block width in tiles (-1: automatic)

@@ -770,6 +770,98 @@ __device__ __forceinline__ void half_steps_f32(Acc& acc, const char* hb, const c
     }
 }
 
+// WINO (exact mode, stage 1: the 5x5 f-convolution alone): every kernel row as row-direction Winograd / Toom-Cook F(2,3) on the points
+// 0, 1, -1, inf.  For an output pair (x, x + 1) and a 3-tap row g over the inputs d0..d3:
+//     U = (d0 - d2, d1 + d2, d2 - d1, d1 - d3),  V = (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2),  m_p += U_p V_p,
+//     y0 = m0 + m1 + m2,  y1 = m1 - m2 - m3.
+// A 5-tap row is two such chunks on the same four accumulator sets m_p: chunk A = taps (-2, -1, 0) on d = x - 2 .. x + 1, chunk B =
+// taps (0-weight, +1, +2) on d = x .. x + 3, whose V0 is zero and whose position 0 is therefore not issued.  The zero tap comes FIRST:
+// every position of every chunk then reads only pixels inside the receptive field of both outputs it feeds, so a non-finite pixel
+// reaches exactly the outputs it reaches in the direct form (a trailing zero tap would multiply the pixel x + 3 into y0 as 0 x NaN).
+// 7 products per row and pair where the direct form has 10.  The transformed weights are computed on the host in double and rounded
+// once (sr_api.cpp pack_steps_wino).
+// M = 32 PAIRS: lane (h, i) of the A operand is pair i % 16 of tile row i / 16 of the wave's two rows, so one v_mfma_f32_32x32x2_f32
+// covers both rows (a 4-row tile has one row per wave: lanes 16-31 repeat lanes 0-15 and their results are dropped).  A pair's six
+// input pixels lie inside the tile's existing halo.  An operand group = one position x 8 channels of the half: two ds_read_b128 of the
+// pair's pixels, one v_pk_add_f32 pair (U), one weight read, four MFMAs.  Group order inside a half: kernel row, chunk, position, 8-channel
+// group -- the same in both kernel forms and both tile classes, so every form stays bit-identical to the others.  70 groups per half =
+// 18 steps of four (the last of two), one 4 KB chunk each.
+constexpr int kWinoGroups = 5 * 7 * 2;
+constexpr int kWinoSteps = (kWinoGroups + 3) / 4;
+// position k of a kernel row (0-3: chunk A, 4-6: chunk B positions 1-3): its accumulator set and the tile columns (from the pair's first
+// halo column) of the two pixels whose sum or difference is U
+constexpr int wino_acc(int k) { return k < 4 ? k : k - 3; }
+constexpr int wino_ca(int k) { return k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 2 : k == 3 ? 1 : k == 4 ? 3 : k == 5 ? 4 : 3; }
+constexpr int wino_cb(int k) { return k == 0 ? 2 : k == 1 ? 2 : k == 2 ? 1 : k == 3 ? 3 : k == 4 ? 4 : k == 5 ? 3 : 5; }
+constexpr bool wino_add(int k) { return k == 1 || k == 4; }
+
+// U of one position for four channels: TWO v_pk_add_f32 (sums or differences).  Written as C on f32x4 values whose elements then feed the
+// MFMAs one by one, the compiler emits four scalar v_add / v_sub instead -- one vector instruction per MFMA, each paid in f32-MFMA time.
+// The compiler's hazard recognizer does not look into an asm statement: an MFMA that reads a VGPR a VALU instruction has just written needs
+// 2 wait states in between, so the statement supplies them itself (s_nop 1 behind the second add; the first add's result has 3).
+template <bool ADD>
+__device__ __forceinline__ void wino_u4(f32x2 x0, f32x2 y0, f32x2 x1, f32x2 y1, f32x2& u0, f32x2& u1) {
+    if constexpr (ADD)
+        asm("v_pk_add_f32 %0, %2, %3\n\tv_pk_add_f32 %1, %4, %5\n\ts_nop 1"
+            : "=&v"(u0), "=&v"(u1) : "v"(x0), "v"(y0), "v"(x1), "v"(y1));
+    else
+        asm("v_pk_add_f32 %0, %2, %3 neg_lo:[0,1] neg_hi:[0,1]\n\tv_pk_add_f32 %1, %4, %5 neg_lo:[0,1] neg_hi:[0,1]\n\ts_nop 1"
+            : "=&v"(u0), "=&v"(u1) : "v"(x0), "v"(y0), "v"(x1), "v"(y1));
+}
+
+template <int TWH, int PS, int T, typename Stream>
+__device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[4], const char* hb, const char* ring, Stream& sm, int wave, int lane) {
+    static_assert(TWH >= kTW + 4, "a pair reads six pixels from its first halo column on");
+    const int i = lane & 31, h = lane >> 5;
+    const int wlane = (h * 32 + i) * 16;
+    const int row = wave * T + (T == 2 ? i >> 4 : 0);
+    const char* abase = hb + h * PS + (row * TWH + 2 * (i & 15)) * 16;
+    struct Ops { f32x4 x, y, b; };
+    auto load = [&](Ops& o, int g, int sl) {  // operand group g = (kernel row, position, 8-channel group rr)
+        const int rr = g & 1, k = (g >> 1) % 7, ky = (g >> 1) / 7;
+        const char* ab = abase + rr * 2 * PS + ky * TWH * 16;
+        o.b = *(const f32x4*)(ring + sl * 4096 + wlane + (g & 3) * 1024);
+        o.x = *(const f32x4*)(ab + wino_ca(k) * 16);
+        o.y = *(const f32x4*)(ab + wino_cb(k) * 16);
+    };
+    auto mfma = [&](const Ops& o, int g) {
+        const int k = (g >> 1) % 7;
+        const f32x2 x0 = {o.x[0], o.x[1]}, x1 = {o.x[2], o.x[3]}, y0 = {o.y[0], o.y[1]}, y1 = {o.y[2], o.y[3]};
+        f32x2 u0, u1;
+        if (wino_add(k)) wino_u4<true>(x0, y0, x1, y1, u0, u1);
+        else wino_u4<false>(x0, y0, x1, y1, u0, u1);
+        const float u[4] = {u0.x, u0.y, u1.x, u1.y};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[wino_acc(k)] = __builtin_amdgcn_mfma_f32_32x32x2f32(u[e], o.b[e], acc[wino_acc(k)], 0, 0, 0);
+    };
+    Ops cur, nxt;
+    load(cur, 0, sm.slot());
+#pragma unroll
+    for (int s = 0; s < kWinoSteps; ++s) {
+        const int ngroups = kWinoGroups - 4 * s < 4 ? kWinoGroups - 4 * s : 4;
+        sm.begin_step();
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (q + 1 < ngroups) {
+                load(nxt, 4 * s + q + 1, sm.slot());
+                sm.piece(4 * s + q);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma(cur, 4 * s + q);
+                __builtin_amdgcn_sched_barrier(0);
+                cur = nxt;
+            }
+        }
+        const bool last = s == kWinoSteps - 1;
+        sm.template end_step<0>(last);
+        if (!last) load(nxt, 4 * s + 4, sm.slot());
+        sm.piece(4 * s + 3);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma(cur, 4 * s + ngroups - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        cur = nxt;
+    }
+}
+
 // (Round 6, as in half_steps_h16: the WEIGHT fragment is the instruction's A operand and the pixel fragment its B -- same register shapes -- so
 // the accumulators hold the transposed tile: lane (i, h) has, of pixel i of the tile row, output slots 8 j + 4 h + (0..3) in registers
 // 4 j + (0..3).  This loop only serves the split-half mode's LAST stage, whose epilogue is then lane-local: stage_epilogue_final_t.)
@@ -1302,6 +1394,54 @@ __device__ __forceinline__ int stage_epilogue(const StageArgs& a, f32x16 (&acc)[
     return stores;
 }
 
+// Epilogue of the WINO form (half_steps_wino): the output transform y0 = m0 + m1 + m2, y1 = m1 - m2 - m3, then bias + BeLU as in
+// stage_epilogue.  Tile row m of the wave is accumulator rows 16 m .. 16 m + 15, i.e. registers 8 m .. 8 m + 7: register 8 m + k of lane
+// (h, i) holds pair (k & 3) + 8 (k >> 2) + 4 h, output channel i; y0 is the pair's first pixel, y1 its second.  Same store paths and
+// counts as stage_epilogue: through the wave's LDS scratch (pipe form), or one store per value.
+template <int T>
+__device__ __forceinline__ int stage_epilogue_wino(const StageArgs& a, const f32x16 (&acc)[4], float bias, float beta, int n, int x0, int y0,
+                                                   int wave, int lane, float* stage_lds) {
+    const int i = lane & 31, h = lane >> 5;
+    const bool full_x = x0 + kTW <= a.W;
+    int stores = 0;
+#pragma unroll
+    for (int m = 0; m < T; ++m) {
+        const int y = y0 + wave * T + m;
+        if (y >= a.y_end) continue;
+        float* grow = a.dst + ((size_t)n * a.img_stride + (long)y * a.pitch + x0) * 32;
+        float o[16];  // o[4 k' + 2 s + t]: pixel 2 j + t of the pair j in register 8 m + 2 k' + s
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) {
+            const int r = 8 * m + k;
+            const f32x2 m0 = {acc[0][r], acc[0][r + 1]}, m1 = {acc[1][r], acc[1][r + 1]};
+            const f32x2 m2 = {acc[2][r], acc[2][r + 1]}, m3 = {acc[3][r], acc[3][r + 1]};
+            const f32x2 bb = {bias, bias};
+            const f32x2 p0 = belu2(((m0 + m1) + m2) + bb, beta), p1 = belu2(((m1 - m2) - m3) + bb, beta);
+            o[2 * k] = p0.x; o[2 * k + 1] = p1.x; o[2 * k + 2] = p0.y; o[2 * k + 3] = p1.y;
+        }
+        auto pixel = [&](int v) { return 2 * (((v >> 1) & 3) + 8 * (v >> 3) + 4 * h) + (v & 1); };  // pixel of o[v]
+        if (full_x && stage_lds) {
+            float* sp = stage_lds + i;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) sp[pixel(v) * 32] = o[v];
+            const f32x4* lp = (const f32x4*)stage_lds + lane;
+            const f32x4 v0 = lp[0], v1 = lp[64], v2 = lp[128], v3 = lp[192];
+            f32x4* gp = (f32x4*)grow + lane;
+            gp[0] = v0; gp[64] = v1; gp[128] = v2; gp[192] = v3;
+            stores += 4;
+        } else if (full_x) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) grow[pixel(v) * 32 + i] = o[v];
+            stores += 16;
+        } else {
+#pragma unroll
+            for (int v = 0; v < 16; ++v)
+                if (x0 + pixel(v) < a.W) grow[pixel(v) * 32 + i] = o[v];
+        }
+    }
+    return stores;
+}
+
 // n consecutive dwords (n a constant after unrolling) at a 4-byte-aligned address, as the widest stores there are
 template <int N>
 struct __attribute__((packed, aligned(4))) DwordRun { uint32_t w[N]; };
@@ -1542,8 +1682,9 @@ __device__ __forceinline__ int queue_first(int block, int nbig, int nsmall) { re
 // tile resident in LDS, sources staged one after the other.  It is what small launches of the exact-f32 mode run (no
 // queue, nothing to amortise: 256x256 is one round of 4-row tiles) and the in-library cross-check of the pipe form
 // (sr_set_experiment "pipe" = "none"): same matrix loops, same step order, same weight chunks, bit-identical results.
-template <int TH, int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3>
+template <int TH, int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false>
 __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
+    static_assert(!WINO || (NSRC == 1 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stage 1 of the exact mode");
     // Two workgroups share each SIMD.  A wave streaming MFMAs is the older one and wins every
     // arbitration, leaving the other workgroup's prologue / staging / epilogue code roughly one
     // issue slot per MFMA.  The matrix stream only needs one slot per 64 cycles, so everything
@@ -1563,7 +1704,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31;
     constexpr bool H16 = kH16<PREC, FINAL>;  // stages 1-3 of the split-half mode: 16x16x32 MFMAs, no half steps (half_steps_h16)
-    constexpr int NTAPS = H16 ? KS0 * KS0 + (NSRC - 1) * 9
+    constexpr int NTAPS = WINO ? 2 * kWinoSteps
+                        : H16 ? KS0 * KS0 + (NSRC - 1) * 9
                               : 2 * ((KS0 * KS0 + 1) / 2 + (NSRC - 1) * 5) * NTN;  // ring chunks: one per (step, N-tile), see half_steps_*
     const TileGrid& grid = a.grid[TH == 8 ? 0 : 1];  // this form runs one tile class per launch
     float bias[NTN];
@@ -1605,10 +1747,20 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { qm[m][k >> 1][k & 1] = bias2[k & 1]; qx[m][k >> 1][k & 1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     }
+    f32x16 wacc[WINO ? 4 : 1];  // WINO: the four position sets m_p (half_steps_wino)
+#pragma unroll
+    for (int p = 0; p < (WINO ? 4 : 1); ++p)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wacc[p][r] = 0.f;
     int gtap = 0, slot = 0;
     auto taps = [&](auto ks_tag) {
         constexpr int KS = decltype(ks_tag)::value;
-        if constexpr (H16) source_steps_h16<TH, KS, T>(qm, qx, tile, ring, a.wpack, gtap, slot, NTAPS, wave, lane);
+        if constexpr (WINO) {
+            using G = TileGeom<TH, KS>;
+            RingStream sm{ring, a.wpack, gtap, slot, NTAPS, wave, lane};
+#pragma unroll 1
+            for (int half = 0; half < 2; ++half) half_steps_wino<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+        } else if constexpr (H16) source_steps_h16<TH, KS, T>(qm, qx, tile, ring, a.wpack, gtap, slot, NTAPS, wave, lane);
         else source_steps<TH, KS, T, NTN, PREC>(acc, accx, tile, ring, a.wpack, gtap, slot, NTAPS, wave, lane);
     };
     ring_barrier<0>();  // every wave's tile + weight DMAs have landed
@@ -1632,7 +1784,9 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
     if constexpr (FINAL)
         lin_taps<TH, T, IMG_U8, NW * 64, NTN, PREC, FACTOR>(acc, accx, tile, ring, a, a.wpack + (size_t)NTAPS * kChunkFloats, n, y0, x0, wave, lane, tid);
     uint32_t dom = 0;
-    if constexpr (H16) {
+    if constexpr (WINO) {
+        stage_epilogue_wino<T>(a, wacc, bias[0], beta, n, x0, y0, wave, lane, nullptr);
+    } else if constexpr (H16) {
         stage_epilogue_h16<T>(a, qm, qx, beta2, n, x0, y0, wave, lane, dom);
     } else if constexpr (FINAL && PREC == 1) {
         f32x4 fbias[NTN][4];  // (transposed accumulators: lane (i, h) holds the slots whose biases are a.bias[32 nt + 16 h + (0..15)])
@@ -1998,8 +2152,9 @@ struct PipeStream {
     }
 };
 
-template <int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3>
+template <int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false>
 __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
+    static_assert(!WINO || (NSRC == 1 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stage 1 of the exact mode");
     __builtin_amdgcn_s_setprio(3);
     constexpr int NTN = FINAL ? (FACTOR * FACTOR + 9) / 10 : 1;  // N-tiles of the node (expand at factor 4: 48 channels = 2)
     using H0 = HalfTile<KS0>;
@@ -2007,7 +2162,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
     constexpr int HB = H0::BYTES;  // KS0 >= 3: the first source has the largest half tile
     constexpr int NH = 2 * NSRC;
     constexpr bool H16 = kH16<PREC, FINAL>;  // stages 1-3 of the split-half mode: 16x16x32 MFMAs, a source's halves share their odd tap's step
-    constexpr int NSTEPS = H16 ? KS0 * KS0 + (NSRC - 1) * 9
+    constexpr int NSTEPS = WINO ? 2 * kWinoSteps
+                         : H16 ? KS0 * KS0 + (NSRC - 1) * 9
                                : 2 * (H0::STEPS + (NSRC - 1) * H3::STEPS) * NTN;  // weight chunks per tile: one per (step, N-tile)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem + 2 * HB;
@@ -2145,6 +2301,11 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
 #pragma unroll
                 for (int g = 0; g < 8; ++g) qa[nt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
+        f32x16 wacc[WINO ? 4 : 1];  // WINO: the four position sets m_p (half_steps_wino)
+#pragma unroll
+        for (int p = 0; p < (WINO ? 4 : 1); ++p)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) wacc[p][r] = 0.f;
         // (local to the tile ON PURPOSE: the registers the asynchronous atomic / load return into must not be live across the
         // tile loop's merge of the two tile bodies -- the compiler then copies them right after the asm statement, i.e. before
         // the data has arrived; it cannot know these asm outputs land later)
@@ -2183,8 +2344,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
             using GJ = TileGeom<8, KSJ>;
             // steps of this half / of the halves before it (kH16: a source's first half is its tap pairs, the second one step more)
             constexpr int PAIRS_J = (KSJ * KSJ - 1) / 2;
-            constexpr int STEPS_J = H16 ? PAIRS_J + (j & 1) : HalfTile<KSJ>::STEPS * NTN;
-            constexpr int GS0 = H16 ? (src == 0 ? 0 : KS0 * KS0 + (src - 1) * 9) + (j & 1) * PAIRS_J
+            constexpr int STEPS_J = WINO ? kWinoSteps : H16 ? PAIRS_J + (j & 1) : HalfTile<KSJ>::STEPS * NTN;
+            constexpr int GS0 = WINO ? j * kWinoSteps : H16 ? (src == 0 ? 0 : KS0 * KS0 + (src - 1) * 9) + (j & 1) * PAIRS_J
                                     : (j == 0 ? 0 : j == 1 ? H0::STEPS : 2 * H0::STEPS + (j - 2) * H3::STEPS) * NTN;
             constexpr int LIN_LO_J = LinPrefetch<IMG_U8, TH>::NPIX * 8;  // split-half mode: bytes from the hi halves of the image tile to its lo halves
             auto lin_store = [&]() {  // (kLinOwn: the pixels requested at this half's start are long in; see s_xown)
@@ -2195,7 +2356,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
                 }
             };
             PipeStream<PREC, KSN, decltype(lin_store)> sm{st, rq, *htn, a, ring_lds, wbase, GS0, wave, lane, (j == 0 && !single) ? s_next : nullptr, xcd, qs, STEPS_J > 3 ? STEPS_J - 3 : 0, 0, lin_store};
-            if constexpr (QUAD) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN, true, FACTOR>(qa, hb, ring, sm, wave, lane);
+            if constexpr (WINO) half_steps_wino<GJ::TWH, GJ::PLANE, T>(wacc, hb, ring, sm, wave, lane);
+            else if constexpr (QUAD) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN, true, FACTOR>(qa, hb, ring, sm, wave, lane);
             else if constexpr (PREC == 0) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN>(acc, hb, ring, sm, wave, lane);
             else if constexpr (H16) half_steps_h16<GJ::TWH, GJ::PLANE, 2, KSJ, T, (j & 1) != 0, -HB>(qm, qx, hb, ring, sm, wave, lane);
             else half_steps_h<GJ::TWH, GJ::PLANE, 2, KSJ, T, NTN>(acc, accx, hb, ring, sm, wave, lane);
@@ -2234,7 +2396,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
             // (stages 1-3: the buffer the tile's LAST half has just left -- every wave is past that half's last barrier, the next tile's second
             // half is requested into it by the steps to come -- lends each wave its own plane as the epilogue's scratch)
             float* scratch = FINAL ? nullptr : (float*)(smem + ((NH - 1) & 1) * HB + wave * H0::G::PLANE);
-            stores = stage_epilogue<TH, T, NTN, FINAL, OUT_U8, FACTOR>(a, acc, bias, beta, n, x0, y0, wave, lane, scratch);
+            if constexpr (WINO) stores = stage_epilogue_wino<T>(a, wacc, bias[0], beta, n, x0, y0, wave, lane, scratch);
+            else stores = stage_epilogue<TH, T, NTN, FINAL, OUT_U8, FACTOR>(a, acc, bias, beta, n, x0, y0, wave, lane, scratch);
         }
         // (Split-half mode only: its steps are shorter than a write acknowledgement takes, so the uncounted stores stalled each tile's first
         // barriers -- 0.8 % of a frame.  An exact-mode step is ten times longer and never saw it: measured, no change, its code is left as it was.)
@@ -2361,10 +2524,13 @@ static hipError_t launch_with_lds(K kern, const StageArgs& a, int nblk, size_t l
 }
 
 template <int TH, int PREC>
-static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int nblk, bool img_u8, bool out_u8,
+static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int nblk, bool img_u8, bool out_u8, bool wino,
                                  hipStream_t s) {
     switch (stage) {
-        case 1: return launch_with_lds(conv_stage_kernel<TH, 1, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+        case 1:
+            if constexpr (PREC == 0)
+                if (wino) return launch_with_lds(conv_stage_kernel<TH, 1, 5, false, false, false, 0, 3, true>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+            return launch_with_lds(conv_stage_kernel<TH, 1, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 2: return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 3: return launch_with_lds(conv_stage_kernel<TH, 3, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 4:
@@ -2383,7 +2549,7 @@ static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int 
 
 // Pipe form (both tile classes of the launch): grid = co-resident workgroups, LDS = two half tiles + ring + mailbox.
 template <int PREC>
-static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a, int grid, bool img_u8, bool out_u8, hipStream_t s) {
+static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a, int grid, bool img_u8, bool out_u8, bool wino, hipStream_t s) {
     constexpr size_t lds5 = 2 * (size_t)HalfTile<5>::BYTES + kRingBytes + 16;
     // + bilinear weights per N-tile, byte / 255 table, and (one N-tile: factor 2, 3) the bilinear taps' own image tile of (8 + 2) x (32 + 2) pixels
     constexpr size_t lds3_1 = 2 * (size_t)HalfTile<3>::BYTES + kRingBytes + 16 + 9 * 128 * sizeof(float) + 256 * sizeof(float) + 10 * 34 * 16;
@@ -2391,7 +2557,10 @@ static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a,
     static_assert(lds3_1 <= 80 * 1024 && lds3_2 <= 80 * 1024, "two workgroups per CU");
     const size_t lds3 = factor == 4 ? lds3_2 : lds3_1;
     switch (stage) {
-        case 1: return launch_with_lds(conv_stage_pipe_kernel<1, 5, false, false, false, PREC>, a, grid, lds5, s);
+        case 1:
+            if constexpr (PREC == 0)
+                if (wino) return launch_with_lds(conv_stage_pipe_kernel<1, 5, false, false, false, 0, 3, true>, a, grid, lds5, s);
+            return launch_with_lds(conv_stage_pipe_kernel<1, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 2: return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 3: return launch_with_lds(conv_stage_pipe_kernel<3, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 4:
@@ -2407,16 +2576,16 @@ static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a,
     }
     return hipErrorInvalidValue;
 }
-hipError_t sr_launch_stage_pipe(int stage, int factor, const StageArgs& a, int prec, int grid, bool img_u8, bool out_u8, hipStream_t s) {
-    return prec == 0 ? launch_stage_pipe_t<0>(stage, factor, a, grid, img_u8, out_u8, s)
-                     : launch_stage_pipe_t<1>(stage, factor, a, grid, img_u8, out_u8, s);
+hipError_t sr_launch_stage_pipe(int stage, int factor, const StageArgs& a, int prec, int grid, bool img_u8, bool out_u8, bool wino, hipStream_t s) {
+    return prec == 0 ? launch_stage_pipe_t<0>(stage, factor, a, grid, img_u8, out_u8, wino, s)
+                     : launch_stage_pipe_t<1>(stage, factor, a, grid, img_u8, out_u8, wino, s);
 }
 
 hipError_t sr_launch_stage(int stage, int factor, const StageArgs& a, int th, int prec, int nblk, bool img_u8,
-                           bool out_u8, hipStream_t s) {
+                           bool out_u8, bool wino, hipStream_t s) {
     if (prec == 0)
-        return th == 8 ? launch_stage_t<8, 0>(stage, factor, a, nblk, img_u8, out_u8, s)
-                       : launch_stage_t<4, 0>(stage, factor, a, nblk, img_u8, out_u8, s);
-    return th == 8 ? launch_stage_t<8, 1>(stage, factor, a, nblk, img_u8, out_u8, s)
-                   : launch_stage_t<4, 1>(stage, factor, a, nblk, img_u8, out_u8, s);
+        return th == 8 ? launch_stage_t<8, 0>(stage, factor, a, nblk, img_u8, out_u8, wino, s)
+                       : launch_stage_t<4, 0>(stage, factor, a, nblk, img_u8, out_u8, wino, s);
+    return th == 8 ? launch_stage_t<8, 1>(stage, factor, a, nblk, img_u8, out_u8, wino, s)
+                   : launch_stage_t<4, 1>(stage, factor, a, nblk, img_u8, out_u8, wino, s);
 }
