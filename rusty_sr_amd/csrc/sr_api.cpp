@@ -114,7 +114,7 @@ void pack_steps(std::vector<float>& dst, const float* w, int ks, int ntn, bool s
             }
 }
 
-// Stage 1's 5x5 weights for the exact mode's Winograd form (sr_kernels.hip half_steps_wino): per 16-channel half, operand groups
+// The 5x5 weights of stages 1 and 2 (conv1, conv2) for the exact mode's Winograd form (sr_kernels.hip half_steps_wino): per 16-channel half, operand groups
 // g = (kernel row ky, position k, 8-channel group rr) = 14 ky + 2 k + rr, four to a 4 KB chunk (the last chunk of a half two):
 //   [q = g % 4][h 2][lane 32][4]    channel = 16 half + 8 rr + 4 h + e
 // Position k < 4 is position k of chunk A (taps 0, 1, 2 of the row), k = 4..6 position k - 3 of chunk B (a zero tap, then taps 3, 4);
@@ -419,6 +419,8 @@ int sr_create_graph(sr_ctx** out, int graph, const float* params, size_t n_param
         }
         w.clear(); pack_steps_wino(w, params + L.conv1);
         c->off_wino1 = push(w);
+        w.clear(); pack_steps_wino(w, params + L.conv2); pack_steps(w, params + L.conv5, 3, 1, false, [](int, int j) { return j; });
+        c->off_wino2 = push(w);
         const size_t boff[4] = {L.f_bias, L.l_bias[0], L.l_bias[1], L.l_bias[2]};
         const size_t aoff[4] = {L.f_activ, L.l_activ[0], L.l_activ[1], L.l_activ[2]};
         for (int s = 0; s < 4; ++s) c->off_bias[s] = push(vec32(boff[s], 32));
@@ -541,8 +543,8 @@ int sr_set_experiment(sr_ctx* c, const char* key, const char* value) {
         sr_fork_tune_clear(c);
     } else if (!strcmp(key, "halo")) {  // sharded calls: "" / "input": 7 input rows per neighbour, the overlap recomputed; "layers": feature rows after every stage
         c->layer_halos = !strcmp(v, "layers");
-    } else if (!strcmp(key, "wino")) {  // exact mode, stage 1: "" / "1": Winograd F(2,3) rows, "0": the direct form (same bar, other last bits)
-        c->wino = strcmp(v, "0") != 0;
+    } else if (!strcmp(key, "wino")) {  // exact mode: "" / "2": stages 1 and 2 as Winograd F(2,3) rows, "1": stage 1 only, "0": all direct (same bar, other last bits)
+        c->wino = !strcmp(v, "0") ? 0 : !strcmp(v, "1") ? 1 : 2;
     } else if (!strcmp(key, "bw")) {   // tile-order column-block width in tiles; "" / negative: automatic, 0: plain row-major
         c->env_bw = *v ? atoi(v) : -1;
     } else {
@@ -727,10 +729,11 @@ int StackJob::prepare() {
         //  conv0 and the first form run one class.
         const long tiles8 = (long)n * tiles_x * ((rows + 7) / 8);
         // (the last stage of factor 4 in the split-half mode exists with 4-row tiles only: two N-tiles of accumulators, sr_kernels.hip kBigTiles)
-        // (the exact mode's stage 1 in its Winograd form: a 4-row tile half-fills the pair dimension, 7 MFMAs per 16 pixels where the direct form
-        // issues 5, so a small launch keeps 8-row tiles instead of switching to 4-row ones -- 256x256 stage 1 0.0488 ms with 4-row tiles, 0.0314
-        // with 8-row ones, direct 0.0368; 360x640 0.1515 / 0.0853 / 0.1080: profiles/r7_ab_wino_stage1.txt.  Tile plans change no bit.)
-        const bool wino8 = st == 1 && c->precision == SR_PRECISION_F32 && c->wino;
+        // (the exact mode's stages 1 and 2 in their Winograd form: a 4-row tile half-fills the pair dimension, 7 MFMAs per 16 pixels where the
+        // direct form issues 5, so a small launch keeps 8-row tiles instead of switching to 4-row ones -- 256x256 stage 1 0.0488 ms with 4-row
+        // tiles, 0.0314 with 8-row ones, direct 0.0368; 360x640 0.1515 / 0.0853 / 0.1080: profiles/r7_ab_wino_stage1.txt; stage 2 256x256
+        // 0.0658 / 0.0402 / 0.0449, 360x640 0.2188 / 0.1242 / 0.1434: profiles/r8_ab_wino_stage2.txt.  Tile plans change no bit.)
+        const bool wino8 = c->precision == SR_PRECISION_F32 && (st == 1 || st == 2) && st <= c->wino;
         const int forced = (st == 4 && c->factor == 4 && c->precision == SR_PRECISION_SPLIT_F16) ? 4 : c->env_th[st];
         const bool small_launch = tiles8 < 2L * resident;
         const bool split = c->precision == SR_PRECISION_SPLIT_F16;
@@ -752,7 +755,9 @@ int StackJob::prepare() {
             // end staggered anyway: 1920x1080 4.048 -> 4.018, 1600x900 2.853 -> 2.825, 1280x720 1.841 -> 1.834 ms without it)
             // (round 6: not in the exact mode's last stage either -- its 8-row tiles run on 4x4x1 MFMAs with 28 output columns, its 4-row
             // tiles still on 32x32x2 with 32, code the launch would otherwise never touch: 0.7775 -> 0.7695 ms at 1080p, profiles/r6_ab_quad.txt)
-            if (tail < 0.0f) tail = (!split && rounds >= 3.0 && !forked && st != 4) ? 1.0f : 0.0f;
+            // (nor in stage 2's Winograd form, whose 4-row tiles cost as many MFMAs as 8-row ones for the 5x5 source: 1080p stage 2 0.856 ms
+            // with the tail, 0.837 without, profiles/r8_ab_wino_stage2.txt)
+            if (tail < 0.0f) tail = (!split && rounds >= 3.0 && !forked && st != 4 && !(st == 2 && wino8)) ? 1.0f : 0.0f;
             if (tail > 0.0f) {
                 const long per_row = (long)n * tiles_x;
                 const int want = (int)((tail * resident + per_row - 1) / per_row);  // tile rows of small tiles
@@ -833,8 +838,8 @@ int StackJob::launch(int st) const {
         case 3: a.src[0] = f; a.src[1] = l1; a.src[2] = l2; a.dst = l3; break;
         case 4: a.src[0] = l1; a.src[1] = l2; a.src[2] = l3; a.img = d_img; a.out = d_out; break;
     }
-    const bool wino = st == 1 && c->precision == SR_PRECISION_F32 && c->wino;
-    a.wpack = P + (c->precision ? c->off_wh[st] : wino ? c->off_wino1 : c->off_w[st]); a.bias = P + c->off_bias[st];
+    const bool wino = c->precision == SR_PRECISION_F32 && (st == 1 || st == 2) && st <= c->wino;
+    a.wpack = P + (c->precision ? c->off_wh[st] : !wino ? c->off_w[st] : st == 1 ? c->off_wino1 : c->off_wino2); a.bias = P + c->off_bias[st];
     a.beta = st < 4 ? P + c->off_beta[st] : nullptr;
     a.H = H; a.W = W; a.img_ch = img_ch;
     a.y_begin = y0; a.y_end = y1; a.tiles_x = tiles_x;

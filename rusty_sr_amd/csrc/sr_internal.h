@@ -19,7 +19,8 @@ struct sr_ctx {
     void* d_qtab = nullptr;     // bilinear_net / downsample_net: data_to_img(LinearToSrgb(l)) as a step table (sr_aux.hip)
     size_t off_w0 = 0, off_w0h = 0, off_w[5] = {0}, off_wh[5] = {0}, off_bias[5] = {0}, off_beta[5] = {0};
     size_t off_wino1 = 0;  // stage 1's weights as Winograd F(2,3) chunks (sr_api.cpp pack_steps_wino)
-    bool wino = true;      // exact mode, stage 1: Winograd F(2,3) rows ("wino" switch; "0": the direct form -- last bits differ)
+    size_t off_wino2 = 0;  // stage 2's: conv2 as Winograd F(2,3) chunks, then conv5's direct chunks
+    int wino = 2;          // exact mode, stages 1 .. wino in their Winograd F(2,3) form ("wino" switch; "0": all direct -- last bits differ)
     int precision = 0;  // SR_PRECISION_F32 / SR_PRECISION_SPLIT_F16
     // Domain of the split-half mode (include/srhip.h, sr_set_precision): values are carried as pairs of HALVES, so every weight, input
     // and activation must be finite and below 65504 in magnitude.  Weights are checked once (split_ok); inputs and activations by the

@@ -124,8 +124,8 @@ hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, 
 hipError_t sr_launch_conv0(const Conv0Args& a, int th, int prec, int nblk, bool img_u8, hipStream_t s);
 // factor (2, 3 or 4) only matters for stage 4 (3 f^2 expand channels, depth-to-space x f)
 // first form: ONE tile class (th = 8: a.grid[0], th = 4: a.grid[1]), whole source tiles resident
-// wino (prec 0, stage 1 only): the 5x5 convolution as row-direction Winograd F(2,3) (sr_kernels.hip half_steps_wino); a.wpack then
-// holds pack_steps_wino chunks
+// wino (prec 0, stages 1 and 2): the 5x5 convolution as row-direction Winograd F(2,3) (sr_kernels.hip half_steps_wino; stage 2's 3x3
+// source on the same pairs, half_steps_pairs); a.wpack then holds pack_steps_wino chunks (stage 2: followed by conv5's direct chunks)
 hipError_t sr_launch_stage(int stage, int factor, const StageArgs& a, int th, int prec, int nblk, bool img_u8, bool out_u8,
                            bool wino, hipStream_t s);
 // "pipe" form of the stage kernels (half-tile double buffering, persistent): both tile classes of `a` in one launch;

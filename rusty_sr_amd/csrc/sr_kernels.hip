@@ -770,7 +770,7 @@ __device__ __forceinline__ void half_steps_f32(Acc& acc, const char* hb, const c
     }
 }
 
-// WINO (exact mode, stage 1: the 5x5 f-convolution alone): every kernel row as row-direction Winograd / Toom-Cook F(2,3) on the points
+// WINO (exact mode, stages 1 and 2: the 5x5 f-convolution; stage 2's 3x3 source runs half_steps_pairs): every kernel row as row-direction Winograd / Toom-Cook F(2,3) on the points
 // 0, 1, -1, inf.  For an output pair (x, x + 1) and a 3-tap row g over the inputs d0..d3:
 //     U = (d0 - d2, d1 + d2, d2 - d1, d1 - d3),  V = (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2),  m_p += U_p V_p,
 //     y0 = m0 + m1 + m2,  y1 = m1 - m2 - m3.
@@ -809,8 +809,8 @@ __device__ __forceinline__ void wino_u4(f32x2 x0, f32x2 y0, f32x2 x1, f32x2 y1, 
             : "=&v"(u0), "=&v"(u1) : "v"(x0), "v"(y0), "v"(x1), "v"(y1));
 }
 
-template <int TWH, int PS, int T, typename Stream>
-__device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[4], const char* hb, const char* ring, Stream& sm, int wave, int lane) {
+template <int TWH, int PS, int T, int NA, typename Stream>
+__device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[NA], const char* hb, const char* ring, Stream& sm, int wave, int lane) {
     static_assert(TWH >= kTW + 4, "a pair reads six pixels from its first halo column on");
     const int i = lane & 31, h = lane >> 5;
     const int wlane = (h * 32 + i) * 16;
@@ -857,6 +857,64 @@ __device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[4], const char* hb
         sm.piece(4 * s + 3);
         __builtin_amdgcn_sched_barrier(0);
         mfma(cur, 4 * s + ngroups - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        cur = nxt;
+    }
+}
+
+// Stage 2's second source (l1, 3x3) in the WINO form: the direct taps of half_steps_f32 -- same weight chunks, same step and group
+// order -- on the pair layout of half_steps_wino, so that the accumulators need no lane exchange.  Lane (h, i) of the A operand is pair
+// i % 16 of tile row i / 16; an operand group reads the pair's even pixel 2 j + kx and its odd pixel 2 j + 1 + kx, one weight register
+// feeds both, the even products go into m0 (acc[0]) and the odd ones into a fifth set m4 (acc[4]): y0 = m0 + m1 + m2, y1 = m1 - m2 - m3
+// + m4 (stage_epilogue_wino).  Per group two pixel reads, one weight read and eight MFMAs, as the direct loop's 8-row tiles; a 4-row
+// tile half-fills the pair dimension as in half_steps_wino.  An even product reads only pixels of y0's field, an odd one only y1's.
+template <int TWH, int PS, int T, typename Stream>
+__device__ __forceinline__ void half_steps_pairs(f32x16 (&acc)[5], const char* hb, const char* ring, Stream& sm, int wave, int lane) {
+    constexpr int NT = 9, NP = (NT + 1) / 2;
+    static_assert(TWH >= kTW + 2, "a pair reads four pixels from its first halo column on");
+    const int i = lane & 31, h = lane >> 5;
+    const int wlane = (h * 32 + i) * 16;
+    const int row = wave * T + (T == 2 ? i >> 4 : 0);
+    const char* abase = hb + h * PS + (row * TWH + 2 * (i & 15)) * 16;
+    struct Ops { f32x4 x, y, b; };
+    // operand group q of pair p: q = 2 * tapslot + rr  (rr: which 8 of the half's 16 channels), as half_steps_f32
+    auto load = [&](Ops& o, int p, int q, int sl) {
+        const int t = 2 * p + (q >> 1), ky = t / 3, kx = t - ky * 3;
+        const char* ab = abase + (q & 1) * 2 * PS + (ky * TWH + kx) * 16;
+        o.b = *(const f32x4*)(ring + sl * 4096 + wlane + q * 1024);
+        o.x = *(const f32x4*)ab;
+        o.y = *(const f32x4*)(ab + 16);
+    };
+    auto mfma = [&](const Ops& o) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.x[e], o.b[e], acc[0], 0, 0, 0);
+            acc[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(o.y[e], o.b[e], acc[4], 0, 0, 0);
+        }
+    };
+    Ops cur, nxt;
+    load(cur, 0, 0, sm.slot());
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const int ngroups = (2 * p + 1 < NT) ? 4 : 2;
+        sm.begin_step();
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (q + 1 < ngroups) {
+                load(nxt, p, q + 1, sm.slot());
+                sm.piece(4 * p + q);
+                __builtin_amdgcn_sched_barrier(0);
+                mfma(cur);
+                __builtin_amdgcn_sched_barrier(0);
+                cur = nxt;
+            }
+        }
+        const bool last = p == NP - 1;
+        sm.template end_step<0>(last);
+        if (!last) load(nxt, p + 1, 0, sm.slot());
+        sm.piece(4 * p + 3);
+        __builtin_amdgcn_sched_barrier(0);
+        mfma(cur);
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
     }
@@ -1395,12 +1453,14 @@ __device__ __forceinline__ int stage_epilogue(const StageArgs& a, f32x16 (&acc)[
 }
 
 // Epilogue of the WINO form (half_steps_wino): the output transform y0 = m0 + m1 + m2, y1 = m1 - m2 - m3, then bias + BeLU as in
-// stage_epilogue.  Tile row m of the wave is accumulator rows 16 m .. 16 m + 15, i.e. registers 8 m .. 8 m + 7: register 8 m + k of lane
-// (h, i) holds pair (k & 3) + 8 (k >> 2) + 4 h, output channel i; y0 is the pair's first pixel, y1 its second.  Same store paths and
-// counts as stage_epilogue: through the wave's LDS scratch (pipe form), or one store per value.
-template <int T>
-__device__ __forceinline__ int stage_epilogue_wino(const StageArgs& a, const f32x16 (&acc)[4], float bias, float beta, int n, int x0, int y0,
+// stage_epilogue.  NA = 5 (stage 2): the fifth set m4 holds the odd pixels' direct 3x3 products (half_steps_pairs), y1 = m1 - m2 - m3 + m4;
+// NA = 4 (stage 1) has no such term.  Tile row m of the wave is accumulator rows 16 m .. 16 m + 15, i.e. registers 8 m .. 8 m + 7: register
+// 8 m + k of lane (h, i) holds pair (k & 3) + 8 (k >> 2) + 4 h, output channel i; y0 is the pair's first pixel, y1 its second.  Same store
+// paths and counts as stage_epilogue: through the wave's LDS scratch (pipe form), or one store per value.
+template <int T, int NA>
+__device__ __forceinline__ int stage_epilogue_wino(const StageArgs& a, const f32x16 (&acc)[NA], float bias, float beta, int n, int x0, int y0,
                                                    int wave, int lane, float* stage_lds) {
+    static_assert(NA == 4 || NA == 5, "four position sets, or four and stage 2's odd-pixel set");
     const int i = lane & 31, h = lane >> 5;
     const bool full_x = x0 + kTW <= a.W;
     int stores = 0;
@@ -1416,7 +1476,9 @@ __device__ __forceinline__ int stage_epilogue_wino(const StageArgs& a, const f32
             const f32x2 m0 = {acc[0][r], acc[0][r + 1]}, m1 = {acc[1][r], acc[1][r + 1]};
             const f32x2 m2 = {acc[2][r], acc[2][r + 1]}, m3 = {acc[3][r], acc[3][r + 1]};
             const f32x2 bb = {bias, bias};
-            const f32x2 p0 = belu2(((m0 + m1) + m2) + bb, beta), p1 = belu2(((m1 - m2) - m3) + bb, beta);
+            f32x2 y1 = (m1 - m2) - m3;
+            if constexpr (NA == 5) y1 = y1 + f32x2{acc[4][r], acc[4][r + 1]};
+            const f32x2 p0 = belu2(((m0 + m1) + m2) + bb, beta), p1 = belu2(y1 + bb, beta);
             o[2 * k] = p0.x; o[2 * k + 1] = p1.x; o[2 * k + 2] = p0.y; o[2 * k + 3] = p1.y;
         }
         auto pixel = [&](int v) { return 2 * (((v >> 1) & 3) + 8 * (v >> 3) + 4 * h) + (v & 1); };  // pixel of o[v]
@@ -1684,7 +1746,7 @@ __device__ __forceinline__ int queue_first(int block, int nbig, int nsmall) { re
 // (sr_set_experiment "pipe" = "none"): same matrix loops, same step order, same weight chunks, bit-identical results.
 template <int TH, int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false>
 __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
-    static_assert(!WINO || (NSRC == 1 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stage 1 of the exact mode");
+    static_assert(!WINO || (NSRC <= 2 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stages 1 and 2 of the exact mode");
     // Two workgroups share each SIMD.  A wave streaming MFMAs is the older one and wins every
     // arbitration, leaving the other workgroup's prologue / staging / epilogue code roughly one
     // issue slot per MFMA.  The matrix stream only needs one slot per 64 cycles, so everything
@@ -1704,7 +1766,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31;
     constexpr bool H16 = kH16<PREC, FINAL>;  // stages 1-3 of the split-half mode: 16x16x32 MFMAs, no half steps (half_steps_h16)
-    constexpr int NTAPS = WINO ? 2 * kWinoSteps
+    constexpr int NTAPS = WINO ? 2 * (kWinoSteps + (NSRC - 1) * 5)
                         : H16 ? KS0 * KS0 + (NSRC - 1) * 9
                               : 2 * ((KS0 * KS0 + 1) / 2 + (NSRC - 1) * 5) * NTN;  // ring chunks: one per (step, N-tile), see half_steps_*
     const TileGrid& grid = a.grid[TH == 8 ? 0 : 1];  // this form runs one tile class per launch
@@ -1747,9 +1809,10 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { qm[m][k >> 1][k & 1] = bias2[k & 1]; qx[m][k >> 1][k & 1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     }
-    f32x16 wacc[WINO ? 4 : 1];  // WINO: the four position sets m_p (half_steps_wino)
+    constexpr int NWACC = WINO ? 3 + NSRC : 1;  // WINO: the four position sets m_p (half_steps_wino), stage 2 the odd pixels' set m4 (half_steps_pairs)
+    f32x16 wacc[NWACC];
 #pragma unroll
-    for (int p = 0; p < (WINO ? 4 : 1); ++p)
+    for (int p = 0; p < NWACC; ++p)
 #pragma unroll
         for (int r = 0; r < 16; ++r) wacc[p][r] = 0.f;
     int gtap = 0, slot = 0;
@@ -1759,7 +1822,10 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
             using G = TileGeom<TH, KS>;
             RingStream sm{ring, a.wpack, gtap, slot, NTAPS, wave, lane};
 #pragma unroll 1
-            for (int half = 0; half < 2; ++half) half_steps_wino<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+            for (int half = 0; half < 2; ++half) {
+                if constexpr (KS == KS0) half_steps_wino<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+                else half_steps_pairs<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+            }
         } else if constexpr (H16) source_steps_h16<TH, KS, T>(qm, qx, tile, ring, a.wpack, gtap, slot, NTAPS, wave, lane);
         else source_steps<TH, KS, T, NTN, PREC>(acc, accx, tile, ring, a.wpack, gtap, slot, NTAPS, wave, lane);
     };
@@ -1785,7 +1851,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
         lin_taps<TH, T, IMG_U8, NW * 64, NTN, PREC, FACTOR>(acc, accx, tile, ring, a, a.wpack + (size_t)NTAPS * kChunkFloats, n, y0, x0, wave, lane, tid);
     uint32_t dom = 0;
     if constexpr (WINO) {
-        stage_epilogue_wino<T>(a, wacc, bias[0], beta, n, x0, y0, wave, lane, nullptr);
+        stage_epilogue_wino<T, NWACC>(a, wacc, bias[0], beta, n, x0, y0, wave, lane, nullptr);
     } else if constexpr (H16) {
         stage_epilogue_h16<T>(a, qm, qx, beta2, n, x0, y0, wave, lane, dom);
     } else if constexpr (FINAL && PREC == 1) {
@@ -2154,7 +2220,7 @@ struct PipeStream {
 
 template <int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false>
 __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
-    static_assert(!WINO || (NSRC == 1 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stage 1 of the exact mode");
+    static_assert(!WINO || (NSRC <= 2 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stages 1 and 2 of the exact mode");
     __builtin_amdgcn_s_setprio(3);
     constexpr int NTN = FINAL ? (FACTOR * FACTOR + 9) / 10 : 1;  // N-tiles of the node (expand at factor 4: 48 channels = 2)
     using H0 = HalfTile<KS0>;
@@ -2162,7 +2228,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
     constexpr int HB = H0::BYTES;  // KS0 >= 3: the first source has the largest half tile
     constexpr int NH = 2 * NSRC;
     constexpr bool H16 = kH16<PREC, FINAL>;  // stages 1-3 of the split-half mode: 16x16x32 MFMAs, a source's halves share their odd tap's step
-    constexpr int NSTEPS = WINO ? 2 * kWinoSteps
+    constexpr int NSTEPS = WINO ? 2 * (kWinoSteps + (NSRC - 1) * H3::STEPS)
                          : H16 ? KS0 * KS0 + (NSRC - 1) * 9
                                : 2 * (H0::STEPS + (NSRC - 1) * H3::STEPS) * NTN;  // weight chunks per tile: one per (step, N-tile)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2301,9 +2367,10 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
 #pragma unroll
                 for (int g = 0; g < 8; ++g) qa[nt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        f32x16 wacc[WINO ? 4 : 1];  // WINO: the four position sets m_p (half_steps_wino)
+        constexpr int NWACC = WINO ? 3 + NSRC : 1;  // WINO: the four position sets m_p (half_steps_wino), stage 2 the odd pixels' set m4 (half_steps_pairs)
+        f32x16 wacc[NWACC];
 #pragma unroll
-        for (int p = 0; p < (WINO ? 4 : 1); ++p)
+        for (int p = 0; p < NWACC; ++p)
 #pragma unroll
             for (int r = 0; r < 16; ++r) wacc[p][r] = 0.f;
         // (local to the tile ON PURPOSE: the registers the asynchronous atomic / load return into must not be live across the
@@ -2344,8 +2411,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
             using GJ = TileGeom<8, KSJ>;
             // steps of this half / of the halves before it (kH16: a source's first half is its tap pairs, the second one step more)
             constexpr int PAIRS_J = (KSJ * KSJ - 1) / 2;
-            constexpr int STEPS_J = WINO ? kWinoSteps : H16 ? PAIRS_J + (j & 1) : HalfTile<KSJ>::STEPS * NTN;
-            constexpr int GS0 = WINO ? j * kWinoSteps : H16 ? (src == 0 ? 0 : KS0 * KS0 + (src - 1) * 9) + (j & 1) * PAIRS_J
+            constexpr int STEPS_J = WINO ? (src == 0 ? kWinoSteps : H3::STEPS) : H16 ? PAIRS_J + (j & 1) : HalfTile<KSJ>::STEPS * NTN;
+            constexpr int GS0 = WINO ? (j < 2 ? j * kWinoSteps : 2 * kWinoSteps + (j - 2) * H3::STEPS) : H16 ? (src == 0 ? 0 : KS0 * KS0 + (src - 1) * 9) + (j & 1) * PAIRS_J
                                     : (j == 0 ? 0 : j == 1 ? H0::STEPS : 2 * H0::STEPS + (j - 2) * H3::STEPS) * NTN;
             constexpr int LIN_LO_J = LinPrefetch<IMG_U8, TH>::NPIX * 8;  // split-half mode: bytes from the hi halves of the image tile to its lo halves
             auto lin_store = [&]() {  // (kLinOwn: the pixels requested at this half's start are long in; see s_xown)
@@ -2356,7 +2423,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
                 }
             };
             PipeStream<PREC, KSN, decltype(lin_store)> sm{st, rq, *htn, a, ring_lds, wbase, GS0, wave, lane, (j == 0 && !single) ? s_next : nullptr, xcd, qs, STEPS_J > 3 ? STEPS_J - 3 : 0, 0, lin_store};
-            if constexpr (WINO) half_steps_wino<GJ::TWH, GJ::PLANE, T>(wacc, hb, ring, sm, wave, lane);
+            if constexpr (WINO && src == 0) half_steps_wino<GJ::TWH, GJ::PLANE, T>(wacc, hb, ring, sm, wave, lane);
+            else if constexpr (WINO) half_steps_pairs<GJ::TWH, GJ::PLANE, T>(wacc, hb, ring, sm, wave, lane);
             else if constexpr (QUAD) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN, true, FACTOR>(qa, hb, ring, sm, wave, lane);
             else if constexpr (PREC == 0) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN>(acc, hb, ring, sm, wave, lane);
             else if constexpr (H16) half_steps_h16<GJ::TWH, GJ::PLANE, 2, KSJ, T, (j & 1) != 0, -HB>(qm, qx, hb, ring, sm, wave, lane);
@@ -2396,7 +2464,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
             // (stages 1-3: the buffer the tile's LAST half has just left -- every wave is past that half's last barrier, the next tile's second
             // half is requested into it by the steps to come -- lends each wave its own plane as the epilogue's scratch)
             float* scratch = FINAL ? nullptr : (float*)(smem + ((NH - 1) & 1) * HB + wave * H0::G::PLANE);
-            if constexpr (WINO) stores = stage_epilogue_wino<T>(a, wacc, bias[0], beta, n, x0, y0, wave, lane, scratch);
+            if constexpr (WINO) stores = stage_epilogue_wino<T, NWACC>(a, wacc, bias[0], beta, n, x0, y0, wave, lane, scratch);
             else stores = stage_epilogue<TH, T, NTN, FINAL, OUT_U8, FACTOR>(a, acc, bias, beta, n, x0, y0, wave, lane, scratch);
         }
         // (Split-half mode only: its steps are shorter than a write acknowledgement takes, so the uncounted stores stalled each tile's first
@@ -2531,7 +2599,10 @@ static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int 
             if constexpr (PREC == 0)
                 if (wino) return launch_with_lds(conv_stage_kernel<TH, 1, 5, false, false, false, 0, 3, true>, a, nblk, stage_lds_bytes<TH, 5>(), s);
             return launch_with_lds(conv_stage_kernel<TH, 1, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
-        case 2: return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+        case 2:
+            if constexpr (PREC == 0)
+                if (wino) return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, 0, 3, true>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+            return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 3: return launch_with_lds(conv_stage_kernel<TH, 3, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 4:
 #define SR_FINAL(F)                                                                                                          \
@@ -2561,7 +2632,10 @@ static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a,
             if constexpr (PREC == 0)
                 if (wino) return launch_with_lds(conv_stage_pipe_kernel<1, 5, false, false, false, 0, 3, true>, a, grid, lds5, s);
             return launch_with_lds(conv_stage_pipe_kernel<1, 5, false, false, false, PREC>, a, grid, lds5, s);
-        case 2: return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, PREC>, a, grid, lds5, s);
+        case 2:
+            if constexpr (PREC == 0)
+                if (wino) return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, 0, 3, true>, a, grid, lds5, s);
+            return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 3: return launch_with_lds(conv_stage_pipe_kernel<3, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 4:
 #define SR_FINAL(F)                                                                                                          \
