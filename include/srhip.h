@@ -329,6 +329,61 @@ int sr_backprop_rgba8_dev(sr_ctx* ctx, const float* d_params, const uint8_t* d_h
 int sr_adam_step_dev(sr_ctx* ctx, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr,
                      float beta1, float beta2, float eps, void* stream);
 
+/* ---- Training: the reference's `train` (main.rs:181-257) behind the ABI ----
+ * sr_init_params: the reference's g.init_params() for sr_net(factor) -- sr_num_params_factor(factor) floats in the .rsr segment order
+ * written to out (cap >= that many, else SR_E_INVALID).  Host only; no device needed.  UNPINNED (alumina's source is not at hand):
+ *   convolutions  MSRA normal, std = multiplier sqrt(2 / fan_in), fan_in = ks^2 in_channels, multiplier 1.0 for conv0 and 0.1 for the rest
+ *                 (network.rs); biases 0; BeLU beta (init_porque_no_los_dos) 1 on even channels, 0 on odd ones.
+ * The generator: SplitMix64 seeded with `seed`; each weight takes two draws u1, u2 = (x >> 11) 2^-53 and is
+ * (float)(std sqrt(-2 ln(1 - u1)) cos(2 pi u2)) in double arithmetic (Box-Muller, one value per pair): the same bits on any host whose
+ * libm rounds log / cos / sqrt of doubles alike. */
+int sr_init_params(int factor, uint64_t seed, float* out, size_t cap);
+
+/* Replace an sr_net context's inference weights: the parameters are packed as sr_create packs them and copied into the context's existing
+ * parameter buffer; the split-half mode's weight check is redone (a weight of 65504 or more, or not finite, then makes
+ * sr_set_precision(SR_PRECISION_SPLIT_F16) refuse, as after sr_create; a context already in that mode refuses such a vector with
+ * SR_E_DOMAIN).  A wrong n_params is SR_E_PARAM_COUNT.  Either refusal leaves the weights unchanged.  Synchronous: waits for the
+ * context's own streams.  The caller must have finished (synchronised) its own *_dev work that uses the context before calling. */
+int sr_set_params(sr_ctx* ctx, const float* params, size_t n_params);
+
+/* A training session on an sr_net context's device: parameters, Adam moments, gradient, a ring of per-step err_sum values and an
+ * image store all live on the device.  One step, queued on the context's own stream without host synchronisation:
+ *   1. train_crop_kernel gathers the n crops (crop_h x crop_w, alpha dropped, pixels outside the source image 0 -- y0 / x0 may be
+ *      negative or overhang) into one n x crop_h x crop_w x 3 u8 batch;
+ *   2. sr_backprop_rgba8_dev on that batch, loss_scale = 1 / n_elems, l2 as given;
+ *   3. sr_adam_step_dev with the session's step count (from 1).
+ * The same items give the same bits on every run.  An item names a resident image (image >= 0, an id of sr_train_add_image) or carries
+ * host pixels (image = -1: px, in_channels 3 or 4, h, w), which pass through page-locked staging that the session reuses only once the
+ * copy that read it has completed; sr_train_step returns once it no longer needs px.  Invalid items -- an unknown id, n outside
+ * 1 .. SR_TRAIN_MAX_BATCH, a crop smaller than the factor, a channel count other than 3 or 4 -- are SR_E_INVALID before any launch.  A
+ * workspace that does not fit is SR_E_NOMEM; the step is not taken and the session stays usable.  At most SR_TRAIN_RING steps are in
+ * flight: a step beyond that first waits for the oldest.  The session uses the context's stream and its backprop workspace: while it
+ * has steps in flight the context takes no other call (sr_train_params / sr_train_sync wait for them).  sr_destroy of the context
+ * waits for its sessions' steps and frees what they hold on the device; such a session refuses every call (SR_E_INVALID) but
+ * sr_train_destroy, which a caller still makes.
+ * store_bytes: the budget of resident images.  SR_TRAIN_STORE_AUTO: the device's free memory at creation less max(8 GiB, 1/8 of it),
+ * which leaves room for the step workspace and for validation passes on large images; 0: every image transient. */
+#define SR_TRAIN_STORE_AUTO ((size_t)-1)
+#define SR_TRAIN_MAX_BATCH 64
+#define SR_TRAIN_RING 64
+typedef struct sr_train sr_train;
+typedef struct {
+    int image;          /* id of a resident image, or -1: the pixels below */
+    const uint8_t* px;  /* image = -1: h x w x in_channels u8, host memory */
+    int in_channels, h, w;
+    int y0, x0;         /* crop origin in the source image */
+} sr_train_crop;
+int sr_train_create(sr_train** out, sr_ctx* ctx, const float* start_params, size_t n_params, int linear_loss, float l2, float lr,
+                    float beta1, float beta2, float eps, size_t store_bytes);
+/* Upload an image into the store: *id >= 0 when it is resident from now on, -1 when the store has no room (the image stays the caller's). */
+int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, int w, int* id);
+int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, int crop_w);
+/* Waits for every queued step; err_sums receives the err_sum of each step since the last sync (at the parameters before that step), in
+ * step order, at most cap of them; *n_steps their number.  err_sums may be NULL. */
+int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps);
+int sr_train_params(sr_train* t, float* out, size_t cap);  /* waits; the current parameters (cap >= n_params) */
+void sr_train_destroy(sr_train* t);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -11,6 +11,23 @@ pub struct SrCtx {
     _private: [u8; 0],
 }
 
+#[repr(C)]
+pub struct SrTrain {
+    _private: [u8; 0],
+}
+
+/// `sr_train_crop`: a resident image id, or -1 and host pixels; the crop origin.
+#[repr(C)]
+pub struct SrTrainCrop {
+    pub image: c_int,
+    pub px: *const u8,
+    pub in_channels: c_int,
+    pub h: c_int,
+    pub w: c_int,
+    pub y0: c_int,
+    pub x0: c_int,
+}
+
 pub const SR_OK: c_int = 0;
 pub const SR_E_HIP: c_int = -5;
 pub const SR_GRAPH_SR_NET: c_int = 0;
@@ -23,6 +40,9 @@ pub const SR_E_COMM: c_int = -9;
 pub const SR_E_DOMAIN: c_int = -10;
 pub const SR_HALO: c_int = 7;
 pub const SR_COMM_ID_BYTES: c_int = 128;
+pub const SR_TRAIN_MAX_BATCH: c_int = 64;
+pub const SR_TRAIN_RING: c_int = 64;
+pub const SR_TRAIN_STORE_AUTO: usize = usize::MAX;
 
 extern "C" {
     pub fn sr_rsr_decode(blob: *const u8, len: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
@@ -91,6 +111,14 @@ extern "C" {
     pub fn sr_backprop_rgba8(ctx: *mut SrCtx, params: *const f32, n_params: usize, hr: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, err_sum: *mut f64, n_elems: *mut usize, grad: *mut f32) -> c_int;
     pub fn sr_backprop_rgba8_dev(ctx: *mut SrCtx, d_params: *const f32, d_hr: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, d_err_sum: *mut f64, d_grad: *mut f32, stream: *mut c_void) -> c_int;
     pub fn sr_adam_step_dev(ctx: *mut SrCtx, d_params: *mut f32, d_m: *mut f32, d_v: *mut f32, d_grad: *const f32, n: usize, step: c_int, lr: f32, beta1: f32, beta2: f32, eps: f32, stream: *mut c_void) -> c_int;
+    pub fn sr_init_params(factor: c_int, seed: u64, out: *mut f32, cap: usize) -> c_int;
+    pub fn sr_set_params(ctx: *mut SrCtx, params: *const f32, n_params: usize) -> c_int;
+    pub fn sr_train_create(out: *mut *mut SrTrain, ctx: *mut SrCtx, start_params: *const f32, n_params: usize, linear_loss: c_int, l2: f32, lr: f32, beta1: f32, beta2: f32, eps: f32, store_bytes: usize) -> c_int;
+    pub fn sr_train_add_image(t: *mut SrTrain, px: *const u8, in_channels: c_int, h: c_int, w: c_int, id: *mut c_int) -> c_int;
+    pub fn sr_train_step(t: *mut SrTrain, items: *const SrTrainCrop, n: c_int, crop_h: c_int, crop_w: c_int) -> c_int;
+    pub fn sr_train_sync(t: *mut SrTrain, err_sums: *mut f64, cap: usize, n_steps: *mut usize) -> c_int;
+    pub fn sr_train_params(t: *mut SrTrain, out: *mut f32, cap: usize) -> c_int;
+    pub fn sr_train_destroy(t: *mut SrTrain);
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

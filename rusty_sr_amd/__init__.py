@@ -3,7 +3,7 @@ millardjn/rusty_sr v1.  The compute lives in libsrhip.so (hand-written HIP,
 C ABI in include/srhip.h); this package is the thin host side."""
 from . import rsr  # noqa: F401
 from .engine import (  # noqa: F401
-    CHANNELS, FACTOR, DataShape, Engine, Graph, NodeData, Trainer, bilinear_net, downsample_net, img_to_data, sr_net,
+    CHANNELS, FACTOR, DataShape, Engine, Graph, NodeData, Trainer, bilinear_net, downsample_net, img_to_data, init_params, sr_net,
     comm_init_all, upscale_batch_multi, upscale_multi, upscale_sharded_all, validation_psnr,
 )
 from ._lib import SrError  # noqa: F401

@@ -15,6 +15,16 @@ SR_E_HIP, SR_E_NOMEM, SR_E_BYTEVEC, SR_E_HALO, SR_E_COMM, SR_E_DOMAIN = -5, -6, 
 SR_COMM_ID_BYTES = 128
 SR_PRECISION_F32, SR_PRECISION_SPLIT_F16 = 0, 1
 SR_GRAPH_SR_NET, SR_GRAPH_BILINEAR, SR_GRAPH_DOWNSAMPLE = 0, 1, 2
+SR_TRAIN_STORE_AUTO = (1 << (8 * C.sizeof(C.c_size_t))) - 1
+SR_TRAIN_MAX_BATCH = 64
+SR_TRAIN_RING = 64
+
+
+class TrainCrop(C.Structure):
+    """sr_train_crop (include/srhip.h): a resident image id, or -1 and host pixels; the crop origin."""
+    _fields_ = [("image", C.c_int), ("px", C.c_void_p), ("in_channels", C.c_int), ("h", C.c_int), ("w", C.c_int),
+                ("y0", C.c_int), ("x0", C.c_int)]
+
 
 # every symbol include/srhip.h declares: (restype, argtypes)
 _vp, _fp, _u8p, _dp = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
@@ -72,6 +82,14 @@ SYMBOLS = {
     "sr_backprop_rgba8": (_i, [_vp, _fp, _sz, _u8p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _dp, C.POINTER(_sz), _fp]),
     "sr_backprop_rgba8_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
     "sr_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp]),
+    "sr_init_params": (_i, [_i, C.c_uint64, _fp, _sz]),
+    "sr_set_params": (_i, [_vp, _fp, _sz]),
+    "sr_train_create": (_i, [C.POINTER(_vp), _vp, _fp, _sz, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _sz]),
+    "sr_train_add_image": (_i, [_vp, _u8p, _i, _i, _i, C.POINTER(_i)]),
+    "sr_train_step": (_i, [_vp, C.POINTER(TrainCrop), _i, _i, _i]),
+    "sr_train_sync": (_i, [_vp, _dp, _sz, C.POINTER(_sz)]),
+    "sr_train_params": (_i, [_vp, _fp, _sz]),
+    "sr_train_destroy": (None, [_vp]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -259,6 +259,78 @@ void pack_lin_split(std::vector<float>& dst, int f) {
                     }
 }
 
+// Every parameter of sr_net(factor) in the layouts the kernels read, one vector (sr_create uploads it, sr_set_params copies it over the
+// upload); the segment offsets go to c (they depend on the factor alone).  *split_ok: every conv weight can be carried as a pair of halves.
+std::vector<float> pack_params(sr_ctx* c, const float* params, int factor, bool* split_ok) {
+    std::vector<float> host, w;
+    auto push = [&](const std::vector<float>& v) {
+        const size_t off = host.size();
+        host.insert(host.end(), v.begin(), v.end());
+        while (host.size() % 64) host.push_back(0.0f);  // keep 256-B alignment
+        return off;
+    };
+    auto vec32 = [&](size_t off, int n) {
+        std::vector<float> v(32, 0.0f);
+        for (int i = 0; i < n; ++i) v[i] = params[off + i];
+        return v;
+    };
+    const ParamLayout L(factor);
+    pack_conv0(w, params + L.conv0);
+    c->off_w0 = push(w);
+    pack_conv0_split(w, params + L.conv0);
+    c->off_w0h = push(w);
+    for (int split = 0; split < 2; ++split) {  // exact-f32 chunks, then the same stages in split-half form
+        auto ident = [](int, int j) { return j; };
+        auto expand = [&](int nt, int j) { return split ? expand_channel_t(factor, nt, j) : expand_channel(factor, nt, j); };
+        const bool h16 = split != 0;  // stages 1-3 of the split-half mode on 16x16x32 MFMAs: their own step order
+        auto conv = [&](const float* wp, int ks) { if (h16) pack_steps_h16(w, wp, ks); else pack_steps(w, wp, ks, 1, split != 0, ident); };
+        auto exp3 = [&](const float* wp) { pack_steps(w, wp, 3, expand_tiles(factor), split != 0, expand); };
+        size_t* off = split ? c->off_wh : c->off_w;
+        w.clear(); conv(params + L.conv1, 5);
+        off[1] = push(w);
+        w.clear(); conv(params + L.conv2, 5); conv(params + L.conv5, 3);
+        off[2] = push(w);
+        w.clear(); conv(params + L.conv3, 5); conv(params + L.conv6, 3); conv(params + L.conv8, 3);
+        off[3] = push(w);
+        w.clear();
+        exp3(params + L.conv7); exp3(params + L.conv9); exp3(params + L.conv10);
+        if (split) pack_lin_split(w, factor);  // the split-half mode: on the f16 pipe too, with exact integer weights (lin_mfma_h)
+        else pack_lin(w, factor);
+        off[4] = push(w);
+    }
+    w.clear(); pack_steps_wino(w, params + L.conv1);
+    c->off_wino1 = push(w);
+    w.clear(); pack_steps_wino(w, params + L.conv2); pack_steps(w, params + L.conv5, 3, 1, false, [](int, int j) { return j; });
+    c->off_wino2 = push(w);
+    const size_t boff[4] = {L.f_bias, L.l_bias[0], L.l_bias[1], L.l_bias[2]};
+    const size_t aoff[4] = {L.f_activ, L.l_activ[0], L.l_activ[1], L.l_activ[2]};
+    for (int s = 0; s < 4; ++s) c->off_bias[s] = push(vec32(boff[s], 32));
+    for (int s = 0; s < 4; ++s) c->off_beta[s] = push(vec32(aoff[s], 32));
+    {   // expand_bias in the triple layout, 32 floats per N-tile
+        std::vector<float> eb((size_t)expand_tiles(factor) * 32, 0.0f);
+        for (int nt = 0; nt < expand_tiles(factor); ++nt)
+            for (int j = 0; j < 32; ++j) {
+                const int ch = expand_channel(factor, nt, j);
+                if (ch >= 0) eb[nt * 32 + j] = params[L.exp_bias + ch];
+            }
+        c->off_bias[4] = push(eb);
+    }
+    // the split-half mode carries every conv weight as a pair of halves: all of them finite and below the largest half, or the mode is refused
+    bool ok = true;
+    for (size_t k = L.conv1; k < L.end && ok; ++k) ok = std::fabs(params[k]) < 65504.0f;   // (false for NaN too)
+    for (size_t k = L.conv0; k < L.conv0 + 2400 && ok; ++k) ok = std::fabs(params[k]) < 65504.0f;
+    *split_ok = ok;
+    return host;
+}
+
+// FNV-1a over the parameter bits: contexts that share a sharded call must hold the same parameters
+unsigned long long params_fnv(const float* params, size_t n) {
+    unsigned long long hsh = 1469598103934665603ull;
+    const unsigned char* pb = (const unsigned char*)params;
+    for (size_t i = 0; i < n * sizeof(float); ++i) { hsh ^= pb[i]; hsh *= 1099511628211ull; }
+    return hsh;
+}
+
 }  // namespace
 
 extern "C" {
@@ -342,12 +414,7 @@ int sr_create_graph(sr_ctx** out, int graph, const float* params, size_t n_param
                                                {"forkshare", "SRHIP_FORKSHARE"}, {"forkmin", "SRHIP_FORKMIN"}, {"forktune", "SRHIP_FORKTUNE"}, {"halo", "SRHIP_HALO"}};
     for (const auto& sw : kSwitch)
         if (const char* e = getenv(sw[1])) (void)sr_set_experiment(c, sw[0], e);
-    {   // FNV-1a over the parameter bits: contexts that share a sharded call must hold the same parameters
-        unsigned long long hsh = 1469598103934665603ull;
-        const unsigned char* pb = (const unsigned char*)params;
-        for (size_t i = 0; i < n_params * sizeof(float); ++i) { hsh ^= pb[i]; hsh *= 1099511628211ull; }
-        c->params_hash = hsh;
-    }
+    c->params_hash = params_fnv(params, n_params);
     // SRHIP_TRACE=1: where sr_create spends its time (a one-shot process pays it once per image)
     const bool trace = getenv("SRHIP_TRACE") != nullptr;
     auto t_last = std::chrono::steady_clock::now();
@@ -380,63 +447,9 @@ int sr_create_graph(sr_ctx** out, int graph, const float* params, size_t n_param
             mark("quantiser table");
             return SR_OK;
         }
-        // ---- pack every parameter once, in the layouts the kernels read
-        std::vector<float> host, w;
-        auto push = [&](const std::vector<float>& v) {
-            const size_t off = host.size();
-            host.insert(host.end(), v.begin(), v.end());
-            while (host.size() % 64) host.push_back(0.0f);  // keep 256-B alignment
-            return off;
-        };
-        auto vec32 = [&](size_t off, int n) {
-            std::vector<float> v(32, 0.0f);
-            for (int i = 0; i < n; ++i) v[i] = params[off + i];
-            return v;
-        };
-        const ParamLayout L(factor);
-        pack_conv0(w, params + L.conv0);
-        c->off_w0 = push(w);
-        pack_conv0_split(w, params + L.conv0);
-        c->off_w0h = push(w);
-        for (int split = 0; split < 2; ++split) {  // exact-f32 chunks, then the same stages in split-half form
-            auto ident = [](int, int j) { return j; };
-            auto expand = [&](int nt, int j) { return split ? expand_channel_t(factor, nt, j) : expand_channel(factor, nt, j); };
-            const bool h16 = split != 0;  // stages 1-3 of the split-half mode on 16x16x32 MFMAs: their own step order
-            auto conv = [&](const float* wp, int ks) { if (h16) pack_steps_h16(w, wp, ks); else pack_steps(w, wp, ks, 1, split != 0, ident); };
-            auto exp3 = [&](const float* wp) { pack_steps(w, wp, 3, expand_tiles(factor), split != 0, expand); };
-            size_t* off = split ? c->off_wh : c->off_w;
-            w.clear(); conv(params + L.conv1, 5);
-            off[1] = push(w);
-            w.clear(); conv(params + L.conv2, 5); conv(params + L.conv5, 3);
-            off[2] = push(w);
-            w.clear(); conv(params + L.conv3, 5); conv(params + L.conv6, 3); conv(params + L.conv8, 3);
-            off[3] = push(w);
-            w.clear();
-            exp3(params + L.conv7); exp3(params + L.conv9); exp3(params + L.conv10);
-            if (split) pack_lin_split(w, factor);  // the split-half mode: on the f16 pipe too, with exact integer weights (lin_mfma_h)
-            else pack_lin(w, factor);
-            off[4] = push(w);
-        }
-        w.clear(); pack_steps_wino(w, params + L.conv1);
-        c->off_wino1 = push(w);
-        w.clear(); pack_steps_wino(w, params + L.conv2); pack_steps(w, params + L.conv5, 3, 1, false, [](int, int j) { return j; });
-        c->off_wino2 = push(w);
-        const size_t boff[4] = {L.f_bias, L.l_bias[0], L.l_bias[1], L.l_bias[2]};
-        const size_t aoff[4] = {L.f_activ, L.l_activ[0], L.l_activ[1], L.l_activ[2]};
-        for (int s = 0; s < 4; ++s) c->off_bias[s] = push(vec32(boff[s], 32));
-        for (int s = 0; s < 4; ++s) c->off_beta[s] = push(vec32(aoff[s], 32));
-        {   // expand_bias in the triple layout, 32 floats per N-tile
-            std::vector<float> eb((size_t)expand_tiles(factor) * 32, 0.0f);
-            for (int nt = 0; nt < expand_tiles(factor); ++nt)
-                for (int j = 0; j < 32; ++j) {
-                    const int ch = expand_channel(factor, nt, j);
-                    if (ch >= 0) eb[nt * 32 + j] = params[L.exp_bias + ch];
-                }
-            c->off_bias[4] = push(eb);
-        }
-        // the split-half mode carries every conv weight as a pair of halves: all of them finite and below the largest half, or the mode is refused
-        for (size_t k = L.conv1; k < L.end && c->split_ok; ++k) c->split_ok = std::fabs(params[k]) < 65504.0f;   // (false for NaN too)
-        for (size_t k = L.conv0; k < L.conv0 + 2400 && c->split_ok; ++k) c->split_ok = std::fabs(params[k]) < 65504.0f;
+        bool split_ok = true;
+        const std::vector<float> host = pack_params(c, params, factor, &split_ok);
+        c->split_ok = split_ok;
         mark("weight packing (host)");
         HIPCHK(c, hipHostMalloc((void**)&c->h_domain, 64, hipHostMallocMapped));
         *c->h_domain = 0;
@@ -462,6 +475,7 @@ void sr_destroy(sr_ctx* c) {
     sr_device_guard restore_device;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    sr_train_detach_all(c);
     sr_comm_release(c);
     sr_valid_release(c);
     sr_grad_release(c);
@@ -502,6 +516,28 @@ int sr_set_precision(sr_ctx* c, int mode) {
         c->last_h = c->last_w = 0;
     }
     c->precision = mode;
+    return SR_OK;
+}
+
+int sr_set_params(sr_ctx* c, const float* params, size_t n_params) {
+    if (!c) {
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return SR_E_NO_DEVICE; }
+        return SR_E_INVALID;
+    }
+    sr_plan_clear(c);
+    if (c->graph != SR_GRAPH_SR_NET || !params) return SR_E_INVALID;
+    if (n_params != ParamLayout(c->factor).end) return SR_E_PARAM_COUNT;
+    bool split_ok = true;
+    const std::vector<float> host = pack_params(c, params, c->factor, &split_ok);
+    if (c->precision == SR_PRECISION_SPLIT_F16 && !split_ok) return SR_E_DOMAIN;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (hipStream_t s : {c->stream, c->stream2, c->copy_in, c->copy_out})
+        if (s) HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipMemcpy(c->d_params, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->split_ok = split_ok;
+    c->params_hash = params_fnv(params, n_params);
     return SR_OK;
 }
 

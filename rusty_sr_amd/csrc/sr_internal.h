@@ -123,6 +123,8 @@ struct sr_ctx {
     // ---- backpropagation (sr_grad.cpp): grown on demand, freed by sr_destroy
     void* d_gws = nullptr; size_t gws_cap = 0;      // saved forward state, gradients of the nodes, partials (sr_grad_workspace_bytes)
     void* d_gin = nullptr; size_t gin_cap = 0;      // host-pointer calls: params, HR batch, pooled LR batch, gradient
+    // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
+    std::vector<sr_train*> trains;
 };
 
 inline void sr_plan_clear(sr_ctx* c) {
@@ -231,3 +233,17 @@ hipError_t sr_launch_grad(const sr_grad_plan& p, hipStream_t s);
 hipError_t sr_launch_grad_adam(float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, float lr, float beta1, float beta2,
                                float eps, float bc1, float bc2, hipStream_t s);
 int sr_valid_ensure_table(sr_ctx* c);  // sr_valid.cpp: the 512-float table behind d_vtab, uploaded on first use
+
+// ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)
+// One crop of a step, as the crop kernel reads it: px is device memory, 4-byte aligned when ch = 4 (rows are then read as whole pixels).
+struct sr_train_crop_desc {
+    const uint8_t* px;
+    int ch, h, w, y0, x0;
+};
+struct sr_train_crop_args {  // passed by value: a step whose images are resident uploads nothing
+    sr_train_crop_desc d[SR_TRAIN_MAX_BATCH];
+    int n, crop_h, crop_w;
+};
+void sr_train_detach_all(sr_ctx* c);  // sr_train.cpp: called by sr_destroy; a detached session refuses every call but sr_train_destroy
+// the n crops -> n x crop_h x crop_w x 3 u8 at d_out, whose allocation holds whole dwords (ceil(n crop_h crop_w 3 / 4) of them)
+hipError_t sr_launch_train_crop(const sr_train_crop_args& a, uint32_t* d_out, hipStream_t s);

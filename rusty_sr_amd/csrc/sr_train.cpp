@@ -1,0 +1,352 @@
+// sr_train.cpp -- the training session of include/srhip.h (sr_train_*) and the reference's parameter initialisation (sr_init_params): the
+// loop of the reference's `train` (main.rs:181-257) without its file handling, which the CLI does.  A step is the crop gather
+// (sr_train.hip), sr_backprop_rgba8_dev and sr_adam_step_dev, queued on the context's stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "sr_internal.h"
+
+namespace {
+
+bool no_device() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return n <= 0;
+}
+
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }
+
+struct SplitMix64 {
+    uint64_t s;
+    uint64_t next() {
+        uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        return z ^ (z >> 31);
+    }
+    double uniform() { return (double)(next() >> 11) * 0x1.0p-53; }  // [0, 1)
+};
+
+constexpr int kStage = 2;  // page-locked staging slots of transient images
+
+}  // namespace
+
+struct sr_train {
+    sr_ctx* c = nullptr;
+    int np = 0;
+    bool linear = false;
+    float l2 = 0, lr = 0, beta1 = 0, beta2 = 0, eps = 0;
+    float* d_state = nullptr;  // parameters, first and second moments, gradient: 4 slices of round256(np floats)
+    float *d_p = nullptr, *d_m = nullptr, *d_v = nullptr, *d_g = nullptr;
+    // err_sum of each step: a ring of mapped host doubles the backprop's sum kernel writes, each slot free once its step's event has fired
+    double* h_err = nullptr;
+    double* d_err = nullptr;
+    hipEvent_t ring_ev[SR_TRAIN_RING] = {nullptr};
+    long long queued = 0, harvested = 0;  // steps issued (= Adam's step count) / whose err_sum has been read
+    std::vector<double> done;              // err_sums read since the last sync
+    // the image store: one allocation per resident image, within the budget
+    struct Img { uint8_t* d; int ch, h, w; };
+    std::vector<Img> images;
+    size_t store_budget = 0, store_used = 0;
+    // per-step buffers, reused in stream order
+    void* d_batch = nullptr; size_t batch_cap = 0;  // the crops, u8
+    void* d_trans = nullptr; size_t trans_cap = 0;  // the rows of transient images a step's crops read
+    void* h_stage[kStage] = {nullptr}; size_t stage_cap[kStage] = {0};
+    hipEvent_t stage_ev[kStage] = {nullptr};
+    bool stage_pending[kStage] = {false};
+    int stage_next = 0;
+    int last_n = 0, last_h = 0, last_w = 0;  // shape of the last step: another one may grow the backprop workspace
+};
+
+namespace {
+
+// A buffer of the session that steps in flight may still read: grown only after the stream has drained.
+int grow(sr_ctx* c, hipStream_t s, void** p, size_t* cap, size_t bytes) {
+    if (bytes <= *cap) return SR_OK;
+    HIPCHK(c, hipStreamSynchronize(s));
+    return sr_ensure_buf(c, p, cap, round256(bytes));
+}
+
+// Read the err_sum of the oldest step in flight (waits for it).
+int harvest_one(sr_train* t) {
+    const int slot = (int)(t->harvested % SR_TRAIN_RING);
+    HIPCHK(t->c, hipEventSynchronize(t->ring_ev[slot]));
+    const double v = ((volatile double*)t->h_err)[slot];
+    t->done.push_back(v);
+    ++t->harvested;
+    return SR_OK;
+}
+
+int drain(sr_train* t) {
+    HIPCHK(t->c, hipStreamSynchronize(t->c->stream));
+    while (t->harvested < t->queued) {
+        const int rc = harvest_one(t);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
+void release(sr_train* t) {
+    sr_ctx* c = t->c;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (auto& im : t->images) (void)hipFree(im.d);
+    if (t->d_state) (void)hipFree(t->d_state);
+    if (t->d_batch) (void)hipFree(t->d_batch);
+    if (t->d_trans) (void)hipFree(t->d_trans);
+    if (t->h_err) (void)hipHostFree(t->h_err);
+    for (int k = 0; k < kStage; ++k) {
+        if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
+        if (t->stage_ev[k]) (void)hipEventDestroy(t->stage_ev[k]);
+    }
+    for (auto& e : t->ring_ev) if (e) (void)hipEventDestroy(e);
+}
+
+}  // namespace
+
+void sr_train_detach_all(sr_ctx* c) {
+    for (sr_train* t : c->trains) {
+        release(t);
+        t->c = nullptr;
+    }
+    c->trains.clear();
+}
+
+extern "C" {
+
+int sr_init_params(int factor, uint64_t seed, float* out, size_t cap) {
+    const int np = sr_num_params_factor(factor);
+    if (np < 0) return SR_E_FACTOR;
+    if (!out || cap < (size_t)np) return SR_E_INVALID;
+    // segments in .rsr order (network.rs:33-72): (length, fan_in, multiplier); fan_in 0: a bias (0), -1: a BeLU beta
+    const int E = 3 * factor * factor;
+    const struct { int n, fan_in; double mult; } seg[] = {
+        {2400, 75, 1.0},                                    // conv0: 5x5, 3 -> 32
+        {32, 0, 0}, {32, -1, 0}, {E, 0, 0},                 // f_bias, f_activ, expand_bias
+        {32, 0, 0}, {32, 0, 0}, {32, 0, 0},                 // l1..l3 biases
+        {32, -1, 0}, {32, -1, 0}, {32, -1, 0},              // l1..l3 activations
+        {25600, 800, 0.1}, {25600, 800, 0.1}, {25600, 800, 0.1},  // conv1..conv3: 5x5, 32 -> 32
+        {9216, 288, 0.1}, {9216, 288, 0.1},                 // conv5, conv6: 3x3, 32 -> 32
+        {E * 288, 288, 0.1}, {9216, 288, 0.1},              // conv7 (3x3, 32 -> 3 f^2), conv8
+        {E * 288, 288, 0.1}, {E * 288, 288, 0.1},           // conv9, conv10
+    };
+    SplitMix64 rng{seed};
+    size_t o = 0;
+    for (const auto& s : seg) {
+        for (int i = 0; i < s.n; ++i, ++o) {
+            if (s.fan_in == 0) out[o] = 0.0f;
+            else if (s.fan_in < 0) out[o] = i % 2 == 0 ? 1.0f : 0.0f;
+            else {
+                const double std = s.mult * std::sqrt(2.0 / s.fan_in);
+                const double u1 = rng.uniform(), u2 = rng.uniform();
+                out[o] = (float)(std * std::sqrt(-2.0 * std::log(1.0 - u1)) * std::cos(2.0 * 3.14159265358979323846 * u2));
+            }
+        }
+    }
+    return o == (size_t)np ? SR_OK : SR_E_INVALID;
+}
+
+int sr_train_create(sr_train** out, sr_ctx* c, const float* start_params, size_t n_params, int linear_loss, float l2, float lr, float beta1,
+                    float beta2, float eps, size_t store_bytes) {
+    if (!c && no_device()) return SR_E_NO_DEVICE;
+    if (!out || !c || !start_params) return SR_E_INVALID;
+    *out = nullptr;
+    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    const int np = sr_num_params_factor(c->factor);
+    if (np < 0 || n_params != (size_t)np) return SR_E_PARAM_COUNT;
+    sr_train* t = new (std::nothrow) sr_train();
+    if (!t) return SR_E_NOMEM;
+    t->c = c;
+    t->np = np;
+    t->linear = linear_loss != 0;
+    t->l2 = l2; t->lr = lr; t->beta1 = beta1; t->beta2 = beta2; t->eps = eps;
+    sr_device_guard restore_device;
+    const int rc = [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        int r = sr_ensure_streams(c, false);
+        if (r != SR_OK) return r;
+        const size_t slice = round256((size_t)np * sizeof(float));
+        HIPCHK(c, hipMalloc((void**)&t->d_state, 4 * slice));
+        t->d_p = t->d_state;
+        t->d_m = (float*)((char*)t->d_state + slice);
+        t->d_v = (float*)((char*)t->d_state + 2 * slice);
+        t->d_g = (float*)((char*)t->d_state + 3 * slice);
+        HIPCHK(c, hipMemcpy(t->d_p, start_params, (size_t)np * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemset(t->d_m, 0, 2 * slice));
+        HIPCHK(c, hipHostMalloc((void**)&t->h_err, SR_TRAIN_RING * sizeof(double), hipHostMallocMapped));
+        HIPCHK(c, hipHostGetDevicePointer((void**)&t->d_err, t->h_err, 0));
+        for (auto& e : t->ring_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (auto& e : t->stage_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (store_bytes == SR_TRAIN_STORE_AUTO) {
+            size_t free_b = 0, total_b = 0;
+            HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+            const size_t keep = std::max<size_t>((size_t)8 << 30, free_b / 8);
+            store_bytes = free_b > keep ? free_b - keep : 0;
+        }
+        t->store_budget = store_bytes;
+        return SR_OK;
+    }();
+    if (rc != SR_OK) {
+        release(t);
+        delete t;
+        return rc;
+    }
+    c->trains.push_back(t);
+    *out = t;
+    return SR_OK;
+}
+
+int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, int w, int* id) {
+    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !px || !id || (in_channels != 3 && in_channels != 4) || h < 1 || w < 1) return SR_E_INVALID;
+    *id = -1;
+    sr_ctx* c = t->c;
+    const size_t bytes = (size_t)h * w * in_channels, alloc = round256(bytes);
+    if (alloc > t->store_budget - std::min(t->store_budget, t->store_used) || t->images.size() >= (size_t)INT32_MAX) return SR_OK;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, alloc) != hipSuccess) {  // the device is fuller than the budget said: no room, not an error
+        (void)hipGetLastError();
+        return SR_OK;
+    }
+    const hipError_t e = hipMemcpy(d, px, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    t->store_used += alloc;
+    t->images.push_back({d, in_channels, h, w});
+    *id = (int)t->images.size() - 1;
+    return SR_OK;
+}
+
+int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, int crop_w) {
+    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !items || n < 1 || n > SR_TRAIN_MAX_BATCH) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    if (crop_h < c->factor || crop_w < c->factor) return SR_E_INVALID;
+    // every item is checked before anything is launched; the rows of each transient image that its crop can reach are what is staged
+    size_t trans_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const sr_train_crop& it = items[i];
+        if (it.image >= 0) {
+            if ((size_t)it.image >= t->images.size()) return SR_E_INVALID;
+        } else if (it.image == -1) {
+            if (!it.px || (it.in_channels != 3 && it.in_channels != 4) || it.h < 1 || it.w < 1) return SR_E_INVALID;
+            const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + crop_h, 0, it.h);
+            trans_bytes += round256((size_t)(r1 - r0) * it.w * it.in_channels);
+        } else {
+            return SR_E_INVALID;
+        }
+    }
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (t->queued - t->harvested >= SR_TRAIN_RING) {  // the ring is full: wait for the oldest step
+        const int rc = harvest_one(t);
+        if (rc != SR_OK) return rc;
+    }
+    if (n != t->last_n || crop_h != t->last_h || crop_w != t->last_w) {  // the backprop workspace may grow: nothing in flight may use it
+        HIPCHK(c, hipStreamSynchronize(s));
+        t->last_n = t->last_h = t->last_w = 0;
+    }
+    const size_t batch_bytes = (size_t)n * crop_h * crop_w * 3;
+    int rc = grow(c, s, &t->d_batch, &t->batch_cap, batch_bytes + 4);
+    if (rc == SR_OK && trans_bytes) rc = grow(c, s, &t->d_trans, &t->trans_cap, trans_bytes);
+    if (rc != SR_OK) return rc;
+    sr_train_crop_args a;
+    a.n = n; a.crop_h = crop_h; a.crop_w = crop_w;
+    const int k = t->stage_next;
+    if (trans_bytes) {
+        if (t->stage_pending[k]) HIPCHK(c, hipEventSynchronize(t->stage_ev[k]));  // the copy that read this slot last has completed
+        t->stage_pending[k] = false;
+        if (t->stage_cap[k] < trans_bytes) {
+            if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
+            t->h_stage[k] = nullptr;
+            t->stage_cap[k] = 0;
+            HIPCHK(c, hipHostMalloc(&t->h_stage[k], round256(trans_bytes), hipHostMallocPortable));
+            t->stage_cap[k] = round256(trans_bytes);
+        }
+    }
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const sr_train_crop& it = items[i];
+        if (it.image != -1) continue;
+        const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + crop_h, 0, it.h);
+        const size_t row = (size_t)it.w * it.in_channels, bytes = (size_t)(r1 - r0) * row;
+        if (bytes) memcpy((char*)t->h_stage[k] + off, it.px + (size_t)r0 * row, bytes);
+        // the staged rows as an image of r1 - r0 rows: the crop's rows outside them are outside the source image too
+        a.d[i] = {(const uint8_t*)t->d_trans + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0};
+        off += round256(bytes);
+    }
+    if (trans_bytes) {
+        HIPCHK(c, hipMemcpyAsync(t->d_trans, t->h_stage[k], trans_bytes, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipEventRecord(t->stage_ev[k], s));
+        t->stage_pending[k] = true;
+        t->stage_next = (k + 1) % kStage;
+    }
+    for (int i = 0; i < n; ++i) {
+        const sr_train_crop& it = items[i];
+        if (it.image < 0) continue;
+        const sr_train::Img& im = t->images[(size_t)it.image];
+        a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0};
+    }
+    HIPCHK(c, sr_launch_train_crop(a, (uint32_t*)t->d_batch, s));
+    const int f = c->factor;
+    const size_t n_elems = (size_t)n * 3 * ((size_t)f * (crop_h / f)) * ((size_t)f * (crop_w / f));
+    const int slot = (int)(t->queued % SR_TRAIN_RING);
+    rc = sr_backprop_rgba8_dev(c, t->d_p, (const uint8_t*)t->d_batch, 3, n, crop_h, crop_w, t->linear ? 1 : 0, (float)(1.0 / (double)n_elems),
+                               t->l2, t->d_err + slot, t->d_g, s);
+    if (rc != SR_OK) return rc;  // (SR_E_NOMEM: the context freed its backprop buffers; the parameters are untouched)
+    t->last_n = n; t->last_h = crop_h; t->last_w = crop_w;
+    rc = sr_adam_step_dev(c, t->d_p, t->d_m, t->d_v, t->d_g, (size_t)t->np, (int)(t->queued + 1), t->lr, t->beta1, t->beta2, t->eps, s);
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, hipEventRecord(t->ring_ev[slot], s));
+    ++t->queued;
+    return SR_OK;
+}
+
+int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps) {
+    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(t->c, hipSetDevice(t->c->device));
+    const int rc = drain(t);
+    if (rc != SR_OK) return rc;
+    if (err_sums) std::copy_n(t->done.begin(), std::min(cap, t->done.size()), err_sums);
+    if (n_steps) *n_steps = t->done.size();
+    t->done.clear();
+    return SR_OK;
+}
+
+int sr_train_params(sr_train* t, float* out, size_t cap) {
+    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !out || cap < (size_t)t->np) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(t->c, hipSetDevice(t->c->device));
+    HIPCHK(t->c, hipStreamSynchronize(t->c->stream));
+    HIPCHK(t->c, hipMemcpy(out, t->d_p, (size_t)t->np * sizeof(float), hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+void sr_train_destroy(sr_train* t) {
+    if (!t) return;
+    if (t->c) {  // (a session whose context was destroyed first has released its device memory then: only the shell is left)
+        sr_device_guard restore_device;
+        if (hipSetDevice(t->c->device) != hipSuccess) (void)hipGetLastError();
+        auto& v = t->c->trains;
+        v.erase(std::remove(v.begin(), v.end(), t), v.end());
+        release(t);
+    }
+    delete t;
+}
+
+}  // extern "C"

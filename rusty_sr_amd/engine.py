@@ -293,6 +293,11 @@ class Engine:
     def num_params(self) -> int:
         return self._L.sr_num_params_factor(self.factor)
 
+    def set_params(self, params):
+        """Replace the inference weights (sr_set_params; synchronous -- finish this engine's own *_dev work first)."""
+        p = np.ascontiguousarray(params, dtype=np.float32)
+        _lib.check(self._L.sr_set_params(self._ctx, p.ctypes.data_as(C.POINTER(C.c_float)), p.size), self._ctx)
+
     def backprop(self, hr: np.ndarray, params, linear_loss: bool = False, loss_scale: Optional[float] = None, l2: float = 0.0):
         """HR batch (n,H,W,3|4) u8 (byte / 255, alpha dropped) or (n,H,W,3) f32 -> (err_sum, n_elems, grad): the squared error of
         sr_net(f) on the pooled batch against its f*(H//f) x f*(W//f) crop (of SrgbToLinear of both with linear_loss) and the gradient
@@ -544,46 +549,108 @@ def validation_psnr(engines, images, linear_loss: bool = False) -> float:
     return math.inf if err == 0.0 else -10.0 * math.log10(err / n)
 
 
+def init_params(factor: int = FACTOR, seed: int = 0) -> np.ndarray:
+    """The reference's g.init_params() for sr_net(factor) (sr_init_params; the seeded generator and the UNPINNED rules are in
+    include/srhip.h).  Host only."""
+    L = _lib.lib()
+    n = L.sr_num_params_factor(factor)
+    if n < 0:
+        raise _lib.SrError(_lib.SR_E_FACTOR)
+    out = np.empty(n, dtype=np.float32)
+    _lib.check(L.sr_init_params(factor, seed & 0xFFFFFFFFFFFFFFFF, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return out
+
+
 class Trainer:
-    """Minibatch Adam on the GPU (the optimisation loop of the reference's `train`, main.rs:181-257, without its data supply): parameters,
-    first and second moments live on the engine's device.  step(hr_batch) -> err_sum of that batch at the parameters before the step."""
+    """Minibatch Adam on the GPU (the optimisation loop of the reference's `train`, main.rs:181-257) over a training session of the
+    engine's context (sr_train_*): parameters, moments and an image store live on the engine's device.
+    step(hr_batch) -> err_sum of that batch at the parameters before the step (synchronous); add_image / step_crops queue steps on
+    random crops without waiting (sync() collects their err_sums)."""
 
     def __init__(self, engine: Engine, start_params, linear_loss: bool = False, l2: float = 1e-6, lr: float = 2e-3,
-                 beta1: float = 0.95, beta2: float = 0.995, eps: float = 1e-7):
-        import torch
+                 beta1: float = 0.95, beta2: float = 0.995, eps: float = 1e-7, store_bytes: Optional[int] = None):
         p = np.ascontiguousarray(start_params, dtype=np.float32)
         if p.size != engine.num_params():
             raise ValueError(f"expected {engine.num_params()} parameters, got {p.size}")
         self.engine = engine
-        self.device = torch.device("cuda", engine.device)
-        self._p = torch.from_numpy(p.copy()).to(self.device)
-        self._m = torch.zeros_like(self._p)
-        self._v = torch.zeros_like(self._p)
-        self._g = torch.empty_like(self._p)
-        self._err = torch.empty(1, dtype=torch.float64, device=self.device)
+        self._L = engine._L
+        self._t = C.c_void_p()
+        store = _lib.SR_TRAIN_STORE_AUTO if store_bytes is None else int(store_bytes)
+        _lib.check(self._L.sr_train_create(C.byref(self._t), engine._ctx, p.ctypes.data_as(C.POINTER(C.c_float)), p.size,
+                                           int(bool(linear_loss)), float(l2), float(lr), float(beta1), float(beta2), float(eps), store),
+                   engine._ctx)
         self.linear_loss, self.l2, self.lr, self.beta1, self.beta2, self.eps = linear_loss, l2, lr, beta1, beta2, eps
         self.steps = 0
+        self._pending = 0
+
+    def add_image(self, px) -> int:
+        """(h, w, 3|4) u8 -> the id of the image in the device store, or -1 when the store has no room."""
+        px = np.ascontiguousarray(px)
+        if px.dtype != np.uint8 or px.ndim != 3:
+            raise ValueError("expected (h, w, 3|4) u8 pixels")
+        h, w, c = px.shape
+        i = C.c_int()
+        _lib.check(self._L.sr_train_add_image(self._t, px.ctypes.data_as(C.POINTER(C.c_uint8)), c, h, w, C.byref(i)), self.engine._ctx)
+        return i.value
+
+    def step_crops(self, items, crop_h: int, crop_w: int) -> None:
+        """One step on crops, queued without waiting.  items: (image, y0, x0) with image an id of add_image or a (h, w, 3|4) u8 array."""
+        arr = (_lib.TrainCrop * max(len(items), 1))()
+        keep = []
+        for k, (img, y0, x0) in enumerate(items):
+            it = arr[k]
+            it.y0, it.x0 = int(y0), int(x0)
+            if isinstance(img, (int, np.integer)):
+                it.image = int(img)
+            else:
+                px = np.ascontiguousarray(img)
+                if px.dtype != np.uint8 or px.ndim != 3:
+                    raise ValueError("expected (h, w, 3|4) u8 pixels")
+                keep.append(px)
+                it.image, it.px = -1, px.ctypes.data
+                it.h, it.w, it.in_channels = px.shape
+        _lib.check(self._L.sr_train_step(self._t, arr, len(items), int(crop_h), int(crop_w)), self.engine._ctx)
+        self.steps += 1
+        self._pending += 1
+
+    def sync(self) -> List[float]:
+        """Wait for every queued step; the err_sum of each step since the last sync."""
+        buf = np.empty(max(self._pending, 1), dtype=np.float64)
+        n = C.c_size_t()
+        _lib.check(self._L.sr_train_sync(self._t, buf.ctypes.data_as(C.POINTER(C.c_double)), buf.size, C.byref(n)), self.engine._ctx)
+        self._pending = 0
+        return [float(v) for v in buf[:n.value]]
 
     def step(self, hr_batch) -> float:
-        """One backprop (loss_scale 1 / n_elems) and one Adam step.  hr_batch: (n,H,W,3|4) u8, numpy or a torch tensor."""
-        import torch
-        hr = hr_batch if isinstance(hr_batch, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(hr_batch))
-        hr = hr.to(self.device).contiguous()
-        if hr.dim() == 3:
+        """One backprop (loss_scale 1 / n_elems) and one Adam step on a whole batch.  hr_batch: (n,H,W,3|4) u8, numpy or a torch tensor."""
+        hr = hr_batch.cpu().numpy() if hasattr(hr_batch, "cpu") else np.asarray(hr_batch)
+        if hr.ndim == 3:
             hr = hr[None]
-        self.engine.backprop_dev(hr, self._p, self.linear_loss, None, self.l2, grad=self._g, err=self._err)
-        self.steps += 1
-        self.engine.adam_step_dev(self._p, self._m, self._v, self._g, self.steps, self.lr, self.beta1, self.beta2, self.eps)
-        return float(self._err.item())
+        n, h, w, _ = hr.shape
+        self.step_crops([(hr[i], 0, 0) for i in range(n)], h, w)
+        return self.sync()[-1]
 
     def params(self) -> np.ndarray:
-        return self._p.cpu().numpy()
+        out = np.empty(self.engine.num_params(), dtype=np.float32)
+        _lib.check(self._L.sr_train_params(self._t, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), self.engine._ctx)
+        return out
 
     def save(self, path: str):
         """Write the parameters as a .rsr file (bytevec, as the reference's train writes them, main.rs:213)."""
         from . import rsr
         with open(path, "wb") as f:
             f.write(rsr.encode(self.params()))
+
+    def close(self):
+        if self._t:
+            self._L.sr_train_destroy(self._t)
+            self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PinnedBuffer:

@@ -1,18 +1,20 @@
 // rusty_sr -- host CLI with the argv surface of millardjn/rusty_sr v1
-// (reference src/main.rs:33-178), driving the MI355X engine through libsrhip's C ABI.
+// (reference src/main.rs:33-258), driving the MI355X engine through libsrhip's C ABI.
 //
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
+//   rusty_sr train [-l] [-r] [-s START] [-v VAL_FOLDER] [-m N] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] <VALIDATION_FOLDER>
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
-// PSNR a parameter set reaches on a folder of HR images.  A first argument that is literally `validate` selects it (as `train` is
-// reserved); every other argv is the upscale surface, unchanged.
+// PSNR a parameter set reaches on a folder of HR images.  A first argument that is literally `train` or `validate` selects it; every
+// other argv is the upscale surface, unchanged.
 //
 // Differences from the reference, all outside the hot path: own codecs (PNG over zlib, baseline + progressive JPEG, GIF,
 // TIFF, TGA, ICO, PPM/PGM/PBM, BMP in; PNG, JPEG, BMP, PPM out by extension -- of what the reference's `image` crate reads
-// only WebP is missing), the `train` sub-command
-// is not part of this build (its validation pass is, as `validate`), and three extra options that cannot collide with the
-// reference's (-p -c -d): --device N, --precision f32|split_f16, --timing.
+// only WebP is missing), and extra options that cannot collide with the reference's: --device N, --precision f32|split_f16,
+// --timing; for `train` --seed N (initial parameters, shuffles and crops are seeded; the reference's are random) and --steps N (stop
+// early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
+// writes it after step 1 and every 100 steps).
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -22,8 +24,10 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <deque>
 #include <filesystem>
 #include <mutex>
+#include <random>
 #include <string>
 #include <thread>
 #include <vector>
@@ -46,7 +50,7 @@ const char* kUsage =
     "Rusty SR v0.1.1 (MI355X engine)\n"
     "A convolutional neural network trained to upscale images\n\n"
     "USAGE:\n    rusty_sr [FLAGS] [OPTIONS] <INPUT_FILE> <OUTPUT_FILE>\n    rusty_sr validate [FLAGS] [OPTIONS] <VALIDATION_FOLDER>\n"
-    "    rusty_sr train ...   (not part of this build)\n\n"
+    "    rusty_sr train [FLAGS] [OPTIONS] <PARAMETER_FILE> <TRAINING_FOLDER>\n\n"
     "FLAGS:\n    -d, --downsample    Perform downscaling rather than upscaling\n    -h, --help          Prints help information\n"
     "    -V, --version       Prints version information\n        --timing        Print device / transfer times on stderr\n\n"
     "OPTIONS:\n    -c, --custom <PARAMETER_FILE>    Sets a custom parameter file (.rsr) to use with the neural net\n"
@@ -56,7 +60,8 @@ const char* kUsage =
     "        --devices <N,N,...>          spread one image over several GPUs (row shares, halo rows from the image)\n"
     "        --precision <MODE>           f32 (exact) or split_f16 (2x faster, same 1e-4 parity bar) [default: f32]\n\n"
     "ARGS:\n    <INPUT_FILE>     Sets the input image to upscale\n    <OUTPUT_FILE>    Sets the output file to write/overwrite (.png recommended)\n\n"
-    "SUBCOMMANDS:\n    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
+    "SUBCOMMANDS:\n    train       Trains a new set of neural network parameters on the GPU (rusty_sr train --help)\n"
+    "    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
     "                (rusty_sr validate --help)\n";
 
 const char* kValidateUsage =
@@ -113,6 +118,101 @@ bool decodable(const std::filesystem::path& p) {
     return false;
 }
 
+// Decoding ahead of the GPU (validate, train): up to 16 host threads (OMP_NUM_THREADS if set) decode queued files; at most `window`
+// decoded images wait to be taken.  Jobs are numbered in push order; take(j) blocks until job j is decoded.  stop() wakes every waiter.
+class DecoderPool {
+public:
+    DecoderPool(const std::vector<std::string>& files, size_t most_jobs, size_t extra_window = 0) : files_(files) {
+        unsigned threads = 16;
+        if (const char* e = getenv("OMP_NUM_THREADS")) { const int v = atoi(e); if (v > 0) threads = (unsigned)std::min(v, 16); }
+        threads = (unsigned)std::max<size_t>(1, std::min<size_t>(threads, most_jobs));
+        window_ = 2 * (size_t)threads + extra_window;
+        for (unsigned t = 0; t < threads; ++t) workers_.emplace_back([this] { work(); });
+    }
+    ~DecoderPool() {
+        stop();
+        for (auto& t : workers_) t.join();
+    }
+    size_t push(size_t file) {
+        std::lock_guard<std::mutex> lk(mu_);
+        jobs_.push_back(Slot{file, {}, {}, 0});
+        cv_.notify_all();
+        return base_ + jobs_.size() - 1;
+    }
+    // false: the file did not decode (err says why) or the pool was stopped (err empty)
+    bool take(size_t job, srpng::Image& img, std::string& err) {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return stop_ || jobs_[job - base_].state != 0; });
+        if (stop_) { err.clear(); return false; }
+        Slot& sl = jobs_[job - base_];
+        const bool ok = sl.state == 1;
+        img = std::move(sl.img);
+        err = std::move(sl.err);
+        sl.state = 3;
+        while (!jobs_.empty() && jobs_.front().state == 3) { jobs_.pop_front(); ++base_; }
+        cv_.notify_all();
+        return ok;
+    }
+    void stop() {
+        std::lock_guard<std::mutex> lk(mu_);
+        stop_ = true;
+        cv_.notify_all();
+    }
+    size_t file_of(size_t job) {
+        std::lock_guard<std::mutex> lk(mu_);
+        return jobs_[job - base_].file;
+    }
+
+private:
+    struct Slot { size_t file; srpng::Image img; std::string err; int state; };  // 0 pending, 1 decoded, 2 failed, 3 taken
+    void work() {
+        for (;;) {
+            size_t j, file;
+            {
+                std::unique_lock<std::mutex> lk(mu_);
+                cv_.wait(lk, [&] { return stop_ || (next_ < base_ + jobs_.size() && next_ < base_ + window_); });
+                if (stop_) return;
+                j = next_++;
+                file = jobs_[j - base_].file;
+            }
+            srpng::Image img;
+            std::string err;
+            const bool ok = srpng::decode_image_file(files_[file], img, err);
+            std::lock_guard<std::mutex> lk(mu_);
+            Slot& sl = jobs_[j - base_];
+            sl.img = std::move(img);
+            sl.err = err;
+            sl.state = ok ? 1 : 2;
+            cv_.notify_all();
+        }
+    }
+    const std::vector<std::string>& files_;
+    std::deque<Slot> jobs_;
+    size_t base_ = 0, next_ = 0, window_ = 32;
+    bool stop_ = false;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::vector<std::thread> workers_;
+};
+
+// The decodable files of a folder (with recurse: of its subfolders too), sorted by path bytes.  false: the folder could not be read.
+bool list_images(const std::string& folder, bool recurse, std::vector<std::string>& files, std::string& err) {
+    namespace fs = std::filesystem;
+    std::error_code ec;
+    auto take = [&](const fs::directory_entry& e) {
+        std::error_code ec2;
+        if (e.is_regular_file(ec2) && decodable(e.path())) files.push_back(e.path().string());
+    };
+    if (recurse) {
+        for (fs::recursive_directory_iterator it(folder, ec), end; !ec && it != end; it.increment(ec)) take(*it);
+    } else {
+        for (fs::directory_iterator it(folder, ec), end; !ec && it != end; it.increment(ec)) take(*it);
+    }
+    if (ec) { err = ec.message(); return false; }
+    std::sort(files.begin(), files.end());
+    return true;
+}
+
 // rusty_sr validate: the validation pass of the reference's `train` (main.rs:220-247) on its own.  Files are decoded on up to 16 host
 // threads (OMP_NUM_THREADS if set) ahead of the GPU, which scores them in path order; with --devices image i goes to context i mod n.
 // The sums are taken in image order, so the printed value does not depend on the number of devices.
@@ -166,22 +266,12 @@ int run_validate(int argc, char** argv) {
     if (devices.empty()) devices.push_back(0);
 
     // ---- the files: decodable extensions, sorted by path bytes, the first N with -m
-    namespace fs = std::filesystem;
     std::vector<std::string> files;
     {
         std::error_code ec;
-        if (!fs::is_directory(folder, ec)) validate_usage_error("'" + folder + "' is not a folder");
-        auto take = [&](const fs::directory_entry& e) {
-            std::error_code ec2;
-            if (e.is_regular_file(ec2) && decodable(e.path())) files.push_back(e.path().string());
-        };
-        if (recurse) {
-            for (fs::recursive_directory_iterator it(folder, ec), end; !ec && it != end; it.increment(ec)) take(*it);
-        } else {
-            for (fs::directory_iterator it(folder, ec), end; !ec && it != end; it.increment(ec)) take(*it);
-        }
-        if (ec) die("could not read the validation folder (" + ec.message() + ")");
-        std::sort(files.begin(), files.end());
+        if (!std::filesystem::is_directory(folder, ec)) validate_usage_error("'" + folder + "' is not a folder");
+        std::string err;
+        if (!list_images(folder, recurse, files, err)) die("could not read the validation folder (" + err + ")");
         if (val_max > 0 && (size_t)val_max < files.size()) files.resize((size_t)val_max);
         if (files.empty()) validate_usage_error("no image files in '" + folder + "'" + (recurse ? "" : " (-r recurses into subfolders)"));
     }
@@ -214,39 +304,11 @@ int run_validate(int argc, char** argv) {
     for (int f : {3, 2, 4})
         if (params.size() == (size_t)sr_num_params_factor(f)) { factor = f; break; }
 
-    // ---- decoding ahead of the GPU: worker threads take the next file; at most 2 x threads decoded images wait for the GPU
+    // ---- decoding ahead of the GPU, in path order
     const size_t nfile = files.size();
-    unsigned threads = 16;
-    if (const char* e = getenv("OMP_NUM_THREADS")) { const int v = atoi(e); if (v > 0) threads = (unsigned)std::min(v, 16); }
-    threads = (unsigned)std::min<size_t>(threads, nfile);
-    struct Slot { srpng::Image img; std::string err; int state = 0; };  // 0 pending, 1 decoded, 2 failed, 3 scored
-    std::vector<Slot> slots(nfile);
+    DecoderPool decoders(files, nfile, devices.size());
+    for (size_t i = 0; i < nfile; ++i) decoders.push(i);
     std::mutex mu;
-    std::condition_variable cv;
-    size_t next = 0, scored = 0;
-    bool stop = false;
-    const size_t window = 2 * (size_t)threads + devices.size();
-    std::vector<std::thread> decoders;
-    for (unsigned t = 0; t < threads; ++t)
-        decoders.emplace_back([&] {
-            for (;;) {
-                size_t i;
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return stop || next >= nfile || next < scored + window; });
-                    if (stop || next >= nfile) return;
-                    i = next++;
-                }
-                srpng::Image img;
-                std::string err;
-                const bool ok = srpng::decode_image_file(files[i], img, err);
-                std::lock_guard<std::mutex> lk(mu);
-                slots[i].img = std::move(img);
-                slots[i].err = err;
-                slots[i].state = ok ? 1 : 2;
-                cv.notify_all();
-            }
-        });
 
     // ---- contexts, one scoring thread per context
     using clk = std::chrono::steady_clock;
@@ -271,41 +333,29 @@ int run_validate(int argc, char** argv) {
             scorers.emplace_back([&, k] {
                 for (size_t i = k; i < nfile; i += ctxs.size()) {
                     srpng::Image img;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        cv.wait(lk, [&] { return stop || slots[i].state != 0; });
-                        if (stop) return;
-                        if (slots[i].state == 2) {
-                            if (failure.empty() || fail_code == 0) { failure = "Error opening validation image file " + files[i] + " (" + slots[i].err + ")"; fail_code = 1; }
-                            stop = true;
-                            cv.notify_all();
-                            return;
-                        }
-                        img = std::move(slots[i].img);
-                        slots[i].state = 3;
+                    std::string derr;
+                    if (!decoders.take(i, img, derr)) {
+                        std::lock_guard<std::mutex> lk(mu);
+                        if (!derr.empty() && fail_code == 0) { failure = "Error opening validation image file " + files[i] + " (" + derr + ")"; fail_code = 1; }
+                        decoders.stop();
+                        return;
                     }
                     const int r = sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
                     if (r == SR_OK && timing) { double tot = 0; sr_last_timing(ctxs[k], &tot, nullptr, nullptr, nullptr); gpu_ms[i] = tot; }
-                    std::lock_guard<std::mutex> lk(mu);
                     if (r != SR_OK) {
-                        if (failure.empty()) {
+                        std::lock_guard<std::mutex> lk(mu);
+                        if (fail_code == 0) {
                             failure = files[i] + ": " + sr_strerror(r) + (r == SR_E_INVALID ? " (smaller than one pooling block?)" : "");
                             fail_code = 1;
                         }
-                        stop = true;
+                        decoders.stop();
+                        return;
                     }
-                    ++scored;
-                    cv.notify_all();
                 }
             });
     }
     for (auto& t : scorers) t.join();
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        stop = true;
-        cv.notify_all();
-    }
-    for (auto& t : decoders) t.join();
+    decoders.stop();
     for (sr_ctx* c : ctxs) sr_destroy(c);
     if (fail_code) die(failure, fail_code);
     double err_sum = 0, n_sum = 0, ms_sum = 0;
@@ -320,6 +370,316 @@ int run_validate(int argc, char** argv) {
     return 0;
 }
 
+
+const char* kTrainUsage =
+    "rusty_sr train\nTrains a new set of neural network parameters on the GPU (the reference's `train`): random 192x192 crops of the\n"
+    "training images, batch 4, Adam; the parameter file is written after the first step and every 100 steps\n\n"
+    "USAGE:\n    rusty_sr train [FLAGS] [OPTIONS] <PARAMETER_FILE> <TRAINING_FOLDER>\n\n"
+    "FLAGS:\n    -l, --linearLoss    Apply MSE loss to a linearised RGB output rather than sRGB values\n"
+    "    -r, --recurse       Recurse into subfolders of training and validation folders looking for files\n"
+    "    -h, --help          Prints help information\n"
+    "        --timing        Print steps/s, the share of resident draws and the decode time on stderr\n\n"
+    "OPTIONS:\n    -s, --start <START_PARAMETERS>    Start training from known parameters loaded from this .rsr file; its size\n"
+    "                                      selects the factor (2, 3 or 4) [default: random parameters at factor 3]\n"
+    "    -v, --val_folder <VAL_FOLDER>     Images from this folder (or sub-folders with -r) are used to report the validation\n"
+    "                                      PSNR after the first step and every 100 steps\n"
+    "    -m, --val_max <N>                 Set upper limit on number of images used for each validation pass\n"
+    "        --device <N>                  HIP device index [default: 0]\n"
+    "        --seed <N>                    Seed of the initial parameters, the shuffles and the crops [default: random]\n"
+    "        --steps <N>                   Stop after N steps [default: 2500000, the reference's 10 000 000 evaluations]\n"
+    "        --store <BYTES>               Device memory for resident training images; 0 decodes every draw again\n"
+    "                                      [default: the device's free memory less max(8 GiB, 1/8 of it)]\n\n"
+    "ARGS:\n    <PARAMETER_FILE>     Learned network parameters will be (over)written to this parameter file (.rsr)\n"
+    "    <TRAINING_FOLDER>    Images from this folder (or sub-folders with -r) are used for training\n";
+
+[[noreturn]] void train_usage_error(const std::string& msg) {
+    fprintf(stderr, "error: %s\n\nUSAGE:\n    rusty_sr train [FLAGS] [OPTIONS] <PARAMETER_FILE> <TRAINING_FOLDER>\n\nFor more information try --help\n",
+            msg.c_str());
+    exit(2);
+}
+
+// SplitMix64: the shuffles and crop origins of `train` (the initial parameters use the library's own, sr_init_params)
+struct Rng {
+    uint64_t s;
+    uint64_t next() {
+        uint64_t z = (s += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        return z ^ (z >> 31);
+    }
+    uint64_t below(uint64_t n) { return next() % n; }  // (the bias of the modulo is below 2^-40 for any image size)
+};
+
+bool parse_count(const std::string& v, long& n) {
+    const auto r = std::from_chars(v.data(), v.data() + v.size(), n);
+    return !v.empty() && r.ec == std::errc() && r.ptr == v.data() + v.size();
+}
+
+bool write_rsr(const std::string& path, const std::vector<float>& p) {
+    size_t len = 0;
+    if (sr_rsr_encode(p.data(), p.size(), nullptr, 0, &len) != SR_OK) return false;
+    std::vector<uint8_t> blob(len);
+    if (sr_rsr_encode(p.data(), p.size(), blob.data(), blob.size(), &len) != SR_OK) return false;
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = fwrite(blob.data(), 1, len, f) == len;
+    return fclose(f) == 0 && ok;
+}
+
+// RGB copy of a decoded RGBA image (the store keeps 3 bytes a pixel)
+std::vector<uint8_t> to_rgb(const srpng::Image& img) {
+    std::vector<uint8_t> rgb((size_t)img.w * img.h * 3);
+    for (size_t i = 0, n = (size_t)img.w * img.h; i < n; ++i) memcpy(&rgb[3 * i], &img.rgba[4 * i], 3);
+    return rgb;
+}
+
+// rusty_sr train: the reference's `train` (main.rs:181-257).  sr_net(f, Some((1e-6, linear_loss))), Adam (lr 2e-3, beta1 0.95, beta2
+// 0.995, eps 1e-7), batches of 4 random 192 x 192 crops, each draw one crop of the next image of a per-epoch shuffle of the training files.
+// Every training image is decoded once, up front, and kept in the device's image store while it has room; the others are decoded again
+// each time they are drawn (ahead of the GPU, on the decoder pool).  After step 1 and every 100th step the parameter file is written and,
+// with -v, the PSNR of the next min(#files, N) validation images (sorted, wrapping round) at the current parameters is printed.
+int run_train(int argc, char** argv) {
+    std::string start, val_folder;
+    std::vector<std::string> pos;
+    bool has_s = false, has_v = false, linear = false, recurse = false, timing = false;
+    long val_max = -1, steps = 2500000, device = 0, store = -1;
+    uint64_t seed = 0;
+    bool has_seed = false;
+    for (int k = 2; k < argc; ++k) {
+        const std::string a = argv[k];
+        auto value = [&](const char* name) -> std::string {
+            if (k + 1 >= argc) train_usage_error(std::string("The argument '") + name + "' requires a value but none was supplied");
+            return argv[++k];
+        };
+        if (a == "-h" || a == "--help") { fputs(kTrainUsage, stdout); return 0; }
+        else if (a == "-l" || a == "--linearLoss") linear = true;
+        else if (a == "-r" || a == "--recurse") recurse = true;
+        else if (a == "--timing") timing = true;
+        else if (a == "-s" || a == "--start") { start = value("--start <START_PARAMETERS>"); has_s = true; }
+        else if (a == "-v" || a == "--val_folder") { val_folder = value("--val_folder <VAL_FOLDER>"); has_v = true; }
+        else if (a == "-m" || a == "--val_max") {
+            const std::string v = value("--val_max <N>");
+            if (!parse_count(v, val_max) || val_max <= 0) train_usage_error("-val_max N must be a positive integer");  // main.rs:225
+        }
+        else if (a == "--device") {
+            const std::string v = value("--device <N>");
+            if (!parse_count(v, device) || device < 0) train_usage_error("'" + v + "' isn't a valid value for '--device <N>'");
+        }
+        else if (a == "--steps") {
+            const std::string v = value("--steps <N>");
+            if (!parse_count(v, steps) || steps <= 0) train_usage_error("'" + v + "' isn't a valid value for '--steps <N>'");
+        }
+        else if (a == "--store") {
+            const std::string v = value("--store <BYTES>");
+            if (!parse_count(v, store) || store < 0) train_usage_error("'" + v + "' isn't a valid value for '--store <BYTES>'");
+        }
+        else if (a == "--seed") {
+            const std::string v = value("--seed <N>");
+            const auto r = std::from_chars(v.data(), v.data() + v.size(), seed);
+            if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size()) train_usage_error("'" + v + "' isn't a valid value for '--seed <N>'");
+            has_seed = true;
+        }
+        else if (a.size() > 1 && a[0] == '-') train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
+        else if (pos.size() == 2) train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
+        else pos.push_back(a);
+    }
+    if (val_max > 0 && !has_v)  // clap: -m requires -v (main.rs:104)
+        train_usage_error("The following required arguments were not provided:\n    --val_folder <VAL_FOLDER>");
+    if (pos.size() < 2) train_usage_error("The following required arguments were not provided:\n    <PARAMETER_FILE>\n    <TRAINING_FOLDER>");
+    if (!has_seed) seed = ((uint64_t)std::random_device{}() << 32) ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
+    const std::string param_file = pos[0], train_folder = pos[1];
+
+    // ---- the folders, before the GPU is touched
+    std::vector<std::string> files, vfiles;
+    {
+        std::error_code ec;
+        std::string err;
+        if (!std::filesystem::is_directory(train_folder, ec)) train_usage_error("'" + train_folder + "' is not a folder");
+        if (!list_images(train_folder, recurse, files, err)) die("could not read the training folder (" + err + ")");
+        if (files.empty()) train_usage_error("no image files in '" + train_folder + "'" + (recurse ? "" : " (-r recurses into subfolders)"));
+        if (has_v) {
+            if (!std::filesystem::is_directory(val_folder, ec)) train_usage_error("'" + val_folder + "' is not a folder");
+            if (!list_images(val_folder, recurse, vfiles, err)) die("could not read the validation folder (" + err + ")");
+            if (vfiles.empty()) train_usage_error("no image files in '" + val_folder + "'" + (recurse ? "" : " (-r recurses into subfolders)"));
+        }
+    }
+    // ---- parameters: the start file (its length selects the factor) or g.init_params() at factor 3
+    std::vector<float> params;
+    int factor = SR_FACTOR;
+    if (has_s) {
+        FILE* f = fopen(start.c_str(), "rb");
+        if (!f) die("Error opening start parameter file");  // main.rs:192
+        std::vector<unsigned char> data;
+        unsigned char tmp[65536];
+        size_t n;
+        while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) data.insert(data.end(), tmp, tmp + n);
+        fclose(f);
+        params = decode_rsr(data.data(), data.size());
+        for (int fc : {3, 2, 4})
+            if (params.size() == (size_t)sr_num_params_factor(fc)) { factor = fc; break; }
+    } else {
+        params.resize((size_t)sr_num_params_factor(factor));
+        if (sr_init_params(factor, seed, params.data(), params.size()) != SR_OK) die("could not initialise the parameters");
+    }
+
+    // ---- the device: a context (its inference path scores the validation images) and the training session on it
+    sr_ctx* ctx = nullptr;
+    int rc = sr_create(&ctx, params.data(), params.size(), factor, (int)device);
+    if (rc != SR_OK) die(sr_strerror(rc));  // SR_E_PARAM_COUNT carries the text of main.rs:162; SR_E_NO_DEVICE: no CPU fallback
+    sr_train* tr = nullptr;
+    rc = sr_train_create(&tr, ctx, params.data(), params.size(), linear ? 1 : 0, 1e-6f, 2e-3f, 0.95f, 0.995f, 1e-7f,
+                         store < 0 ? SR_TRAIN_STORE_AUTO : (size_t)store);
+    if (rc != SR_OK) die(sr_strerror(rc));
+    using clk = std::chrono::steady_clock;
+    const clk::time_point t_load = clk::now();
+
+    // ---- every training image decoded once: into the store while it has room; the rest are transient (their sizes are kept)
+    const size_t nfile = files.size();
+    struct TrainImage { int id = -1, h = 0, w = 0; bool ok = false; };
+    std::vector<TrainImage> timg(nfile);
+    double decode_ms = 0;
+    {
+        DecoderPool pool(files, nfile);
+        for (size_t i = 0; i < nfile; ++i) pool.push(i);
+        for (size_t i = 0; i < nfile; ++i) {
+            srpng::Image img;
+            std::string err;
+            if (!pool.take(i, img, err)) { fprintf(stderr, "warning: skipping training image %s (%s)\n", files[i].c_str(), err.c_str()); continue; }
+            timg[i].h = img.h; timg[i].w = img.w; timg[i].ok = true;
+            const std::vector<uint8_t> rgb = to_rgb(img);
+            rc = sr_train_add_image(tr, rgb.data(), 3, img.h, img.w, &timg[i].id);
+            if (rc != SR_OK) die(std::string("could not store a training image: ") + sr_strerror(rc));
+        }
+    }
+    decode_ms += std::chrono::duration<double, std::milli>(clk::now() - t_load).count();
+    std::vector<size_t> usable;
+    for (size_t i = 0; i < nfile; ++i) if (timg[i].ok) usable.push_back(i);
+    if (usable.empty()) train_usage_error("no decodable image in '" + train_folder + "'");
+    // ---- validation images: decoded once, kept on the host
+    std::vector<srpng::Image> vimg;
+    if (has_v) {
+        DecoderPool pool(vfiles, vfiles.size());
+        for (size_t i = 0; i < vfiles.size(); ++i) pool.push(i);
+        vimg.resize(vfiles.size());
+        for (size_t i = 0; i < vfiles.size(); ++i) {
+            std::string err;
+            if (!pool.take(i, vimg[i], err)) die("Error opening validation image file " + vfiles[i] + " (" + err + ")");
+        }
+    }
+    const size_t val_n = has_v ? std::min(vimg.size(), val_max > 0 ? (size_t)val_max : vimg.size()) : 0;
+    size_t val_next = 0;
+
+    // ---- the draws: a fresh shuffle of the usable files each epoch, one crop of each drawn image
+    constexpr int kBatch = 4, kCrop = 192;
+    Rng rng{seed ^ 0x5eed5eed5eed5eedull};
+    std::vector<size_t> perm;
+    size_t perm_pos = 0;
+    struct Draw { size_t file; int y0, x0; };
+    auto draw = [&]() -> Draw {
+        if (perm_pos == perm.size()) {
+            perm = usable;
+            for (size_t i = perm.size(); i > 1; --i) std::swap(perm[i - 1], perm[rng.below(i)]);
+            perm_pos = 0;
+        }
+        const size_t fi = perm[perm_pos++];
+        const TrainImage& im = timg[fi];
+        // the crop origin: uniform over the positions inside the image; 0 on an axis shorter than the crop (the rest is zero padding)
+        const int y0 = im.h > kCrop ? (int)rng.below((uint64_t)(im.h - kCrop + 1)) : 0;
+        const int x0 = im.w > kCrop ? (int)rng.below((uint64_t)(im.w - kCrop + 1)) : 0;
+        return {fi, y0, x0};
+    };
+    // draws are made a window of steps ahead, so that transient images decode while the GPU works
+    DecoderPool pool(files, 16 * kBatch);
+    std::deque<std::pair<Draw, long>> ahead;  // (draw, decoder job or -1)
+    const long lookahead = 8 * kBatch;
+    long drawn = 0;
+    auto fill = [&]() {
+        while ((long)ahead.size() < lookahead && drawn < steps * kBatch) {
+            const Draw d = draw();
+            ++drawn;
+            ahead.emplace_back(d, timg[d.file].id >= 0 ? -1 : (long)pool.push(d.file));
+        }
+    };
+
+    auto checkpoint = [&](bool validate) {
+        std::vector<float> p(params.size());
+        int r = sr_train_params(tr, p.data(), p.size());
+        if (r != SR_OK) die(sr_strerror(r));
+        if (!write_rsr(param_file, p)) fprintf(stderr, "Could not make parameter file\n");
+        if (!validate || !has_v) return;
+        r = sr_set_params(ctx, p.data(), p.size());
+        if (r != SR_OK) die(sr_strerror(r));
+        double err_sum = 0, n_sum = 0;
+        for (size_t k = 0; k < val_n; ++k) {
+            const srpng::Image& im = vimg[val_next];
+            val_next = (val_next + 1) % vimg.size();
+            double e = 0;
+            size_t ne = 0;
+            r = sr_validation_error_rgba8(ctx, im.rgba.data(), 4, im.h, im.w, linear ? 1 : 0, &e, &ne);
+            if (r != SR_OK) die(std::string("validation: ") + sr_strerror(r) + (r == SR_E_INVALID ? " (an image smaller than one pooling block?)" : ""));
+            err_sum += e;
+            n_sum += (double)ne;
+        }
+        const float psnr = err_sum == 0.0 ? INFINITY : (float)(-10.0 * std::log10(err_sum / n_sum));
+        printf("Validation PSNR:\t%s\n", rust_f32(psnr).c_str());  // main.rs:246
+        fflush(stdout);
+    };
+
+    printf("Beginning Training\n");
+    fflush(stdout);
+    const clk::time_point t0 = clk::now();
+    long resident_draws = 0;
+    double wait_ms = 0;
+    std::vector<std::vector<uint8_t>> held(kBatch);  // transient pixels of the step being queued
+    for (long step = 1; step <= steps; ++step) {
+        fill();
+        sr_train_crop items[kBatch];
+        for (int i = 0; i < kBatch; ++i) {
+            const auto [d, job] = ahead.front();
+            ahead.pop_front();
+            items[i].y0 = d.y0;
+            items[i].x0 = d.x0;
+            if (job < 0) {
+                items[i].image = timg[d.file].id;
+                items[i].px = nullptr;
+                items[i].in_channels = 3; items[i].h = timg[d.file].h; items[i].w = timg[d.file].w;
+                ++resident_draws;
+                continue;
+            }
+            srpng::Image img;
+            std::string err;
+            const clk::time_point tw = clk::now();
+            if (!pool.take((size_t)job, img, err)) die("Error opening training image file " + files[d.file] + " (" + err + ")");
+            wait_ms += std::chrono::duration<double, std::milli>(clk::now() - tw).count();
+            held[i] = std::move(img.rgba);
+            items[i].image = -1;
+            items[i].px = held[i].data();
+            items[i].in_channels = 4; items[i].h = img.h; items[i].w = img.w;
+        }
+        rc = sr_train_step(tr, items, kBatch, kCrop, kCrop);
+        if (rc != SR_OK) die(std::string("training step: ") + sr_strerror(rc));
+        if (step % 1000 == 0) {  // keep the err_sum list of the session short (the values are not reported)
+            rc = sr_train_sync(tr, nullptr, 0, nullptr);
+            if (rc != SR_OK) die(sr_strerror(rc));
+        }
+        if (step == 1 || step % 100 == 0) checkpoint(true);
+        else if (step == steps) checkpoint(false);  // --steps ended the run between two checkpoints: the file holds the last step
+    }
+    rc = sr_train_sync(tr, nullptr, 0, nullptr);
+    if (rc != SR_OK) die(sr_strerror(rc));
+    if (timing) {
+        const double s = std::chrono::duration<double>(clk::now() - t0).count();
+        fprintf(stderr, "[timing] %ld steps in %.3f s: %.1f steps/s (checkpoints and validation included); resident draws %.1f %%; "
+                        "decode: %.1f ms up front (%zu images, %d resident), %.1f ms waited for transient images\n",
+                steps, s, steps / s, 100.0 * resident_draws / ((double)steps * kBatch), decode_ms, nfile,
+                (int)std::count_if(timg.begin(), timg.end(), [](const TrainImage& t) { return t.id >= 0; }), wait_ms);
+    }
+    pool.stop();
+    sr_train_destroy(tr);
+    sr_destroy(ctx);
+    printf("Done\n");
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -328,8 +688,7 @@ int main(int argc, char** argv) {
     bool has_p = false, has_c = false, downsample = false, timing = false;
     int device = 0;
     std::vector<int> devices;
-    if (argc >= 2 && !strcmp(argv[1], "train"))  // main.rs:119-121
-        die("the `train` sub-command is not part of this build (the MI355X engine covers the upscale path only)", 2);
+    if (argc >= 2 && !strcmp(argv[1], "train")) return run_train(argc, argv);  // main.rs:119-121
     if (argc >= 2 && !strcmp(argv[1], "validate")) return run_validate(argc, argv);
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
