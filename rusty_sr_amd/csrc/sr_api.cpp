@@ -18,37 +18,9 @@
 #include "../../include/srhip_experimental.h"
 #include "sr_kernels.h"
 #include "sr_internal.h"
+#include "sr_params.h"
 
 namespace {
-
-// Parameter segment offsets: op insertion order of reference src/network.rs:33-72
-// (SURVEY.md 8(a) row W).  Only the expand node depends on the factor f: 3 f^2 channels
-// (network.rs:37), so expand_bias and conv7 / conv9 / conv10 scale with it.
-struct ParamLayout {
-    size_t conv0, f_bias, f_activ, exp_bias, l_bias[3], l_activ[3], conv1, conv2, conv3, conv5, conv6, conv7, conv8,
-        conv9, conv10, end;
-    int E;  // expand channels
-    explicit ParamLayout(int f) {
-        E = 3 * f * f;
-        size_t o = 0;
-        conv0 = o; o += 2400;
-        f_bias = o; o += 32;
-        f_activ = o; o += 32;
-        exp_bias = o; o += E;
-        for (auto& b : l_bias) { b = o; o += 32; }
-        for (auto& a : l_activ) { a = o; o += 32; }
-        conv1 = o; o += 25600;
-        conv2 = o; o += 25600;
-        conv3 = o; o += 25600;
-        conv5 = o; o += 9216;
-        conv6 = o; o += 9216;
-        conv7 = o; o += (size_t)E * 288;
-        conv8 = o; o += 9216;
-        conv9 = o; o += (size_t)E * 288;
-        conv10 = o; o += (size_t)E * 288;
-        end = o;
-    }
-};
 
 constexpr int kChunk = 1024;  // floats per tap chunk (32 cin x 32 cout)
 constexpr int kAutoBlockWidth = 16;  // default tile order of the stage kernels (StageArgs::bw): 16-tile (512 px) column blocks;
@@ -274,10 +246,10 @@ std::vector<float> pack_params(sr_ctx* c, const float* params, int factor, bool*
         for (int i = 0; i < n; ++i) v[i] = params[off + i];
         return v;
     };
-    const ParamLayout L(factor);
-    pack_conv0(w, params + L.conv0);
+    const sr_param_layout L(factor);
+    pack_conv0(w, params + L.off[SR_SEG_CONV0]);
     c->off_w0 = push(w);
-    pack_conv0_split(w, params + L.conv0);
+    pack_conv0_split(w, params + L.off[SR_SEG_CONV0]);
     c->off_w0h = push(w);
     for (int split = 0; split < 2; ++split) {  // exact-f32 chunks, then the same stages in split-half form
         auto ident = [](int, int j) { return j; };
@@ -286,24 +258,24 @@ std::vector<float> pack_params(sr_ctx* c, const float* params, int factor, bool*
         auto conv = [&](const float* wp, int ks) { if (h16) pack_steps_h16(w, wp, ks); else pack_steps(w, wp, ks, 1, split != 0, ident); };
         auto exp3 = [&](const float* wp) { pack_steps(w, wp, 3, expand_tiles(factor), split != 0, expand); };
         size_t* off = split ? c->off_wh : c->off_w;
-        w.clear(); conv(params + L.conv1, 5);
+        w.clear(); conv(params + L.off[SR_SEG_CONV1], 5);
         off[1] = push(w);
-        w.clear(); conv(params + L.conv2, 5); conv(params + L.conv5, 3);
+        w.clear(); conv(params + L.off[SR_SEG_CONV2], 5); conv(params + L.off[SR_SEG_CONV5], 3);
         off[2] = push(w);
-        w.clear(); conv(params + L.conv3, 5); conv(params + L.conv6, 3); conv(params + L.conv8, 3);
+        w.clear(); conv(params + L.off[SR_SEG_CONV3], 5); conv(params + L.off[SR_SEG_CONV6], 3); conv(params + L.off[SR_SEG_CONV8], 3);
         off[3] = push(w);
         w.clear();
-        exp3(params + L.conv7); exp3(params + L.conv9); exp3(params + L.conv10);
+        exp3(params + L.off[SR_SEG_CONV7]); exp3(params + L.off[SR_SEG_CONV9]); exp3(params + L.off[SR_SEG_CONV10]);
         if (split) pack_lin_split(w, factor);  // the split-half mode: on the f16 pipe too, with exact integer weights (lin_mfma_h)
         else pack_lin(w, factor);
         off[4] = push(w);
     }
-    w.clear(); pack_steps_wino(w, params + L.conv1);
+    w.clear(); pack_steps_wino(w, params + L.off[SR_SEG_CONV1]);
     c->off_wino1 = push(w);
-    w.clear(); pack_steps_wino(w, params + L.conv2); pack_steps(w, params + L.conv5, 3, 1, false, [](int, int j) { return j; });
+    w.clear(); pack_steps_wino(w, params + L.off[SR_SEG_CONV2]); pack_steps(w, params + L.off[SR_SEG_CONV5], 3, 1, false, [](int, int j) { return j; });
     c->off_wino2 = push(w);
-    const size_t boff[4] = {L.f_bias, L.l_bias[0], L.l_bias[1], L.l_bias[2]};
-    const size_t aoff[4] = {L.f_activ, L.l_activ[0], L.l_activ[1], L.l_activ[2]};
+    const size_t boff[4] = {L.off[SR_SEG_F_BIAS], L.off[SR_SEG_L1_BIAS], L.off[SR_SEG_L2_BIAS], L.off[SR_SEG_L3_BIAS]};
+    const size_t aoff[4] = {L.off[SR_SEG_F_ACTIV], L.off[SR_SEG_L1_ACTIV], L.off[SR_SEG_L2_ACTIV], L.off[SR_SEG_L3_ACTIV]};
     for (int s = 0; s < 4; ++s) c->off_bias[s] = push(vec32(boff[s], 32));
     for (int s = 0; s < 4; ++s) c->off_beta[s] = push(vec32(aoff[s], 32));
     {   // expand_bias in the triple layout, 32 floats per N-tile
@@ -311,14 +283,14 @@ std::vector<float> pack_params(sr_ctx* c, const float* params, int factor, bool*
         for (int nt = 0; nt < expand_tiles(factor); ++nt)
             for (int j = 0; j < 32; ++j) {
                 const int ch = expand_channel(factor, nt, j);
-                if (ch >= 0) eb[nt * 32 + j] = params[L.exp_bias + ch];
+                if (ch >= 0) eb[nt * 32 + j] = params[L.off[SR_SEG_EXP_BIAS] + ch];
             }
         c->off_bias[4] = push(eb);
     }
     // the split-half mode carries every conv weight as a pair of halves: all of them finite and below the largest half, or the mode is refused
     bool ok = true;
-    for (size_t k = L.conv1; k < L.end && ok; ++k) ok = std::fabs(params[k]) < 65504.0f;   // (false for NaN too)
-    for (size_t k = L.conv0; k < L.conv0 + 2400 && ok; ++k) ok = std::fabs(params[k]) < 65504.0f;
+    for (size_t k = L.off[SR_SEG_CONV1]; k < L.total && ok; ++k) ok = std::fabs(params[k]) < 65504.0f;   // (false for NaN too)
+    for (size_t k = L.off[SR_SEG_CONV0]; k < L.off[SR_SEG_CONV0] + L.len[SR_SEG_CONV0] && ok; ++k) ok = std::fabs(params[k]) < 65504.0f;
     *split_ok = ok;
     return host;
 }
@@ -397,10 +369,10 @@ int sr_create_graph(sr_ctx** out, int graph, const float* params, size_t n_param
     // (network.rs:16), so user-trained 2x / 4x parameter files are accepted too
     if (graph == SR_GRAPH_SR_NET ? (factor < 2 || factor > 4) : factor != SR_FACTOR) return SR_E_FACTOR;
     // main.rs:162 assert_eq!(params.len(), graph.num_params()): 130459 for sr_net(3), 0 for the other two
-    if (n_params != (graph == SR_GRAPH_SR_NET ? ParamLayout(factor).end : 0)) return SR_E_PARAM_COUNT;
+    if (n_params != (graph == SR_GRAPH_SR_NET ? sr_param_layout(factor).total : 0)) return SR_E_PARAM_COUNT;
     if (graph == SR_GRAPH_SR_NET && !params) return SR_E_INVALID;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SR_E_NO_DEVICE;
+    if (sr_no_device(false, &ndev)) return SR_E_NO_DEVICE;
     if (device < 0 || device >= ndev) return SR_E_INVALID;
     sr_ctx* c = new (std::nothrow) sr_ctx();
     if (!c) return SR_E_NOMEM;
@@ -502,7 +474,7 @@ void sr_destroy(sr_ctx* c) {
 
 int sr_last_hip_error(sr_ctx* c) { return c ? c->last_hip : 0; }
 
-int sr_num_params_factor(int factor) { return factor >= 2 && factor <= 4 ? (int)ParamLayout(factor).end : -1; }
+int sr_num_params_factor(int factor) { return factor >= 2 && factor <= 4 ? (int)sr_param_layout(factor).total : -1; }
 
 int sr_num_params(int graph) { return graph == SR_GRAPH_SR_NET ? SR_NUM_PARAMS : (graph == SR_GRAPH_BILINEAR || graph == SR_GRAPH_DOWNSAMPLE ? 0 : -1); }
 
@@ -520,14 +492,10 @@ int sr_set_precision(sr_ctx* c, int mode) {
 }
 
 int sr_set_params(sr_ctx* c, const float* params, size_t n_params) {
-    if (!c) {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return SR_E_NO_DEVICE; }
-        return SR_E_INVALID;
-    }
+    if (!c) return sr_no_device() ? SR_E_NO_DEVICE : SR_E_INVALID;
     sr_plan_clear(c);
     if (c->graph != SR_GRAPH_SR_NET || !params) return SR_E_INVALID;
-    if (n_params != ParamLayout(c->factor).end) return SR_E_PARAM_COUNT;
+    if (n_params != sr_param_layout(c->factor).total) return SR_E_PARAM_COUNT;
     bool split_ok = true;
     const std::vector<float> host = pack_params(c, params, c->factor, &split_ok);
     if (c->precision == SR_PRECISION_SPLIT_F16 && !split_ok) return SR_E_DOMAIN;
@@ -619,8 +587,7 @@ int sr_set_pipeline(sr_ctx* c, int enabled) {
 int sr_host_alloc(void** out, size_t bytes) {
     if (!out || bytes == 0) return SR_E_INVALID;
     *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return SR_E_NO_DEVICE;
+    if (sr_no_device(false)) return SR_E_NO_DEVICE;
     const hipError_t e = hipHostMalloc(out, bytes, hipHostMallocPortable);
     if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return e == hipErrorOutOfMemory ? SR_E_NOMEM : SR_E_HIP; }
     return SR_OK;

@@ -1,6 +1,6 @@
 // sr_grad.cpp -- host side of backpropagation through the reference's training graph (network.rs:78-103, `g.backprop` in
 // Adam::optimise_from, main.rs:181-257) and of one Adam step (include/srhip.h sr_backprop_*, sr_adam_step_dev).  Kernels: sr_grad.hip;
-// the pool: sr_valid.hip.
+// the pool and the sum of the loss partials: sr_valid.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -10,30 +10,10 @@
 
 namespace {
 
-bool no_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    return n <= 0;
-}
-
-void free_buf(void*& p, size_t& cap) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-}
-
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }
-
 // Arguments of every backprop entry point, checked before the GPU is touched.
 int check_args(sr_ctx* c, const void* params, const void* hr, bool hr_u8, int ch, int n, int h, int w, const void* grad) {
     if (!c || !params || !hr || !grad) return SR_E_INVALID;
-    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
-    if (hr_u8 ? (ch != 3 && ch != 4) : ch != 3) return SR_E_INVALID;
-    if (n < 1 || h < c->factor || w < c->factor) return SR_E_INVALID;  // not one f x f pooling block
-    return SR_OK;
+    return sr_check_hr_args(c, hr_u8, ch, n, h, w);
 }
 
 size_t lr_floats(int f, int n, int h, int w) { return (size_t)n * (h / f) * (w / f) * 3; }
@@ -42,12 +22,12 @@ size_t lr_floats(int f, int n, int h, int w) { return (size_t)n * (h / f) * (w /
 int run_backprop(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8, int ch, int n, int h, int w, bool linear, float loss_scale,
                  float l2, void* d_err, float* d_grad, hipStream_t s, double** result_slot) {
     const int f = c->factor, OH = h / f, OW = w / f;
-    const size_t x_bytes = round256(lr_floats(f, n, h, w) * sizeof(float));
+    const size_t x_bytes = sr_round256(lr_floats(f, n, h, w) * sizeof(float));
     int rc = sr_valid_ensure_table(c);
     if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_gws, &c->gws_cap, x_bytes + sr_grad_workspace_bytes(f, n, OH, OW));
     if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
-        free_buf(c->d_gws, c->gws_cap);
-        free_buf(c->d_gin, c->gin_cap);
+        sr_free_buf(c->d_gws, c->gws_cap);
+        sr_free_buf(c->d_gin, c->gin_cap);
         return rc;
     }
     float* x = (float*)c->d_gws;
@@ -78,7 +58,7 @@ int run_backprop(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8,
 // The host-pointer calls: upload parameters and HR batch, run, download err_sum and the gradient, on the context's own stream; synchronous.
 int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* hr, bool hr_u8, int ch, int n, int h, int w, int linear,
                   float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad) {
-    if (!c && no_device()) return SR_E_NO_DEVICE;
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
     sr_plan_clear(c);
     int rc = check_args(c, params, hr, hr_u8, ch, n, h, w, grad);
     if (rc != SR_OK) return rc;
@@ -89,12 +69,12 @@ int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* h
     HIPCHK(c, hipSetDevice(c->device));
     rc = sr_ensure_streams(c, false);
     if (rc != SR_OK) return rc;
-    const size_t p_bytes = round256((size_t)np * sizeof(float));
+    const size_t p_bytes = sr_round256((size_t)np * sizeof(float));
     const size_t hr_bytes = (size_t)n * h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
-    rc = sr_ensure_buf(c, &c->d_gin, &c->gin_cap, 2 * p_bytes + round256(hr_bytes));
+    rc = sr_ensure_buf(c, &c->d_gin, &c->gin_cap, 2 * p_bytes + sr_round256(hr_bytes));
     if (rc != SR_OK) {
-        free_buf(c->d_gin, c->gin_cap);
-        free_buf(c->d_gws, c->gws_cap);
+        sr_free_buf(c->d_gin, c->gin_cap);
+        sr_free_buf(c->d_gws, c->gws_cap);
         return rc;
     }
     float* d_params = (float*)c->d_gin;
@@ -116,15 +96,15 @@ int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* h
     HIPCHK(c, e1);
     HIPCHK(c, e2);
     *err_sum = sum;
-    *n_elems = (size_t)n * 3 * ((size_t)c->factor * (h / c->factor)) * ((size_t)c->factor * (w / c->factor));
+    *n_elems = sr_loss_elems(c->factor, n, h, w);
     return SR_OK;
 }
 
 }  // namespace
 
 void sr_grad_release(sr_ctx* c) {
-    free_buf(c->d_gws, c->gws_cap);
-    free_buf(c->d_gin, c->gin_cap);
+    sr_free_buf(c->d_gws, c->gws_cap);
+    sr_free_buf(c->d_gin, c->gin_cap);
 }
 
 extern "C" {
@@ -141,7 +121,7 @@ int sr_backprop_rgba8(sr_ctx* c, const float* params, size_t n_params, const uin
 
 int sr_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_hr, int in_channels, int n, int h, int w, int linear_loss,
                           float loss_scale, float l2, double* d_err_sum, float* d_grad, void* stream) {
-    if (!c && no_device()) return SR_E_NO_DEVICE;
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
     sr_plan_clear(c);
     const int rc = check_args(c, d_params, d_hr, true, in_channels, n, h, w, d_grad);
     if (rc != SR_OK) return rc;
@@ -154,7 +134,7 @@ int sr_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_hr,
 
 int sr_adam_step_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr, float beta1,
                      float beta2, float eps, void* stream) {
-    if (!c && no_device()) return SR_E_NO_DEVICE;
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
     sr_plan_clear(c);
     if (!c || !d_params || !d_m || !d_v || !d_grad || n == 0 || step < 1) return SR_E_INVALID;
     if (!sr_dword_aligned(d_params) || !sr_dword_aligned(d_m) || !sr_dword_aligned(d_v) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;

@@ -6,7 +6,7 @@
 //   pool       input = LinearToSrgb(mean_fxf(SrgbToLinear(hr)))       sr_launch_valid_pool (sr_valid.hip), 1 launch (n if h % f != 0)
 //   forward    z, a of f, l1, l2, l3; e (3f^2 expand channels)        grad_conv_kernel<FWD/LIN>, 5 launches (one per stage)
 //   loss       out = LinearInterp(input) + d2s(e); e' = out - hr      grad_loss_kernel: d_e = 2 s e' (x SrgbToLinear'(out)) and one f64
-//              (or of SrgbToLinear of both)                           partial of sum e'^2 per workgroup; grad_sum_kernel adds them in order
+//              (or of SrgbToLinear of both)                           partial of sum e'^2 per workgroup; sr_launch_loss_sum adds them in order
 //   bias of e  sum of d_e over pixels                                 grad_colsum_kernel, per-chunk partials
 //   data grads d_a3 = conv10^T d_e; d_a2 = conv9^T d_e + conv8^T d_z3; grad_conv_kernel<BWD>, 4 launches, each summing all its
 //              d_a1 = conv7^T d_e + conv6^T d_z3 + conv5^T d_z2;       sources; epilogue: d_z = d_a (beta + z / sqrt(z^2 + 1)) and per-
@@ -25,6 +25,8 @@
 #include <algorithm>
 
 #include "sr_internal.h"
+#include "sr_params.h"
+#include "sr_reduce.h"
 #include "sr_transfer.h"
 
 #pragma clang fp contract(off)
@@ -256,20 +258,6 @@ __global__ __launch_bounds__(256) void grad_colsum_kernel(const float* __restric
     if (threadIdx.x < C) part[(size_t)blockIdx.x * C + threadIdx.x] = ((s[0][threadIdx.x] + s[1][threadIdx.x]) + s[2][threadIdx.x]) + s[3][threadIdx.x];
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* s_part) {
-    v = wave_sum(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) s_part[wave] = v;
-    __syncthreads();
-    return ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-}
-
 // SrgbToLinear'(s): 1 / 12.92 on the linear segment, else 2.4 / 1.055 a^1.4 with a = (s + 0.055) / 1.055 (f64, rounded once)
 __device__ __forceinline__ float srgb_to_linear_deriv(float s) {
     if (s <= 0.04045f) return (float)(1.0 / 12.92);
@@ -334,27 +322,13 @@ __global__ __launch_bounds__(256) void grad_loss_kernel(const float* __restrict_
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
-// one workgroup adds the partials in a fixed order; the result as two dwords (the caller's pointer is 4-byte aligned)
-__global__ __launch_bounds__(256) void grad_sum_kernel(const double* __restrict__ partial, int n, uint32_t* __restrict__ result) {
-    __shared__ double s_part[4];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    acc = block_sum(acc, s_part);
-    if (threadIdx.x == 0) {
-        const uint64_t bits = (uint64_t)__double_as_longlong(acc);
-        result[0] = (uint32_t)bits;
-        result[1] = (uint32_t)(bits >> 32);
-    }
-}
-
 // The gradient in .rsr order: each segment is the sum of its nparts partials (in order) plus 2 l2 p.
-constexpr int kSegs = 19;
 struct SegDesc {
     const float* part;
     int off, len, nparts;
 };
 struct AssembleArgs {
-    SegDesc seg[kSegs];
+    SegDesc seg[SR_SEGS];
     int total;
 };
 
@@ -362,7 +336,7 @@ __global__ __launch_bounds__(256) void grad_assemble_kernel(AssembleArgs a, cons
     const int g = blockIdx.x * 256 + threadIdx.x;
     if (g >= a.total) return;
     int s = 0;
-    while (s + 1 < kSegs && g >= a.seg[s + 1].off) ++s;
+    while (s + 1 < SR_SEGS && g >= a.seg[s + 1].off) ++s;
     const SegDesc d = a.seg[s];
     const int k = g - d.off;
     float acc = 0.f;
@@ -396,29 +370,6 @@ struct Layout {
     size_t floats;
 };
 
-// parameter segments of sr_net(f) in .rsr order (oracle/oracle.py SEGMENTS at f = 3)
-struct Segs {
-    int off[kSegs], len[kSegs];
-};
-enum { S_CONV0, S_FBIAS, S_FACT, S_EBIAS, S_L1B, S_L2B, S_L3B, S_L1A, S_L2A, S_L3A, S_CONV1, S_CONV2, S_CONV3, S_CONV5, S_CONV6, S_CONV7,
-       S_CONV8, S_CONV9, S_CONV10 };
-
-Segs segments(int f) {
-    const int E = 3 * f * f;
-    const int len[kSegs] = {2400, 32, 32, E, 32, 32, 32, 32, 32, 32, 25600, 25600, 25600, 9216, 9216, E * 288, 9216, E * 288, E * 288};
-    Segs s;
-    int off = 0;
-    for (int k = 0; k < kSegs; ++k) {
-        s.off[k] = off;
-        s.len[k] = len[k];
-        off += len[k];
-    }
-    return s;
-}
-
-// conv segment -> (cout, ks, cin) and its weight-gradient job index
-constexpr int kConvSeg[10] = {S_CONV0, S_CONV1, S_CONV2, S_CONV3, S_CONV5, S_CONV6, S_CONV7, S_CONV8, S_CONV9, S_CONV10};
-
 Layout layout(int f, int n, int H, int W) {
     Layout L;
     L.E = 3 * f * f;
@@ -430,7 +381,7 @@ Layout layout(int f, int n, int H, int W) {
     L.wchunk = (L.NP + L.wchunks - 1) / L.wchunks;
     L.cchunks = (int)std::min<long>(256, std::max<long>(1, (L.NP + 1023) / 1024));
     L.cchunk = (L.NP + L.cchunks - 1) / L.cchunks;
-    const Segs S = segments(f);
+    const sr_param_layout S(f);
     size_t o = 0;
     auto take = [&](size_t floats) { const size_t at = o; o += (floats + 63) / 64 * 64; return at; };
     L.o_zf = 0;
@@ -439,24 +390,14 @@ Layout layout(int f, int n, int H, int W) {
     L.o_e = take((size_t)L.NP * L.E);
     L.o_de = take((size_t)L.NP * L.EP);
     for (int k = 0; k < 4; ++k) L.o_dz[k] = take((size_t)L.NP * 32);
-    for (int k = 0; k < 10; ++k) L.o_wpart[k] = take((size_t)L.wchunks * S.len[kConvSeg[k]]);
+    for (int sg = 0, k = 0; sg < SR_SEGS; ++sg)  // the convolutions, in segment order
+        if (S.is_conv(sg)) L.o_wpart[k++] = take((size_t)L.wchunks * S.len[sg]);
     for (int k = 0; k < 4; ++k) L.o_pbeta[k] = take((size_t)L.conv_grid * 32);
     for (int k = 0; k < 4; ++k) L.o_pbias[k] = take((size_t)L.conv_grid * 32);
     L.o_pebias = take((size_t)L.cchunks * L.E);
     L.o_err = take((size_t)2 * (L.loss_grid + 1));  // doubles: partials, then the host-pointer call's result slot
     L.floats = o;
     return L;
-}
-
-GradSrc fwd_src(const float* in, int pitch, int cin, const float* w, int ks) {
-    const int kk = ks * ks;
-    return GradSrc{in, w, pitch, cin, cin, ks, kk * cin, cin, 1, 0};
-}
-
-// data gradient through a conv of cin_orig inputs: source = the gradient of its output (pitch, cin loop cin, real cout_orig channels)
-GradSrc bwd_src(const float* dy, int pitch, int cin_loop, int cout_orig, const float* w, int ks, int cin_orig) {
-    const int kk = ks * ks;
-    return GradSrc{dy, w, pitch, cin_loop, cout_orig, ks, 1, -cin_orig, kk * cin_orig, (kk - 1) * cin_orig};
 }
 
 template <int MODE, bool SCALAR>
@@ -468,17 +409,12 @@ hipError_t launch_conv(const GradConvArgs& a, int grid, hipStream_t s) {
 
 template <int F>
 hipError_t launch_loss(const sr_grad_plan& P, const Layout& L, float* ws, hipStream_t s) {
-    const float* x = P.x;
-    const float* e = ws + L.o_e;
-    float* de = ws + L.o_de;
-    double* part = (double*)(ws + L.o_err);
     const float seed = 2.0f * P.loss_scale;
-    const dim3 g((unsigned)L.loss_grid), b(256);
-#define SR_LOSS(U8, CH, LIN) hipLaunchKernelGGL((grad_loss_kernel<F, U8, CH, LIN>), g, b, 0, s, x, e, P.hr, P.tab, P.n, P.H, P.W, P.hr_h, P.hr_w, seed, de, L.EP, part)
-    if (P.hr_u8 && P.hr_ch == 3) { if (P.linear) SR_LOSS(true, 3, true); else SR_LOSS(true, 3, false); }
-    else if (P.hr_u8) { if (P.linear) SR_LOSS(true, 4, true); else SR_LOSS(true, 4, false); }
-    else { if (P.linear) SR_LOSS(false, 3, true); else SR_LOSS(false, 3, false); }
-#undef SR_LOSS
+    sr_dispatch_hr(P.hr_u8, P.hr_ch, P.linear, [&](auto u8, auto ch, auto lin) {
+        hipLaunchKernelGGL((grad_loss_kernel<F, decltype(u8)::value, decltype(ch)::value, decltype(lin)::value>), dim3((unsigned)L.loss_grid),
+                           dim3(256), 0, s, P.x, (const float*)(ws + L.o_e), P.hr, P.tab, P.n, P.H, P.W, P.hr_h, P.hr_w, seed, ws + L.o_de, L.EP,
+                           (double*)(ws + L.o_err));
+    });
     return hipGetLastError();
 }
 
@@ -494,10 +430,6 @@ size_t sr_grad_workspace_bytes(int factor, int n, int H, int W) {
     return layout(factor, n, H, W).floats * sizeof(float);
 }
 
-int sr_grad_loss_partials(int factor, int n, int H, int W) {
-    return layout(factor, n, H, W).loss_grid;
-}
-
 double* sr_grad_result_slot(const sr_grad_plan& P) {
     const Layout L = layout(P.factor, P.n, P.H, P.W);
     return (double*)(P.ws + L.o_err) + L.loss_grid;
@@ -507,10 +439,23 @@ hipError_t sr_launch_grad(const sr_grad_plan& P, hipStream_t s) {
     const int f = P.factor;
     if (f < 2 || f > 4 || P.n <= 0 || P.H <= 0 || P.W <= 0) return hipErrorInvalidValue;
     const Layout L = layout(f, P.n, P.H, P.W);
-    const Segs S = segments(f);
+    const sr_param_layout S(f);
     float* ws = P.ws;
     const float* prm = P.params;
     auto seg = [&](int k) { return prm + S.off[k]; };
+    // convolution `sg` applied to `in` (channel pitch `pitch`), and the data gradient through it: source = the gradient of its output
+    // (the reduction loops over all `pitch` channels, cout of them real)
+    auto fwd = [&](const float* in, int pitch, int sg) {
+        const int ks = S.ks(sg), cin = S.cin(sg);
+        return GradSrc{in, seg(sg), pitch, cin, cin, ks, ks * ks * cin, cin, 1, 0};
+    };
+    auto bwd_of = [&](const float* dy, int pitch, int sg) {
+        const int ks = S.ks(sg), cin = S.cin(sg);
+        return GradSrc{dy, seg(sg), pitch, pitch, S.cout(sg), ks, 1, -cin, ks * ks * cin, (ks * ks - 1) * cin};
+    };
+    float* wpart[SR_SEGS] = {};  // a convolution's weight-gradient partials
+    for (int sg = 0, k = 0; sg < SR_SEGS; ++sg)
+        if (S.is_conv(sg)) wpart[sg] = ws + L.o_wpart[k++];
     float* z[4];
     float* act[4];
     float* dz[4];
@@ -522,36 +467,38 @@ hipError_t sr_launch_grad(const sr_grad_plan& P, hipStream_t s) {
     float* e = ws + L.o_e;
     float* de = ws + L.o_de;
     const int E = L.E, EP = L.EP;
-    const float* bias[4] = {seg(S_FBIAS), seg(S_L1B), seg(S_L2B), seg(S_L3B)};
-    const float* beta[4] = {seg(S_FACT), seg(S_L1A), seg(S_L2A), seg(S_L3A)};
+    const int bias_seg[4] = {SR_SEG_F_BIAS, SR_SEG_L1_BIAS, SR_SEG_L2_BIAS, SR_SEG_L3_BIAS};
+    const int beta_seg[4] = {SR_SEG_F_ACTIV, SR_SEG_L1_ACTIV, SR_SEG_L2_ACTIV, SR_SEG_L3_ACTIV};
+    const float* bias[4] = {seg(bias_seg[0]), seg(bias_seg[1]), seg(bias_seg[2]), seg(bias_seg[3])};
+    const float* beta[4] = {seg(beta_seg[0]), seg(beta_seg[1]), seg(beta_seg[2]), seg(beta_seg[3])};
 
     // ---- forward with saved state
     GradConvArgs a{};
     a.n = P.n; a.H = P.H; a.W = P.W;
     a.cout = 32; a.out_pitch = 32;
     a.nsrc = 1;
-    a.src[0] = fwd_src(P.x, 3, 3, seg(S_CONV0), 5);
+    a.src[0] = fwd(P.x, 3, SR_SEG_CONV0);
     a.bias = bias[0]; a.beta = beta[0]; a.out0 = z[0]; a.out1 = act[0];
     SR_TRY((launch_conv<kFwd, true>(a, L.conv_grid, s)));
-    a.src[0] = fwd_src(act[0], 32, 32, seg(S_CONV1), 5);
+    a.src[0] = fwd(act[0], 32, SR_SEG_CONV1);
     a.bias = bias[1]; a.beta = beta[1]; a.out0 = z[1]; a.out1 = act[1];
     SR_TRY((launch_conv<kFwd, false>(a, L.conv_grid, s)));
     a.nsrc = 2;
-    a.src[1] = fwd_src(act[1], 32, 32, seg(S_CONV5), 3);
-    a.src[0] = fwd_src(act[0], 32, 32, seg(S_CONV2), 5);
+    a.src[1] = fwd(act[1], 32, SR_SEG_CONV5);
+    a.src[0] = fwd(act[0], 32, SR_SEG_CONV2);
     a.bias = bias[2]; a.beta = beta[2]; a.out0 = z[2]; a.out1 = act[2];
     SR_TRY((launch_conv<kFwd, false>(a, L.conv_grid, s)));
     a.nsrc = 3;
-    a.src[0] = fwd_src(act[0], 32, 32, seg(S_CONV3), 5);
-    a.src[1] = fwd_src(act[1], 32, 32, seg(S_CONV6), 3);
-    a.src[2] = fwd_src(act[2], 32, 32, seg(S_CONV8), 3);
+    a.src[0] = fwd(act[0], 32, SR_SEG_CONV3);
+    a.src[1] = fwd(act[1], 32, SR_SEG_CONV6);
+    a.src[2] = fwd(act[2], 32, SR_SEG_CONV8);
     a.bias = bias[3]; a.beta = beta[3]; a.out0 = z[3]; a.out1 = act[3];
     SR_TRY((launch_conv<kFwd, false>(a, L.conv_grid, s)));
-    a.src[0] = fwd_src(act[1], 32, 32, seg(S_CONV7), 3);
-    a.src[1] = fwd_src(act[2], 32, 32, seg(S_CONV9), 3);
-    a.src[2] = fwd_src(act[3], 32, 32, seg(S_CONV10), 3);
+    a.src[0] = fwd(act[1], 32, SR_SEG_CONV7);
+    a.src[1] = fwd(act[2], 32, SR_SEG_CONV9);
+    a.src[2] = fwd(act[3], 32, SR_SEG_CONV10);
     a.cout = E; a.out_pitch = E;
-    a.bias = seg(S_EBIAS); a.beta = nullptr; a.out0 = e; a.out1 = nullptr;
+    a.bias = seg(SR_SEG_EXP_BIAS); a.beta = nullptr; a.out0 = e; a.out1 = nullptr;
     SR_TRY((launch_conv<kLin, false>(a, L.conv_grid, s)));
 
     // ---- loss and seed
@@ -561,9 +508,7 @@ hipError_t sr_launch_grad(const sr_grad_plan& P, hipStream_t s) {
         default: SR_TRY(launch_loss<4>(P, L, ws, s)); break;
     }
     double* err_part = (double*)(ws + L.o_err);
-    void* err_out = P.err_out ? P.err_out : (void*)(err_part + L.loss_grid);
-    hipLaunchKernelGGL(grad_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)err_part, L.loss_grid, (uint32_t*)err_out);
-    SR_TRY(hipGetLastError());
+    SR_TRY(sr_launch_loss_sum(err_part, L.loss_grid, P.err_out ? P.err_out : (void*)(err_part + L.loss_grid), s));
     hipLaunchKernelGGL(grad_colsum_kernel, dim3((unsigned)L.cchunks), dim3(256), 0, s, (const float*)de, EP, E, L.NP, L.cchunk,
                        ws + L.o_pebias);
     SR_TRY(hipGetLastError());
@@ -578,36 +523,39 @@ hipError_t sr_launch_grad(const sr_grad_plan& P, hipStream_t s) {
         return launch_conv<kBwd, false>(b, L.conv_grid, s);
     };
     b.nsrc = 1;
-    b.src[0] = bwd_src(de, EP, EP, E, seg(S_CONV10), 3, 32);
+    b.src[0] = bwd_of(de, EP, SR_SEG_CONV10);
     SR_TRY(bwd(3));
     b.nsrc = 2;
-    b.src[0] = bwd_src(de, EP, EP, E, seg(S_CONV9), 3, 32);
-    b.src[1] = bwd_src(dz[3], 32, 32, 32, seg(S_CONV8), 3, 32);
+    b.src[0] = bwd_of(de, EP, SR_SEG_CONV9);
+    b.src[1] = bwd_of(dz[3], 32, SR_SEG_CONV8);
     SR_TRY(bwd(2));
     b.nsrc = 3;
-    b.src[0] = bwd_src(de, EP, EP, E, seg(S_CONV7), 3, 32);
-    b.src[1] = bwd_src(dz[3], 32, 32, 32, seg(S_CONV6), 3, 32);
-    b.src[2] = bwd_src(dz[2], 32, 32, 32, seg(S_CONV5), 3, 32);
+    b.src[0] = bwd_of(de, EP, SR_SEG_CONV7);
+    b.src[1] = bwd_of(dz[3], 32, SR_SEG_CONV6);
+    b.src[2] = bwd_of(dz[2], 32, SR_SEG_CONV5);
     SR_TRY(bwd(1));
-    b.src[0] = bwd_src(dz[3], 32, 32, 32, seg(S_CONV3), 5, 32);
-    b.src[1] = bwd_src(dz[2], 32, 32, 32, seg(S_CONV2), 5, 32);
-    b.src[2] = bwd_src(dz[1], 32, 32, 32, seg(S_CONV1), 5, 32);
+    b.src[0] = bwd_of(dz[3], 32, SR_SEG_CONV3);
+    b.src[1] = bwd_of(dz[2], 32, SR_SEG_CONV2);
+    b.src[2] = bwd_of(dz[1], 32, SR_SEG_CONV1);
     SR_TRY(bwd(0));
 
     // ---- weight gradients: the 5x5 convs in one launch, the 3x3 ones in another
     WgradArgs w5{}, w3{};
     w5.n = w3.n = P.n; w5.H = w3.H = P.H; w5.W = w3.W = P.W;
     w5.chunk = w3.chunk = L.wchunk;
-    w5.job[0] = WgradJob{P.x, dz[0], ws + L.o_wpart[0], 3, 3, 32, 32};
-    w5.job[1] = WgradJob{act[0], dz[1], ws + L.o_wpart[1], 32, 32, 32, 32};
-    w5.job[2] = WgradJob{act[0], dz[2], ws + L.o_wpart[2], 32, 32, 32, 32};
-    w5.job[3] = WgradJob{act[0], dz[3], ws + L.o_wpart[3], 32, 32, 32, 32};
-    w3.job[0] = WgradJob{act[1], dz[2], ws + L.o_wpart[4], 32, 32, 32, 32};  // conv5
-    w3.job[1] = WgradJob{act[1], dz[3], ws + L.o_wpart[5], 32, 32, 32, 32};  // conv6
-    w3.job[2] = WgradJob{act[1], de, ws + L.o_wpart[6], 32, 32, E, EP};      // conv7
-    w3.job[3] = WgradJob{act[2], dz[3], ws + L.o_wpart[7], 32, 32, 32, 32};  // conv8
-    w3.job[4] = WgradJob{act[2], de, ws + L.o_wpart[8], 32, 32, E, EP};      // conv9
-    w3.job[5] = WgradJob{act[3], de, ws + L.o_wpart[9], 32, 32, E, EP};      // conv10
+    auto wjob = [&](const float* x, int x_pitch, const float* dy, int dy_pitch, int sg) {
+        return WgradJob{x, dy, wpart[sg], S.cin(sg), x_pitch, S.cout(sg), dy_pitch};
+    };
+    w5.job[0] = wjob(P.x, 3, dz[0], 32, SR_SEG_CONV0);
+    w5.job[1] = wjob(act[0], 32, dz[1], 32, SR_SEG_CONV1);
+    w5.job[2] = wjob(act[0], 32, dz[2], 32, SR_SEG_CONV2);
+    w5.job[3] = wjob(act[0], 32, dz[3], 32, SR_SEG_CONV3);
+    w3.job[0] = wjob(act[1], 32, dz[2], 32, SR_SEG_CONV5);
+    w3.job[1] = wjob(act[1], 32, dz[3], 32, SR_SEG_CONV6);
+    w3.job[2] = wjob(act[1], 32, de, EP, SR_SEG_CONV7);
+    w3.job[3] = wjob(act[2], 32, dz[3], 32, SR_SEG_CONV8);
+    w3.job[4] = wjob(act[2], 32, de, EP, SR_SEG_CONV9);
+    w3.job[5] = wjob(act[3], 32, de, EP, SR_SEG_CONV10);
     hipLaunchKernelGGL((grad_wgrad_kernel<5>), dim3((unsigned)L.wchunks, 5, 4 * 2), dim3(64), 0, s, w5);
     SR_TRY(hipGetLastError());
     hipLaunchKernelGGL((grad_wgrad_kernel<3>), dim3((unsigned)L.wchunks, 3, 6 * 2), dim3(64), 0, s, w3);
@@ -615,24 +563,23 @@ hipError_t sr_launch_grad(const sr_grad_plan& P, hipStream_t s) {
 
     // ---- assembly
     AssembleArgs as{};
-    as.total = S.off[kSegs - 1] + S.len[kSegs - 1];
-    for (int k = 0; k < kSegs; ++k) {
-        as.seg[k].off = S.off[k];
-        as.seg[k].len = S.len[k];
+    as.total = (int)S.total;
+    for (int sg = 0; sg < SR_SEGS; ++sg) {
+        as.seg[sg].off = (int)S.off[sg];
+        as.seg[sg].len = (int)S.len[sg];
+        if (S.is_conv(sg)) {
+            as.seg[sg].part = wpart[sg];
+            as.seg[sg].nparts = L.wchunks;
+        }
     }
-    for (int k = 0; k < 10; ++k) {
-        as.seg[kConvSeg[k]].part = ws + L.o_wpart[k];
-        as.seg[kConvSeg[k]].nparts = L.wchunks;
-    }
-    const int bias_seg[4] = {S_FBIAS, S_L1B, S_L2B, S_L3B}, beta_seg[4] = {S_FACT, S_L1A, S_L2A, S_L3A};
     for (int k = 0; k < 4; ++k) {
         as.seg[bias_seg[k]].part = ws + L.o_pbias[k];
         as.seg[bias_seg[k]].nparts = L.conv_grid;
         as.seg[beta_seg[k]].part = ws + L.o_pbeta[k];
         as.seg[beta_seg[k]].nparts = L.conv_grid;
     }
-    as.seg[S_EBIAS].part = ws + L.o_pebias;
-    as.seg[S_EBIAS].nparts = L.cchunks;
+    as.seg[SR_SEG_EXP_BIAS].part = ws + L.o_pebias;
+    as.seg[SR_SEG_EXP_BIAS].nparts = L.cchunks;
     hipLaunchKernelGGL(grad_assemble_kernel, dim3((unsigned)((as.total + 255) / 256)), dim3(256), 0, s, as, prm, 2.0f * P.l2, P.grad);
     return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -142,6 +143,52 @@ inline bool sr_dword_aligned(const void* p) {
     return ((uintptr_t)p & 3u) == 0;
 }
 
+// No HIP device to run on (the runtime reports none, or fails): what an entry point without a context answers SR_E_NO_DEVICE to.
+// clear_error: read the runtime's error away, so that no later launch check finds it.  count (optional): the number of devices.
+inline bool sr_no_device(bool clear_error = true, int* count = nullptr) {
+    int n = 0;
+    const bool failed = hipGetDeviceCount(&n) != hipSuccess;
+    if (failed && clear_error) (void)hipGetLastError();
+    if (count) *count = n;
+    return failed || n <= 0;
+}
+
+inline void sr_free_buf(void*& p, size_t& cap) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+}
+
+inline size_t sr_round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// ---- the HR images of the training graph (validation, backpropagation, training session): n images of h x w pixels, u8 with 3 or 4
+// channels (alpha is ignored) or f32 RGB
+inline bool sr_hr_channels_ok(bool hr_u8, int ch) { return hr_u8 ? (ch == 3 || ch == 4) : ch == 3; }
+
+// The HR arguments of an entry point of context c (not null), checked before the GPU is touched.
+inline int sr_check_hr_args(const sr_ctx* c, bool hr_u8, int ch, int n, int h, int w) {
+    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    if (!sr_hr_channels_ok(hr_u8, ch)) return SR_E_INVALID;
+    if (n < 1 || h < c->factor || w < c->factor) return SR_E_INVALID;  // not one f x f pooling block
+    return SR_OK;
+}
+
+// Elements the loss is summed over: 3 channels of the top-left f floor(h / f) x f floor(w / f) crop of each image.
+inline size_t sr_loss_elems(int f, int n, int h, int w) { return (size_t)n * 3 * ((size_t)f * (h / f)) * ((size_t)f * (w / f)); }
+
+// The run-time (hr_u8, ch, linear) of such a call as compile-time constants: fn(bool_constant<HR_U8>, integral_constant<int, CH>,
+// bool_constant<LINEAR>), for the combinations sr_hr_channels_ok admits.
+template <class Fn>
+void sr_dispatch_hr(bool hr_u8, int ch, bool linear, Fn&& fn) {
+    auto with_linear = [&](auto u8, auto channels) {
+        if (linear) fn(u8, channels, std::true_type{});
+        else fn(u8, channels, std::false_type{});
+    };
+    if (hr_u8 && ch == 3) with_linear(std::true_type{}, std::integral_constant<int, 3>{});
+    else if (hr_u8) with_linear(std::true_type{}, std::integral_constant<int, 4>{});
+    else with_linear(std::false_type{}, std::integral_constant<int, 3>{});
+}
+
 // The library never leaves the calling thread on another device than it found it on: torch (and any HIP host) takes
 // "the current device" from hipGetDevice, and the one-process multi-GPU calls walk over every context's device.
 // Every extern "C" entry point that may call hipSetDevice holds one of these for its duration.
@@ -209,6 +256,9 @@ hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch
 // sum over the HC x WC crop of (out - hr)^2 (linear: of SrgbToLinear of both) -> one double at d_result (4-byte aligned)
 hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,
                                 double* d_partial, void* d_result, hipStream_t s);
+// The f64 partials of a loss kernel -> their sum, one double at d_result (4-byte aligned): one workgroup, a fixed order of additions, so
+// the same bits on every run, context and device (also the backward pass's err_sum)
+hipError_t sr_launch_loss_sum(const double* d_partial, int n, void* d_result, hipStream_t s);
 
 // ---- backpropagation (sr_grad.hip kernels, sr_grad.cpp host side)
 void sr_grad_release(sr_ctx* c);  // sr_grad.cpp: free the backprop buffers (called by sr_destroy)

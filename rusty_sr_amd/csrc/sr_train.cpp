@@ -10,19 +10,9 @@
 #include <vector>
 
 #include "sr_internal.h"
+#include "sr_params.h"
 
 namespace {
-
-bool no_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    return n <= 0;
-}
-
-size_t round256(size_t b) { return (b + 255) / 256 * 256; }
 
 struct SplitMix64 {
     uint64_t s;
@@ -44,7 +34,7 @@ struct sr_train {
     int np = 0;
     bool linear = false;
     float l2 = 0, lr = 0, beta1 = 0, beta2 = 0, eps = 0;
-    float* d_state = nullptr;  // parameters, first and second moments, gradient: 4 slices of round256(np floats)
+    float* d_state = nullptr;  // parameters, first and second moments, gradient: 4 slices of sr_round256(np floats)
     float *d_p = nullptr, *d_m = nullptr, *d_v = nullptr, *d_g = nullptr;
     // err_sum of each step: a ring of mapped host doubles the backprop's sum kernel writes, each slot free once its step's event has fired
     double* h_err = nullptr;
@@ -72,7 +62,7 @@ namespace {
 int grow(sr_ctx* c, hipStream_t s, void** p, size_t* cap, size_t bytes) {
     if (bytes <= *cap) return SR_OK;
     HIPCHK(c, hipStreamSynchronize(s));
-    return sr_ensure_buf(c, p, cap, round256(bytes));
+    return sr_ensure_buf(c, p, cap, sr_round256(bytes));
 }
 
 // Read the err_sum of the oldest step in flight (waits for it).
@@ -125,26 +115,17 @@ int sr_init_params(int factor, uint64_t seed, float* out, size_t cap) {
     const int np = sr_num_params_factor(factor);
     if (np < 0) return SR_E_FACTOR;
     if (!out || cap < (size_t)np) return SR_E_INVALID;
-    // segments in .rsr order (network.rs:33-72): (length, fan_in, multiplier); fan_in 0: a bias (0), -1: a BeLU beta
-    const int E = 3 * factor * factor;
-    const struct { int n, fan_in; double mult; } seg[] = {
-        {2400, 75, 1.0},                                    // conv0: 5x5, 3 -> 32
-        {32, 0, 0}, {32, -1, 0}, {E, 0, 0},                 // f_bias, f_activ, expand_bias
-        {32, 0, 0}, {32, 0, 0}, {32, 0, 0},                 // l1..l3 biases
-        {32, -1, 0}, {32, -1, 0}, {32, -1, 0},              // l1..l3 activations
-        {25600, 800, 0.1}, {25600, 800, 0.1}, {25600, 800, 0.1},  // conv1..conv3: 5x5, 32 -> 32
-        {9216, 288, 0.1}, {9216, 288, 0.1},                 // conv5, conv6: 3x3, 32 -> 32
-        {E * 288, 288, 0.1}, {9216, 288, 0.1},              // conv7 (3x3, 32 -> 3 f^2), conv8
-        {E * 288, 288, 0.1}, {E * 288, 288, 0.1},           // conv9, conv10
-    };
+    // segment by segment in .rsr order: a bias is 0, a BeLU beta alternates 1, 0, a convolution draws He-normal weights (two uniforms each)
+    const sr_param_layout L(factor);
     SplitMix64 rng{seed};
     size_t o = 0;
-    for (const auto& s : seg) {
-        for (int i = 0; i < s.n; ++i, ++o) {
-            if (s.fan_in == 0) out[o] = 0.0f;
-            else if (s.fan_in < 0) out[o] = i % 2 == 0 ? 1.0f : 0.0f;
+    for (int sg = 0; sg < SR_SEGS; ++sg) {
+        const sr_seg_def& d = kSrSegDefs[sg];
+        for (size_t i = 0; i < L.len[sg]; ++i, ++o) {
+            if (d.kind == SR_KIND_BIAS) out[o] = 0.0f;
+            else if (d.kind == SR_KIND_BETA) out[o] = i % 2 == 0 ? 1.0f : 0.0f;
             else {
-                const double std = s.mult * std::sqrt(2.0 / s.fan_in);
+                const double std = d.init_mult * std::sqrt(2.0 / L.fan_in(sg));
                 const double u1 = rng.uniform(), u2 = rng.uniform();
                 out[o] = (float)(std * std::sqrt(-2.0 * std::log(1.0 - u1)) * std::cos(2.0 * 3.14159265358979323846 * u2));
             }
@@ -155,7 +136,7 @@ int sr_init_params(int factor, uint64_t seed, float* out, size_t cap) {
 
 int sr_train_create(sr_train** out, sr_ctx* c, const float* start_params, size_t n_params, int linear_loss, float l2, float lr, float beta1,
                     float beta2, float eps, size_t store_bytes) {
-    if (!c && no_device()) return SR_E_NO_DEVICE;
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
     if (!out || !c || !start_params) return SR_E_INVALID;
     *out = nullptr;
     if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
@@ -172,7 +153,7 @@ int sr_train_create(sr_train** out, sr_ctx* c, const float* start_params, size_t
         HIPCHK(c, hipSetDevice(c->device));
         int r = sr_ensure_streams(c, false);
         if (r != SR_OK) return r;
-        const size_t slice = round256((size_t)np * sizeof(float));
+        const size_t slice = sr_round256((size_t)np * sizeof(float));
         HIPCHK(c, hipMalloc((void**)&t->d_state, 4 * slice));
         t->d_p = t->d_state;
         t->d_m = (float*)((char*)t->d_state + slice);
@@ -204,11 +185,11 @@ int sr_train_create(sr_train** out, sr_ctx* c, const float* start_params, size_t
 }
 
 int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, int w, int* id) {
-    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c || !px || !id || (in_channels != 3 && in_channels != 4) || h < 1 || w < 1) return SR_E_INVALID;
     *id = -1;
     sr_ctx* c = t->c;
-    const size_t bytes = (size_t)h * w * in_channels, alloc = round256(bytes);
+    const size_t bytes = (size_t)h * w * in_channels, alloc = sr_round256(bytes);
     if (alloc > t->store_budget - std::min(t->store_budget, t->store_used) || t->images.size() >= (size_t)INT32_MAX) return SR_OK;
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
@@ -229,7 +210,7 @@ int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, i
 }
 
 int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, int crop_w) {
-    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c || !items || n < 1 || n > SR_TRAIN_MAX_BATCH) return SR_E_INVALID;
     sr_ctx* c = t->c;
     if (crop_h < c->factor || crop_w < c->factor) return SR_E_INVALID;
@@ -242,7 +223,7 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
         } else if (it.image == -1) {
             if (!it.px || (it.in_channels != 3 && it.in_channels != 4) || it.h < 1 || it.w < 1) return SR_E_INVALID;
             const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + crop_h, 0, it.h);
-            trans_bytes += round256((size_t)(r1 - r0) * it.w * it.in_channels);
+            trans_bytes += sr_round256((size_t)(r1 - r0) * it.w * it.in_channels);
         } else {
             return SR_E_INVALID;
         }
@@ -272,8 +253,8 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
             if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
             t->h_stage[k] = nullptr;
             t->stage_cap[k] = 0;
-            HIPCHK(c, hipHostMalloc(&t->h_stage[k], round256(trans_bytes), hipHostMallocPortable));
-            t->stage_cap[k] = round256(trans_bytes);
+            HIPCHK(c, hipHostMalloc(&t->h_stage[k], sr_round256(trans_bytes), hipHostMallocPortable));
+            t->stage_cap[k] = sr_round256(trans_bytes);
         }
     }
     size_t off = 0;
@@ -285,7 +266,7 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
         if (bytes) memcpy((char*)t->h_stage[k] + off, it.px + (size_t)r0 * row, bytes);
         // the staged rows as an image of r1 - r0 rows: the crop's rows outside them are outside the source image too
         a.d[i] = {(const uint8_t*)t->d_trans + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0};
-        off += round256(bytes);
+        off += sr_round256(bytes);
     }
     if (trans_bytes) {
         HIPCHK(c, hipMemcpyAsync(t->d_trans, t->h_stage[k], trans_bytes, hipMemcpyHostToDevice, s));
@@ -300,8 +281,7 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
         a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0};
     }
     HIPCHK(c, sr_launch_train_crop(a, (uint32_t*)t->d_batch, s));
-    const int f = c->factor;
-    const size_t n_elems = (size_t)n * 3 * ((size_t)f * (crop_h / f)) * ((size_t)f * (crop_w / f));
+    const size_t n_elems = sr_loss_elems(c->factor, n, crop_h, crop_w);
     const int slot = (int)(t->queued % SR_TRAIN_RING);
     rc = sr_backprop_rgba8_dev(c, t->d_p, (const uint8_t*)t->d_batch, 3, n, crop_h, crop_w, t->linear ? 1 : 0, (float)(1.0 / (double)n_elems),
                                t->l2, t->d_err + slot, t->d_g, s);
@@ -315,7 +295,7 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
 }
 
 int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps) {
-    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c) return SR_E_INVALID;
     sr_device_guard restore_device;
     HIPCHK(t->c, hipSetDevice(t->c->device));
@@ -328,7 +308,7 @@ int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps) {
 }
 
 int sr_train_params(sr_train* t, float* out, size_t cap) {
-    if (!t && no_device()) return SR_E_NO_DEVICE;
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c || !out || cap < (size_t)t->np) return SR_E_INVALID;
     sr_device_guard restore_device;
     HIPCHK(t->c, hipSetDevice(t->c->device));

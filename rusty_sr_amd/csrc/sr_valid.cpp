@@ -31,19 +31,10 @@ int ensure_table(sr_ctx* c) {
     return SR_OK;
 }
 
-void free_buf(void*& p, size_t& cap) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-}
-
 // Arguments of every entry point, checked before the GPU is touched.
 int check_args(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w) {
     if (!c || !hr) return SR_E_INVALID;
-    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
-    if (hr_u8 ? (ch != 3 && ch != 4) : ch != 3) return SR_E_INVALID;
-    if (h < c->factor || w < c->factor) return SR_E_INVALID;  // not one f x f pooling block
-    return SR_OK;
+    return sr_check_hr_args(c, hr_u8, ch, 1, h, w);
 }
 
 // Pool, network, loss on device buffers, queued on s; the sum lands at d_result (nullptr: the slot behind the partials, for the
@@ -58,8 +49,8 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
     if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vpart, &c->vpart_cap, (size_t)(grid + 1) * sizeof(double));
     c->vnode_h = c->vnode_w = 0;
     if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
-        free_buf(c->d_vlr, c->vlr_cap);
-        free_buf(c->d_vout, c->vout_cap);
+        sr_free_buf(c->d_vlr, c->vlr_cap);
+        sr_free_buf(c->d_vout, c->vout_cap);
         return rc;
     }
     if (!d_result) d_result = (double*)c->d_vpart + grid;
@@ -87,7 +78,7 @@ int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w,
     const size_t hr_bytes = (size_t)h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
     rc = sr_ensure_buf(c, &c->d_vhr, &c->vhr_cap, hr_bytes);
     if (rc != SR_OK) {
-        free_buf(c->d_vhr, c->vhr_cap);
+        sr_free_buf(c->d_vhr, c->vhr_cap);
         return rc;
     }
     hipStream_t s = c->stream;
@@ -117,7 +108,7 @@ int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w,
         if (hipEventElapsedTime(&ms, c->ev[6], c->ev[7]) == hipSuccess) c->total_ms = ms; else (void)hipGetLastError();
     }
     *err_sum = sum;
-    *n_elems = (size_t)f * (h / f) * f * (w / f) * 3;
+    *n_elems = sr_loss_elems(f, 1, h, w);
     return SR_OK;
 }
 
@@ -128,10 +119,10 @@ int sr_valid_ensure_table(sr_ctx* c) {
 }
 
 void sr_valid_release(sr_ctx* c) {
-    free_buf(c->d_vhr, c->vhr_cap);
-    free_buf(c->d_vlr, c->vlr_cap);
-    free_buf(c->d_vout, c->vout_cap);
-    free_buf(c->d_vpart, c->vpart_cap);
+    sr_free_buf(c->d_vhr, c->vhr_cap);
+    sr_free_buf(c->d_vlr, c->vlr_cap);
+    sr_free_buf(c->d_vout, c->vout_cap);
+    sr_free_buf(c->d_vpart, c->vpart_cap);
     if (c->d_vtab) (void)hipFree(c->d_vtab);
     c->d_vtab = nullptr;
     c->vnode_h = c->vnode_w = 0;

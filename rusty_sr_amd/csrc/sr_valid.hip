@@ -3,7 +3,7 @@
 //
 //   input  = LinearToSrgb(mean_{f x f}(SrgbToLinear(hr)))       valid_pool_kernel    (the network's LR input, f32, not quantised)
 //   output = sr_net(f)(input)                                     the stage kernels (sr_kernels.hip), f32 output
-//   err    = sum (output - hr)^2                                  valid_loss_kernel + valid_sum_kernel
+//   err    = sum (output - hr)^2                                  valid_loss_kernel + loss_sum_kernel
 //         or sum (SrgbToLinear(output) - SrgbToLinear(hr))^2     (-l / --linearLoss)
 //
 // over the top-left f*floor(h/f) x f*floor(w/f) crop of the HR image (UNPINNED: the remainder rule of the downsample graph).
@@ -17,7 +17,7 @@
 // Loss: memory-bound (a 4K HR image: 100 MB of f32 output + 33 MB of RGBA8), so the kernel is sized against the measured 6.29 TB/s copy
 // rate: a thread takes 4 output pixels at a time -- three 16-byte loads of the output, the 4 HR pixels as the aligned dwords that hold
 // them -- and every difference is formed in f32 and squared and summed in f64.  One f64 partial per workgroup; the grid depends on
-// the shape alone (never on the CU count), and valid_sum_kernel adds the partials in a fixed order in one workgroup: the result is
+// the shape alone (never on the CU count), and loss_sum_kernel adds the partials in a fixed order in one workgroup: the result is
 // the same bits on every run, context and device.  No atomics.
 // In linear-loss mode SrgbToLinear must be a function the tests can restate bit for bit: it is the correctly rounded f32 of the
 // formula (an f32 estimate on the hardware pow, two Newton steps for the fifth root in f64 -- x^2.4 = x^2 * (x^2)^(1/5) -- then one
@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "sr_internal.h"
+#include "sr_reduce.h"
 #include "sr_transfer.h"
 
 #pragma clang fp contract(off)
@@ -104,22 +105,6 @@ __global__ __launch_bounds__(256) void valid_pool_kernel(const void* __restrict_
     ((F3*)lr)[idx] = o;
 }
 
-// sum over the 64 lanes of a wave by butterfly shuffles: every lane ends with the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// workgroup of 256: every wave's sum, then the four in order; the result in thread 0
-__device__ __forceinline__ double block_sum(double v, double* s_part) {
-    v = wave_sum(v);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) s_part[wave] = v;
-    __syncthreads();
-    return ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-}
-
 constexpr int kLossMaxGrid = 2048;   // workgroups of valid_loss_kernel at most (the number of f64 partials)
 
 // out: the network's f32 output, HC x WC x 3, contiguous and 16-byte aligned (a context buffer); hr: the HR image, row pitch W pixels;
@@ -183,8 +168,8 @@ __global__ __launch_bounds__(256) void valid_loss_kernel(const float* __restrict
 }
 
 // one workgroup: partials t, t + 256, ... per thread, then the workgroup's sum; stored as two dwords (the caller's pointer is only
-// 4-byte aligned)
-__global__ __launch_bounds__(256) void valid_sum_kernel(const double* __restrict__ partial, int n, uint32_t* __restrict__ result) {
+// 4-byte aligned).  Also the sum of the backward pass's loss partials (sr_grad.hip).
+__global__ __launch_bounds__(256) void loss_sum_kernel(const double* __restrict__ partial, int n, uint32_t* __restrict__ result) {
     __shared__ double s_part[4];
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
@@ -198,17 +183,10 @@ __global__ __launch_bounds__(256) void valid_sum_kernel(const double* __restrict
 
 template <int F>
 void launch_pool(const void* hr, bool hr_u8, int ch, float* lr, const float* tab, int W, int OH, int OW, hipStream_t s) {
-    const long px = (long)OH * OW;
-    const dim3 grid((unsigned)((px + 255) / 256));
-    if (hr_u8 && ch == 3) hipLaunchKernelGGL((valid_pool_kernel<F, true, 3>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
-    else if (hr_u8) hipLaunchKernelGGL((valid_pool_kernel<F, true, 4>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
-    else hipLaunchKernelGGL((valid_pool_kernel<F, false, 3>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
-}
-
-template <bool HR_U8, int CH>
-void launch_loss(bool linear, int grid, const float* out, const void* hr, const float* tab, int W, int HC, int WC, double* partial, hipStream_t s) {
-    if (linear) hipLaunchKernelGGL((valid_loss_kernel<HR_U8, CH, true>), dim3(grid), dim3(256), 0, s, out, hr, tab, W, HC, WC, partial);
-    else hipLaunchKernelGGL((valid_loss_kernel<HR_U8, CH, false>), dim3(grid), dim3(256), 0, s, out, hr, tab, W, HC, WC, partial);
+    const dim3 grid((unsigned)(((long)OH * OW + 255) / 256));
+    sr_dispatch_hr(hr_u8, ch, false, [&](auto u8, auto channels, auto) {  // (the pool is the same in both loss modes)
+        hipLaunchKernelGGL((valid_pool_kernel<F, decltype(u8)::value, decltype(channels)::value>), grid, dim3(256), 0, s, hr, lr, tab, W, OH, OW);
+    });
 }
 
 }  // namespace
@@ -220,7 +198,7 @@ int sr_valid_loss_grid(int HC, int WC) {
 
 hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch, int W, int OH, int OW, float* d_lr, const float* d_tab,
                                 hipStream_t s) {
-    if (OH <= 0 || OW <= 0 || (hr_u8 ? (ch != 3 && ch != 4) : ch != 3)) return hipErrorInvalidValue;
+    if (OH <= 0 || OW <= 0 || !sr_hr_channels_ok(hr_u8, ch)) return hipErrorInvalidValue;
     switch (factor) {
         case 2: launch_pool<2>(d_hr, hr_u8, ch, d_lr, d_tab, W, OH, OW, s); break;
         case 3: launch_pool<3>(d_hr, hr_u8, ch, d_lr, d_tab, W, OH, OW, s); break;
@@ -232,13 +210,18 @@ hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch
 
 hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,
                                 double* d_partial, void* d_result, hipStream_t s) {
-    if (HC <= 0 || WC <= 0 || (hr_u8 ? (ch != 3 && ch != 4) : ch != 3)) return hipErrorInvalidValue;
+    if (HC <= 0 || WC <= 0 || !sr_hr_channels_ok(hr_u8, ch)) return hipErrorInvalidValue;
     const int grid = sr_valid_loss_grid(HC, WC);
-    if (hr_u8 && ch == 3) launch_loss<true, 3>(linear, grid, d_out, d_hr, d_tab, W, HC, WC, d_partial, s);
-    else if (hr_u8) launch_loss<true, 4>(linear, grid, d_out, d_hr, d_tab, W, HC, WC, d_partial, s);
-    else launch_loss<false, 3>(linear, grid, d_out, d_hr, d_tab, W, HC, WC, d_partial, s);
-    hipError_t e = hipGetLastError();
+    sr_dispatch_hr(hr_u8, ch, linear, [&](auto u8, auto channels, auto lin) {
+        hipLaunchKernelGGL((valid_loss_kernel<decltype(u8)::value, decltype(channels)::value, decltype(lin)::value>), dim3(grid), dim3(256), 0,
+                           s, d_out, d_hr, d_tab, W, HC, WC, d_partial);
+    });
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(valid_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)d_partial, grid, (uint32_t*)d_result);
+    return sr_launch_loss_sum(d_partial, grid, d_result, s);
+}
+
+hipError_t sr_launch_loss_sum(const double* d_partial, int n, void* d_result, hipStream_t s) {
+    hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(256), 0, s, d_partial, n, (uint32_t*)d_result);
     return hipGetLastError();
 }
