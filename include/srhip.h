@@ -384,6 +384,59 @@ int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps);
 int sr_train_params(sr_train* t, float* out, size_t cap);  /* waits; the current parameters (cap >= n_params) */
 void sr_train_destroy(sr_train* t);
 
+/* ---- Pairs: validation, backpropagation and training on LR / HR image pairs ----
+ * The reference's training graph makes its own input, LinearToSrgb(mean_f x f(SrgbToLinear(hr))) (network.rs:87-92): every parameter file
+ * it trains is a model of that one degradation.  The sr_pair_* entry points (and the session's sr_train_add_pair / sr_train_step_pairs) take the network's input from the
+ * caller instead (the reference's later releases have this as train_prescaled).  For the context's factor f (2, 3 or 4):
+ *   The LR image is lh x lw, the HR image exactly f lh x f lw -- the sizes are passed once, as lh, lw; lh < 1 or lw < 1 is SR_E_INVALID
+ *   before any launch, and a host whose images have other sizes must refuse them itself (the Python binding and the CLI do).
+ *   input  = img_to_data(lr): each byte as (float)b / 255.0f, RGB, alpha dropped (bit-equal to an f32 division for all 256 bytes);
+ *            an f32 LR image is taken as is
+ *   output = sr_net(f)(input), f32, no clamp;  e = output - hr, or SrgbToLinear(output) - SrgbToLinear(hr) with linear_loss
+ *   err_sum, grad: the text of sr_validation_error_* / sr_backprop_* above -- differences formed in f32, squares summed in f64,
+ *            n_elems = n 3 f lh f lw, the gradient of loss_scale sum e^2 + l2 sum p^2 at the `params` passed
+ * Backpropagation is always exact f32; validation follows the context's precision (and, in SR_PRECISION_SPLIT_F16, the host-pointer forms
+ * recompute in exact f32 where a value leaves that mode's domain).  No atomics, a fixed reduction order: the same bits on every run,
+ * context and device.  Everything behind the input stage is the code of the pooled calls: a pair whose LR image is the pooled calls' own
+ * input gives their result bit for bit.  SR_GRAPH_SR_NET contexts only; the other refusals (SR_E_PARAM_COUNT, SR_E_NOMEM, SR_E_NO_DEVICE)
+ * are those of the pooled calls.  u8 forms: lr_channels and hr_channels are 3 or 4, independently.  Synchronous, host memory: */
+int sr_pair_validation_error_rgba8(sr_ctx* ctx, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
+                                   int linear_loss, double* err_sum, size_t* n_elems);
+int sr_pair_validation_error_f32(sr_ctx* ctx, const float* lr, const float* hr, int lh, int lw, int linear_loss,
+                                 double* err_sum, size_t* n_elems);
+/* ... device memory, ordered on `stream` alone.  d_lr, like d_hr, may start at any byte (read as whole aligned 32-bit words);
+ * d_err_sum 4-byte aligned.  After any of the three, sr_read_validation_nodes' lr_out is the converted LR image (lh x lw x 3). */
+int sr_pair_validation_error_rgba8_dev(sr_ctx* ctx, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
+                                       int linear_loss, double* d_err_sum, void* stream);
+/* Batches of n pairs (`lr` n x lh x lw x lr_channels bytes or x 3 floats, `hr` n x f lh x f lw x hr_channels bytes or x 3 floats): */
+int sr_pair_backprop_f32(sr_ctx* ctx, const float* params, size_t n_params, const float* lr, const float* hr, int n, int lh, int lw,
+                         int linear_loss, float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad);
+int sr_pair_backprop_rgba8(sr_ctx* ctx, const float* params, size_t n_params, const uint8_t* lr, int lr_channels, const uint8_t* hr,
+                           int hr_channels, int n, int lh, int lw, int linear_loss, float loss_scale, float l2, double* err_sum,
+                           size_t* n_elems, float* grad);
+/* ... device memory: d_lr and d_hr may start at any byte; d_params, d_grad and d_err_sum must be 4-byte aligned (else SR_E_INVALID before
+ * any launch).  16 kernel launches: the LR conversion in the pool's place, then the 15 of the backward pass. */
+int sr_pair_backprop_rgba8_dev(sr_ctx* ctx, const float* d_params, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels,
+                               int n, int lh, int lw, int linear_loss, float loss_scale, float l2, double* d_err_sum, float* d_grad,
+                               void* stream);
+/* A training session's pairs.  sr_train_add_pair uploads both images as ONE store entry (out of the same budget; *id = -1 when there is
+ * no room); ids of pairs and of plain images come from one sequence, and each kind is refused (SR_E_INVALID) where the other is asked
+ * for.  sr_train_step_pairs is sr_train_step on pairs: y0 / x0 are in LR pixels, the LR crop is crop_lh x crop_lw there and the HR crop
+ * f crop_lh x f crop_lw at (f y0, f x0); pixels outside the images are 0 in both crops, origins may be negative or overhang.  One launch,
+ * train_pair_crop_kernel, cuts the HR crops into the u8 batch and the LR crops -- converted, f32 -- straight into the backward pass's input:
+ * such a step has no pool launch (crop, the backward pass's 15 launches, Adam).  A transient pair (pair = -1) passes the rows its crops can
+ * reach through the session's staging.  The refusals and the ring, drain and SR_E_NOMEM rules of sr_train_step hold; a session may mix both
+ * kinds of step. */
+typedef struct {
+    int pair;              /* id of a resident pair, or -1: the pixels below */
+    const uint8_t* lr_px;  /* pair = -1: lh x lw x lr_channels u8, host memory */
+    const uint8_t* hr_px;  /*            f lh x f lw x hr_channels u8 */
+    int lr_channels, hr_channels, lh, lw;
+    int y0, x0;            /* crop origin in the LR image */
+} sr_train_pair_crop;
+int sr_train_add_pair(sr_train* t, const uint8_t* lr_px, int lr_channels, const uint8_t* hr_px, int hr_channels, int lh, int lw, int* id);
+int sr_train_step_pairs(sr_train* t, const sr_train_pair_crop* items, int n, int crop_lh, int crop_lw);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -16,6 +16,20 @@ pub struct SrTrain {
     _private: [u8; 0],
 }
 
+/// `sr_train_pair_crop`: a resident pair id, or -1 and both images' host pixels; the crop origin in LR pixels.
+#[repr(C)]
+pub struct SrTrainPairCrop {
+    pub pair: c_int,
+    pub lr_px: *const u8,
+    pub hr_px: *const u8,
+    pub lr_channels: c_int,
+    pub hr_channels: c_int,
+    pub lh: c_int,
+    pub lw: c_int,
+    pub y0: c_int,
+    pub x0: c_int,
+}
+
 /// `sr_train_crop`: a resident image id, or -1 and host pixels; the crop origin.
 #[repr(C)]
 pub struct SrTrainCrop {
@@ -119,6 +133,14 @@ extern "C" {
     pub fn sr_train_sync(t: *mut SrTrain, err_sums: *mut f64, cap: usize, n_steps: *mut usize) -> c_int;
     pub fn sr_train_params(t: *mut SrTrain, out: *mut f32, cap: usize) -> c_int;
     pub fn sr_train_destroy(t: *mut SrTrain);
+    pub fn sr_pair_validation_error_rgba8(ctx: *mut SrCtx, lr: *const u8, lr_channels: c_int, hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
+    pub fn sr_pair_validation_error_f32(ctx: *mut SrCtx, lr: *const f32, hr: *const f32, lh: c_int, lw: c_int, linear_loss: c_int, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
+    pub fn sr_pair_validation_error_rgba8_dev(ctx: *mut SrCtx, d_lr: *const u8, lr_channels: c_int, d_hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, d_err_sum: *mut f64, stream: *mut c_void) -> c_int;
+    pub fn sr_pair_backprop_f32(ctx: *mut SrCtx, params: *const f32, n_params: usize, lr: *const f32, hr: *const f32, n: c_int, lh: c_int, lw: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, err_sum: *mut f64, n_elems: *mut usize, grad: *mut f32) -> c_int;
+    pub fn sr_pair_backprop_rgba8(ctx: *mut SrCtx, params: *const f32, n_params: usize, lr: *const u8, lr_channels: c_int, hr: *const u8, hr_channels: c_int, n: c_int, lh: c_int, lw: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, err_sum: *mut f64, n_elems: *mut usize, grad: *mut f32) -> c_int;
+    pub fn sr_pair_backprop_rgba8_dev(ctx: *mut SrCtx, d_params: *const f32, d_lr: *const u8, lr_channels: c_int, d_hr: *const u8, hr_channels: c_int, n: c_int, lh: c_int, lw: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, d_err_sum: *mut f64, d_grad: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_train_add_pair(t: *mut SrTrain, lr_px: *const u8, lr_channels: c_int, hr_px: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, id: *mut c_int) -> c_int;
+    pub fn sr_train_step_pairs(t: *mut SrTrain, items: *const SrTrainPairCrop, n: c_int, crop_lh: c_int, crop_lw: c_int) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

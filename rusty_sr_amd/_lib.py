@@ -26,6 +26,12 @@ class TrainCrop(C.Structure):
                 ("y0", C.c_int), ("x0", C.c_int)]
 
 
+class TrainPairCrop(C.Structure):
+    """sr_train_pair_crop (include/srhip.h): a resident pair id, or -1 and both images' host pixels; the crop origin in LR pixels."""
+    _fields_ = [("pair", C.c_int), ("lr_px", C.c_void_p), ("hr_px", C.c_void_p), ("lr_channels", C.c_int), ("hr_channels", C.c_int),
+                ("lh", C.c_int), ("lw", C.c_int), ("y0", C.c_int), ("x0", C.c_int)]
+
+
 # every symbol include/srhip.h declares: (restype, argtypes)
 _vp, _fp, _u8p, _dp = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
 _sz, _i = C.c_size_t, C.c_int
@@ -90,6 +96,14 @@ SYMBOLS = {
     "sr_train_sync": (_i, [_vp, _dp, _sz, C.POINTER(_sz)]),
     "sr_train_params": (_i, [_vp, _fp, _sz]),
     "sr_train_destroy": (None, [_vp]),
+    "sr_pair_validation_error_rgba8": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, _i, _dp, C.POINTER(_sz)]),
+    "sr_pair_validation_error_f32": (_i, [_vp, _fp, _fp, _i, _i, _i, _dp, C.POINTER(_sz)]),
+    "sr_pair_validation_error_rgba8_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_pair_backprop_f32": (_i, [_vp, _fp, _sz, _fp, _fp, _i, _i, _i, _i, C.c_float, C.c_float, _dp, C.POINTER(_sz), _fp]),
+    "sr_pair_backprop_rgba8": (_i, [_vp, _fp, _sz, _u8p, _i, _u8p, _i, _i, _i, _i, _i, C.c_float, C.c_float, _dp, C.POINTER(_sz), _fp]),
+    "sr_pair_backprop_rgba8_dev": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "sr_train_add_pair": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, C.POINTER(_i)]),
+    "sr_train_step_pairs": (_i, [_vp, C.POINTER(TrainPairCrop), _i, _i, _i]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

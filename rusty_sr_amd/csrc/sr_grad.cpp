@@ -18,21 +18,92 @@ int check_args(sr_ctx* c, const void* params, const void* hr, bool hr_u8, int ch
 
 size_t lr_floats(int f, int n, int h, int w) { return (size_t)n * (h / f) * (w / f) * 3; }
 
-// Pool, then the backward pass, on device buffers, queued on s.  The context's device is current; the workspace is grown here.
-int run_backprop(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8, int ch, int n, int h, int w, bool linear, float loss_scale,
-                 float l2, void* d_err, float* d_grad, hipStream_t s, double** result_slot) {
-    const int f = c->factor, OH = h / f, OW = w / f;
-    const size_t x_bytes = sr_round256(lr_floats(f, n, h, w) * sizeof(float));
+// A paired call's arguments: the LR batch is n x lh x lw, the HR batch f times that (include/srhip.h, "pairs")
+int check_pair_args(sr_ctx* c, const void* params, const void* lr, bool u8, int lr_ch, const void* hr, int hr_ch, int n, int lh, int lw,
+                    const void* grad) {
+    if (!c || !params || !lr || !hr || !grad) return SR_E_INVALID;
+    return sr_check_pair_args(c, u8, lr_ch, hr_ch, n, lh, lw);
+}
+
+// The host-pointer calls: upload parameters, HR batch and (pairs) LR batch, run, download err_sum and the gradient, on the context's own
+// stream; synchronous.  lr: nullptr = the pooled form, h x w the HR size; else h x w is the LR size and lr_ch its channel count.
+int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* lr, int lr_ch, const void* hr, bool hr_u8, int ch, int n, int h,
+                  int w, int linear, float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad, bool pair) {
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    int rc = pair ? check_pair_args(c, params, lr, hr_u8, lr_ch, hr, ch, n, h, w, grad) : check_args(c, params, hr, hr_u8, ch, n, h, w, grad);
+    if (rc != SR_OK) return rc;
+    if (!err_sum || !n_elems) return SR_E_INVALID;
+    const int np = sr_num_params_factor(c->factor);
+    if (np < 0 || n_params != (size_t)np) return SR_E_PARAM_COUNT;
+    const size_t lr_bytes = pair ? (size_t)n * h * w * (hr_u8 ? (size_t)lr_ch : 3 * sizeof(float)) : 0;
+    if (pair) { h *= c->factor; w *= c->factor; }
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = sr_ensure_streams(c, false);
+    if (rc != SR_OK) return rc;
+    const size_t p_bytes = sr_round256((size_t)np * sizeof(float));
+    const size_t hr_bytes = (size_t)n * h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
+    rc = sr_ensure_buf(c, &c->d_gin, &c->gin_cap, 2 * p_bytes + sr_round256(hr_bytes) + sr_round256(lr_bytes));
+    if (rc != SR_OK) {
+        sr_free_buf(c->d_gin, c->gin_cap);
+        sr_free_buf(c->d_gws, c->gws_cap);
+        return rc;
+    }
+    float* d_params = (float*)c->d_gin;
+    float* d_grad = (float*)((char*)c->d_gin + p_bytes);
+    void* d_hr = (char*)c->d_gin + 2 * p_bytes;
+    sr_lr_input in;
+    in.d_lr = (char*)d_hr + sr_round256(hr_bytes); in.u8 = hr_u8; in.ch = lr_ch;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(d_params, params, (size_t)np * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_hr, hr, hr_bytes, hipMemcpyHostToDevice, s));
+    if (pair) HIPCHK(c, hipMemcpyAsync((void*)in.d_lr, lr, lr_bytes, hipMemcpyHostToDevice, s));
+    double* slot = nullptr;
+    rc = sr_grad_queue(c, d_params, d_hr, hr_u8, ch, n, h, w, linear != 0, loss_scale, l2, nullptr, d_grad, s, &slot, pair ? &in : nullptr);
+    double sum = 0.0;
+    hipError_t e1 = hipSuccess;
+    if (rc == SR_OK) {
+        e1 = hipMemcpyAsync(&sum, slot, sizeof sum, hipMemcpyDeviceToHost, s);
+        if (e1 == hipSuccess) e1 = hipMemcpyAsync(grad, d_grad, (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, e1);
+    HIPCHK(c, e2);
+    *err_sum = sum;
+    *n_elems = sr_loss_elems(c->factor, n, h, w);
+    return SR_OK;
+}
+
+}  // namespace
+
+int sr_grad_input_buffer(sr_ctx* c, int n, int OH, int OW, float** x) {
+    const size_t x_bytes = sr_round256((size_t)n * OH * OW * 3 * sizeof(float));
     int rc = sr_valid_ensure_table(c);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_gws, &c->gws_cap, x_bytes + sr_grad_workspace_bytes(f, n, OH, OW));
+    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_gws, &c->gws_cap, x_bytes + sr_grad_workspace_bytes(c->factor, n, OH, OW));
     if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
         sr_free_buf(c->d_gws, c->gws_cap);
         sr_free_buf(c->d_gin, c->gin_cap);
         return rc;
     }
-    float* x = (float*)c->d_gws;
+    *x = (float*)c->d_gws;
+    return SR_OK;
+}
+
+// The input stage -- the pool, or a paired call's LR batch -- then the backward pass, on device buffers, queued on s.  The workspace is
+// grown here.
+int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8, int ch, int n, int h, int w, bool linear, float loss_scale,
+                  float l2, void* d_err, float* d_grad, hipStream_t s, double** result_slot, const sr_lr_input* lr) {
+    const int f = c->factor, OH = h / f, OW = w / f;
+    const size_t x_bytes = sr_round256(lr_floats(f, n, h, w) * sizeof(float));
+    float* x = nullptr;
+    const int rc = sr_grad_input_buffer(c, n, OH, OW, &x);
+    if (rc != SR_OK) return rc;
     const float* tab_lin = c->d_vtab + 256;
-    if (h % f == 0) {  // the batch is one image of n h rows
+    if (lr) {
+        HIPCHK(c, sr_queue_lr_input(*lr, (long)n * OH * OW, x, c->d_vtab, s));
+    } else if (h % f == 0) {  // the batch is one image of n h rows
         HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, n * OH, OW, x, tab_lin, s));
     } else {  // each image drops its own last h % f rows
         const size_t img_bytes = (size_t)h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
@@ -55,53 +126,6 @@ int run_backprop(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8,
     return SR_OK;
 }
 
-// The host-pointer calls: upload parameters and HR batch, run, download err_sum and the gradient, on the context's own stream; synchronous.
-int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* hr, bool hr_u8, int ch, int n, int h, int w, int linear,
-                  float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad) {
-    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
-    sr_plan_clear(c);
-    int rc = check_args(c, params, hr, hr_u8, ch, n, h, w, grad);
-    if (rc != SR_OK) return rc;
-    if (!err_sum || !n_elems) return SR_E_INVALID;
-    const int np = sr_num_params_factor(c->factor);
-    if (np < 0 || n_params != (size_t)np) return SR_E_PARAM_COUNT;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
-    const size_t p_bytes = sr_round256((size_t)np * sizeof(float));
-    const size_t hr_bytes = (size_t)n * h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
-    rc = sr_ensure_buf(c, &c->d_gin, &c->gin_cap, 2 * p_bytes + sr_round256(hr_bytes));
-    if (rc != SR_OK) {
-        sr_free_buf(c->d_gin, c->gin_cap);
-        sr_free_buf(c->d_gws, c->gws_cap);
-        return rc;
-    }
-    float* d_params = (float*)c->d_gin;
-    float* d_grad = (float*)((char*)c->d_gin + p_bytes);
-    void* d_hr = (char*)c->d_gin + 2 * p_bytes;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_params, params, (size_t)np * sizeof(float), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_hr, hr, hr_bytes, hipMemcpyHostToDevice, s));
-    double* slot = nullptr;
-    rc = run_backprop(c, d_params, d_hr, hr_u8, ch, n, h, w, linear != 0, loss_scale, l2, nullptr, d_grad, s, &slot);
-    double sum = 0.0;
-    hipError_t e1 = hipSuccess;
-    if (rc == SR_OK) {
-        e1 = hipMemcpyAsync(&sum, slot, sizeof sum, hipMemcpyDeviceToHost, s);
-        if (e1 == hipSuccess) e1 = hipMemcpyAsync(grad, d_grad, (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
-    if (rc != SR_OK) return rc;
-    HIPCHK(c, e1);
-    HIPCHK(c, e2);
-    *err_sum = sum;
-    *n_elems = sr_loss_elems(c->factor, n, h, w);
-    return SR_OK;
-}
-
-}  // namespace
-
 void sr_grad_release(sr_ctx* c) {
     sr_free_buf(c->d_gws, c->gws_cap);
     sr_free_buf(c->d_gin, c->gin_cap);
@@ -111,12 +135,13 @@ extern "C" {
 
 int sr_backprop_f32(sr_ctx* c, const float* params, size_t n_params, const float* hr, int n, int h, int w, int linear_loss, float loss_scale,
                     float l2, double* err_sum, size_t* n_elems, float* grad) {
-    return backprop_host(c, params, n_params, hr, false, 3, n, h, w, linear_loss, loss_scale, l2, err_sum, n_elems, grad);
+    return backprop_host(c, params, n_params, nullptr, 3, hr, false, 3, n, h, w, linear_loss, loss_scale, l2, err_sum, n_elems, grad, false);
 }
 
 int sr_backprop_rgba8(sr_ctx* c, const float* params, size_t n_params, const uint8_t* hr, int in_channels, int n, int h, int w, int linear_loss,
                       float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad) {
-    return backprop_host(c, params, n_params, hr, true, in_channels, n, h, w, linear_loss, loss_scale, l2, err_sum, n_elems, grad);
+    return backprop_host(c, params, n_params, nullptr, 3, hr, true, in_channels, n, h, w, linear_loss, loss_scale, l2, err_sum, n_elems, grad,
+                         false);
 }
 
 int sr_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_hr, int in_channels, int n, int h, int w, int linear_loss,
@@ -128,8 +153,36 @@ int sr_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_hr,
     if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
-    return run_backprop(c, d_params, d_hr, true, in_channels, n, h, w, linear_loss != 0, loss_scale, l2, d_err_sum, d_grad,
-                        (hipStream_t)stream, nullptr);
+    return sr_grad_queue(c, d_params, d_hr, true, in_channels, n, h, w, linear_loss != 0, loss_scale, l2, d_err_sum, d_grad,
+                         (hipStream_t)stream, nullptr, nullptr);
+}
+
+int sr_pair_backprop_f32(sr_ctx* c, const float* params, size_t n_params, const float* lr, const float* hr, int n, int lh, int lw,
+                         int linear_loss, float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad) {
+    return backprop_host(c, params, n_params, lr, 3, hr, false, 3, n, lh, lw, linear_loss, loss_scale, l2, err_sum, n_elems, grad, true);
+}
+
+int sr_pair_backprop_rgba8(sr_ctx* c, const float* params, size_t n_params, const uint8_t* lr, int lr_channels, const uint8_t* hr,
+                           int hr_channels, int n, int lh, int lw, int linear_loss, float loss_scale, float l2, double* err_sum,
+                           size_t* n_elems, float* grad) {
+    return backprop_host(c, params, n_params, lr, lr_channels, hr, true, hr_channels, n, lh, lw, linear_loss, loss_scale, l2, err_sum, n_elems,
+                         grad, true);
+}
+
+int sr_pair_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels,
+                               int n, int lh, int lw, int linear_loss, float loss_scale, float l2, double* d_err_sum, float* d_grad,
+                               void* stream) {
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    const int rc = check_pair_args(c, d_params, d_lr, true, lr_channels, d_hr, hr_channels, n, lh, lw, d_grad);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    sr_lr_input in;
+    in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
+    return sr_grad_queue(c, d_params, d_hr, true, hr_channels, n, c->factor * lh, c->factor * lw, linear_loss != 0, loss_scale, l2, d_err_sum,
+                         d_grad, (hipStream_t)stream, nullptr, &in);
 }
 
 int sr_adam_step_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr, float beta1,

@@ -173,6 +173,15 @@ inline int sr_check_hr_args(const sr_ctx* c, bool hr_u8, int ch, int n, int h, i
     return SR_OK;
 }
 
+// The arguments of a paired call (include/srhip.h, "pairs"): n LR images of lh x lw (u8 with lr_ch channels, or f32 RGB like the HR batch)
+// beside n HR images of exactly f lh x f lw.
+inline int sr_check_pair_args(const sr_ctx* c, bool u8, int lr_ch, int hr_ch, int n, int lh, int lw) {
+    if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    if (!sr_hr_channels_ok(u8, lr_ch) || !sr_hr_channels_ok(u8, hr_ch)) return SR_E_INVALID;
+    if (n < 1 || lh < 1 || lw < 1 || lh > INT32_MAX / c->factor || lw > INT32_MAX / c->factor) return SR_E_INVALID;
+    return SR_OK;
+}
+
 // Elements the loss is summed over: 3 channels of the top-left f floor(h / f) x f floor(w / f) crop of each image.
 inline size_t sr_loss_elems(int f, int n, int h, int w) { return (size_t)n * 3 * ((size_t)f * (h / f)) * ((size_t)f * (w / f)); }
 
@@ -253,6 +262,18 @@ int sr_valid_loss_grid(int HC, int WC);  // workgroups (= f64 partials) of the l
 // HR (W px per row, u8 with ch channels or f32 RGB) -> LR image OH x OW x 3 f32 = LinearToSrgb(mean_{f x f}(SrgbToLinear(hr)))
 hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch, int W, int OH, int OW, float* d_lr, const float* d_tab,
                                 hipStream_t s);
+// LR pixels (u8 with ch channels, any byte offset, npx of them, contiguous) -> npx x 3 f32, img_to_data: byte / 255 (d_tab's first 256 floats)
+hipError_t sr_launch_lr_input(const uint8_t* d_lr, int ch, long npx, float* d_x, const float* d_tab, hipStream_t s);
+// The LR batch a paired call supplies in place of the pool (include/srhip.h, "pairs"): device memory, u8 (ch 3 or 4) or f32 RGB -- or, with
+// in_place, already converted at the input buffer (sr_grad_input_buffer) by the caller.
+struct sr_lr_input {
+    const void* d_lr = nullptr;
+    bool u8 = true;
+    int ch = 3;
+    bool in_place = false;
+};
+// queue the conversion (u8) or the copy (f32) of npx LR pixels to d_x
+hipError_t sr_queue_lr_input(const sr_lr_input& lr, long npx, float* d_x, const float* d_tab, hipStream_t s);
 // sum over the HC x WC crop of (out - hr)^2 (linear: of SrgbToLinear of both) -> one double at d_result (4-byte aligned)
 hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,
                                 double* d_partial, void* d_result, hipStream_t s);
@@ -282,6 +303,12 @@ double* sr_grad_result_slot(const sr_grad_plan& p);  // the workspace's own slot
 hipError_t sr_launch_grad(const sr_grad_plan& p, hipStream_t s);
 hipError_t sr_launch_grad_adam(float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, float lr, float beta1, float beta2,
                                float eps, float bc1, float bc2, hipStream_t s);
+// The backward pass of a batch of n HR images of h x w on device buffers, queued on s (what sr_backprop_rgba8_dev does after its argument
+// checks); lr: nullptr = pool the HR batch, else the LR batch of a paired call (h, w = f x its size).  The context's device is current.
+int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8, int ch, int n, int h, int w, bool linear, float loss_scale,
+                  float l2, void* d_err, float* d_grad, hipStream_t s, double** result_slot, const sr_lr_input* lr);
+// Grow the backprop workspace for n LR images of OH x OW; *x: where the pass reads its input batch (n x OH x OW x 3 f32, whole 256 bytes)
+int sr_grad_input_buffer(sr_ctx* c, int n, int OH, int OW, float** x);
 int sr_valid_ensure_table(sr_ctx* c);  // sr_valid.cpp: the 512-float table behind d_vtab, uploaded on first use
 
 // ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)
@@ -294,6 +321,21 @@ struct sr_train_crop_args {  // passed by value: a step whose images are residen
     sr_train_crop_desc d[SR_TRAIN_MAX_BATCH];
     int n, crop_h, crop_w;
 };
+// One LR / HR pair of a paired step: the LR image is lh x lw, the HR image f lh x f lw; the crop origin in LR pixels.  (Compact: 64 of
+// them are one kernel's arguments.)
+struct sr_train_pair_desc {
+    const uint8_t* lr;
+    const uint8_t* hr;
+    int lr_ch, hr_ch, lh, lw, y0, x0;
+};
+struct sr_train_pair_args {
+    sr_train_pair_desc d[SR_TRAIN_MAX_BATCH];
+    int n, crop_lh, crop_lw;
+    int hr_blocks;  // set by the launcher: blocks of a grid row that cut the HR crop
+};
 void sr_train_detach_all(sr_ctx* c);  // sr_train.cpp: called by sr_destroy; a detached session refuses every call but sr_train_destroy
 // the n crops -> n x crop_h x crop_w x 3 u8 at d_out, whose allocation holds whole dwords (ceil(n crop_h crop_w 3 / 4) of them)
 hipError_t sr_launch_train_crop(const sr_train_crop_args& a, uint32_t* d_out, hipStream_t s);
+// the n HR crops (f crop_lh x f crop_lw) -> u8 at d_out as above, and the n LR crops -> n x crop_lh x crop_lw x 3 f32 (byte / 255, d_tab)
+// at d_x, which is 16-byte aligned and holds whole 16-byte groups
+hipError_t sr_launch_train_pair_crop(int factor, sr_train_pair_args a, uint32_t* d_out, float* d_x, const float* d_tab, hipStream_t s);

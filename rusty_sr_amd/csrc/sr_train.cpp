@@ -43,7 +43,8 @@ struct sr_train {
     long long queued = 0, harvested = 0;  // steps issued (= Adam's step count) / whose err_sum has been read
     std::vector<double> done;              // err_sums read since the last sync
     // the image store: one allocation per resident image, within the budget
-    struct Img { uint8_t* d; int ch, h, w; };
+    // (a pair is one entry: d_lr its LR image of h / f x w / f in the same allocation, nullptr for a plain image)
+    struct Img { uint8_t* d; int ch, h, w; uint8_t* d_lr; int lr_ch; };
     std::vector<Img> images;
     size_t store_budget = 0, store_used = 0;
     // per-step buffers, reused in stream order
@@ -81,6 +82,66 @@ int drain(sr_train* t) {
         const int rc = harvest_one(t);
         if (rc != SR_OK) return rc;
     }
+    return SR_OK;
+}
+
+// What every step does before it queues anything: room in the ring, and a drained stream where the backprop workspace may grow.
+int begin_step(sr_train* t, int n, int crop_h, int crop_w) {
+    sr_ctx* c = t->c;
+    if (t->queued - t->harvested >= SR_TRAIN_RING) {  // the ring is full: wait for the oldest step
+        const int rc = harvest_one(t);
+        if (rc != SR_OK) return rc;
+    }
+    if (n != t->last_n || crop_h != t->last_h || crop_w != t->last_w) {  // the backprop workspace may grow: nothing in flight may use it
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        t->last_n = t->last_h = t->last_w = 0;
+    }
+    return SR_OK;
+}
+
+// The staging slot a step's transient rows go through, trans_bytes of them: free once the copy that read it last has completed.
+int acquire_stage(sr_train* t, size_t trans_bytes, int* slot) {
+    sr_ctx* c = t->c;
+    const int k = t->stage_next;
+    *slot = k;
+    if (!trans_bytes) return SR_OK;
+    if (t->stage_pending[k]) HIPCHK(c, hipEventSynchronize(t->stage_ev[k]));
+    t->stage_pending[k] = false;
+    if (t->stage_cap[k] < trans_bytes) {
+        if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
+        t->h_stage[k] = nullptr;
+        t->stage_cap[k] = 0;
+        HIPCHK(c, hipHostMalloc(&t->h_stage[k], sr_round256(trans_bytes), hipHostMallocPortable));
+        t->stage_cap[k] = sr_round256(trans_bytes);
+    }
+    return SR_OK;
+}
+
+int upload_stage(sr_train* t, size_t trans_bytes, int k) {
+    sr_ctx* c = t->c;
+    if (!trans_bytes) return SR_OK;
+    HIPCHK(c, hipMemcpyAsync(t->d_trans, t->h_stage[k], trans_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(t->stage_ev[k], c->stream));
+    t->stage_pending[k] = true;
+    t->stage_next = (k + 1) % kStage;
+    return SR_OK;
+}
+
+// Backprop on the gathered u8 batch (crop_h x crop_w each; lr: the input the gather has already written, or nullptr: pool), Adam, the ring.
+int finish_step(sr_train* t, int n, int crop_h, int crop_w, const sr_lr_input* lr) {
+    sr_ctx* c = t->c;
+    hipStream_t s = c->stream;
+    const size_t n_elems = sr_loss_elems(c->factor, n, crop_h, crop_w);
+    const int slot = (int)(t->queued % SR_TRAIN_RING);
+    sr_plan_clear(c);
+    int rc = sr_grad_queue(c, t->d_p, t->d_batch, true, 3, n, crop_h, crop_w, t->linear, (float)(1.0 / (double)n_elems), t->l2, t->d_err + slot,
+                           t->d_g, s, nullptr, lr);
+    if (rc != SR_OK) return rc;  // (SR_E_NOMEM: the context freed its backprop buffers; the parameters are untouched)
+    t->last_n = n; t->last_h = crop_h; t->last_w = crop_w;
+    rc = sr_adam_step_dev(c, t->d_p, t->d_m, t->d_v, t->d_g, (size_t)t->np, (int)(t->queued + 1), t->lr, t->beta1, t->beta2, t->eps, s);
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, hipEventRecord(t->ring_ev[slot], s));
+    ++t->queued;
     return SR_OK;
 }
 
@@ -204,7 +265,7 @@ int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, i
         HIPCHK(c, e);
     }
     t->store_used += alloc;
-    t->images.push_back({d, in_channels, h, w});
+    t->images.push_back({d, in_channels, h, w, nullptr, 0});
     *id = (int)t->images.size() - 1;
     return SR_OK;
 }
@@ -219,7 +280,7 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
     for (int i = 0; i < n; ++i) {
         const sr_train_crop& it = items[i];
         if (it.image >= 0) {
-            if ((size_t)it.image >= t->images.size()) return SR_E_INVALID;
+            if ((size_t)it.image >= t->images.size() || t->images[(size_t)it.image].d_lr) return SR_E_INVALID;  // (a pair is no plain image)
         } else if (it.image == -1) {
             if (!it.px || (it.in_channels != 3 && it.in_channels != 4) || it.h < 1 || it.w < 1) return SR_E_INVALID;
             const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + crop_h, 0, it.h);
@@ -231,32 +292,17 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (t->queued - t->harvested >= SR_TRAIN_RING) {  // the ring is full: wait for the oldest step
-        const int rc = harvest_one(t);
-        if (rc != SR_OK) return rc;
-    }
-    if (n != t->last_n || crop_h != t->last_h || crop_w != t->last_w) {  // the backprop workspace may grow: nothing in flight may use it
-        HIPCHK(c, hipStreamSynchronize(s));
-        t->last_n = t->last_h = t->last_w = 0;
-    }
+    int rc = begin_step(t, n, crop_h, crop_w);
+    if (rc != SR_OK) return rc;
     const size_t batch_bytes = (size_t)n * crop_h * crop_w * 3;
-    int rc = grow(c, s, &t->d_batch, &t->batch_cap, batch_bytes + 4);
+    rc = grow(c, s, &t->d_batch, &t->batch_cap, batch_bytes + 4);
     if (rc == SR_OK && trans_bytes) rc = grow(c, s, &t->d_trans, &t->trans_cap, trans_bytes);
     if (rc != SR_OK) return rc;
     sr_train_crop_args a;
     a.n = n; a.crop_h = crop_h; a.crop_w = crop_w;
-    const int k = t->stage_next;
-    if (trans_bytes) {
-        if (t->stage_pending[k]) HIPCHK(c, hipEventSynchronize(t->stage_ev[k]));  // the copy that read this slot last has completed
-        t->stage_pending[k] = false;
-        if (t->stage_cap[k] < trans_bytes) {
-            if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
-            t->h_stage[k] = nullptr;
-            t->stage_cap[k] = 0;
-            HIPCHK(c, hipHostMalloc(&t->h_stage[k], sr_round256(trans_bytes), hipHostMallocPortable));
-            t->stage_cap[k] = sr_round256(trans_bytes);
-        }
-    }
+    int k = 0;
+    rc = acquire_stage(t, trans_bytes, &k);
+    if (rc != SR_OK) return rc;
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         const sr_train_crop& it = items[i];
@@ -268,12 +314,8 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
         a.d[i] = {(const uint8_t*)t->d_trans + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0};
         off += sr_round256(bytes);
     }
-    if (trans_bytes) {
-        HIPCHK(c, hipMemcpyAsync(t->d_trans, t->h_stage[k], trans_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipEventRecord(t->stage_ev[k], s));
-        t->stage_pending[k] = true;
-        t->stage_next = (k + 1) % kStage;
-    }
+    rc = upload_stage(t, trans_bytes, k);
+    if (rc != SR_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const sr_train_crop& it = items[i];
         if (it.image < 0) continue;
@@ -281,17 +323,104 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
         a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0};
     }
     HIPCHK(c, sr_launch_train_crop(a, (uint32_t*)t->d_batch, s));
-    const size_t n_elems = sr_loss_elems(c->factor, n, crop_h, crop_w);
-    const int slot = (int)(t->queued % SR_TRAIN_RING);
-    rc = sr_backprop_rgba8_dev(c, t->d_p, (const uint8_t*)t->d_batch, 3, n, crop_h, crop_w, t->linear ? 1 : 0, (float)(1.0 / (double)n_elems),
-                               t->l2, t->d_err + slot, t->d_g, s);
-    if (rc != SR_OK) return rc;  // (SR_E_NOMEM: the context freed its backprop buffers; the parameters are untouched)
-    t->last_n = n; t->last_h = crop_h; t->last_w = crop_w;
-    rc = sr_adam_step_dev(c, t->d_p, t->d_m, t->d_v, t->d_g, (size_t)t->np, (int)(t->queued + 1), t->lr, t->beta1, t->beta2, t->eps, s);
+    return finish_step(t, n, crop_h, crop_w, nullptr);
+}
+
+int sr_train_add_pair(sr_train* t, const uint8_t* lr_px, int lr_channels, const uint8_t* hr_px, int hr_channels, int lh, int lw, int* id) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !lr_px || !hr_px || !id) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    const int rc = sr_check_pair_args(c, true, lr_channels, hr_channels, 1, lh, lw);
     if (rc != SR_OK) return rc;
-    HIPCHK(c, hipEventRecord(t->ring_ev[slot], s));
-    ++t->queued;
+    *id = -1;
+    const int f = c->factor;
+    const size_t hr_bytes = (size_t)f * lh * f * lw * hr_channels, lr_bytes = (size_t)lh * lw * lr_channels;
+    const size_t alloc = sr_round256(hr_bytes) + sr_round256(lr_bytes);  // one entry, both images
+    if (alloc > t->store_budget - std::min(t->store_budget, t->store_used) || t->images.size() >= (size_t)INT32_MAX) return SR_OK;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t* d = nullptr;
+    if (hipMalloc((void**)&d, alloc) != hipSuccess) {  // the device is fuller than the budget said: no room, not an error
+        (void)hipGetLastError();
+        return SR_OK;
+    }
+    uint8_t* d_lr = d + sr_round256(hr_bytes);
+    hipError_t e = hipMemcpy(d, hr_px, hr_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_lr, lr_px, lr_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        HIPCHK(c, e);
+    }
+    t->store_used += alloc;
+    t->images.push_back({d, hr_channels, f * lh, f * lw, d_lr, lr_channels});
+    *id = (int)t->images.size() - 1;
     return SR_OK;
+}
+
+int sr_train_step_pairs(sr_train* t, const sr_train_pair_crop* items, int n, int crop_lh, int crop_lw) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !items || n < 1 || n > SR_TRAIN_MAX_BATCH) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    const int f = c->factor;
+    if (crop_lh < 1 || crop_lw < 1 || crop_lh > INT32_MAX / f || crop_lw > INT32_MAX / f) return SR_E_INVALID;
+    // every item is checked before anything is launched; of a transient pair, the rows its crops can reach are what is staged
+    size_t trans_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const sr_train_pair_crop& it = items[i];
+        if (it.pair >= 0) {
+            if ((size_t)it.pair >= t->images.size() || !t->images[(size_t)it.pair].d_lr) return SR_E_INVALID;  // (a plain image is no pair)
+        } else if (it.pair == -1) {
+            if (!it.lr_px || !it.hr_px || sr_check_pair_args(c, true, it.lr_channels, it.hr_channels, 1, it.lh, it.lw) != SR_OK)
+                return SR_E_INVALID;
+            const long r0 = std::clamp<long>(it.y0, 0, it.lh), r1 = std::clamp<long>((long)it.y0 + crop_lh, 0, it.lh);
+            trans_bytes += sr_round256((size_t)(r1 - r0) * it.lw * it.lr_channels) +
+                           sr_round256((size_t)(r1 - r0) * f * it.lw * f * it.hr_channels);
+        } else {
+            return SR_E_INVALID;
+        }
+    }
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const int crop_h = f * crop_lh, crop_w = f * crop_lw;
+    int rc = begin_step(t, n, crop_h, crop_w);
+    if (rc != SR_OK) return rc;
+    const size_t batch_bytes = (size_t)n * crop_h * crop_w * 3;
+    rc = grow(c, s, &t->d_batch, &t->batch_cap, batch_bytes + 4);
+    if (rc == SR_OK && trans_bytes) rc = grow(c, s, &t->d_trans, &t->trans_cap, trans_bytes);
+    float* x = nullptr;
+    if (rc == SR_OK) rc = sr_grad_input_buffer(c, n, crop_lh, crop_lw, &x);  // (the stream has drained if this grows the workspace)
+    if (rc != SR_OK) return rc;
+    sr_train_pair_args a;
+    a.n = n; a.crop_lh = crop_lh; a.crop_lw = crop_lw; a.hr_blocks = 0;
+    int k = 0;
+    rc = acquire_stage(t, trans_bytes, &k);
+    if (rc != SR_OK) return rc;
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const sr_train_pair_crop& it = items[i];
+        if (it.pair >= 0) {
+            const sr_train::Img& im = t->images[(size_t)it.pair];
+            a.d[i] = {im.d_lr, im.d, im.lr_ch, im.ch, im.h / f, im.w / f, it.y0, it.x0};
+            continue;
+        }
+        // the staged rows as a pair of r1 - r0 LR rows: the crops' rows outside them are outside the source images too
+        const long r0 = std::clamp<long>(it.y0, 0, it.lh), r1 = std::clamp<long>((long)it.y0 + crop_lh, 0, it.lh);
+        const size_t lrow = (size_t)it.lw * it.lr_channels, lbytes = (size_t)(r1 - r0) * lrow;
+        const size_t hrow = (size_t)f * it.lw * it.hr_channels, hbytes = (size_t)(r1 - r0) * f * hrow;
+        if (lbytes) memcpy((char*)t->h_stage[k] + off, it.lr_px + (size_t)r0 * lrow, lbytes);
+        const uint8_t* d_lr = (const uint8_t*)t->d_trans + off;
+        off += sr_round256(lbytes);
+        if (hbytes) memcpy((char*)t->h_stage[k] + off, it.hr_px + (size_t)r0 * f * hrow, hbytes);
+        a.d[i] = {d_lr, (const uint8_t*)t->d_trans + off, it.lr_channels, it.hr_channels, (int)(r1 - r0), it.lw, (int)(it.y0 - r0), it.x0};
+        off += sr_round256(hbytes);
+    }
+    rc = upload_stage(t, trans_bytes, k);
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, sr_launch_train_pair_crop(f, a, (uint32_t*)t->d_batch, x, c->d_vtab, s));
+    sr_lr_input in;
+    in.in_place = true;
+    return finish_step(t, n, crop_h, crop_w, &in);
 }
 
 int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps) {

@@ -9,6 +9,10 @@
 // from the aligned word that holds it: nothing outside the words of the image is read).  The descriptors arrive by value (kernel
 // arguments), so a step whose images are all resident uploads nothing.  Blocks along y are items, so each block reads its descriptor with
 // scalar loads.
+//
+// A step on LR / HR pairs (sr_train_step_pairs) gathers both crops in one launch, train_pair_crop_kernel: the HR crops as above, and the LR
+// crops -- cut by the same code, a crop of crop_lh x crop_lw at (y0, x0) of the LR image -- converted on the way (byte / 255, the
+// validation pass's table) and stored as 16-byte groups straight into the backward pass's input buffer.  Such a step has no pool launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,14 +34,16 @@ __device__ __forceinline__ uint32_t crop_byte(const sr_train_crop_desc& d, long 
     return word_at(d.px + (sy * d.w + sx) * d.ch + c) & 0xffu;
 }
 
-__global__ __launch_bounds__(256) void train_crop_kernel(sr_train_crop_args a, uint32_t* __restrict__ out) {
-    const int b = blockIdx.y;
-    const long rowb = (long)a.crop_w * 3, cb = (long)a.crop_h * rowb;
+// The dword (four bytes of the n x crop_h x crop_w x 3 RGB batch) number blockIdx-relative `t` of those whose first byte lies in crop b;
+// desc(i): the descriptor of crop i.  *k: its index in the batch.  false: no such dword.
+template <class Desc>
+__device__ __forceinline__ bool crop_dword(Desc&& desc, int n, int b, long t, int crop_h, int crop_w, long* k_out, uint32_t* word_out) {
+    const long rowb = (long)crop_w * 3, cb = (long)crop_h * rowb;
     const long base = (long)b * cb;
-    const long k = (base + 3) / 4 + (long)blockIdx.x * 256 + threadIdx.x;  // the dwords whose first byte lies in crop b
-    if (4 * k >= base + cb) return;
+    const long k = (base + 3) / 4 + t;  // the dwords whose first byte lies in crop b
+    if (4 * k >= base + cb) return false;
     const long o = 4 * k - base;
-    const sr_train_crop_desc& d = a.d[b];
+    const sr_train_crop_desc d = desc(b);
     const long y = o / rowb, xb = o - y * rowb;
     const long sy = (long)d.y0 + y, x = xb / 3, sx = (long)d.x0 + x;
     const int c = (int)(xb - x * 3);
@@ -65,12 +71,56 @@ __global__ __launch_bounds__(256) void train_crop_kernel(sr_train_crop_args a, u
             if (ob >= cb) {  // the dword runs on into the next crop (cb not a multiple of 4), or into the batch's padding
                 ob -= cb;
                 bi = b + 1;
-                if (bi >= a.n) break;
+                if (bi >= n) break;
             }
-            word |= crop_byte(a.d[bi], ob, rowb) << (8 * j);
+            word |= crop_byte(desc(bi), ob, rowb) << (8 * j);
         }
     }
-    out[k] = word;
+    *k_out = k;
+    *word_out = word;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void train_crop_kernel(sr_train_crop_args a, uint32_t* __restrict__ out) {
+    long k;
+    uint32_t word;
+    if (crop_dword([&](int i) { return a.d[i]; }, a.n, blockIdx.y, (long)blockIdx.x * 256 + threadIdx.x, a.crop_h, a.crop_w, &k, &word))
+        out[k] = word;
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// A paired step's gather: blocks [0, hr_blocks) of a row cut item blockIdx.y's HR crop into the u8 batch as train_crop_kernel does; the
+// others cut its LR crop the same way -- one thread per four consecutive values of the n x crop_lh x crop_lw x 3 batch -- and store it
+// as img_to_data makes it (tab: 256 floats byte / 255), four floats at a time, at x: the network's input.  x holds whole 16-byte
+// groups (its buffer is a multiple of 256 bytes).
+template <int F>
+__global__ __launch_bounds__(256) void train_pair_crop_kernel(sr_train_pair_args a, uint32_t* __restrict__ out, f32x4* __restrict__ x,
+                                                              const float* __restrict__ tab) {
+    long k;
+    uint32_t word;
+    if ((int)blockIdx.x < a.hr_blocks) {
+        auto hr = [&](int i) {
+            const sr_train_pair_desc& p = a.d[i];
+            return sr_train_crop_desc{p.hr, p.hr_ch, F * p.lh, F * p.lw, F * p.y0, F * p.x0};
+        };
+        if (crop_dword(hr, a.n, blockIdx.y, (long)blockIdx.x * 256 + threadIdx.x, F * a.crop_lh, F * a.crop_lw, &k, &word)) out[k] = word;
+        return;
+    }
+    __shared__ float s_tab[256];
+    s_tab[threadIdx.x] = tab[threadIdx.x];
+    __syncthreads();
+    auto lr = [&](int i) {
+        const sr_train_pair_desc& p = a.d[i];
+        return sr_train_crop_desc{p.lr, p.lr_ch, p.lh, p.lw, p.y0, p.x0};
+    };
+    if (!crop_dword(lr, a.n, blockIdx.y, (long)(blockIdx.x - a.hr_blocks) * 256 + threadIdx.x, a.crop_lh, a.crop_lw, &k, &word)) return;
+    f32x4 v;
+    v.x = s_tab[word & 0xffu];
+    v.y = s_tab[(word >> 8) & 0xffu];
+    v.z = s_tab[(word >> 16) & 0xffu];
+    v.w = s_tab[word >> 24];
+    x[k] = v;
 }
 
 }  // namespace
@@ -81,5 +131,19 @@ hipError_t sr_launch_train_crop(const sr_train_crop_args& a, uint32_t* d_out, hi
     const long dwords = cb / 4 + 1;  // most dwords whose first byte lies in one crop
     const dim3 grid((unsigned)((dwords + 255) / 256), (unsigned)a.n);
     hipLaunchKernelGGL(train_crop_kernel, grid, dim3(256), 0, s, a, d_out);
+    return hipGetLastError();
+}
+
+hipError_t sr_launch_train_pair_crop(int factor, sr_train_pair_args a, uint32_t* d_out, float* d_x, const float* d_tab, hipStream_t s) {
+    if (a.n < 1 || a.n > SR_TRAIN_MAX_BATCH || a.crop_lh < 1 || a.crop_lw < 1) return hipErrorInvalidValue;
+    const long lr_vals = (long)a.crop_lh * a.crop_lw * 3, hr_bytes = lr_vals * factor * factor;
+    a.hr_blocks = (int)((hr_bytes / 4 + 1 + 255) / 256);  // most dwords whose first byte lies in one crop
+    const dim3 grid((unsigned)(a.hr_blocks + (lr_vals / 4 + 1 + 255) / 256), (unsigned)a.n);
+    switch (factor) {
+        case 2: hipLaunchKernelGGL(train_pair_crop_kernel<2>, grid, dim3(256), 0, s, a, d_out, (f32x4*)d_x, d_tab); break;
+        case 3: hipLaunchKernelGGL(train_pair_crop_kernel<3>, grid, dim3(256), 0, s, a, d_out, (f32x4*)d_x, d_tab); break;
+        case 4: hipLaunchKernelGGL(train_pair_crop_kernel<4>, grid, dim3(256), 0, s, a, d_out, (f32x4*)d_x, d_tab); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }

@@ -37,9 +37,15 @@ int check_args(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w) {
     return sr_check_hr_args(c, hr_u8, ch, 1, h, w);
 }
 
-// Pool, network, loss on device buffers, queued on s; the sum lands at d_result (nullptr: the slot behind the partials, for the
-// host-pointer calls).  The context's device is current.
-int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w, bool linear, void* d_result, hipStream_t s) {
+int check_pair_args(sr_ctx* c, const void* lr, bool u8, int lr_ch, const void* hr, int hr_ch, int lh, int lw) {
+    if (!c || !lr || !hr) return SR_E_INVALID;
+    return sr_check_pair_args(c, u8, lr_ch, hr_ch, 1, lh, lw);
+}
+
+// Pool (or, with lr, a paired call's LR image in its place), network, loss on device buffers, queued on s; the sum lands at d_result
+// (nullptr: the slot behind the partials, for the host-pointer calls).  The context's device is current.
+int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w, bool linear, void* d_result, hipStream_t s,
+                   const sr_lr_input* lr) {
     const int f = c->factor, OH = h / f, OW = w / f, HC = f * OH, WC = f * OW;
     const int grid = sr_valid_loss_grid(HC, WC);
     const size_t lr_bytes = (size_t)OH * OW * 3 * sizeof(float), out_bytes = (size_t)HC * WC * 3 * sizeof(float);
@@ -54,7 +60,8 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
         return rc;
     }
     if (!d_result) d_result = (double*)c->d_vpart + grid;
-    HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, OH, OW, (float*)c->d_vlr, c->d_vtab + 256, s));  // (SrgbToLinear of the bytes)
+    if (lr) HIPCHK(c, sr_queue_lr_input(*lr, (long)OH * OW, (float*)c->d_vlr, c->d_vtab, s));
+    else HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, OH, OW, (float*)c->d_vlr, c->d_vtab + 256, s));  // (SrgbToLinear of the bytes)
     rc = sr_run_stack_auto(c, c->d_vlr, false, 3, 1, OH, OW, 0, 0, c->d_vout, false, s);
     if (rc != SR_OK) return rc;
     HIPCHK(c, sr_launch_valid_loss((const float*)c->d_vout, d_hr, hr_u8, ch, linear, w, HC, WC, c->d_vtab, (double*)c->d_vpart, d_result, s));
@@ -64,11 +71,16 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
 
 // The host-pointer calls: upload, run, download 8 bytes, on the context's own stream; synchronous.  In the split-half mode a value that
 // left its domain makes the whole call run again in exact f32, as the host-pointer upscale calls do (include/srhip.h sr_set_precision).
-int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w, int linear, double* err_sum, size_t* n_elems) {
+// lr: nullptr = the pooled form, h x w the HR size; else (pair) h x w is the LR size and lr_ch its channel count.
+int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool hr_u8, int ch, int h, int w, int linear, double* err_sum,
+                    size_t* n_elems, bool pair) {
     sr_plan_clear(c);
-    int rc = check_args(c, hr, hr_u8, ch, h, w);
+    int rc = pair ? check_pair_args(c, lr, hr_u8, lr_ch, hr, ch, h, w) : check_args(c, hr, hr_u8, ch, h, w);
     if (rc != SR_OK) return rc;
     if (!err_sum || !n_elems) return SR_E_INVALID;
+    const int lh = h, lw = w;
+    const size_t lr_bytes = pair ? (size_t)h * w * (hr_u8 ? (size_t)lr_ch : 3 * sizeof(float)) : 0;
+    if (pair) { h *= c->factor; w *= c->factor; }
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     rc = sr_ensure_streams(c, false);
@@ -76,7 +88,7 @@ int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w,
     // a fault an earlier unchecked *_dev call left is that call's to report (sr_check_domain), not a reason to recompute this one
     if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
     const size_t hr_bytes = (size_t)h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
-    rc = sr_ensure_buf(c, &c->d_vhr, &c->vhr_cap, hr_bytes);
+    rc = sr_ensure_buf(c, &c->d_vhr, &c->vhr_cap, pair ? sr_round256(hr_bytes) + lr_bytes : hr_bytes);
     if (rc != SR_OK) {
         sr_free_buf(c->d_vhr, c->vhr_cap);
         return rc;
@@ -87,7 +99,10 @@ int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w,
     bool profiled = false;
     if (c->profiling) profiled = hipEventRecord(c->ev[6], s) == hipSuccess;
     HIPCHK(c, hipMemcpyAsync(c->d_vhr, hr, hr_bytes, hipMemcpyHostToDevice, s));
-    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s);
+    sr_lr_input in;
+    in.d_lr = (char*)c->d_vhr + sr_round256(hr_bytes); in.u8 = hr_u8; in.ch = lr_ch;
+    if (pair) HIPCHK(c, hipMemcpyAsync((void*)in.d_lr, lr, lr_bytes, hipMemcpyHostToDevice, s));
+    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr);
     double sum = 0.0;
     const hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(&sum, (double*)c->d_vpart + grid, sizeof sum, hipMemcpyDeviceToHost, s) : hipSuccess;
     if (profiled && e1 == hipSuccess && rc == SR_OK) profiled = hipEventRecord(c->ev[7], s) == hipSuccess;
@@ -98,7 +113,7 @@ int validation_host(sr_ctx* c, const void* hr, bool hr_u8, int ch, int h, int w,
     if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
         *(volatile int*)c->h_domain = 0;
         (void)sr_set_precision(c, SR_PRECISION_F32);
-        rc = validation_host(c, hr, hr_u8, ch, h, w, linear, err_sum, n_elems);
+        rc = validation_host(c, lr, lr_ch, hr, hr_u8, ch, pair ? lh : h, pair ? lw : w, linear, err_sum, n_elems, pair);
         (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
         ++c->domain_fallbacks;
         return rc;
@@ -131,11 +146,11 @@ void sr_valid_release(sr_ctx* c) {
 extern "C" {
 
 int sr_validation_error_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, double* err_sum, size_t* n_elems) {
-    return validation_host(c, hr, true, in_channels, h, w, linear_loss, err_sum, n_elems);
+    return validation_host(c, nullptr, 3, hr, true, in_channels, h, w, linear_loss, err_sum, n_elems, false);
 }
 
 int sr_validation_error_f32(sr_ctx* c, const float* hr, int h, int w, int linear_loss, double* err_sum, size_t* n_elems) {
-    return validation_host(c, hr, false, 3, h, w, linear_loss, err_sum, n_elems);
+    return validation_host(c, nullptr, 3, hr, false, 3, h, w, linear_loss, err_sum, n_elems, false);
 }
 
 int sr_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss, double* d_err_sum, void* stream) {
@@ -145,7 +160,29 @@ int sr_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channel
     if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
-    return run_validation(c, d_hr, true, in_channels, h, w, linear_loss != 0, d_err_sum, (hipStream_t)stream);
+    return run_validation(c, d_hr, true, in_channels, h, w, linear_loss != 0, d_err_sum, (hipStream_t)stream, nullptr);
+}
+
+int sr_pair_validation_error_rgba8(sr_ctx* c, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
+                                   int linear_loss, double* err_sum, size_t* n_elems) {
+    return validation_host(c, lr, lr_channels, hr, true, hr_channels, lh, lw, linear_loss, err_sum, n_elems, true);
+}
+
+int sr_pair_validation_error_f32(sr_ctx* c, const float* lr, const float* hr, int lh, int lw, int linear_loss, double* err_sum, size_t* n_elems) {
+    return validation_host(c, lr, 3, hr, false, 3, lh, lw, linear_loss, err_sum, n_elems, true);
+}
+
+int sr_pair_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
+                                       int linear_loss, double* d_err_sum, void* stream) {
+    sr_plan_clear(c);
+    const int rc = check_pair_args(c, d_lr, true, lr_channels, d_hr, hr_channels, lh, lw);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    sr_lr_input in;
+    in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
+    return run_validation(c, d_hr, true, hr_channels, c->factor * lh, c->factor * lw, linear_loss != 0, d_err_sum, (hipStream_t)stream, &in);
 }
 
 int sr_read_validation_nodes(sr_ctx* c, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out) {

@@ -2,6 +2,7 @@
 // network.rs:88-102), on gfx950:
 //
 //   input  = LinearToSrgb(mean_{f x f}(SrgbToLinear(hr)))       valid_pool_kernel    (the network's LR input, f32, not quantised)
+//         or img_to_data(lr) of a supplied LR image (pairs)       lr_input_kernel      (u8; an f32 LR image is copied)
 //   output = sr_net(f)(input)                                     the stage kernels (sr_kernels.hip), f32 output
 //   err    = sum (output - hr)^2                                  valid_loss_kernel + loss_sum_kernel
 //         or sum (SrgbToLinear(output) - SrgbToLinear(hr))^2     (-l / --linearLoss)
@@ -105,6 +106,53 @@ __global__ __launch_bounds__(256) void valid_pool_kernel(const void* __restrict_
     ((F3*)lr)[idx] = o;
 }
 
+// A supplied LR batch (pairs): npx pixels of CH bytes, contiguous from any byte address -> npx x 3 f32, img_to_data (tab: byte / 255).
+// One thread per four consecutive output floats, which cross pixel boundaries: of an RGB source they are four consecutive bytes (the two
+// aligned dwords that hold them, shifted into place with v_alignbyte), of an RGBA source RGB bytes c .. c + 3 of two pixels (three aligned
+// dwords at most); every store is a whole 16-byte group, consecutive across the wave.  The last, partial group goes float by float,
+// each byte from the aligned dword that holds it: nothing outside the words of the image is read, nothing outside x written.
+template <int CH>
+__global__ __launch_bounds__(256) void lr_input_kernel(const uint8_t* __restrict__ lr, float* __restrict__ x, const float* __restrict__ tab, long nval) {
+    __shared__ float s_tab[256];
+    s_tab[threadIdx.x] = tab[threadIdx.x];
+    __syncthreads();
+    const long v0 = 4 * ((long)blockIdx.x * 256 + threadIdx.x);  // the first of this thread's values (value v: pixel v / 3, channel v % 3)
+    if (v0 >= nval) return;
+    if (v0 + 4 <= nval) {
+        uint32_t word;
+        if constexpr (CH == 3) {
+            const uint8_t* p = lr + v0;
+            const uint32_t mis = (uint32_t)(uintptr_t)p & 3u;
+            const uint32_t* q = (const uint32_t*)(p - mis);
+            const uint32_t w0 = q[0], w1 = mis ? q[1] : 0u;  // (with mis > 0, q[1] holds byte 3 of the run: inside the image)
+            word = __builtin_amdgcn_alignbyte(w1, w0, mis);
+        } else {
+            const long px = v0 / 3;
+            const int c = (int)(v0 - 3 * px);
+            const uint8_t* p = lr + 4 * px;  // pixels px, px + 1 (the second exists: value v0 + 3 is in it)
+            const uint32_t mis = (uint32_t)(uintptr_t)p & 3u;
+            const uint32_t* q = (const uint32_t*)(p - mis);
+            const uint32_t w0 = q[0], w1 = q[1], w2 = mis ? q[2] : 0u;  // (with mis > 0, q[2] holds pixel px + 1's last byte)
+            const uint32_t p0 = __builtin_amdgcn_alignbyte(w1, w0, mis), p1 = __builtin_amdgcn_alignbyte(w2, w1, mis);
+            const uint64_t rgb = (uint64_t)(p0 & 0xffffffu) | ((uint64_t)(p1 & 0xffffffu) << 24);
+            word = (uint32_t)(rgb >> (8 * c));
+        }
+        f32x4 v;
+        v.x = s_tab[word & 0xffu];
+        v.y = s_tab[(word >> 8) & 0xffu];
+        v.z = s_tab[(word >> 16) & 0xffu];
+        v.w = s_tab[word >> 24];
+        *(f32x4*)(x + v0) = v;
+    } else {
+        for (long v = v0; v < nval; ++v) {
+            const long px = v / 3;
+            const uint8_t* p = lr + CH * px + (v - 3 * px);
+            const uint32_t mis = (uint32_t)(uintptr_t)p & 3u;
+            x[v] = s_tab[(*(const uint32_t*)(p - mis) >> (8 * mis)) & 0xffu];
+        }
+    }
+}
+
 constexpr int kLossMaxGrid = 2048;   // workgroups of valid_loss_kernel at most (the number of f64 partials)
 
 // out: the network's f32 output, HC x WC x 3, contiguous and 16-byte aligned (a context buffer); hr: the HR image, row pitch W pixels;
@@ -206,6 +254,21 @@ hipError_t sr_launch_valid_pool(int factor, const void* d_hr, bool hr_u8, int ch
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+
+hipError_t sr_launch_lr_input(const uint8_t* d_lr, int ch, long npx, float* d_x, const float* d_tab, hipStream_t s) {
+    if (npx <= 0 || (ch != 3 && ch != 4) || ((uintptr_t)d_x & 15u)) return hipErrorInvalidValue;
+    const long nval = 3 * npx;
+    const dim3 grid((unsigned)(((nval + 3) / 4 + 255) / 256));
+    if (ch == 3) hipLaunchKernelGGL(lr_input_kernel<3>, grid, dim3(256), 0, s, d_lr, d_x, d_tab, nval);
+    else hipLaunchKernelGGL(lr_input_kernel<4>, grid, dim3(256), 0, s, d_lr, d_x, d_tab, nval);
+    return hipGetLastError();
+}
+
+hipError_t sr_queue_lr_input(const sr_lr_input& lr, long npx, float* d_x, const float* d_tab, hipStream_t s) {
+    if (lr.in_place) return hipSuccess;
+    if (lr.u8) return sr_launch_lr_input((const uint8_t*)lr.d_lr, lr.ch, npx, d_x, d_tab, s);
+    return hipMemcpyAsync(d_x, lr.d_lr, (size_t)npx * 3 * sizeof(float), hipMemcpyDeviceToDevice, s);
 }
 
 hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8, int ch, bool linear, int W, int HC, int WC, const float* d_tab,

@@ -279,6 +279,115 @@ class Engine:
                                                          C.c_void_p(out.data_ptr()), self._stream_ptr(stream, hr.device)), self._ctx)
         return out
 
+    # ---- pairs: the LR image is the caller's, not the pool of the HR image (include/srhip.h, "Pairs") ----
+    def _pair_shapes(self, lr_shape, hr_shape):
+        """(lh, lw) of a pair or a batch of pairs whose trailing dimensions are (h, w, c); the HR size must be exactly f x the LR size."""
+        f = self.factor
+        lh, lw = lr_shape[-3], lr_shape[-2]
+        if tuple(lr_shape[:-3]) != tuple(hr_shape[:-3]) or (hr_shape[-3], hr_shape[-2]) != (f * lh, f * lw):
+            raise _lib.SrError(_lib.SR_E_INVALID, f"HR {tuple(hr_shape)} is not {f} x LR {tuple(lr_shape)}")
+        return lh, lw
+
+    def validation_error_pair(self, lr: np.ndarray, hr: np.ndarray, linear_loss: bool = False):
+        """LR image (lh,lw,3|4) and HR image (f*lh,f*lw,3|4), both u8 (byte / 255, alpha dropped) or both (.,.,3) f32 ->
+        (err_sum, n_elems): the squared error of sr_net(f)(lr) against hr (sr_pair_validation_error_*)."""
+        lr, hr = np.asarray(lr), np.asarray(hr)
+        if lr.ndim != 3 or hr.ndim != 3:
+            raise ValueError("expected one (H, W, C) image each")
+        if lr.dtype != hr.dtype:
+            raise ValueError("LR and HR must both be u8 or both f32")
+        lh, lw = self._pair_shapes(lr.shape, hr.shape)
+        err, n = C.c_double(), C.c_size_t()
+        lr, hr = np.ascontiguousarray(lr), np.ascontiguousarray(hr)
+        if hr.dtype == np.uint8:
+            u8p = C.POINTER(C.c_uint8)
+            st = self._L.sr_pair_validation_error_rgba8(self._ctx, lr.ctypes.data_as(u8p), lr.shape[2], hr.ctypes.data_as(u8p), hr.shape[2],
+                                                        lh, lw, int(bool(linear_loss)), C.byref(err), C.byref(n))
+        elif hr.dtype == np.float32:
+            if lr.shape[2] != 3 or hr.shape[2] != 3:
+                raise ValueError("an f32 image has 3 channels")
+            fp = C.POINTER(C.c_float)
+            st = self._L.sr_pair_validation_error_f32(self._ctx, lr.ctypes.data_as(fp), hr.ctypes.data_as(fp), lh, lw, int(bool(linear_loss)),
+                                                      C.byref(err), C.byref(n))
+        else:
+            raise ValueError("expected u8 or f32 pixels")
+        _lib.check(st, self._ctx)
+        return err.value, n.value
+
+    def validation_error_pair_dev(self, lr, hr, linear_loss: bool = False, out=None, stream=None):
+        """(lh,lw,3|4) and (f*lh,f*lw,3|4) u8 torch tensors on this engine's device -> a float64 tensor of one element holding err_sum,
+        asynchronous on the stream (sr_pair_validation_error_rgba8_dev)."""
+        import torch
+        for t in (lr, hr):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3
+        lh, lw = self._pair_shapes(lr.shape, hr.shape)
+        if out is None:
+            out = torch.empty(1, dtype=torch.float64, device=hr.device)
+        _lib.check(self._L.sr_pair_validation_error_rgba8_dev(self._ctx, C.c_void_p(lr.data_ptr()), lr.shape[2], C.c_void_p(hr.data_ptr()),
+                                                              hr.shape[2], lh, lw, int(bool(linear_loss)), C.c_void_p(out.data_ptr()),
+                                                              self._stream_ptr(stream, hr.device)), self._ctx)
+        return out
+
+    def backprop_pair(self, lr: np.ndarray, hr: np.ndarray, params, linear_loss: bool = False, loss_scale: Optional[float] = None,
+                      l2: float = 0.0):
+        """LR batch (n,lh,lw,3|4) and HR batch (n,f*lh,f*lw,3|4), both u8 or both (.,.,.,3) f32 -> (err_sum, n_elems, grad), as
+        backprop() with the network's input taken from lr (sr_pair_backprop_*).  loss_scale None: 1 / n_elems."""
+        lr, hr = np.asarray(lr), np.asarray(hr)
+        if lr.ndim == 3 and hr.ndim == 3:
+            lr, hr = lr[None], hr[None]
+        if lr.ndim != 4 or hr.ndim != 4:
+            raise ValueError("expected (n, H, W, C) images")
+        if lr.dtype != hr.dtype:
+            raise ValueError("LR and HR must both be u8 or both f32")
+        lh, lw = self._pair_shapes(lr.shape, hr.shape)
+        n, f = hr.shape[0], self.factor
+        if loss_scale is None:
+            loss_scale = 1.0 / (n * 3 * f * lh * f * lw) if lh >= 1 and lw >= 1 and n >= 1 else 1.0
+        p = np.ascontiguousarray(params, dtype=np.float32)
+        grad = np.empty(max(self.num_params(), 1), dtype=np.float32)
+        err, ne = C.c_double(), C.c_size_t()
+        fp = C.POINTER(C.c_float)
+        lr, hr = np.ascontiguousarray(lr), np.ascontiguousarray(hr)
+        if hr.dtype == np.uint8:
+            u8p = C.POINTER(C.c_uint8)
+            st = self._L.sr_pair_backprop_rgba8(self._ctx, p.ctypes.data_as(fp), p.size, lr.ctypes.data_as(u8p), lr.shape[3],
+                                                hr.ctypes.data_as(u8p), hr.shape[3], n, lh, lw, int(bool(linear_loss)), float(loss_scale),
+                                                float(l2), C.byref(err), C.byref(ne), grad.ctypes.data_as(fp))
+        elif hr.dtype == np.float32:
+            if lr.shape[3] != 3 or hr.shape[3] != 3:
+                raise ValueError("an f32 batch has 3 channels")
+            st = self._L.sr_pair_backprop_f32(self._ctx, p.ctypes.data_as(fp), p.size, lr.ctypes.data_as(fp), hr.ctypes.data_as(fp), n, lh, lw,
+                                              int(bool(linear_loss)), float(loss_scale), float(l2), C.byref(err), C.byref(ne),
+                                              grad.ctypes.data_as(fp))
+        else:
+            raise ValueError("expected u8 or f32 pixels")
+        _lib.check(st, self._ctx)
+        return err.value, ne.value, grad
+
+    def backprop_pair_dev(self, lr, hr, params, linear_loss: bool = False, loss_scale: Optional[float] = None, l2: float = 0.0,
+                          grad=None, err=None, stream=None):
+        """(n,lh,lw,3|4) and (n,f*lh,f*lw,3|4) u8 torch tensors and an f32 parameter tensor on this engine's device -> (err, grad),
+        asynchronous on the stream (sr_pair_backprop_rgba8_dev)."""
+        import torch
+        for t in (lr, hr):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 4
+        assert params.is_cuda and params.dtype == torch.float32 and params.is_contiguous()
+        lh, lw = self._pair_shapes(lr.shape, hr.shape)
+        n, f = hr.shape[0], self.factor
+        if loss_scale is None:
+            loss_scale = 1.0 / (n * 3 * f * lh * f * lw) if lh >= 1 and lw >= 1 and n >= 1 else 1.0
+        if grad is None:
+            grad = torch.empty_like(params)
+        if err is None:
+            err = torch.empty(1, dtype=torch.float64, device=hr.device)
+        if params.numel() != self.num_params():
+            raise _lib.SrError(_lib.SR_E_PARAM_COUNT)
+        _lib.check(self._L.sr_pair_backprop_rgba8_dev(self._ctx, C.c_void_p(params.data_ptr()), C.c_void_p(lr.data_ptr()), lr.shape[3],
+                                                      C.c_void_p(hr.data_ptr()), hr.shape[3], n, lh, lw, int(bool(linear_loss)),
+                                                      float(loss_scale), float(l2), C.c_void_p(err.data_ptr()),
+                                                      C.c_void_p(grad.data_ptr()), self._stream_ptr(stream, hr.device)), self._ctx)
+        return err, grad
+
     def validation_nodes(self, h: int, w: int):
         """The last validation call's `input` node (the pooled LR image, (h//f, w//f, 3)) and `output` node (the f32 network output,
         (f*(h//f), f*(w//f), 3)), for an HR image of h x w (sr_read_validation_nodes)."""
@@ -522,10 +631,11 @@ def upscale_sharded_all(engines, bands, outs=None):
     return outs
 
 
-def validation_psnr(engines, images, linear_loss: bool = False) -> float:
+def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None) -> float:
     """The reference's validation PSNR (main.rs:236-246) of a set of HR images: -10 log10(sum err_i / sum n_i).  Images are dealt
     round-robin over the engines (one host thread each); the sums are taken in image order, so the value does not depend on how many
-    engines there are.  A zero error is +inf."""
+    engines there are.  A zero error is +inf.  lr_images: the LR partner of each image -- the set is then scored as pairs
+    (validation_error_pair) instead of by pooling."""
     import math
     from concurrent.futures import ThreadPoolExecutor
     if isinstance(engines, Engine):
@@ -533,11 +643,18 @@ def validation_psnr(engines, images, linear_loss: bool = False) -> float:
     images = list(images)
     if not engines or not images:
         raise ValueError("validation_psnr needs at least one engine and one image")
+    if lr_images is not None:
+        lr_images = list(lr_images)
+        if len(lr_images) != len(images):
+            raise ValueError("validation_psnr needs one LR image per HR image")
     res = [None] * len(images)
 
     def run(k):
         for i in range(k, len(images), len(engines)):
-            res[i] = engines[k].validation_error(images[i], linear_loss)
+            if lr_images is None:
+                res[i] = engines[k].validation_error(images[i], linear_loss)
+            else:
+                res[i] = engines[k].validation_error_pair(lr_images[i], images[i], linear_loss)
 
     with ThreadPoolExecutor(max_workers=len(engines)) as pool:
         for fut in [pool.submit(run, k) for k in range(len(engines))]:
@@ -612,6 +729,51 @@ class Trainer:
         _lib.check(self._L.sr_train_step(self._t, arr, len(items), int(crop_h), int(crop_w)), self.engine._ctx)
         self.steps += 1
         self._pending += 1
+
+    def add_pair(self, lr, hr) -> int:
+        """(lh, lw, 3|4) and (f*lh, f*lw, 3|4) u8 -> the id of the pair in the device store (one entry), or -1 when there is no room."""
+        lr, hr = np.ascontiguousarray(lr), np.ascontiguousarray(hr)
+        if lr.dtype != np.uint8 or hr.dtype != np.uint8 or lr.ndim != 3 or hr.ndim != 3:
+            raise ValueError("expected (h, w, 3|4) u8 pixels")
+        lh, lw = self.engine._pair_shapes(lr.shape, hr.shape)
+        i = C.c_int()
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_train_add_pair(self._t, lr.ctypes.data_as(u8p), lr.shape[2], hr.ctypes.data_as(u8p), hr.shape[2], lh, lw,
+                                             C.byref(i)), self.engine._ctx)
+        return i.value
+
+    def step_pair_crops(self, items, crop_lh: int, crop_lw: int) -> None:
+        """One step on crops of pairs, queued without waiting.  items: (pair, y0, x0), pair an id of add_pair or an (lr, hr) tuple of u8
+        arrays; y0, x0 and the crop size are in LR pixels."""
+        arr = (_lib.TrainPairCrop * max(len(items), 1))()
+        keep = []
+        for k, (pair, y0, x0) in enumerate(items):
+            it = arr[k]
+            it.y0, it.x0 = int(y0), int(x0)
+            if isinstance(pair, (int, np.integer)):
+                it.pair = int(pair)
+            else:
+                lr, hr = (np.ascontiguousarray(a) for a in pair)
+                if lr.dtype != np.uint8 or hr.dtype != np.uint8 or lr.ndim != 3 or hr.ndim != 3:
+                    raise ValueError("expected (h, w, 3|4) u8 pixels")
+                it.lh, it.lw = self.engine._pair_shapes(lr.shape, hr.shape)
+                keep += [lr, hr]
+                it.pair, it.lr_px, it.hr_px = -1, lr.ctypes.data, hr.ctypes.data
+                it.lr_channels, it.hr_channels = lr.shape[2], hr.shape[2]
+        _lib.check(self._L.sr_train_step_pairs(self._t, arr, len(items), int(crop_lh), int(crop_lw)), self.engine._ctx)
+        self.steps += 1
+        self._pending += 1
+
+    def step_pairs(self, lr_batch, hr_batch) -> float:
+        """One backprop and one Adam step on a whole batch of pairs: (n,lh,lw,3|4) and (n,f*lh,f*lw,3|4) u8, numpy or torch tensors."""
+        lr = lr_batch.cpu().numpy() if hasattr(lr_batch, "cpu") else np.asarray(lr_batch)
+        hr = hr_batch.cpu().numpy() if hasattr(hr_batch, "cpu") else np.asarray(hr_batch)
+        if lr.ndim == 3 and hr.ndim == 3:
+            lr, hr = lr[None], hr[None]
+        if lr.shape[0] != hr.shape[0]:
+            raise ValueError("expected as many LR as HR images")
+        self.step_pair_crops([((lr[i], hr[i]), 0, 0) for i in range(hr.shape[0])], lr.shape[1], lr.shape[2])
+        return self.sync()[-1]
 
     def sync(self) -> List[float]:
         """Wait for every queued step; the err_sum of each step since the last sync."""

@@ -2,8 +2,8 @@
 // (reference src/main.rs:33-258), driving the MI355X engine through libsrhip's C ABI.
 //
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
-//   rusty_sr train [-l] [-r] [-s START] [-v VAL_FOLDER] [-m N] <PARAMETER_FILE> <TRAINING_FOLDER>
-//   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] <VALIDATION_FOLDER>
+//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] <PARAMETER_FILE> <TRAINING_FOLDER>
+//   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] <VALIDATION_FOLDER>
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
 // PSNR a parameter set reaches on a folder of HR images.  A first argument that is literally `train` or `validate` selects it; every
@@ -26,6 +26,7 @@
 #include <condition_variable>
 #include <deque>
 #include <filesystem>
+#include <map>
 #include <mutex>
 #include <random>
 #include <string>
@@ -74,6 +75,8 @@ const char* kValidateUsage =
     "OPTIONS:\n    -c, --custom <PARAMETER_FILE>    Sets a custom parameter file (.rsr); its size selects the factor (2, 3 or 4)\n"
     "    -p, --parameters <PARAMETERS>    Sets which built-in parameters to use [values: imagenet, imagenetlinear, anime]\n"
     "    -m, --val_max <N>                Set upper limit on number of images used for the validation pass\n"
+    "        --lr_folder <DIR>            Score LR / HR pairs: the network's input is the file of DIR with the same relative\n"
+    "                                     path (extension ignored), exactly 1/f the size, instead of the pooled HR image\n"
     "        --devices <N,N,...>          HIP devices; images are dealt round-robin [default: 0]\n"
     "        --precision <MODE>           f32 (exact) or split_f16 [default: f32]\n\n"
     "ARGS:\n    <VALIDATION_FOLDER>    Images from this folder (or sub-folders with -r) are scored, in path order\n";
@@ -213,12 +216,41 @@ bool list_images(const std::string& folder, bool recurse, std::vector<std::strin
     return true;
 }
 
+// --lr_folder: the LR partner of every HR file -- the file of lr_folder with the same path relative to its folder, extension ignored.
+// An HR file without one ends the run (the message names it); LR files without an HR partner are ignored.
+std::vector<std::string> pair_files(const std::string& hr_folder, const std::vector<std::string>& hr_files, const std::string& lr_folder,
+                                    bool recurse) {
+    namespace fs = std::filesystem;
+    std::vector<std::string> lr_files;
+    std::string err;
+    if (!list_images(lr_folder, recurse, lr_files, err)) die("could not read the LR folder (" + err + ")");
+    auto key = [](const std::string& folder, const std::string& file) {
+        return fs::path(file).lexically_relative(folder).replace_extension().generic_string();
+    };
+    std::map<std::string, std::string> by_key;
+    for (const std::string& f : lr_files) by_key.emplace(key(lr_folder, f), f);  // (sorted: of two extensions the first in path order)
+    std::vector<std::string> out;
+    for (const std::string& f : hr_files) {
+        const auto it = by_key.find(key(hr_folder, f));
+        if (it == by_key.end()) die(f + " has no LR partner in '" + lr_folder + "'");
+        out.push_back(it->second);
+    }
+    return out;
+}
+
+// A pair whose HR size is not exactly f x its LR size ends the run.
+void check_pair_sizes(const std::string& hr_file, const srpng::Image& hr, const std::string& lr_file, const srpng::Image& lr, int f) {
+    if (hr.h == f * lr.h && hr.w == f * lr.w) return;
+    die(hr_file + " is " + std::to_string(hr.w) + "x" + std::to_string(hr.h) + " but its LR partner " + lr_file + " is " +
+        std::to_string(lr.w) + "x" + std::to_string(lr.h) + ": the HR size must be exactly " + std::to_string(f) + " x the LR size");
+}
+
 // rusty_sr validate: the validation pass of the reference's `train` (main.rs:220-247) on its own.  Files are decoded on up to 16 host
 // threads (OMP_NUM_THREADS if set) ahead of the GPU, which scores them in path order; with --devices image i goes to context i mod n.
 // The sums are taken in image order, so the printed value does not depend on the number of devices.
 int run_validate(int argc, char** argv) {
-    std::string parameters, custom, precision = "f32", folder;
-    bool has_p = false, has_c = false, linear = false, recurse = false, timing = false, has_folder = false;
+    std::string parameters, custom, precision = "f32", folder, lr_folder;
+    bool has_p = false, has_c = false, linear = false, recurse = false, timing = false, has_folder = false, has_lr = false;
     long val_max = -1;
     std::vector<int> devices;
     for (int k = 2; k < argc; ++k) {
@@ -254,6 +286,7 @@ int run_validate(int argc, char** argv) {
             }
         }
         else if (a == "--precision") precision = value("--precision <MODE>");
+        else if (a == "--lr_folder") { lr_folder = value("--lr_folder <DIR>"); has_lr = true; }
         else if (a.size() > 1 && a[0] == '-') validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (has_folder) validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else { folder = a; has_folder = true; }
@@ -274,7 +307,10 @@ int run_validate(int argc, char** argv) {
         if (!list_images(folder, recurse, files, err)) die("could not read the validation folder (" + err + ")");
         if (val_max > 0 && (size_t)val_max < files.size()) files.resize((size_t)val_max);
         if (files.empty()) validate_usage_error("no image files in '" + folder + "'" + (recurse ? "" : " (-r recurses into subfolders)"));
+        if (has_lr && !std::filesystem::is_directory(lr_folder, ec)) validate_usage_error("'" + lr_folder + "' is not a folder");
     }
+    std::vector<std::string> lr_files;
+    if (has_lr) lr_files = pair_files(folder, files, lr_folder, recurse);
 
     // ---- parameters; a custom file's length selects the factor it was trained for
     std::vector<float> params;
@@ -308,6 +344,8 @@ int run_validate(int argc, char** argv) {
     const size_t nfile = files.size();
     DecoderPool decoders(files, nfile, devices.size());
     for (size_t i = 0; i < nfile; ++i) decoders.push(i);
+    DecoderPool lr_decoders(lr_files, std::max<size_t>(1, lr_files.size()), devices.size());
+    for (size_t i = 0; i < lr_files.size(); ++i) lr_decoders.push(i);
     std::mutex mu;
 
     // ---- contexts, one scoring thread per context
@@ -338,9 +376,24 @@ int run_validate(int argc, char** argv) {
                         std::lock_guard<std::mutex> lk(mu);
                         if (!derr.empty() && fail_code == 0) { failure = "Error opening validation image file " + files[i] + " (" + derr + ")"; fail_code = 1; }
                         decoders.stop();
+                        lr_decoders.stop();
                         return;
                     }
-                    const int r = sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
+                    srpng::Image lr;
+                    if (has_lr && !lr_decoders.take(i, lr, derr)) {
+                        std::lock_guard<std::mutex> lk(mu);
+                        if (!derr.empty() && fail_code == 0) { failure = "Error opening validation image file " + lr_files[i] + " (" + derr + ")"; fail_code = 1; }
+                        decoders.stop();
+                        lr_decoders.stop();
+                        return;
+                    }
+                    if (has_lr) {
+                        std::lock_guard<std::mutex> lk(mu);  // (a mismatch ends the run from here: one thread at a time)
+                        check_pair_sizes(files[i], img, lr_files[i], lr, factor);
+                    }
+                    const int r = has_lr ? sr_pair_validation_error_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
+                                                                          &err[i], &cnt[i])
+                                         : sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
                     if (r == SR_OK && timing) { double tot = 0; sr_last_timing(ctxs[k], &tot, nullptr, nullptr, nullptr); gpu_ms[i] = tot; }
                     if (r != SR_OK) {
                         std::lock_guard<std::mutex> lk(mu);
@@ -349,6 +402,7 @@ int run_validate(int argc, char** argv) {
                             fail_code = 1;
                         }
                         decoders.stop();
+                        lr_decoders.stop();
                         return;
                     }
                 }
@@ -356,6 +410,7 @@ int run_validate(int argc, char** argv) {
     }
     for (auto& t : scorers) t.join();
     decoders.stop();
+    lr_decoders.stop();
     for (sr_ctx* c : ctxs) sr_destroy(c);
     if (fail_code) die(failure, fail_code);
     double err_sum = 0, n_sum = 0, ms_sum = 0;
@@ -384,6 +439,10 @@ const char* kTrainUsage =
     "    -v, --val_folder <VAL_FOLDER>     Images from this folder (or sub-folders with -r) are used to report the validation\n"
     "                                      PSNR after the first step and every 100 steps\n"
     "    -m, --val_max <N>                 Set upper limit on number of images used for each validation pass\n"
+    "    -f, --factor <2|3|4>              The up-scaling factor when there is no -s [default: 3]\n"
+    "        --lr_folder <DIR>             Train on LR / HR pairs: TRAINING_FOLDER holds the HR images, DIR their LR partners (the\n"
+    "                                      same relative path, extension ignored, exactly 1/f the size); crops are 192/f LR pixels\n"
+    "        --val_lr_folder <DIR>         The LR partners of the validation images: the validation PSNR is then the paired score\n"
     "        --device <N>                  HIP device index [default: 0]\n"
     "        --seed <N>                    Seed of the initial parameters, the shuffles and the crops [default: random]\n"
     "        --steps <N>                   Stop after N steps [default: 2500000, the reference's 10 000 000 evaluations]\n"
@@ -439,9 +498,10 @@ std::vector<uint8_t> to_rgb(const srpng::Image& img) {
 // each time they are drawn (ahead of the GPU, on the decoder pool).  After step 1 and every 100th step the parameter file is written and,
 // with -v, the PSNR of the next min(#files, N) validation images (sorted, wrapping round) at the current parameters is printed.
 int run_train(int argc, char** argv) {
-    std::string start, val_folder;
+    std::string start, val_folder, lr_folder, val_lr_folder;
     std::vector<std::string> pos;
-    bool has_s = false, has_v = false, linear = false, recurse = false, timing = false;
+    bool has_s = false, has_v = false, linear = false, recurse = false, timing = false, has_lr = false, has_vlr = false, has_f = false;
+    long factor_arg = SR_FACTOR;
     long val_max = -1, steps = 2500000, device = 0, store = -1;
     uint64_t seed = 0;
     bool has_seed = false;
@@ -460,6 +520,14 @@ int run_train(int argc, char** argv) {
         else if (a == "-m" || a == "--val_max") {
             const std::string v = value("--val_max <N>");
             if (!parse_count(v, val_max) || val_max <= 0) train_usage_error("-val_max N must be a positive integer");  // main.rs:225
+        }
+        else if (a == "--lr_folder") { lr_folder = value("--lr_folder <DIR>"); has_lr = true; }
+        else if (a == "--val_lr_folder") { val_lr_folder = value("--val_lr_folder <DIR>"); has_vlr = true; }
+        else if (a == "-f" || a == "--factor") {
+            const std::string v = value("--factor <2|3|4>");
+            if (!parse_count(v, factor_arg) || factor_arg < 2 || factor_arg > 4)
+                train_usage_error("'" + v + "' isn't a valid value for '--factor <2|3|4>'\n\t[values: 2, 3, 4]");
+            has_f = true;
         }
         else if (a == "--device") {
             const std::string v = value("--device <N>");
@@ -485,6 +553,8 @@ int run_train(int argc, char** argv) {
     }
     if (val_max > 0 && !has_v)  // clap: -m requires -v (main.rs:104)
         train_usage_error("The following required arguments were not provided:\n    --val_folder <VAL_FOLDER>");
+    if (has_vlr && !has_v)
+        train_usage_error("The following required arguments were not provided:\n    --val_folder <VAL_FOLDER>");
     if (pos.size() < 2) train_usage_error("The following required arguments were not provided:\n    <PARAMETER_FILE>\n    <TRAINING_FOLDER>");
     if (!has_seed) seed = ((uint64_t)std::random_device{}() << 32) ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
     const std::string param_file = pos[0], train_folder = pos[1];
@@ -502,10 +572,15 @@ int run_train(int argc, char** argv) {
             if (!list_images(val_folder, recurse, vfiles, err)) die("could not read the validation folder (" + err + ")");
             if (vfiles.empty()) train_usage_error("no image files in '" + val_folder + "'" + (recurse ? "" : " (-r recurses into subfolders)"));
         }
+        if (has_lr && !std::filesystem::is_directory(lr_folder, ec)) train_usage_error("'" + lr_folder + "' is not a folder");
+        if (has_vlr && !std::filesystem::is_directory(val_lr_folder, ec)) train_usage_error("'" + val_lr_folder + "' is not a folder");
     }
-    // ---- parameters: the start file (its length selects the factor) or g.init_params() at factor 3
+    std::vector<std::string> lr_files, vlr_files;
+    if (has_lr) lr_files = pair_files(train_folder, files, lr_folder, recurse);
+    if (has_vlr) vlr_files = pair_files(val_folder, vfiles, val_lr_folder, recurse);
+    // ---- parameters: the start file (its length selects the factor) or g.init_params() at the factor of -f (3 without it)
     std::vector<float> params;
-    int factor = SR_FACTOR;
+    int factor = (int)factor_arg;
     if (has_s) {
         FILE* f = fopen(start.c_str(), "rb");
         if (!f) die("Error opening start parameter file");  // main.rs:192
@@ -515,8 +590,13 @@ int run_train(int argc, char** argv) {
         while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) data.insert(data.end(), tmp, tmp + n);
         fclose(f);
         params = decode_rsr(data.data(), data.size());
+        int file_factor = SR_FACTOR;
         for (int fc : {3, 2, 4})
-            if (params.size() == (size_t)sr_num_params_factor(fc)) { factor = fc; break; }
+            if (params.size() == (size_t)sr_num_params_factor(fc)) { file_factor = fc; break; }
+        if (has_f && file_factor != factor && params.size() == (size_t)sr_num_params_factor(file_factor))
+            train_usage_error("The argument '--factor " + std::to_string(factor) + "' cannot be used with start parameters of factor " +
+                              std::to_string(file_factor));
+        factor = file_factor;
     } else {
         params.resize((size_t)sr_num_params_factor(factor));
         if (sr_init_params(factor, seed, params.data(), params.size()) != SR_OK) die("could not initialise the parameters");
@@ -535,19 +615,29 @@ int run_train(int argc, char** argv) {
 
     // ---- every training image decoded once: into the store while it has room; the rest are transient (their sizes are kept)
     const size_t nfile = files.size();
-    struct TrainImage { int id = -1, h = 0, w = 0; bool ok = false; };
+    struct TrainImage { int id = -1, h = 0, w = 0; bool ok = false; };  // (h, w: of the HR image)
     std::vector<TrainImage> timg(nfile);
     double decode_ms = 0;
     {
-        DecoderPool pool(files, nfile);
+        DecoderPool pool(files, nfile), lr_pool(lr_files, std::max<size_t>(1, lr_files.size()));
         for (size_t i = 0; i < nfile; ++i) pool.push(i);
+        for (size_t i = 0; i < lr_files.size(); ++i) lr_pool.push(i);
         for (size_t i = 0; i < nfile; ++i) {
-            srpng::Image img;
+            srpng::Image img, lr;
             std::string err;
-            if (!pool.take(i, img, err)) { fprintf(stderr, "warning: skipping training image %s (%s)\n", files[i].c_str(), err.c_str()); continue; }
+            const bool ok = pool.take(i, img, err);
+            if (!ok) fprintf(stderr, "warning: skipping training image %s (%s)\n", files[i].c_str(), err.c_str());
+            if (has_lr && !lr_pool.take(i, lr, err)) die("Error opening training image file " + lr_files[i] + " (" + err + ")");
+            if (!ok) continue;
             timg[i].h = img.h; timg[i].w = img.w; timg[i].ok = true;
             const std::vector<uint8_t> rgb = to_rgb(img);
-            rc = sr_train_add_image(tr, rgb.data(), 3, img.h, img.w, &timg[i].id);
+            if (has_lr) {
+                check_pair_sizes(files[i], img, lr_files[i], lr, factor);
+                const std::vector<uint8_t> lr_rgb = to_rgb(lr);
+                rc = sr_train_add_pair(tr, lr_rgb.data(), 3, rgb.data(), 3, lr.h, lr.w, &timg[i].id);
+            } else {
+                rc = sr_train_add_image(tr, rgb.data(), 3, img.h, img.w, &timg[i].id);
+            }
             if (rc != SR_OK) die(std::string("could not store a training image: ") + sr_strerror(rc));
         }
     }
@@ -556,21 +646,28 @@ int run_train(int argc, char** argv) {
     for (size_t i = 0; i < nfile; ++i) if (timg[i].ok) usable.push_back(i);
     if (usable.empty()) train_usage_error("no decodable image in '" + train_folder + "'");
     // ---- validation images: decoded once, kept on the host
-    std::vector<srpng::Image> vimg;
+    std::vector<srpng::Image> vimg, vlr;
     if (has_v) {
-        DecoderPool pool(vfiles, vfiles.size());
+        DecoderPool pool(vfiles, vfiles.size()), lr_pool(vlr_files, std::max<size_t>(1, vlr_files.size()));
         for (size_t i = 0; i < vfiles.size(); ++i) pool.push(i);
+        for (size_t i = 0; i < vlr_files.size(); ++i) lr_pool.push(i);
         vimg.resize(vfiles.size());
+        vlr.resize(vlr_files.size());
         for (size_t i = 0; i < vfiles.size(); ++i) {
             std::string err;
             if (!pool.take(i, vimg[i], err)) die("Error opening validation image file " + vfiles[i] + " (" + err + ")");
+            if (!has_vlr) continue;
+            if (!lr_pool.take(i, vlr[i], err)) die("Error opening validation image file " + vlr_files[i] + " (" + err + ")");
+            check_pair_sizes(vfiles[i], vimg[i], vlr_files[i], vlr[i], factor);
         }
     }
     const size_t val_n = has_v ? std::min(vimg.size(), val_max > 0 ? (size_t)val_max : vimg.size()) : 0;
     size_t val_next = 0;
 
     // ---- the draws: a fresh shuffle of the usable files each epoch, one crop of each drawn image
-    constexpr int kBatch = 4, kCrop = 192;
+    // (pairs: one crop of 192 / f LR pixels per draw, its origin in LR pixels, uniform over the positions inside the LR image)
+    constexpr int kBatch = 4, kCropHr = 192;
+    const int unit = has_lr ? factor : 1, kCrop = kCropHr / unit;
     Rng rng{seed ^ 0x5eed5eed5eed5eedull};
     std::vector<size_t> perm;
     size_t perm_pos = 0;
@@ -584,20 +681,23 @@ int run_train(int argc, char** argv) {
         const size_t fi = perm[perm_pos++];
         const TrainImage& im = timg[fi];
         // the crop origin: uniform over the positions inside the image; 0 on an axis shorter than the crop (the rest is zero padding)
-        const int y0 = im.h > kCrop ? (int)rng.below((uint64_t)(im.h - kCrop + 1)) : 0;
-        const int x0 = im.w > kCrop ? (int)rng.below((uint64_t)(im.w - kCrop + 1)) : 0;
+        const int h = im.h / unit, w = im.w / unit;
+        const int y0 = h > kCrop ? (int)rng.below((uint64_t)(h - kCrop + 1)) : 0;
+        const int x0 = w > kCrop ? (int)rng.below((uint64_t)(w - kCrop + 1)) : 0;
         return {fi, y0, x0};
     };
     // draws are made a window of steps ahead, so that transient images decode while the GPU works
-    DecoderPool pool(files, 16 * kBatch);
-    std::deque<std::pair<Draw, long>> ahead;  // (draw, decoder job or -1)
+    DecoderPool pool(files, 16 * kBatch), lr_pool(lr_files, 16 * kBatch);
+    std::deque<std::pair<Draw, long>> ahead;  // (draw, decoder job or -1; a transient pair's LR file has the same job number in lr_pool)
     const long lookahead = 8 * kBatch;
     long drawn = 0;
     auto fill = [&]() {
         while ((long)ahead.size() < lookahead && drawn < steps * kBatch) {
             const Draw d = draw();
             ++drawn;
-            ahead.emplace_back(d, timg[d.file].id >= 0 ? -1 : (long)pool.push(d.file));
+            const long job = timg[d.file].id >= 0 ? -1 : (long)pool.push(d.file);
+            if (job >= 0 && has_lr) lr_pool.push(d.file);
+            ahead.emplace_back(d, job);
         }
     };
 
@@ -615,7 +715,12 @@ int run_train(int argc, char** argv) {
             val_next = (val_next + 1) % vimg.size();
             double e = 0;
             size_t ne = 0;
-            r = sr_validation_error_rgba8(ctx, im.rgba.data(), 4, im.h, im.w, linear ? 1 : 0, &e, &ne);
+            if (has_vlr) {
+                const srpng::Image& lr = vlr[(val_next + vimg.size() - 1) % vimg.size()];
+                r = sr_pair_validation_error_rgba8(ctx, lr.rgba.data(), 4, im.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0, &e, &ne);
+            } else {
+                r = sr_validation_error_rgba8(ctx, im.rgba.data(), 4, im.h, im.w, linear ? 1 : 0, &e, &ne);
+            }
             if (r != SR_OK) die(std::string("validation: ") + sr_strerror(r) + (r == SR_E_INVALID ? " (an image smaller than one pooling block?)" : ""));
             err_sum += e;
             n_sum += (double)ne;
@@ -630,33 +735,40 @@ int run_train(int argc, char** argv) {
     const clk::time_point t0 = clk::now();
     long resident_draws = 0;
     double wait_ms = 0;
-    std::vector<std::vector<uint8_t>> held(kBatch);  // transient pixels of the step being queued
+    std::vector<std::vector<uint8_t>> held(kBatch), held_lr(kBatch);  // transient pixels of the step being queued
     for (long step = 1; step <= steps; ++step) {
         fill();
         sr_train_crop items[kBatch];
+        sr_train_pair_crop pairs[kBatch];
         for (int i = 0; i < kBatch; ++i) {
             const auto [d, job] = ahead.front();
             ahead.pop_front();
-            items[i].y0 = d.y0;
-            items[i].x0 = d.x0;
+            items[i].y0 = pairs[i].y0 = d.y0;
+            items[i].x0 = pairs[i].x0 = d.x0;
             if (job < 0) {
-                items[i].image = timg[d.file].id;
-                items[i].px = nullptr;
+                items[i].image = pairs[i].pair = timg[d.file].id;
+                items[i].px = pairs[i].lr_px = pairs[i].hr_px = nullptr;
                 items[i].in_channels = 3; items[i].h = timg[d.file].h; items[i].w = timg[d.file].w;
+                pairs[i].lr_channels = pairs[i].hr_channels = 3; pairs[i].lh = timg[d.file].h / unit; pairs[i].lw = timg[d.file].w / unit;
                 ++resident_draws;
                 continue;
             }
-            srpng::Image img;
+            srpng::Image img, lr;
             std::string err;
             const clk::time_point tw = clk::now();
             if (!pool.take((size_t)job, img, err)) die("Error opening training image file " + files[d.file] + " (" + err + ")");
+            if (has_lr && !lr_pool.take((size_t)job, lr, err)) die("Error opening training image file " + lr_files[d.file] + " (" + err + ")");
             wait_ms += std::chrono::duration<double, std::milli>(clk::now() - tw).count();
+            if (has_lr) check_pair_sizes(files[d.file], img, lr_files[d.file], lr, factor);
             held[i] = std::move(img.rgba);
-            items[i].image = -1;
-            items[i].px = held[i].data();
+            held_lr[i] = std::move(lr.rgba);
+            items[i].image = pairs[i].pair = -1;
+            items[i].px = pairs[i].hr_px = held[i].data();
             items[i].in_channels = 4; items[i].h = img.h; items[i].w = img.w;
+            pairs[i].lr_px = held_lr[i].data();
+            pairs[i].lr_channels = pairs[i].hr_channels = 4; pairs[i].lh = lr.h; pairs[i].lw = lr.w;
         }
-        rc = sr_train_step(tr, items, kBatch, kCrop, kCrop);
+        rc = has_lr ? sr_train_step_pairs(tr, pairs, kBatch, kCrop, kCrop) : sr_train_step(tr, items, kBatch, kCrop, kCrop);
         if (rc != SR_OK) die(std::string("training step: ") + sr_strerror(rc));
         if (step % 1000 == 0) {  // keep the err_sum list of the session short (the values are not reported)
             rc = sr_train_sync(tr, nullptr, 0, nullptr);
@@ -675,6 +787,7 @@ int run_train(int argc, char** argv) {
                 (int)std::count_if(timg.begin(), timg.end(), [](const TrainImage& t) { return t.id >= 0; }), wait_ms);
     }
     pool.stop();
+    lr_pool.stop();
     sr_train_destroy(tr);
     sr_destroy(ctx);
     printf("Done\n");

@@ -7,7 +7,15 @@ against the same folder forced transient (--store 0).  Prints one JSON line per 
   session      wall time per step of Trainer.step_crops (queued, one sync at the end) -- what the host sustains
   device       HIP events around the same number of sr_backprop_rgba8_dev + sr_adam_step_dev calls on a pre-cut batch: the device
                time of a step without its crop gather (the crop kernel's own time: run this under rocprofv3 --kernel-trace --stats)
-  cli          steps/s of `rusty_sr train --timing` on a generated folder, with the store and with --store 0"""
+  cli          steps/s of `rusty_sr train --timing` on a generated folder, with the store and with --store 0
+
+    python scripts/train_bench.py --ab OTHER_CHECKOUT [--repeats 3] [--steps 1000] [--warmup 100] [--out FILE]
+
+  The paired step against the pooled step, and this build against another (its parent): in turn, each in a fresh process and
+  `--repeats` times over, the other checkout's pooled session step, this build's pooled step and this build's paired step
+  (sr_train_step_pairs on resident LR / HR pairs, LR crops of 64 x 64) -- same images, same origins.  The spread of each row over its
+  repeats is the run-to-run spread the differences are read against.  (--one MODE: a single such measurement, of the package under
+  --root.)"""
 import argparse
 import json
 import os
@@ -20,7 +28,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
@@ -80,6 +87,56 @@ def session_bench(steps, warmup, out):
           "backprop_adam_device_ms_per_step": round(device_ms, 4), "wall_over_device": round(wall / device_ms, 4)}, out)
 
 
+def one_step_bench(mode, steps, warmup):
+    """wall ms per queued session step at the reference step: mode "pooled" (step_crops on HR images) or "paired" (step_pair_crops)"""
+    import rusty_sr_amd as r
+    from conftest import synth_u8
+    params = r.rsr.builtin("imagenet")
+    eng = r.Engine(params, device=0)
+    rng = np.random.default_rng(0)
+    imgs = [synth_u8(k, 1, 480, 642)[0] for k in range(8)]
+    tr = r.Trainer(eng, params)
+    if mode == "paired":
+        lrs = [np.ascontiguousarray(im.reshape(160, 3, 214, 3, 3)[:, 1, :, 1]) for im in imgs]  # (any LR image will do for the timing)
+        ids = [tr.add_pair(lr, im) for lr, im in zip(lrs, imgs)]
+        step = lambda it: tr.step_pair_crops(it, 64, 64)
+    else:
+        ids = [tr.add_image(im) for im in imgs]
+        step = lambda it: tr.step_crops([(i, 3 * y, 3 * x) for i, y, x in it], 192, 192)
+    assert min(ids) >= 0
+
+    def items():  # origins in LR pixels
+        return [(ids[int(rng.integers(0, len(ids)))], int(rng.integers(0, 160 - 64)), int(rng.integers(0, 214 - 64))) for _ in range(4)]
+    for _ in range(warmup):
+        step(items())
+    tr.sync()
+    plan = [items() for _ in range(steps)]
+    t0 = time.perf_counter()
+    for it in plan:
+        step(it)
+    errs = tr.sync()
+    wall = (time.perf_counter() - t0) / steps * 1e3
+    assert len(errs) == steps and all(np.isfinite(errs))
+    tr.close()
+    eng.close()
+    return wall
+
+
+def ab_bench(other, repeats, steps, warmup, out):
+    rows = [("parent_pooled", other, "pooled"), ("pooled", ROOT, "pooled"), ("paired", ROOT, "paired")]
+    got = {label: [] for label, _, _ in rows}
+    for _ in range(repeats):
+        for label, root, mode in rows:
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--root", root, "--one", mode, "--steps", str(steps), "--warmup",
+                                  str(warmup)], capture_output=True, text=True, timeout=900)
+            assert res.returncode == 0, res.stderr
+            got[label].append(json.loads(res.stdout.strip().splitlines()[-1])["wall_ms_per_step"])
+    for label, _, _ in rows:
+        v = got[label]
+        emit({"what": "pairs_ab", "row": label, "steps": steps, "warmup": warmup, "wall_ms_per_step": v, "median": round(float(np.median(v)), 4),
+              "spread": round(max(v) - min(v), 4)}, out)
+
+
 def cli_bench(steps, out):
     from PIL import Image
     from conftest import synth_u8
@@ -105,7 +162,18 @@ def main():
     ap.add_argument("--cli-steps", type=int, default=400)
     ap.add_argument("--no-cli", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--ab", default="", help="another checkout of this project, built: alternate its pooled step with this build's steps")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--root", default=ROOT, help="import rusty_sr_amd from this checkout")
+    ap.add_argument("--one", default="", choices=["", "pooled", "paired"])
     a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    if a.one:
+        emit({"what": "step", "mode": a.one, "root": a.root, "wall_ms_per_step": round(one_step_bench(a.one, a.steps, a.warmup), 4)}, "")
+        return
+    if a.ab:
+        ab_bench(a.ab, a.repeats, a.steps, a.warmup, a.out)
+        return
     session_bench(a.steps, a.warmup, a.out)
     if not a.no_cli:
         cli_bench(a.cli_steps, a.out)
