@@ -437,6 +437,44 @@ typedef struct {
 int sr_train_add_pair(sr_train* t, const uint8_t* lr_px, int lr_channels, const uint8_t* hr_px, int hr_channels, int lh, int lw, int* id);
 int sr_train_step_pairs(sr_train* t, const sr_train_pair_crop* items, int n, int crop_lh, int crop_lw);
 
+/* ---- Self-ensemble: the network averaged over flips and rotations of the image ----
+ * The reference has no counterpart (main.rs:171 runs graph.forward once); other super-resolution tools call it geometric self-ensemble or
+ * test-time augmentation.  Member k (0..7) transforms an h x w x C image, T_k:
+ *   if k & 4, swap the two spatial axes;  then, if k & 2, reverse the rows;  then, if k & 1, reverse the columns.
+ * T_k^-1 undoes these steps in the opposite order.  For a mask `members` (bits 0..7, not 0, count = its number of set bits):
+ *   acc = 0.0f
+ *   for k = 0..7 ascending, if members has bit k:  acc = acc + T_k^-1(sr_net(T_k(x)))        plain f32 adds, in this order
+ *   out = acc * (1.0f / count)                                                              the reciprocal formed in f32 on the host
+ * Each sr_net(.) is exactly what the plain call of that shape computes in the context's precision (members with bit 2 run a w x h pass).
+ * u8 input is byte / 255 with alpha dropped, as in the plain call (the bytes are transformed); RGBA8 output is clamp(floor(255 out + 0.5))
+ * with alpha 255.  members == 1 gives the plain call's bits.  Any image size, factors 2, 3 and 4, both precisions; no atomics, a grid that
+ * depends on the shape alone: the same bits on every run.  n images are handled one after another.
+ * Refused with SR_E_INVALID before any launch, the output untouched: a context other than SR_GRAPH_SR_NET, members == 0 or > 255, and (the
+ * _dev forms) pointers that break the alignment rules of sr_upscale_*_dev.  Workspace: the plain call's, an f32 copy of the image, one f32 output map and -- for RGBA8
+ * output -- one f32 accumulator (an f32 call accumulates in its output buffer), grown on first use; sr_reserve_* knows nothing of them.  A
+ * shape that cannot fit is SR_E_NOMEM and leaves the context usable.
+ * Quality: +0.06 .. +0.15 dB PSNR on images pooled by 3 with the bundled weights -- but LOWER on an image that is itself
+ * this network's output, whose artefacts the identity member reproduces and the others do not.
+ * Device memory, asynchronous and ordered on `stream` alone, like sr_upscale_*_dev (a member may run as two bands there, too): */
+#define SR_ENSEMBLE_ALL 0xFFu   /* all 8 flips and rotations */
+#define SR_ENSEMBLE_FLIPS 0x0Fu /* identity, column flip, row flip, both: every pass is h x w */
+#define SR_ENSEMBLE_HFLIP 0x03u /* identity and the column flip */
+int sr_upscale_ensemble_f32_dev(sr_ctx* ctx, const float* d_in, int n, int h, int w, float* d_out, unsigned members, void* stream);
+int sr_upscale_ensemble_rgba8_dev(sr_ctx* ctx, const uint8_t* d_in, int in_channels, int n, int h, int w, uint8_t* d_out_rgba,
+                                  unsigned members, void* stream);
+/* ... host memory, synchronous: one upload, the device call on the context's own stream, one download.  In SR_PRECISION_SPLIT_F16 the
+ * whole call is computed again in exact f32 where a value left that mode's domain, like sr_upscale_f32 / _rgba8.  With sr_set_profiling on,
+ * sr_last_timing's total_ms is every pass and pixel move of the call, h2d / d2h its two copies. */
+int sr_upscale_ensemble_f32(sr_ctx* ctx, const float* in, int n, int h, int w, float* out, unsigned members);
+int sr_upscale_ensemble_rgba8(sr_ctx* ctx, const uint8_t* in, int in_channels, int n, int h, int w, uint8_t* out_rgba, unsigned members);
+/* sr_validation_error_rgba8 ("pool": the input is the pooled HR image) / sr_pair_validation_error_rgba8 with `output` replaced by the
+ * ensemble of the network over `input`: pool or LR conversion, loss, f64 sum, n_elems and the crop rule are theirs.
+ * sr_read_validation_nodes afterwards returns the ensemble output as `output`. */
+int sr_pool_validation_error_ensemble_rgba8(sr_ctx* ctx, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, unsigned members,
+                                       double* err_sum, size_t* n_elems);
+int sr_pair_validation_error_ensemble_rgba8(sr_ctx* ctx, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh,
+                                            int lw, int linear_loss, unsigned members, double* err_sum, size_t* n_elems);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -3,7 +3,7 @@
 //! and `tests/test_rust_host.py` checks that every symbol named here is exported.
 #![allow(dead_code)]
 use std::ffi::CStr;
-use std::os::raw::{c_char, c_int, c_void};
+use std::os::raw::{c_char, c_int, c_uint, c_void};
 use std::ptr;
 
 #[repr(C)]
@@ -141,6 +141,12 @@ extern "C" {
     pub fn sr_pair_backprop_rgba8_dev(ctx: *mut SrCtx, d_params: *const f32, d_lr: *const u8, lr_channels: c_int, d_hr: *const u8, hr_channels: c_int, n: c_int, lh: c_int, lw: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, d_err_sum: *mut f64, d_grad: *mut f32, stream: *mut c_void) -> c_int;
     pub fn sr_train_add_pair(t: *mut SrTrain, lr_px: *const u8, lr_channels: c_int, hr_px: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, id: *mut c_int) -> c_int;
     pub fn sr_train_step_pairs(t: *mut SrTrain, items: *const SrTrainPairCrop, n: c_int, crop_lh: c_int, crop_lw: c_int) -> c_int;
+    pub fn sr_upscale_ensemble_f32_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut f32, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_ensemble_rgba8_dev(ctx: *mut SrCtx, d_in: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_ensemble_f32(ctx: *mut SrCtx, input: *const f32, n: c_int, h: c_int, w: c_int, out: *mut f32, members: c_uint) -> c_int;
+    pub fn sr_upscale_ensemble_rgba8(ctx: *mut SrCtx, input: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, members: c_uint) -> c_int;
+    pub fn sr_pool_validation_error_ensemble_rgba8(ctx: *mut SrCtx, hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, members: c_uint, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
+    pub fn sr_pair_validation_error_ensemble_rgba8(ctx: *mut SrCtx, lr: *const u8, lr_channels: c_int, hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, members: c_uint, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

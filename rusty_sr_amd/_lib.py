@@ -18,6 +18,7 @@ SR_GRAPH_SR_NET, SR_GRAPH_BILINEAR, SR_GRAPH_DOWNSAMPLE = 0, 1, 2
 SR_TRAIN_STORE_AUTO = (1 << (8 * C.sizeof(C.c_size_t))) - 1
 SR_TRAIN_MAX_BATCH = 64
 SR_TRAIN_RING = 64
+SR_ENSEMBLE_ALL, SR_ENSEMBLE_FLIPS, SR_ENSEMBLE_HFLIP = 0xFF, 0x0F, 0x03
 
 
 class TrainCrop(C.Structure):
@@ -104,6 +105,12 @@ SYMBOLS = {
     "sr_pair_backprop_rgba8_dev": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
     "sr_train_add_pair": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, C.POINTER(_i)]),
     "sr_train_step_pairs": (_i, [_vp, C.POINTER(TrainPairCrop), _i, _i, _i]),
+    "sr_upscale_ensemble_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, C.c_uint, _vp]),
+    "sr_upscale_ensemble_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_uint, _vp]),
+    "sr_upscale_ensemble_f32": (_i, [_vp, _fp, _i, _i, _i, _fp, C.c_uint]),
+    "sr_upscale_ensemble_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, _u8p, C.c_uint]),
+    "sr_pool_validation_error_ensemble_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, C.c_uint, _dp, C.POINTER(_sz)]),
+    "sr_pair_validation_error_ensemble_rgba8": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, _i, C.c_uint, _dp, C.POINTER(_sz)]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

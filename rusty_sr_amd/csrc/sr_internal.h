@@ -124,6 +124,11 @@ struct sr_ctx {
     // ---- backpropagation (sr_grad.cpp): grown on demand, freed by sr_destroy
     void* d_gws = nullptr; size_t gws_cap = 0;      // saved forward state, gradients of the nodes, partials (sr_grad_workspace_bytes)
     void* d_gin = nullptr; size_t gin_cap = 0;      // host-pointer calls: params, HR batch, pooled LR batch, gradient
+    // ---- self-ensemble (sr_ensemble.cpp): grown on demand, freed by sr_destroy
+    void* d_ein = nullptr; size_t ein_cap = 0;      // T_k of the caller's image, f32 RGB
+    void* d_eout = nullptr; size_t eout_cap = 0;    // one member's f32 output map
+    void* d_eacc = nullptr; size_t eacc_cap = 0;    // the f32 accumulator of a call with RGBA8 output (an f32 call accumulates in its output)
+    size_t total_mem = 0;                           // the device's memory, asked for once: a shape beyond it is refused without an allocation
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
 };
@@ -310,6 +315,25 @@ int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8
 // Grow the backprop workspace for n LR images of OH x OW; *x: where the pass reads its input batch (n x OH x OW x 3 f32, whole 256 bytes)
 int sr_grad_input_buffer(sr_ctx* c, int n, int OH, int OW, float** x);
 int sr_valid_ensure_table(sr_ctx* c);  // sr_valid.cpp: the 512-float table behind d_vtab, uploaded on first use
+
+// ---- self-ensemble (sr_ensemble.hip kernels, sr_ensemble.cpp host side; include/srhip.h sr_upscale_ensemble_*)
+// One gather of DH x DW pixels: dst[p][q] = src[r][c], (r0, c0) = swap ? (q, p) : (p, q), r / c = r0 / c0 reversed within src if flip_r / flip_c.
+struct sr_ens_map {
+    int DH, DW, swap, flip_r, flip_c;
+};
+// workgroups of such a launch (0: an empty shape), a function of the shape alone; the launchers refuse more than INT32_MAX
+size_t sr_ens_blocks(int DH, int DW, bool swap, int* lw_out = nullptr, unsigned* blocks_x_out = nullptr);
+// the image (u8 with ch channels at any byte, or f32 RGB) -> its transform at d_dst, f32 RGB (u8: byte / 255, alpha dropped)
+hipError_t sr_launch_ens_input(const void* d_src, bool u8, int ch, void* d_dst, const sr_ens_map& m, hipStream_t s);
+// acc = (first ? 0.0f : acc) + gather(member); the last member stores (that sum) * scale at d_out instead, as f32 (d_out may be d_acc) or RGBA8
+hipError_t sr_launch_ens_accumulate(const float* d_member, float* d_acc, void* d_out, bool out_u8, bool first, bool last, float scale,
+                                    const sr_ens_map& m, hipStream_t s);
+void sr_ensemble_release(sr_ctx* c);  // free the ensemble buffers (called by sr_destroy)
+// The ensemble of one image on device buffers, queued on s: the arguments are the caller's to have checked (sr_ensemble_check).  The
+// context's device is current.
+int sr_ensemble_check(const sr_ctx* c, unsigned members, int h, int w);
+int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int h, int w, void* d_out, bool out_u8, unsigned members,
+                      hipStream_t s);
 
 // ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)
 // One crop of a step, as the crop kernel reads it: px is device memory, 4-byte aligned when ch = 4 (rows are then read as whole pixels).

@@ -43,9 +43,10 @@ int check_pair_args(sr_ctx* c, const void* lr, bool u8, int lr_ch, const void* h
 }
 
 // Pool (or, with lr, a paired call's LR image in its place), network, loss on device buffers, queued on s; the sum lands at d_result
-// (nullptr: the slot behind the partials, for the host-pointer calls).  The context's device is current.
+// (nullptr: the slot behind the partials, for the host-pointer calls).  members: 0 = the network's output as it is, else the mask of a
+// self-ensemble (sr_ensemble.cpp) whose output takes its place.  The context's device is current.
 int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w, bool linear, void* d_result, hipStream_t s,
-                   const sr_lr_input* lr) {
+                   const sr_lr_input* lr, unsigned members = 0) {
     const int f = c->factor, OH = h / f, OW = w / f, HC = f * OH, WC = f * OW;
     const int grid = sr_valid_loss_grid(HC, WC);
     const size_t lr_bytes = (size_t)OH * OW * 3 * sizeof(float), out_bytes = (size_t)HC * WC * 3 * sizeof(float);
@@ -62,7 +63,8 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
     if (!d_result) d_result = (double*)c->d_vpart + grid;
     if (lr) HIPCHK(c, sr_queue_lr_input(*lr, (long)OH * OW, (float*)c->d_vlr, c->d_vtab, s));
     else HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, OH, OW, (float*)c->d_vlr, c->d_vtab + 256, s));  // (SrgbToLinear of the bytes)
-    rc = sr_run_stack_auto(c, c->d_vlr, false, 3, 1, OH, OW, 0, 0, c->d_vout, false, s);
+    if (members) rc = sr_ensemble_queue(c, c->d_vlr, false, 3, OH, OW, c->d_vout, false, members, s);
+    else rc = sr_run_stack_auto(c, c->d_vlr, false, 3, 1, OH, OW, 0, 0, c->d_vout, false, s);
     if (rc != SR_OK) return rc;
     HIPCHK(c, sr_launch_valid_loss((const float*)c->d_vout, d_hr, hr_u8, ch, linear, w, HC, WC, c->d_vtab, (double*)c->d_vpart, d_result, s));
     c->vnode_h = OH; c->vnode_w = OW;
@@ -72,11 +74,14 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
 // The host-pointer calls: upload, run, download 8 bytes, on the context's own stream; synchronous.  In the split-half mode a value that
 // left its domain makes the whole call run again in exact f32, as the host-pointer upscale calls do (include/srhip.h sr_set_precision).
 // lr: nullptr = the pooled form, h x w the HR size; else (pair) h x w is the LR size and lr_ch its channel count.
+// ensemble: `members` is a self-ensemble's mask (checked here), else it is not looked at.
 int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool hr_u8, int ch, int h, int w, int linear, double* err_sum,
-                    size_t* n_elems, bool pair) {
+                    size_t* n_elems, bool pair, bool ensemble = false, unsigned members = 0) {
     sr_plan_clear(c);
     int rc = pair ? check_pair_args(c, lr, hr_u8, lr_ch, hr, ch, h, w) : check_args(c, hr, hr_u8, ch, h, w);
+    if (rc == SR_OK && ensemble) rc = sr_ensemble_check(c, members, pair ? h : h / c->factor, pair ? w : w / c->factor);
     if (rc != SR_OK) return rc;
+    if (!ensemble) members = 0;
     if (!err_sum || !n_elems) return SR_E_INVALID;
     const int lh = h, lw = w;
     const size_t lr_bytes = pair ? (size_t)h * w * (hr_u8 ? (size_t)lr_ch : 3 * sizeof(float)) : 0;
@@ -102,7 +107,7 @@ int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool h
     sr_lr_input in;
     in.d_lr = (char*)c->d_vhr + sr_round256(hr_bytes); in.u8 = hr_u8; in.ch = lr_ch;
     if (pair) HIPCHK(c, hipMemcpyAsync((void*)in.d_lr, lr, lr_bytes, hipMemcpyHostToDevice, s));
-    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr);
+    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr, members);
     double sum = 0.0;
     const hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(&sum, (double*)c->d_vpart + grid, sizeof sum, hipMemcpyDeviceToHost, s) : hipSuccess;
     if (profiled && e1 == hipSuccess && rc == SR_OK) profiled = hipEventRecord(c->ev[7], s) == hipSuccess;
@@ -113,7 +118,7 @@ int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool h
     if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
         *(volatile int*)c->h_domain = 0;
         (void)sr_set_precision(c, SR_PRECISION_F32);
-        rc = validation_host(c, lr, lr_ch, hr, hr_u8, ch, pair ? lh : h, pair ? lw : w, linear, err_sum, n_elems, pair);
+        rc = validation_host(c, lr, lr_ch, hr, hr_u8, ch, pair ? lh : h, pair ? lw : w, linear, err_sum, n_elems, pair, ensemble, members);
         (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
         ++c->domain_fallbacks;
         return rc;
@@ -183,6 +188,16 @@ int sr_pair_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int lr_ch
     sr_lr_input in;
     in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
     return run_validation(c, d_hr, true, hr_channels, c->factor * lh, c->factor * lw, linear_loss != 0, d_err_sum, (hipStream_t)stream, &in);
+}
+
+int sr_pool_validation_error_ensemble_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, unsigned members,
+                                       double* err_sum, size_t* n_elems) {
+    return validation_host(c, nullptr, 3, hr, true, in_channels, h, w, linear_loss, err_sum, n_elems, false, true, members);
+}
+
+int sr_pair_validation_error_ensemble_rgba8(sr_ctx* c, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
+                                            int linear_loss, unsigned members, double* err_sum, size_t* n_elems) {
+    return validation_host(c, lr, lr_channels, hr, true, hr_channels, lh, lw, linear_loss, err_sum, n_elems, true, true, members);
 }
 
 int sr_read_validation_nodes(sr_ctx* c, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out) {

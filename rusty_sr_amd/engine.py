@@ -127,6 +127,50 @@ class Engine:
         _lib.check(self._L.sr_upscale_rgba8(self._ctx, px.ctypes.data_as(u8p), c, n, h, w, out.ctypes.data_as(u8p)), self._ctx)
         return out[0] if squeeze else out
 
+    # ---- self-ensemble: the network averaged over the flips and rotations `members` names (include/srhip.h sr_upscale_ensemble_*) ----
+    @staticmethod
+    def _members(members) -> int:
+        """The mask as the unsigned the ABI takes; what does not fit one (negative, huge) is refused here as the library would."""
+        m = int(members)
+        if m < 0 or m > 0xFFFFFFFF:
+            raise _lib.SrError(_lib.SR_E_INVALID, f"members {members}")
+        return m
+
+    def upscale_ensemble_f32(self, x: np.ndarray, members: int = _lib.SR_ENSEMBLE_ALL) -> np.ndarray:
+        """upscale_f32 averaged over the members of the mask (bit k: flip / rotation k; 0xFF all 8, 0x0F the 4 flips, 0x03 identity and
+        the column flip): (n,H,W,3) or (H,W,3) f32 -> (n,fH,fW,3) f32."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        squeeze = x.ndim == 3
+        if squeeze:
+            x = x[None]
+        n, h, w, c = x.shape
+        if c != 3:
+            raise ValueError("expected 3 channels")
+        out = np.empty((n, self.factor * h, self.factor * w, 3), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._L.sr_upscale_ensemble_f32(self._ctx, x.ctypes.data_as(fp), n, h, w, out.ctypes.data_as(fp), self._members(members)),
+                   self._ctx)
+        return out[0] if squeeze else out
+
+    def upscale_ensemble_rgba8(self, px: np.ndarray, members: int = _lib.SR_ENSEMBLE_ALL, out: np.ndarray = None) -> np.ndarray:
+        """upscale_rgba8 averaged over the members of the mask, quantised once at the end: (n,H,W,3|4) or (H,W,3|4) u8 -> (n,fH,fW,4) u8."""
+        px = np.ascontiguousarray(px, dtype=np.uint8)
+        squeeze = px.ndim == 3
+        if squeeze:
+            px = px[None]
+        n, h, w, c = px.shape
+        oh, ow = self.factor * h, self.factor * w
+        if out is None:
+            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
+        else:
+            out = out.reshape(n, oh, ow, 4)
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_upscale_ensemble_rgba8(self._ctx, px.ctypes.data_as(u8p), c, n, h, w, out.ctypes.data_as(u8p),
+                                                     self._members(members)), self._ctx)
+        return out[0] if squeeze else out
+
     def reserve(self, n: int, h: int, w: int, io: str = "rgba8", channels: int = 3):
         """Allocate and warm everything upscale_rgba8 / upscale_f32 of that shape needs (sr_reserve_*): optional."""
         if io == "rgba8":
@@ -163,6 +207,26 @@ class Engine:
             out = torch.empty((n,) + self._out_hw(h, w) + (4,), dtype=torch.uint8, device=px.device)
         _lib.check(self._L.sr_upscale_rgba8_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w,
                                                 C.c_void_p(out.data_ptr()), self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
+    def upscale_ensemble_f32_dev(self, x, members: int = _lib.SR_ENSEMBLE_ALL, out=None, stream=None):
+        import torch
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
+        n, h, w, _ = x.shape
+        if out is None:
+            out = torch.empty((n, self.factor * h, self.factor * w, 3), dtype=torch.float32, device=x.device)
+        _lib.check(self._L.sr_upscale_ensemble_f32_dev(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
+                                                       self._members(members), self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def upscale_ensemble_rgba8_dev(self, px, members: int = _lib.SR_ENSEMBLE_ALL, out=None, stream=None):
+        import torch
+        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4
+        n, h, w, c = px.shape
+        if out is None:
+            out = torch.empty((n, self.factor * h, self.factor * w, 4), dtype=torch.uint8, device=px.device)
+        _lib.check(self._L.sr_upscale_ensemble_rgba8_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w, C.c_void_p(out.data_ptr()),
+                                                         self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
     def upscale_band_f32_dev(self, x_ext, halo_top, halo_bot, out=None, stream=None):
@@ -243,16 +307,23 @@ class Engine:
         return out
 
     # ---- validation: the forward half of the training graph (reference main.rs:220-247, network.rs:88-102) ----
-    def validation_error(self, hr: np.ndarray, linear_loss: bool = False):
+    def validation_error(self, hr: np.ndarray, linear_loss: bool = False, members=None):
         """HR image (H,W,3|4) u8 (img_to_data: byte / 255, alpha dropped) or (H,W,3) f32 -> (err_sum, n_elems): the squared error of
         sr_net(f)(LinearToSrgb(mean_fxf(SrgbToLinear(hr)))) against hr (of SrgbToLinear of both with linear_loss) over the top-left
-        f*(H//f) x f*(W//f) crop, and the number of elements compared (sr_validation_error_*)."""
+        f*(H//f) x f*(W//f) crop, and the number of elements compared (sr_validation_error_*).  members: None, or the mask of a
+        self-ensemble whose output is scored in the network's place (u8 images only; sr_pool_validation_error_ensemble_rgba8)."""
         hr = np.asarray(hr)
         if hr.ndim != 3:
             raise ValueError("expected one (H, W, C) image")
         h, w, c = hr.shape
         err, n = C.c_double(), C.c_size_t()
-        if hr.dtype == np.uint8:
+        if members is not None:
+            if hr.dtype != np.uint8:
+                raise ValueError("the ensemble form takes u8 pixels")
+            hr = np.ascontiguousarray(hr)
+            st = self._L.sr_pool_validation_error_ensemble_rgba8(self._ctx, hr.ctypes.data_as(C.POINTER(C.c_uint8)), c, h, w, int(bool(linear_loss)),
+                                                            self._members(members), C.byref(err), C.byref(n))
+        elif hr.dtype == np.uint8:
             hr = np.ascontiguousarray(hr)
             st = self._L.sr_validation_error_rgba8(self._ctx, hr.ctypes.data_as(C.POINTER(C.c_uint8)), c, h, w, int(bool(linear_loss)),
                                                    C.byref(err), C.byref(n))
@@ -288,9 +359,10 @@ class Engine:
             raise _lib.SrError(_lib.SR_E_INVALID, f"HR {tuple(hr_shape)} is not {f} x LR {tuple(lr_shape)}")
         return lh, lw
 
-    def validation_error_pair(self, lr: np.ndarray, hr: np.ndarray, linear_loss: bool = False):
+    def validation_error_pair(self, lr: np.ndarray, hr: np.ndarray, linear_loss: bool = False, members=None):
         """LR image (lh,lw,3|4) and HR image (f*lh,f*lw,3|4), both u8 (byte / 255, alpha dropped) or both (.,.,3) f32 ->
-        (err_sum, n_elems): the squared error of sr_net(f)(lr) against hr (sr_pair_validation_error_*)."""
+        (err_sum, n_elems): the squared error of sr_net(f)(lr) against hr (sr_pair_validation_error_*).  members: None, or the mask of a
+        self-ensemble whose output is scored in the network's place (u8 pairs only; sr_pair_validation_error_ensemble_rgba8)."""
         lr, hr = np.asarray(lr), np.asarray(hr)
         if lr.ndim != 3 or hr.ndim != 3:
             raise ValueError("expected one (H, W, C) image each")
@@ -299,7 +371,14 @@ class Engine:
         lh, lw = self._pair_shapes(lr.shape, hr.shape)
         err, n = C.c_double(), C.c_size_t()
         lr, hr = np.ascontiguousarray(lr), np.ascontiguousarray(hr)
-        if hr.dtype == np.uint8:
+        if members is not None:
+            if hr.dtype != np.uint8:
+                raise ValueError("the ensemble form takes u8 pixels")
+            u8p = C.POINTER(C.c_uint8)
+            st = self._L.sr_pair_validation_error_ensemble_rgba8(self._ctx, lr.ctypes.data_as(u8p), lr.shape[2], hr.ctypes.data_as(u8p),
+                                                                 hr.shape[2], lh, lw, int(bool(linear_loss)), self._members(members),
+                                                                 C.byref(err), C.byref(n))
+        elif hr.dtype == np.uint8:
             u8p = C.POINTER(C.c_uint8)
             st = self._L.sr_pair_validation_error_rgba8(self._ctx, lr.ctypes.data_as(u8p), lr.shape[2], hr.ctypes.data_as(u8p), hr.shape[2],
                                                         lh, lw, int(bool(linear_loss)), C.byref(err), C.byref(n))
@@ -631,11 +710,11 @@ def upscale_sharded_all(engines, bands, outs=None):
     return outs
 
 
-def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None) -> float:
+def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None, members=None) -> float:
     """The reference's validation PSNR (main.rs:236-246) of a set of HR images: -10 log10(sum err_i / sum n_i).  Images are dealt
     round-robin over the engines (one host thread each); the sums are taken in image order, so the value does not depend on how many
     engines there are.  A zero error is +inf.  lr_images: the LR partner of each image -- the set is then scored as pairs
-    (validation_error_pair) instead of by pooling."""
+    (validation_error_pair) instead of by pooling.  members: None, or the mask of a self-ensemble that is scored in the network's place."""
     import math
     from concurrent.futures import ThreadPoolExecutor
     if isinstance(engines, Engine):
@@ -648,13 +727,14 @@ def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None) 
         if len(lr_images) != len(images):
             raise ValueError("validation_psnr needs one LR image per HR image")
     res = [None] * len(images)
+    kw = {} if members is None else {"members": members}
 
     def run(k):
         for i in range(k, len(images), len(engines)):
             if lr_images is None:
-                res[i] = engines[k].validation_error(images[i], linear_loss)
+                res[i] = engines[k].validation_error(images[i], linear_loss, **kw)
             else:
-                res[i] = engines[k].validation_error_pair(lr_images[i], images[i], linear_loss)
+                res[i] = engines[k].validation_error_pair(lr_images[i], images[i], linear_loss, **kw)
 
     with ThreadPoolExecutor(max_workers=len(engines)) as pool:
         for fut in [pool.submit(run, k) for k in range(len(engines))]:

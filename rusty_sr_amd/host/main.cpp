@@ -12,7 +12,8 @@
 // Differences from the reference, all outside the hot path: own codecs (PNG over zlib, baseline + progressive JPEG, GIF,
 // TIFF, TGA, ICO, PPM/PGM/PBM, BMP in; PNG, JPEG, BMP, PPM out by extension -- of what the reference's `image` crate reads
 // only WebP is missing), and extra options that cannot collide with the reference's: --device N, --precision f32|split_f16,
-// --timing; for `train` --seed N (initial parameters, shuffles and crops are seeded; the reference's are random) and --steps N (stop
+// --timing, --ensemble 2|4|8 (upscale and validate: the network averaged over flips / rotations); for `train` --seed N (initial
+// parameters, shuffles and crops are seeded; the reference's are random) and --steps N (stop
 // early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
 // writes it after step 1 and every 100 steps).
 #include <cstdio>
@@ -59,7 +60,9 @@ const char* kUsage =
     "                                     imagenetlinear, anime, bilinear]\n"
     "        --device <N>                 HIP device index [default: 0]\n"
     "        --devices <N,N,...>          spread one image over several GPUs (row shares, halo rows from the image)\n"
-    "        --precision <MODE>           f32 (exact) or split_f16 (2x faster, same 1e-4 parity bar) [default: f32]\n\n"
+    "        --precision <MODE>           f32 (exact) or split_f16 (2x faster, same 1e-4 parity bar) [default: f32]\n"
+    "        --ensemble <N>               average the network over N flips / rotations of the image: 2 (mirror), 4 (flips)\n"
+    "                                     or 8 (flips and rotations); N passes for slightly better pixels\n\n"
     "ARGS:\n    <INPUT_FILE>     Sets the input image to upscale\n    <OUTPUT_FILE>    Sets the output file to write/overwrite (.png recommended)\n\n"
     "SUBCOMMANDS:\n    train       Trains a new set of neural network parameters on the GPU (rusty_sr train --help)\n"
     "    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
@@ -78,13 +81,15 @@ const char* kValidateUsage =
     "        --lr_folder <DIR>            Score LR / HR pairs: the network's input is the file of DIR with the same relative\n"
     "                                     path (extension ignored), exactly 1/f the size, instead of the pooled HR image\n"
     "        --devices <N,N,...>          HIP devices; images are dealt round-robin [default: 0]\n"
-    "        --precision <MODE>           f32 (exact) or split_f16 [default: f32]\n\n"
+    "        --precision <MODE>           f32 (exact) or split_f16 [default: f32]\n"
+    "        --ensemble <N>               score the network averaged over N flips / rotations of its input [values: 2, 4, 8]\n\n"
     "ARGS:\n    <VALIDATION_FOLDER>    Images from this folder (or sub-folders with -r) are scored, in path order\n";
 
 [[noreturn]] void die(const std::string& msg, int code = 1) {
     fprintf(stderr, "error: %s\n", msg.c_str());
     exit(code);
 }
+
 [[noreturn]] void usage_error(const std::string& msg) {
     fprintf(stderr, "error: %s\n\nUSAGE:\n    rusty_sr [FLAGS] [OPTIONS] <INPUT_FILE> <OUTPUT_FILE>\n\nFor more information try --help\n", msg.c_str());
     exit(2);
@@ -101,6 +106,11 @@ std::vector<float> decode_rsr(const unsigned char* blob, size_t len) {
 [[noreturn]] void validate_usage_error(const std::string& msg) {
     fprintf(stderr, "error: %s\n\nUSAGE:\n    rusty_sr validate [FLAGS] [OPTIONS] <VALIDATION_FOLDER>\n\nFor more information try --help\n", msg.c_str());
     exit(2);
+}
+
+// --ensemble 2|4|8 -> the member mask of sr_upscale_ensemble_* (0: not a valid value)
+unsigned ensemble_mask(const std::string& v) {
+    return v == "2" ? SR_ENSEMBLE_HFLIP : v == "4" ? SR_ENSEMBLE_FLIPS : v == "8" ? SR_ENSEMBLE_ALL : 0u;
 }
 
 // Rust's `{}` of an f32: the shortest digits that read back as the same float, never an exponent; inf / NaN as Rust spells them
@@ -252,6 +262,7 @@ int run_validate(int argc, char** argv) {
     std::string parameters, custom, precision = "f32", folder, lr_folder;
     bool has_p = false, has_c = false, linear = false, recurse = false, timing = false, has_folder = false, has_lr = false;
     long val_max = -1;
+    unsigned ensemble = 0;  // 0: the plain validation pass
     std::vector<int> devices;
     for (int k = 2; k < argc; ++k) {
         const std::string a = argv[k];
@@ -287,6 +298,10 @@ int run_validate(int argc, char** argv) {
         }
         else if (a == "--precision") precision = value("--precision <MODE>");
         else if (a == "--lr_folder") { lr_folder = value("--lr_folder <DIR>"); has_lr = true; }
+        else if (a == "--ensemble") {
+            const std::string v = value("--ensemble <N>");
+            if (!(ensemble = ensemble_mask(v))) validate_usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
+        }
         else if (a.size() > 1 && a[0] == '-') validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (has_folder) validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else { folder = a; has_folder = true; }
@@ -296,6 +311,8 @@ int run_validate(int argc, char** argv) {
     if (has_c && has_p) validate_usage_error("The argument '--custom <PARAMETER_FILE>' cannot be used with '--parameters <PARAMETERS>'");
     if (!has_folder) validate_usage_error("The following required arguments were not provided:\n    <VALIDATION_FOLDER>");
     if (precision != "f32" && precision != "split_f16") validate_usage_error("'" + precision + "' isn't a valid value for '--precision <MODE>'");
+    if (ensemble && devices.size() > 1)
+        validate_usage_error("The argument '--ensemble <N>' cannot be used with more than one device: the ensemble has no multi-GPU form");
     if (devices.empty()) devices.push_back(0);
 
     // ---- the files: decodable extensions, sorted by path bytes, the first N with -m
@@ -391,9 +408,16 @@ int run_validate(int argc, char** argv) {
                         std::lock_guard<std::mutex> lk(mu);  // (a mismatch ends the run from here: one thread at a time)
                         check_pair_sizes(files[i], img, lr_files[i], lr, factor);
                     }
-                    const int r = has_lr ? sr_pair_validation_error_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
-                                                                          &err[i], &cnt[i])
-                                         : sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
+                    int r;
+                    if (ensemble)
+                        r = has_lr ? sr_pair_validation_error_ensemble_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
+                                                                             ensemble, &err[i], &cnt[i])
+                                   : sr_pool_validation_error_ensemble_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble,
+                                                                        &err[i], &cnt[i]);
+                    else
+                        r = has_lr ? sr_pair_validation_error_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
+                                                                    &err[i], &cnt[i])
+                                   : sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
                     if (r == SR_OK && timing) { double tot = 0; sr_last_timing(ctxs[k], &tot, nullptr, nullptr, nullptr); gpu_ms[i] = tot; }
                     if (r != SR_OK) {
                         std::lock_guard<std::mutex> lk(mu);
@@ -800,6 +824,7 @@ int main(int argc, char** argv) {
     std::string parameters, custom, precision = "f32";
     bool has_p = false, has_c = false, downsample = false, timing = false;
     int device = 0;
+    unsigned ensemble = 0;  // 0: one pass of the network
     std::vector<int> devices;
     if (argc >= 2 && !strcmp(argv[1], "train")) return run_train(argc, argv);  // main.rs:119-121
     if (argc >= 2 && !strcmp(argv[1], "validate")) return run_validate(argc, argv);
@@ -828,6 +853,10 @@ int main(int argc, char** argv) {
             }
         }
         else if (a == "--precision") precision = value("--precision <MODE>");
+        else if (a == "--ensemble") {
+            const std::string v = value("--ensemble <N>");
+            if (!(ensemble = ensemble_mask(v))) usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
+        }
         else if (a.size() > 1 && a[0] == '-') usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
     }
@@ -839,6 +868,12 @@ int main(int argc, char** argv) {
     if (pos.size() < 2) usage_error("The following required arguments were not provided:\n    <INPUT_FILE>\n    <OUTPUT_FILE>");
     if (pos.size() > 2) usage_error("Found argument '" + pos[2] + "' which wasn't expected, or isn't valid in this context");
     if (precision != "f32" && precision != "split_f16") usage_error("'" + precision + "' isn't a valid value for '--precision <MODE>'");
+    // the ensemble averages the NETWORK over flips and rotations: the parameter-free graphs commute with them, and it has no multi-GPU form
+    if (ensemble && has_p && parameters == "bilinear")
+        usage_error("The argument '--ensemble <N>' cannot be used with '--parameters bilinear': bilinear interpolation has no network to average");
+    if (ensemble && downsample) usage_error("The argument '--ensemble <N>' cannot be used with '--downsample': there is no network to average");
+    if (ensemble && devices.size() > 1)
+        usage_error("The argument '--ensemble <N>' cannot be used with more than one device: the ensemble has no multi-GPU form");
 
     // ---- parameters + graph (main.rs:133-158), same progress text
     std::vector<float> params;
@@ -911,6 +946,7 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < devices.size() && rc == SR_OK; ++k) {
         rc = sr_create_graph(&ctxs[k], graph, params.empty() ? nullptr : params.data(), params.size(), SR_FACTOR, devices[k]);
         if (rc == SR_OK && graph == SR_GRAPH_SR_NET) rc = sr_set_precision(ctxs[k], precision == "f32" ? SR_PRECISION_F32 : SR_PRECISION_SPLIT_F16);
+        if (rc == SR_OK && ensemble && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble call times itself only when asked to)
     }
     const double t_create = ms_since(t_start);
     double t_prep = 0;
@@ -938,14 +974,16 @@ int main(int argc, char** argv) {
     // img_to_data + graph.forward + data_to_img(..).to_rgba(), fused on the device (main.rs:168-175)
     const double t_alloc = ms_since(t_al);
     const clk::time_point t_up = clk::now();
-    rc = ctxs.size() > 1 ? sr_upscale_rgba8_multi(ctxs.data(), (int)ctxs.size(), in.rgba.data(), 4, in.h, in.w, out)
-                         : sr_upscale_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out);
+    rc = ensemble ? sr_upscale_ensemble_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out, ensemble)
+         : ctxs.size() > 1 ? sr_upscale_rgba8_multi(ctxs.data(), (int)ctxs.size(), in.rgba.data(), 4, in.h, in.w, out)
+                           : sr_upscale_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out);
     if (rc != SR_OK) die(std::string(sr_strerror(rc)) + (rc == SR_E_HIP ? " (hipError " + std::to_string(sr_last_hip_error(ctx)) + ")" : ""));
     const double t_upscale = ms_since(t_up);
     if (timing) {
         double tot = 0, h2d = 0, d2h = 0;
         sr_last_timing(ctx, &tot, nullptr, &h2d, &d2h);
-        fprintf(stderr, "\n[timing] %dx%d -> %dx%d: kernels %.3f ms, h2d %.3f ms, d2h %.3f ms\n", in.w, in.h, ow, oh, tot, h2d, d2h);
+        fprintf(stderr, "\n[timing] %dx%d -> %dx%d%s: kernels %.3f ms, h2d %.3f ms, d2h %.3f ms\n", in.w, in.h, ow, oh,
+                ensemble ? (" (ensemble of " + std::to_string(__builtin_popcount(ensemble)) + ")").c_str() : "", tot, h2d, d2h);
     }
     printf(" Writing file...");
     fflush(stdout);
