@@ -378,6 +378,19 @@ int sr_train_create(sr_train** out, sr_ctx* ctx, const float* start_params, size
 /* Upload an image into the store: *id >= 0 when it is resident from now on, -1 when the store has no room (the image stays the caller's). */
 int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, int w, int* id);
 int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, int crop_w);
+/* Augmented steps: sr_train_step / sr_train_step_pairs with a member k (0..7) per item, members[i] for items[i]; members == NULL means
+ * all 0, and that is what the two plain calls are.  T_k is the self-ensemble's (below): swap the two spatial axes if k & 4, then reverse
+ * the rows if k & 2, then the columns if k & 1.  The batch keeps its shape n x crop_h x crop_w x 3: item i of it is T_k(W), W the source
+ * window at (y0, x0) -- crop_h x crop_w pixels for k < 4, crop_w x crop_h (rows x columns) for k >= 4 -- cut exactly as the plain
+ * call cuts it: alpha dropped, zero outside the image, origins that may be negative or overhang.  k = 0 is the plain call's crop, by the
+ * plain call's code.  For pairs, windows and origins are in LR pixels: the LR item is T_k of the LR window (crop_lh x crop_lw, or
+ * crop_lw x crop_lh), the HR item T_k of the f x as large HR window at (f y0, f x0); T_k maps f x f blocks onto f x f blocks, so the two
+ * stay aligned, and the LR item still goes through the byte / 255 table straight into the backward pass's input (no pool launch, no
+ * conversion launch).  The transform is part of the gather: no extra launch, memory or host work.  A step equals sr_backprop_rgba8_dev
+ * (sr_pair_backprop_rgba8_dev) + sr_adam_step_dev on the transformed crops, bit for bit.  A member above 7 is SR_E_INVALID before any
+ * launch, with the other item checks.  A transient item stages the rows its window can reach (crop_w of them for k >= 4, f x as many HR
+ * rows for a pair).  The ring, drain, staging and SR_E_NOMEM rules are those of sr_train_step. */
+int sr_train_step_aug(sr_train* t, const sr_train_crop* items, const uint8_t* members, int n, int crop_h, int crop_w);
 /* Waits for every queued step; err_sums receives the err_sum of each step since the last sync (at the parameters before that step), in
  * step order, at most cap of them; *n_steps their number.  err_sums may be NULL. */
 int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps);
@@ -436,6 +449,7 @@ typedef struct {
 } sr_train_pair_crop;
 int sr_train_add_pair(sr_train* t, const uint8_t* lr_px, int lr_channels, const uint8_t* hr_px, int hr_channels, int lh, int lw, int* id);
 int sr_train_step_pairs(sr_train* t, const sr_train_pair_crop* items, int n, int crop_lh, int crop_lw);
+int sr_train_step_pairs_aug(sr_train* t, const sr_train_pair_crop* items, const uint8_t* members, int n, int crop_lh, int crop_lw);  /* (above) */
 
 /* ---- Self-ensemble: the network averaged over flips and rotations of the image ----
  * The reference has no counterpart (main.rs:171 runs graph.forward once); other super-resolution tools call it geometric self-ensemble or

@@ -130,6 +130,7 @@ extern "C" {
     pub fn sr_train_create(out: *mut *mut SrTrain, ctx: *mut SrCtx, start_params: *const f32, n_params: usize, linear_loss: c_int, l2: f32, lr: f32, beta1: f32, beta2: f32, eps: f32, store_bytes: usize) -> c_int;
     pub fn sr_train_add_image(t: *mut SrTrain, px: *const u8, in_channels: c_int, h: c_int, w: c_int, id: *mut c_int) -> c_int;
     pub fn sr_train_step(t: *mut SrTrain, items: *const SrTrainCrop, n: c_int, crop_h: c_int, crop_w: c_int) -> c_int;
+    pub fn sr_train_step_aug(t: *mut SrTrain, items: *const SrTrainCrop, members: *const u8, n: c_int, crop_h: c_int, crop_w: c_int) -> c_int;
     pub fn sr_train_sync(t: *mut SrTrain, err_sums: *mut f64, cap: usize, n_steps: *mut usize) -> c_int;
     pub fn sr_train_params(t: *mut SrTrain, out: *mut f32, cap: usize) -> c_int;
     pub fn sr_train_destroy(t: *mut SrTrain);
@@ -141,6 +142,7 @@ extern "C" {
     pub fn sr_pair_backprop_rgba8_dev(ctx: *mut SrCtx, d_params: *const f32, d_lr: *const u8, lr_channels: c_int, d_hr: *const u8, hr_channels: c_int, n: c_int, lh: c_int, lw: c_int, linear_loss: c_int, loss_scale: f32, l2: f32, d_err_sum: *mut f64, d_grad: *mut f32, stream: *mut c_void) -> c_int;
     pub fn sr_train_add_pair(t: *mut SrTrain, lr_px: *const u8, lr_channels: c_int, hr_px: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, id: *mut c_int) -> c_int;
     pub fn sr_train_step_pairs(t: *mut SrTrain, items: *const SrTrainPairCrop, n: c_int, crop_lh: c_int, crop_lw: c_int) -> c_int;
+    pub fn sr_train_step_pairs_aug(t: *mut SrTrain, items: *const SrTrainPairCrop, members: *const u8, n: c_int, crop_lh: c_int, crop_lw: c_int) -> c_int;
     pub fn sr_upscale_ensemble_f32_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut f32, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_ensemble_rgba8_dev(ctx: *mut SrCtx, d_in: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_ensemble_f32(ctx: *mut SrCtx, input: *const f32, n: c_int, h: c_int, w: c_int, out: *mut f32, members: c_uint) -> c_int;

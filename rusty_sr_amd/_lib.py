@@ -94,6 +94,7 @@ SYMBOLS = {
     "sr_train_create": (_i, [C.POINTER(_vp), _vp, _fp, _sz, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _sz]),
     "sr_train_add_image": (_i, [_vp, _u8p, _i, _i, _i, C.POINTER(_i)]),
     "sr_train_step": (_i, [_vp, C.POINTER(TrainCrop), _i, _i, _i]),
+    "sr_train_step_aug": (_i, [_vp, C.POINTER(TrainCrop), _u8p, _i, _i, _i]),
     "sr_train_sync": (_i, [_vp, _dp, _sz, C.POINTER(_sz)]),
     "sr_train_params": (_i, [_vp, _fp, _sz]),
     "sr_train_destroy": (None, [_vp]),
@@ -105,6 +106,7 @@ SYMBOLS = {
     "sr_pair_backprop_rgba8_dev": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
     "sr_train_add_pair": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, C.POINTER(_i)]),
     "sr_train_step_pairs": (_i, [_vp, C.POINTER(TrainPairCrop), _i, _i, _i]),
+    "sr_train_step_pairs_aug": (_i, [_vp, C.POINTER(TrainPairCrop), _u8p, _i, _i, _i]),
     "sr_upscale_ensemble_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, C.c_uint, _vp]),
     "sr_upscale_ensemble_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_uint, _vp]),
     "sr_upscale_ensemble_f32": (_i, [_vp, _fp, _i, _i, _i, _fp, C.c_uint]),

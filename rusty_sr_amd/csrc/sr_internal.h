@@ -337,9 +337,11 @@ int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
 
 // ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)
 // One crop of a step, as the crop kernel reads it: px is device memory, 4-byte aligned when ch = 4 (rows are then read as whole pixels).
+// k: the item's member (0..7, include/srhip.h sr_train_step_aug); the source window at (y0, x0) is crop_w x crop_h when k & 4.
 struct sr_train_crop_desc {
     const uint8_t* px;
     int ch, h, w, y0, x0;
+    int k;
 };
 struct sr_train_crop_args {  // passed by value: a step whose images are resident uploads nothing
     sr_train_crop_desc d[SR_TRAIN_MAX_BATCH];
@@ -350,8 +352,10 @@ struct sr_train_crop_args {  // passed by value: a step whose images are residen
 struct sr_train_pair_desc {
     const uint8_t* lr;
     const uint8_t* hr;
-    int lr_ch, hr_ch, lh, lw, y0, x0;
+    uint8_t lr_ch, hr_ch, k, pad;  // k: the item's member; (bytes, so that a descriptor stays 40 bytes)
+    int lh, lw, y0, x0;
 };
+static_assert(sizeof(sr_train_pair_desc) == 40 && sizeof(sr_train_crop_desc) == 32, "64 descriptors are one kernel's arguments");
 struct sr_train_pair_args {
     sr_train_pair_desc d[SR_TRAIN_MAX_BATCH];
     int n, crop_lh, crop_lw;

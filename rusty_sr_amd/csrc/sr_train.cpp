@@ -271,19 +271,27 @@ int sr_train_add_image(sr_train* t, const uint8_t* px, int in_channels, int h, i
 }
 
 int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, int crop_w) {
+    return sr_train_step_aug(t, items, nullptr, n, crop_h, crop_w);
+}
+
+int sr_train_step_aug(sr_train* t, const sr_train_crop* items, const uint8_t* members, int n, int crop_h, int crop_w) {
     if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c || !items || n < 1 || n > SR_TRAIN_MAX_BATCH) return SR_E_INVALID;
     sr_ctx* c = t->c;
     if (crop_h < c->factor || crop_w < c->factor) return SR_E_INVALID;
-    // every item is checked before anything is launched; the rows of each transient image that its crop can reach are what is staged
+    // every item is checked before anything is launched; the rows of each transient image that its window can reach are what is staged
+    // (the window of a member that swaps the axes has crop_w rows)
+    auto member = [&](int i) { return members ? (int)members[i] : 0; };
+    auto window_rows = [&](int i) { return member(i) & 4 ? crop_w : crop_h; };
     size_t trans_bytes = 0;
     for (int i = 0; i < n; ++i) {
         const sr_train_crop& it = items[i];
+        if (member(i) > 7) return SR_E_INVALID;
         if (it.image >= 0) {
             if ((size_t)it.image >= t->images.size() || t->images[(size_t)it.image].d_lr) return SR_E_INVALID;  // (a pair is no plain image)
         } else if (it.image == -1) {
             if (!it.px || (it.in_channels != 3 && it.in_channels != 4) || it.h < 1 || it.w < 1) return SR_E_INVALID;
-            const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + crop_h, 0, it.h);
+            const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + window_rows(i), 0, it.h);
             trans_bytes += sr_round256((size_t)(r1 - r0) * it.w * it.in_channels);
         } else {
             return SR_E_INVALID;
@@ -307,11 +315,11 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
     for (int i = 0; i < n; ++i) {
         const sr_train_crop& it = items[i];
         if (it.image != -1) continue;
-        const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + crop_h, 0, it.h);
+        const long r0 = std::clamp<long>(it.y0, 0, it.h), r1 = std::clamp<long>((long)it.y0 + window_rows(i), 0, it.h);
         const size_t row = (size_t)it.w * it.in_channels, bytes = (size_t)(r1 - r0) * row;
         if (bytes) memcpy((char*)t->h_stage[k] + off, it.px + (size_t)r0 * row, bytes);
         // the staged rows as an image of r1 - r0 rows: the crop's rows outside them are outside the source image too
-        a.d[i] = {(const uint8_t*)t->d_trans + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0};
+        a.d[i] = {(const uint8_t*)t->d_trans + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0, member(i)};
         off += sr_round256(bytes);
     }
     rc = upload_stage(t, trans_bytes, k);
@@ -320,7 +328,7 @@ int sr_train_step(sr_train* t, const sr_train_crop* items, int n, int crop_h, in
         const sr_train_crop& it = items[i];
         if (it.image < 0) continue;
         const sr_train::Img& im = t->images[(size_t)it.image];
-        a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0};
+        a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0, member(i)};
     }
     HIPCHK(c, sr_launch_train_crop(a, (uint32_t*)t->d_batch, s));
     return finish_step(t, n, crop_h, crop_w, nullptr);
@@ -358,21 +366,29 @@ int sr_train_add_pair(sr_train* t, const uint8_t* lr_px, int lr_channels, const 
 }
 
 int sr_train_step_pairs(sr_train* t, const sr_train_pair_crop* items, int n, int crop_lh, int crop_lw) {
+    return sr_train_step_pairs_aug(t, items, nullptr, n, crop_lh, crop_lw);
+}
+
+int sr_train_step_pairs_aug(sr_train* t, const sr_train_pair_crop* items, const uint8_t* members, int n, int crop_lh, int crop_lw) {
     if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c || !items || n < 1 || n > SR_TRAIN_MAX_BATCH) return SR_E_INVALID;
     sr_ctx* c = t->c;
     const int f = c->factor;
     if (crop_lh < 1 || crop_lw < 1 || crop_lh > INT32_MAX / f || crop_lw > INT32_MAX / f) return SR_E_INVALID;
-    // every item is checked before anything is launched; of a transient pair, the rows its crops can reach are what is staged
+    // every item is checked before anything is launched; of a transient pair, the rows its windows can reach are what is staged
+    // (the LR window of a member that swaps the axes has crop_lw rows)
+    auto member = [&](int i) { return members ? (int)members[i] : 0; };
+    auto window_rows = [&](int i) { return member(i) & 4 ? crop_lw : crop_lh; };
     size_t trans_bytes = 0;
     for (int i = 0; i < n; ++i) {
         const sr_train_pair_crop& it = items[i];
+        if (member(i) > 7) return SR_E_INVALID;
         if (it.pair >= 0) {
             if ((size_t)it.pair >= t->images.size() || !t->images[(size_t)it.pair].d_lr) return SR_E_INVALID;  // (a plain image is no pair)
         } else if (it.pair == -1) {
             if (!it.lr_px || !it.hr_px || sr_check_pair_args(c, true, it.lr_channels, it.hr_channels, 1, it.lh, it.lw) != SR_OK)
                 return SR_E_INVALID;
-            const long r0 = std::clamp<long>(it.y0, 0, it.lh), r1 = std::clamp<long>((long)it.y0 + crop_lh, 0, it.lh);
+            const long r0 = std::clamp<long>(it.y0, 0, it.lh), r1 = std::clamp<long>((long)it.y0 + window_rows(i), 0, it.lh);
             trans_bytes += sr_round256((size_t)(r1 - r0) * it.lw * it.lr_channels) +
                            sr_round256((size_t)(r1 - r0) * f * it.lw * f * it.hr_channels);
         } else {
@@ -401,18 +417,19 @@ int sr_train_step_pairs(sr_train* t, const sr_train_pair_crop* items, int n, int
         const sr_train_pair_crop& it = items[i];
         if (it.pair >= 0) {
             const sr_train::Img& im = t->images[(size_t)it.pair];
-            a.d[i] = {im.d_lr, im.d, im.lr_ch, im.ch, im.h / f, im.w / f, it.y0, it.x0};
+            a.d[i] = {im.d_lr, im.d, (uint8_t)im.lr_ch, (uint8_t)im.ch, (uint8_t)member(i), 0, im.h / f, im.w / f, it.y0, it.x0};
             continue;
         }
         // the staged rows as a pair of r1 - r0 LR rows: the crops' rows outside them are outside the source images too
-        const long r0 = std::clamp<long>(it.y0, 0, it.lh), r1 = std::clamp<long>((long)it.y0 + crop_lh, 0, it.lh);
+        const long r0 = std::clamp<long>(it.y0, 0, it.lh), r1 = std::clamp<long>((long)it.y0 + window_rows(i), 0, it.lh);
         const size_t lrow = (size_t)it.lw * it.lr_channels, lbytes = (size_t)(r1 - r0) * lrow;
         const size_t hrow = (size_t)f * it.lw * it.hr_channels, hbytes = (size_t)(r1 - r0) * f * hrow;
         if (lbytes) memcpy((char*)t->h_stage[k] + off, it.lr_px + (size_t)r0 * lrow, lbytes);
         const uint8_t* d_lr = (const uint8_t*)t->d_trans + off;
         off += sr_round256(lbytes);
         if (hbytes) memcpy((char*)t->h_stage[k] + off, it.hr_px + (size_t)r0 * f * hrow, hbytes);
-        a.d[i] = {d_lr, (const uint8_t*)t->d_trans + off, it.lr_channels, it.hr_channels, (int)(r1 - r0), it.lw, (int)(it.y0 - r0), it.x0};
+        a.d[i] = {d_lr, (const uint8_t*)t->d_trans + off, (uint8_t)it.lr_channels, (uint8_t)it.hr_channels, (uint8_t)member(i), 0, (int)(r1 - r0), it.lw,
+                  (int)(it.y0 - r0), it.x0};
         off += sr_round256(hbytes);
     }
     rc = upload_stage(t, trans_bytes, k);

@@ -10,6 +10,15 @@
 // arguments), so a step whose images are all resident uploads nothing.  Blocks along y are items, so each block reads its descriptor with
 // scalar loads.
 //
+// Augmented steps (sr_train_step_aug / sr_train_step_pairs_aug): a descriptor carries its item's member k, and blocks along y are items,
+// so the branch on k is uniform within a block.  k = 0 takes the path above, unchanged.  Any other member reads whole pixels: a batch
+// dword lies in two neighbouring pixels (q, q + 1) of one batch row p, pixel (p, q) of T_k(W) is pixel (p', q') or (q', p') of the window
+// W (p' / q': p / q reversed within the crop if k & 2 / k & 1; swapped if k & 4), and a pixel outside the image is 0.  A pixel is one
+// aligned dword (RGBA) or the one or two aligned dwords that hold its three bytes (RGB): nothing outside the words of the image is read.
+// The store is the same whole dword.  Neighbouring lanes read neighbouring pixels of a source row (k < 4, backwards when k & 1) or of a
+// source column (k >= 4): the column reads are not coalesced.  Measured (DESIGN.md 4j "Augmentation"): every member class takes the
+// 4.2 - 4.7 us a call (member 0: 4.4 us), 0.35 % of a step against a budget of 2 %, so the members have no LDS-tile form.
+//
 // A step on LR / HR pairs (sr_train_step_pairs) gathers both crops in one launch, train_pair_crop_kernel: the HR crops as above, and the LR
 // crops -- cut by the same code, a crop of crop_lh x crop_lw at (y0, x0) of the LR image -- converted on the way (byte / 255, the
 // validation pass's table) and stored as 16-byte groups straight into the backward pass's input buffer.  Such a step has no pool launch.
@@ -25,10 +34,25 @@ __device__ __forceinline__ uint32_t word_at(const uint8_t* p) {  // the aligned 
     return *(const uint32_t*)(p - mis) >> (8 * mis);
 }
 
+// pixel (p, q) of T_k(window) of descriptor d (k = d.k, any member), as 0x00bbggrr; 0 outside the source image
+__device__ __forceinline__ uint32_t member_pixel(const sr_train_crop_desc& d, long p, long q, int crop_h, int crop_w) {
+    if (d.k & 2) p = crop_h - 1 - p;
+    if (d.k & 1) q = crop_w - 1 - q;
+    const long sy = (long)d.y0 + ((d.k & 4) ? q : p), sx = (long)d.x0 + ((d.k & 4) ? p : q);
+    if (sy < 0 || sy >= d.h || sx < 0 || sx >= d.w) return 0u;
+    const uint8_t* s = d.px + (sy * d.w + sx) * d.ch;
+    if (d.ch != 3) return *(const uint32_t*)s & 0xffffffu;  // RGBA: 4-byte aligned pixels
+    const uint32_t mis = (uint32_t)(uintptr_t)s & 3u;
+    const uint32_t* w = (const uint32_t*)(s - mis);
+    const uint32_t w0 = w[0], w1 = mis >= 2 ? w[1] : 0u;  // (with mis >= 2, w[1] holds the pixel's last byte: inside the image)
+    return __builtin_amdgcn_alignbyte(w1, w0, mis) & 0xffffffu;
+}
+
 // byte ob (0 .. cb-1) of a crop of descriptor d, crop rows of rowb bytes
-__device__ __forceinline__ uint32_t crop_byte(const sr_train_crop_desc& d, long ob, long rowb) {
+__device__ __forceinline__ uint32_t crop_byte(const sr_train_crop_desc& d, long ob, long rowb, int crop_h, int crop_w) {
     const long y = ob / rowb, r = ob - y * rowb, x = r / 3;
     const int c = (int)(r - x * 3);
+    if (d.k != 0) return (member_pixel(d, y, x, crop_h, crop_w) >> (8 * c)) & 0xffu;
     const long sy = (long)d.y0 + y, sx = (long)d.x0 + x;
     if (sy < 0 || sy >= d.h || sx < 0 || sx >= d.w) return 0u;
     return word_at(d.px + (sy * d.w + sx) * d.ch + c) & 0xffu;
@@ -48,8 +72,8 @@ __device__ __forceinline__ bool crop_dword(Desc&& desc, int n, int b, long t, in
     const long sy = (long)d.y0 + y, x = xb / 3, sx = (long)d.x0 + x;
     const int c = (int)(xb - x * 3);
     uint32_t word;
-    // the four bytes lie in one crop row and in pixels x, x + 1 of the source row sy
-    if (xb + 4 <= rowb && sy >= 0 && sy < d.h && sx >= 0 && sx + 1 < d.w) {
+    // (member 0) the four bytes lie in one crop row and in pixels x, x + 1 of the source row sy
+    if (d.k == 0 && xb + 4 <= rowb && sy >= 0 && sy < d.h && sx >= 0 && sx + 1 < d.w) {
         const uint8_t* p = d.px + (sy * d.w + sx) * d.ch;
         if (d.ch == 3) {
             p += c;
@@ -62,7 +86,10 @@ __device__ __forceinline__ bool crop_dword(Desc&& desc, int n, int b, long t, in
             const uint64_t rgb = (uint64_t)(q[0] & 0xffffffu) | ((uint64_t)(q[1] & 0xffffffu) << 24);
             word = (uint32_t)(rgb >> (8 * c));
         }
-    } else {
+    } else if (d.k != 0 && xb + 4 <= rowb) {  // any other member: the four bytes lie in pixels x, x + 1 of the batch row y
+        const uint64_t rgb = (uint64_t)member_pixel(d, y, x, crop_h, crop_w) | ((uint64_t)member_pixel(d, y, x + 1, crop_h, crop_w) << 24);
+        word = (uint32_t)(rgb >> (8 * c));
+    } else {  // (every member) a dword that touches an image edge or crosses a crop-row end
         word = 0u;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -73,7 +100,7 @@ __device__ __forceinline__ bool crop_dword(Desc&& desc, int n, int b, long t, in
                 bi = b + 1;
                 if (bi >= n) break;
             }
-            word |= crop_byte(desc(bi), ob, rowb) << (8 * j);
+            word |= crop_byte(desc(bi), ob, rowb, crop_h, crop_w) << (8 * j);
         }
     }
     *k_out = k;
@@ -102,7 +129,7 @@ __global__ __launch_bounds__(256) void train_pair_crop_kernel(sr_train_pair_args
     if ((int)blockIdx.x < a.hr_blocks) {
         auto hr = [&](int i) {
             const sr_train_pair_desc& p = a.d[i];
-            return sr_train_crop_desc{p.hr, p.hr_ch, F * p.lh, F * p.lw, F * p.y0, F * p.x0};
+            return sr_train_crop_desc{p.hr, p.hr_ch, F * p.lh, F * p.lw, F * p.y0, F * p.x0, p.k};
         };
         if (crop_dword(hr, a.n, blockIdx.y, (long)blockIdx.x * 256 + threadIdx.x, F * a.crop_lh, F * a.crop_lw, &k, &word)) out[k] = word;
         return;
@@ -112,7 +139,7 @@ __global__ __launch_bounds__(256) void train_pair_crop_kernel(sr_train_pair_args
     __syncthreads();
     auto lr = [&](int i) {
         const sr_train_pair_desc& p = a.d[i];
-        return sr_train_crop_desc{p.lr, p.lr_ch, p.lh, p.lw, p.y0, p.x0};
+        return sr_train_crop_desc{p.lr, p.lr_ch, p.lh, p.lw, p.y0, p.x0, p.k};
     };
     if (!crop_dword(lr, a.n, blockIdx.y, (long)(blockIdx.x - a.hr_blocks) * 256 + threadIdx.x, a.crop_lh, a.crop_lw, &k, &word)) return;
     f32x4 v;

@@ -790,11 +790,24 @@ class Trainer:
         _lib.check(self._L.sr_train_add_image(self._t, px.ctypes.data_as(C.POINTER(C.c_uint8)), c, h, w, C.byref(i)), self.engine._ctx)
         return i.value
 
+    @staticmethod
+    def _members(items):
+        """The member of each item -- its optional fourth element, 0..7 -- as the u8 array the _aug entry points take, or None when no
+        item has one (the plain call)."""
+        if not any(len(it) > 3 for it in items):
+            return None
+        ks = [int(it[3]) if len(it) > 3 else 0 for it in items]
+        if any(k < 0 or k > 7 for k in ks):
+            raise ValueError("a member is one of the 8 flips and rotations, 0..7")
+        return (C.c_uint8 * len(ks))(*ks)
+
     def step_crops(self, items, crop_h: int, crop_w: int) -> None:
-        """One step on crops, queued without waiting.  items: (image, y0, x0) with image an id of add_image or a (h, w, 3|4) u8 array."""
+        """One step on crops, queued without waiting.  items: (image, y0, x0[, member]) with image an id of add_image or a (h, w, 3|4) u8
+        array; member k (0..7, default 0) makes the item T_k of its window (sr_train_step_aug: the window of k >= 4 is crop_w x crop_h)."""
+        members = self._members(items)
         arr = (_lib.TrainCrop * max(len(items), 1))()
         keep = []
-        for k, (img, y0, x0) in enumerate(items):
+        for k, (img, y0, x0) in enumerate(it[:3] for it in items):
             it = arr[k]
             it.y0, it.x0 = int(y0), int(x0)
             if isinstance(img, (int, np.integer)):
@@ -806,7 +819,11 @@ class Trainer:
                 keep.append(px)
                 it.image, it.px = -1, px.ctypes.data
                 it.h, it.w, it.in_channels = px.shape
-        _lib.check(self._L.sr_train_step(self._t, arr, len(items), int(crop_h), int(crop_w)), self.engine._ctx)
+        if members is None:
+            rc = self._L.sr_train_step(self._t, arr, len(items), int(crop_h), int(crop_w))
+        else:
+            rc = self._L.sr_train_step_aug(self._t, arr, members, len(items), int(crop_h), int(crop_w))
+        _lib.check(rc, self.engine._ctx)
         self.steps += 1
         self._pending += 1
 
@@ -823,11 +840,12 @@ class Trainer:
         return i.value
 
     def step_pair_crops(self, items, crop_lh: int, crop_lw: int) -> None:
-        """One step on crops of pairs, queued without waiting.  items: (pair, y0, x0), pair an id of add_pair or an (lr, hr) tuple of u8
-        arrays; y0, x0 and the crop size are in LR pixels."""
+        """One step on crops of pairs, queued without waiting.  items: (pair, y0, x0[, member]), pair an id of add_pair or an (lr, hr)
+        tuple of u8 arrays; y0, x0 and the crop size are in LR pixels; member as in step_crops (sr_train_step_pairs_aug)."""
+        members = self._members(items)
         arr = (_lib.TrainPairCrop * max(len(items), 1))()
         keep = []
-        for k, (pair, y0, x0) in enumerate(items):
+        for k, (pair, y0, x0) in enumerate(it[:3] for it in items):
             it = arr[k]
             it.y0, it.x0 = int(y0), int(x0)
             if isinstance(pair, (int, np.integer)):
@@ -840,7 +858,11 @@ class Trainer:
                 keep += [lr, hr]
                 it.pair, it.lr_px, it.hr_px = -1, lr.ctypes.data, hr.ctypes.data
                 it.lr_channels, it.hr_channels = lr.shape[2], hr.shape[2]
-        _lib.check(self._L.sr_train_step_pairs(self._t, arr, len(items), int(crop_lh), int(crop_lw)), self.engine._ctx)
+        if members is None:
+            rc = self._L.sr_train_step_pairs(self._t, arr, len(items), int(crop_lh), int(crop_lw))
+        else:
+            rc = self._L.sr_train_step_pairs_aug(self._t, arr, members, len(items), int(crop_lh), int(crop_lw))
+        _lib.check(rc, self.engine._ctx)
         self.steps += 1
         self._pending += 1
 

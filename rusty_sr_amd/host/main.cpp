@@ -2,7 +2,7 @@
 // (reference src/main.rs:33-258), driving the MI355X engine through libsrhip's C ABI.
 //
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
-//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] <PARAMETER_FILE> <TRAINING_FOLDER>
+//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] <VALIDATION_FOLDER>
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
@@ -13,7 +13,8 @@
 // TIFF, TGA, ICO, PPM/PGM/PBM, BMP in; PNG, JPEG, BMP, PPM out by extension -- of what the reference's `image` crate reads
 // only WebP is missing), and extra options that cannot collide with the reference's: --device N, --precision f32|split_f16,
 // --timing, --ensemble 2|4|8 (upscale and validate: the network averaged over flips / rotations); for `train` --seed N (initial
-// parameters, shuffles and crops are seeded; the reference's are random) and --steps N (stop
+// parameters, shuffles and crops are seeded; the reference's are random), --augment (each crop under a random one of the 8 flips and
+// rotations, applied by the crop kernel) and --steps N (stop
 // early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
 // writes it after step 1 and every 100 steps).
 #include <cstdio>
@@ -302,6 +303,7 @@ int run_validate(int argc, char** argv) {
             const std::string v = value("--ensemble <N>");
             if (!(ensemble = ensemble_mask(v))) validate_usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
         }
+        else if (a == "--augment") validate_usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a.size() > 1 && a[0] == '-') validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (has_folder) validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else { folder = a; has_folder = true; }
@@ -457,7 +459,8 @@ const char* kTrainUsage =
     "FLAGS:\n    -l, --linearLoss    Apply MSE loss to a linearised RGB output rather than sRGB values\n"
     "    -r, --recurse       Recurse into subfolders of training and validation folders looking for files\n"
     "    -h, --help          Prints help information\n"
-    "        --timing        Print steps/s, the share of resident draws and the decode time on stderr\n\n"
+    "        --timing        Print steps/s, the share of resident draws and the decode time on stderr\n"
+    "        --augment       Cut each crop under a random one of the 8 flips and rotations (the transforms of --ensemble 8)\n\n"
     "OPTIONS:\n    -s, --start <START_PARAMETERS>    Start training from known parameters loaded from this .rsr file; its size\n"
     "                                      selects the factor (2, 3 or 4) [default: random parameters at factor 3]\n"
     "    -v, --val_folder <VAL_FOLDER>     Images from this folder (or sub-folders with -r) are used to report the validation\n"
@@ -481,7 +484,10 @@ const char* kTrainUsage =
     exit(2);
 }
 
-// SplitMix64: the shuffles and crop origins of `train` (the initial parameters use the library's own, sr_init_params)
+// SplitMix64: the shuffles and crop origins of `train` (the initial parameters use the library's own, sr_init_params), one stream
+// seeded with seed ^ 0x5eed5eed5eed5eed.  --augment draws the members from a SECOND stream, seeded with seed ^ 0x6175676d656e7421
+// ("augment!"): one value per draw, in draw order, member = next() >> 61 (its top three bits, uniform over 0..7).  The first stream is
+// the same with and without the flag, so a seed's shuffles and origins are too; without the flag the second stream is never drawn from.
 struct Rng {
     uint64_t s;
     uint64_t next() {
@@ -525,6 +531,7 @@ int run_train(int argc, char** argv) {
     std::string start, val_folder, lr_folder, val_lr_folder;
     std::vector<std::string> pos;
     bool has_s = false, has_v = false, linear = false, recurse = false, timing = false, has_lr = false, has_vlr = false, has_f = false;
+    bool augment = false;
     long factor_arg = SR_FACTOR;
     long val_max = -1, steps = 2500000, device = 0, store = -1;
     uint64_t seed = 0;
@@ -539,6 +546,7 @@ int run_train(int argc, char** argv) {
         else if (a == "-l" || a == "--linearLoss") linear = true;
         else if (a == "-r" || a == "--recurse") recurse = true;
         else if (a == "--timing") timing = true;
+        else if (a == "--augment") augment = true;
         else if (a == "-s" || a == "--start") { start = value("--start <START_PARAMETERS>"); has_s = true; }
         else if (a == "-v" || a == "--val_folder") { val_folder = value("--val_folder <VAL_FOLDER>"); has_v = true; }
         else if (a == "-m" || a == "--val_max") {
@@ -693,9 +701,10 @@ int run_train(int argc, char** argv) {
     constexpr int kBatch = 4, kCropHr = 192;
     const int unit = has_lr ? factor : 1, kCrop = kCropHr / unit;
     Rng rng{seed ^ 0x5eed5eed5eed5eedull};
+    Rng aug_rng{seed ^ 0x6175676d656e7421ull};  // --augment: the members, a stream of their own
     std::vector<size_t> perm;
     size_t perm_pos = 0;
-    struct Draw { size_t file; int y0, x0; };
+    struct Draw { size_t file; int y0, x0; uint8_t member; };
     auto draw = [&]() -> Draw {
         if (perm_pos == perm.size()) {
             perm = usable;
@@ -708,7 +717,8 @@ int run_train(int argc, char** argv) {
         const int h = im.h / unit, w = im.w / unit;
         const int y0 = h > kCrop ? (int)rng.below((uint64_t)(h - kCrop + 1)) : 0;
         const int x0 = w > kCrop ? (int)rng.below((uint64_t)(w - kCrop + 1)) : 0;
-        return {fi, y0, x0};
+        // (the crop is square: the window of a member that swaps the axes has the same origins to choose from)
+        return {fi, y0, x0, augment ? (uint8_t)(aug_rng.next() >> 61) : (uint8_t)0};
     };
     // draws are made a window of steps ahead, so that transient images decode while the GPU works
     DecoderPool pool(files, 16 * kBatch), lr_pool(lr_files, 16 * kBatch);
@@ -764,11 +774,13 @@ int run_train(int argc, char** argv) {
         fill();
         sr_train_crop items[kBatch];
         sr_train_pair_crop pairs[kBatch];
+        uint8_t members[kBatch];
         for (int i = 0; i < kBatch; ++i) {
             const auto [d, job] = ahead.front();
             ahead.pop_front();
             items[i].y0 = pairs[i].y0 = d.y0;
             items[i].x0 = pairs[i].x0 = d.x0;
+            members[i] = d.member;
             if (job < 0) {
                 items[i].image = pairs[i].pair = timg[d.file].id;
                 items[i].px = pairs[i].lr_px = pairs[i].hr_px = nullptr;
@@ -792,7 +804,8 @@ int run_train(int argc, char** argv) {
             pairs[i].lr_px = held_lr[i].data();
             pairs[i].lr_channels = pairs[i].hr_channels = 4; pairs[i].lh = lr.h; pairs[i].lw = lr.w;
         }
-        rc = has_lr ? sr_train_step_pairs(tr, pairs, kBatch, kCrop, kCrop) : sr_train_step(tr, items, kBatch, kCrop, kCrop);
+        if (augment) rc = has_lr ? sr_train_step_pairs_aug(tr, pairs, members, kBatch, kCrop, kCrop) : sr_train_step_aug(tr, items, members, kBatch, kCrop, kCrop);
+        else rc = has_lr ? sr_train_step_pairs(tr, pairs, kBatch, kCrop, kCrop) : sr_train_step(tr, items, kBatch, kCrop, kCrop);
         if (rc != SR_OK) die(std::string("training step: ") + sr_strerror(rc));
         if (step % 1000 == 0) {  // keep the err_sum list of the session short (the values are not reported)
             rc = sr_train_sync(tr, nullptr, 0, nullptr);
@@ -857,6 +870,7 @@ int main(int argc, char** argv) {
             const std::string v = value("--ensemble <N>");
             if (!(ensemble = ensemble_mask(v))) usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
         }
+        else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a.size() > 1 && a[0] == '-') usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
     }

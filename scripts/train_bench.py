@@ -15,7 +15,9 @@ against the same folder forced transient (--store 0).  Prints one JSON line per 
   `--repeats` times over, the other checkout's pooled session step, this build's pooled step and this build's paired step
   (sr_train_step_pairs on resident LR / HR pairs, LR crops of 64 x 64) -- same images, same origins.  The spread of each row over its
   repeats is the run-to-run spread the differences are read against.  (--one MODE: a single such measurement, of the package under
-  --root.)"""
+  --root.)  With --augment the other checkout's paired step and this build's two augmented steps (every item a member uniform over
+  0..7, from a generator of its own: the origins stay those of the other rows) join the rows.  The augmented gather's share of a step:
+  run `--one pooled_aug` (or paired_aug) under rocprofv3 --kernel-trace --stats; `--members 4,5,6,7` draws from one class of members."""
 import argparse
 import json
 import os
@@ -87,8 +89,9 @@ def session_bench(steps, warmup, out):
           "backprop_adam_device_ms_per_step": round(device_ms, 4), "wall_over_device": round(wall / device_ms, 4)}, out)
 
 
-def one_step_bench(mode, steps, warmup):
-    """wall ms per queued session step at the reference step: mode "pooled" (step_crops on HR images) or "paired" (step_pair_crops)"""
+def one_step_bench(mode, steps, warmup, members=tuple(range(8))):
+    """wall ms per queued session step at the reference step: mode "pooled" (step_crops on HR images) or "paired" (step_pair_crops);
+    "pooled_aug" / "paired_aug": the same with a random member per item, uniform over `members`"""
     import rusty_sr_amd as r
     from conftest import synth_u8
     params = r.rsr.builtin("imagenet")
@@ -96,13 +99,16 @@ def one_step_bench(mode, steps, warmup):
     rng = np.random.default_rng(0)
     imgs = [synth_u8(k, 1, 480, 642)[0] for k in range(8)]
     tr = r.Trainer(eng, params)
-    if mode == "paired":
+    aug = mode.endswith("_aug")
+    krng = np.random.default_rng(1)
+    member = (lambda: (int(members[int(krng.integers(0, len(members)))]),)) if aug else (lambda: ())
+    if mode.startswith("paired"):
         lrs = [np.ascontiguousarray(im.reshape(160, 3, 214, 3, 3)[:, 1, :, 1]) for im in imgs]  # (any LR image will do for the timing)
         ids = [tr.add_pair(lr, im) for lr, im in zip(lrs, imgs)]
-        step = lambda it: tr.step_pair_crops(it, 64, 64)
+        step = lambda it: tr.step_pair_crops([i + member() for i in it], 64, 64)
     else:
         ids = [tr.add_image(im) for im in imgs]
-        step = lambda it: tr.step_crops([(i, 3 * y, 3 * x) for i, y, x in it], 192, 192)
+        step = lambda it: tr.step_crops([(i, 3 * y, 3 * x) + member() for i, y, x in it], 192, 192)
     assert min(ids) >= 0
 
     def items():  # origins in LR pixels
@@ -122,8 +128,10 @@ def one_step_bench(mode, steps, warmup):
     return wall
 
 
-def ab_bench(other, repeats, steps, warmup, out):
+def ab_bench(other, repeats, steps, warmup, out, augment=False):
     rows = [("parent_pooled", other, "pooled"), ("pooled", ROOT, "pooled"), ("paired", ROOT, "paired")]
+    if augment:
+        rows = [rows[0], ("parent_paired", other, "paired"), *rows[1:], ("pooled_aug", ROOT, "pooled_aug"), ("paired_aug", ROOT, "paired_aug")]
     got = {label: [] for label, _, _ in rows}
     for _ in range(repeats):
         for label, root, mode in rows:
@@ -133,7 +141,7 @@ def ab_bench(other, repeats, steps, warmup, out):
             got[label].append(json.loads(res.stdout.strip().splitlines()[-1])["wall_ms_per_step"])
     for label, _, _ in rows:
         v = got[label]
-        emit({"what": "pairs_ab", "row": label, "steps": steps, "warmup": warmup, "wall_ms_per_step": v, "median": round(float(np.median(v)), 4),
+        emit({"what": "augment_ab" if augment else "pairs_ab", "row": label, "steps": steps, "warmup": warmup, "wall_ms_per_step": v, "median": round(float(np.median(v)), 4),
               "spread": round(max(v) - min(v), 4)}, out)
 
 
@@ -165,14 +173,18 @@ def main():
     ap.add_argument("--ab", default="", help="another checkout of this project, built: alternate its pooled step with this build's steps")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--root", default=ROOT, help="import rusty_sr_amd from this checkout")
-    ap.add_argument("--one", default="", choices=["", "pooled", "paired"])
+    ap.add_argument("--one", default="", choices=["", "pooled", "paired", "pooled_aug", "paired_aug"])
+    ap.add_argument("--augment", action="store_true", help="with --ab: add the parent's paired row and this build's augmented rows")
+    ap.add_argument("--members", default="0,1,2,3,4,5,6,7", help="with --one *_aug: the members an item's member is drawn from")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     if a.one:
-        emit({"what": "step", "mode": a.one, "root": a.root, "wall_ms_per_step": round(one_step_bench(a.one, a.steps, a.warmup), 4)}, "")
+        members = tuple(int(k) for k in a.members.split(","))
+        emit({"what": "step", "mode": a.one, "root": a.root, "members": list(members) if a.one.endswith("_aug") else [0],
+              "wall_ms_per_step": round(one_step_bench(a.one, a.steps, a.warmup, members), 4)}, "")
         return
     if a.ab:
-        ab_bench(a.ab, a.repeats, a.steps, a.warmup, a.out)
+        ab_bench(a.ab, a.repeats, a.steps, a.warmup, a.out, a.augment)
         return
     session_bench(a.steps, a.warmup, a.out)
     if not a.no_cli:
