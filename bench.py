@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the upscale hot path (graph.forward, reference
-src/main.rs:171) on MI355X, with the roofline of its dominant kernel and a CPU
-baseline beside it.
+src/main.rs:171) on MI355X; with --full, the roofline of its dominant kernel, the
+other named configurations and a CPU baseline beside it.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
-        --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+        --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, K timed steps, --dump-outputs, the
+JSON line (`value`, `ms_per_step` and the fields that describe them).  --full adds every other measurement to that same line,
+after the timed steps -- the headline is measured the same way in both.
 
 One "step" = one pass of the whole conv stack over one image resident in HBM
 (u8 RGB in -> u8 RGBA out by default, i.e. img_to_data + graph.forward +
@@ -15,7 +19,7 @@ Workload of `value` at N=1: 1920x1080 RGB (BASELINE.json configs[2], the configu
 north_star quotes its target on), x3 upscale with the bundled imagenet.rsr.
 BASELINE.json says "4x"; the reference is hard-wired to factor 3
 (main.rs:31) and its weights only fit factor 3, so every number here is x3.
-The other named configurations ride along as keyed entries of the same JSON line:
+With --full the other named configurations ride along as keyed entries of the same JSON line:
   config_A  256x256                       (N=1)
   config_C  3840x2160: at N=1 the whole image on one GPU; at N>1 STRONG scaling -- N row bands
             (2160/N rows each), 7-row halo exchange inside the timed region, per-rank roofline fraction
@@ -351,10 +355,15 @@ def main():
                     help="f32 (default, the headline `value`): exact-f32 MFMA, the reference's own arithmetic class.  "
                          "split_f16: hi/lo half pairs, 3 f16 MFMAs per product on the matrix cores -- 2x faster and inside "
                          "the same north-star parity bar (<= 1e-4; measured <= 2e-5, every GPU parity test runs in both "
-                         "modes); at N=1 it is measured in the same run and reported as `other_precision`.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the config_A / config_C / config_D entries")
+                         "modes); at N=1 --full measures it in the same run and reports it as `other_precision`.")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything else the line can carry: the sustained loop, the fork A/B, the "
+                         "per-stage roofline, the other precision, the x4 net, config_A / config_C / config_D and the other workloads, "
+                         "the CPU baseline.  Off by default: a plain run measures the headline figure alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the sustained loop, the fork A/B, the per-stage roofline, the other precision and the x4 net")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the config_A / config_C / config_D entries")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last timed step returned as DIR/output.npy (float32; an output over "
                          "64 MB as a fixed, seeded sample of whole rows, their indices in DIR/output_rows.npy): the inputs are seeded, "
@@ -362,6 +371,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_cpu_baseline = args.no_roofline = args.no_configs = True
 
     # (before the HSA runtime comes up: the host driver only supports dmabuf IPC, RCCL's peer connections need this)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -575,6 +586,9 @@ def main():
         "whole_call_frac": round(H * W * FLOP_PER_PX / (ms_per_step / 1e3) / 1e12 /
                                  (PEAK_F32_MFMA_TFLOPS if args.precision == "f32" else PEAK_F16_MFMA_TFLOPS), 4),
     }
+    result["full"] = args.full
+    if exchange_check is not None:  # (the live check that chose the exchange `value` was measured through: in a plain line too)
+        result["exchange_check"] = exchange_check
     if dumped:
         result["dump_outputs"] = {"dir": args.dump_outputs, "files": [n + ".npy" for names in dumped for n in names]}
 

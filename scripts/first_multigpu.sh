@@ -38,16 +38,16 @@ timeout 1800 python -m pytest tests/test_gpu_multi.py -q -m gpu -rs -k "other_de
 for N in 1 2 4 8; do
     [ "$N" -le "$NDEV" ] || continue
     if [ "$N" = 1 ]; then
-        timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/scale_$N.json" 2> "$OUT/scale_$N.err"
+        timeout 900 python bench.py --gpus 1 --full --steps 20 --warmup 5 > "$OUT/scale_$N.json" 2> "$OUT/scale_$N.err"
     else
         timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((29500 + N)) \
-            bench.py --gpus "$N" --steps 20 --warmup 5 > "$OUT/scale_$N.json" 2> "$OUT/scale_$N.err"
+            bench.py --gpus "$N" --full --steps 20 --warmup 5 > "$OUT/scale_$N.json" 2> "$OUT/scale_$N.err"
     fi
     echo "bench --gpus $N rc=$?"
     tail -1 "$OUT/scale_$N.json" > "profiles/r6_scale_$N.json"
     if [ "$N" -gt 1 ]; then  # the same line with feature rows exchanged after every stage instead of the recomputed overlap
         SRHIP_HALO=layers timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((29600 + N)) \
-            bench.py --gpus "$N" --steps 20 --warmup 5 > "$OUT/scale_layers_$N.json" 2> "$OUT/scale_layers_$N.err"
+            bench.py --gpus "$N" --full --steps 20 --warmup 5 > "$OUT/scale_layers_$N.json" 2> "$OUT/scale_layers_$N.err"
         echo "bench --gpus $N (layer halos) rc=$?"
         tail -1 "$OUT/scale_layers_$N.json" > "profiles/r6_scale_layers_$N.json"
     fi

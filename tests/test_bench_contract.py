@@ -1,10 +1,11 @@
-"""bench.py's one-line JSON contract, on the GPU: N=1 with roofline + cpu_baseline objects, the files of --dump-outputs, and a
-2-rank rehearsal of the sharded path (gloo, both ranks folded onto the one GPU of the test box --
-RCCL refuses two ranks per device; the driver's real N>1 runs use RCCL)."""
+"""bench.py's one-line JSON contract, on the GPU: a plain N=1 run (the headline figure alone, and the files of --dump-outputs),
+--full at N=1 with roofline + cpu_baseline objects, and a --full 2-rank rehearsal of the sharded path (gloo, both ranks folded
+onto the one GPU of the test box -- RCCL refuses two ranks per device; the driver's real N>1 runs use RCCL)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -21,10 +22,11 @@ def _last_json(stdout):
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--height", "360", "--width", "640"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--height", "360", "--width", "640"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
+    assert d["full"] is True
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -70,16 +72,46 @@ def test_bench_single_gpu_contract():
     assert d["config_D"]["images_per_rank"] == 64 and d["config_D"]["data_path_collectives"] == 0 and "host_pipelined" in d["config_D"]
 
 
-def test_bench_dump_outputs(tmp_path, params):
+# what --full adds to the line: no plain run may carry (that is: spend time on) any of it
+FULL_ONLY = ("sustained", "fork_ab", "roofline", "stages", "hbm", "other_precision", "x4_synthetic_weights", "config_A", "config_C",
+             "config_D", "mid_size_frames", "aux_graphs", "batch_of_4", "two_frames_in_flight", "host_call", "cpu_baseline",
+             "speedup_vs_cpu_baseline")
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    """One plain run (no --full) with --dump-outputs: its line, its wall time from start to exit, and where it wrote."""
+    out = tmp_path_factory.mktemp("dump")
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0", "--height", "360", "--width", "640",
+                        "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    return _last_json(r.stdout), wall, out
+
+
+def test_bench_plain_run_is_lean(plain_run):
+    """Without --full the line carries the headline figure and what describes it, nothing that takes a measurement of its own, and
+    the run spends at most 30 s outside its steps (start to exit, less (steps + warmup) x ms_per_step)."""
+    d, wall, _ = plain_run
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+              "dtype", "data", "config"):
+        assert k in d, k
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 0 and d["higher_is_better"] is True
+    assert d["unit"] == "output MP/s" and d["dtype"] == "f32" and d["metric"].startswith("output megapixels/sec at 3x upscale")
+    assert abs(d["value"] - 9 * 360 * 640 / 1e6 / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-3
+    assert not [k for k in FULL_ONLY if k in d]
+    outside = wall - (d["steps"] + d["warmup"]) * d["ms_per_step"] / 1e3
+    print(f"plain run: {wall:.2f} s from start to exit, {outside:.2f} s outside its steps")
+    assert outside <= 30.0, (wall, outside)
+
+
+def test_bench_dump_outputs(plain_run, params):
     """--dump-outputs: the last timed step's output, written whole at this size, is the oracle's upscale of bench.py's seeded input
     frame (u8: within 1, only on rounding knife-edges); --steps sets the steps the line reports."""
     import bench
     import oracle
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "0", "--height", "360", "--width", "640", "--no-roofline",
-                        "--no-configs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    d = _last_json(r.stdout)
+    d, _, tmp_path = plain_run
     assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dump_outputs"]["files"] == ["output.npy"]
     got = np.load(tmp_path / "output.npy")
     assert got.dtype == np.float32 and got.shape == (1080, 1920, 4)
@@ -91,7 +123,7 @@ def test_bench_dump_outputs(tmp_path, params):
 def test_bench_two_rank_rehearsal():
     env = dict(os.environ, SRHIP_DIST_BACKEND="gloo", SRHIP_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "2", "--steps", "3",
+                        "--master-addr", "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "2", "--full", "--steps", "3",
                         "--warmup", "1", "--height", "360", "--width", "640"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
