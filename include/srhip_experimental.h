@@ -31,9 +31,11 @@ extern "C" {
  * tiles; "forktune": "" / "1" -- for mid-size shapes (0.55-12 rounds of tiles) the automatic choice is MEASURED on the caller's own calls
  * (four undivided, four forked, timed by event pairs that are queried, never waited for; then the faster plan stays for that shape),
  * "0" -- the rule alone; setting it forgets what was measured.
- * "wino": the exact mode's 5x5 convolutions over f -- "" / "2": those of stages 1 and 2 (conv1, conv2) with every kernel row as
- * row-direction Winograd F(2,3) (7 products per row and output pair instead of 10; stage 2's 3x3 source stays direct), "1": stage 1's
- * only, "0": every stage in the direct form.  Unlike the others this switch changes the last bits of f32 results (every setting is
+ * "wino": the exact mode's convolutions as row-direction Winograd F(2,3) -- "": the 5x5 convolutions over f of stages 1 and 2 (conv1,
+ * conv2; 7 products per kernel row and output pair instead of 10) and input channels 0-15 of stage 2's 3x3 source (conv5; 4 products
+ * instead of 6), whose channels 16-31 stay direct; "2": conv1 and conv2 only, conv5 direct (the form before conv5's: its bits); "3":
+ * both halves of conv5 as well (for measurement only, never the default: it takes the call too close to the f32 roof that bench.py's
+ * contract holds it below); "1": stage 1's conv1 only; "0": every stage in the direct form.  Unlike the others this switch changes the last bits of f32 results (every setting is
  * held to the same parity bar); every kernel form, tile class and band of one setting stays bit-identical to the others.
  * Defaults come from SRHIP_WINO / SRHIP_TH / SRHIP_TAIL / SRHIP_PIPE / SRHIP_BW / SRHIP_BANDS / SRHIP_ROWS / SRHIP_GEO / SRHIP_HALO, read once in sr_create.
  * Unknown key: SR_E_INVALID. */

@@ -51,10 +51,11 @@ int expand_channel_t(int f, int nt, int j) { return expand_channel(f, nt, 16 * (
 //   f32  : [q = 2 tapslot + rr][h 2][lane 32][4]    channel = 16 half + 8 rr + 4 h + e
 //   split: [hi | lo] x [tapslot 2][h 2][lane 32][8]  channel = 16 half + 8 h + e
 // `lane_channel(nt, j)` maps MFMA column j of N-tile nt to the output channel of w ([O][ks][ks][32]) or -1.
+// Only the halves [half_lo, half_hi) are written (stage 2's conv5 in the Winograd form: the halves that stay direct).
 template <typename F>
-void pack_steps(std::vector<float>& dst, const float* w, int ks, int ntn, bool split, F lane_channel) {
+void pack_steps(std::vector<float>& dst, const float* w, int ks, int ntn, bool split, F lane_channel, int half_lo = 0, int half_hi = 2) {
     const int nt = ks * ks, np = (nt + 1) / 2;
-    for (int half = 0; half < 2; ++half)
+    for (int half = half_lo; half < half_hi; ++half)
         for (int p = 0; p < np; ++p)
             for (int tile = 0; tile < ntn; ++tile) {
                 const size_t base = dst.size();
@@ -91,19 +92,21 @@ void pack_steps(std::vector<float>& dst, const float* w, int ks, int ntn, bool s
 //   [q = g % 4][h 2][lane 32][4]    channel = 16 half + 8 rr + 4 h + e
 // Position k < 4 is position k of chunk A (taps 0, 1, 2 of the row), k = 4..6 position k - 3 of chunk B (a zero tap, then taps 3, 4);
 // V = (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2), computed in double and rounded once.
-void pack_steps_wino(std::vector<float>& dst, const float* w) {
-    constexpr int kGroups = 5 * 7 * 2, kSteps = (kGroups + 3) / 4;
-    for (int half = 0; half < 2; ++half) {
+// A 3x3 weight (ks = 3: conv5, stage 2's second source) has chunk A alone: g = 8 ky + 2 k + rr, 24 groups = 6 chunks per half; only the
+// halves [half_lo, half_hi) are written.
+void pack_steps_wino(std::vector<float>& dst, const float* w, int ks = 5, int half_lo = 0, int half_hi = 2) {
+    const int npos = ks == 5 ? 7 : 4, kGroups = ks * npos * 2, kSteps = (kGroups + 3) / 4;
+    for (int half = half_lo; half < half_hi; ++half) {
         const size_t base = dst.size();
         dst.resize(base + (size_t)kSteps * kChunk, 0.0f);
         for (int g = 0; g < kGroups; ++g) {
-            const int rr = g & 1, k = (g >> 1) % 7, ky = (g >> 1) / 7;
+            const int rr = g & 1, k = (g >> 1) % npos, ky = (g >> 1) / npos;
             float* chunk = dst.data() + base + (size_t)(g / 4) * kChunk + (g % 4) * 256;
             for (int j = 0; j < 32; ++j)
                 for (int h = 0; h < 2; ++h)
                     for (int e = 0; e < 4; ++e) {
                         const int c = 16 * half + 8 * rr + 4 * h + e;
-                        auto tap = [&](int kx) { return (double)w[((size_t)j * 25 + ky * 5 + kx) * 32 + c]; };
+                        auto tap = [&](int kx) { return (double)w[((size_t)j * ks * ks + ky * ks + kx) * 32 + c]; };
                         const double g0 = k < 4 ? tap(0) : 0.0, g1 = k < 4 ? tap(1) : tap(3), g2 = k < 4 ? tap(2) : tap(4);
                         const int pos = k < 4 ? k : k - 3;
                         const double v = pos == 0 ? g0 : pos == 1 ? (g0 + g1 + g2) * 0.5 : pos == 2 ? (g0 - g1 + g2) * 0.5 : g2;
@@ -272,8 +275,12 @@ std::vector<float> pack_params(sr_ctx* c, const float* params, int factor, bool*
     }
     w.clear(); pack_steps_wino(w, params + L.off[SR_SEG_CONV1]);
     c->off_wino1 = push(w);
-    w.clear(); pack_steps_wino(w, params + L.off[SR_SEG_CONV2]); pack_steps(w, params + L.off[SR_SEG_CONV5], 3, 1, false, [](int, int j) { return j; });
-    c->off_wino2 = push(w);
+    for (int h5 = 0; h5 <= 2; ++h5) {  // 46 + h5 chunks per tile: a Winograd half of conv5 is 6 chunks, a direct half 5
+        w.clear(); pack_steps_wino(w, params + L.off[SR_SEG_CONV2]);
+        pack_steps_wino(w, params + L.off[SR_SEG_CONV5], 3, 0, h5);
+        pack_steps(w, params + L.off[SR_SEG_CONV5], 3, 1, false, [](int, int j) { return j; }, h5, 2);
+        c->off_wino2[h5] = push(w);
+    }
     const size_t boff[4] = {L.off[SR_SEG_F_BIAS], L.off[SR_SEG_L1_BIAS], L.off[SR_SEG_L2_BIAS], L.off[SR_SEG_L3_BIAS]};
     const size_t aoff[4] = {L.off[SR_SEG_F_ACTIV], L.off[SR_SEG_L1_ACTIV], L.off[SR_SEG_L2_ACTIV], L.off[SR_SEG_L3_ACTIV]};
     for (int s = 0; s < 4; ++s) c->off_bias[s] = push(vec32(boff[s], 32));
@@ -548,8 +555,10 @@ int sr_set_experiment(sr_ctx* c, const char* key, const char* value) {
         sr_fork_tune_clear(c);
     } else if (!strcmp(key, "halo")) {  // sharded calls: "" / "input": 7 input rows per neighbour, the overlap recomputed; "layers": feature rows after every stage
         c->layer_halos = !strcmp(v, "layers");
-    } else if (!strcmp(key, "wino")) {  // exact mode: "" / "2": stages 1 and 2 as Winograd F(2,3) rows, "1": stage 1 only, "0": all direct (same bar, other last bits)
+    } else if (!strcmp(key, "wino")) {  // exact mode: "": stages 1 and 2 as Winograd F(2,3) rows, half of conv5 included; "2": conv5 direct (the form before);
+                                        // "3": both halves of conv5 (measurement only); "1": stage 1 only, "0": all direct (same bar, other last bits)
         c->wino = !strcmp(v, "0") ? 0 : !strcmp(v, "1") ? 1 : 2;
+        c->wino5 = !strcmp(v, "3") ? 2 : !strcmp(v, "2") ? 0 : kWinoConv5Halves;
     } else if (!strcmp(key, "bw")) {   // tile-order column-block width in tiles; "" / negative: automatic, 0: plain row-major
         c->env_bw = *v ? atoi(v) : -1;
     } else {
@@ -843,15 +852,16 @@ int StackJob::launch(int st) const {
         case 4: a.src[0] = l1; a.src[1] = l2; a.src[2] = l3; a.img = d_img; a.out = d_out; break;
     }
     const bool wino = c->precision == SR_PRECISION_F32 && (st == 1 || st == 2) && st <= c->wino;
-    a.wpack = P + (c->precision ? c->off_wh[st] : !wino ? c->off_w[st] : st == 1 ? c->off_wino1 : c->off_wino2); a.bias = P + c->off_bias[st];
+    const int wino5 = wino && st == 2 ? c->wino5 : 0;
+    a.wpack = P + (c->precision ? c->off_wh[st] : !wino ? c->off_w[st] : st == 1 ? c->off_wino1 : c->off_wino2[wino5]); a.bias = P + c->off_bias[st];
     a.beta = st < 4 ? P + c->off_beta[st] : nullptr;
     a.H = H; a.W = W; a.img_ch = img_ch;
     a.y_begin = y0; a.y_end = y1; a.tiles_x = tiles_x;
     a.n_img = n; a.queue = ws->d_queue + st * 8; a.domain = c->d_domain;
     a.grid[0] = make_tile_grid(8, y0, l.ty8, tiles_x, n, bw);
     a.grid[1] = make_tile_grid(4, y0 + 8 * l.ty8, l.ty4, tiles_x, n, bw);
-    if (l.pipe) HIPCHK(c, sr_launch_stage_pipe(st, c->factor, a, c->precision, l.grid, img_u8, out_u8, wino, s));
-    else HIPCHK(c, sr_launch_stage(st, c->factor, a, l.th, c->precision, l.grid, img_u8, out_u8, wino, s));
+    if (l.pipe) HIPCHK(c, sr_launch_stage_pipe(st, c->factor, a, c->precision, l.grid, img_u8, out_u8, wino, wino5, s));
+    else HIPCHK(c, sr_launch_stage(st, c->factor, a, l.th, c->precision, l.grid, img_u8, out_u8, wino, wino5, s));
     return SR_OK;
 }
 

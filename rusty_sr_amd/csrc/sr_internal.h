@@ -11,6 +11,11 @@
 
 #include "../../include/srhip.h"
 
+// 16-channel halves of conv5 (stage 2's 3x3 source) that the exact mode runs as Winograd F(2,3) rows by default: 1.  Both halves would take
+// the whole call's direct-FLOP rate to within 1 % of the f32 roof on the fastest boxes, which bench.py's contract asserts it stays below
+// (DESIGN.md 4a, item 4); "wino" = "3" runs both, for measurement.
+constexpr int kWinoConv5Halves = 1;
+
 struct sr_ctx {
     int device = 0;
     int cus = 0, clock_mhz = 0;
@@ -20,8 +25,9 @@ struct sr_ctx {
     void* d_qtab = nullptr;     // bilinear_net / downsample_net: data_to_img(LinearToSrgb(l)) as a step table (sr_aux.hip)
     size_t off_w0 = 0, off_w0h = 0, off_w[5] = {0}, off_wh[5] = {0}, off_bias[5] = {0}, off_beta[5] = {0};
     size_t off_wino1 = 0;  // stage 1's weights as Winograd F(2,3) chunks (sr_api.cpp pack_steps_wino)
-    size_t off_wino2 = 0;  // stage 2's: conv2 as Winograd F(2,3) chunks, then conv5's direct chunks
+    size_t off_wino2[3] = {0, 0, 0};  // stage 2's, by wino5: conv2 as Winograd F(2,3) chunks, then conv5's first wino5 halves as 3-tap Winograd chunks, then its other halves' direct chunks
     int wino = 2;          // exact mode, stages 1 .. wino in their Winograd F(2,3) form ("wino" switch; "0": all direct -- last bits differ)
+    int wino5 = kWinoConv5Halves;  // ... and, with stage 2, the first wino5 halves of conv5 ("wino" = "2": none, the form before; "3": both)
     int precision = 0;  // SR_PRECISION_F32 / SR_PRECISION_SPLIT_F16
     // Domain of the split-half mode (include/srhip.h, sr_set_precision): values are carried as pairs of HALVES, so every weight, input
     // and activation must be finite and below 65504 in magnitude.  Weights are checked once (split_ok); inputs and activations by the

@@ -125,10 +125,12 @@ hipError_t sr_launch_conv0(const Conv0Args& a, int th, int prec, int nblk, bool 
 // factor (2, 3 or 4) only matters for stage 4 (3 f^2 expand channels, depth-to-space x f)
 // first form: ONE tile class (th = 8: a.grid[0], th = 4: a.grid[1]), whole source tiles resident
 // wino (prec 0, stages 1 and 2): the 5x5 convolution as row-direction Winograd F(2,3) (sr_kernels.hip half_steps_wino; stage 2's 3x3
-// source on the same pairs, half_steps_pairs); a.wpack then holds pack_steps_wino chunks (stage 2: followed by conv5's direct chunks)
+// source on the same pairs: its first wino5 (0, 1 or 2) 16-channel halves as 3-tap Winograd rows, the others as direct taps,
+// half_steps_pairs); a.wpack then holds pack_steps_wino chunks (stage 2: conv2's, then conv5's Winograd halves, then its direct halves'
+// chunks).  wino5 matters for stage 2 with wino only.
 hipError_t sr_launch_stage(int stage, int factor, const StageArgs& a, int th, int prec, int nblk, bool img_u8, bool out_u8,
-                           bool wino, hipStream_t s);
+                           bool wino, int wino5, hipStream_t s);
 // "pipe" form of the stage kernels (half-tile double buffering, persistent): both tile classes of `a` in one launch;
 // grid = co-resident workgroups.
 hipError_t sr_launch_stage_pipe(int stage, int factor, const StageArgs& a, int prec, int grid, bool img_u8, bool out_u8,
-                                bool wino, hipStream_t s);
+                                bool wino, int wino5, hipStream_t s);

@@ -770,7 +770,7 @@ __device__ __forceinline__ void half_steps_f32(Acc& acc, const char* hb, const c
     }
 }
 
-// WINO (exact mode, stages 1 and 2: the 5x5 f-convolution; stage 2's 3x3 source runs half_steps_pairs): every kernel row as row-direction Winograd / Toom-Cook F(2,3) on the points
+// WINO (exact mode, stages 1 and 2: the 5x5 f-convolution, and the first W3H -- by default kWinoConv5Halves, sr_internal.h -- 16-channel halves of stage 2's 3x3 source; its other halves run half_steps_pairs): every kernel row as row-direction Winograd / Toom-Cook F(2,3) on the points
 // 0, 1, -1, inf.  For an output pair (x, x + 1) and a 3-tap row g over the inputs d0..d3:
 //     U = (d0 - d2, d1 + d2, d2 - d1, d1 - d3),  V = (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2),  m_p += U_p V_p,
 //     y0 = m0 + m1 + m2,  y1 = m1 - m2 - m3.
@@ -786,8 +786,14 @@ __device__ __forceinline__ void half_steps_f32(Acc& acc, const char* hb, const c
 // pair's pixels, one v_pk_add_f32 pair (U), one weight read, four MFMAs.  Group order inside a half: kernel row, chunk, position, 8-channel
 // group -- the same in both kernel forms and both tile classes, so every form stays bit-identical to the others.  70 groups per half =
 // 18 steps of four (the last of two), one 4 KB chunk each.
-constexpr int kWinoGroups = 5 * 7 * 2;
-constexpr int kWinoSteps = (kWinoGroups + 3) / 4;
+// A 3-tap row (stage 2's 3x3 source l1, conv5) is chunk A alone: positions 0-3 on d0..d3 = the four columns from the pair's first halo
+// column of the 34-wide tile, 4 products per row and pair where the direct form has 6; 3 kernel rows x 4 positions x 2 channel groups =
+// 24 groups per half = 6 full steps.  Position 0 feeds y0 only and reads d0, d2, position 3 feeds y1 only and reads d1, d3, positions 1
+// and 2 read d1, d2, which lie in both fields: a non-finite value reaches exactly its 3x3 field.
+constexpr int wino_positions(int ks) { return ks == 5 ? 7 : 4; }  // per kernel row: chunk A's four, a 5-tap row chunk B's three more
+constexpr int wino_groups(int ks) { return ks * wino_positions(ks) * 2; }
+constexpr int wino_steps(int ks) { return (wino_groups(ks) + 3) / 4; }
+constexpr int kWinoSteps = wino_steps(5), kWino3Steps = wino_steps(3);
 // position k of a kernel row (0-3: chunk A, 4-6: chunk B positions 1-3): its accumulator set and the tile columns (from the pair's first
 // halo column) of the two pixels whose sum or difference is U
 constexpr int wino_acc(int k) { return k < 4 ? k : k - 3; }
@@ -809,23 +815,25 @@ __device__ __forceinline__ void wino_u4(f32x2 x0, f32x2 y0, f32x2 x1, f32x2 y1, 
             : "=&v"(u0), "=&v"(u1) : "v"(x0), "v"(y0), "v"(x1), "v"(y1));
 }
 
-template <int TWH, int PS, int T, int NA, typename Stream>
+template <int TWH, int PS, int T, int KS, int NA, typename Stream>
 __device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[NA], const char* hb, const char* ring, Stream& sm, int wave, int lane) {
-    static_assert(TWH >= kTW + 4, "a pair reads six pixels from its first halo column on");
+    static_assert(KS == 5 || KS == 3, "5-tap rows: chunks A and B; 3-tap rows: chunk A");
+    static_assert(TWH >= kTW + KS - 1, "a pair reads KS + 1 pixels from its first halo column on: the highest is column 2 * 15 + KS");
+    constexpr int NPOS = wino_positions(KS), NGROUPS = wino_groups(KS), NSTEPS = wino_steps(KS);
     const int i = lane & 31, h = lane >> 5;
     const int wlane = (h * 32 + i) * 16;
     const int row = wave * T + (T == 2 ? i >> 4 : 0);
     const char* abase = hb + h * PS + (row * TWH + 2 * (i & 15)) * 16;
     struct Ops { f32x4 x, y, b; };
     auto load = [&](Ops& o, int g, int sl) {  // operand group g = (kernel row, position, 8-channel group rr)
-        const int rr = g & 1, k = (g >> 1) % 7, ky = (g >> 1) / 7;
+        const int rr = g & 1, k = (g >> 1) % NPOS, ky = (g >> 1) / NPOS;
         const char* ab = abase + rr * 2 * PS + ky * TWH * 16;
         o.b = *(const f32x4*)(ring + sl * 4096 + wlane + (g & 3) * 1024);
         o.x = *(const f32x4*)(ab + wino_ca(k) * 16);
         o.y = *(const f32x4*)(ab + wino_cb(k) * 16);
     };
     auto mfma = [&](const Ops& o, int g) {
-        const int k = (g >> 1) % 7;
+        const int k = (g >> 1) % NPOS;
         const f32x2 x0 = {o.x[0], o.x[1]}, x1 = {o.x[2], o.x[3]}, y0 = {o.y[0], o.y[1]}, y1 = {o.y[2], o.y[3]};
         f32x2 u0, u1;
         if (wino_add(k)) wino_u4<true>(x0, y0, x1, y1, u0, u1);
@@ -837,8 +845,8 @@ __device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[NA], const char* h
     Ops cur, nxt;
     load(cur, 0, sm.slot());
 #pragma unroll
-    for (int s = 0; s < kWinoSteps; ++s) {
-        const int ngroups = kWinoGroups - 4 * s < 4 ? kWinoGroups - 4 * s : 4;
+    for (int s = 0; s < NSTEPS; ++s) {
+        const int ngroups = NGROUPS - 4 * s < 4 ? NGROUPS - 4 * s : 4;
         sm.begin_step();
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -851,7 +859,7 @@ __device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[NA], const char* h
                 cur = nxt;
             }
         }
-        const bool last = s == kWinoSteps - 1;
+        const bool last = s == NSTEPS - 1;
         sm.template end_step<0>(last);
         if (!last) load(nxt, 4 * s + 4, sm.slot());
         sm.piece(4 * s + 3);
@@ -862,7 +870,7 @@ __device__ __forceinline__ void half_steps_wino(f32x16 (&acc)[NA], const char* h
     }
 }
 
-// Stage 2's second source (l1, 3x3) in the WINO form: the direct taps of half_steps_f32 -- same weight chunks, same step and group
+// Stage 2's second source (l1, 3x3) in the WINO form, the halves that are not Winograd rows (template parameter W3H of the stage kernels): the direct taps of half_steps_f32 -- same weight chunks, same step and group
 // order -- on the pair layout of half_steps_wino, so that the accumulators need no lane exchange.  Lane (h, i) of the A operand is pair
 // i % 16 of tile row i / 16; an operand group reads the pair's even pixel 2 j + kx and its odd pixel 2 j + 1 + kx, one weight register
 // feeds both, the even products go into m0 (acc[0]) and the odd ones into a fifth set m4 (acc[4]): y0 = m0 + m1 + m2, y1 = m1 - m2 - m3
@@ -1744,9 +1752,10 @@ __device__ __forceinline__ int queue_first(int block, int nbig, int nsmall) { re
 // tile resident in LDS, sources staged one after the other.  It is what small launches of the exact-f32 mode run (no
 // queue, nothing to amortise: 256x256 is one round of 4-row tiles) and the in-library cross-check of the pipe form
 // (sr_set_experiment "pipe" = "none"): same matrix loops, same step order, same weight chunks, bit-identical results.
-template <int TH, int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false>
+template <int TH, int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false, int W3H = 0>
 __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
     static_assert(!WINO || (NSRC <= 2 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stages 1 and 2 of the exact mode");
+    static_assert(W3H >= 0 && W3H <= 2 && (W3H == 0 || (WINO && NSRC == 2)), "W3H: the first W3H halves of stage 2's 3x3 source as Winograd rows");
     // Two workgroups share each SIMD.  A wave streaming MFMAs is the older one and wins every
     // arbitration, leaving the other workgroup's prologue / staging / epilogue code roughly one
     // issue slot per MFMA.  The matrix stream only needs one slot per 64 cycles, so everything
@@ -1766,7 +1775,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31;
     constexpr bool H16 = kH16<PREC, FINAL>;  // stages 1-3 of the split-half mode: 16x16x32 MFMAs, no half steps (half_steps_h16)
-    constexpr int NTAPS = WINO ? 2 * (kWinoSteps + (NSRC - 1) * 5)
+    constexpr int NTAPS = WINO ? 2 * kWinoSteps + (NSRC - 1) * (W3H * kWino3Steps + (2 - W3H) * 5)
                         : H16 ? KS0 * KS0 + (NSRC - 1) * 9
                               : 2 * ((KS0 * KS0 + 1) / 2 + (NSRC - 1) * 5) * NTN;  // ring chunks: one per (step, N-tile), see half_steps_*
     const TileGrid& grid = a.grid[TH == 8 ? 0 : 1];  // this form runs one tile class per launch
@@ -1809,7 +1818,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) { qm[m][k >> 1][k & 1] = bias2[k & 1]; qx[m][k >> 1][k & 1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     }
-    constexpr int NWACC = WINO ? 3 + NSRC : 1;  // WINO: the four position sets m_p (half_steps_wino), stage 2 the odd pixels' set m4 (half_steps_pairs)
+    constexpr int NWACC = WINO ? 3 + NSRC : 1;  // WINO: the four position sets m_p (half_steps_wino), stage 2 the odd pixels' set m4 (half_steps_pairs; unused but kept with W3H = 2)
     f32x16 wacc[NWACC];
 #pragma unroll
     for (int p = 0; p < NWACC; ++p)
@@ -1823,7 +1832,10 @@ __global__ __launch_bounds__(256, 2) void conv_stage_kernel(StageArgs a) {
             RingStream sm{ring, a.wpack, gtap, slot, NTAPS, wave, lane};
 #pragma unroll 1
             for (int half = 0; half < 2; ++half) {
-                if constexpr (KS == KS0) half_steps_wino<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+                if constexpr (KS == KS0) half_steps_wino<G::TWH, G::PLANE, T, KS0>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+                else if constexpr (W3H == 0) half_steps_pairs<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+                else if constexpr (W3H == 2) half_steps_wino<G::TWH, G::PLANE, T, 3>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
+                else if (half < W3H) half_steps_wino<G::TWH, G::PLANE, T, 3>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
                 else half_steps_pairs<G::TWH, G::PLANE, T>(wacc, tile + half * 4 * G::PLANE, ring, sm, wave, lane);
             }
         } else if constexpr (H16) source_steps_h16<TH, KS, T>(qm, qx, tile, ring, a.wpack, gtap, slot, NTAPS, wave, lane);
@@ -2218,9 +2230,10 @@ struct PipeStream {
     }
 };
 
-template <int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false>
+template <int NSRC, int KS0, bool FINAL, bool IMG_U8, bool OUT_U8, int PREC, int FACTOR = 3, bool WINO = false, int W3H = 0>
 __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
     static_assert(!WINO || (NSRC <= 2 && KS0 == 5 && !FINAL && PREC == 0), "WINO: stages 1 and 2 of the exact mode");
+    static_assert(W3H >= 0 && W3H <= 2 && (W3H == 0 || (WINO && NSRC == 2)), "W3H: the first W3H halves of stage 2's 3x3 source as Winograd rows");
     __builtin_amdgcn_s_setprio(3);
     constexpr int NTN = FINAL ? (FACTOR * FACTOR + 9) / 10 : 1;  // N-tiles of the node (expand at factor 4: 48 channels = 2)
     using H0 = HalfTile<KS0>;
@@ -2228,7 +2241,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
     constexpr int HB = H0::BYTES;  // KS0 >= 3: the first source has the largest half tile
     constexpr int NH = 2 * NSRC;
     constexpr bool H16 = kH16<PREC, FINAL>;  // stages 1-3 of the split-half mode: 16x16x32 MFMAs, a source's halves share their odd tap's step
-    constexpr int NSTEPS = WINO ? 2 * (kWinoSteps + (NSRC - 1) * H3::STEPS)
+    constexpr int NSTEPS = WINO ? 2 * kWinoSteps + (NSRC - 1) * (W3H * kWino3Steps + (2 - W3H) * H3::STEPS)
                          : H16 ? KS0 * KS0 + (NSRC - 1) * 9
                                : 2 * (H0::STEPS + (NSRC - 1) * H3::STEPS) * NTN;  // weight chunks per tile: one per (step, N-tile)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -2367,7 +2380,7 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
 #pragma unroll
                 for (int g = 0; g < 8; ++g) qa[nt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        constexpr int NWACC = WINO ? 3 + NSRC : 1;  // WINO: the four position sets m_p (half_steps_wino), stage 2 the odd pixels' set m4 (half_steps_pairs)
+        constexpr int NWACC = WINO ? 3 + NSRC : 1;  // WINO: the four position sets m_p (half_steps_wino), stage 2 the odd pixels' set m4 (half_steps_pairs; unused but kept with W3H = 2)
         f32x16 wacc[NWACC];
 #pragma unroll
         for (int p = 0; p < NWACC; ++p)
@@ -2411,8 +2424,9 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
             using GJ = TileGeom<8, KSJ>;
             // steps of this half / of the halves before it (kH16: a source's first half is its tap pairs, the second one step more)
             constexpr int PAIRS_J = (KSJ * KSJ - 1) / 2;
-            constexpr int STEPS_J = WINO ? (src == 0 ? kWinoSteps : H3::STEPS) : H16 ? PAIRS_J + (j & 1) : HalfTile<KSJ>::STEPS * NTN;
-            constexpr int GS0 = WINO ? (j < 2 ? j * kWinoSteps : 2 * kWinoSteps + (j - 2) * H3::STEPS) : H16 ? (src == 0 ? 0 : KS0 * KS0 + (src - 1) * 9) + (j & 1) * PAIRS_J
+            constexpr bool WINO3_J = WINO && src == 1 && (j & 1) < W3H;  // this half of the 3x3 source runs as Winograd rows
+            constexpr int STEPS_J = WINO ? (src == 0 ? kWinoSteps : WINO3_J ? kWino3Steps : H3::STEPS) : H16 ? PAIRS_J + (j & 1) : HalfTile<KSJ>::STEPS * NTN;
+            constexpr int GS0 = WINO ? (j < 2 ? j * kWinoSteps : 2 * kWinoSteps + (j - 2) * (W3H >= 1 ? kWino3Steps : H3::STEPS)) : H16 ? (src == 0 ? 0 : KS0 * KS0 + (src - 1) * 9) + (j & 1) * PAIRS_J
                                     : (j == 0 ? 0 : j == 1 ? H0::STEPS : 2 * H0::STEPS + (j - 2) * H3::STEPS) * NTN;
             constexpr int LIN_LO_J = LinPrefetch<IMG_U8, TH>::NPIX * 8;  // split-half mode: bytes from the hi halves of the image tile to its lo halves
             auto lin_store = [&]() {  // (kLinOwn: the pixels requested at this half's start are long in; see s_xown)
@@ -2423,7 +2437,8 @@ __global__ __launch_bounds__(256, 2) void conv_stage_pipe_kernel(StageArgs a) {
                 }
             };
             PipeStream<PREC, KSN, decltype(lin_store)> sm{st, rq, *htn, a, ring_lds, wbase, GS0, wave, lane, (j == 0 && !single) ? s_next : nullptr, xcd, qs, STEPS_J > 3 ? STEPS_J - 3 : 0, 0, lin_store};
-            if constexpr (WINO && src == 0) half_steps_wino<GJ::TWH, GJ::PLANE, T>(wacc, hb, ring, sm, wave, lane);
+            if constexpr (WINO && src == 0) half_steps_wino<GJ::TWH, GJ::PLANE, T, KS0>(wacc, hb, ring, sm, wave, lane);
+            else if constexpr (WINO3_J) half_steps_wino<GJ::TWH, GJ::PLANE, T, 3>(wacc, hb, ring, sm, wave, lane);
             else if constexpr (WINO) half_steps_pairs<GJ::TWH, GJ::PLANE, T>(wacc, hb, ring, sm, wave, lane);
             else if constexpr (QUAD) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN, true, FACTOR>(qa, hb, ring, sm, wave, lane);
             else if constexpr (PREC == 0) half_steps_f32<GJ::TWH, GJ::PLANE, KSJ, T, NTN>(acc, hb, ring, sm, wave, lane);
@@ -2592,7 +2607,7 @@ static hipError_t launch_with_lds(K kern, const StageArgs& a, int nblk, size_t l
 }
 
 template <int TH, int PREC>
-static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int nblk, bool img_u8, bool out_u8, bool wino,
+static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int nblk, bool img_u8, bool out_u8, bool wino, int wino5,
                                  hipStream_t s) {
     switch (stage) {
         case 1:
@@ -2601,7 +2616,11 @@ static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int 
             return launch_with_lds(conv_stage_kernel<TH, 1, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 2:
             if constexpr (PREC == 0)
-                if (wino) return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, 0, 3, true>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+                if (wino) {
+                    if (wino5 == 1) return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, 0, 3, true, 1>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+                    if (wino5 == 2) return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, 0, 3, true, 2>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+                    return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, 0, 3, true>, a, nblk, stage_lds_bytes<TH, 5>(), s);
+                }
             return launch_with_lds(conv_stage_kernel<TH, 2, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 3: return launch_with_lds(conv_stage_kernel<TH, 3, 5, false, false, false, PREC>, a, nblk, stage_lds_bytes<TH, 5>(), s);
         case 4:
@@ -2620,7 +2639,7 @@ static hipError_t launch_stage_t(int stage, int factor, const StageArgs& a, int 
 
 // Pipe form (both tile classes of the launch): grid = co-resident workgroups, LDS = two half tiles + ring + mailbox.
 template <int PREC>
-static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a, int grid, bool img_u8, bool out_u8, bool wino, hipStream_t s) {
+static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a, int grid, bool img_u8, bool out_u8, bool wino, int wino5, hipStream_t s) {
     constexpr size_t lds5 = 2 * (size_t)HalfTile<5>::BYTES + kRingBytes + 16;
     // + bilinear weights per N-tile, byte / 255 table, and (one N-tile: factor 2, 3) the bilinear taps' own image tile of (8 + 2) x (32 + 2) pixels
     constexpr size_t lds3_1 = 2 * (size_t)HalfTile<3>::BYTES + kRingBytes + 16 + 9 * 128 * sizeof(float) + 256 * sizeof(float) + 10 * 34 * 16;
@@ -2634,7 +2653,11 @@ static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a,
             return launch_with_lds(conv_stage_pipe_kernel<1, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 2:
             if constexpr (PREC == 0)
-                if (wino) return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, 0, 3, true>, a, grid, lds5, s);
+                if (wino) {
+                    if (wino5 == 1) return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, 0, 3, true, 1>, a, grid, lds5, s);
+                    if (wino5 == 2) return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, 0, 3, true, 2>, a, grid, lds5, s);
+                    return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, 0, 3, true>, a, grid, lds5, s);
+                }
             return launch_with_lds(conv_stage_pipe_kernel<2, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 3: return launch_with_lds(conv_stage_pipe_kernel<3, 5, false, false, false, PREC>, a, grid, lds5, s);
         case 4:
@@ -2650,16 +2673,17 @@ static hipError_t launch_stage_pipe_t(int stage, int factor, const StageArgs& a,
     }
     return hipErrorInvalidValue;
 }
-hipError_t sr_launch_stage_pipe(int stage, int factor, const StageArgs& a, int prec, int grid, bool img_u8, bool out_u8, bool wino, hipStream_t s) {
-    return prec == 0 ? launch_stage_pipe_t<0>(stage, factor, a, grid, img_u8, out_u8, wino, s)
-                     : launch_stage_pipe_t<1>(stage, factor, a, grid, img_u8, out_u8, wino, s);
+hipError_t sr_launch_stage_pipe(int stage, int factor, const StageArgs& a, int prec, int grid, bool img_u8, bool out_u8, bool wino, int wino5,
+                                hipStream_t s) {
+    return prec == 0 ? launch_stage_pipe_t<0>(stage, factor, a, grid, img_u8, out_u8, wino, wino5, s)
+                     : launch_stage_pipe_t<1>(stage, factor, a, grid, img_u8, out_u8, wino, wino5, s);
 }
 
 hipError_t sr_launch_stage(int stage, int factor, const StageArgs& a, int th, int prec, int nblk, bool img_u8,
-                           bool out_u8, bool wino, hipStream_t s) {
+                           bool out_u8, bool wino, int wino5, hipStream_t s) {
     if (prec == 0)
-        return th == 8 ? launch_stage_t<8, 0>(stage, factor, a, nblk, img_u8, out_u8, wino, s)
-                       : launch_stage_t<4, 0>(stage, factor, a, nblk, img_u8, out_u8, wino, s);
-    return th == 8 ? launch_stage_t<8, 1>(stage, factor, a, nblk, img_u8, out_u8, wino, s)
-                   : launch_stage_t<4, 1>(stage, factor, a, nblk, img_u8, out_u8, wino, s);
+        return th == 8 ? launch_stage_t<8, 0>(stage, factor, a, nblk, img_u8, out_u8, wino, wino5, s)
+                       : launch_stage_t<4, 0>(stage, factor, a, nblk, img_u8, out_u8, wino, wino5, s);
+    return th == 8 ? launch_stage_t<8, 1>(stage, factor, a, nblk, img_u8, out_u8, wino, wino5, s)
+                   : launch_stage_t<4, 1>(stage, factor, a, nblk, img_u8, out_u8, wino, wino5, s);
 }

@@ -42,6 +42,7 @@ ap.add_argument("--prec", default="split_f16")
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--hw", default="1080x1920")
+ap.add_argument("--per-round", action="store_true", help="also print stage 2's and the wall time of every round")
 ap.add_argument("libs", nargs="+")
 a = ap.parse_args()
 H, W = map(int, a.hw.split("x"))
@@ -51,9 +52,9 @@ for rnd in range(a.rounds):
         path, *envs = lib.split("@")  # lib.so@SRHIP_TAIL=0@SRHIP_BW=8 ...
         env = dict(os.environ, SRHIP_LIB=os.path.abspath(path), **dict(e.split("=", 1) for e in envs))
         r = subprocess.run([sys.executable, "-c", CHILD, a.prec, str(H), str(W), str(a.reps)], env=env, capture_output=True, text=True, timeout=300)
-        if r.returncode != 0:
-            print(lib, "FAILED", r.stderr[-500:])
-            continue
+        if r.returncode != 0:  # a child that failed may have faulted the GPU: start nothing more on it
+            print(lib, "FAILED", r.returncode, r.stderr[-500:])
+            sys.exit(1)
         d = json.loads(r.stdout.strip().splitlines()[-1])
         res[lib].append(d["stages"] + [sum(d["stages"]), d["wall"]])
 for lib, v in res.items():
@@ -61,3 +62,5 @@ for lib, v in res.items():
         m = np.median(np.array(v), axis=0)
         mn = np.min(np.array(v), axis=0)
         print(f"{a.prec} {a.hw} {os.path.basename(lib):40s} stages {' '.join(f'{x:7.4f}' for x in m[:5])}  sum {m[5]:.4f}  wall {m[6]:.4f}  (min sum {mn[5]:.4f})", flush=True)
+        if a.per_round:  # what each round gave: the spread between a library's own rounds is the A/B's noise floor
+            print(f"    rounds: stage 2 {' '.join(f'{r[2]:.4f}' for r in v)} | wall {' '.join(f'{r[6]:.4f}' for r in v)}", flush=True)
