@@ -489,6 +489,57 @@ int sr_pool_validation_error_ensemble_rgba8(sr_ctx* ctx, const uint8_t* hr, int 
 int sr_pair_validation_error_ensemble_rgba8(sr_ctx* ctx, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh,
                                             int lw, int linear_loss, unsigned members, double* err_sum, size_t* n_elems);
 
+/* ---- Metrics: Y-channel PSNR and SSIM, the super-resolution benchmark protocol ----
+ * The reference scores a parameter file by one pooled RGB MSE (main.rs:236-246, the validation calls above).  Papers and leaderboards
+ * score the 8-bit luma of the saved image, with a border shaved off, per image.  Two operands A (the scored image) and B (the ground
+ * truth), both H x W, 8-bit RGB; alpha is dropped, as img_to_data drops it.  Where A is the network's f32 output (the validation forms
+ * below) it is quantised on load by data_to_img's rule, clamp(floor(255 v + 0.5), 0, 255) in f32: the scores are exactly those of the
+ * pixels `rusty_sr IN OUT` would save, and no u8 copy of the output is written.
+ *   Luma      Y = (65481 R + 128553 G + 24966 B + 127500) div 255000 + 16, in integer arithmetic: round(16 + (65.481 R + 128.553 G +
+ *             24.966 B) / 255), MATLAB's rgb2ycbcr on uint8, ties upward (194 of the 2^24 colours sit exactly on .5, and the double
+ *             formula misses the exact value on 39).  Y is in [16, 235].
+ *   Shave     s >= 0 pixels are removed from each border; the scored region is (H - 2s) x (W - 2s).  shave = -1 means the context's
+ *             factor f, the protocol's value; anything below is SR_E_INVALID before any launch.  In the validation forms H x W is the
+ *             top-left f floor(h/f) x f floor(w/f) crop of the HR image, the one the loss uses.
+ *   Y-PSNR    y_sq_err = sum of (Y_A - Y_B)^2 over the region, an exact integer; y_count = the region's pixels.  Per image the PSNR is
+ *             10 log10(255^2 y_count / y_sq_err), and inf at zero error.
+ *   SSIM      (Wang et al. 2004, as the benchmark scripts apply it.)  Window: 11 x 11 Gaussian, sigma 1.5, g_i = exp(-(i - 5)^2 / 4.5) /
+ *             sum, applied separably (rows, then columns); only "valid" positions inside the region count: ssim_count = (H - 2s - 10)
+ *             (W - 2s - 10).  C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2; mu = filt(Y), var = filt(Y^2) - mu^2, cov = filt(Y_A Y_B) -
+ *             mu_A mu_B; the map is ((2 mu_A mu_B + C1)(2 cov + C2)) / ((mu_A^2 + mu_B^2 + C1)(var_A + var_B + C2)); ssim_sum is the
+ *             f64 sum of the map, and per image the SSIM is ssim_sum / ssim_count.
+ *   Arithmetic  The weights are an f64 table computed once on the host; filters, map and sum are f64 (in f32, filt(Y^2) - mu^2 cancels
+ *             at 65 025 and the mean is off by 4e-5 on a bright image).  One partial per workgroup of SR_METRICS_TILE x SR_METRICS_TILE
+ *             region pixels, a grid that depends on the shape alone, one workgroup adding the partials in a fixed order, no atomics:
+ *             the same bits on every run, context and device.  Identical operands give ssim_sum == ssim_count exactly.
+ *   Degenerate sizes are not errors: a region with a side below 11 has ssim_count = 0 and ssim_sum = 0; an empty region also y_count =
+ *             0 and y_sq_err = 0.
+ * u8 images only: the scores are defined on 8-bit images.  A job that does not fit is SR_E_NOMEM and leaves the context usable. */
+#define SR_METRICS_TILE 32
+typedef struct sr_metrics { uint64_t y_sq_err, y_count; double ssim_sum; uint64_t ssim_count; } sr_metrics;
+/* Two images the caller holds (h x w x a_channels and h x w x b_channels bytes, 3 or 4 channels each); no network runs, and a context of
+ * any graph will do -- so a bilinear or foreign upscaler's output can be scored.  Synchronous, host memory: */
+int sr_image_metrics_rgba8(sr_ctx* ctx, const uint8_t* a, int a_channels, const uint8_t* b, int b_channels, int h, int w, int shave,
+                           sr_metrics* metrics);
+/* ... device memory: ordered on `stream` alone, no host synchronisation.  d_a and d_b may start at any byte (read as whole aligned 32-bit
+ * words, nothing outside the words of the image).  d_result16 (device memory, 4-byte aligned) receives 16 bytes: the uint64 y_sq_err, then
+ * the double ssim_sum; the counts follow from h, w and shave. */
+int sr_image_metrics_rgba8_dev(sr_ctx* ctx, const uint8_t* d_a, int a_channels, const uint8_t* d_b, int b_channels, int h, int w, int shave,
+                               void* d_result16, void* stream);
+/* sr_validation_error_rgba8 / sr_pair_validation_error_rgba8 (members = 0) or their ensemble forms (members = the mask) with the scores
+ * of the same run of the network: A = the quantised output, B = the HR crop.  err_sum and n_elems are the bits of those calls; one more
+ * pass behind the loss does the scoring.  The context's precision applies, and the split-half mode's recomputation in exact f32. */
+int sr_pool_validation_metrics_rgba8(sr_ctx* ctx, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, unsigned members, int shave,
+                                double* err_sum, size_t* n_elems, sr_metrics* metrics);
+int sr_pair_validation_metrics_rgba8(sr_ctx* ctx, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
+                                     int linear_loss, unsigned members, int shave, double* err_sum, size_t* n_elems, sr_metrics* metrics);
+/* ... device memory, like sr_validation_error_rgba8_dev / sr_pair_validation_error_rgba8_dev (no ensemble): d_err_sum one double,
+ * d_result16 the 16 bytes above, both 4-byte aligned. */
+int sr_pool_validation_metrics_rgba8_dev(sr_ctx* ctx, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss, int shave,
+                                    double* d_err_sum, void* d_result16, void* stream);
+int sr_pair_validation_metrics_rgba8_dev(sr_ctx* ctx, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
+                                         int linear_loss, int shave, double* d_err_sum, void* d_result16, void* stream);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -1,7 +1,7 @@
 //! rusty_sr -- Rust host over libsrhip (the MI355X engine).
 //!
 //!     rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
-//!     rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] <VALIDATION_FOLDER>
+//!     rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--metrics [--shave N]] <VALIDATION_FOLDER>
 //!
 //! Same arguments, progress text and failure text as millardjn/rusty_sr v1; decoding and encoding
 //! of image files stay with the `image` crate as in the reference, everything between the decoded
@@ -88,6 +88,7 @@ fn parse_args() -> Options {
                     _ => usage_error(&format!("'{}' isn't a valid value for '--precision <MODE>'", v)),
                 }
             }
+            "--metrics" | "--shave" => usage_error(&format!("The argument '{}' can only be used with the 'validate' subcommand", a)),
             s if s.len() > 1 && s.starts_with('-') => {
                 usage_error(&format!("Found argument '{}' which wasn't expected, or isn't valid in this context", s))
             }
@@ -147,8 +148,9 @@ fn collect_files(dir: &Path, recurse: bool, out: &mut Vec<std::path::PathBuf>) {
 /// (main.rs:83-114).  Files are decoded on a second thread ahead of the GPU; PSNR = -10 log10(sum err / sum n) (main.rs:236-246).
 fn validate(args: Vec<String>) {
     let (mut parameters, mut custom, mut folder): (Option<String>, Option<String>, Option<String>) = (None, None, None);
-    let (mut linear, mut recurse, mut split_f16, mut timing) = (false, false, false, false);
+    let (mut linear, mut recurse, mut split_f16, mut timing, mut metrics) = (false, false, false, false, false);
     let mut val_max: Option<usize> = None;
+    let mut shave: Option<i32> = None;  // --metrics: None = the factor
     let mut devices: Vec<i32> = Vec::new();
     let mut it = args.into_iter();
     while let Some(a) = it.next() {
@@ -161,12 +163,20 @@ fn validate(args: Vec<String>) {
         match a.as_str() {
             "-h" | "--help" => {
                 println!("USAGE:\n    rusty_sr validate [-l|--linearLoss] [-r|--recurse] [-m|--val_max N] [-p PARAMETERS | -c PARAMETER_FILE] \
-                          [--precision f32|split_f16] [--devices N,N,...] [--timing] <VALIDATION_FOLDER>");
+                          [--precision f32|split_f16] [--devices N,N,...] [--timing] [--metrics [--shave N]] <VALIDATION_FOLDER>");
                 exit(0)
             }
             "-l" | "--linearLoss" => linear = true,
             "-r" | "--recurse" => recurse = true,
             "--timing" => timing = true,
+            "--metrics" => metrics = true,
+            "--shave" => {
+                let v = value("--shave <N>");
+                match v.parse::<i32>() {
+                    Ok(n) if n >= 0 => shave = Some(n),
+                    _ => validate_usage_error(&format!("'{}' isn't a valid value for '--shave <N>'", v)),
+                }
+            }
             "-d" | "--downsample" => validate_usage_error("The argument '--downsample' cannot be used with 'validate'"),
             "-p" | "--parameters" => parameters = Some(value("--parameters <PARAMETERS>")),
             "-c" | "--custom" => custom = Some(value("--custom <PARAMETER_FILE>")),
@@ -207,6 +217,9 @@ fn validate(args: Vec<String>) {
         validate_usage_error("The argument '--custom <PARAMETER_FILE>' cannot be used with '--parameters <PARAMETERS>'");
     }
     let folder = folder.unwrap_or_else(|| validate_usage_error("The following required arguments were not provided:\n    <VALIDATION_FOLDER>"));
+    if shave.is_some() && !metrics {
+        validate_usage_error("The following required arguments were not provided:\n    --metrics");
+    }
     if !Path::new(&folder).is_dir() {
         validate_usage_error(&format!("'{}' is not a folder", folder));
     }
@@ -256,17 +269,40 @@ fn validate(args: Vec<String>) {
     });
     let t0 = std::time::Instant::now();
     let (mut err_sum, mut n_sum) = (0f64, 0f64);
+    let (mut y_sum, mut y_n, mut s_sum, mut s_n) = (0f64, 0usize, 0f64, 0usize);  // --metrics: per-image means
     for (i, (path, img)) in rx.iter().enumerate() {
         let rgba = img.unwrap_or_else(|_| die(&format!("Error opening validation image file {}", path.display())));
         let (w, h) = rgba.dimensions();
         let k = i % engines.len();
-        let (e, n) = engines[k].validation_error(&rgba.into_raw(), w, h, linear).unwrap_or_else(|err| die(&format!("{}: {}", path.display(), err)));
+        let (e, n) = if metrics {
+            let (e, n, m) = engines[k].validation_metrics(&rgba.into_raw(), w, h, linear, 0, shave.unwrap_or(-1))
+                .unwrap_or_else(|err| die(&format!("{}: {}", path.display(), err)));
+            if m.y_count > 0 {
+                y_sum += if m.y_sq_err == 0 { std::f64::INFINITY } else { 10.0 * (65025.0 * m.y_count as f64 / m.y_sq_err as f64).log10() };
+                y_n += 1;
+            } else {
+                let _ = writeln!(std::io::stderr(), "{}: nothing left after the shave, left out of Y-PSNR", path.display());
+            }
+            if m.ssim_count > 0 {
+                s_sum += m.ssim_sum / m.ssim_count as f64;
+                s_n += 1;
+            } else {
+                let _ = writeln!(std::io::stderr(), "{}: too small for an 11x11 window after the shave, left out of SSIM", path.display());
+            }
+            (e, n)
+        } else {
+            engines[k].validation_error(&rgba.into_raw(), w, h, linear).unwrap_or_else(|err| die(&format!("{}: {}", path.display(), err)))
+        };
         err_sum += e;
         n_sum += n as f64;
     }
     let _ = decoder.join();
     let psnr = if err_sum == 0.0 { std::f32::INFINITY } else { (-10.0 * (err_sum / n_sum).log10()) as f32 };
     println!("Validation PSNR:\t{}", psnr);  // main.rs:246
+    if metrics {
+        println!("Y-PSNR:\t{}", if y_n > 0 { (y_sum / y_n as f64) as f32 } else { std::f32::NAN });
+        println!("SSIM:\t{}", if s_n > 0 { (s_sum / s_n as f64) as f32 } else { std::f32::NAN });
+    }
     if timing {
         let s = t0.elapsed().as_secs_f64();
         let _ = writeln!(std::io::stderr(), "[timing] {} images in {:.3} s: {:.2} images/s", files.len(), s, files.len() as f64 / s);

@@ -42,6 +42,16 @@ pub struct SrTrainCrop {
     pub x0: c_int,
 }
 
+/// `sr_metrics`: the sums and counts the Y-PSNR and the SSIM of one image are made of.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrMetrics {
+    pub y_sq_err: u64,
+    pub y_count: u64,
+    pub ssim_sum: f64,
+    pub ssim_count: u64,
+}
+
 pub const SR_OK: c_int = 0;
 pub const SR_E_HIP: c_int = -5;
 pub const SR_GRAPH_SR_NET: c_int = 0;
@@ -149,6 +159,12 @@ extern "C" {
     pub fn sr_upscale_ensemble_rgba8(ctx: *mut SrCtx, input: *const u8, in_channels: c_int, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, members: c_uint) -> c_int;
     pub fn sr_pool_validation_error_ensemble_rgba8(ctx: *mut SrCtx, hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, members: c_uint, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
     pub fn sr_pair_validation_error_ensemble_rgba8(ctx: *mut SrCtx, lr: *const u8, lr_channels: c_int, hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, members: c_uint, err_sum: *mut f64, n_elems: *mut usize) -> c_int;
+    pub fn sr_image_metrics_rgba8(ctx: *mut SrCtx, a: *const u8, a_channels: c_int, b: *const u8, b_channels: c_int, h: c_int, w: c_int, shave: c_int, metrics: *mut SrMetrics) -> c_int;
+    pub fn sr_image_metrics_rgba8_dev(ctx: *mut SrCtx, d_a: *const u8, a_channels: c_int, d_b: *const u8, b_channels: c_int, h: c_int, w: c_int, shave: c_int, d_result16: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn sr_pool_validation_metrics_rgba8(ctx: *mut SrCtx, hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, members: c_uint, shave: c_int, err_sum: *mut f64, n_elems: *mut usize, metrics: *mut SrMetrics) -> c_int;
+    pub fn sr_pair_validation_metrics_rgba8(ctx: *mut SrCtx, lr: *const u8, lr_channels: c_int, hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, members: c_uint, shave: c_int, err_sum: *mut f64, n_elems: *mut usize, metrics: *mut SrMetrics) -> c_int;
+    pub fn sr_pool_validation_metrics_rgba8_dev(ctx: *mut SrCtx, d_hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, shave: c_int, d_err_sum: *mut f64, d_result16: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn sr_pair_validation_metrics_rgba8_dev(ctx: *mut SrCtx, d_lr: *const u8, lr_channels: c_int, d_hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, shave: c_int, d_err_sum: *mut f64, d_result16: *mut c_void, stream: *mut c_void) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.
@@ -213,6 +229,18 @@ impl Engine {
             sr_validation_error_rgba8(self.ctx, rgba.as_ptr(), 4, h as c_int, w as c_int, linear_loss as c_int, &mut err, &mut n)
         };
         if rc == SR_OK { Ok((err, n)) } else { Err(strerror(rc)) }
+    }
+
+    /// `validation_error` with the benchmark protocol's scores of the same run (sr_pool_validation_metrics_rgba8): shave -1 = the factor.
+    pub fn validation_metrics(&mut self, rgba: &[u8], w: u32, h: u32, linear_loss: bool, members: c_uint, shave: c_int)
+                              -> Result<(f64, usize, SrMetrics), String> {
+        assert_eq!(rgba.len(), w as usize * h as usize * 4);
+        let (mut err, mut n, mut m) = (0f64, 0usize, SrMetrics::default());
+        let rc = unsafe {
+            sr_pool_validation_metrics_rgba8(self.ctx, rgba.as_ptr(), 4, h as c_int, w as c_int, linear_loss as c_int, members, shave, &mut err,
+                                        &mut n, &mut m)
+        };
+        if rc == SR_OK { Ok((err, n, m)) } else { Err(strerror(rc)) }
     }
 
     pub fn set_precision(&mut self, mode: c_int) -> Result<(), String> {

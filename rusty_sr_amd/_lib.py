@@ -19,6 +19,7 @@ SR_TRAIN_STORE_AUTO = (1 << (8 * C.sizeof(C.c_size_t))) - 1
 SR_TRAIN_MAX_BATCH = 64
 SR_TRAIN_RING = 64
 SR_ENSEMBLE_ALL, SR_ENSEMBLE_FLIPS, SR_ENSEMBLE_HFLIP = 0xFF, 0x0F, 0x03
+SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
 class TrainCrop(C.Structure):
@@ -31,6 +32,11 @@ class TrainPairCrop(C.Structure):
     """sr_train_pair_crop (include/srhip.h): a resident pair id, or -1 and both images' host pixels; the crop origin in LR pixels."""
     _fields_ = [("pair", C.c_int), ("lr_px", C.c_void_p), ("hr_px", C.c_void_p), ("lr_channels", C.c_int), ("hr_channels", C.c_int),
                 ("lh", C.c_int), ("lw", C.c_int), ("y0", C.c_int), ("x0", C.c_int)]
+
+
+class Metrics(C.Structure):
+    """sr_metrics (include/srhip.h): the sums and counts the Y-PSNR and the SSIM of one image are made of."""
+    _fields_ = [("y_sq_err", C.c_uint64), ("y_count", C.c_uint64), ("ssim_sum", C.c_double), ("ssim_count", C.c_uint64)]
 
 
 # every symbol include/srhip.h declares: (restype, argtypes)
@@ -113,6 +119,12 @@ SYMBOLS = {
     "sr_upscale_ensemble_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, _u8p, C.c_uint]),
     "sr_pool_validation_error_ensemble_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, C.c_uint, _dp, C.POINTER(_sz)]),
     "sr_pair_validation_error_ensemble_rgba8": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, _i, C.c_uint, _dp, C.POINTER(_sz)]),
+    "sr_image_metrics_rgba8": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, _i, C.POINTER(Metrics)]),
+    "sr_image_metrics_rgba8_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_pool_validation_metrics_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, C.c_uint, _i, _dp, C.POINTER(_sz), C.POINTER(Metrics)]),
+    "sr_pair_validation_metrics_rgba8": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, _i, C.c_uint, _i, _dp, C.POINTER(_sz), C.POINTER(Metrics)]),
+    "sr_pool_validation_metrics_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_pair_validation_metrics_rgba8_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -134,6 +134,9 @@ struct sr_ctx {
     void* d_ein = nullptr; size_t ein_cap = 0;      // T_k of the caller's image, f32 RGB
     void* d_eout = nullptr; size_t eout_cap = 0;    // one member's f32 output map
     void* d_eacc = nullptr; size_t eacc_cap = 0;    // the f32 accumulator of a call with RGBA8 output (an f32 call accumulates in its output)
+    // ---- metrics (sr_metrics.cpp): grown on demand, freed by sr_destroy
+    void* d_mpart = nullptr; size_t mpart_cap = 0;  // the tile kernel's partials (f64, then u64), then the host-pointer calls' 16-byte result
+    void* d_mimg = nullptr; size_t mimg_cap = 0;    // both images of a host-pointer sr_image_metrics_rgba8 call
     size_t total_mem = 0;                           // the device's memory, asked for once: a shape beyond it is refused without an allocation
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
@@ -291,6 +294,27 @@ hipError_t sr_launch_valid_loss(const float* d_out, const void* d_hr, bool hr_u8
 // The f64 partials of a loss kernel -> their sum, one double at d_result (4-byte aligned): one workgroup, a fixed order of additions, so
 // the same bits on every run, context and device (also the backward pass's err_sum)
 hipError_t sr_launch_loss_sum(const double* d_partial, int n, void* d_result, hipStream_t s);
+
+// ---- metrics (sr_metrics.hip kernels, sr_metrics.cpp host side; include/srhip.h "Metrics")
+void sr_metrics_release(sr_ctx* c);  // free the metrics buffers (called by sr_destroy)
+long sr_metrics_blocks(int H, int W, int shave);  // workgroups (= partials) of the tile kernel: a function of the shape alone; 0: an empty region
+// Scores of A (H x W; u8 with a_ch channels at any byte and pitch_a pixels per row, or the contiguous, 16-byte aligned f32 RGB output, quantised
+// on load) against B (u8, b_ch channels, any byte, pitch_b pixels per row) -> 16 bytes at d_result16 (4-byte aligned): u64 y_sq_err, f64
+// ssim_sum.  weights: the window's 11 f64 weights (host memory); d_partial: 16 sr_metrics_blocks(..) bytes.
+hipError_t sr_launch_metrics(const void* d_a, bool a_u8, int a_ch, long pitch_a, const uint8_t* d_b, int b_ch, long pitch_b, int H, int W,
+                             int shave, const double* weights, void* d_partial, void* d_result16, hipStream_t s);
+// What a validation call may ask for beside its loss (sr_valid.cpp run_validation): the scores of its quantised output against the HR image.
+struct sr_metrics_request {
+    int shave = 0;               // >= 0: resolved and checked by sr_metrics_shave
+    void* d_result16 = nullptr;  // nullptr: the context's own slot (sr_metrics_slot), for the host-pointer calls
+};
+int sr_metrics_shave(const sr_ctx* c, int shave, int* out);  // -1 -> the context's factor; below that SR_E_INVALID
+int sr_metrics_reserve(sr_ctx* c, int H, int W, int shave);  // grow the partials buffer for such a call (sr_metrics_queue does it too)
+// queue the scoring of an H x W image pair on s (the arguments are the caller's to have checked); the context's device is current
+int sr_metrics_queue(sr_ctx* c, const void* d_a, bool a_u8, int a_ch, long pitch_a, const uint8_t* d_b, int b_ch, long pitch_b, int H, int W,
+                     const sr_metrics_request& rq, hipStream_t s);
+void* sr_metrics_slot(const sr_ctx* c, int H, int W, int shave);  // where a request without d_result16 left its 16 bytes
+void sr_metrics_fill(sr_metrics* m, const void* result16, int H, int W, int shave);  // the counts, and the two sums from the 16 bytes
 
 // ---- backpropagation (sr_grad.hip kernels, sr_grad.cpp host side)
 void sr_grad_release(sr_ctx* c);  // sr_grad.cpp: free the backprop buffers (called by sr_destroy)

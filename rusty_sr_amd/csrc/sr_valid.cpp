@@ -44,9 +44,11 @@ int check_pair_args(sr_ctx* c, const void* lr, bool u8, int lr_ch, const void* h
 
 // Pool (or, with lr, a paired call's LR image in its place), network, loss on device buffers, queued on s; the sum lands at d_result
 // (nullptr: the slot behind the partials, for the host-pointer calls).  members: 0 = the network's output as it is, else the mask of a
-// self-ensemble (sr_ensemble.cpp) whose output takes its place.  The context's device is current.
+// self-ensemble (sr_ensemble.cpp) whose output takes its place.  metrics (u8 HR images only): also score the quantised output against the
+// HR crop (sr_metrics.cpp), one more pass behind the loss; without it the call's launches are exactly the loss's.  The context's device
+// is current.
 int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w, bool linear, void* d_result, hipStream_t s,
-                   const sr_lr_input* lr, unsigned members = 0) {
+                   const sr_lr_input* lr, unsigned members = 0, const sr_metrics_request* metrics = nullptr) {
     const int f = c->factor, OH = h / f, OW = w / f, HC = f * OH, WC = f * OW;
     const int grid = sr_valid_loss_grid(HC, WC);
     const size_t lr_bytes = (size_t)OH * OW * 3 * sizeof(float), out_bytes = (size_t)HC * WC * 3 * sizeof(float);
@@ -54,6 +56,7 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
     if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vlr, &c->vlr_cap, lr_bytes);
     if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vout, &c->vout_cap, out_bytes);
     if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vpart, &c->vpart_cap, (size_t)(grid + 1) * sizeof(double));
+    if (rc == SR_OK && metrics) rc = sr_metrics_reserve(c, HC, WC, metrics->shave);
     c->vnode_h = c->vnode_w = 0;
     if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
         sr_free_buf(c->d_vlr, c->vlr_cap);
@@ -68,18 +71,22 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
     if (rc != SR_OK) return rc;
     HIPCHK(c, sr_launch_valid_loss((const float*)c->d_vout, d_hr, hr_u8, ch, linear, w, HC, WC, c->d_vtab, (double*)c->d_vpart, d_result, s));
     c->vnode_h = OH; c->vnode_w = OW;
+    if (metrics) return sr_metrics_queue(c, c->d_vout, false, 3, WC, (const uint8_t*)d_hr, ch, w, HC, WC, *metrics, s);
     return SR_OK;
 }
 
 // The host-pointer calls: upload, run, download 8 bytes, on the context's own stream; synchronous.  In the split-half mode a value that
 // left its domain makes the whole call run again in exact f32, as the host-pointer upscale calls do (include/srhip.h sr_set_precision).
 // lr: nullptr = the pooled form, h x w the HR size; else (pair) h x w is the LR size and lr_ch its channel count.
-// ensemble: `members` is a self-ensemble's mask (checked here), else it is not looked at.
+// ensemble: `members` is a self-ensemble's mask (checked here), else it is not looked at.  metrics (with its shave as the caller gave
+// it; u8 only): the scores of the same run of the network, beside the loss.
 int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool hr_u8, int ch, int h, int w, int linear, double* err_sum,
-                    size_t* n_elems, bool pair, bool ensemble = false, unsigned members = 0) {
+                    size_t* n_elems, bool pair, bool ensemble = false, unsigned members = 0, sr_metrics* metrics = nullptr, int shave = 0) {
     sr_plan_clear(c);
     int rc = pair ? check_pair_args(c, lr, hr_u8, lr_ch, hr, ch, h, w) : check_args(c, hr, hr_u8, ch, h, w);
     if (rc == SR_OK && ensemble) rc = sr_ensemble_check(c, members, pair ? h : h / c->factor, pair ? w : w / c->factor);
+    sr_metrics_request rq;
+    if (rc == SR_OK && metrics) rc = sr_metrics_shave(c, shave, &rq.shave);
     if (rc != SR_OK) return rc;
     if (!ensemble) members = 0;
     if (!err_sum || !n_elems) return SR_E_INVALID;
@@ -107,9 +114,13 @@ int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool h
     sr_lr_input in;
     in.d_lr = (char*)c->d_vhr + sr_round256(hr_bytes); in.u8 = hr_u8; in.ch = lr_ch;
     if (pair) HIPCHK(c, hipMemcpyAsync((void*)in.d_lr, lr, lr_bytes, hipMemcpyHostToDevice, s));
-    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr, members);
+    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr, members, metrics ? &rq : nullptr);
     double sum = 0.0;
-    const hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(&sum, (double*)c->d_vpart + grid, sizeof sum, hipMemcpyDeviceToHost, s) : hipSuccess;
+    unsigned char scores[16] = {0};
+    const int HC = f * (h / f), WC = f * (w / f);
+    hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(&sum, (double*)c->d_vpart + grid, sizeof sum, hipMemcpyDeviceToHost, s) : hipSuccess;
+    if (rc == SR_OK && metrics && e1 == hipSuccess)
+        e1 = hipMemcpyAsync(scores, sr_metrics_slot(c, HC, WC, rq.shave), sizeof scores, hipMemcpyDeviceToHost, s);
     if (profiled && e1 == hipSuccess && rc == SR_OK) profiled = hipEventRecord(c->ev[7], s) == hipSuccess;
     const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
     if (rc != SR_OK) return rc;
@@ -118,7 +129,8 @@ int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool h
     if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
         *(volatile int*)c->h_domain = 0;
         (void)sr_set_precision(c, SR_PRECISION_F32);
-        rc = validation_host(c, lr, lr_ch, hr, hr_u8, ch, pair ? lh : h, pair ? lw : w, linear, err_sum, n_elems, pair, ensemble, members);
+        rc = validation_host(c, lr, lr_ch, hr, hr_u8, ch, pair ? lh : h, pair ? lw : w, linear, err_sum, n_elems, pair, ensemble, members, metrics,
+                             shave);
         (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
         ++c->domain_fallbacks;
         return rc;
@@ -129,6 +141,7 @@ int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool h
     }
     *err_sum = sum;
     *n_elems = sr_loss_elems(f, 1, h, w);
+    if (metrics) sr_metrics_fill(metrics, scores, HC, WC, rq.shave);
     return SR_OK;
 }
 
@@ -198,6 +211,49 @@ int sr_pool_validation_error_ensemble_rgba8(sr_ctx* c, const uint8_t* hr, int in
 int sr_pair_validation_error_ensemble_rgba8(sr_ctx* c, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
                                             int linear_loss, unsigned members, double* err_sum, size_t* n_elems) {
     return validation_host(c, lr, lr_channels, hr, true, hr_channels, lh, lw, linear_loss, err_sum, n_elems, true, true, members);
+}
+
+int sr_pool_validation_metrics_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, unsigned members, int shave,
+                                double* err_sum, size_t* n_elems, sr_metrics* metrics) {
+    if (!metrics) return SR_E_INVALID;
+    return validation_host(c, nullptr, 3, hr, true, in_channels, h, w, linear_loss, err_sum, n_elems, false, members != 0, members, metrics, shave);
+}
+
+int sr_pair_validation_metrics_rgba8(sr_ctx* c, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
+                                     int linear_loss, unsigned members, int shave, double* err_sum, size_t* n_elems, sr_metrics* metrics) {
+    if (!metrics) return SR_E_INVALID;
+    return validation_host(c, lr, lr_channels, hr, true, hr_channels, lh, lw, linear_loss, err_sum, n_elems, true, members != 0, members, metrics,
+                           shave);
+}
+
+int sr_pool_validation_metrics_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss, int shave, double* d_err_sum,
+                                    void* d_result16, void* stream) {
+    sr_plan_clear(c);
+    int rc = check_args(c, d_hr, true, in_channels, h, w);
+    sr_metrics_request rq;
+    if (rc == SR_OK) rc = sr_metrics_shave(c, shave, &rq.shave);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !d_result16 || !sr_dword_aligned(d_result16)) return SR_E_INVALID;
+    rq.d_result16 = d_result16;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    return run_validation(c, d_hr, true, in_channels, h, w, linear_loss != 0, d_err_sum, (hipStream_t)stream, nullptr, 0, &rq);
+}
+
+int sr_pair_validation_metrics_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
+                                         int linear_loss, int shave, double* d_err_sum, void* d_result16, void* stream) {
+    sr_plan_clear(c);
+    int rc = check_pair_args(c, d_lr, true, lr_channels, d_hr, hr_channels, lh, lw);
+    sr_metrics_request rq;
+    if (rc == SR_OK) rc = sr_metrics_shave(c, shave, &rq.shave);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !d_result16 || !sr_dword_aligned(d_result16)) return SR_E_INVALID;
+    rq.d_result16 = d_result16;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    sr_lr_input in;
+    in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
+    return run_validation(c, d_hr, true, hr_channels, c->factor * lh, c->factor * lw, linear_loss != 0, d_err_sum, (hipStream_t)stream, &in, 0, &rq);
 }
 
 int sr_read_validation_nodes(sr_ctx* c, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out) {

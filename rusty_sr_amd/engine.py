@@ -467,6 +467,88 @@ class Engine:
                                                       C.c_void_p(grad.data_ptr()), self._stream_ptr(stream, hr.device)), self._ctx)
         return err, grad
 
+    # ---- metrics: Y-channel PSNR and SSIM of the benchmark protocol (include/srhip.h, "Metrics") ----
+    @staticmethod
+    def _metrics_dict(m):
+        return {"y_sq_err": int(m.y_sq_err), "y_count": int(m.y_count), "ssim_sum": float(m.ssim_sum), "ssim_count": int(m.ssim_count),
+                "y_psnr": y_psnr(int(m.y_sq_err), int(m.y_count)), "ssim": ssim_mean(float(m.ssim_sum), int(m.ssim_count))}
+
+    def image_metrics(self, a: np.ndarray, b: np.ndarray, shave=None):
+        """Two (H,W,3|4) u8 images, a the scored one and b the ground truth -> a dict of y_sq_err, y_count, ssim_sum, ssim_count and the
+        image's y_psnr and ssim (None where the count is 0).  shave None: the engine's factor.  No network runs (sr_image_metrics_rgba8)."""
+        a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        if a.ndim != 3 or b.ndim != 3 or a.dtype != np.uint8 or b.dtype != np.uint8 or a.shape[:2] != b.shape[:2]:
+            raise ValueError("expected two (H, W, C) u8 images of one size")
+        m = _lib.Metrics()
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_image_metrics_rgba8(self._ctx, a.ctypes.data_as(u8p), a.shape[2], b.ctypes.data_as(u8p), b.shape[2], a.shape[0],
+                                                  a.shape[1], -1 if shave is None else int(shave), C.byref(m)), self._ctx)
+        return self._metrics_dict(m)
+
+    def image_metrics_dev(self, a, b, shave=None, out=None, stream=None):
+        """Two (H,W,3|4) u8 torch tensors on this engine's device -> a uint8 tensor of 16 bytes, the uint64 y_sq_err then the float64
+        ssim_sum (metrics_from_bytes reads them), asynchronous on the stream (sr_image_metrics_rgba8_dev).  out: 16 bytes at a 4-byte
+        aligned address."""
+        import torch
+        for t in (a, b):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3
+        assert a.shape[:2] == b.shape[:2]
+        if out is None:
+            out = torch.empty(16, dtype=torch.uint8, device=a.device)
+        _lib.check(self._L.sr_image_metrics_rgba8_dev(self._ctx, C.c_void_p(a.data_ptr()), a.shape[2], C.c_void_p(b.data_ptr()), b.shape[2],
+                                                      a.shape[0], a.shape[1], -1 if shave is None else int(shave),
+                                                      C.c_void_p(out.data_ptr()), self._stream_ptr(stream, a.device)), self._ctx)
+        return out
+
+    def validation_metrics(self, hr: np.ndarray, lr=None, linear_loss: bool = False, members=None, shave=None):
+        """validation_error (lr None) or validation_error_pair of u8 images, and the scores of the same run of the network: the
+        quantised output against the HR crop.  -> a dict of err_sum, n_elems (the bits of those calls), y_sq_err, y_count, ssim_sum,
+        ssim_count, y_psnr, ssim.  shave None: the factor.  (sr_pool_validation_metrics_rgba8 / sr_pair_validation_metrics_rgba8)"""
+        hr = np.ascontiguousarray(hr)
+        if hr.ndim != 3 or hr.dtype != np.uint8:
+            raise ValueError("expected one (H, W, C) u8 image")
+        err, n, m = C.c_double(), C.c_size_t(), _lib.Metrics()
+        u8p = C.POINTER(C.c_uint8)
+        mask = 0 if members is None else self._members(members)
+        s = -1 if shave is None else int(shave)
+        if lr is None:
+            st = self._L.sr_pool_validation_metrics_rgba8(self._ctx, hr.ctypes.data_as(u8p), hr.shape[2], hr.shape[0], hr.shape[1],
+                                                     int(bool(linear_loss)), mask, s, C.byref(err), C.byref(n), C.byref(m))
+        else:
+            lr = np.ascontiguousarray(lr)
+            if lr.ndim != 3 or lr.dtype != np.uint8:
+                raise ValueError("expected one (H, W, C) u8 image")
+            lh, lw = self._pair_shapes(lr.shape, hr.shape)
+            st = self._L.sr_pair_validation_metrics_rgba8(self._ctx, lr.ctypes.data_as(u8p), lr.shape[2], hr.ctypes.data_as(u8p), hr.shape[2],
+                                                          lh, lw, int(bool(linear_loss)), mask, s, C.byref(err), C.byref(n), C.byref(m))
+        _lib.check(st, self._ctx)
+        out = {"err_sum": err.value, "n_elems": n.value}
+        out.update(self._metrics_dict(m))
+        return out
+
+    def validation_metrics_dev(self, hr, lr=None, linear_loss: bool = False, shave=None, err=None, out=None, stream=None):
+        """The device form: (H,W,3|4) u8 torch tensors -> (a float64 tensor of one element holding err_sum, a uint8 tensor of the 16
+        result bytes), asynchronous on the stream (sr_pool_validation_metrics_rgba8_dev / sr_pair_validation_metrics_rgba8_dev)."""
+        import torch
+        for t in (hr,) if lr is None else (hr, lr):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3
+        if err is None:
+            err = torch.empty(1, dtype=torch.float64, device=hr.device)
+        if out is None:
+            out = torch.empty(16, dtype=torch.uint8, device=hr.device)
+        s = -1 if shave is None else int(shave)
+        if lr is None:
+            st = self._L.sr_pool_validation_metrics_rgba8_dev(self._ctx, C.c_void_p(hr.data_ptr()), hr.shape[2], hr.shape[0], hr.shape[1],
+                                                         int(bool(linear_loss)), s, C.c_void_p(err.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                         self._stream_ptr(stream, hr.device))
+        else:
+            lh, lw = self._pair_shapes(lr.shape, hr.shape)
+            st = self._L.sr_pair_validation_metrics_rgba8_dev(self._ctx, C.c_void_p(lr.data_ptr()), lr.shape[2], C.c_void_p(hr.data_ptr()),
+                                                              hr.shape[2], lh, lw, int(bool(linear_loss)), s, C.c_void_p(err.data_ptr()),
+                                                              C.c_void_p(out.data_ptr()), self._stream_ptr(stream, hr.device))
+        _lib.check(st, self._ctx)
+        return err, out
+
     def validation_nodes(self, h: int, w: int):
         """The last validation call's `input` node (the pooled LR image, (h//f, w//f, 3)) and `output` node (the f32 network output,
         (f*(h//f), f*(w//f), 3)), for an HR image of h x w (sr_read_validation_nodes)."""
@@ -744,6 +826,81 @@ def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None, 
         err += e
         n += m
     return math.inf if err == 0.0 else -10.0 * math.log10(err / n)
+
+
+def y_psnr(y_sq_err: int, y_count: int):
+    """One image's Y-PSNR from its sums: 10 log10(255^2 y_count / y_sq_err); inf at zero error, None for an empty region."""
+    import math
+    if y_count == 0:
+        return None
+    return math.inf if y_sq_err == 0 else 10.0 * math.log10(65025.0 * y_count / y_sq_err)
+
+
+def ssim_mean(ssim_sum: float, ssim_count: int):
+    """One image's SSIM: ssim_sum / ssim_count; None where the region holds no window."""
+    return None if ssim_count == 0 else ssim_sum / ssim_count
+
+
+def metrics_from_bytes(result16, h: int, w: int, shave: int) -> dict:
+    """The 16 bytes a *_dev metrics call wrote (uint64 y_sq_err, float64 ssim_sum) and the counts of an h x w image shaved by `shave`."""
+    import struct
+    y_sq_err, ssim_sum = struct.unpack("<Qd", bytes(bytearray(result16)))
+    rh, rw = h - 2 * shave, w - 2 * shave
+    y_count = rh * rw if rh > 0 and rw > 0 else 0
+    ssim_count = (rh - 10) * (rw - 10) if rh >= 11 and rw >= 11 else 0
+    return {"y_sq_err": y_sq_err, "y_count": y_count, "ssim_sum": ssim_sum, "ssim_count": ssim_count,
+            "y_psnr": y_psnr(y_sq_err, y_count), "ssim": ssim_mean(ssim_sum, ssim_count)}
+
+
+def aggregate_metrics(per_image) -> dict:
+    """Per-image dicts (validation_metrics) in image order -> {"psnr": the pooled figure of validation_psnr, "y_psnr", "ssim": the means of
+    the per-image values (a zero-error image contributes inf), "skipped": [(index, "y_psnr" | "ssim"), ...] for the images whose region
+    was empty or held no window and which the mean leaves out}.  A mean over no image is None."""
+    import math
+    err = n = 0.0
+    ys, ss, skipped = [], [], []
+    for i, m in enumerate(per_image):
+        err += m["err_sum"]
+        n += m["n_elems"]
+        if m["y_psnr"] is None:
+            skipped.append((i, "y_psnr"))
+        else:
+            ys.append(m["y_psnr"])
+        if m["ssim"] is None:
+            skipped.append((i, "ssim"))
+        else:
+            ss.append(m["ssim"])
+    return {"psnr": math.inf if err == 0.0 else -10.0 * math.log10(err / n),
+            "y_psnr": math.fsum(ys) / len(ys) if ys else None,
+            "ssim": math.fsum(ss) / len(ss) if ss else None, "skipped": skipped}
+
+
+def validation_metrics(engines, images, lr_images=None, members=None, shave=None, linear_loss: bool = False) -> dict:
+    """validation_psnr with the benchmark protocol's scores: images are dealt round-robin over the engines, each scored by
+    Engine.validation_metrics, and the results aggregated in image order (aggregate_metrics), so the values do not depend on how many
+    engines there are.  "per_image" holds the per-image dicts."""
+    from concurrent.futures import ThreadPoolExecutor
+    if isinstance(engines, Engine):
+        engines = [engines]
+    images = list(images)
+    if not engines or not images:
+        raise ValueError("validation_metrics needs at least one engine and one image")
+    if lr_images is not None:
+        lr_images = list(lr_images)
+        if len(lr_images) != len(images):
+            raise ValueError("validation_metrics needs one LR image per HR image")
+    res = [None] * len(images)
+
+    def run(k):
+        for i in range(k, len(images), len(engines)):
+            res[i] = engines[k].validation_metrics(images[i], None if lr_images is None else lr_images[i], linear_loss, members, shave)
+
+    with ThreadPoolExecutor(max_workers=len(engines)) as pool:
+        for fut in [pool.submit(run, k) for k in range(len(engines))]:
+            fut.result()
+    out = aggregate_metrics(res)
+    out["per_image"] = res
+    return out
 
 
 def init_params(factor: int = FACTOR, seed: int = 0) -> np.ndarray:

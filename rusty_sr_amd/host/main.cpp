@@ -3,7 +3,7 @@
 //
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
 //   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] <PARAMETER_FILE> <TRAINING_FOLDER>
-//   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] <VALIDATION_FOLDER>
+//   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] <VALIDATION_FOLDER>
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
 // PSNR a parameter set reaches on a folder of HR images.  A first argument that is literally `train` or `validate` selects it; every
@@ -75,7 +75,8 @@ const char* kValidateUsage =
     "USAGE:\n    rusty_sr validate [FLAGS] [OPTIONS] <VALIDATION_FOLDER>\n\n"
     "FLAGS:\n    -l, --linearLoss    Apply MSE loss to a linearised RGB output rather than sRGB values\n"
     "    -r, --recurse       Recurse into subfolders of the validation folder looking for files\n"
-    "    -h, --help          Prints help information\n        --timing        Print images/s and GPU ms per image on stderr\n\n"
+    "    -h, --help          Prints help information\n        --timing        Print images/s and GPU ms per image on stderr\n"
+    "        --metrics       Also print Y-PSNR and SSIM: the 8-bit luma of the saved image, border shaved, averaged per image\n\n"
     "OPTIONS:\n    -c, --custom <PARAMETER_FILE>    Sets a custom parameter file (.rsr); its size selects the factor (2, 3 or 4)\n"
     "    -p, --parameters <PARAMETERS>    Sets which built-in parameters to use [values: imagenet, imagenetlinear, anime]\n"
     "    -m, --val_max <N>                Set upper limit on number of images used for the validation pass\n"
@@ -83,7 +84,8 @@ const char* kValidateUsage =
     "                                     path (extension ignored), exactly 1/f the size, instead of the pooled HR image\n"
     "        --devices <N,N,...>          HIP devices; images are dealt round-robin [default: 0]\n"
     "        --precision <MODE>           f32 (exact) or split_f16 [default: f32]\n"
-    "        --ensemble <N>               score the network averaged over N flips / rotations of its input [values: 2, 4, 8]\n\n"
+    "        --ensemble <N>               score the network averaged over N flips / rotations of its input [values: 2, 4, 8]\n"
+    "        --shave <N>                  with --metrics: pixels removed from each border before scoring [default: the factor]\n\n"
     "ARGS:\n    <VALIDATION_FOLDER>    Images from this folder (or sub-folders with -r) are scored, in path order\n";
 
 [[noreturn]] void die(const std::string& msg, int code = 1) {
@@ -262,7 +264,9 @@ void check_pair_sizes(const std::string& hr_file, const srpng::Image& hr, const 
 int run_validate(int argc, char** argv) {
     std::string parameters, custom, precision = "f32", folder, lr_folder;
     bool has_p = false, has_c = false, linear = false, recurse = false, timing = false, has_folder = false, has_lr = false;
+    bool metrics = false, has_shave = false;
     long val_max = -1;
+    int shave = -1;         // --metrics: -1 = the factor
     unsigned ensemble = 0;  // 0: the plain validation pass
     std::vector<int> devices;
     for (int k = 2; k < argc; ++k) {
@@ -303,6 +307,14 @@ int run_validate(int argc, char** argv) {
             const std::string v = value("--ensemble <N>");
             if (!(ensemble = ensemble_mask(v))) validate_usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
         }
+        else if (a == "--metrics") metrics = true;
+        else if (a == "--shave" || a.rfind("--shave=", 0) == 0) {
+            const std::string v = a == "--shave" ? value("--shave <N>") : a.substr(8);
+            const auto r = std::from_chars(v.data(), v.data() + v.size(), shave);
+            if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size() || shave < 0)
+                validate_usage_error("'" + v + "' isn't a valid value for '--shave <N>'");
+            has_shave = true;
+        }
         else if (a == "--augment") validate_usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a.size() > 1 && a[0] == '-') validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (has_folder) validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
@@ -315,6 +327,7 @@ int run_validate(int argc, char** argv) {
     if (precision != "f32" && precision != "split_f16") validate_usage_error("'" + precision + "' isn't a valid value for '--precision <MODE>'");
     if (ensemble && devices.size() > 1)
         validate_usage_error("The argument '--ensemble <N>' cannot be used with more than one device: the ensemble has no multi-GPU form");
+    if (has_shave && !metrics) validate_usage_error("The following required arguments were not provided:\n    --metrics");
     if (devices.empty()) devices.push_back(0);
 
     // ---- the files: decodable extensions, sorted by path bytes, the first N with -m
@@ -379,6 +392,7 @@ int run_validate(int argc, char** argv) {
     }
     std::vector<double> err(nfile, 0.0), gpu_ms(nfile, 0.0);
     std::vector<size_t> cnt(nfile, 0);
+    std::vector<sr_metrics> scores(metrics ? nfile : 0);
     std::string failure;
     int fail_code = 0;
     std::vector<std::thread> scorers;
@@ -411,7 +425,12 @@ int run_validate(int argc, char** argv) {
                         check_pair_sizes(files[i], img, lr_files[i], lr, factor);
                     }
                     int r;
-                    if (ensemble)
+                    if (metrics)  // (members 0: the plain pass)
+                        r = has_lr ? sr_pair_validation_metrics_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
+                                                                      ensemble, shave, &err[i], &cnt[i], &scores[i])
+                                   : sr_pool_validation_metrics_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble, shave,
+                                                                 &err[i], &cnt[i], &scores[i]);
+                    else if (ensemble)
                         r = has_lr ? sr_pair_validation_error_ensemble_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
                                                                              ensemble, &err[i], &cnt[i])
                                    : sr_pool_validation_error_ensemble_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble,
@@ -443,6 +462,20 @@ int run_validate(int argc, char** argv) {
     for (size_t i = 0; i < nfile; ++i) { err_sum += err[i]; n_sum += (double)cnt[i]; ms_sum += gpu_ms[i]; }
     const float psnr = err_sum == 0.0 ? INFINITY : (float)(-10.0 * std::log10(err_sum / n_sum));
     printf("Validation PSNR:\t%s\n", rust_f32(psnr).c_str());  // main.rs:246
+    if (metrics) {
+        // per-image means, in image order; an image whose shaved region is empty (or holds no 11 x 11 window) is left out and named
+        double y_sum = 0, s_sum = 0;
+        size_t y_n = 0, s_n = 0;
+        for (size_t i = 0; i < nfile; ++i) {
+            const sr_metrics& m = scores[i];
+            if (m.y_count) { y_sum += m.y_sq_err ? 10.0 * std::log10(65025.0 * (double)m.y_count / (double)m.y_sq_err) : INFINITY; ++y_n; }
+            else fprintf(stderr, "%s: nothing left after the shave, left out of Y-PSNR\n", files[i].c_str());
+            if (m.ssim_count) { s_sum += m.ssim_sum / (double)m.ssim_count; ++s_n; }
+            else fprintf(stderr, "%s: too small for an 11x11 window after the shave, left out of SSIM\n", files[i].c_str());
+        }
+        printf("Y-PSNR:\t%s\n", rust_f32(y_n ? (float)(y_sum / (double)y_n) : NAN).c_str());
+        printf("SSIM:\t%s\n", rust_f32(s_n ? (float)(s_sum / (double)s_n) : NAN).c_str());
+    }
     if (timing) {
         const double s = std::chrono::duration<double>(clk::now() - t0).count();
         fprintf(stderr, "[timing] %zu images in %.3f s: %.2f images/s; GPU %.3f ms per image (whole validation call)\n", nfile, s, nfile / s,
@@ -579,6 +612,8 @@ int run_train(int argc, char** argv) {
             if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size()) train_usage_error("'" + v + "' isn't a valid value for '--seed <N>'");
             has_seed = true;
         }
+        else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
+            train_usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
         else if (a.size() > 1 && a[0] == '-') train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (pos.size() == 2) train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
@@ -871,6 +906,8 @@ int main(int argc, char** argv) {
             if (!(ensemble = ensemble_mask(v))) usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
         }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
+        else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
+            usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
         else if (a.size() > 1 && a[0] == '-') usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
     }
