@@ -108,7 +108,7 @@ int sr_upscale_f32(sr_ctx* ctx, const float* in, int n, int h, int w, float* out
 /* Replaces: img_to_data + graph.forward + data_to_img(..).to_rgba() (reference
  * main.rs:170-175) as one fused device pass: u8/255 on load, and
  * clamp(floor(255 v + 0.5)) with alpha = 255 on store.
- * in : n*h*w*in_channels u8, in_channels 3 (RGB) or 4 (RGBA, alpha dropped).
+ * in : n*h*w*in_channels u8, in_channels 3 (RGB) or 4 (RGBA, alpha dropped; sr_upscale_rgba8_alpha below keeps it).
  * out: n*(3h)*(3w)*4 u8 RGBA.  Host memory. */
 int sr_upscale_rgba8(sr_ctx* ctx, const uint8_t* in, int in_channels, int n, int h, int w,
                      uint8_t* out_rgba);
@@ -539,6 +539,47 @@ int sr_pool_validation_metrics_rgba8_dev(sr_ctx* ctx, const uint8_t* d_hr, int i
                                     double* d_err_sum, void* d_result16, void* stream);
 int sr_pair_validation_metrics_rgba8_dev(sr_ctx* ctx, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
                                          int linear_loss, int shave, double* d_err_sum, void* d_result16, void* stream);
+
+/* ---- Transparency: the alpha channel upscaled, the colours bled under it ----
+ * The reference drops alpha (data_to_img(..).to_rgba() writes 255, main.rs:175), and so does every call above.  In a straight-alpha image
+ * the RGB under alpha == 0 is arbitrary, usually black: the network, whose receptive field reaches SR_HALO pixels, would paint that hard edge
+ * as a dark, ringing fringe into pixels that are still partly visible once the alpha is interpolated.  So the call is three passes: bleed
+ * the visible colours outward under the transparent area, upscale the bled image, write the interpolated alpha of the ORIGINAL image into
+ * the result.  Both rules are integer arithmetic, the same bits on every run and device.  UNPINNED: the reference has nothing to compare with;
+ * tests/alpha_ref.py restates both rules in numpy.
+ *   Bleed, radius R (0 .. SR_ALPHA_BLEED_MAX), of an h x w RGBA8 image: known_0(p) = alpha(p) > 0, c_0(p) = RGB(p).  For t = 1 .. R every
+ *     pixel p that is not known_{t-1} looks at its 8 neighbours inside the image; with N those that are known_{t-1} and N not empty, per
+ *     channel c_t(p) = (2 sum_{q in N} c_{t-1}(q) + |N|) div (2 |N|) -- the mean, rounded half up -- and p is known_t.  Each step reads the
+ *     step before only, so the result does not depend on any order.  Output: RGB = c_R, alpha = the input's, untouched.  Pixels with
+ *     alpha > 0 never change, pixels farther than R (Chebyshev) from every visible one keep their RGB, R = 0 is the identity, and the
+ *     images of a batch do not see each other.  The rule commutes with the self-ensemble's eight transforms.
+ *   Alpha x f (f = 2, 3, 4): bilinear interpolation with half-pixel centres and clamped edges, the geometry of the bilinear graph, on the
+ *     alpha bytes.  Along an axis of length len, output index o: i = o div f, m = 2 (o mod f) + 1 - f; taps (i, i + 1) with weights
+ *     (2f - m, m) if m >= 0, else (i - 1, i) with (-m, 2f + m); tap indices clamped to [0, len - 1].  A_out = (sum wy wx a + 2 f^2) div
+ *     (4 f^2): the exact bilinear value rounded half up.  A constant alpha stays that constant; an opaque image stays 255.
+ * Images are RGBA8 in device memory, 4 bytes a pixel, and BOTH the input and the output pointers must be 4-byte aligned (the kernels move
+ * whole dwords; no larger alignment is needed).  Every call is asynchronous and ordered on `stream` alone.
+ * sr_bleed_rgba8_dev: d_out = bleed(d_in, radius), n images of h x w; any context.  d_out == d_in is refused (a workgroup reads its
+ *   neighbours' pixels), and the two images must not overlap otherwise.
+ * sr_merge_alpha_rgba8_dev: byte 3 of every pixel of the f h x f w image at d_out_rgba <- alpha x f of d_lr_rgba (h x w), f the context's
+ *   factor; the three colour bytes are left as they are.  SR_GRAPH_SR_NET and SR_GRAPH_BILINEAR contexts.
+ * sr_upscale_rgba8_alpha_dev: bleed into a workspace buffer of the context (grown on first use, freed by sr_destroy; radius == 0 launches no
+ *   bleed and reads the caller's image), then exactly sr_upscale_rgba8_dev's path (members == 1) or sr_upscale_ensemble_rgba8_dev's
+ *   (any other mask) on the bled image, then the merge from the original d_in_rgba.  An opaque image gives the plain call's bytes.
+ * sr_upscale_rgba8_alpha: the same on host memory, synchronous: one upload, the device call on the context's own stream, one download; in
+ *   SR_PRECISION_SPLIT_F16 the whole call is computed again in exact f32 where a value left that mode's domain.  With sr_set_profiling on,
+ *   sr_last_timing's total_ms is the bleed, every pass of the network and the merge, h2d / d2h the two copies.
+ * Refused with SR_E_INVALID before any launch, the output untouched: SR_GRAPH_DOWNSAMPLE contexts (merge and upscale calls), a radius outside
+ * 0 .. SR_ALPHA_BLEED_MAX, members == 0 or > 255, members != 1 on a context other than SR_GRAPH_SR_NET, a device pointer that is not 4-byte
+ * aligned.  A shape whose workspace does not fit is SR_E_NOMEM and leaves the context usable.  Cost at 1920 x 1080: DESIGN.md 4m. */
+#define SR_ALPHA_BLEED_DEFAULT 8   /* >= SR_HALO: every visible pixel's receptive field is then bled */
+#define SR_ALPHA_BLEED_MAX 16
+#define SR_ALPHA_BLEED_TILE 32     /* side of the bleed kernel's output tile (the tests put sizes either side of its multiples) */
+int sr_bleed_rgba8_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int h, int w, int radius, uint8_t* d_out_rgba, void* stream);
+int sr_merge_alpha_rgba8_dev(sr_ctx* ctx, const uint8_t* d_lr_rgba, int n, int h, int w, uint8_t* d_out_rgba, void* stream);
+int sr_upscale_rgba8_alpha_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int h, int w, uint8_t* d_out_rgba, int radius, unsigned members,
+                               void* stream);
+int sr_upscale_rgba8_alpha(sr_ctx* ctx, const uint8_t* in_rgba, int n, int h, int w, uint8_t* out_rgba, int radius, unsigned members);
 
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels

@@ -1,6 +1,6 @@
 //! rusty_sr -- Rust host over libsrhip (the MI355X engine).
 //!
-//!     rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
+//!     rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d] [--alpha [--bleed N]]
 //!     rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--metrics [--shave N]] <VALIDATION_FOLDER>
 //!
 //! Same arguments, progress text and failure text as millardjn/rusty_sr v1; decoding and encoding
@@ -36,6 +36,8 @@ struct Options {
     device: i32,
     split_f16: bool,
     timing: bool,
+    alpha: bool,
+    bleed: i32,
 }
 
 fn usage_error(msg: &str) -> ! {
@@ -51,7 +53,9 @@ fn die(msg: &str) -> ! {
 
 fn parse_args() -> Options {
     let mut o = Options { input: String::new(), output: String::new(), parameters: None, custom: None,
-                          downsample: false, device: 0, split_f16: false, timing: false };
+                          downsample: false, device: 0, split_f16: false, timing: false, alpha: false,
+                          bleed: srhip::SR_ALPHA_BLEED_DEFAULT };
+    let mut has_bleed = false;
     let mut positional: Vec<String> = Vec::new();
     let mut args = env::args().skip(1);
     while let Some(a) = args.next() {
@@ -68,7 +72,10 @@ fn parse_args() -> Options {
             }
             "-h" | "--help" => {
                 println!("Rusty SR v0.1.1 (MI355X engine)\nUSAGE:\n    rusty_sr [-d] [-p PARAMETERS | -c PARAMETER_FILE] \
-                          [--device N] [--precision f32|split_f16] [--timing] <INPUT_FILE> <OUTPUT_FILE>");
+                          [--device N] [--precision f32|split_f16] [--timing] [--alpha [--bleed N]] <INPUT_FILE> <OUTPUT_FILE>\n\
+                          \x20       --alpha         Keep transparency: bleed the visible colours under the transparent pixels, upscale, and\n\
+                          \x20                       write the interpolated alpha channel (.png output only)\n\
+                          \x20       --bleed <N>     with --alpha: how many pixels the colours are bled outward, 0..16 [default: 8]");
                 exit(0)
             }
             "-V" | "--version" => {
@@ -87,6 +94,15 @@ fn parse_args() -> Options {
                     "split_f16" => o.split_f16 = true,
                     _ => usage_error(&format!("'{}' isn't a valid value for '--precision <MODE>'", v)),
                 }
+            }
+            "--alpha" => o.alpha = true,
+            "--bleed" => {
+                let v = value("--bleed <N>");
+                match v.parse::<i32>() {
+                    Ok(n) if n >= 0 && n <= srhip::SR_ALPHA_BLEED_MAX => o.bleed = n,
+                    _ => usage_error(&format!("'{}' isn't a valid value for '--bleed <N>'\n\t[values: 0..16]", v)),
+                }
+                has_bleed = true;
             }
             "--metrics" | "--shave" => usage_error(&format!("The argument '{}' can only be used with the 'validate' subcommand", a)),
             s if s.len() > 1 && s.starts_with('-') => {
@@ -111,6 +127,15 @@ fn parse_args() -> Options {
     }
     if positional.len() > 2 {
         usage_error(&format!("Found argument '{}' which wasn't expected, or isn't valid in this context", positional[2]));
+    }
+    if has_bleed && !o.alpha {
+        usage_error("The following required arguments were not provided:\n    --alpha");
+    }
+    if o.alpha && o.downsample {
+        usage_error("The argument '--alpha' cannot be used with '--downsample'");
+    }
+    if o.alpha && !positional[1].to_lowercase().ends_with(".png") {
+        usage_error("The argument '--alpha' cannot be used with an output file other than .png: JPEG, BMP and PPM carry no alpha channel");
     }
     o.input = positional[0].clone();
     o.output = positional[1].clone();
@@ -347,7 +372,11 @@ fn main() {
 
     let rgba = image::open(Path::new(&o.input)).unwrap_or_else(|_| die("Error opening input image file.")).to_rgba();
     let (w, h) = rgba.dimensions();
-    let out = engine.upscale_rgba8(&rgba.into_raw(), w, h).unwrap_or_else(|e| die(&e));
+    let out = if o.alpha {
+        engine.upscale_rgba8_alpha(&rgba.into_raw(), w, h, o.bleed).unwrap_or_else(|e| die(&e))
+    } else {
+        engine.upscale_rgba8(&rgba.into_raw(), w, h).unwrap_or_else(|e| die(&e))
+    };
     if o.timing {
         let (total, h2d, d2h) = engine.last_timing();
         let _ = writeln!(std::io::stderr(), "\n[timing] kernels {:.3} ms, h2d {:.3} ms, d2h {:.3} ms", total, h2d, d2h);

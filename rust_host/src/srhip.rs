@@ -67,6 +67,8 @@ pub const SR_COMM_ID_BYTES: c_int = 128;
 pub const SR_TRAIN_MAX_BATCH: c_int = 64;
 pub const SR_TRAIN_RING: c_int = 64;
 pub const SR_TRAIN_STORE_AUTO: usize = usize::MAX;
+pub const SR_ALPHA_BLEED_DEFAULT: c_int = 8;
+pub const SR_ALPHA_BLEED_MAX: c_int = 16;
 
 extern "C" {
     pub fn sr_rsr_decode(blob: *const u8, len: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
@@ -165,6 +167,10 @@ extern "C" {
     pub fn sr_pair_validation_metrics_rgba8(ctx: *mut SrCtx, lr: *const u8, lr_channels: c_int, hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, members: c_uint, shave: c_int, err_sum: *mut f64, n_elems: *mut usize, metrics: *mut SrMetrics) -> c_int;
     pub fn sr_pool_validation_metrics_rgba8_dev(ctx: *mut SrCtx, d_hr: *const u8, in_channels: c_int, h: c_int, w: c_int, linear_loss: c_int, shave: c_int, d_err_sum: *mut f64, d_result16: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn sr_pair_validation_metrics_rgba8_dev(ctx: *mut SrCtx, d_lr: *const u8, lr_channels: c_int, d_hr: *const u8, hr_channels: c_int, lh: c_int, lw: c_int, linear_loss: c_int, shave: c_int, d_err_sum: *mut f64, d_result16: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn sr_bleed_rgba8_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, radius: c_int, d_out_rgba: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sr_merge_alpha_rgba8_dev(ctx: *mut SrCtx, d_lr_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_rgba8_alpha_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, radius: c_int, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_rgba8_alpha(ctx: *mut SrCtx, in_rgba: *const u8, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, radius: c_int, members: c_uint) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.
@@ -259,6 +265,22 @@ impl Engine {
         let (ow, oh) = self.out_dims(w, h);
         let mut out = vec![0u8; ow as usize * oh as usize * 4];
         let rc = unsafe { sr_upscale_rgba8(self.ctx, rgba.as_ptr(), 4, 1, h as c_int, w as c_int, out.as_mut_ptr()) };
+        if rc == SR_OK {
+            Ok(out)
+        } else if rc == SR_E_HIP {
+            Err(format!("{} (hipError {})", strerror(rc), unsafe { sr_last_hip_error(self.ctx) }))
+        } else {
+            Err(strerror(rc))
+        }
+    }
+
+    /// `upscale_rgba8` that keeps the alpha channel (sr_upscale_rgba8_alpha): the colours are bled `bleed` pixels under the transparent
+    /// area, the bled image is upscaled, and the interpolated alpha of `rgba` is written into the result.
+    pub fn upscale_rgba8_alpha(&mut self, rgba: &[u8], w: u32, h: u32, bleed: c_int) -> Result<Vec<u8>, String> {
+        assert_eq!(rgba.len(), w as usize * h as usize * 4);
+        let (ow, oh) = self.out_dims(w, h);
+        let mut out = vec![0u8; ow as usize * oh as usize * 4];
+        let rc = unsafe { sr_upscale_rgba8_alpha(self.ctx, rgba.as_ptr(), 1, h as c_int, w as c_int, out.as_mut_ptr(), bleed, 1) };
         if rc == SR_OK {
             Ok(out)
         } else if rc == SR_E_HIP {

@@ -19,6 +19,8 @@ SR_TRAIN_STORE_AUTO = (1 << (8 * C.sizeof(C.c_size_t))) - 1
 SR_TRAIN_MAX_BATCH = 64
 SR_TRAIN_RING = 64
 SR_ENSEMBLE_ALL, SR_ENSEMBLE_FLIPS, SR_ENSEMBLE_HFLIP = 0xFF, 0x0F, 0x03
+SR_ALPHA_BLEED_DEFAULT, SR_ALPHA_BLEED_MAX = 8, 16
+SR_ALPHA_BLEED_TILE = 32  # side of the bleed kernel's output tile (the tests put sizes on and across its seams)
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -125,6 +127,10 @@ SYMBOLS = {
     "sr_pair_validation_metrics_rgba8": (_i, [_vp, _u8p, _i, _u8p, _i, _i, _i, _i, C.c_uint, _i, _dp, C.POINTER(_sz), C.POINTER(Metrics)]),
     "sr_pool_validation_metrics_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "sr_pair_validation_metrics_rgba8_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "sr_bleed_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_merge_alpha_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "sr_upscale_rgba8_alpha_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, C.c_uint, _vp]),
+    "sr_upscale_rgba8_alpha": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, C.c_uint]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -137,6 +137,8 @@ struct sr_ctx {
     // ---- metrics (sr_metrics.cpp): grown on demand, freed by sr_destroy
     void* d_mpart = nullptr; size_t mpart_cap = 0;  // the tile kernel's partials (f64, then u64), then the host-pointer calls' 16-byte result
     void* d_mimg = nullptr; size_t mimg_cap = 0;    // both images of a host-pointer sr_image_metrics_rgba8 call
+    // ---- transparency (sr_alpha.cpp): grown on demand, freed by sr_destroy
+    void* d_ableed = nullptr; size_t ableed_cap = 0;  // the bled copy of the caller's RGBA8 image
     size_t total_mem = 0;                           // the device's memory, asked for once: a shape beyond it is refused without an allocation
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
@@ -364,6 +366,16 @@ void sr_ensemble_release(sr_ctx* c);  // free the ensemble buffers (called by sr
 int sr_ensemble_check(const sr_ctx* c, unsigned members, int h, int w);
 int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int h, int w, void* d_out, bool out_u8, unsigned members,
                       hipStream_t s);
+
+// ---- transparency (sr_alpha.hip kernels, sr_alpha.cpp host side; include/srhip.h "Transparency")
+// workgroups of either launch (0: an empty shape), functions of the shape alone; the launchers refuse more than INT32_MAX
+size_t sr_alpha_bleed_blocks(int n, int h, int w, unsigned* tiles_x_out = nullptr, unsigned* tiles_y_out = nullptr);
+size_t sr_alpha_merge_blocks(int factor, int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+// d_out = bleed(d_in, radius): n RGBA8 images of h x w, both 4-byte aligned and not overlapping
+hipError_t sr_launch_alpha_bleed(const uint8_t* d_in, uint8_t* d_out, int n, int h, int w, int radius, hipStream_t s);
+// byte 3 of the n images of factor h x factor w at d_out <- the alpha of d_lr (n x h x w RGBA8) interpolated; both 4-byte aligned
+hipError_t sr_launch_alpha_merge(int factor, const uint8_t* d_lr, uint8_t* d_out, int n, int h, int w, hipStream_t s);
+void sr_alpha_release(sr_ctx* c);  // free the bleed buffer (called by sr_destroy)
 
 // ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)
 // One crop of a step, as the crop kernel reads it: px is device memory, 4-byte aligned when ch = 4 (rows are then read as whole pixels).

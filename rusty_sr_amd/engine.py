@@ -229,6 +229,80 @@ class Engine:
                                                          self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
+    # ---- transparency: colours bled under the transparent pixels, the alpha channel interpolated (include/srhip.h "Transparency") ----
+    def _rgba_dev(self, px):
+        """An (n,H,W,4) or (H,W,4) u8 image as a contiguous 4-d tensor on the GPU: a numpy array is uploaded, a tensor taken as it is."""
+        import torch
+        numpy_in = not torch.is_tensor(px)
+        if numpy_in:
+            px = torch.from_numpy(np.ascontiguousarray(px, dtype=np.uint8)).to(f"cuda:{self.device}")
+        squeeze = px.dim() == 3
+        if squeeze:
+            px = px[None]
+        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
+        return px, squeeze, numpy_in
+
+    @staticmethod
+    def _rgba_result(out, squeeze, numpy_in):
+        out = out[0] if squeeze else out
+        return out.cpu().numpy() if numpy_in else out
+
+    def bleed(self, img_rgba, radius: int = _lib.SR_ALPHA_BLEED_DEFAULT, out=None, stream=None):
+        """sr_bleed_rgba8_dev: the colours of the pixels with alpha > 0 spread `radius` pixels (0..16) under the transparent ones, alpha
+        untouched.  (n,H,W,4) or (H,W,4) u8, a tensor on this GPU (4-byte aligned) or a numpy array; the result is of the same kind."""
+        import torch
+        px, squeeze, numpy_in = self._rgba_dev(img_rgba)
+        n, h, w, _ = px.shape
+        if out is None:
+            out = torch.empty_like(px)
+        _lib.check(self._L.sr_bleed_rgba8_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w, int(radius), C.c_void_p(out.data_ptr()),
+                                              self._stream_ptr(stream, px.device)), self._ctx)
+        return self._rgba_result(out, squeeze, numpy_in)
+
+    def merge_alpha(self, lr_rgba, out_rgba, stream=None):
+        """sr_merge_alpha_rgba8_dev: the alpha of lr_rgba (n,H,W,4), interpolated to (n,fH,fW), replaces byte 3 of every pixel of out_rgba
+        IN PLACE when that is a tensor on this GPU; a numpy out_rgba is copied, and the merged copy returned."""
+        import torch
+        lr, squeeze, _ = self._rgba_dev(lr_rgba)
+        out, _, numpy_out = self._rgba_dev(out_rgba)
+        n, h, w, _ = lr.shape
+        assert tuple(out.shape) == (n, self.factor * h, self.factor * w, 4) and out.device == lr.device
+        _lib.check(self._L.sr_merge_alpha_rgba8_dev(self._ctx, C.c_void_p(lr.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
+                                                    self._stream_ptr(stream, lr.device)), self._ctx)
+        return self._rgba_result(out, squeeze, numpy_out)
+
+    def upscale_rgba8_alpha(self, img_rgba: np.ndarray, bleed: int = _lib.SR_ALPHA_BLEED_DEFAULT, members: int = 1, out: np.ndarray = None) -> np.ndarray:
+        """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) that keeps transparency: (n,H,W,4) or (H,W,4) u8 ->
+        (n,fH,fW,4) u8 whose RGB is the network's output on the image bled by `bleed` pixels and whose alpha is the input's, interpolated."""
+        px = np.ascontiguousarray(img_rgba, dtype=np.uint8)
+        squeeze = px.ndim == 3
+        if squeeze:
+            px = px[None]
+        n, h, w, c = px.shape
+        if c != 4:
+            raise ValueError("expected 4 channels")
+        oh, ow = self._out_hw(h, w)
+        if out is None:
+            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
+        else:
+            out = out.reshape(n, oh, ow, 4)
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_upscale_rgba8_alpha(self._ctx, px.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), int(bleed),
+                                                  self._members(members)), self._ctx)
+        return out[0] if squeeze else out
+
+    def upscale_rgba8_alpha_dev(self, px, bleed: int = _lib.SR_ALPHA_BLEED_DEFAULT, members: int = 1, out=None, stream=None):
+        import torch
+        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
+        n, h, w, _ = px.shape
+        if out is None:
+            out = torch.empty((n,) + self._out_hw(h, w) + (4,), dtype=torch.uint8, device=px.device)
+        _lib.check(self._L.sr_upscale_rgba8_alpha_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()), int(bleed),
+                                                      self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
     def upscale_band_f32_dev(self, x_ext, halo_top, halo_bot, out=None, stream=None):
         """x_ext: (h_ext,W,3) f32 rows = halo_top + band + halo_bot -> (3*band,3W,3)."""
         import torch

@@ -12,7 +12,8 @@
 // Differences from the reference, all outside the hot path: own codecs (PNG over zlib, baseline + progressive JPEG, GIF,
 // TIFF, TGA, ICO, PPM/PGM/PBM, BMP in; PNG, JPEG, BMP, PPM out by extension -- of what the reference's `image` crate reads
 // only WebP is missing), and extra options that cannot collide with the reference's: --device N, --precision f32|split_f16,
-// --timing, --ensemble 2|4|8 (upscale and validate: the network averaged over flips / rotations); for `train` --seed N (initial
+// --timing, --ensemble 2|4|8 (upscale and validate: the network averaged over flips / rotations), --alpha [--bleed N] (upscale: the alpha
+// channel is kept -- colours bled under the transparent pixels, alpha interpolated; PNG output only); for `train` --seed N (initial
 // parameters, shuffles and crops are seeded; the reference's are random), --augment (each crop under a random one of the 8 flips and
 // rotations, applied by the crop kernel) and --steps N (stop
 // early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
@@ -55,7 +56,9 @@ const char* kUsage =
     "USAGE:\n    rusty_sr [FLAGS] [OPTIONS] <INPUT_FILE> <OUTPUT_FILE>\n    rusty_sr validate [FLAGS] [OPTIONS] <VALIDATION_FOLDER>\n"
     "    rusty_sr train [FLAGS] [OPTIONS] <PARAMETER_FILE> <TRAINING_FOLDER>\n\n"
     "FLAGS:\n    -d, --downsample    Perform downscaling rather than upscaling\n    -h, --help          Prints help information\n"
-    "    -V, --version       Prints version information\n        --timing        Print device / transfer times on stderr\n\n"
+    "    -V, --version       Prints version information\n        --timing        Print device / transfer times on stderr\n"
+    "        --alpha         Keep transparency: bleed the visible colours under the transparent pixels, upscale, and\n"
+    "                        write the interpolated alpha channel (.png output only)\n\n"
     "OPTIONS:\n    -c, --custom <PARAMETER_FILE>    Sets a custom parameter file (.rsr) to use with the neural net\n"
     "    -p, --parameters <PARAMETERS>    Sets which built-in parameters to use with the neural net [values: imagenet,\n"
     "                                     imagenetlinear, anime, bilinear]\n"
@@ -63,7 +66,8 @@ const char* kUsage =
     "        --devices <N,N,...>          spread one image over several GPUs (row shares, halo rows from the image)\n"
     "        --precision <MODE>           f32 (exact) or split_f16 (2x faster, same 1e-4 parity bar) [default: f32]\n"
     "        --ensemble <N>               average the network over N flips / rotations of the image: 2 (mirror), 4 (flips)\n"
-    "                                     or 8 (flips and rotations); N passes for slightly better pixels\n\n"
+    "                                     or 8 (flips and rotations); N passes for slightly better pixels\n"
+    "        --bleed <N>                  with --alpha: how many pixels the colours are bled outward, 0..16 [default: 8]\n\n"
     "ARGS:\n    <INPUT_FILE>     Sets the input image to upscale\n    <OUTPUT_FILE>    Sets the output file to write/overwrite (.png recommended)\n\n"
     "SUBCOMMANDS:\n    train       Trains a new set of neural network parameters on the GPU (rusty_sr train --help)\n"
     "    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
@@ -873,6 +877,8 @@ int main(int argc, char** argv) {
     bool has_p = false, has_c = false, downsample = false, timing = false;
     int device = 0;
     unsigned ensemble = 0;  // 0: one pass of the network
+    bool alpha = false, has_bleed = false;
+    int bleed = SR_ALPHA_BLEED_DEFAULT;
     std::vector<int> devices;
     if (argc >= 2 && !strcmp(argv[1], "train")) return run_train(argc, argv);  // main.rs:119-121
     if (argc >= 2 && !strcmp(argv[1], "validate")) return run_validate(argc, argv);
@@ -905,6 +911,14 @@ int main(int argc, char** argv) {
             const std::string v = value("--ensemble <N>");
             if (!(ensemble = ensemble_mask(v))) usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
         }
+        else if (a == "--alpha") alpha = true;
+        else if (a == "--bleed" || a.rfind("--bleed=", 0) == 0) {
+            const std::string v = a == "--bleed" ? value("--bleed <N>") : a.substr(8);
+            const auto r = std::from_chars(v.data(), v.data() + v.size(), bleed);
+            if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size() || bleed < 0 || bleed > SR_ALPHA_BLEED_MAX)
+                usage_error("'" + v + "' isn't a valid value for '--bleed <N>'\n\t[values: 0..16]");
+            has_bleed = true;
+        }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
@@ -925,6 +939,17 @@ int main(int argc, char** argv) {
     if (ensemble && downsample) usage_error("The argument '--ensemble <N>' cannot be used with '--downsample': there is no network to average");
     if (ensemble && devices.size() > 1)
         usage_error("The argument '--ensemble <N>' cannot be used with more than one device: the ensemble has no multi-GPU form");
+    // --alpha: the bleed / upscale / merge call has no downsampling and no multi-GPU form, and only PNG carries an alpha channel
+    if (has_bleed && !alpha) usage_error("The following required arguments were not provided:\n    --alpha");
+    if (alpha && downsample) usage_error("The argument '--alpha' cannot be used with '--downsample'");
+    if (alpha && devices.size() > 1) usage_error("The argument '--alpha' cannot be used with more than one device: the alpha path has no multi-GPU form");
+    if (alpha) {
+        const size_t dot = pos[1].find_last_of('.');
+        std::string ext = dot == std::string::npos ? "" : pos[1].substr(dot + 1);
+        for (auto& ch : ext) ch = (char)tolower((unsigned char)ch);
+        if (ext != "png")
+            usage_error("The argument '--alpha' cannot be used with an output file other than .png: JPEG, BMP and PPM carry no alpha channel");
+    }
 
     // ---- parameters + graph (main.rs:133-158), same progress text
     std::vector<float> params;
@@ -997,7 +1022,7 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < devices.size() && rc == SR_OK; ++k) {
         rc = sr_create_graph(&ctxs[k], graph, params.empty() ? nullptr : params.data(), params.size(), SR_FACTOR, devices[k]);
         if (rc == SR_OK && graph == SR_GRAPH_SR_NET) rc = sr_set_precision(ctxs[k], precision == "f32" ? SR_PRECISION_F32 : SR_PRECISION_SPLIT_F16);
-        if (rc == SR_OK && ensemble && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble call times itself only when asked to)
+        if (rc == SR_OK && (ensemble || alpha) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble and alpha calls time themselves only when asked to)
     }
     const double t_create = ms_since(t_start);
     double t_prep = 0;
@@ -1025,7 +1050,8 @@ int main(int argc, char** argv) {
     // img_to_data + graph.forward + data_to_img(..).to_rgba(), fused on the device (main.rs:168-175)
     const double t_alloc = ms_since(t_al);
     const clk::time_point t_up = clk::now();
-    rc = ensemble ? sr_upscale_ensemble_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out, ensemble)
+    rc = alpha ? sr_upscale_rgba8_alpha(ctx, in.rgba.data(), 1, in.h, in.w, out, bleed, ensemble ? ensemble : 1u)
+         : ensemble ? sr_upscale_ensemble_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out, ensemble)
          : ctxs.size() > 1 ? sr_upscale_rgba8_multi(ctxs.data(), (int)ctxs.size(), in.rgba.data(), 4, in.h, in.w, out)
                            : sr_upscale_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out);
     if (rc != SR_OK) die(std::string(sr_strerror(rc)) + (rc == SR_E_HIP ? " (hipError " + std::to_string(sr_last_hip_error(ctx)) + ")" : ""));
