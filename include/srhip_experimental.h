@@ -37,6 +37,10 @@ extern "C" {
  * both halves of conv5 as well (for measurement only, never the default: it takes the call too close to the f32 roof that bench.py's
  * contract holds it below); "1": stage 1's conv1 only; "0": every stage in the direct form.  Unlike the others this switch changes the last bits of f32 results (every setting is
  * held to the same parity bar); every kernel form, tile class and band of one setting stays bit-identical to the others.
+ * "auxgrid": the parameter-free graphs (SR_GRAPH_BILINEAR / SR_GRAPH_DOWNSAMPLE) -- "" automatic, "N" (N >= 1): every launch of their kernels
+ * takes min(automatic grid, N) workgroups.  The kernels walk their tiles / items with the grid as stride, so a small N reaches their
+ * multi-round paths (carries of the item counter, the prefetch of the next round) at tiny shapes and on any CU count; host side only, no
+ * output byte depends on it.  Anything but "" or a positive integer: SR_E_INVALID.  (No environment default.)
  * Defaults come from SRHIP_WINO / SRHIP_TH / SRHIP_TAIL / SRHIP_PIPE / SRHIP_BW / SRHIP_BANDS / SRHIP_ROWS / SRHIP_GEO / SRHIP_HALO, read once in sr_create.
  * Unknown key: SR_E_INVALID. */
 int sr_set_experiment(sr_ctx* ctx, const char* key, const char* value);
@@ -52,6 +56,11 @@ int sr_set_experiment(sr_ctx* ctx, const char* key, const char* value);
  *   "launch st=S form=first|pipe ty8=A ty4=B grid=G prec=f32|split_f16 f=F img=u8|f32 out=u8|f32 ch=C"
  *                                       one launch of stage S (0: conv0, 4: the final stage): A rows of 8-row tiles then B rows of 4-row
  *                                       tiles, G workgroups; C: channels of the input image.
+ *   "aux graph=bilinear|downsample img=u8|f32 ch=C grid=G units=U"
+ *                                       one launch of a parameter-free graph: G workgroups walk U pieces, a workgroup every G-th -- tiles
+ *                                       (64 x 16 input pixels, bilinear f32; 64 x 4 output pixels, downsample), or for the u8 bilinear kernel
+ *                                       groups of four wave items (an item: 64 16-byte chunks of one input row's three output rows), U =
+ *                                       ceil(items / 4).  The launch is multi-round exactly when U > G.
  * Identical lines in a row are one, followed by " xN".  Host-side text written where the decisions are made: no result depends on it.
  * Unknown key, or a buffer too small: SR_E_INVALID. */
 int sr_get_experiment(sr_ctx* ctx, const char* key, char* buf, size_t cap);

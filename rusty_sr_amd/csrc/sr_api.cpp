@@ -563,6 +563,14 @@ int sr_set_experiment(sr_ctx* c, const char* key, const char* value) {
         c->wino5 = !strcmp(v, "3") ? 2 : !strcmp(v, "2") ? 0 : kWinoConv5Halves;
     } else if (!strcmp(key, "bw")) {   // tile-order column-block width in tiles; "" / negative: automatic, 0: plain row-major
         c->env_bw = *v ? atoi(v) : -1;
+    } else if (!strcmp(key, "auxgrid")) {  // bilinear_net / downsample_net: "" automatic, "N" (N >= 1): never more than N workgroups per launch
+        long cap = 0;
+        for (const char* p = v; *p; ++p) {
+            if (*p < '0' || *p > '9' || cap > INT32_MAX / 10) return SR_E_INVALID;
+            cap = 10 * cap + (*p - '0');
+        }
+        if (*v && (cap < 1 || cap > INT32_MAX)) return SR_E_INVALID;
+        c->env_auxgrid = (int)cap;
     } else {
         return SR_E_INVALID;
     }
@@ -884,7 +892,14 @@ int sr_run_stack(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int n, i
         if (img_u8 != out_u8) return SR_E_INVALID;
         HIPCHK(c, hipSetDevice(c->device));
         AuxArgs a{d_img, d_out, n, H, W, img_ch, c->d_qtab};
-        HIPCHK(c, sr_launch_aux(c->graph, a, img_u8, out_u8, s));
+        AuxLaunch ran{0, 0};
+        HIPCHK(c, sr_launch_aux(c->graph, a, img_u8, out_u8, s, c->env_auxgrid, &ran));
+        if (ran.grid > 0) {
+            char line[128];
+            snprintf(line, sizeof line, "aux graph=%s img=%s ch=%d grid=%d units=%ld", c->graph == SR_GRAPH_BILINEAR ? "bilinear" : "downsample",
+                     img_u8 ? "u8" : "f32", img_u8 ? img_ch : 3, ran.grid, ran.units);
+            sr_plan_note(c, line);
+        }
         c->last_h = H; c->last_w = W;
         return SR_OK;
     }

@@ -580,7 +580,14 @@ static int balanced_grid(long units, long resident, int cus) {
     return (int)(100 * best_load <= 97 * load0 ? best_grid : (units + per0 - 1) / per0);
 }
 
-hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, hipStream_t s) {
+hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, hipStream_t s, int max_grid, AuxLaunch* ran) {
+    if (ran) *ran = AuxLaunch{0, 0};
+    // the automatic grid, or the caller's cap where that is smaller; what is about to run goes into *ran
+    auto capped = [&](int automatic, long units) {
+        const int grid = max_grid > 0 ? std::min(automatic, max_grid) : automatic;
+        if (ran) *ran = AuxLaunch{grid, units};
+        return grid;
+    };
     if (img_u8 != out_u8) return hipErrorInvalidValue;
     if (out_u8 && !a.qtab) return hipErrorInvalidValue;
     int dev = 0, cus = 256;
@@ -600,7 +607,8 @@ hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, 
                                            : (aligned ? (const void*)bilinear_u8_kernel<4, true> : (const void*)bilinear_u8_kernel<4, false>);
             int resident = 0;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, fn, 256, 0) != hipSuccess || resident < 1) resident = 4;
-            const int grid = balanced_grid((items + 3) / 4, (long)resident * cus, cus);  // (a workgroup: 4 waves, 4 blocks at a time)
+            const long units = (items + 3) / 4;  // (a workgroup: 4 waves, 4 blocks at a time)
+            const int grid = capped(balanced_grid(units, (long)resident * cus, cus), units);
             if (a.img_ch == 3) {
                 if (aligned) hipLaunchKernelGGL((bilinear_u8_kernel<3, true>), dim3(grid), dim3(256), 0, s, a);
                 else hipLaunchKernelGGL((bilinear_u8_kernel<3, false>), dim3(grid), dim3(256), 0, s, a);
@@ -613,14 +621,14 @@ hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, 
         const void* fn = aligned ? (const void*)bilinear_tile_kernel<true> : (const void*)bilinear_tile_kernel<false>;
         int resident = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, fn, 256, 0) != hipSuccess || resident < 1) resident = 4;
-        const int grid = balanced_grid(tiles, (long)std::min(resident, 6) * cus, cus);
+        const int grid = capped(balanced_grid(tiles, (long)std::min(resident, 6) * cus, cus), tiles);
         if (aligned) hipLaunchKernelGGL((bilinear_tile_kernel<true>), dim3(grid), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((bilinear_tile_kernel<false>), dim3(grid), dim3(256), 0, s, a);
     } else {
         const int OH = a.H / 3, OW = a.W / 3;
         const long tiles = (long)a.n * ((OW + kDsTW - 1) / kDsTW) * ((OH + kDsTH - 1) / kDsTH);
         if (tiles == 0) return hipSuccess;
-        const int grid = balanced_grid(tiles, 8L * cus, cus);  // (8 workgroups per CU: 3 / 4 / 6 measured 10-60 % slower at 5760x3240)
+        const int grid = capped(balanced_grid(tiles, 8L * cus, cus), tiles);  // (8 workgroups per CU: 3 / 4 / 6 measured 10-60 % slower at 5760x3240)
         if (img_u8 && a.img_ch == 3) hipLaunchKernelGGL((downsample_tile_kernel<true, true, 3>), dim3(grid), dim3(256), 0, s, a);
         else if (img_u8 && a.img_ch == 4) hipLaunchKernelGGL((downsample_tile_kernel<true, true, 4>), dim3(grid), dim3(256), 0, s, a);
         else if (img_u8) return hipErrorInvalidValue;

@@ -94,6 +94,7 @@ struct sr_ctx {
     std::vector<ForkTune> fork_tune;
     bool fork_autotune = true;
     unsigned long long fork_tune_clock = 0;
+    int env_auxgrid = 0;              // bilinear_net / downsample_net: at most this many workgroups per launch (0: automatic); "auxgrid"
     int env_bands = 0;                // host pipeline: forced number of row bands (0: automatic)
     std::vector<int> env_rows;        // host pipeline: forced band heights (empty: automatic)
     bool env_rows_two = false;        //   ... computed on alternating streams instead of in order

@@ -118,7 +118,13 @@ struct AuxArgs {          // bilinear_net / downsample_net (parameter-free graph
     const void* qtab;     // u8 output: the quantiser table of the context (sr_aux_build_tables), else unused
 };
 hipError_t sr_aux_build_tables(void** d_tab);  // sr_aux.hip: data_to_img(LinearToSrgb(l)) as a step table, built once per context
-hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, hipStream_t s);  // graph: 1 bilinear, 2 downsample
+struct AuxLaunch {        // what sr_launch_aux launched: workgroups, and the pieces their outer loops walk (tiles; bilinear_u8_kernel: groups
+    int grid;             // of four wave items) -- a workgroup takes every grid-th piece, so the launch is multi-round exactly when
+    long units;           // units > grid.  0, 0: an empty image, nothing launched
+};
+// graph: 1 bilinear, 2 downsample.  max_grid > 0: never more workgroups than that (sr_set_experiment "auxgrid": the kernels take their
+// stride from gridDim.x, so no output byte depends on it)
+hipError_t sr_launch_aux(int graph, const AuxArgs& a, bool img_u8, bool out_u8, hipStream_t s, int max_grid = 0, AuxLaunch* ran = nullptr);
 
 // prec: 0 = exact f32 (v_mfma_f32_32x32x2_f32), 1 = split-half (3 x v_mfma_f32_32x32x16_f16)
 hipError_t sr_launch_conv0(const Conv0Args& a, int th, int prec, int nblk, bool img_u8, hipStream_t s);

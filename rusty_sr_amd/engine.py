@@ -719,7 +719,7 @@ class Engine:
         _lib.check(self._L.sr_set_pipeline(self._ctx, 1 if on else 0))
 
     def set_experiment(self, key: str, value: str = ""):
-        """sr_set_experiment: "th" / "pipe" / "bw" A/B switches (results do not depend on them)."""
+        """sr_set_experiment: "th" / "pipe" / "bw" A/B switches, "auxgrid" (results do not depend on them)."""
         _lib.check(self._L.sr_set_experiment(self._ctx, key.encode(), value.encode()))
 
     def get_experiment(self, key: str) -> str:
@@ -737,10 +737,11 @@ class Engine:
 
     def last_plan(self) -> dict:
         """What the last call on this context ran (sr_get_experiment "plan"), as data:
-        {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...]}.
+        {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...], "aux": [dict, ...]}.
         host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
-        st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row)."""
-        rec = {"host": [], "fork": [], "launches": []}
+        st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
+        parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid."""
+        rec = {"host": [], "fork": [], "launches": [], "aux": []}
         for line in self.get_experiment("plan").splitlines():
             words = line.split()
             count = 1
@@ -763,6 +764,12 @@ class Engine:
                     d[k] = int(d[k])
                 d["count"] = count
                 rec["launches"].append(d)
+            elif words[0] == "aux":
+                d = dict(w.split("=", 1) for w in words[1:])
+                for k in ("ch", "grid", "units"):
+                    d[k] = int(d[k])
+                d["count"] = count
+                rec["aux"].append(d)
         return rec
 
     def set_profiling(self, on: bool):
