@@ -31,17 +31,14 @@ int queue_alpha(sr_ctx* c, const uint8_t* d_in, int n, int h, int w, uint8_t* d_
     if (sr_alpha_bleed_blocks(n, h, w) > (size_t)INT32_MAX || sr_alpha_merge_blocks(c->factor, n, h, w) > (size_t)INT32_MAX) return SR_E_NOMEM;
     const uint8_t* img = d_in;
     if (radius > 0) {
-        if ((size_t)n * in_img > c->ableed_cap) {  // more than the device has at all: refused by arithmetic, nothing attempted
+        if ((size_t)n * in_img > c->d_ableed.cap) {  // more than the device has at all: refused by arithmetic, nothing attempted
             if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
             if ((size_t)n * (in_img + out_img) > c->total_mem) return SR_E_NOMEM;
         }
-        const int rc = sr_ensure_buf(c, &c->d_ableed, &c->ableed_cap, (size_t)n * in_img);
-        if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated
-            sr_free_buf(c->d_ableed, c->ableed_cap);
-            return rc;
-        }
-        HIPCHK(c, sr_launch_alpha_bleed(d_in, (uint8_t*)c->d_ableed, n, h, w, radius, s));
-        img = (const uint8_t*)c->d_ableed;
+        const int rc = sr_ensure_bufs(c, {{&c->d_ableed, (size_t)n * in_img}});
+        if (rc != SR_OK) return rc;
+        HIPCHK(c, sr_launch_alpha_bleed(d_in, (uint8_t*)c->d_ableed.p, n, h, w, radius, s));
+        img = (const uint8_t*)c->d_ableed.p;
     }
     if (members == 1u) {
         const int rc = sr_run_stack_auto(c, img, true, 4, n, h, w, 0, 0, d_out, true, s);
@@ -56,67 +53,31 @@ int queue_alpha(sr_ctx* c, const uint8_t* d_in, int n, int h, int w, uint8_t* d_
     return SR_OK;
 }
 
-// The host-pointer call, after sr_ensemble.cpp's ensemble_host: one upload, the device call, one download, on the context's own stream;
-// synchronous.  In the split-half mode a value that left its domain makes the whole call run again in exact f32.
+// The host-pointer call: one upload, the device call, one download (sr_host_call).  sr_last_timing: total = bleed, every pass of the network
+// and the merge; h2d / d2h the two copies.
 int alpha_host(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* out, int radius, unsigned members) {
     sr_plan_clear(c);
-    int rc = check_upscale_args(c, in, out, n, h, w, radius, members);
+    const int rc = check_upscale_args(c, in, out, n, h, w, radius, members);
     if (rc != SR_OK) return rc;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
-    // a fault an earlier unchecked *_dev call left is that call's to report (sr_check_domain), not a reason to recompute this one
-    if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
     const size_t f = (size_t)c->factor;
     const size_t in_bytes = (size_t)n * h * w * 4, out_bytes = (size_t)n * f * h * f * w * 4;
-    rc = sr_ensure_buf(c, &c->d_in[0], &c->in_cap[0], in_bytes);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_out[0], &c->out_cap[0], out_bytes);
-    if (rc != SR_OK) {
-        sr_free_buf(c->d_in[0], c->in_cap[0]);
-        sr_free_buf(c->d_out[0], c->out_cap[0]);
-        return rc;
-    }
-    const bool prof = c->profiling;
-    while (prof && c->pool.size() < 4) {
-        hipEvent_t e = nullptr;
-        HIPCHK(c, hipEventCreate(&e));
-        c->pool.push_back(e);
-    }
-    hipStream_t s = c->stream;
-    if (prof) HIPCHK(c, hipEventRecord(c->pool[0], s));
-    HIPCHK(c, hipMemcpyAsync(c->d_in[0], in, in_bytes, hipMemcpyHostToDevice, s));
-    if (prof) HIPCHK(c, hipEventRecord(c->pool[1], s));
-    rc = queue_alpha(c, (const uint8_t*)c->d_in[0], n, h, w, (uint8_t*)c->d_out[0], radius, members, s);
-    hipError_t e1 = hipSuccess;
-    if (rc == SR_OK && prof) e1 = hipEventRecord(c->pool[2], s);
-    if (rc == SR_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(out, c->d_out[0], out_bytes, hipMemcpyDeviceToHost, s);
-    if (rc == SR_OK && e1 == hipSuccess && prof) e1 = hipEventRecord(c->pool[3], s);
-    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
-    if (rc != SR_OK) return rc;
-    HIPCHK(c, e1);
-    HIPCHK(c, e2);
-    if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
-        *(volatile int*)c->h_domain = 0;
-        (void)sr_set_precision(c, SR_PRECISION_F32);
-        rc = alpha_host(c, in, n, h, w, out, radius, members);
-        (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
-        ++c->domain_fallbacks;
-        return rc;
-    }
-    if (prof) {  // sr_last_timing: total = bleed, every pass of the network and the merge; h2d / d2h the two copies
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[0], c->pool[1])); c->h2d_ms = ms;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[1], c->pool[2])); c->total_ms = ms;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[2], c->pool[3])); c->d2h_ms = ms;
-    }
-    return SR_OK;
+    return sr_host_call(
+        c, true, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) { return queue_alpha(c, (const uint8_t*)c->d_in[0].p, n, h, w, (uint8_t*)c->d_out[0].p, radius, members, s); },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
 }
 
 }  // namespace
 
 void sr_alpha_release(sr_ctx* c) {
-    sr_free_buf(c->d_ableed, c->ableed_cap);
+    sr_free_buf(c->d_ableed);
 }
 
 extern "C" {

@@ -470,8 +470,8 @@ void sr_destroy(sr_ctx* c) {
     if (c->d_params) (void)hipFree(c->d_params);
     if (c->d_qtab) (void)hipFree(c->d_qtab);
     if (c->h_domain) (void)hipHostFree(c->h_domain);
-    for (auto& p : c->d_in) if (p) (void)hipFree(p);
-    for (auto& p : c->d_out) if (p) (void)hipFree(p);
+    for (auto& b : c->d_in) sr_free_buf(b);
+    for (auto& b : c->d_out) sr_free_buf(b);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : c->ev_fork) if (e) (void)hipEventDestroy(e);
     sr_fork_tune_clear(c);
@@ -683,12 +683,83 @@ int sr_ensure_streams(sr_ctx* c, bool pipelined) {
     return SR_OK;
 }
 
-int sr_ensure_buf(sr_ctx* c, void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return SR_OK;
-    if (*p) HIPCHK(c, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    HIPCHK(c, hipMalloc(p, bytes));
-    *cap = bytes;
+int sr_ensure_buf(sr_ctx* c, sr_buf& b, size_t bytes) {
+    if (bytes <= b.cap) return SR_OK;
+    if (b.p) HIPCHK(c, hipFree(b.p));
+    b = sr_buf{};
+    HIPCHK(c, hipMalloc(&b.p, bytes));
+    b.cap = bytes;
+    return SR_OK;
+}
+
+int sr_ensure_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group) {
+    for (const sr_buf_want& w : group) {
+        const int rc = sr_ensure_buf(c, *w.buf, w.bytes);
+        if (rc == SR_OK) continue;
+        for (const sr_buf_want& g : group) sr_free_buf(*g.buf);
+        return rc;
+    }
+    return SR_OK;
+}
+
+// The synchronous host-pointer call on the context's own stream (sr_internal.h).  The phases are callables so that whatever fails in one
+// of them -- a HIPCHK around a copy as much as the queued work -- returns HERE: between the first queued operation and the drain there is
+// no return, so the stream is drained also on failure: nothing of the call may still run once it has returned, neither a copy from or to
+// the caller's memory nor a kernel.
+int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_list<sr_buf_want> staging, const sr_host_phase& upload,
+                 const sr_host_phase& work, const sr_host_phase& download) {
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = sr_ensure_streams(c, false);
+    if (rc != SR_OK) return rc;
+    if (network) sr_domain_set_aside(c);
+    rc = sr_ensure_bufs(c, staging);
+    if (rc != SR_OK) return rc;
+    const bool prof = c->profiling && times != SR_TIMES_NONE, parts = prof && times == SR_TIMES_PARTS;
+    while (prof && c->pool.size() < 4) {
+        hipEvent_t e = nullptr;
+        HIPCHK(c, hipEventCreate(&e));
+        c->pool.push_back(e);
+    }
+    hipStream_t s = c->stream;
+    const auto queue = [&]() -> int {
+        if (prof) HIPCHK(c, hipEventRecord(c->pool[0], s));
+        int r = upload(s);
+        if (r != SR_OK) return r;
+        if (parts) HIPCHK(c, hipEventRecord(c->pool[1], s));
+        r = work(s);
+        if (r != SR_OK) return r;
+        if (parts) HIPCHK(c, hipEventRecord(c->pool[2], s));
+        r = download(s);
+        if (r != SR_OK) return r;
+        if (prof) HIPCHK(c, hipEventRecord(c->pool[3], s));
+        return SR_OK;
+    };
+    const auto run = [&]() -> int {
+        const int r = queue();
+        const hipError_t drained = hipStreamSynchronize(s);
+        if (r != SR_OK) return r;
+        HIPCHK(c, drained);
+        return SR_OK;
+    };
+    rc = run();
+    if (rc == SR_OK && network && sr_domain_tripped(c)) {
+        // Some value of the call left the split-half mode's domain (the stream has drained: the flag is final).  A synchronous call never
+        // hands out clamped pixels: the whole job is computed again in exact f32 -- graph.forward takes any f32 (main.rs:171).
+        sr_plan_clear(c);
+        (void)sr_set_precision(c, SR_PRECISION_F32);
+        rc = run();
+        (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
+    }
+    if (rc != SR_OK || !prof) return rc;
+    float ms = 0;  // sr_last_timing; the stage times are the conv stack's own (its last pass's)
+    if (parts) {
+        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[0], c->pool[1])); c->h2d_ms = ms;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[1], c->pool[2])); c->total_ms = ms;
+        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[2], c->pool[3])); c->d2h_ms = ms;
+    } else {
+        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[0], c->pool[3])); c->total_ms = ms;
+    }
     return SR_OK;
 }
 
@@ -1404,10 +1475,7 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     if ((y_lo > 0 || y_hi < h) && (n != 1 || c->graph != SR_GRAPH_SR_NET)) return SR_E_INVALID;
     if (y_lo > 0 && y_lo < SR_HALO) return SR_E_HALO;
     if (y_hi < h && h - y_hi < SR_HALO) return SR_E_HALO;
-    // A fault still standing in the context's domain word was raised by an EARLIER call -- an unchecked *_dev call (a context has one
-    // caller: nothing of it is still running once that caller is here) -- and is that call's to report (sr_check_domain); it must
-    // not make this call, whose values may all be in range, recompute in f32.  Set it aside.
-    if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
+    sr_domain_set_aside(c);
     bool in_order = false;
     const std::vector<Chunk> plan = plan_chunks(c, deal, h, w, in_px, out_px, y_lo, y_hi, &in_order);
     const int nch = (int)plan.size();
@@ -1438,18 +1506,10 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     hipStream_t down = nch > 1 ? c->copy_out : c->stream;
     size_t in_max = 0, out_max = 0;
     for (const Chunk& k : plan) { in_max = std::max(in_max, k.in_bytes); out_max = std::max(out_max, k.out_bytes); }
-    for (int sl = 0; sl < slots; ++sl) {
-        int rc = sr_ensure_buf(c, &c->d_in[sl], &c->in_cap[sl], in_max);
-        if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_out[sl], &c->out_cap[sl], out_max);
-        if (rc != SR_OK) {  // a job that does not fit must not leave its partial staging buffers behind (they may be most of the device)
-            for (int k = 0; k < 2; ++k) {
-                if (c->d_in[k]) (void)hipFree(c->d_in[k]);
-                if (c->d_out[k]) (void)hipFree(c->d_out[k]);
-                c->d_in[k] = c->d_out[k] = nullptr;
-                c->in_cap[k] = c->out_cap[k] = 0;
-            }
-            return rc;
-        }
+    {
+        const size_t in1 = slots == 2 ? in_max : 0, out1 = slots == 2 ? out_max : 0;
+        const int rc = sr_ensure_bufs(c, {{&c->d_in[0], in_max}, {&c->d_out[0], out_max}, {&c->d_in[1], in1}, {&c->d_out[1], out1}});
+        if (rc != SR_OK) return rc;
     }
     // events per chunk: 0 upload begins, 1 upload done, 2 kernels begin, 3 kernels done, 4 download done
     while (c->pool.size() < (size_t)nch * 5) {
@@ -1467,8 +1527,8 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
         const int pieces = contiguous ? 1 : k.n;
         const size_t in_img = k.in_bytes / (contiguous ? 1 : k.n), out_img = k.out_bytes / (contiguous ? 1 : k.n);
         for (int j = 0; j < pieces; ++j) {
-            if (up) HIPCHK(c, hipMemcpyAsync((char*)c->d_in[sl] + j * in_img, src + k.in_off + j * k.in_step, in_img, hipMemcpyHostToDevice, on));
-            else HIPCHK(c, hipMemcpyAsync(dst + k.out_off + j * k.out_step, (const char*)c->d_out[sl] + j * out_img, out_img, hipMemcpyDeviceToHost, on));
+            if (up) HIPCHK(c, hipMemcpyAsync((char*)c->d_in[sl].p + j * in_img, src + k.in_off + j * k.in_step, in_img, hipMemcpyHostToDevice, on));
+            else HIPCHK(c, hipMemcpyAsync(dst + k.out_off + j * k.out_step, (const char*)c->d_out[sl].p + j * out_img, out_img, hipMemcpyDeviceToHost, on));
         }
         return SR_OK;
     };
@@ -1490,7 +1550,7 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
         if (upl != cs) HIPCHK(c, hipStreamWaitEvent(cs, ev(i, 1), 0));
         if (i >= 2) HIPCHK(c, hipStreamWaitEvent(cs, ev(i - 2, 4), 0));   // slot's previous download
         HIPCHK(c, hipEventRecord(ev(i, 2), cs));
-        rc = sr_run_stack(c, c->d_in[sl], img_u8, img_ch, k.n, k.h_ext, w, k.halo_top, k.halo_bot, c->d_out[sl],
+        rc = sr_run_stack(c, c->d_in[sl].p, img_u8, img_ch, k.n, k.h_ext, w, k.halo_top, k.halo_bot, c->d_out[sl].p,
                           out_u8, cs, sl);
         if (rc != SR_OK) return rc;
         HIPCHK(c, hipEventRecord(ev(i, 3), cs));
@@ -1525,15 +1585,11 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     c->h2d_ms = h2d; c->total_ms = ker; c->d2h_ms = d2h; c->band_pending = false;
     c->last_chunks = nch;
     if (nch > 1) c->last_h = c->last_w = 0;  // the feature maps hold one chunk only: sr_read_feature refuses
-    if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
-        // Some value of this call left the split-half mode's domain (every stream has drained: the flag is final).  A synchronous
-        // call never hands out clamped pixels: the whole job is computed again in exact f32 -- graph.forward takes any f32 (main.rs:171).
-        *(volatile int*)c->h_domain = 0;
+    if (sr_domain_tripped(c)) {  // (every stream has drained: the flag is final) the whole job again in exact f32, as sr_host_call does
         if (reserve) return SR_OK;
         (void)sr_set_precision(c, SR_PRECISION_F32);
         const int rc2 = run_host(c, in, img_u8, img_ch, deal, h, w, out, out_u8, y_lo, y_hi, false);
         (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
-        ++c->domain_fallbacks;
         return rc2;
     }
     return SR_OK;

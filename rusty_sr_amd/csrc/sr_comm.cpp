@@ -116,7 +116,7 @@ BandGeom band_geom(const sr_ctx* c, int h_band, int w, size_t px_bytes) {
 // rank's send blocks for a receive nobody has posted yet).
 int post_exchange(sr_ctx* c, Rccl* R, const void* d_band, int h_band, const BandGeom& g, hipStream_t s) {
     const char* band = (const char*)d_band;
-    char* ext = (char*)c->d_ext;
+    char* ext = (char*)c->d_ext.p;
     const size_t halo = (size_t)SR_HALO * g.row_bytes;
     ncclComm_t comm = (ncclComm_t)c->comm;
     if (g.top) {
@@ -137,7 +137,7 @@ int prepare_band(sr_ctx* c, const void* d_band, int h_band, int w, size_t px_byt
     if (c->comm_nranks > 1 && h_band < SR_HALO) return SR_E_HALO;  // a neighbour reads SR_HALO rows of this band
     HIPCHK(c, hipSetDevice(c->device));
     g = band_geom(c, h_band, w, px_bytes);
-    const int rc = sr_ensure_buf(c, &c->d_ext, &c->ext_cap, (size_t)g.h_ext * g.row_bytes);
+    const int rc = sr_ensure_buf(c, c->d_ext, (size_t)g.h_ext * g.row_bytes);
     if (rc != SR_OK) return rc;
     // Two event pairs time every sharded step on the band's stream, profiling or not (an event record costs the stream nothing):
     // the whole step of this context and the halo exchange inside it.  They are read -- with a wait for the second event -- only when
@@ -157,7 +157,7 @@ int prepare_band(sr_ctx* c, const void* d_band, int h_band, int w, size_t px_byt
         HIPCHK(c, hipEventRecord(c->ev_xfork, s));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_xfork, 0));
     }
-    HIPCHK(c, hipMemcpyAsync((char*)c->d_ext + (size_t)g.top * g.row_bytes, d_band, (size_t)h_band * g.row_bytes,
+    HIPCHK(c, hipMemcpyAsync((char*)c->d_ext.p + (size_t)g.top * g.row_bytes, d_band, (size_t)h_band * g.row_bytes,
                              hipMemcpyDeviceToDevice, s));
     return SR_OK;
 }
@@ -206,7 +206,7 @@ int post_layer_exchange(sr_ctx* c, Rccl* R, const LayerRows& r, hipStream_t s) {
 // one rank's band pass in that mode: stage, exchange, stage, ... all on `s`
 int run_layers_rank(sr_ctx* c, Rccl* R, bool u8, int img_ch, int h_band, int w, const BandGeom& g, void* d_out, const sr_halo_gate* gate, hipStream_t s) {
     sr_band_pass* bp = nullptr;
-    int rc = sr_band_pass_begin(c, c->d_ext, u8, img_ch, g.h_ext, w, g.top, g.bot, d_out, u8, s, true, gate, &bp);
+    int rc = sr_band_pass_begin(c, c->d_ext.p, u8, img_ch, g.h_ext, w, g.top, g.bot, d_out, u8, s, true, gate, &bp);
     for (int st = 0; st < 5 && rc == SR_OK; ++st) {
         rc = sr_band_pass_stage(bp, st);
         if (rc != SR_OK || st == 4) break;
@@ -250,7 +250,7 @@ int run_sharded(sr_ctx* c, const void* d_band, bool u8, int img_ch, int h_band, 
         gate = gate_of(c, g);
     }
     if (c->layer_halos && c->comm_nranks > 1) rc = run_layers_rank(c, rccl(), u8, img_ch, h_band, w, g, d_out, &gate, s);
-    else rc = sr_run_stack_auto(c, c->d_ext, u8, img_ch, 1, g.h_ext, w, g.top, g.bot, d_out, u8, s, c->comm_nranks > 1 ? &gate : nullptr);
+    else rc = sr_run_stack_auto(c, c->d_ext.p, u8, img_ch, 1, g.h_ext, w, g.top, g.bot, d_out, u8, s, c->comm_nranks > 1 ? &gate : nullptr);
     if (rc != SR_OK) return rc;
     HIPCHK(c, hipEventRecord(c->ev_band[1], s));
     c->comm_pending = c->wait_pending = c->comm_nranks > 1;
@@ -299,7 +299,7 @@ int run_sharded_all(sr_ctx* const* ctxs, int n, const void* const* d_bands, cons
         for (int k = 0; k < n && rc == SR_OK; ++k) {
             sr_ctx* c = ctxs[k];
             const size_t halo = (size_t)SR_HALO * g[k].row_bytes;
-            char* ext = (char*)c->d_ext;
+            char* ext = (char*)c->d_ext.p;
             rc = hip(c, hipSetDevice(c->device));
             if (rc == SR_OK) rc = hip(c, hipEventRecord(c->ev_comm[0], c->stream2));
             if (rc == SR_OK && g[k].top)
@@ -347,7 +347,7 @@ int run_sharded_all(sr_ctx* const* ctxs, int n, const void* const* d_bands, cons
             rc = hip(c, hipSetDevice(c->device));
             for (auto& e : c->ev_layer) if (rc == SR_OK && !e) rc = hip(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
             gates[k] = gate_of(c, g[k]);
-            if (rc == SR_OK) rc = sr_band_pass_begin(c, c->d_ext, u8, img_ch, g[k].h_ext, w, g[k].top, g[k].bot, d_outs[k], u8, c->stream, true, &gates[k], &bp[k]);
+            if (rc == SR_OK) rc = sr_band_pass_begin(c, c->d_ext.p, u8, img_ch, g[k].h_ext, w, g[k].top, g[k].bot, d_outs[k], u8, c->stream, true, &gates[k], &bp[k]);
         }
         for (int st = 0; st < 5 && rc == SR_OK; ++st) {
             for (int k = 0; k < n && rc == SR_OK; ++k) {
@@ -393,7 +393,7 @@ int run_sharded_all(sr_ctx* const* ctxs, int n, const void* const* d_bands, cons
     }
     for (int k = 0; k < n && rc == SR_OK && !layers; ++k) {
         const sr_halo_gate gate = gate_of(ctxs[k], g[k]);
-        rc = sr_run_stack_auto(ctxs[k], ctxs[k]->d_ext, u8, img_ch, 1, g[k].h_ext, w, g[k].top, g[k].bot, d_outs[k], u8, ctxs[k]->stream,
+        rc = sr_run_stack_auto(ctxs[k], ctxs[k]->d_ext.p, u8, img_ch, 1, g[k].h_ext, w, g[k].top, g[k].bot, d_outs[k], u8, ctxs[k]->stream,
                                n > 1 ? &gate : nullptr);
         if (rc == SR_OK) rc = hip(ctxs[k], hipSetDevice(ctxs[k]->device));
         if (rc == SR_OK) rc = hip(ctxs[k], hipEventRecord(ctxs[k]->ev_band[1], ctxs[k]->stream));
@@ -418,7 +418,7 @@ void sr_comm_release(sr_ctx* c) {
         c->comm = nullptr;
     }
     c->comm_rank = 0; c->comm_nranks = 1; c->comm_local = false; c->comm_broken = false;
-    if (c->d_ext) { (void)hipFree(c->d_ext); c->d_ext = nullptr; c->ext_cap = 0; }
+    sr_free_buf(c->d_ext);
     for (auto& e : c->ev_comm) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : c->ev_band) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     for (auto& e : c->ev_wait) if (e) { (void)hipEventDestroy(e); e = nullptr; }

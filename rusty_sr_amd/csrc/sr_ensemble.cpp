@@ -31,12 +31,6 @@ sr_ens_map member_map(int k, bool inverse, int dst_h, int dst_w) {
     return m;
 }
 
-void free_all(sr_ctx* c) {
-    sr_free_buf(c->d_ein, c->ein_cap);
-    sr_free_buf(c->d_eout, c->eout_cap);
-    sr_free_buf(c->d_eacc, c->eacc_cap);
-}
-
 int check_image_args(const sr_ctx* c, const void* in, const void* out, bool img_u8, int ch, int n, int h, int w, unsigned members) {
     if (!c || !in || !out || n < 1) return SR_E_INVALID;
     if (img_u8 && ch != 3 && ch != 4) return SR_E_INVALID;
@@ -55,62 +49,26 @@ int queue_batch(sr_ctx* c, const void* d_in, bool img_u8, int ch, int n, int h, 
     return SR_OK;
 }
 
-// The host-pointer calls: one upload, the device call, one download, on the context's own stream; synchronous.  In the split-half mode a
-// value that left its domain makes the whole call run again in exact f32, as the plain host-pointer calls do.
+// The host-pointer calls: one upload, the device call, one download (sr_host_call).  sr_last_timing: total = every pass and pixel move of the
+// call; the stage times are the last pass's.
 int ensemble_host(sr_ctx* c, const void* in, bool img_u8, int ch, int n, int h, int w, void* out, bool out_u8, unsigned members) {
     sr_plan_clear(c);
-    int rc = check_image_args(c, in, out, img_u8, ch, n, h, w, members);
+    const int rc = check_image_args(c, in, out, img_u8, ch, n, h, w, members);
     if (rc != SR_OK) return rc;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
-    // a fault an earlier unchecked *_dev call left is that call's to report (sr_check_domain), not a reason to recompute this one
-    if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
     const size_t f = (size_t)c->factor;
     const size_t in_bytes = (size_t)n * h * w * (img_u8 ? (size_t)ch : 3 * sizeof(float));
     const size_t out_bytes = (size_t)n * f * h * f * w * (out_u8 ? 4 : 3 * sizeof(float));
-    rc = sr_ensure_buf(c, &c->d_in[0], &c->in_cap[0], in_bytes);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_out[0], &c->out_cap[0], out_bytes);
-    if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated
-        sr_free_buf(c->d_in[0], c->in_cap[0]);
-        sr_free_buf(c->d_out[0], c->out_cap[0]);
-        return rc;
-    }
-    const bool prof = c->profiling;
-    while (prof && c->pool.size() < 4) {
-        hipEvent_t e = nullptr;
-        HIPCHK(c, hipEventCreate(&e));
-        c->pool.push_back(e);
-    }
-    hipStream_t s = c->stream;
-    if (prof) HIPCHK(c, hipEventRecord(c->pool[0], s));
-    HIPCHK(c, hipMemcpyAsync(c->d_in[0], in, in_bytes, hipMemcpyHostToDevice, s));
-    if (prof) HIPCHK(c, hipEventRecord(c->pool[1], s));
-    rc = queue_batch(c, c->d_in[0], img_u8, ch, n, h, w, c->d_out[0], out_u8, members, s);
-    hipError_t e1 = hipSuccess;
-    if (rc == SR_OK && prof) e1 = hipEventRecord(c->pool[2], s);
-    if (rc == SR_OK && e1 == hipSuccess) e1 = hipMemcpyAsync(out, c->d_out[0], out_bytes, hipMemcpyDeviceToHost, s);
-    if (rc == SR_OK && e1 == hipSuccess && prof) e1 = hipEventRecord(c->pool[3], s);
-    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
-    if (rc != SR_OK) return rc;
-    HIPCHK(c, e1);
-    HIPCHK(c, e2);
-    if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
-        *(volatile int*)c->h_domain = 0;
-        (void)sr_set_precision(c, SR_PRECISION_F32);
-        rc = ensemble_host(c, in, img_u8, ch, n, h, w, out, out_u8, members);
-        (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
-        ++c->domain_fallbacks;
-        return rc;
-    }
-    if (prof) {  // sr_last_timing: total = every pass and pixel move of the call; the stage times are the last pass's
-        float ms = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[0], c->pool[1])); c->h2d_ms = ms;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[1], c->pool[2])); c->total_ms = ms;
-        HIPCHK(c, hipEventElapsedTime(&ms, c->pool[2], c->pool[3])); c->d2h_ms = ms;
-    }
-    return SR_OK;
+    return sr_host_call(
+        c, true, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) { return queue_batch(c, c->d_in[0].p, img_u8, ch, n, h, w, c->d_out[0].p, out_u8, members, s); },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
 }
 
 int ensemble_dev(sr_ctx* c, const void* d_in, bool img_u8, int ch, int n, int h, int w, void* d_out, bool out_u8, unsigned members,
@@ -127,7 +85,7 @@ int ensemble_dev(sr_ctx* c, const void* d_in, bool img_u8, int ch, int n, int h,
 }  // namespace
 
 void sr_ensemble_release(sr_ctx* c) {
-    free_all(c);
+    for (sr_buf* b : {&c->d_ein, &c->d_eout, &c->d_eacc}) sr_free_buf(*b);
 }
 
 int sr_ensemble_check(const sr_ctx* c, unsigned members, int h, int w) {
@@ -152,18 +110,13 @@ int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
     const size_t acc_bytes = out_u8 && count > 1 ? map_bytes : 0;
     const size_t blocks = std::max(sr_ens_blocks(OH, OW, false), sr_ens_blocks(OH, OW, true));
     if (blocks > (size_t)INT32_MAX) return SR_E_NOMEM;
-    if (in_bytes > c->ein_cap || map_bytes > c->eout_cap || acc_bytes > c->eacc_cap) {
+    if (in_bytes > c->d_ein.cap || map_bytes > c->d_eout.cap || acc_bytes > c->d_eacc.cap) {
         if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
         if (map_bytes + acc_bytes + in_bytes > c->total_mem) return SR_E_NOMEM;
     }
-    int rc = sr_ensure_buf(c, &c->d_ein, &c->ein_cap, in_bytes);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_eout, &c->eout_cap, map_bytes);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_eacc, &c->eacc_cap, acc_bytes);
-    if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
-        free_all(c);
-        return rc;
-    }
-    float* acc = out_u8 ? (float*)c->d_eacc : (float*)d_out;
+    int rc = sr_ensure_bufs(c, {{&c->d_ein, in_bytes}, {&c->d_eout, map_bytes}, {&c->d_eacc, acc_bytes}});
+    if (rc != SR_OK) return rc;
+    float* acc = out_u8 ? (float*)c->d_eacc.p : (float*)d_out;
     const float scale = 1.0f / (float)count;
     int done = 0;
     for (int k = 0; k < 8; ++k) {
@@ -172,13 +125,13 @@ int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
         const int hk = swap ? w : h, wk = swap ? h : w;
         const void* img = d_img;
         if (k != 0 || img_u8) {
-            HIPCHK(c, sr_launch_ens_input(d_img, img_u8, img_ch, c->d_ein, member_map(k, false, hk, wk), s));
-            img = c->d_ein;
+            HIPCHK(c, sr_launch_ens_input(d_img, img_u8, img_ch, c->d_ein.p, member_map(k, false, hk, wk), s));
+            img = c->d_ein.p;
         }
-        rc = sr_run_stack_auto(c, img, false, 3, 1, hk, wk, 0, 0, c->d_eout, false, s);
+        rc = sr_run_stack_auto(c, img, false, 3, 1, hk, wk, 0, 0, c->d_eout.p, false, s);
         if (rc != SR_OK) return rc;
         ++done;
-        HIPCHK(c, sr_launch_ens_accumulate((const float*)c->d_eout, acc, d_out, out_u8, done == 1, done == count, scale,
+        HIPCHK(c, sr_launch_ens_accumulate((const float*)c->d_eout.p, acc, d_out, out_u8, done == 1, done == count, scale,
                                            member_map(k, true, OH, OW), s));
     }
     return SR_OK;

@@ -25,8 +25,8 @@ int check_pair_args(sr_ctx* c, const void* params, const void* lr, bool u8, int 
     return sr_check_pair_args(c, u8, lr_ch, hr_ch, n, lh, lw);
 }
 
-// The host-pointer calls: upload parameters, HR batch and (pairs) LR batch, run, download err_sum and the gradient, on the context's own
-// stream; synchronous.  lr: nullptr = the pooled form, h x w the HR size; else h x w is the LR size and lr_ch its channel count.
+// The host-pointer calls: upload parameters, HR batch and (pairs) LR batch, run, download err_sum and the gradient, as one sr_host_call.
+// lr: nullptr = the pooled form, h x w the HR size; else h x w is the LR size and lr_ch its channel count.
 int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* lr, int lr_ch, const void* hr, bool hr_u8, int ch, int n, int h,
                   int w, int linear, float loss_scale, float l2, double* err_sum, size_t* n_elems, float* grad, bool pair) {
     if (!c && sr_no_device()) return SR_E_NO_DEVICE;
@@ -38,42 +38,56 @@ int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* l
     if (np < 0 || n_params != (size_t)np) return SR_E_PARAM_COUNT;
     const size_t lr_bytes = pair ? (size_t)n * h * w * (hr_u8 ? (size_t)lr_ch : 3 * sizeof(float)) : 0;
     if (pair) { h *= c->factor; w *= c->factor; }
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
     const size_t p_bytes = sr_round256((size_t)np * sizeof(float));
     const size_t hr_bytes = (size_t)n * h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
-    rc = sr_ensure_buf(c, &c->d_gin, &c->gin_cap, 2 * p_bytes + sr_round256(hr_bytes) + sr_round256(lr_bytes));
-    if (rc != SR_OK) {
-        sr_free_buf(c->d_gin, c->gin_cap);
-        sr_free_buf(c->d_gws, c->gws_cap);
-        return rc;
-    }
-    float* d_params = (float*)c->d_gin;
-    float* d_grad = (float*)((char*)c->d_gin + p_bytes);
-    void* d_hr = (char*)c->d_gin + 2 * p_bytes;
-    sr_lr_input in;
-    in.d_lr = (char*)d_hr + sr_round256(hr_bytes); in.u8 = hr_u8; in.ch = lr_ch;
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(d_params, params, (size_t)np * sizeof(float), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_hr, hr, hr_bytes, hipMemcpyHostToDevice, s));
-    if (pair) HIPCHK(c, hipMemcpyAsync((void*)in.d_lr, lr, lr_bytes, hipMemcpyHostToDevice, s));
+    // d_gin: the parameters, the gradient, the HR batch, a pair's LR batch
+    const auto d_params = [&] { return (float*)c->d_gin.p; };
+    const auto d_grad = [&] { return (float*)((char*)c->d_gin.p + p_bytes); };
+    const auto d_hr = [&] { return (char*)c->d_gin.p + 2 * p_bytes; };
+    const auto d_lr = [&] { return d_hr() + sr_round256(hr_bytes); };
     double* slot = nullptr;
-    rc = sr_grad_queue(c, d_params, d_hr, hr_u8, ch, n, h, w, linear != 0, loss_scale, l2, nullptr, d_grad, s, &slot, pair ? &in : nullptr);
     double sum = 0.0;
-    hipError_t e1 = hipSuccess;
-    if (rc == SR_OK) {
-        e1 = hipMemcpyAsync(&sum, slot, sizeof sum, hipMemcpyDeviceToHost, s);
-        if (e1 == hipSuccess) e1 = hipMemcpyAsync(grad, d_grad, (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
+    rc = sr_host_call(  // (no conv stack runs: no domain handling; the workspace shares the staging buffer's fate)
+        c, false, SR_TIMES_NONE, {{&c->d_gin, 2 * p_bytes + sr_round256(hr_bytes) + sr_round256(lr_bytes)}, {&c->d_gws, 0}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(d_params(), params, (size_t)np * sizeof(float), hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(d_hr(), hr, hr_bytes, hipMemcpyHostToDevice, s));
+            if (pair) HIPCHK(c, hipMemcpyAsync(d_lr(), lr, lr_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) {
+            sr_lr_input in;
+            in.d_lr = d_lr(); in.u8 = hr_u8; in.ch = lr_ch;
+            return sr_grad_queue(c, d_params(), d_hr(), hr_u8, ch, n, h, w, linear != 0, loss_scale, l2, nullptr, d_grad(), s, &slot,
+                                 pair ? &in : nullptr);
+        },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(&sum, slot, sizeof sum, hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipMemcpyAsync(grad, d_grad(), (size_t)np * sizeof(float), hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
     if (rc != SR_OK) return rc;
-    HIPCHK(c, e1);
-    HIPCHK(c, e2);
     *err_sum = sum;
     *n_elems = sr_loss_elems(c->factor, n, h, w);
     return SR_OK;
+}
+
+// The device entry points: the arguments checked, then sr_grad_queue on the caller's stream.  pair: h x w is the LR size (else the HR
+// size, and d_lr is not looked at).
+int backprop_dev(sr_ctx* c, const float* d_params, bool pair, const uint8_t* d_lr, int lr_ch, const uint8_t* d_hr, int ch, int n, int h, int w,
+                 int linear, float loss_scale, float l2, double* d_err_sum, float* d_grad, void* stream) {
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    const int rc = pair ? check_pair_args(c, d_params, d_lr, true, lr_ch, d_hr, ch, n, h, w, d_grad) : check_args(c, d_params, d_hr, true, ch, n, h, w, d_grad);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    sr_lr_input in;
+    in.d_lr = d_lr; in.u8 = true; in.ch = lr_ch;
+    if (pair) { h *= c->factor; w *= c->factor; }
+    return sr_grad_queue(c, d_params, d_hr, true, ch, n, h, w, linear != 0, loss_scale, l2, d_err_sum, d_grad, (hipStream_t)stream, nullptr,
+                         pair ? &in : nullptr);
 }
 
 }  // namespace
@@ -81,13 +95,10 @@ int backprop_host(sr_ctx* c, const float* params, size_t n_params, const void* l
 int sr_grad_input_buffer(sr_ctx* c, int n, int OH, int OW, float** x) {
     const size_t x_bytes = sr_round256((size_t)n * OH * OW * 3 * sizeof(float));
     int rc = sr_valid_ensure_table(c);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_gws, &c->gws_cap, x_bytes + sr_grad_workspace_bytes(c->factor, n, OH, OW));
-    if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
-        sr_free_buf(c->d_gws, c->gws_cap);
-        sr_free_buf(c->d_gin, c->gin_cap);
-        return rc;
-    }
-    *x = (float*)c->d_gws;
+    // (the host-pointer calls' staging buffer shares the workspace's fate)
+    if (rc == SR_OK) rc = sr_ensure_bufs(c, {{&c->d_gws, x_bytes + sr_grad_workspace_bytes(c->factor, n, OH, OW)}, {&c->d_gin, 0}});
+    if (rc != SR_OK) return rc;
+    *x = (float*)c->d_gws.p;
     return SR_OK;
 }
 
@@ -118,7 +129,7 @@ int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8
     p.hr = d_hr; p.hr_u8 = hr_u8; p.hr_ch = ch; p.hr_h = h; p.hr_w = w;
     p.tab = c->d_vtab;
     p.linear = linear; p.loss_scale = loss_scale; p.l2 = l2;
-    p.ws = (float*)((char*)c->d_gws + x_bytes);
+    p.ws = (float*)((char*)c->d_gws.p + x_bytes);
     p.err_out = d_err;
     p.grad = d_grad;
     if (result_slot) *result_slot = sr_grad_result_slot(p);
@@ -127,8 +138,8 @@ int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8
 }
 
 void sr_grad_release(sr_ctx* c) {
-    sr_free_buf(c->d_gws, c->gws_cap);
-    sr_free_buf(c->d_gin, c->gin_cap);
+    sr_free_buf(c->d_gws);
+    sr_free_buf(c->d_gin);
 }
 
 extern "C" {
@@ -146,15 +157,7 @@ int sr_backprop_rgba8(sr_ctx* c, const float* params, size_t n_params, const uin
 
 int sr_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_hr, int in_channels, int n, int h, int w, int linear_loss,
                           float loss_scale, float l2, double* d_err_sum, float* d_grad, void* stream) {
-    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
-    sr_plan_clear(c);
-    const int rc = check_args(c, d_params, d_hr, true, in_channels, n, h, w, d_grad);
-    if (rc != SR_OK) return rc;
-    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    return sr_grad_queue(c, d_params, d_hr, true, in_channels, n, h, w, linear_loss != 0, loss_scale, l2, d_err_sum, d_grad,
-                         (hipStream_t)stream, nullptr, nullptr);
+    return backprop_dev(c, d_params, false, nullptr, 3, d_hr, in_channels, n, h, w, linear_loss, loss_scale, l2, d_err_sum, d_grad, stream);
 }
 
 int sr_pair_backprop_f32(sr_ctx* c, const float* params, size_t n_params, const float* lr, const float* hr, int n, int lh, int lw,
@@ -172,17 +175,7 @@ int sr_pair_backprop_rgba8(sr_ctx* c, const float* params, size_t n_params, cons
 int sr_pair_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels,
                                int n, int lh, int lw, int linear_loss, float loss_scale, float l2, double* d_err_sum, float* d_grad,
                                void* stream) {
-    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
-    sr_plan_clear(c);
-    const int rc = check_pair_args(c, d_params, d_lr, true, lr_channels, d_hr, hr_channels, n, lh, lw, d_grad);
-    if (rc != SR_OK) return rc;
-    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    sr_lr_input in;
-    in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
-    return sr_grad_queue(c, d_params, d_hr, true, hr_channels, n, c->factor * lh, c->factor * lw, linear_loss != 0, loss_scale, l2, d_err_sum,
-                         d_grad, (hipStream_t)stream, nullptr, &in);
+    return backprop_dev(c, d_params, true, d_lr, lr_channels, d_hr, hr_channels, n, lh, lw, linear_loss, loss_scale, l2, d_err_sum, d_grad, stream);
 }
 
 int sr_adam_step_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr, float beta1,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -15,6 +17,12 @@
 // the whole call's direct-FLOP rate to within 1 % of the f32 roof on the fastest boxes, which bench.py's contract asserts it stays below
 // (DESIGN.md 4a, item 4); "wino" = "3" runs both, for measurement.
 constexpr int kWinoConv5Halves = 1;
+
+// A device buffer that grows on demand (sr_ensure_buf / sr_ensure_bufs) and is never shrunk but by sr_free_buf.
+struct sr_buf {
+    void* p = nullptr;
+    size_t cap = 0;
+};
 
 struct sr_ctx {
     int device = 0;
@@ -35,7 +43,6 @@ struct sr_ctx {
     bool split_ok = true;
     int* h_domain = nullptr;   // host address of the flag
     int* d_domain = nullptr;   // the same word as the device sees it
-    int domain_fallbacks = 0;  // host-pointer calls that were recomputed in exact f32 because of it
     bool dev_fault = false;    // a fault an earlier *_dev call left in *h_domain, set aside at the start of a host-pointer call: sr_check_domain's
     int graph = SR_GRAPH_SR_NET;
     int factor = SR_FACTOR;
@@ -52,15 +59,14 @@ struct sr_ctx {
     hipStream_t stream2 = nullptr;    // second compute stream of the host pipeline
     // host-pointer entry points: two in / out slots so that chunk i+1 uploads and chunk i-1
     // downloads while chunk i computes (run_host)
-    void* d_in[2] = {nullptr, nullptr};  size_t in_cap[2] = {0, 0};
-    void* d_out[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0};
+    sr_buf d_in[2], d_out[2];
     hipStream_t copy_out = nullptr;   // downloads of a pipelined host call
     hipStream_t copy_in = nullptr;    // uploads: exact-f32 contexts, from their second pipelined call on (else on the compute streams)
     int pipelined_calls = 0;
     std::vector<hipEvent_t> pool;  // per-chunk timing / ordering events of run_host, grown on demand
     int pipeline = 1;              // 0: one upload, one pass, one download
     int last_chunks = 0;
-    hipEvent_t ev[8] = {nullptr};
+    hipEvent_t ev[6] = {nullptr};  // around the five stages of a profiled pass of the conv stack (sr_run_stack)
     bool profiling = false;
     double total_ms = 0, stage_ms[5] = {0}, h2d_ms = 0, d2h_ms = 0;
     int last_h = 0, last_w = 0;
@@ -104,7 +110,7 @@ struct sr_ctx {
     void* comm = nullptr;             // ncclComm_t
     bool comm_local = false;          // sr_comm_init_local: neighbours are contexts of this process, halos go by peer copy
     int comm_rank = 0, comm_nranks = 1;
-    void* d_ext = nullptr; size_t ext_cap = 0;  // band + halo rows, the exchange lands here
+    sr_buf d_ext;  // band + halo rows, the exchange lands here
     hipEvent_t ev_comm[2] = {nullptr, nullptr};  // around the halo exchange of a sharded call, on the stream it runs on (round 6: the context's stream2)
     hipEvent_t ev_wait[2] = {nullptr, nullptr};  // on the band's stream, either side of its wait for the exchange: what of the exchange was NOT hidden
     hipEvent_t ev_xfork = nullptr;               // band's stream -> exchange stream: the caller's band is complete
@@ -122,24 +128,24 @@ struct sr_ctx {
     // made; cleared by every public entry point.
     std::vector<std::pair<std::string, int>> plan_rec;
     // ---- validation pass (sr_valid.cpp): the forward half of the training graph, grown on demand, freed by sr_destroy
-    void* d_vhr = nullptr; size_t vhr_cap = 0;      // the HR image of a host-pointer call
-    void* d_vlr = nullptr; size_t vlr_cap = 0;      // the pooled LR image (the graph's `input` node), f32
-    void* d_vout = nullptr; size_t vout_cap = 0;    // the network's f32 output (`output` node)
-    void* d_vpart = nullptr; size_t vpart_cap = 0;  // the loss kernel's f64 partials, then the host-pointer calls' result
+    sr_buf d_vhr;                                   // the HR image of a host-pointer call
+    sr_buf d_vlr;                                   // the pooled LR image (the graph's `input` node), f32
+    sr_buf d_vout;                                  // the network's f32 output (`output` node)
+    sr_buf d_vpart;                                 // the loss kernel's f64 partials, then the host-pointer calls' result
     float* d_vtab = nullptr;                        // 512 floats: byte / 255, then SrgbToLinear of those (sr_valid.cpp)
     int vnode_h = 0, vnode_w = 0;                   // LR size of the last validation call (0: none yet)
     // ---- backpropagation (sr_grad.cpp): grown on demand, freed by sr_destroy
-    void* d_gws = nullptr; size_t gws_cap = 0;      // saved forward state, gradients of the nodes, partials (sr_grad_workspace_bytes)
-    void* d_gin = nullptr; size_t gin_cap = 0;      // host-pointer calls: params, HR batch, pooled LR batch, gradient
+    sr_buf d_gws;                                   // saved forward state, gradients of the nodes, partials (sr_grad_workspace_bytes)
+    sr_buf d_gin;                                   // host-pointer calls: params, HR batch, pooled LR batch, gradient
     // ---- self-ensemble (sr_ensemble.cpp): grown on demand, freed by sr_destroy
-    void* d_ein = nullptr; size_t ein_cap = 0;      // T_k of the caller's image, f32 RGB
-    void* d_eout = nullptr; size_t eout_cap = 0;    // one member's f32 output map
-    void* d_eacc = nullptr; size_t eacc_cap = 0;    // the f32 accumulator of a call with RGBA8 output (an f32 call accumulates in its output)
+    sr_buf d_ein;                                   // T_k of the caller's image, f32 RGB
+    sr_buf d_eout;                                  // one member's f32 output map
+    sr_buf d_eacc;                                  // the f32 accumulator of a call with RGBA8 output (an f32 call accumulates in its output)
     // ---- metrics (sr_metrics.cpp): grown on demand, freed by sr_destroy
-    void* d_mpart = nullptr; size_t mpart_cap = 0;  // the tile kernel's partials (f64, then u64), then the host-pointer calls' 16-byte result
-    void* d_mimg = nullptr; size_t mimg_cap = 0;    // both images of a host-pointer sr_image_metrics_rgba8 call
+    sr_buf d_mpart;                                 // the tile kernel's partials (f64, then u64), then the host-pointer calls' 16-byte result
+    sr_buf d_mimg;                                  // both images of a host-pointer sr_image_metrics_rgba8 call
     // ---- transparency (sr_alpha.cpp): grown on demand, freed by sr_destroy
-    void* d_ableed = nullptr; size_t ableed_cap = 0;  // the bled copy of the caller's RGBA8 image
+    sr_buf d_ableed;                                // the bled copy of the caller's RGBA8 image
     size_t total_mem = 0;                           // the device's memory, asked for once: a shape beyond it is refused without an allocation
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
@@ -170,10 +176,9 @@ inline bool sr_no_device(bool clear_error = true, int* count = nullptr) {
     return failed || n <= 0;
 }
 
-inline void sr_free_buf(void*& p, size_t& cap) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+inline void sr_free_buf(sr_buf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b = sr_buf{};
 }
 
 inline size_t sr_round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
@@ -269,8 +274,43 @@ int sr_band_pass_stage(sr_band_pass* p, int st);                 // launch stage
 float* sr_band_pass_row(const sr_band_pass* p, int map, int y);  // row y (the pass's image coordinates) of map 0..3 = f, l1, l2, l3, border columns included
 size_t sr_band_pass_row_floats(const sr_band_pass* p);           // ... its length: pitch x 32 floats, contiguous in both map layouts
 void sr_band_pass_end(sr_band_pass* p);
-int sr_ensure_buf(sr_ctx* c, void** p, size_t* cap, size_t bytes);
+int sr_ensure_buf(sr_ctx* c, sr_buf& b, size_t bytes);  // at least `bytes`; what the buffer held is lost when it grows
+// The buffers of one job, all or nothing: each is grown to its size; should one not fit, EVERY buffer of the group is freed -- a job that
+// does not fit must not keep what of it was allocated (it may be most of the device).  (A size of 0 grows nothing: the buffer only shares
+// the group's fate.)
+struct sr_buf_want {
+    sr_buf* buf;
+    size_t bytes;
+};
+int sr_ensure_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group);
 int sr_ensure_streams(sr_ctx* c, bool pipelined);  // the context's own streams are created on first use
+
+// ---- the split-half mode's domain word (sr_ctx::h_domain) in the synchronous host-pointer calls
+// A fault still standing in the word when such a call begins was raised by an EARLIER call -- an unchecked *_dev call (a context has one
+// caller: nothing of it is still running once that caller is here) -- and is that call's to report (sr_check_domain); it must not make
+// this call, whose values may all be in range, recompute in f32.  Set it aside.
+inline void sr_domain_set_aside(sr_ctx* c) {
+    if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
+}
+// Once every stream of the call has drained: did a value of it leave the split-half mode's domain?  Clears the word.
+inline bool sr_domain_tripped(sr_ctx* c) {
+    if (c->precision != SR_PRECISION_SPLIT_F16 || !c->h_domain || !*(volatile int*)c->h_domain) return false;
+    *(volatile int*)c->h_domain = 0;
+    return true;
+}
+
+// ---- One synchronous host-pointer call on the context's own stream (sr_api.cpp): every such entry point but the pipelined upscale
+// (run_host) is its argument checks and a call of this.  It makes the context's device current (and restores the caller's), creates the
+// stream, grows `staging` all or nothing, then runs upload, work, download -- callables that QUEUE on the stream they are given and
+// return a status (a HIPCHK inside one returns into this function) -- and drains the stream whatever they returned.
+// network: the work runs the conv stack -- a stale domain fault is set aside before it, and in the split-half mode a value that left
+// its domain makes all three phases run again in exact f32 (the mode is switched back).  The phases may therefore run twice.
+// times, with profiling on (sr_last_timing): PARTS = h2d_ms the upload, total_ms the work, d2h_ms the download; TOTAL = total_ms all three.
+enum sr_host_times { SR_TIMES_NONE, SR_TIMES_TOTAL, SR_TIMES_PARTS };
+using sr_host_phase = std::function<int(hipStream_t)>;
+int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_list<sr_buf_want> staging, const sr_host_phase& upload,
+                 const sr_host_phase& work, const sr_host_phase& download);
+
 void sr_comm_release(sr_ctx* c);  // sr_comm.cpp: destroy the communicator and its buffers (called by sr_destroy)
 
 // ---- validation pass (sr_valid.hip kernels, sr_valid.cpp host side)

@@ -38,12 +38,12 @@ int sr_metrics_shave(const sr_ctx* c, int shave, int* out) {
 }
 
 void sr_metrics_release(sr_ctx* c) {
-    sr_free_buf(c->d_mpart, c->mpart_cap);
-    sr_free_buf(c->d_mimg, c->mimg_cap);
+    sr_free_buf(c->d_mpart);
+    sr_free_buf(c->d_mimg);
 }
 
 void* sr_metrics_slot(const sr_ctx* c, int H, int W, int shave) {
-    return (char*)c->d_mpart + 16 * (size_t)sr_metrics_blocks(H, W, shave);
+    return (char*)c->d_mpart.p + 16 * (size_t)sr_metrics_blocks(H, W, shave);
 }
 
 void sr_metrics_fill(sr_metrics* m, const void* result16, int H, int W, int shave) {
@@ -57,9 +57,7 @@ void sr_metrics_fill(sr_metrics* m, const void* result16, int H, int W, int shav
 int sr_metrics_reserve(sr_ctx* c, int H, int W, int shave) {
     const long blocks = sr_metrics_blocks(H, W, shave);
     if (blocks > INT32_MAX) return SR_E_INVALID;
-    const int rc = sr_ensure_buf(c, &c->d_mpart, &c->mpart_cap, 16 * (size_t)blocks + 16);
-    if (rc != SR_OK) sr_free_buf(c->d_mpart, c->mpart_cap);
-    return rc;
+    return sr_ensure_bufs(c, {{&c->d_mpart, 16 * (size_t)blocks + 16}});
 }
 
 int sr_metrics_queue(sr_ctx* c, const void* d_a, bool a_u8, int a_ch, long pitch_a, const uint8_t* d_b, int b_ch, long pitch_b, int H, int W,
@@ -67,7 +65,7 @@ int sr_metrics_queue(sr_ctx* c, const void* d_a, bool a_u8, int a_ch, long pitch
     const int rc = sr_metrics_reserve(c, H, W, rq.shave);
     if (rc != SR_OK) return rc;
     void* d_result16 = rq.d_result16 ? rq.d_result16 : sr_metrics_slot(c, H, W, rq.shave);
-    HIPCHK(c, sr_launch_metrics(d_a, a_u8, a_ch, pitch_a, d_b, b_ch, pitch_b, H, W, rq.shave, weights(), c->d_mpart, d_result16, s));
+    HIPCHK(c, sr_launch_metrics(d_a, a_u8, a_ch, pitch_a, d_b, b_ch, pitch_b, H, W, rq.shave, weights(), c->d_mpart.p, d_result16, s));
     return SR_OK;
 }
 
@@ -93,28 +91,22 @@ int sr_image_metrics_rgba8(sr_ctx* c, const uint8_t* a, int a_channels, const ui
     int rc = check_image_args(c, a, a_channels, b, b_channels, h, w, shave, &rq.shave);
     if (rc != SR_OK) return rc;
     if (!metrics) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
     const size_t a_bytes = (size_t)h * w * a_channels, b_bytes = (size_t)h * w * b_channels;
-    rc = sr_ensure_buf(c, &c->d_mimg, &c->mimg_cap, sr_round256(a_bytes) + b_bytes);
-    if (rc != SR_OK) {
-        sr_free_buf(c->d_mimg, c->mimg_cap);
-        return rc;
-    }
-    hipStream_t s = c->stream;
-    uint8_t* d_a = (uint8_t*)c->d_mimg;
-    uint8_t* d_b = d_a + sr_round256(a_bytes);
-    HIPCHK(c, hipMemcpyAsync(d_a, a, a_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(d_b, b, b_bytes, hipMemcpyHostToDevice, s));
-    rc = sr_metrics_queue(c, d_a, true, a_channels, w, d_b, b_channels, w, h, w, rq, s);
     unsigned char result[16] = {0};
-    const hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(result, sr_metrics_slot(c, h, w, rq.shave), 16, hipMemcpyDeviceToHost, s) : hipSuccess;
-    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
+    const auto d_b = [&] { return (uint8_t*)c->d_mimg.p + sr_round256(a_bytes); };
+    rc = sr_host_call(  // (no network runs: no domain handling)
+        c, false, SR_TIMES_NONE, {{&c->d_mimg, sr_round256(a_bytes) + b_bytes}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(c->d_mimg.p, a, a_bytes, hipMemcpyHostToDevice, s));
+            HIPCHK(c, hipMemcpyAsync(d_b(), b, b_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) { return sr_metrics_queue(c, c->d_mimg.p, true, a_channels, w, d_b(), b_channels, w, h, w, rq, s); },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(result, sr_metrics_slot(c, h, w, rq.shave), 16, hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
     if (rc != SR_OK) return rc;
-    HIPCHK(c, e1);
-    HIPCHK(c, e2);
     sr_metrics_fill(metrics, result, h, w, rq.shave);
     return SR_OK;
 }

@@ -48,8 +48,8 @@ struct sr_train {
     std::vector<Img> images;
     size_t store_budget = 0, store_used = 0;
     // per-step buffers, reused in stream order
-    void* d_batch = nullptr; size_t batch_cap = 0;  // the crops, u8
-    void* d_trans = nullptr; size_t trans_cap = 0;  // the rows of transient images a step's crops read
+    sr_buf d_batch;  // the crops, u8
+    sr_buf d_trans;  // the rows of transient images a step's crops read
     void* h_stage[kStage] = {nullptr}; size_t stage_cap[kStage] = {0};
     hipEvent_t stage_ev[kStage] = {nullptr};
     bool stage_pending[kStage] = {false};
@@ -60,10 +60,10 @@ struct sr_train {
 namespace {
 
 // A buffer of the session that steps in flight may still read: grown only after the stream has drained.
-int grow(sr_ctx* c, hipStream_t s, void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return SR_OK;
+int grow(sr_ctx* c, hipStream_t s, sr_buf& b, size_t bytes) {
+    if (bytes <= b.cap) return SR_OK;
     HIPCHK(c, hipStreamSynchronize(s));
-    return sr_ensure_buf(c, p, cap, sr_round256(bytes));
+    return sr_ensure_buf(c, b, sr_round256(bytes));
 }
 
 // Read the err_sum of the oldest step in flight (waits for it).
@@ -120,7 +120,7 @@ int acquire_stage(sr_train* t, size_t trans_bytes, int* slot) {
 int upload_stage(sr_train* t, size_t trans_bytes, int k) {
     sr_ctx* c = t->c;
     if (!trans_bytes) return SR_OK;
-    HIPCHK(c, hipMemcpyAsync(t->d_trans, t->h_stage[k], trans_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(t->d_trans.p, t->h_stage[k], trans_bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(t->stage_ev[k], c->stream));
     t->stage_pending[k] = true;
     t->stage_next = (k + 1) % kStage;
@@ -134,7 +134,7 @@ int finish_step(sr_train* t, int n, int crop_h, int crop_w, const sr_lr_input* l
     const size_t n_elems = sr_loss_elems(c->factor, n, crop_h, crop_w);
     const int slot = (int)(t->queued % SR_TRAIN_RING);
     sr_plan_clear(c);
-    int rc = sr_grad_queue(c, t->d_p, t->d_batch, true, 3, n, crop_h, crop_w, t->linear, (float)(1.0 / (double)n_elems), t->l2, t->d_err + slot,
+    int rc = sr_grad_queue(c, t->d_p, t->d_batch.p, true, 3, n, crop_h, crop_w, t->linear, (float)(1.0 / (double)n_elems), t->l2, t->d_err + slot,
                            t->d_g, s, nullptr, lr);
     if (rc != SR_OK) return rc;  // (SR_E_NOMEM: the context freed its backprop buffers; the parameters are untouched)
     t->last_n = n; t->last_h = crop_h; t->last_w = crop_w;
@@ -150,8 +150,8 @@ void release(sr_train* t) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& im : t->images) (void)hipFree(im.d);
     if (t->d_state) (void)hipFree(t->d_state);
-    if (t->d_batch) (void)hipFree(t->d_batch);
-    if (t->d_trans) (void)hipFree(t->d_trans);
+    sr_free_buf(t->d_batch);
+    sr_free_buf(t->d_trans);
     if (t->h_err) (void)hipHostFree(t->h_err);
     for (int k = 0; k < kStage; ++k) {
         if (t->h_stage[k]) (void)hipHostFree(t->h_stage[k]);
@@ -303,8 +303,8 @@ int sr_train_step_aug(sr_train* t, const sr_train_crop* items, const uint8_t* me
     int rc = begin_step(t, n, crop_h, crop_w);
     if (rc != SR_OK) return rc;
     const size_t batch_bytes = (size_t)n * crop_h * crop_w * 3;
-    rc = grow(c, s, &t->d_batch, &t->batch_cap, batch_bytes + 4);
-    if (rc == SR_OK && trans_bytes) rc = grow(c, s, &t->d_trans, &t->trans_cap, trans_bytes);
+    rc = grow(c, s, t->d_batch, batch_bytes + 4);
+    if (rc == SR_OK && trans_bytes) rc = grow(c, s, t->d_trans, trans_bytes);
     if (rc != SR_OK) return rc;
     sr_train_crop_args a;
     a.n = n; a.crop_h = crop_h; a.crop_w = crop_w;
@@ -319,7 +319,7 @@ int sr_train_step_aug(sr_train* t, const sr_train_crop* items, const uint8_t* me
         const size_t row = (size_t)it.w * it.in_channels, bytes = (size_t)(r1 - r0) * row;
         if (bytes) memcpy((char*)t->h_stage[k] + off, it.px + (size_t)r0 * row, bytes);
         // the staged rows as an image of r1 - r0 rows: the crop's rows outside them are outside the source image too
-        a.d[i] = {(const uint8_t*)t->d_trans + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0, member(i)};
+        a.d[i] = {(const uint8_t*)t->d_trans.p + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0, member(i)};
         off += sr_round256(bytes);
     }
     rc = upload_stage(t, trans_bytes, k);
@@ -330,7 +330,7 @@ int sr_train_step_aug(sr_train* t, const sr_train_crop* items, const uint8_t* me
         const sr_train::Img& im = t->images[(size_t)it.image];
         a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0, member(i)};
     }
-    HIPCHK(c, sr_launch_train_crop(a, (uint32_t*)t->d_batch, s));
+    HIPCHK(c, sr_launch_train_crop(a, (uint32_t*)t->d_batch.p, s));
     return finish_step(t, n, crop_h, crop_w, nullptr);
 }
 
@@ -402,8 +402,8 @@ int sr_train_step_pairs_aug(sr_train* t, const sr_train_pair_crop* items, const 
     int rc = begin_step(t, n, crop_h, crop_w);
     if (rc != SR_OK) return rc;
     const size_t batch_bytes = (size_t)n * crop_h * crop_w * 3;
-    rc = grow(c, s, &t->d_batch, &t->batch_cap, batch_bytes + 4);
-    if (rc == SR_OK && trans_bytes) rc = grow(c, s, &t->d_trans, &t->trans_cap, trans_bytes);
+    rc = grow(c, s, t->d_batch, batch_bytes + 4);
+    if (rc == SR_OK && trans_bytes) rc = grow(c, s, t->d_trans, trans_bytes);
     float* x = nullptr;
     if (rc == SR_OK) rc = sr_grad_input_buffer(c, n, crop_lh, crop_lw, &x);  // (the stream has drained if this grows the workspace)
     if (rc != SR_OK) return rc;
@@ -425,16 +425,16 @@ int sr_train_step_pairs_aug(sr_train* t, const sr_train_pair_crop* items, const 
         const size_t lrow = (size_t)it.lw * it.lr_channels, lbytes = (size_t)(r1 - r0) * lrow;
         const size_t hrow = (size_t)f * it.lw * it.hr_channels, hbytes = (size_t)(r1 - r0) * f * hrow;
         if (lbytes) memcpy((char*)t->h_stage[k] + off, it.lr_px + (size_t)r0 * lrow, lbytes);
-        const uint8_t* d_lr = (const uint8_t*)t->d_trans + off;
+        const uint8_t* d_lr = (const uint8_t*)t->d_trans.p + off;
         off += sr_round256(lbytes);
         if (hbytes) memcpy((char*)t->h_stage[k] + off, it.hr_px + (size_t)r0 * f * hrow, hbytes);
-        a.d[i] = {d_lr, (const uint8_t*)t->d_trans + off, (uint8_t)it.lr_channels, (uint8_t)it.hr_channels, (uint8_t)member(i), 0, (int)(r1 - r0), it.lw,
+        a.d[i] = {d_lr, (const uint8_t*)t->d_trans.p + off, (uint8_t)it.lr_channels, (uint8_t)it.hr_channels, (uint8_t)member(i), 0, (int)(r1 - r0), it.lw,
                   (int)(it.y0 - r0), it.x0};
         off += sr_round256(hbytes);
     }
     rc = upload_stage(t, trans_bytes, k);
     if (rc != SR_OK) return rc;
-    HIPCHK(c, sr_launch_train_pair_crop(f, a, (uint32_t*)t->d_batch, x, c->d_vtab, s));
+    HIPCHK(c, sr_launch_train_pair_crop(f, a, (uint32_t*)t->d_batch.p, x, c->d_vtab, s));
     sr_lr_input in;
     in.in_place = true;
     return finish_step(t, n, crop_h, crop_w, &in);

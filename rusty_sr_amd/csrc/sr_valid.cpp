@@ -53,33 +53,31 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
     const int grid = sr_valid_loss_grid(HC, WC);
     const size_t lr_bytes = (size_t)OH * OW * 3 * sizeof(float), out_bytes = (size_t)HC * WC * 3 * sizeof(float);
     int rc = ensure_table(c);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vlr, &c->vlr_cap, lr_bytes);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vout, &c->vout_cap, out_bytes);
-    if (rc == SR_OK) rc = sr_ensure_buf(c, &c->d_vpart, &c->vpart_cap, (size_t)(grid + 1) * sizeof(double));
+    if (rc == SR_OK) rc = sr_ensure_bufs(c, {{&c->d_vlr, lr_bytes}, {&c->d_vout, out_bytes}, {&c->d_vpart, (size_t)(grid + 1) * sizeof(double)}});
     if (rc == SR_OK && metrics) rc = sr_metrics_reserve(c, HC, WC, metrics->shave);
     c->vnode_h = c->vnode_w = 0;
-    if (rc != SR_OK) {  // a job that does not fit must not keep what of it was allocated (it may be most of the device)
-        sr_free_buf(c->d_vlr, c->vlr_cap);
-        sr_free_buf(c->d_vout, c->vout_cap);
+    if (rc != SR_OK) {  // also when it was the scores' partials that did not fit: the job keeps nothing of its two large buffers
+        sr_free_buf(c->d_vlr);
+        sr_free_buf(c->d_vout);
         return rc;
     }
-    if (!d_result) d_result = (double*)c->d_vpart + grid;
-    if (lr) HIPCHK(c, sr_queue_lr_input(*lr, (long)OH * OW, (float*)c->d_vlr, c->d_vtab, s));
-    else HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, OH, OW, (float*)c->d_vlr, c->d_vtab + 256, s));  // (SrgbToLinear of the bytes)
-    if (members) rc = sr_ensemble_queue(c, c->d_vlr, false, 3, OH, OW, c->d_vout, false, members, s);
-    else rc = sr_run_stack_auto(c, c->d_vlr, false, 3, 1, OH, OW, 0, 0, c->d_vout, false, s);
+    if (!d_result) d_result = (double*)c->d_vpart.p + grid;
+    if (lr) HIPCHK(c, sr_queue_lr_input(*lr, (long)OH * OW, (float*)c->d_vlr.p, c->d_vtab, s));
+    else HIPCHK(c, sr_launch_valid_pool(f, d_hr, hr_u8, ch, w, OH, OW, (float*)c->d_vlr.p, c->d_vtab + 256, s));  // (SrgbToLinear of the bytes)
+    if (members) rc = sr_ensemble_queue(c, c->d_vlr.p, false, 3, OH, OW, c->d_vout.p, false, members, s);
+    else rc = sr_run_stack_auto(c, c->d_vlr.p, false, 3, 1, OH, OW, 0, 0, c->d_vout.p, false, s);
     if (rc != SR_OK) return rc;
-    HIPCHK(c, sr_launch_valid_loss((const float*)c->d_vout, d_hr, hr_u8, ch, linear, w, HC, WC, c->d_vtab, (double*)c->d_vpart, d_result, s));
+    HIPCHK(c, sr_launch_valid_loss((const float*)c->d_vout.p, d_hr, hr_u8, ch, linear, w, HC, WC, c->d_vtab, (double*)c->d_vpart.p, d_result, s));
     c->vnode_h = OH; c->vnode_w = OW;
-    if (metrics) return sr_metrics_queue(c, c->d_vout, false, 3, WC, (const uint8_t*)d_hr, ch, w, HC, WC, *metrics, s);
+    if (metrics) return sr_metrics_queue(c, c->d_vout.p, false, 3, WC, (const uint8_t*)d_hr, ch, w, HC, WC, *metrics, s);
     return SR_OK;
 }
 
-// The host-pointer calls: upload, run, download 8 bytes, on the context's own stream; synchronous.  In the split-half mode a value that
-// left its domain makes the whole call run again in exact f32, as the host-pointer upscale calls do (include/srhip.h sr_set_precision).
+// The host-pointer calls: upload, run, download 8 bytes (and the scores' 16), as one sr_host_call.
 // lr: nullptr = the pooled form, h x w the HR size; else (pair) h x w is the LR size and lr_ch its channel count.
 // ensemble: `members` is a self-ensemble's mask (checked here), else it is not looked at.  metrics (with its shave as the caller gave
 // it; u8 only): the scores of the same run of the network, beside the loss.
+// sr_last_timing: total = the whole call on the device (upload, pool, network, loss, download); stages: the network's.
 int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool hr_u8, int ch, int h, int w, int linear, double* err_sum,
                     size_t* n_elems, bool pair, bool ensemble = false, unsigned members = 0, sr_metrics* metrics = nullptr, int shave = 0) {
     sr_plan_clear(c);
@@ -90,59 +88,55 @@ int validation_host(sr_ctx* c, const void* lr, int lr_ch, const void* hr, bool h
     if (rc != SR_OK) return rc;
     if (!ensemble) members = 0;
     if (!err_sum || !n_elems) return SR_E_INVALID;
-    const int lh = h, lw = w;
     const size_t lr_bytes = pair ? (size_t)h * w * (hr_u8 ? (size_t)lr_ch : 3 * sizeof(float)) : 0;
     if (pair) { h *= c->factor; w *= c->factor; }
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
-    // a fault an earlier unchecked *_dev call left is that call's to report (sr_check_domain), not a reason to recompute this one
-    if (c->h_domain && *(volatile int*)c->h_domain) { c->dev_fault = true; *(volatile int*)c->h_domain = 0; }
     const size_t hr_bytes = (size_t)h * w * (hr_u8 ? (size_t)ch : 3 * sizeof(float));
-    rc = sr_ensure_buf(c, &c->d_vhr, &c->vhr_cap, pair ? sr_round256(hr_bytes) + lr_bytes : hr_bytes);
-    if (rc != SR_OK) {
-        sr_free_buf(c->d_vhr, c->vhr_cap);
-        return rc;
-    }
-    hipStream_t s = c->stream;
-    const int f = c->factor;
-    const int grid = sr_valid_loss_grid(f * (h / f), f * (w / f));
-    bool profiled = false;
-    if (c->profiling) profiled = hipEventRecord(c->ev[6], s) == hipSuccess;
-    HIPCHK(c, hipMemcpyAsync(c->d_vhr, hr, hr_bytes, hipMemcpyHostToDevice, s));
-    sr_lr_input in;
-    in.d_lr = (char*)c->d_vhr + sr_round256(hr_bytes); in.u8 = hr_u8; in.ch = lr_ch;
-    if (pair) HIPCHK(c, hipMemcpyAsync((void*)in.d_lr, lr, lr_bytes, hipMemcpyHostToDevice, s));
-    rc = run_validation(c, c->d_vhr, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr, members, metrics ? &rq : nullptr);
+    const int f = c->factor, HC = f * (h / f), WC = f * (w / f);
+    const auto d_lr = [&] { return (char*)c->d_vhr.p + sr_round256(hr_bytes); };  // a pair's LR image, behind the HR image
     double sum = 0.0;
     unsigned char scores[16] = {0};
-    const int HC = f * (h / f), WC = f * (w / f);
-    hipError_t e1 = rc == SR_OK ? hipMemcpyAsync(&sum, (double*)c->d_vpart + grid, sizeof sum, hipMemcpyDeviceToHost, s) : hipSuccess;
-    if (rc == SR_OK && metrics && e1 == hipSuccess)
-        e1 = hipMemcpyAsync(scores, sr_metrics_slot(c, HC, WC, rq.shave), sizeof scores, hipMemcpyDeviceToHost, s);
-    if (profiled && e1 == hipSuccess && rc == SR_OK) profiled = hipEventRecord(c->ev[7], s) == hipSuccess;
-    const hipError_t e2 = hipStreamSynchronize(s);  // also on failure: nothing of the call may still run once it has returned
+    rc = sr_host_call(
+        c, true, SR_TIMES_TOTAL, {{&c->d_vhr, pair ? sr_round256(hr_bytes) + lr_bytes : hr_bytes}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(c->d_vhr.p, hr, hr_bytes, hipMemcpyHostToDevice, s));
+            if (pair) HIPCHK(c, hipMemcpyAsync(d_lr(), lr, lr_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) {
+            sr_lr_input in;
+            in.d_lr = d_lr(); in.u8 = hr_u8; in.ch = lr_ch;
+            return run_validation(c, c->d_vhr.p, hr_u8, ch, h, w, linear != 0, nullptr, s, pair ? &in : nullptr, members, metrics ? &rq : nullptr);
+        },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(&sum, (double*)c->d_vpart.p + sr_valid_loss_grid(HC, WC), sizeof sum, hipMemcpyDeviceToHost, s));
+            if (metrics) HIPCHK(c, hipMemcpyAsync(scores, sr_metrics_slot(c, HC, WC, rq.shave), sizeof scores, hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
     if (rc != SR_OK) return rc;
-    HIPCHK(c, e1);
-    HIPCHK(c, e2);
-    if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
-        *(volatile int*)c->h_domain = 0;
-        (void)sr_set_precision(c, SR_PRECISION_F32);
-        rc = validation_host(c, lr, lr_ch, hr, hr_u8, ch, pair ? lh : h, pair ? lw : w, linear, err_sum, n_elems, pair, ensemble, members, metrics,
-                             shave);
-        (void)sr_set_precision(c, SR_PRECISION_SPLIT_F16);
-        ++c->domain_fallbacks;
-        return rc;
-    }
-    if (profiled) {  // sr_last_timing: total = the whole call on the device (upload, pool, network, loss, download); stages: the network's
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, c->ev[6], c->ev[7]) == hipSuccess) c->total_ms = ms; else (void)hipGetLastError();
-    }
     *err_sum = sum;
     *n_elems = sr_loss_elems(f, 1, h, w);
     if (metrics) sr_metrics_fill(metrics, scores, HC, WC, rq.shave);
     return SR_OK;
+}
+
+// The device entry points: the arguments checked, then run_validation on the caller's stream.  pair: h x w is the LR size (else the HR
+// size, and d_lr is not looked at).  with_metrics: the scores too, at d_result16 (shave as the caller gave it).
+int validation_dev(sr_ctx* c, bool pair, const uint8_t* d_lr, int lr_ch, const uint8_t* d_hr, int ch, int h, int w, int linear, double* d_err_sum,
+                   bool with_metrics, int shave, void* d_result16, void* stream) {
+    sr_plan_clear(c);
+    int rc = pair ? check_pair_args(c, d_lr, true, lr_ch, d_hr, ch, h, w) : check_args(c, d_hr, true, ch, h, w);
+    sr_metrics_request rq;
+    if (rc == SR_OK && with_metrics) rc = sr_metrics_shave(c, shave, &rq.shave);
+    if (rc != SR_OK) return rc;
+    if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
+    if (with_metrics && (!d_result16 || !sr_dword_aligned(d_result16))) return SR_E_INVALID;
+    rq.d_result16 = d_result16;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    sr_lr_input in;
+    in.d_lr = d_lr; in.u8 = true; in.ch = lr_ch;
+    if (pair) { h *= c->factor; w *= c->factor; }
+    return run_validation(c, d_hr, true, ch, h, w, linear != 0, d_err_sum, (hipStream_t)stream, pair ? &in : nullptr, 0, with_metrics ? &rq : nullptr);
 }
 
 }  // namespace
@@ -152,10 +146,7 @@ int sr_valid_ensure_table(sr_ctx* c) {
 }
 
 void sr_valid_release(sr_ctx* c) {
-    sr_free_buf(c->d_vhr, c->vhr_cap);
-    sr_free_buf(c->d_vlr, c->vlr_cap);
-    sr_free_buf(c->d_vout, c->vout_cap);
-    sr_free_buf(c->d_vpart, c->vpart_cap);
+    for (sr_buf* b : {&c->d_vhr, &c->d_vlr, &c->d_vout, &c->d_vpart}) sr_free_buf(*b);
     if (c->d_vtab) (void)hipFree(c->d_vtab);
     c->d_vtab = nullptr;
     c->vnode_h = c->vnode_w = 0;
@@ -172,13 +163,7 @@ int sr_validation_error_f32(sr_ctx* c, const float* hr, int h, int w, int linear
 }
 
 int sr_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss, double* d_err_sum, void* stream) {
-    sr_plan_clear(c);
-    const int rc = check_args(c, d_hr, true, in_channels, h, w);
-    if (rc != SR_OK) return rc;
-    if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    return run_validation(c, d_hr, true, in_channels, h, w, linear_loss != 0, d_err_sum, (hipStream_t)stream, nullptr);
+    return validation_dev(c, false, nullptr, 3, d_hr, in_channels, h, w, linear_loss, d_err_sum, false, 0, nullptr, stream);
 }
 
 int sr_pair_validation_error_rgba8(sr_ctx* c, const uint8_t* lr, int lr_channels, const uint8_t* hr, int hr_channels, int lh, int lw,
@@ -192,15 +177,7 @@ int sr_pair_validation_error_f32(sr_ctx* c, const float* lr, const float* hr, in
 
 int sr_pair_validation_error_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
                                        int linear_loss, double* d_err_sum, void* stream) {
-    sr_plan_clear(c);
-    const int rc = check_pair_args(c, d_lr, true, lr_channels, d_hr, hr_channels, lh, lw);
-    if (rc != SR_OK) return rc;
-    if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    sr_lr_input in;
-    in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
-    return run_validation(c, d_hr, true, hr_channels, c->factor * lh, c->factor * lw, linear_loss != 0, d_err_sum, (hipStream_t)stream, &in);
+    return validation_dev(c, true, d_lr, lr_channels, d_hr, hr_channels, lh, lw, linear_loss, d_err_sum, false, 0, nullptr, stream);
 }
 
 int sr_pool_validation_error_ensemble_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int linear_loss, unsigned members,
@@ -228,32 +205,12 @@ int sr_pair_validation_metrics_rgba8(sr_ctx* c, const uint8_t* lr, int lr_channe
 
 int sr_pool_validation_metrics_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h, int w, int linear_loss, int shave, double* d_err_sum,
                                     void* d_result16, void* stream) {
-    sr_plan_clear(c);
-    int rc = check_args(c, d_hr, true, in_channels, h, w);
-    sr_metrics_request rq;
-    if (rc == SR_OK) rc = sr_metrics_shave(c, shave, &rq.shave);
-    if (rc != SR_OK) return rc;
-    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !d_result16 || !sr_dword_aligned(d_result16)) return SR_E_INVALID;
-    rq.d_result16 = d_result16;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    return run_validation(c, d_hr, true, in_channels, h, w, linear_loss != 0, d_err_sum, (hipStream_t)stream, nullptr, 0, &rq);
+    return validation_dev(c, false, nullptr, 3, d_hr, in_channels, h, w, linear_loss, d_err_sum, true, shave, d_result16, stream);
 }
 
 int sr_pair_validation_metrics_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int lr_channels, const uint8_t* d_hr, int hr_channels, int lh, int lw,
                                          int linear_loss, int shave, double* d_err_sum, void* d_result16, void* stream) {
-    sr_plan_clear(c);
-    int rc = check_pair_args(c, d_lr, true, lr_channels, d_hr, hr_channels, lh, lw);
-    sr_metrics_request rq;
-    if (rc == SR_OK) rc = sr_metrics_shave(c, shave, &rq.shave);
-    if (rc != SR_OK) return rc;
-    if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !d_result16 || !sr_dword_aligned(d_result16)) return SR_E_INVALID;
-    rq.d_result16 = d_result16;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    sr_lr_input in;
-    in.d_lr = d_lr; in.u8 = true; in.ch = lr_channels;
-    return run_validation(c, d_hr, true, hr_channels, c->factor * lh, c->factor * lw, linear_loss != 0, d_err_sum, (hipStream_t)stream, &in, 0, &rq);
+    return validation_dev(c, true, d_lr, lr_channels, d_hr, hr_channels, lh, lw, linear_loss, d_err_sum, true, shave, d_result16, stream);
 }
 
 int sr_read_validation_nodes(sr_ctx* c, float* lr_out, size_t cap_lr, float* out_out, size_t cap_out) {
@@ -263,8 +220,8 @@ int sr_read_validation_nodes(sr_ctx* c, float* lr_out, size_t cap_lr, float* out
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (lr_out) HIPCHK(c, hipMemcpy(lr_out, c->d_vlr, n_lr * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_out) HIPCHK(c, hipMemcpy(out_out, c->d_vout, n_out * sizeof(float), hipMemcpyDeviceToHost));
+    if (lr_out) HIPCHK(c, hipMemcpy(lr_out, c->d_vlr.p, n_lr * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_out) HIPCHK(c, hipMemcpy(out_out, c->d_vout.p, n_out * sizeof(float), hipMemcpyDeviceToHost));
     return SR_OK;
 }
 
