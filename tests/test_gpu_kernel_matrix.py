@@ -14,6 +14,7 @@ import pytest
 
 import oracle
 from conftest import synth_u8
+from param_families import bundled_scale as _synthetic_params   # (the one generator of bundled-scale weights)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,20 +30,6 @@ FORMS = {  # the switches that force each cell (sr_set_experiment); the mixed ce
     "pipe/8+4": {"tail": "1"},
 }
 SWITCHES = ("pipe", "th", "tail", "bw", "fork", "forktune")
-
-
-def _synthetic_params(factor, seed):
-    """No 2x / 4x weights ship with the reference: seeded synthetic parameters with the bundled
-    weights' scales (conv std from imagenet.rsr, small biases, BeLU betas in [-0.5, 1.5])."""
-    rng = np.random.default_rng(seed)
-    n = oracle.num_params(factor)
-    p = (rng.standard_normal(n) * 0.03).astype(np.float32)
-    e = 3 * factor * factor
-    p[2400:2464 + e + 96] = (rng.standard_normal(64 + e + 96) * 0.05).astype(np.float32)       # biases
-    p[2432:2464] = rng.uniform(-0.5, 1.5, 32).astype(np.float32)                                 # f_activ
-    a0 = 2464 + e + 96
-    p[a0:a0 + 96] = rng.uniform(-0.5, 1.5, 96).astype(np.float32)                                # l1..l3 activ
-    return p
 
 
 def _check_u8(got, v_ref):

@@ -10,24 +10,13 @@ import pytest
 
 import oracle
 from conftest import GOLDEN, load_png, synth_u8
+from param_families import bundled_scale as synthetic_params   # (the one generator of bundled-scale weights)
 
 pytestmark = pytest.mark.gpu
 
 POOL_TOL = 2e-6   # the pool's stated error (sr_valid.hip): hardware log2 / exp2 transfer functions, f32 sums
 GOLDENS = ("cartoon_rsa.png", "butterfly_rs.png", "logo_nn.png")
 F32_0_04045 = np.float32(0.04045)
-
-
-def synthetic_params(factor, seed):
-    """Seeded weights of sr_net(factor) at the bundled weights' scales (as tests/test_gpu_kernel_matrix.py makes them)."""
-    rng = np.random.default_rng(seed)
-    p = (rng.standard_normal(oracle.num_params(factor)) * 0.03).astype(np.float32)
-    e = 3 * factor * factor
-    p[2400:2464 + e + 96] = (rng.standard_normal(64 + e + 96) * 0.05).astype(np.float32)
-    p[2432:2464] = rng.uniform(-0.5, 1.5, 32).astype(np.float32)
-    a0 = 2464 + e + 96
-    p[a0:a0 + 96] = rng.uniform(-0.5, 1.5, 96).astype(np.float32)
-    return p
 
 
 # ---- the f64 restatement -----------------------------------------------------------------------------------------------------

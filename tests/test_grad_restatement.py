@@ -12,6 +12,7 @@ import torch
 import grad_ref
 import oracle
 from conftest import ROOT
+from param_families import bundled_scale as synthetic_params   # (the one generator of bundled-scale weights)
 
 NEW = ["sr_adam_step_dev", "sr_backprop_f32", "sr_backprop_rgba8", "sr_backprop_rgba8_dev"]
 
@@ -19,18 +20,6 @@ NEW = ["sr_adam_step_dev", "sr_backprop_f32", "sr_backprop_rgba8", "sr_backprop_
 def _read(*p):
     with open(os.path.join(*p)) as f:
         return f.read()
-
-
-def synthetic_params(factor, seed):
-    """Seeded weights of sr_net(factor) at the bundled weights' scales (as the GPU tests make them)."""
-    rng = np.random.default_rng(seed)
-    p = (rng.standard_normal(oracle.num_params(factor)) * 0.03).astype(np.float32)
-    e = 3 * factor * factor
-    p[2400:2464 + e + 96] = (rng.standard_normal(64 + e + 96) * 0.05).astype(np.float32)
-    p[2432:2464] = rng.uniform(-0.5, 1.5, 32).astype(np.float32)
-    a0 = 2464 + e + 96
-    p[a0:a0 + 96] = rng.uniform(-0.5, 1.5, 96).astype(np.float32)
-    return p
 
 
 def test_segments_are_the_oracles():
