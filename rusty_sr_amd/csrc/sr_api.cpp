@@ -184,14 +184,17 @@ void pack_conv0_split(std::vector<float>& dst, const float* w) {
 // SURVEY.md 8(a) G1): negative -> inputs (i-1, i) with weights (1-t, t), t = (2p+1+f)/(2f);
 // otherwise -> inputs (i, i+1) with weights (1-t, t), t = (2p+1-f)/(2f).  Same f32 constants
 // as the oracle; the 2-D weight is their f32 product.
-void pack_lin(std::vector<float>& dst, int f) {
-    float w1[4][3] = {};
+void lin_taps(int f, float w1[4][3]) {
     for (int p = 0; p < f; ++p) {
         const int nn = 2 * p + 1 - f;
         const float t = (float)(nn < 0 ? nn + 2 * f : nn) / (float)(2 * f);
         if (nn < 0) { w1[p][0] = 1.0f - t; w1[p][1] = t; }
         else { w1[p][1] = 1.0f - t; w1[p][2] = t; }
     }
+}
+void pack_lin(std::vector<float>& dst, int f) {
+    float w1[4][3] = {};
+    lin_taps(f, w1);
     const int ntn = expand_tiles(f);
     const size_t base = dst.size();
     dst.resize(base + (size_t)9 * ntn * 128, 0.0f);
@@ -211,12 +214,7 @@ void pack_lin(std::vector<float>& dst, int f) {
 // [b 3][N-tile][h 2][lane 32][e 8] halves, slot 16 b + 8 h + e.
 void pack_lin_split(std::vector<float>& dst, int f) {
     float w1[4][3] = {};
-    for (int p = 0; p < f; ++p) {
-        const int nn = 2 * p + 1 - f;
-        const float t = (float)(nn < 0 ? nn + 2 * f : nn) / (float)(2 * f);
-        if (nn < 0) { w1[p][0] = 1.0f - t; w1[p][1] = t; }
-        else { w1[p][1] = 1.0f - t; w1[p][2] = t; }
-    }
+    lin_taps(f, w1);
     const int ntn = expand_tiles(f);
     const float scale = 4.0f * f * f;
     const size_t base = dst.size();
@@ -710,11 +708,9 @@ int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_
                  const sr_host_phase& work, const sr_host_phase& download) {
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = sr_ensure_streams(c, false);
-    if (rc != SR_OK) return rc;
+    SRCHK(sr_ensure_streams(c, false));
     if (network) sr_domain_set_aside(c);
-    rc = sr_ensure_bufs(c, staging);
-    if (rc != SR_OK) return rc;
+    SRCHK(sr_ensure_bufs(c, staging));
     const bool prof = c->profiling && times != SR_TIMES_NONE, parts = prof && times == SR_TIMES_PARTS;
     while (prof && c->pool.size() < 4) {
         hipEvent_t e = nullptr;
@@ -742,7 +738,7 @@ int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_
         HIPCHK(c, drained);
         return SR_OK;
     };
-    rc = run();
+    int rc = run();
     if (rc == SR_OK && network && sr_domain_tripped(c)) {
         // Some value of the call left the split-half mode's domain (the stream has drained: the flag is final).  A synchronous call never
         // hands out clamped pixels: the whole job is computed again in exact f32 -- graph.forward takes any f32 (main.rs:171).
@@ -775,114 +771,46 @@ struct StackJob {
     void* d_out = nullptr;
     bool img_u8 = false, out_u8 = false;
     int img_ch = 3, n = 1, H = 0, W = 0, top = 0, bot = 0, tiles_x = 0;
-    bool forked = false;  // one of the two bands of sr_run_stack_auto: no 4-row tail (see prepare)
+    bool forked = false;  // one of the two bands of sr_run_stack_auto: no 4-row tail (sr_tile_plan)
     bool layers = false;  // every stage computes rows [top, bot) only: the rows beyond come from the neighbours' maps (sr_band_pass)
     // rows [0, late_top) and [H - late_bot, H) of the image arrive with gate->ready (sr_internal.h sr_halo_gate); mark: record gate->mark around the wait
     const sr_halo_gate* gate = nullptr;
     int late_top = 0, late_bot = 0;
     bool mark = false;
     hipStream_t s = nullptr;
-    struct Launch { int y0, y1, ty8, ty4, th, grid; bool pipe; } L[5];
+    sr_launch_plan L[5];
     float* feat[4] = {nullptr, nullptr, nullptr, nullptr};
     int prepare();
     int launch(int st) const;
 };
 
 int StackJob::prepare() {
-    static const int margin[5] = {5, 3, 2, 1, 0};
     tiles_x = (W + 31) / 32;
-    const int rc = ensure_features(c, *ws, n, H, W, tiles_x, s);
-    if (rc != SR_OK) return rc;
-    const int cus = c->cus > 0 ? c->cus : 256;
-    const int resident = 2 * cus;  // workgroups of a stage kernel that fit the chip at once (2 per CU: 76-78 KB of LDS each)
+    SRCHK(ensure_features(c, *ws, n, H, W, tiles_x, s));
     // pointers to pixel (0,0) of image 0 inside the zero-bordered maps
     // (row-planar maps of the split-half mode: pixel (0,0) of channel group 0 -- kFeatPad rows down, kFeatPad 16-byte cells in)
     const bool planar = c->precision == SR_PRECISION_SPLIT_F16;
     for (int k = 0; k < 4; ++k) feat[k] = ws->d_feat[k] + (planar ? (size_t)kFeatPad * ws->pitch * 32 + kFeatPad * 4 : ((size_t)kFeatPad * ws->pitch + kFeatPad) * 32);
     // ---- plan every launch first: conv0 (the call's first launch) sets the tile-queue heads of the four stage kernels
-    for (int st = 0; st < 5; ++st) {
-        Launch& l = L[st];
-        l.y0 = layers ? top : std::max(0, top - margin[st]);
-        l.y1 = layers ? bot : std::min(H, bot + margin[st]);
-        const int rows = l.y1 - l.y0;
-        // Tile classes of the launch (sr_kernels.h TileGrid): `ty8` rows of 8-row tiles, then `ty4` rows of 4-row tiles.
-        // Measured on MI355X (profiles/r3_tileplans_*, r3_queuefix_*; `rounds` = 8-row tiles per resident workgroup):
-        //  * exact f32, a SMALL launch (rounds < 2): 4-row tiles on the first form of the stage kernel -- one tile per
-        //    workgroup, no queue (256x256: 0.157 ms against 0.176-0.178 on either tile class of the pipe form);
-        //  * split-half mode, small launch: the pipe form all the same (256x256: 0.091 ms against 0.24), 8-row tiles while
-        //    they still give every CU one, else 4-row tiles;
-        //  * otherwise the pipe form on 8-row tiles, and in exact f32 the LAST tiles of every XCD's queue are 4-row tiles, one per
-        //    resident workgroup (sr_set_experiment "tail"): a persistent launch ends when its slowest workgroup does, and with
-        //    half-size last tiles (and stealing) the workgroups finish closer together -- also when the tile count is an exact
-        //    multiple of the workgroups (1024x768, 6.00 rounds: -4.9 %).  Measured, interleaved A/B (profiles/r3_tail_ab.txt):
-        //    800x600 -4.7 %, 1000x600 -4.2 %, 1280x720 -2.4 %, 1920x1200 -1.4 %, the 8- / 4- / 2-way band of 3840x2160 -2.1 /
-        //    -0.3 / -0.4 %, 2560x1440 -0.4 %, 3840x2160 0; but 512x512 (2.0 rounds) +5...9 % and 640x480 (2.3) +2 %: the 4-row
-        //    tile body is code the launch would otherwise never touch (~30 us of cold instruction fetch per call), so no tail below
-        //    3 rounds (round 3 also excluded launches above 14 rounds with a last round more than 70 % full -- 1920x1080, 15.8: 0 then; see below).  The
-        //    split-half mode pays 17 % per 4-row tile (its B operands are re-read per tile row) and keeps 8-row tiles.
-        //  conv0 and the first form run one class.
-        const long tiles8 = (long)n * tiles_x * ((rows + 7) / 8);
-        // (the last stage of factor 4 in the split-half mode exists with 4-row tiles only: two N-tiles of accumulators, sr_kernels.hip kBigTiles)
-        // (the exact mode's stages 1 and 2 in their Winograd form: a 4-row tile half-fills the pair dimension, 7 MFMAs per 16 pixels where the
-        // direct form issues 5, so a small launch keeps 8-row tiles instead of switching to 4-row ones -- 256x256 stage 1 0.0488 ms with 4-row
-        // tiles, 0.0314 with 8-row ones, direct 0.0368; 360x640 0.1515 / 0.0853 / 0.1080: profiles/r7_ab_wino_stage1.txt; stage 2 256x256
-        // 0.0658 / 0.0402 / 0.0449, 360x640 0.2188 / 0.1242 / 0.1434: profiles/r8_ab_wino_stage2.txt.  Tile plans change no bit.)
-        const bool wino8 = c->precision == SR_PRECISION_F32 && (st == 1 || st == 2) && st <= c->wino;
-        const int forced = (st == 4 && c->factor == 4 && c->precision == SR_PRECISION_SPLIT_F16) ? 4 : c->env_th[st];
-        const bool small_launch = tiles8 < 2L * resident;
-        const bool split = c->precision == SR_PRECISION_SPLIT_F16;
-        // (round 4: with the scalar overheads of the pipe form gone it also wins where every workgroup has exactly ONE 4-row tile and the
-        // node has several sources -- their tiles arrive under the previous source's taps instead of between them: 256x256 stages 2 / 3
-        // 40.5 / 49.0 -> 39.1 / 47.2 us; with more than one round of small tiles the first form still leads, 384x384 0.356 against 0.382 ms:
-        // profiles/r4_ab_small_pipe.txt)
-        const bool one_small_round = small_launch && (long)n * tiles_x * ((rows + 3) / 4) <= resident;
-        l.pipe = st > 0 && c->env_pipe != 0 && (c->env_pipe == 2 || !small_launch || split || (st >= 2 && one_small_round));
-        l.ty8 = (rows + 7) / 8; l.ty4 = 0;
-        if (forced == 4 || (!forced && small_launch && !wino8 && (!split || tiles8 < cus))) {
-            l.ty8 = 0; l.ty4 = (rows + 3) / 4;
-        } else if (!forced && l.pipe && !small_launch) {
-            const double rounds = (double)tiles8 / resident;
-            float tail = c->env_tail;
-            // (round 4, after the matrix stream lost its scalar overheads and 4-row tiles became relatively cheaper -- interleaved A/B,
-            // profiles/r4_fork_tail.jsonl: the tail now also pays where round 3 excluded it, above 14 rounds with a nearly full last round
-            // (1920x1080 undivided: 4.066 -> 4.052 ms); but NOT in the two bands of a forked call, whose launches run side by side and
-            // end staggered anyway: 1920x1080 4.048 -> 4.018, 1600x900 2.853 -> 2.825, 1280x720 1.841 -> 1.834 ms without it)
-            // (round 6: not in the exact mode's last stage either -- its 8-row tiles run on 4x4x1 MFMAs with 28 output columns, its 4-row
-            // tiles still on 32x32x2 with 32, code the launch would otherwise never touch: 0.7775 -> 0.7695 ms at 1080p, profiles/r6_ab_quad.txt)
-            // (nor in stage 2's Winograd form, whose 4-row tiles cost as many MFMAs as 8-row ones for the 5x5 source: 1080p stage 2 0.856 ms
-            // with the tail, 0.837 without, profiles/r8_ab_wino_stage2.txt)
-            if (tail < 0.0f) tail = (!split && rounds >= 3.0 && !forked && st != 4 && !(st == 2 && wino8)) ? 1.0f : 0.0f;
-            if (tail > 0.0f) {
-                const long per_row = (long)n * tiles_x;
-                const int want = (int)((tail * resident + per_row - 1) / per_row);  // tile rows of small tiles
-                l.ty8 = std::max(0, (rows - 4 * want) / 8);
-                l.ty4 = std::max(0, (rows - 8 * l.ty8 + 3) / 4);
-            }
-        }
-        if (!forced && l.pipe && !small_launch && !split && l.ty4 == 0 && (double)tiles8 / resident >= 3.0 && rows % 8 >= 1 && rows % 8 <= 4) {
-            // the last 1-4 rows as ONE row of 4-row tiles instead of a mostly empty row of 8-row tiles (a band of a forked call, an image
-            // height that is not a multiple of 8): half a tile row of matrix work saved
-            l.ty8 = rows / 8; l.ty4 = 1;
-        }
-        if (l.ty8 > 0 && l.ty4 > 0 && (long)n * tiles_x * (l.ty8 + l.ty4) <= resident) {
-            // (cannot happen with the rules above -- a tail is only added to launches of >= 2 rounds -- but a launch with a workgroup
-            // per tile hands out tiles by workgroup number alone, which is only a bijection for ONE tile class)
-            l.ty8 = 0; l.ty4 = (rows + 3) / 4;
-        }
-        l.th = l.ty8 > 0 ? 8 : 4;  // the one class of conv0 / the first form
-        if (!l.pipe && l.ty8 > 0) { l.ty8 = (rows + 7) / 8; l.ty4 = 0; }
-        const int ntiles = n * tiles_x * (l.ty8 + l.ty4);
-        // the pipe form is persistent: one workgroup per resident slot, tiles from the queue; the first form one per tile
-        l.grid = l.pipe ? std::min(ntiles, resident) : ntiles;
-    }
+    sr_tile_plan(*c, n, H, W, top, bot, forked, layers, L);
     return SR_OK;
 }
 
+// A job over rows [top, bot) of n images of H x W, on stream s with workspace `slot`; gate: all of it behind that gate, the wait marked
+StackJob stack_job(sr_ctx* c, int slot, const void* d_img, bool img_u8, int img_ch, int n, int H, int W, int top, int bot, void* d_out, bool out_u8,
+                   hipStream_t s, const sr_halo_gate* gate = nullptr) {
+    StackJob job;
+    job.c = c; job.ws = &c->ws[slot]; job.d_img = d_img; job.d_out = d_out; job.img_u8 = img_u8; job.out_u8 = out_u8;
+    job.img_ch = img_ch; job.n = n; job.H = H; job.W = W; job.top = top; job.bot = bot; job.s = s;
+    if (gate) { job.gate = gate; job.late_top = gate->top; job.late_bot = gate->bot; job.mark = true; }
+    return job;
+}
+
 int StackJob::launch(int st) const {
-    const int cus = c->cus > 0 ? c->cus : 256;
+    const int cus = sr_plan_cus(*c);
     const float* P = c->d_params;
     const int bw = c->env_bw >= 0 ? c->env_bw : kAutoBlockWidth;
-    const Launch& l = L[st];
+    const sr_launch_plan& l = L[st];
     const int y0 = l.y0, y1 = l.y1;
     {
         char line[160];
@@ -914,14 +842,13 @@ int StackJob::launch(int st) const {
         // Interior first (sr_halo_gate): f row y reads image rows y - 2 .. y + 2; those that touch none of the rows still on their way
         // are launched now, the rest -- at most 2 + the stage's margin rows either side -- behind the wait.
         const int lo = late_top > 0 ? std::max(y0, late_top + 2) : y0, hi = late_bot > 0 ? std::min(y1, H - late_bot - 2) : y1;
-        int rc = lo < hi ? rows(lo, hi) : SR_OK;
-        if (rc != SR_OK) return rc;
+        SRCHK(lo < hi ? rows(lo, hi) : SR_OK);
         if (mark && gate->mark[0]) HIPCHK(c, hipEventRecord(gate->mark[0], s));
         HIPCHK(c, hipStreamWaitEvent(s, gate->ready, 0));
         if (mark && gate->mark[1]) HIPCHK(c, hipEventRecord(gate->mark[1], s));
         if (lo >= hi) return rows(y0, y1);
-        rc = rows(y0, lo);
-        return rc != SR_OK ? rc : rows(hi, y1);
+        SRCHK(rows(y0, lo));
+        return rows(hi, y1);
     }
     StageArgs a{};
     float* f = feat[0]; float* l1 = feat[1]; float* l2 = feat[2]; float* l3 = feat[3];
@@ -955,10 +882,9 @@ int sr_run_stack(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int n, i
                  int halo_bot, void* d_out, bool out_u8, hipStream_t s, int slot, const sr_halo_gate* gate) {
     if (!c || !d_img || !d_out || slot < 0 || slot > 1) return SR_E_INVALID;
     sr_device_guard restore_device;
-    if (n <= 0 || H <= 0 || W <= 0) return SR_E_INVALID;
-    if (img_u8 && img_ch != 3 && img_ch != 4) return SR_E_INVALID;
+    if (c->graph != SR_GRAPH_SR_NET && (halo_top || halo_bot || gate)) return SR_E_INVALID;  // (a parameter-free graph takes no band)
+    SRCHK(sr_check_band_args(img_u8, img_ch, n, H, W, halo_top, halo_bot));
     if (c->graph != SR_GRAPH_SR_NET) {  // bilinear_net / downsample_net: one elementwise kernel
-        if (halo_top || halo_bot || gate) return SR_E_INVALID;
         if (c->graph == SR_GRAPH_DOWNSAMPLE && (H < 3 || W < 3)) return SR_E_INVALID;
         if (img_u8 != out_u8) return SR_E_INVALID;
         HIPCHK(c, hipSetDevice(c->device));
@@ -974,27 +900,19 @@ int sr_run_stack(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int n, i
         c->last_h = H; c->last_w = W;
         return SR_OK;
     }
-    if ((halo_top != 0 && halo_top < SR_HALO) || (halo_bot != 0 && halo_bot < SR_HALO)) return SR_E_HALO;
-    if (halo_top < 0 || halo_bot < 0 || halo_top + halo_bot >= H) return SR_E_INVALID;
-    if ((halo_top || halo_bot) && n != 1) return SR_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     // s == nullptr is HIP's legacy default stream (what torch's default stream is);
     // the context's own non-blocking stream is used only by the host-pointer entry points.
-    StackJob job;
-    job.c = c; job.ws = &c->ws[slot]; job.d_img = d_img; job.d_out = d_out; job.img_u8 = img_u8; job.out_u8 = out_u8;
-    job.img_ch = img_ch; job.n = n; job.H = H; job.W = W; job.top = halo_top; job.bot = H - halo_bot; job.s = s;
-    if (gate) { job.gate = gate; job.late_top = gate->top; job.late_bot = gate->bot; job.mark = true; }
-    int rc = job.prepare();
-    if (rc != SR_OK) return rc;
+    StackJob job = stack_job(c, slot, d_img, img_u8, img_ch, n, H, W, halo_top, H - halo_bot, d_out, out_u8, s, gate);
+    SRCHK(job.prepare());
     const bool prof = c->profiling;
     static const bool trace_stages = [] { const char* e = getenv("SRHIP_TRACE"); return e && atoi(e) >= 2; }();
     if (prof) HIPCHK(c, hipEventRecord(c->ev[0], s));
     for (int st = 0; st < 5; ++st) {
-        rc = job.launch(st);
-        if (rc != SR_OK) return rc;
+        SRCHK(job.launch(st));
         if (prof) HIPCHK(c, hipEventRecord(c->ev[st + 1], s));
         if (trace_stages) {  // SRHIP_TRACE=2: which launch a hang or a fault belongs to
-            const StackJob::Launch& l = job.L[st];
+            const sr_launch_plan& l = job.L[st];
             fprintf(stderr, "[srhip] stage %d launched: rows [%d,%d) th8 x%d th4 x%d grid %d %s ... ", st, l.y0, l.y1, l.ty8, l.ty4, l.grid, l.pipe ? "pipe" : "first");
             const hipError_t e = hipStreamSynchronize(s);
             fprintf(stderr, "%s\n", e == hipSuccess ? "done" : hipGetErrorString(e));
@@ -1023,17 +941,14 @@ int sr_band_pass_begin(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, in
                        hipStream_t s, bool layers, const sr_halo_gate* gate, sr_band_pass** out) {
     if (!c || !d_img || !d_out || !out || c->graph != SR_GRAPH_SR_NET || H <= 0 || W <= 0) return SR_E_INVALID;
     *out = nullptr;
-    if (img_u8 && img_ch != 3 && img_ch != 4) return SR_E_INVALID;
-    if ((halo_top != 0 && halo_top < SR_HALO) || (halo_bot != 0 && halo_bot < SR_HALO)) return SR_E_HALO;
-    if (halo_top < 0 || halo_bot < 0 || halo_top + halo_bot >= H) return SR_E_INVALID;
+    SRCHK(sr_check_band_args(img_u8, img_ch, 1, H, W, halo_top, halo_bot));
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     sr_band_pass* p = new (std::nothrow) sr_band_pass();
     if (!p) return SR_E_NOMEM;
     StackJob& job = p->job;
-    job.c = c; job.ws = &c->ws[0]; job.d_img = d_img; job.d_out = d_out; job.img_u8 = img_u8; job.out_u8 = out_u8;
-    job.img_ch = img_ch; job.n = 1; job.H = H; job.W = W; job.top = halo_top; job.bot = H - halo_bot; job.s = s; job.layers = layers;
-    if (gate) { job.gate = gate; job.late_top = gate->top; job.late_bot = gate->bot; job.mark = true; }
+    job = stack_job(c, 0, d_img, img_u8, img_ch, 1, H, W, halo_top, H - halo_bot, d_out, out_u8, s, gate);
+    job.layers = layers;
     const int rc = job.prepare();
     if (rc != SR_OK) { delete p; return rc; }
     c->band_pending = false;
@@ -1069,66 +984,10 @@ void sr_band_pass_end(sr_band_pass* p) { delete p; }
 // second set of feature maps (each band's are half the size).
 namespace {
 
-// Whether a device call of this shape runs as two bands (the automatic rule or sr_set_experiment("fork")), and the first band's rows.
-// `mode`: c->env_fork (-1: the automatic rule, 0: never, 1: always, > 1: always, that many rows first) -- or the tuner's 0 / 1.
-bool plan_fork(const sr_ctx* c, int mode, bool img_u8, int img_ch, int n, int H, int W, int halo_top, int halo_bot, int* rows_a_out) {
-    const int own = H - halo_top - halo_bot;
-    bool fork = c->graph == SR_GRAPH_SR_NET && n == 1 && !c->profiling && mode != 0 && W > 0 && own >= 4 * SR_HALO &&
-                (!img_u8 || img_ch == 3 || img_ch == 4) &&   // (anything sr_run_stack would refuse is left for it to refuse)
-                halo_top >= 0 && halo_bot >= 0 && (halo_top == 0 || halo_top >= SR_HALO) && (halo_bot == 0 || halo_bot >= SR_HALO);
-    if (fork && mode < 0) {
-        // automatic: where the launches have enough rounds of tiles for two bands to fill the chip each (measured)
-        const int cus = c->cus > 0 ? c->cus : 256;
-        const double rounds = (double)((W + 31) / 32) * ((own + 7) / 8) / (2.0 * cus);
-        // measured, interleaved in one process (scripts/fork_ab.py).  With the bands' launches free of 4-row tails (StackJob::prepare) the fork
-        // wins wherever a band still has a few rounds of tiles, exact f32 (profiles/r4_fork_ab_f32_final_rule.jsonl): 800x600 (3.7 rounds)
-        // -3.8 %, 1280x720 -1.6 %, 1920x1080 -0.8 %, 1920x1200 -0.9 %, 2560x1440 -0.4 %, 3840x2160 -0.1 %, a 276-row band of a 3840-wide
-        // image -0.4 %; 960x540 (4.0 rounds) ties.  The split-half mode (tiles of 14 us) loses 0.6-2.4 % (r4_fork_ab_split.jsonl).
-        fork = c->precision == SR_PRECISION_F32 && rounds >= c->fork_min_rounds && rounds < c->fork_max_rounds;
-    }
-    if (!fork) return false;
-    // The first band's own rows: near the requested share, at the cut (within +-8 rows of it) that wastes the least matrix work in
-    // partly filled tile rows.  Stage s of the first band computes rows_a + margin rows from the band's top, of the second band
-    // own - rows_a + margin rows; a remainder of 1-4 rows costs a row of 4-row tiles (0.52 of an 8-row one), 5-7 rows a full one.
-    int rows_a = mode > 1 ? mode : (int)(own * c->fork_share);
-    rows_a = std::max(2 * SR_HALO, std::min(rows_a, own - 2 * SR_HALO));
-    if (mode <= 1) {
-        static const int margin[5] = {5, 3, 2, 1, 0};
-        static const double weight[5] = {0.0, 25600.0, 34816.0, 44032.0, 28800.0};  // issued MACs per pixel of stages 1-4 (conv0: negligible)
-        const bool fours = c->precision == SR_PRECISION_F32;
-        auto tile_rows = [&](int rows) { const int r = rows % 8; return rows / 8 + (r == 0 ? 0.0 : (r <= 4 && fours) ? 0.52 : 1.0); };
-        double best = 1e300;
-        int best_rows = rows_a;
-        for (int cand = rows_a - 8; cand <= rows_a + 8; ++cand) {
-            if (cand < 2 * SR_HALO || own - cand < 2 * SR_HALO) continue;
-            double cost = 0.0;
-            for (int st = 1; st < 5; ++st) {
-                const int ra = cand + margin[st] + std::min(halo_top, margin[st]), rb = own - cand + margin[st] + std::min(halo_bot, margin[st]);
-                cost += weight[st] * (tile_rows(ra) + tile_rows(rb));
-            }
-            cost += 1e-3 * std::abs(cand - rows_a);  // ties: the cut nearest the requested share
-            if (cost < best) { best = cost; best_rows = cand; }
-        }
-        rows_a = best_rows;
-    }
-    *rows_a_out = rows_a;
-    return true;
-}
-
 // ---- the fork decision measured on the caller's own calls (sr_internal.h ForkTune) ----------------------------------------------
 constexpr int kForkTuneBlock = 4;     // calls per plan: one dropped (the workspace meets a new geometry, first-use allocations), three timed
 constexpr size_t kForkTuneShapes = 8;  // shapes remembered per context
-constexpr double kForkTuneMinRounds = 0.55, kForkTuneMaxRounds = 12.0;  // outside: the rule (256x256 = 0.5 rounds: never; 1920x1080 = 15.8: exact f32 always)
 constexpr float kForkTuneGain = 0.985f;  // the fork must win by 1.5 % to be chosen: it costs a second workspace
-
-bool fork_tunable(const sr_ctx* c, int n, int H, int W, int halo_top, int halo_bot, const sr_halo_gate* gate) {
-    if (!c->fork_autotune || c->env_fork >= 0 || c->graph != SR_GRAPH_SR_NET || n != 1 || c->profiling || gate || W <= 0) return false;
-    const int own = H - halo_top - halo_bot;
-    if (own < 4 * SR_HALO) return false;
-    const int cus = c->cus > 0 ? c->cus : 256;
-    const double rounds = (double)((W + 31) / 32) * ((own + 7) / 8) / (2.0 * cus);
-    return rounds >= kForkTuneMinRounds && rounds < kForkTuneMaxRounds;
-}
 
 void fork_tune_release(sr_ctx::ForkTune& t) {
     for (auto& e : t.ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1195,12 +1054,12 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
     int mode = c->env_fork;
     sr_ctx::ForkTune* tune = nullptr;
     bool sample = false;
-    if (fork_tunable(c, n, H, W, halo_top, halo_bot, gate)) {
+    if (sr_fork_tunable(*c, n, H, W, halo_top, halo_bot, gate != nullptr)) {
         HIPCHK(c, hipSetDevice(c->device));
         tune = fork_tune_entry(c, img_u8, out_u8, img_ch, H, W, halo_top, halo_bot);
         if (tune) {
             int rows_rule = 0;
-            const int rule = plan_fork(c, -1, img_u8, img_ch, n, H, W, halo_top, halo_bot, &rows_rule) ? 1 : 0;
+            const int rule = sr_plan_fork(*c, -1, img_u8, img_ch, n, H, W, halo_top, halo_bot, &rows_rule) ? 1 : 0;
             if (tune->decided < 0) fork_tune_harvest(*tune, rule);
             if (tune->decided >= 0) {
                 mode = tune->decided;
@@ -1217,28 +1076,20 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
         }
         return rc;
     };
-    if (!plan_fork(c, mode, img_u8, img_ch, n, H, W, halo_top, halo_bot, &rows_a)) {
+    if (!sr_plan_fork(*c, mode, img_u8, img_ch, n, H, W, halo_top, halo_bot, &rows_a)) {
         if (tune && tune->decided < 0 && mode == 1) tune->decided = 0;  // (cannot be forked at all)
         if (c->graph == SR_GRAPH_SR_NET) sr_plan_note(c, "fork 0");
         return sampled(sr_run_stack(c, d_img, img_u8, img_ch, n, H, W, halo_top, halo_bot, d_out, out_u8, s, 0, gate));
     }
     HIPCHK(c, hipSetDevice(c->device));
-    {
-        const int rc = sr_ensure_fork_resources(c);
-        if (rc != SR_OK) return rc;
-    }
-    const int cut = halo_top + rows_a;  // first row of the second band, in the coordinates of the caller's buffer
+    SRCHK(sr_ensure_fork_resources(c));
     const size_t in_px = img_u8 ? (size_t)img_ch : 3 * sizeof(float), out_px = out_u8 ? 4 : 3 * sizeof(float);
-    const int f = c->factor;
-    StackJob a, b;
+    sr_fork_band fb[2];
+    sr_fork_bands(H, halo_top, halo_bot, rows_a, fb);
+    StackJob a = stack_job(c, 0, d_img, img_u8, img_ch, 1, fb[0].H, W, fb[0].top, fb[0].bot, d_out, out_u8, s);
+    StackJob b = stack_job(c, 1, (const char*)d_img + (size_t)fb[1].first_row * W * in_px, img_u8, img_ch, 1, fb[1].H, W, fb[1].top, fb[1].bot,
+                           (char*)d_out + (size_t)rows_a * c->factor * W * c->factor * out_px, out_u8, c->stream2);
     a.forked = b.forked = true;
-    a.c = b.c = c; a.img_u8 = b.img_u8 = img_u8; a.out_u8 = b.out_u8 = out_u8; a.img_ch = b.img_ch = img_ch; a.W = b.W = W;
-    a.ws = &c->ws[0]; a.s = s;
-    a.d_img = d_img; a.d_out = d_out; a.H = cut + SR_HALO; a.top = halo_top; a.bot = cut;
-    b.ws = &c->ws[1]; b.s = c->stream2;
-    b.d_img = (const char*)d_img + (size_t)(cut - SR_HALO) * W * in_px;
-    b.d_out = (char*)d_out + (size_t)rows_a * f * W * f * out_px;
-    b.H = H - (cut - SR_HALO); b.top = SR_HALO; b.bot = b.H - halo_bot;
     if (gate) {  // the first band holds the late rows at the image's top, the second those at its bottom; the caller's stream is the one whose wait is timed
         a.gate = b.gate = gate; a.late_top = gate->top; b.late_bot = gate->bot; a.mark = true;
     }
@@ -1246,9 +1097,8 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork[0], 0));
     // Both bands are planned (and their workspaces allocated) before anything is launched: should the second set of feature maps not fit,
     // the undivided pass on the first workspace still may -- the call must not fail for want of an optimisation's memory.
-    int rc = a.prepare();
-    if (rc != SR_OK) return rc;  // (the first band's maps do not fit: the undivided pass, which needs larger ones, cannot either)
-    rc = b.prepare();
+    SRCHK(a.prepare());  // (the first band's maps do not fit: the undivided pass, which needs larger ones, cannot either)
+    int rc = b.prepare();
     if (rc == SR_E_NOMEM) {  // the second workspace is the optimisation's: give back what of it exists and run undivided on the first
         for (auto& p : c->ws[1].d_feat) { if (p) (void)hipFree(p); p = nullptr; }
         c->ws[1].feat_cap_px = 0; c->ws[1].geo_n = 0;
@@ -1273,193 +1123,13 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
 
 namespace {
 
-// One unit of the host pipeline: some whole images of a batch, or a row band of a single image
-// with the halo rows it needs (band == untiled bit for bit, see sr_upscale_band_*).
-struct Chunk {
-    size_t in_off, in_bytes, out_off, out_bytes;  // of the chunk's FIRST image / of the band, in the caller's buffers
-    int n, h_ext, halo_top, halo_bot;
-    size_t in_step, out_step;                     // n > 1: distance between consecutive images of the chunk in the caller's
-                                                  // buffers (= the image size for a contiguous batch, stride x that for a deal)
-};
-
-// Which images of the caller's batch a call processes: first, first + stride, ... (count of them).  A plain call is
-// {0, 1, n}; a context's share of a round-robin deal over N contexts is {k, N, ceil((n - k) / N)}.
-struct Deal {
-    int first, stride, count;
-};
-
-// Split the job.  Batches go in chunks of ~1M px of whole images.  A single large sr_net image goes as row bands: band k
-// owns rows [y0,y1) and carries them plus SR_HALO rows on every side that is not an image edge.  Bands may differ in
-// height -- a workspace that meets a new geometry only has its border re-cleared (ensure_features), microseconds.
-// [y_lo, y_hi): the image rows this call is to produce (a whole image: 0, h; a device's share of a multi-GPU
-// call: its rows, sr_net and n == 1 only).
-std::vector<Chunk> plan_chunks(const sr_ctx* c, Deal deal, int h, int w, size_t in_px_bytes, size_t out_px_bytes, int y_lo, int y_hi,
-                               bool* in_order) {
-    std::vector<Chunk> plan;
-    *in_order = false;
-    const int f = c->factor, n = deal.count;
-    const size_t in_img = (size_t)h * w * in_px_bytes;
-    const size_t out_img = c->graph == SR_GRAPH_DOWNSAMPLE ? (size_t)(h / 3) * (w / 3) * out_px_bytes
-                                                           : (size_t)h * f * w * f * out_px_bytes;
-    const size_t in_step = in_img * deal.stride, out_step = out_img * deal.stride;
-    const bool pipe = c->pipeline && !c->profiling;  // per-stage profiling times one undivided pass
-    const int per = (int)std::max<size_t>(1, ((size_t)1 << 20) / ((size_t)h * w));  // images per chunk: ~1M px of work
-    if (pipe && n > per) {
-        for (int i = 0; i < n; i += per) {
-            const int m = std::min(per, n - i);
-            const size_t img = (size_t)deal.first + (size_t)i * deal.stride;
-            plan.push_back({img * in_img, m * in_img, img * out_img, m * out_img, m, h, 0, 0, in_step, out_step});
-        }
-        return plan;
-    }
-    const bool part = y_lo > 0 || y_hi < h;  // a share of the image: always in band form (halo rows from the image itself)
-    const int span = y_hi - y_lo;
-    std::vector<int> rows;  // rows of each band, top to bottom
-    int forced_sum = 0;
-    for (int rk : c->env_rows) forced_sum += rk;
-    const bool forced_plan = (!c->env_rows.empty() && forced_sum == span) || c->env_bands > 0;  // (sr_set_experiment "rows" / "bands": at any size)
-    // Below 2^19 px a lone frame used to go as ONE chunk: upload, kernels, download, nothing overlapping.  Round 6, u8 output, from
-    // ~200K px on: TWO bands in order on one stream -- the first band's download runs under the second band's kernels, which is worth more
-    // than the second band's 7 recomputed rows and five launches cost (scripts/host_plan_sweep.py, profiles/r6_host_mid_plans.txt: exact f32,
-    // 70 / 30: 640x480 0.970 -> 0.873 ms, 854x480 1.311 -> 1.138, 800x600 1.420 -> 1.330, 720x576 1.312 -> 1.186, 960x540 1.479 -> 1.342;
-    // the split-half mode, whose kernels are shorter beside the same download, 60 / 40: 640x480 0.536 -> 0.468, 800x600 0.792 -> 0.660,
-    // 960x540 0.837 -> 0.701; at 320x320 neither mode gains).  Equal bands on alternating streams are within 2 % of these on most shapes
-    // and 6 % better on some (800x600), 6 % worse on others: the in-order plan is the even-tempered one.
-    // (from 200K px in exact f32 -- 448x448 -5.4 %, 640x360 -6.5 %, 640x480 -5.5 % against one chunk measured alternately, but 430x419 +3 % -- and
-    // from 180K px in the split-half mode: 430x419 -4 %, 448x448 -11 %)
-    // f32 OUTPUT (three times the download, as long as the kernels or longer): in-order bands pay more still -- exact f32 60 / 40: 448x448
-    // 0.982 -> 0.801 ms, 640x480 1.379 -> 1.143; three equal bands from 400K px: 800x600 2.186 -> 1.556, 960x540 2.253 -> 1.784; split-half
-    // two equal bands: 448x448 0.686 -> 0.603, three from 300K px: 640x480 0.974 -> 0.845, 800x600 1.472 -> 1.234, 960x540 1.582 -> 1.328.
-    const bool split_mode = c->precision == SR_PRECISION_SPLIT_F16;
-    const size_t px_span = (size_t)span * w;
-    // (f32 output, smaller frames: exact f32 60 / 40 at 384x384 0.737 -> 0.621, at 320x320 0.578 -> 0.500; split-half 50 / 50 at 384x384 0.523 -> 0.483,
-    // at 320x320 -3 %: from 100K / 140K px)
-    const size_t mid_lo = out_px_bytes == 4 ? (split_mode ? 180000u : 200000u) : (split_mode ? 140000u : 100000u);
-    const bool mid_size = px_span >= mid_lo && px_span < ((size_t)1 << 19);
-    if (pipe && n == 1 && c->graph == SR_GRAPH_SR_NET && (forced_plan || mid_size || (size_t)span * w >= ((size_t)1 << 19))) {
-        // Kernel and download time per input pixel decide the shape of the plan (measured, page-locked buffers, PCIe 5 x16):
-        const double kern_ns = (c->precision == SR_PRECISION_SPLIT_F16 ? 0.9 : 2.0) * (f == 4 ? 1.2 : 1.0);
-        const double d2h_ns = (double)out_px_bytes * f * f / 52.0;
-        const double rho = kern_ns / d2h_ns;
-        int forced_rows = 0;
-        for (int rk : c->env_rows) forced_rows += rk;
-        if (!c->env_rows.empty() && forced_rows == span) {  // sr_set_experiment("rows"): exactly these bands
-            rows = c->env_rows;
-            *in_order = !c->env_rows_two;
-        } else if (c->env_bands > 0) {  // sr_set_experiment("bands"): that many equal bands
-            const int nb = std::min(c->env_bands, span / (2 * SR_HALO));
-            for (int k = 0; k < nb; ++k) rows.push_back((span * (k + 1)) / nb - (span * k) / nb);
-        } else if (mid_size) {
-            const bool u8_out = out_px_bytes == 4;
-            if (!u8_out && px_span >= (split_mode ? 300000u : 400000u) && span >= 6 * SR_HALO) {
-                const int third = span / 3 / 8 * 8;
-                rows = {third, third, span - 2 * third};
-            } else {
-                const double share = u8_out ? (split_mode ? 0.6 : 0.7) : (split_mode ? 0.5 : 0.6);
-                const int first = (int)(span * share) / 8 * 8;
-                if (first >= 2 * SR_HALO && span - first >= 2 * SR_HALO) rows = {first, span - first};
-            }
-            *in_order = !rows.empty();
-        } else {
-            // Compute-bound (f32 arithmetic, u8 output: rho = 2.9): only the LAST band's download is exposed, and band
-            // i's download hides under band i+1's kernels as long as band i+1 is at least 1/rho of it -- bands that
-            // shrink geometrically, as many as keep the last one >= 300K px (smaller bands no longer fill the chip: at
-            // 1080p the 128-row third band costs more than it hides, 4.95 against 4.85 ms with four equal bands).
-            // They compute IN ORDER on one stream: on two, band 1 runs beside band 0, both finish late and the
-            // largest download is the exposed one (1080p 5.54 ms).  Measured (scripts/geo_exp.py), geometric
-            // against equal bands: 2560x1440 8.17 / 8.37 ms, 3840x2160 17.50 / 17.78 ms.
-            const double r = std::min(rho * 0.85, 3.0);
-            int nb = 1;
-            double sum = 1.0, term = 1.0;
-            while (rho >= 2.0 && c->env_geo && nb < 5 && (double)span * w / (sum + term * r) >= 300e3) { term *= r; sum += term; ++nb; }
-            if (nb >= 3) {
-                int left = span;
-                for (int k = 0; k < nb - 1; ++k) {
-                    int rk = (int)((double)span * term / sum) / 8 * 8;  // whole 8-row tiles
-                    rk = std::max(2 * SR_HALO, std::min(rk, left - 2 * SR_HALO));
-                    rows.push_back(rk);
-                    left -= rk;
-                    term /= r;
-                }
-                rows.push_back(left);
-                *in_order = true;
-            } else if (rho >= 2.0 && c->env_geo && (double)span * w >= 800e3) {
-                // Compute-bound, but too small for three bands in order (720p .. ~2.8 M px): on alternating streams, two equal
-                // bands that keep the chip full, then a tail -- the exposed download is the last band's, so that one is
-                // ~150K px (smaller no longer pays its five launches), from 1.8 M px on with a band of 2.5x that in front of
-                // it under which the second big band's download finishes.  Measured round 3 (scripts/host_plan_sweep.py,
-                // profiles/r3_host_plans.txt), against the equal bands of round 2: 1920x1080 400,400,200,80 = 4.60 against
-                // 4.89 ms; 1600x900 3.36 / 3.54; 1280x720 2.22 / 2.36.  2560x1440 is the geometric plan's either way.
-                const int last = std::max(16, (int)(150e3 / w + 4.0) / 8 * 8);
-                const int mid = (double)span * w >= 1.8e6 ? (5 * last / 2) / 8 * 8 : 0;
-                const int big = (span - last - mid) / 2 / 8 * 8;
-                if (big >= 2 * last) {
-                    rows = {big, span - last - mid - big};
-                    if (mid) rows.push_back(mid);
-                    rows.push_back(last);
-                }
-            }
-        }
-        if (rows.empty() && !mid_size) {
-            // Download-bound or balanced (f32 output, the split-half mode): equal bands.  Few expose the first upload
-            // and the last download, many pay 14 recomputed rows and five launches each.  Measured, f32 1080p
-            // 1 / 2 / 4 / 5 / 8 bands = 5.96 / 5.14 / 4.93 / 5.12 / 5.22 ms; the split-half mode computes 2.2x faster
-            // than the bus drains its output and prefers more: 4 / 5 / 6 / 8 bands = 3.77 / 2.7-3.4 / 2.82 / 3.05 ms.
-            // Round 6, f32 OUTPUT re-measured on this round's kernels (scripts/host_plan_sweep.py, profiles/r6_host_mid_plans.txt 6.): five equal bands
-            // IN ORDER on one stream, eight from 3 M px, beat the equal bands on alternating streams of rounds 2-3 in a process of its own (a C / Rust
-            // host) -- exact f32 1280x720 3.53 -> 2.71 ms, 1920x1080 6.25 -> 5.69, 3840x2160 21.1 -> 19.9; split-half 2.29 -> 2.17, 4.74 -> 4.60,
-            // 17.8 -> 17.2 -- and are within +-6 % of them inside bench.py's long-lived torch process (exact f32 1920x1080 6.17 against 5.85, split-half
-            // 4.60 against 4.93: 7.).
-            // The split-half mode with u8 output keeps its equal bands on alternating streams: bands in order that shrink by 0.85 are 3-6 % faster
-            // in a fresh process (1920x1080 2.30 -> 2.12 ms) but read 3.37 ms for the first dozens of calls inside bench.py's process -- no overlap at
-            // all between the one compute stream and the download stream, which two compute streams never lose entirely (7.); not adopted.
-            if (out_px_bytes != 4) {
-                const int nb = std::min(px_span < 3000000u ? 5 : 8, std::max(1, span / (2 * SR_HALO)));
-                for (int k = 0; k < nb; ++k) rows.push_back((span * (k + 1)) / nb - (span * k) / nb);
-                *in_order = true;
-            } else {
-                int nb = span / (split_mode ? 176 : 256);
-                if (nb > 8) nb = 8;
-                for (int k = 0; k < nb; ++k) rows.push_back((span * (k + 1)) / nb - (span * k) / nb);
-            }
-        }
-    }
-    const size_t img0_in = (size_t)deal.first * in_img, img0_out = (size_t)deal.first * out_img;
-    if (rows.size() >= 2) {
-        bool ok = true;
-        int y0 = y_lo;
-        for (int rk : rows) {
-            const int y1 = y0 + rk;
-            const int start = std::max(0, y0 - SR_HALO), end = std::min(h, y1 + SR_HALO);
-            const int ht = y0 - start, hb = end - y1;
-            // sr_run_stack's rules: a halo is SR_HALO rows or, at an image edge, none
-            ok = ok && rk > 0 && (ht == 0 || ht == SR_HALO) && (hb == 0 || hb == SR_HALO);
-            plan.push_back({img0_in + (size_t)start * w * in_px_bytes, (size_t)(end - start) * w * in_px_bytes,
-                            img0_out + (size_t)y0 * f * w * f * out_px_bytes, (size_t)rk * f * w * f * out_px_bytes, 1, end - start, ht, hb,
-                            0, 0});
-            y0 = y1;
-        }
-        if (ok && y0 == y_hi) return plan;
-        plan.clear();
-    }
-    if (part) {  // one band: the rows themselves plus SR_HALO rows on every side that is not an image edge
-        const int start = std::max(0, y_lo - SR_HALO), end = std::min(h, y_hi + SR_HALO);
-        plan.push_back({img0_in + (size_t)start * w * in_px_bytes, (size_t)(end - start) * w * in_px_bytes,
-                        img0_out + (size_t)y_lo * f * w * f * out_px_bytes, (size_t)span * f * w * f * out_px_bytes, 1, end - start,
-                        y_lo - start, end - y_hi, 0, 0});
-        return plan;
-    }
-    plan.push_back({img0_in, (size_t)n * in_img, img0_out, (size_t)n * out_img, n, h, 0, 0, in_step, out_step});
-    return plan;
-}
-
 // Host-pointer entry points: upload, conv stack, download -- software-pipelined over chunks on
 // three streams.  Issue order is H2D(i+1), kernels(i+1), D2H(i): with pageable caller memory the
 // runtime blocks the calling thread inside each copy, and this order keeps kernels queued behind
 // it; with pinned memory (sr_host_alloc) all three engines run concurrently.
 // reserve: no caller buffers -- everything else of the call happens (allocations, events, the kernels on whatever the
 // staging buffers hold), so that the first real call costs what every later one does (sr_reserve_*).
-int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int h, int w, void* out, bool out_u8, int y_lo = 0,
+int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, sr_deal deal, int h, int w, void* out, bool out_u8, int y_lo = 0,
              int y_hi = -1, bool reserve = false) {
     const int n = deal.count;
     if (!c || ((!in || !out) && !reserve) || n <= 0 || h <= 0 || w <= 0 || deal.first < 0 || deal.stride < 1) return SR_E_INVALID;
@@ -1477,7 +1147,7 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     if (y_hi < h && h - y_hi < SR_HALO) return SR_E_HALO;
     sr_domain_set_aside(c);
     bool in_order = false;
-    const std::vector<Chunk> plan = plan_chunks(c, deal, h, w, in_px, out_px, y_lo, y_hi, &in_order);
+    const std::vector<sr_chunk> plan = sr_plan_chunks(*c, deal, h, w, in_px, out_px, y_lo, y_hi, &in_order);
     const int nch = (int)plan.size();
     const int slots = nch > 1 ? 2 : 1;
     {
@@ -1489,10 +1159,7 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
         if (y_lo > 0 || y_hi < h) line += " rows=" + std::to_string(y_lo) + ":" + std::to_string(y_hi);
         if (c->graph == SR_GRAPH_SR_NET) sr_plan_note(c, line);
     }
-    {
-        const int rc = sr_ensure_streams(c, nch > 1);
-        if (rc != SR_OK) return rc;
-    }
+    SRCHK(sr_ensure_streams(c, nch > 1));
     // One chunk: upload, kernels and download in order on `stream`.  Several: chunk i uploads on the stream its kernels
     // follow on (the other compute stream is busy with chunk i-1 meanwhile) -- or, when all chunks compute in order on
     // `stream`, on the idle `stream2` -- and downloads on `copy_out`.
@@ -1505,12 +1172,9 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     const bool own_upload = nch > 1 && c->copy_in && c->precision == SR_PRECISION_F32;
     hipStream_t down = nch > 1 ? c->copy_out : c->stream;
     size_t in_max = 0, out_max = 0;
-    for (const Chunk& k : plan) { in_max = std::max(in_max, k.in_bytes); out_max = std::max(out_max, k.out_bytes); }
-    {
-        const size_t in1 = slots == 2 ? in_max : 0, out1 = slots == 2 ? out_max : 0;
-        const int rc = sr_ensure_bufs(c, {{&c->d_in[0], in_max}, {&c->d_out[0], out_max}, {&c->d_in[1], in1}, {&c->d_out[1], out1}});
-        if (rc != SR_OK) return rc;
-    }
+    for (const sr_chunk& k : plan) { in_max = std::max(in_max, k.in_bytes); out_max = std::max(out_max, k.out_bytes); }
+    const size_t in1 = slots == 2 ? in_max : 0, out1 = slots == 2 ? out_max : 0;
+    SRCHK(sr_ensure_bufs(c, {{&c->d_in[0], in_max}, {&c->d_out[0], out_max}, {&c->d_in[1], in1}, {&c->d_out[1], out1}}));
     // events per chunk: 0 upload begins, 1 upload done, 2 kernels begin, 3 kernels done, 4 download done
     while (c->pool.size() < (size_t)nch * 5) {
         hipEvent_t e = nullptr;
@@ -1521,7 +1185,7 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     const char* src = (const char*)in;
     char* dst = (char*)out;
     // a chunk's images are contiguous on the device; in the caller's buffers they are in_step / out_step apart
-    auto copy_images = [&](const Chunk& k, bool up, int sl, hipStream_t on) -> int {
+    auto copy_images = [&](const sr_chunk& k, bool up, int sl, hipStream_t on) -> int {
         if (reserve) return SR_OK;
         const bool contiguous = k.n == 1 || (up ? k.in_step == k.in_bytes / k.n : k.out_step == k.out_bytes / k.n);
         const int pieces = contiguous ? 1 : k.n;
@@ -1538,28 +1202,24 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     // (a geometric band plan wants the opposite: band i finished, and downloading, before band i+1 takes the chip)
     auto cstream = [&](int i) { return (slots == 2 && (i & 1) && !in_order) ? c->stream2 : c->stream; };
     auto issue_front = [&](int i) -> int {  // upload + kernels of chunk i
-        const Chunk& k = plan[i];
+        const sr_chunk& k = plan[i];
         const int sl = i % slots;
         hipStream_t cs = cstream(i);
         hipStream_t upl = own_upload ? c->copy_in : (in_order && nch > 1) ? c->stream2 : cs;
         if (i >= 2) HIPCHK(c, hipStreamWaitEvent(upl, ev(i - 2, 3), 0));  // slot's previous reader
         HIPCHK(c, hipEventRecord(ev(i, 0), upl));
-        int rc = copy_images(k, true, sl, upl);
-        if (rc != SR_OK) return rc;
+        SRCHK(copy_images(k, true, sl, upl));
         HIPCHK(c, hipEventRecord(ev(i, 1), upl));
         if (upl != cs) HIPCHK(c, hipStreamWaitEvent(cs, ev(i, 1), 0));
         if (i >= 2) HIPCHK(c, hipStreamWaitEvent(cs, ev(i - 2, 4), 0));   // slot's previous download
         HIPCHK(c, hipEventRecord(ev(i, 2), cs));
-        rc = sr_run_stack(c, c->d_in[sl].p, img_u8, img_ch, k.n, k.h_ext, w, k.halo_top, k.halo_bot, c->d_out[sl].p,
-                          out_u8, cs, sl);
-        if (rc != SR_OK) return rc;
+        SRCHK(sr_run_stack(c, c->d_in[sl].p, img_u8, img_ch, k.n, k.h_ext, w, k.halo_top, k.halo_bot, c->d_out[sl].p, out_u8, cs, sl));
         HIPCHK(c, hipEventRecord(ev(i, 3), cs));
         return SR_OK;
     };
     auto issue_back = [&](int i) -> int {  // download of chunk i
         if (down != cstream(i)) HIPCHK(c, hipStreamWaitEvent(down, ev(i, 3), 0));
-        const int rc = copy_images(plan[i], false, i % slots, down);
-        if (rc != SR_OK) return rc;
+        SRCHK(copy_images(plan[i], false, i % slots, down));
         HIPCHK(c, hipEventRecord(ev(i, 4), down));
         return SR_OK;
     };
@@ -1583,7 +1243,6 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
         HIPCHK(c, hipEventElapsedTime(&ms, ev(i, 3), ev(i, 4))); d2h += ms;  // includes waiting for the copy engine
     }
     c->h2d_ms = h2d; c->total_ms = ker; c->d2h_ms = d2h; c->band_pending = false;
-    c->last_chunks = nch;
     if (nch > 1) c->last_h = c->last_w = 0;  // the feature maps hold one chunk only: sr_read_feature refuses
     if (sr_domain_tripped(c)) {  // (every stream has drained: the flag is final) the whole job again in exact f32, as sr_host_call does
         if (reserve) return SR_OK;
@@ -1595,10 +1254,28 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, Deal deal, int 
     return SR_OK;
 }
 
+// Each of `parts` shares on its own host thread -- or, should the system refuse another thread, right here: no exception may cross
+// the C ABI with joinable threads behind it.  The first share that failed gives the status.
+template <class F>
+int run_shares(int parts, F share) {
+    std::vector<int> rc(parts, SR_OK);
+    std::vector<std::thread> th;
+    for (int k = 0; k < parts; ++k) {
+        auto fn = [&rc, &share, k] { rc[k] = share(k); };
+        try { th.emplace_back(fn); } catch (const std::exception&) { fn(); }
+    }
+    for (auto& t : th) t.join();
+    for (int k = 0; k < parts; ++k)
+        if (rc[k] != SR_OK) return rc[k];
+    return SR_OK;
+}
+
+}  // namespace
+
 // Contexts that cooperate on one call must be distinct objects computing the same function: same graph, factor,
 // arithmetic mode and parameters -- or the "bit-identical to the single-device call" guarantee silently breaks
 // (a seam between shares), and one context driven from two threads at once races on its workspace.
-int check_context_set(sr_ctx* const* ctxs, int n_ctx) {
+int sr_check_context_set(sr_ctx* const* ctxs, int n_ctx) {
     if (!ctxs || n_ctx <= 0) return SR_E_INVALID;
     for (int k = 0; k < n_ctx; ++k) {
         if (!ctxs[k] || ctxs[k]->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
@@ -1608,21 +1285,6 @@ int check_context_set(sr_ctx* const* ctxs, int n_ctx) {
     }
     return SR_OK;
 }
-
-// A share on its own host thread -- or, should the system refuse another thread, right here: no exception may cross the C ABI
-// with joinable threads behind it.
-template <class F>
-void spawn_or_run(std::vector<std::thread>& th, F fn) {
-    try {
-        th.emplace_back(fn);
-    } catch (const std::exception&) {
-        fn();
-    }
-}
-
-}  // namespace
-
-int sr_check_context_set(sr_ctx* const* ctxs, int n_ctx) { return check_context_set(ctxs, n_ctx); }
 
 extern "C" {
 
@@ -1654,24 +1316,23 @@ int sr_upscale_band_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, i
                              (hipStream_t)stream);
 }
 
-// ... and what a DEVICE-pointer call of that shape would create on its first use: if it runs as two bands (plan_fork), the second
+// ... and what a DEVICE-pointer call of that shape would create on its first use: if it runs as two bands (sr_plan_fork), the second
 // stream, the fork / join events and both workspaces at the bands' geometry -- allocations and a stream creation that would
 // otherwise happen, synchronously, inside the first "asynchronous" sr_upscale_*_dev call after the reserve.
 static int reserve_fork(sr_ctx* c, bool img_u8, int img_ch, int n, int h, int w) {
     int rows_a = 0;
     // (a shape the fork tuner will measure runs both ways: what the forked calls need is created here too)
-    if (!plan_fork(c, fork_tunable(c, n, h, w, 0, 0, nullptr) ? 1 : c->env_fork, img_u8, img_ch, n, h, w, 0, 0, &rows_a)) return SR_OK;
+    if (!sr_plan_fork(*c, sr_fork_tunable(*c, n, h, w, 0, 0, false) ? 1 : c->env_fork, img_u8, img_ch, n, h, w, 0, 0, &rows_a)) return SR_OK;
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = sr_ensure_streams(c, false);
-    if (rc == SR_OK) rc = sr_ensure_fork_resources(c);
-    if (rc != SR_OK) return rc;
-    StackJob a, b;
+    SRCHK(sr_ensure_streams(c, false));
+    SRCHK(sr_ensure_fork_resources(c));
+    sr_fork_band fb[2];
+    sr_fork_bands(h, 0, 0, rows_a, fb);
+    StackJob a = stack_job(c, 0, nullptr, img_u8, img_ch, 1, fb[0].H, w, fb[0].top, fb[0].bot, nullptr, false, c->stream);
+    StackJob b = stack_job(c, 1, nullptr, img_u8, img_ch, 1, fb[1].H, w, fb[1].top, fb[1].bot, nullptr, false, c->stream);
     a.forked = b.forked = true;
-    a.c = b.c = c; a.W = b.W = w; a.img_u8 = b.img_u8 = img_u8; a.img_ch = b.img_ch = img_ch;
-    a.ws = &c->ws[0]; a.s = c->stream; a.H = rows_a + SR_HALO; a.top = 0; a.bot = rows_a;
-    b.ws = &c->ws[1]; b.s = c->stream; b.H = h - (rows_a - SR_HALO); b.top = SR_HALO; b.bot = b.H;
-    rc = a.prepare();
+    int rc = a.prepare();
     if (rc == SR_OK) rc = b.prepare();
     if (rc == SR_E_NOMEM) return SR_OK;  // the device call will run undivided (sr_run_stack_auto)
     if (rc != SR_OK) return rc;
@@ -1681,24 +1342,24 @@ static int reserve_fork(sr_ctx* c, bool img_u8, int img_ch, int n, int h, int w)
 
 int sr_reserve_f32(sr_ctx* c, int n, int h, int w) {
     sr_plan_clear(c);
-    const int rc = run_host(c, nullptr, false, 3, Deal{0, 1, n}, h, w, nullptr, false, 0, -1, true);
+    const int rc = run_host(c, nullptr, false, 3, sr_deal{0, 1, n}, h, w, nullptr, false, 0, -1, true);
     return rc == SR_OK ? reserve_fork(c, false, 3, n, h, w) : rc;
 }
 
 int sr_reserve_rgba8(sr_ctx* c, int in_channels, int n, int h, int w) {
     sr_plan_clear(c);
-    const int rc = run_host(c, nullptr, true, in_channels, Deal{0, 1, n}, h, w, nullptr, true, 0, -1, true);
+    const int rc = run_host(c, nullptr, true, in_channels, sr_deal{0, 1, n}, h, w, nullptr, true, 0, -1, true);
     return rc == SR_OK ? reserve_fork(c, true, in_channels, n, h, w) : rc;
 }
 
 int sr_upscale_f32(sr_ctx* c, const float* in, int n, int h, int w, float* out) {
     sr_plan_clear(c);
-    return run_host(c, in, false, 3, Deal{0, 1, n}, h, w, out, false);
+    return run_host(c, in, false, 3, sr_deal{0, 1, n}, h, w, out, false);
 }
 
 int sr_upscale_rgba8(sr_ctx* c, const uint8_t* in, int in_channels, int n, int h, int w, uint8_t* out) {
     sr_plan_clear(c);
-    return run_host(c, in, true, in_channels, Deal{0, 1, n}, h, w, out, true);
+    return run_host(c, in, true, in_channels, sr_deal{0, 1, n}, h, w, out, true);
 }
 
 // One image, several GPUs, one process: device k produces its share of the rows from the caller's image directly
@@ -1706,27 +1367,12 @@ int sr_upscale_rgba8(sr_ctx* c, const uint8_t* in, int in_channels, int n, int h
 // devices); one host thread per context drives its pipeline.  Shares are multiples of 8 rows (whole tiles).
 static int run_multi(sr_ctx* const* ctxs, int n_ctx, const void* in, bool img_u8, int img_ch, int h, int w, void* out, bool out_u8) {
     if (!in || !out || h <= 0 || w <= 0) return SR_E_INVALID;
-    const int chk = check_context_set(ctxs, n_ctx);
-    if (chk != SR_OK) return chk;
+    SRCHK(sr_check_context_set(ctxs, n_ctx));
     for (int k = 0; k < n_ctx; ++k) sr_plan_clear(ctxs[k]);
-    int rows = (h + n_ctx - 1) / n_ctx;
-    rows = std::max(8, (rows + 7) / 8 * 8);
-    const int used = (h + rows - 1) / rows;
-    if (used == 1) return run_host(ctxs[0], in, img_u8, img_ch, Deal{0, 1, 1}, h, w, out, out_u8);
-    // the last share must not be thinner than the halo its neighbour reads from it
-    std::vector<int> lo(used), hi(used);
-    for (int k = 0; k < used; ++k) { lo[k] = k * rows; hi[k] = std::min(h, lo[k] + rows); }
-    if (hi[used - 1] - lo[used - 1] < SR_HALO) { hi[used - 2] = h; lo.pop_back(); hi.pop_back(); }
-    const int parts = (int)lo.size();
-    if (parts == 1) return run_host(ctxs[0], in, img_u8, img_ch, Deal{0, 1, 1}, h, w, out, out_u8);
-    std::vector<int> rc(parts, SR_OK);
-    std::vector<std::thread> th;
-    for (int k = 0; k < parts; ++k)
-        spawn_or_run(th, [&, k] { rc[k] = run_host(ctxs[k], in, img_u8, img_ch, Deal{0, 1, 1}, h, w, out, out_u8, lo[k], hi[k]); });
-    for (auto& t : th) t.join();
-    for (int k = 0; k < parts; ++k)
-        if (rc[k] != SR_OK) return rc[k];
-    return SR_OK;
+    const std::vector<sr_row_share> share = sr_multi_shares(n_ctx, h);
+    const int parts = (int)share.size();
+    if (parts == 1) return run_host(ctxs[0], in, img_u8, img_ch, sr_deal{0, 1, 1}, h, w, out, out_u8);
+    return run_shares(parts, [&](int k) { return run_host(ctxs[k], in, img_u8, img_ch, sr_deal{0, 1, 1}, h, w, out, out_u8, share[k].lo, share[k].hi); });
 }
 
 int sr_upscale_f32_multi(sr_ctx* const* ctxs, int n_ctx, const float* in, int h, int w, float* out) {
@@ -1743,19 +1389,11 @@ int sr_upscale_rgba8_multi(sr_ctx* const* ctxs, int n_ctx, const uint8_t* in, in
 static int run_batch_multi(sr_ctx* const* ctxs, int n_ctx, const void* in, bool img_u8, int img_ch, int n, int h, int w, void* out,
                            bool out_u8) {
     if (!in || !out || n <= 0 || h <= 0 || w <= 0) return SR_E_INVALID;
-    const int chk = check_context_set(ctxs, n_ctx);
-    if (chk != SR_OK) return chk;
+    SRCHK(sr_check_context_set(ctxs, n_ctx));
     for (int k = 0; k < n_ctx; ++k) sr_plan_clear(ctxs[k]);
     const int used = std::min(n_ctx, n);
-    if (used == 1) return run_host(ctxs[0], in, img_u8, img_ch, Deal{0, 1, n}, h, w, out, out_u8);
-    std::vector<int> rc(used, SR_OK);
-    std::vector<std::thread> th;
-    for (int k = 0; k < used; ++k)
-        spawn_or_run(th, [&, k] { rc[k] = run_host(ctxs[k], in, img_u8, img_ch, Deal{k, used, (n - k + used - 1) / used}, h, w, out, out_u8); });
-    for (auto& t : th) t.join();
-    for (int k = 0; k < used; ++k)
-        if (rc[k] != SR_OK) return rc[k];
-    return SR_OK;
+    if (used == 1) return run_host(ctxs[0], in, img_u8, img_ch, sr_deal{0, 1, n}, h, w, out, out_u8);
+    return run_shares(used, [&](int k) { return run_host(ctxs[k], in, img_u8, img_ch, sr_deal{k, used, (n - k + used - 1) / used}, h, w, out, out_u8); });
 }
 
 int sr_upscale_f32_batch_multi(sr_ctx* const* ctxs, int n_ctx, const float* in, int n, int h, int w, float* out) {

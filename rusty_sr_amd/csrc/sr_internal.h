@@ -11,7 +11,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/srhip.h"
+#include "sr_plan.h"  // (and with it include/srhip.h)
 
 // 16-channel halves of conv5 (stage 2's 3x3 source) that the exact mode runs as Winograd F(2,3) rows by default: 1.  Both halves would take
 // the whole call's direct-FLOP rate to within 1 % of the f32 roof on the fastest boxes, which bench.py's contract asserts it stays below
@@ -24,9 +24,9 @@ struct sr_buf {
     size_t cap = 0;
 };
 
-struct sr_ctx {
+struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk planners read of a context, sr_plan.h)
     int device = 0;
-    int cus = 0, clock_mhz = 0;
+    int clock_mhz = 0;
     char name[128] = {0};
     hipStream_t stream = nullptr;
     float* d_params = nullptr;  // all packed parameters, one allocation
@@ -34,9 +34,7 @@ struct sr_ctx {
     size_t off_w0 = 0, off_w0h = 0, off_w[5] = {0}, off_wh[5] = {0}, off_bias[5] = {0}, off_beta[5] = {0};
     size_t off_wino1 = 0;  // stage 1's weights as Winograd F(2,3) chunks (sr_api.cpp pack_steps_wino)
     size_t off_wino2[3] = {0, 0, 0};  // stage 2's, by wino5: conv2 as Winograd F(2,3) chunks, then conv5's first wino5 halves as 3-tap Winograd chunks, then its other halves' direct chunks
-    int wino = 2;          // exact mode, stages 1 .. wino in their Winograd F(2,3) form ("wino" switch; "0": all direct -- last bits differ)
-    int wino5 = kWinoConv5Halves;  // ... and, with stage 2, the first wino5 halves of conv5 ("wino" = "2": none, the form before; "3": both)
-    int precision = 0;  // SR_PRECISION_F32 / SR_PRECISION_SPLIT_F16
+    int wino5 = kWinoConv5Halves;  // exact mode, with stage 2 in its Winograd form (sr_plan_env::wino), the first wino5 halves of conv5 ("wino" = "2": none, the form before; "3": both)
     // Domain of the split-half mode (include/srhip.h, sr_set_precision): values are carried as pairs of HALVES, so every weight, input
     // and activation must be finite and below 65504 in magnitude.  Weights are checked once (split_ok); inputs and activations by the
     // kernels, which raise *h_domain -- one word of mapped host memory, read by the host without a copy once the stream has drained.
@@ -44,8 +42,6 @@ struct sr_ctx {
     int* h_domain = nullptr;   // host address of the flag
     int* d_domain = nullptr;   // the same word as the device sees it
     bool dev_fault = false;    // a fault an earlier *_dev call left in *h_domain, set aside at the start of a host-pointer call: sr_check_domain's
-    int graph = SR_GRAPH_SR_NET;
-    int factor = SR_FACTOR;
     // Device workspace of one pass of the conv stack.  Two of them: the host pipeline (run_host) alternates chunks between
     // two compute streams so that the tail of one chunk's stage launches overlaps the head of the next chunk's; every
     // other entry point uses ws[0] only (ws[1] is allocated on first use).
@@ -64,23 +60,12 @@ struct sr_ctx {
     hipStream_t copy_in = nullptr;    // uploads: exact-f32 contexts, from their second pipelined call on (else on the compute streams)
     int pipelined_calls = 0;
     std::vector<hipEvent_t> pool;  // per-chunk timing / ordering events of run_host, grown on demand
-    int pipeline = 1;              // 0: one upload, one pass, one download
-    int last_chunks = 0;
     hipEvent_t ev[6] = {nullptr};  // around the five stages of a profiled pass of the conv stack (sr_run_stack)
-    bool profiling = false;
     double total_ms = 0, stage_ms[5] = {0}, h2d_ms = 0, d2h_ms = 0;
     int last_h = 0, last_w = 0;
     int last_hip = 0;
-    // experiment switches, read once at sr_create (none changes results but "wino", see wino above): SRHIP_TH, SRHIP_PIPE, SRHIP_BW, SRHIP_TAIL
-    int env_th[5] = {0, 0, 0, 0, 0};  // 0: automatic
-    int env_pipe = 1;                 // 0: first form everywhere, 1: pipe form except for small launches, 2: pipe form everywhere
+    // experiment switches beside the planners' (sr_plan_env), read once at sr_create like them
     int env_bw = -1;                  // tile-order column-block width in tiles (-1: automatic)
-    float env_tail = -1.0f;           // 4-row tiles at the end of a launch, in resident workgroups (< 0: automatic = 1 where the tail rule applies, 0: none)
-    int env_fork = -1;                // device entry points, one image: two row bands on two streams (sr_run_stack_auto); -1 automatic, 0 never,
-                                      // 1 always, > 1: always, with this many rows in the first band
-    double fork_min_rounds = 3.5;     //   automatic: fork from this many rounds of 8-row tiles per resident workgroup on ...
-    double fork_max_rounds = 1e9;     //   ... and below this many (no upper bound by default)
-    double fork_share = 0.5;          //   the first band's share of the rows
     hipEvent_t ev_fork[2] = {nullptr, nullptr};  // fork (caller's stream -> stream2) and join (stream2 -> caller's stream)
     // Mid-size shapes (0.55-12 rounds of 8-row tiles): whether the fork pays depends on how the tiles of the image and of its two bands
     // happen to fill the chip's last round -- -15 ... +20 % from one shape to the next (profiles/r6_fork_tune.txt), which no rule in
@@ -98,13 +83,8 @@ struct sr_ctx {
         unsigned long long used = 0;      // for eviction: the entry used longest ago goes
     };
     std::vector<ForkTune> fork_tune;
-    bool fork_autotune = true;
     unsigned long long fork_tune_clock = 0;
     int env_auxgrid = 0;              // bilinear_net / downsample_net: at most this many workgroups per launch (0: automatic); "auxgrid"
-    int env_bands = 0;                // host pipeline: forced number of row bands (0: automatic)
-    std::vector<int> env_rows;        // host pipeline: forced band heights (empty: automatic)
-    bool env_rows_two = false;        //   ... computed on alternating streams instead of in order
-    bool env_geo = true;              // host pipeline: geometric band plan where the call is compute-bound
     unsigned long long params_hash = 0;  // FNV-1a of the parameter vector: contexts of one sharded call must agree
     // ---- multi-GPU (sr_comm.cpp): one RCCL communicator per context, neighbour halo exchange
     void* comm = nullptr;             // ncclComm_t
@@ -231,6 +211,7 @@ struct sr_device_guard {
     sr_device_guard& operator=(const sr_device_guard&) = delete;
 };
 
+#define SRCHK(expr) do { const int rc__ = (expr); if (rc__ != SR_OK) return rc__; } while (0)  // a status that is not SR_OK is the caller's
 #define HIPCHK(ctx, expr)                         \
     do {                                          \
         hipError_t e__ = (expr);                  \

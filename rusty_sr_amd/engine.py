@@ -53,6 +53,44 @@ def img_to_data(pixels: np.ndarray) -> np.ndarray:
     return px[..., :3].astype(np.float32) / np.float32(255.0)
 
 
+def parse_plan(text: str) -> dict:
+    """A plan record (the text of sr_get_experiment "plan") as data:
+    {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...], "aux": [dict, ...]}.
+    host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
+    st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
+    parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid."""
+    rec = {"host": [], "fork": [], "launches": [], "aux": []}
+    for line in text.splitlines():
+        words = line.split()
+        count = 1
+        if words[-1].startswith("x") and words[-1][1:].isdigit():
+            count = int(words.pop()[1:])
+        if words[0] == "host":
+            rows = None
+            if words[-1].startswith("rows="):
+                a, b = words.pop()[5:].split(":")
+                rows = (int(a), int(b))
+            for _ in range(count):
+                rec["host"].append((words[1], [int(v) for v in words[2].split(",")], rows))
+        elif words[0] == "fork":
+            sizes = [int(v) for v in words[2].split(",")] if len(words) > 2 and words[2][0].isdigit() else [0, 0]
+            for _ in range(count):
+                rec["fork"].append((words[1] == "1", sizes[0], sizes[1]))
+        elif words[0] == "launch":
+            d = dict(w.split("=", 1) for w in words[1:])
+            for k in ("st", "ty8", "ty4", "grid", "f", "ch"):
+                d[k] = int(d[k])
+            d["count"] = count
+            rec["launches"].append(d)
+        elif words[0] == "aux":
+            d = dict(w.split("=", 1) for w in words[1:])
+            for k in ("ch", "grid", "units"):
+                d[k] = int(d[k])
+            d["count"] = count
+            rec["aux"].append(d)
+    return rec
+
+
 class Engine:
     """One sr_ctx (= one GPU, one parameter set)."""
 
@@ -736,41 +774,8 @@ class Engine:
         return buf.value.decode()
 
     def last_plan(self) -> dict:
-        """What the last call on this context ran (sr_get_experiment "plan"), as data:
-        {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...], "aux": [dict, ...]}.
-        host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
-        st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
-        parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid."""
-        rec = {"host": [], "fork": [], "launches": [], "aux": []}
-        for line in self.get_experiment("plan").splitlines():
-            words = line.split()
-            count = 1
-            if words[-1].startswith("x") and words[-1][1:].isdigit():
-                count = int(words.pop()[1:])
-            if words[0] == "host":
-                rows = None
-                if words[-1].startswith("rows="):
-                    a, b = words.pop()[5:].split(":")
-                    rows = (int(a), int(b))
-                for _ in range(count):
-                    rec["host"].append((words[1], [int(v) for v in words[2].split(",")], rows))
-            elif words[0] == "fork":
-                sizes = [int(v) for v in words[2].split(",")] if len(words) > 2 and words[2][0].isdigit() else [0, 0]
-                for _ in range(count):
-                    rec["fork"].append((words[1] == "1", sizes[0], sizes[1]))
-            elif words[0] == "launch":
-                d = dict(w.split("=", 1) for w in words[1:])
-                for k in ("st", "ty8", "ty4", "grid", "f", "ch"):
-                    d[k] = int(d[k])
-                d["count"] = count
-                rec["launches"].append(d)
-            elif words[0] == "aux":
-                d = dict(w.split("=", 1) for w in words[1:])
-                for k in ("ch", "grid", "units"):
-                    d[k] = int(d[k])
-                d["count"] = count
-                rec["aux"].append(d)
-        return rec
+        """What the last call on this context ran (sr_get_experiment "plan"), as data: parse_plan of its text."""
+        return parse_plan(self.get_experiment("plan"))
 
     def set_profiling(self, on: bool):
         _lib.check(self._L.sr_set_profiling(self._ctx, int(on)))
