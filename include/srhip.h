@@ -581,6 +581,48 @@ int sr_upscale_rgba8_alpha_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int
                                void* stream);
 int sr_upscale_rgba8_alpha(sr_ctx* ctx, const uint8_t* in_rgba, int n, int h, int w, uint8_t* out_rgba, int radius, unsigned members);
 
+/* ---- Resampling to any size ----
+ * The network upscales by exactly its factor and the downsample graph shrinks by exactly 3; these calls produce any output size, on the
+ * device, from values that have not been quantised yet.  UNPINNED: the reference has no counterpart; tests/resize_ref.py restates the rule
+ * in numpy (f64) and tests/test_resize_cpu.py holds that restatement to Pillow's Image.resize.
+ *   The rule is a separable resampler in Pillow's convention.  Per axis, n_in -> n_out samples: scale = n_in / n_out, fs = max(scale, 1); a
+ *     filter F of support S reaches s = S fs.  Output index o has its centre at c = (o + 0.5) scale and the taps i = lo .. hi - 1 with
+ *     lo = max(trunc(c - s + 0.5), 0), hi = min(trunc(c + s + 0.5), n_in); w_i = F((i + 0.5 - c) / fs), divided by the sum of the w_i: taps
+ *     are clipped at the border and renormalised, never replicated.  Filters: SR_FILTER_BOX, S = 0.5, F = 1 for -0.5 < x <= 0.5;
+ *     SR_FILTER_TRIANGLE, S = 1, F = max(0, 1 - |x|); SR_FILTER_CATROM, S = 2, the Keys cubic with a = -0.5; SR_FILTER_LANCZOS3, S = 3,
+ *     F = sinc(x) sinc(x / 3) for |x| < 3.  Weights are computed in f64 and stored as f32.
+ *   Columns are resampled first (horizontally, over every input row), then rows; sums run in f32 over the taps in ascending index.  Colours
+ *     go through SrgbToLinear before the horizontal pass and LinearToSrgb after the vertical one -- the expressions of the bilinear and
+ *     downsample graphs; a negative linear value takes the linear branch -- unless SR_RESIZE_SRGB_SPACE is set in `flags`, when neither
+ *     is applied.  SR_PIXELS_RGBA8 input is byte / 255 with alpha ignored; SR_PIXELS_RGBA8 output is clamp(floor(255 v + 0.5)) with alpha
+ *     255.  SR_PIXELS_F32 is n x h x w x 3 f32.  The images of a batch do not see each other.  SR_FILTER_BOX from h x w to h/3 x w/3
+ *     (sizes divisible by 3) is the downsample graph, SR_FILTER_TRIANGLE to 3h x 3w the bilinear graph.
+ * sr_resize_dev: n images of h x w at d_in (in_pixels: an sr_pixels) -> n images of oh x ow at d_out (out_pixels), on any context (no
+ *   parameters are used).  Three launches on `stream`: the tap tables (computed on the device: no copy from the host), the horizontal and
+ *   the vertical pass; the tables and the f32 intermediate (n x h x ow pixels) live in a workspace of the context, grown on first use and
+ *   freed by sr_destroy.  Asynchronous and ordered on `stream` alone.  Both pointers 4-byte aligned; the images must not overlap.
+ * sr_resize_rgba8: the same from and to RGBA8 in host memory, synchronous: one upload, the device call on the context's stream, one download.
+ * sr_upscale_rgba8_sized_dev: the network's path of sr_upscale_f32_dev (members == 1) or sr_upscale_ensemble_f32_dev (any other mask) on
+ *   byte / 255 of the image, into a workspace buffer, then sr_resize_dev from that f32 image to RGBA8 of oh x ow: the result is quantised
+ *   once, after the resampling.  SR_GRAPH_SR_NET (factors 2-4) and SR_GRAPH_BILINEAR contexts.
+ * sr_upscale_rgba8_sized: the same on host memory, synchronous; in SR_PRECISION_SPLIT_F16 the whole call is computed again in exact f32
+ *   where a value left that mode's domain.  With sr_set_profiling on, sr_last_timing's total_ms is the network and the three launches of
+ *   the resampling, h2d / d2h the two copies.
+ * Refused with SR_E_INVALID before any launch, the output untouched: a null pointer; n, h, w, oh or ow below 1; sizes whose byte counts
+ * overflow; an unknown filter or pixel kind; a flag bit other than SR_RESIZE_SRGB_SPACE; d_in == d_out; a pointer that is not 4-byte
+ * aligned; SR_GRAPH_DOWNSAMPLE contexts, members == 0 or > 255 and members != 1 on a context other than SR_GRAPH_SR_NET (the _sized calls).
+ * A shape whose workspace does not fit is SR_E_NOMEM and leaves the context usable.  Cost: DESIGN.md 4n. */
+enum sr_filter { SR_FILTER_BOX = 0, SR_FILTER_TRIANGLE = 1, SR_FILTER_CATROM = 2, SR_FILTER_LANCZOS3 = 3 };
+enum sr_pixels { SR_PIXELS_RGBA8 = 0, SR_PIXELS_F32 = 1 };
+#define SR_RESIZE_SRGB_SPACE 1
+int sr_resize_dev(sr_ctx* ctx, const void* d_in, int in_pixels, int n, int h, int w, void* d_out, int out_pixels, int oh, int ow, int filter,
+                  unsigned flags, void* stream);
+int sr_resize_rgba8(sr_ctx* ctx, const uint8_t* in, int n, int h, int w, uint8_t* out, int oh, int ow, int filter, unsigned flags);
+int sr_upscale_rgba8_sized_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int h, int w, uint8_t* d_out_rgba, int oh, int ow, int filter,
+                               unsigned flags, unsigned members, void* stream);
+int sr_upscale_rgba8_sized(sr_ctx* ctx, const uint8_t* in_rgba, int n, int h, int w, uint8_t* out_rgba, int oh, int ow, int filter,
+                           unsigned flags, unsigned members);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

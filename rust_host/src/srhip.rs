@@ -171,6 +171,10 @@ extern "C" {
     pub fn sr_merge_alpha_rgba8_dev(ctx: *mut SrCtx, d_lr_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_rgba8_alpha_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, radius: c_int, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_rgba8_alpha(ctx: *mut SrCtx, in_rgba: *const u8, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, radius: c_int, members: c_uint) -> c_int;
+    pub fn sr_resize_dev(ctx: *mut SrCtx, d_in: *const c_void, in_pixels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut c_void, out_pixels: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_resize_rgba8(ctx: *mut SrCtx, input: *const u8, n: c_int, h: c_int, w: c_int, out: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint) -> c_int;
+    pub fn sr_upscale_rgba8_sized_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_rgba8_sized(ctx: *mut SrCtx, in_rgba: *const u8, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

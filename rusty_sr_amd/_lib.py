@@ -21,6 +21,9 @@ SR_TRAIN_RING = 64
 SR_ENSEMBLE_ALL, SR_ENSEMBLE_FLIPS, SR_ENSEMBLE_HFLIP = 0xFF, 0x0F, 0x03
 SR_ALPHA_BLEED_DEFAULT, SR_ALPHA_BLEED_MAX = 8, 16
 SR_ALPHA_BLEED_TILE = 32  # side of the bleed kernel's output tile (the tests put sizes on and across its seams)
+SR_FILTER_BOX, SR_FILTER_TRIANGLE, SR_FILTER_CATROM, SR_FILTER_LANCZOS3 = 0, 1, 2, 3
+SR_PIXELS_RGBA8, SR_PIXELS_F32 = 0, 1
+SR_RESIZE_SRGB_SPACE = 1
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -131,6 +134,10 @@ SYMBOLS = {
     "sr_merge_alpha_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "sr_upscale_rgba8_alpha_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, C.c_uint, _vp]),
     "sr_upscale_rgba8_alpha": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, C.c_uint]),
+    "sr_resize_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, C.c_uint, _vp]),
+    "sr_resize_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, _i, _i, C.c_uint]),
+    "sr_upscale_rgba8_sized_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
+    "sr_upscale_rgba8_sized": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, _i, _i, C.c_uint, C.c_uint]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

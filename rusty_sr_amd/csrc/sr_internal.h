@@ -127,6 +127,11 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     // ---- transparency (sr_alpha.cpp): grown on demand, freed by sr_destroy
     sr_buf d_ableed;                                // the bled copy of the caller's RGBA8 image
     size_t total_mem = 0;                           // the device's memory, asked for once: a shape beyond it is refused without an allocation
+    // ---- resampling to any size (sr_resize.cpp): grown on demand, freed by sr_destroy
+    sr_buf d_rtab;                                  // both axes' tap tables: first tap, tap count, weights (sr_resize_axis)
+    sr_buf d_rmid;                                  // the horizontal pass's output, n x h x ow x 3 f32
+    sr_buf d_rin;                                   // the _sized calls: byte / 255 of the caller's image, f32 RGB
+    sr_buf d_rnet;                                  // the _sized calls: the network's f32 output
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
 };
@@ -398,6 +403,30 @@ hipError_t sr_launch_alpha_bleed(const uint8_t* d_in, uint8_t* d_out, int n, int
 // byte 3 of the n images of factor h x factor w at d_out <- the alpha of d_lr (n x h x w RGBA8) interpolated; both 4-byte aligned
 hipError_t sr_launch_alpha_merge(int factor, const uint8_t* d_lr, uint8_t* d_out, int n, int h, int w, hipStream_t s);
 void sr_alpha_release(sr_ctx* c);  // free the bleed buffer (called by sr_destroy)
+
+// ---- resampling to any size (sr_resize.hip kernels, sr_resize.cpp host side; include/srhip.h "Resampling to any size")
+// One axis of a resampling, n_in -> n_out samples: the rule's constants (f64, from the host) and where its tables lie in device memory.
+// taps: the padded tap count, an upper bound of hi - lo over the axis; w is tap-major, w[k * n_out + o] (taps beyond an index's count: 0).
+struct sr_resize_axis {
+    int n_in, n_out, taps;
+    double scale, fs, reach;  // n_in / n_out, max(scale, 1), S fs
+    int* lo;
+    int* cnt;
+    float* w;
+};
+sr_resize_axis sr_resize_plan_axis(int n_in, int n_out, int filter);  // everything but the pointers
+// The horizontal pass's form for an axis: the input rows a workgroup takes; *cap_out > 0: the staged form, with that many pixels of each row
+// in LDS, 0: the direct form (a scale whose run under 256 columns does not fit).
+int sr_resize_h_form(const sr_resize_axis& x, int* cap_out);
+// workgroups of the two passes (0: an empty shape), functions of the shape alone; the launchers refuse more than INT32_MAX
+size_t sr_resize_h_blocks(size_t rows, const sr_resize_axis& x, unsigned* blocks_x_out = nullptr);
+size_t sr_resize_v_blocks(int n, int oh, int ow, unsigned* blocks_x_out = nullptr, unsigned* groups_out = nullptr);
+hipError_t sr_launch_resize_taps(const sr_resize_axis& x, const sr_resize_axis& y, int filter, hipStream_t s);
+// rows (= n h) rows of x.n_in pixels (RGBA8 or f32 RGB; linear: through SrgbToLinear) -> rows x x.n_out x 3 f32 at d_mid
+hipError_t sr_launch_resize_h(const void* d_in, bool in_u8, bool linear, size_t rows, const sr_resize_axis& x, float* d_mid, hipStream_t s);
+// n images of y.n_in x ow x 3 f32 at d_mid -> n images of y.n_out x ow (RGBA8 or f32 RGB; linear: through LinearToSrgb) at d_out
+hipError_t sr_launch_resize_v(const float* d_mid, int n, int ow, const sr_resize_axis& y, void* d_out, bool out_u8, bool linear, hipStream_t s);
+void sr_resize_release(sr_ctx* c);  // free the resampling buffers (called by sr_destroy)
 
 // ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)
 // One crop of a step, as the crop kernel reads it: px is device memory, 4-byte aligned when ch = 4 (rows are then read as whole pixels).

@@ -1,0 +1,216 @@
+// sr_resize.cpp -- resampling to any size (include/srhip.h "Resampling to any size"): sr_resize_* resample an image that is already in
+// device or host memory; sr_upscale_rgba8_sized* run the network with f32 output -- the path of sr_upscale_f32_dev or of the f32 ensemble,
+// untouched, on the caller's stream -- and resample that, so that the picture is quantised once, at its final size.  The reference has no
+// counterpart (main.rs:171-175 writes the factor's size).  Kernels: sr_resize.hip.
+//
+// Workspace of a context, all grown on first use and freed by sr_destroy: the tap tables of both axes (d_rtab), the horizontal pass's f32
+// output (d_rmid), and for the _sized calls the image as f32 (d_rin) and the network's f32 output (d_rnet).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "sr_internal.h"
+
+namespace {
+
+// a x b x c x d bytes, or false where that does not fit a size_t
+bool bytes_of(size_t a, size_t b, size_t c, size_t d, size_t* out) {
+    size_t v = 0;
+    return !__builtin_mul_overflow(a, b, &v) && !__builtin_mul_overflow(v, c, &v) && !__builtin_mul_overflow(v, d, out);
+}
+
+size_t pixel_bytes(int pixels) { return pixels == SR_PIXELS_RGBA8 ? 4 : 3 * sizeof(float); }
+
+// One resampling of n images h x w -> oh x ow: its two axes and what it needs of the workspace.
+struct ResizeJob {
+    int n = 0, h = 0, w = 0, oh = 0, ow = 0, filter = 0;
+    bool linear = true;
+    sr_resize_axis x{}, y{};
+    size_t tab_bytes = 0, mid_bytes = 0;
+};
+
+// everything sr_resize_* refuse for their arguments alone; *job is filled where they pass
+int plan_resize(const void* in, int in_pixels, int n, int h, int w, const void* out, int out_pixels, int oh, int ow, int filter, unsigned flags,
+                ResizeJob* job) {
+    if (!in || !out || n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1) return SR_E_INVALID;
+    if (filter < SR_FILTER_BOX || filter > SR_FILTER_LANCZOS3) return SR_E_INVALID;
+    if ((in_pixels != SR_PIXELS_RGBA8 && in_pixels != SR_PIXELS_F32) || (out_pixels != SR_PIXELS_RGBA8 && out_pixels != SR_PIXELS_F32)) return SR_E_INVALID;
+    if (flags & ~(unsigned)SR_RESIZE_SRGB_SPACE) return SR_E_INVALID;
+    if (in == out) return SR_E_INVALID;
+    size_t in_bytes = 0, out_bytes = 0, mid_bytes = 0;
+    if (!bytes_of(n, h, w, 3 * sizeof(float), &in_bytes) || !bytes_of(n, oh, ow, 3 * sizeof(float), &out_bytes) ||
+        !bytes_of(n, h, ow, 3 * sizeof(float), &mid_bytes))
+        return SR_E_INVALID;
+    job->n = n; job->h = h; job->w = w; job->oh = oh; job->ow = ow; job->filter = filter;
+    job->linear = !(flags & SR_RESIZE_SRGB_SPACE);
+    job->x = sr_resize_plan_axis(w, ow, filter);
+    job->y = sr_resize_plan_axis(h, oh, filter);
+    size_t wx = 0, wy = 0;
+    if (!bytes_of(job->x.taps, ow, sizeof(float), 1, &wx) || !bytes_of(job->y.taps, oh, sizeof(float), 1, &wy)) return SR_E_INVALID;
+    const size_t heads = 2 * sizeof(int) * ((size_t)ow + (size_t)oh);
+    if (__builtin_add_overflow(wx, wy, &job->tab_bytes) || __builtin_add_overflow(job->tab_bytes, heads, &job->tab_bytes)) return SR_E_INVALID;
+    job->mid_bytes = mid_bytes;
+    return SR_OK;
+}
+
+// The workspace of a job (and, for the _sized calls, in_bytes of d_rin and net_bytes of d_rnet beside it), all or nothing.  A shape that
+// can never fit is refused by arithmetic -- more than the device has at all, or a grid beyond what a launch takes -- before an allocation is
+// attempted; the context's device is current.
+int reserve(sr_ctx* c, ResizeJob& j, size_t in_bytes, size_t net_bytes) {
+    if (sr_resize_h_blocks((size_t)j.n * j.h, j.x) > (size_t)INT32_MAX || sr_resize_v_blocks(j.n, j.oh, j.ow) > (size_t)INT32_MAX)
+        return SR_E_NOMEM;
+    if (j.tab_bytes > c->d_rtab.cap || j.mid_bytes > c->d_rmid.cap || in_bytes > c->d_rin.cap || net_bytes > c->d_rnet.cap) {
+        if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
+        size_t all = 0;
+        if (__builtin_add_overflow(j.tab_bytes, j.mid_bytes, &all) || __builtin_add_overflow(all, in_bytes, &all) ||
+            __builtin_add_overflow(all, net_bytes, &all) || all > c->total_mem)
+            return SR_E_NOMEM;
+    }
+    SRCHK(sr_ensure_bufs(c, {{&c->d_rtab, j.tab_bytes}, {&c->d_rmid, j.mid_bytes}, {&c->d_rin, in_bytes}, {&c->d_rnet, net_bytes}}));
+    // the tables: [x.lo][x.cnt][y.lo][y.cnt][x.w][y.w]
+    int* p = (int*)c->d_rtab.p;
+    j.x.lo = p; j.x.cnt = p + j.ow;
+    j.y.lo = p + 2 * (size_t)j.ow; j.y.cnt = j.y.lo + j.oh;
+    j.x.w = (float*)(j.y.cnt + j.oh);
+    j.y.w = j.x.w + (size_t)j.x.taps * j.ow;
+    return SR_OK;
+}
+
+// the three launches of a reserved job on s
+int queue_resize(sr_ctx* c, const ResizeJob& j, const void* d_in, bool in_u8, void* d_out, bool out_u8, hipStream_t s) {
+    HIPCHK(c, sr_launch_resize_taps(j.x, j.y, j.filter, s));
+    HIPCHK(c, sr_launch_resize_h(d_in, in_u8, j.linear, (size_t)j.n * j.h, j.x, (float*)c->d_rmid.p, s));
+    HIPCHK(c, sr_launch_resize_v((const float*)c->d_rmid.p, j.n, j.ow, j.y, d_out, out_u8, j.linear, s));
+    return SR_OK;
+}
+
+// ---- the network, then the resampling
+
+struct SizedJob {
+    ResizeJob resize;  // of the network's output, fh x fw
+    size_t in_bytes = 0, net_bytes = 0;
+};
+
+// everything sr_upscale_rgba8_sized[_dev] refuse for their arguments alone
+int plan_sized(const sr_ctx* c, const void* in, const void* out, int n, int h, int w, int oh, int ow, int filter, unsigned flags, unsigned members,
+               SizedJob* job) {
+    if (!c || !in || !out || n < 1 || h < 1 || w < 1) return SR_E_INVALID;
+    if (c->graph != SR_GRAPH_SR_NET && c->graph != SR_GRAPH_BILINEAR) return SR_E_INVALID;
+    if (h > INT32_MAX / c->factor || w > INT32_MAX / c->factor) return SR_E_INVALID;
+    if (members == 0 || members > 255u) return SR_E_INVALID;
+    if (members != 1u && c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    const int fh = c->factor * h, fw = c->factor * w;
+    // (the resampling reads the workspace, never the caller's image: `in` stands in for its input so that in == out is refused here too)
+    SRCHK(plan_resize(in, SR_PIXELS_F32, n, fh, fw, out, SR_PIXELS_RGBA8, oh, ow, filter, flags, &job->resize));
+    if (!bytes_of(n, h, w, 3 * sizeof(float), &job->in_bytes) || !bytes_of(n, fh, fw, 3 * sizeof(float), &job->net_bytes)) return SR_E_INVALID;
+    return SR_OK;
+}
+
+// byte / 255 -> network (f32 out) -> resampling (RGBA8 out) on device buffers, queued on s; the context's device is current
+int queue_sized(sr_ctx* c, SizedJob& j, const uint8_t* d_in, int h, int w, uint8_t* d_out, unsigned members, hipStream_t s) {
+    const int n = j.resize.n;
+    SRCHK(reserve(c, j.resize, j.in_bytes, j.net_bytes));
+    // img_to_data on the device: the ensemble's input pass with the identity map, the batch as one image of n h rows
+    if ((size_t)n * h > (size_t)INT32_MAX) return SR_E_NOMEM;
+    const sr_ens_map same{n * h, w, 0, 0, 0};
+    if (sr_ens_blocks(same.DH, same.DW, false) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_ens_input(d_in, true, 4, c->d_rin.p, same, s));
+    const size_t in_img = (size_t)h * w * 3, out_img = (size_t)j.resize.h * j.resize.w * 3;  // floats
+    if (members == 1u) {
+        SRCHK(sr_run_stack_auto(c, c->d_rin.p, false, 3, n, h, w, 0, 0, c->d_rnet.p, false, s));
+    } else {
+        for (int i = 0; i < n; ++i)
+            SRCHK(sr_ensemble_queue(c, (const float*)c->d_rin.p + i * in_img, false, 3, h, w, (float*)c->d_rnet.p + i * out_img, false, members, s));
+    }
+    return queue_resize(c, j.resize, c->d_rnet.p, false, d_out, true, s);
+}
+
+}  // namespace
+
+sr_resize_axis sr_resize_plan_axis(int n_in, int n_out, int filter) {
+    sr_resize_axis a{};
+    const double support = filter == SR_FILTER_BOX ? 0.5 : filter == SR_FILTER_TRIANGLE ? 1.0 : filter == SR_FILTER_CATROM ? 2.0 : 3.0;
+    a.n_in = n_in;
+    a.n_out = n_out;
+    a.scale = (double)n_in / (double)n_out;
+    a.fs = std::max(a.scale, 1.0);
+    a.reach = support * a.fs;
+    // hi - lo = trunc(t + 2 reach) - trunc(t) <= floor(2 reach) + 1 for t >= 0 (a negative t is clipped to 0: fewer); one more for the
+    // rounding of t; never more than the axis has samples
+    a.taps = (int)std::min(std::floor(2.0 * a.reach) + 2.0, (double)n_in);
+    return a;
+}
+
+void sr_resize_release(sr_ctx* c) {
+    for (sr_buf* b : {&c->d_rtab, &c->d_rmid, &c->d_rin, &c->d_rnet}) sr_free_buf(*b);
+}
+
+extern "C" {
+
+int sr_resize_dev(sr_ctx* c, const void* d_in, int in_pixels, int n, int h, int w, void* d_out, int out_pixels, int oh, int ow, int filter,
+                  unsigned flags, void* stream) {
+    sr_plan_clear(c);
+    if (!c) return SR_E_INVALID;
+    ResizeJob j;
+    SRCHK(plan_resize(d_in, in_pixels, n, h, w, d_out, out_pixels, oh, ow, filter, flags, &j));
+    if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    SRCHK(reserve(c, j, 0, 0));
+    return queue_resize(c, j, d_in, in_pixels == SR_PIXELS_RGBA8, d_out, out_pixels == SR_PIXELS_RGBA8, (hipStream_t)stream);
+}
+
+int sr_resize_rgba8(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* out, int oh, int ow, int filter, unsigned flags) {
+    sr_plan_clear(c);
+    if (!c) return SR_E_INVALID;
+    ResizeJob j;
+    SRCHK(plan_resize(in, SR_PIXELS_RGBA8, n, h, w, out, SR_PIXELS_RGBA8, oh, ow, filter, flags, &j));
+    const size_t in_bytes = (size_t)n * h * w * pixel_bytes(SR_PIXELS_RGBA8), out_bytes = (size_t)n * oh * ow * pixel_bytes(SR_PIXELS_RGBA8);
+    return sr_host_call(
+        c, false, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) -> int {
+            SRCHK(reserve(c, j, 0, 0));
+            return queue_resize(c, j, c->d_in[0].p, true, c->d_out[0].p, true, s);
+        },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
+}
+
+int sr_upscale_rgba8_sized_dev(sr_ctx* c, const uint8_t* d_in, int n, int h, int w, uint8_t* d_out, int oh, int ow, int filter, unsigned flags,
+                               unsigned members, void* stream) {
+    sr_plan_clear(c);
+    SizedJob j;
+    SRCHK(plan_sized(c, d_in, d_out, n, h, w, oh, ow, filter, flags, members, &j));
+    if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    return queue_sized(c, j, d_in, h, w, d_out, members, (hipStream_t)stream);
+}
+
+int sr_upscale_rgba8_sized(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* out, int oh, int ow, int filter, unsigned flags,
+                           unsigned members) {
+    sr_plan_clear(c);
+    SizedJob j;
+    SRCHK(plan_sized(c, in, out, n, h, w, oh, ow, filter, flags, members, &j));
+    const size_t in_bytes = (size_t)n * h * w * 4, out_bytes = (size_t)n * oh * ow * 4;
+    return sr_host_call(
+        c, true, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
+            return SR_OK;
+        },
+        [&](hipStream_t s) { return queue_sized(c, j, (const uint8_t*)c->d_in[0].p, h, w, (uint8_t*)c->d_out[0].p, members, s); },
+        [&](hipStream_t s) -> int {
+            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
+            return SR_OK;
+        });
+}
+
+}  // extern "C"

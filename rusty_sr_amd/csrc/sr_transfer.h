@@ -8,6 +8,10 @@
 __device__ __forceinline__ float fast_pow(float x, float p) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(x)); }
 __device__ __forceinline__ float srgb_to_linear_fast(float s) { return s <= 0.04045f ? s / 12.92f : fast_pow((s + 0.055f) / 1.055f, 2.4f); }
 __device__ __forceinline__ float linear_to_srgb_fast(float l) { return l <= 0.0031308f ? 12.92f * l : 1.055f * fast_pow(l, 1.0f / 2.4f) - 0.055f; }
+// ... SrgbToLinear on the library's powf: the expression sr_aux.hip's lut_kernel tabulates for the 256 bytes (sr_resize.hip builds the same
+// table in LDS), and data_to_img (main.rs:175) of one value
+__device__ __forceinline__ float srgb_to_linear_powf(float s) { return s <= 0.04045f ? s / 12.92f : powf((s + 0.055f) / 1.055f, 2.4f); }
+__device__ __forceinline__ uint32_t quant_u8(float v) { return (uint32_t)fminf(fmaxf(floorf(255.0f * v + 0.5f), 0.0f), 255.0f); }
 
 // SrgbToLinear(s), correctly rounded to f32 but for inputs within ~1e-16 relative of a rounding boundary: the f64 formula
 // ((s + 0.055) / 1.055)^2.4, with the power as a^2 * y, y = (a^2)^(1/5) refined by two Newton steps from the hardware estimate

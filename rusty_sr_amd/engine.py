@@ -341,6 +341,102 @@ class Engine:
                                                       self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
+    # ---- resampling to any size: a separable resampler in Pillow's convention, on the device (include/srhip.h "Resampling to any size") ----
+    FILTERS = {"box": _lib.SR_FILTER_BOX, "triangle": _lib.SR_FILTER_TRIANGLE, "catrom": _lib.SR_FILTER_CATROM,
+               "lanczos3": _lib.SR_FILTER_LANCZOS3}
+    PIXELS = {"rgba8": _lib.SR_PIXELS_RGBA8, "f32": _lib.SR_PIXELS_F32}
+
+    @classmethod
+    def _resize_args(cls, size, filter, srgb_space):
+        """(oh, ow), the filter's number (a name of FILTERS, or the number itself) and the flags word of the sr_resize_* calls."""
+        oh, ow = (int(v) for v in size)
+        return oh, ow, cls.FILTERS[filter] if isinstance(filter, str) else int(filter), _lib.SR_RESIZE_SRGB_SPACE if srgb_space else 0
+
+    def resize_dev(self, x, size, out_pixels=None, filter="lanczos3", srgb_space=False, out=None, stream=None):
+        """sr_resize_dev: (n,H,W,4) u8 RGBA or (n,H,W,3) f32 on this GPU -> (n,oh,ow,4) u8 (alpha 255) or (n,oh,ow,3) f32, size = (oh, ow).
+        out_pixels: "rgba8" or "f32" (default: the input's kind, or `out`'s)."""
+        import torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 4
+        in_u8 = x.dtype == torch.uint8
+        assert (in_u8 and x.shape[-1] == 4) or (x.dtype == torch.float32 and x.shape[-1] == 3)
+        n, h, w, _ = x.shape
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        if out_pixels is None:
+            out_pixels = ("rgba8" if out.dtype == torch.uint8 else "f32") if out is not None else ("rgba8" if in_u8 else "f32")
+        out_u8 = self.PIXELS[out_pixels] == _lib.SR_PIXELS_RGBA8
+        if out is None and oh >= 1 and ow >= 1:
+            out = torch.empty((n, oh, ow, 4 if out_u8 else 3), dtype=torch.uint8 if out_u8 else torch.float32, device=x.device)
+        _lib.check(self._L.sr_resize_dev(self._ctx, C.c_void_p(x.data_ptr()), _lib.SR_PIXELS_RGBA8 if in_u8 else _lib.SR_PIXELS_F32, n, h, w,
+                                         C.c_void_p(out.data_ptr() if out is not None else None), self.PIXELS[out_pixels], oh, ow, flt, flags,
+                                         self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def resize(self, img, size, filter="lanczos3", srgb_space=False, out=None):
+        """(n,H,W,4) or (H,W,4) u8 RGBA -> u8 RGBA (sr_resize_rgba8), or (n,H,W,3) or (H,W,3) f32 -> f32 (through sr_resize_dev), numpy in
+        and out, resampled to size = (oh, ow)."""
+        img = np.ascontiguousarray(img)
+        squeeze = img.ndim == 3
+        if squeeze:
+            img = img[None]
+        n, h, w, c = img.shape
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        if img.dtype == np.uint8:
+            if c != 4:
+                raise ValueError("expected 4 channels")
+            if out is None:
+                out = np.empty((n, max(oh, 0), max(ow, 0), 4), dtype=np.uint8)
+            elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
+                raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
+            else:
+                out = out.reshape(n, oh, ow, 4)
+            u8p = C.POINTER(C.c_uint8)
+            _lib.check(self._L.sr_resize_rgba8(self._ctx, img.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), oh, ow, flt, flags), self._ctx)
+        else:
+            import torch
+            if img.dtype != np.float32 or c != 3:
+                raise ValueError("expected u8 RGBA or f32 RGB")
+            res = self.resize_dev(torch.from_numpy(img).to(f"cuda:{self.device}"), (oh, ow), "f32", flt, srgb_space).cpu().numpy()
+            if out is not None:
+                out = out.reshape(res.shape)
+                out[...] = res
+            else:
+                out = res
+        return out[0] if squeeze else out
+
+    def upscale_rgba8_sized(self, px: np.ndarray, size, filter="lanczos3", srgb_space=False, members: int = 1, out: np.ndarray = None) -> np.ndarray:
+        """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) to size = (oh, ow): (n,H,W,4) or (H,W,4) u8 -> (n,oh,ow,4)
+        u8, the network's f32 output resampled on the device and quantised once."""
+        px = np.ascontiguousarray(px, dtype=np.uint8)
+        squeeze = px.ndim == 3
+        if squeeze:
+            px = px[None]
+        n, h, w, c = px.shape
+        if c != 4:
+            raise ValueError("expected 4 channels")
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        if out is None:
+            out = np.empty((n, max(oh, 0), max(ow, 0), 4), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
+        else:
+            out = out.reshape(n, oh, ow, 4)
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_upscale_rgba8_sized(self._ctx, px.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), oh, ow, flt, flags,
+                                                  self._members(members)), self._ctx)
+        return out[0] if squeeze else out
+
+    def upscale_rgba8_sized_dev(self, px, size, filter="lanczos3", srgb_space=False, members: int = 1, out=None, stream=None):
+        import torch
+        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
+        n, h, w, _ = px.shape
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        if out is None and oh >= 1 and ow >= 1:
+            out = torch.empty((n, oh, ow, 4), dtype=torch.uint8, device=px.device)
+        _lib.check(self._L.sr_upscale_rgba8_sized_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w,
+                                                      C.c_void_p(out.data_ptr() if out is not None else None), oh, ow, flt, flags,
+                                                      self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
     def upscale_band_f32_dev(self, x_ext, halo_top, halo_bot, out=None, stream=None):
         """x_ext: (h_ext,W,3) f32 rows = halo_top + band + halo_bot -> (3*band,3W,3)."""
         import torch

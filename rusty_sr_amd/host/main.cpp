@@ -13,7 +13,8 @@
 // TIFF, TGA, ICO, PPM/PGM/PBM, BMP in; PNG, JPEG, BMP, PPM out by extension -- of what the reference's `image` crate reads
 // only WebP is missing), and extra options that cannot collide with the reference's: --device N, --precision f32|split_f16,
 // --timing, --ensemble 2|4|8 (upscale and validate: the network averaged over flips / rotations), --alpha [--bleed N] (upscale: the alpha
-// channel is kept -- colours bled under the transparent pixels, alpha interpolated; PNG output only); for `train` --seed N (initial
+// channel is kept -- colours bled under the transparent pixels, alpha interpolated; PNG output only), --size WxH | --scale S [--filter F]
+// [--resize-space linear|srgb] (upscale: the network's f32 output resampled to that size on the GPU, quantised once); for `train` --seed N (initial
 // parameters, shuffles and crops are seeded; the reference's are random), --augment (each crop under a random one of the 8 flips and
 // rotations, applied by the crop kernel) and --steps N (stop
 // early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
@@ -67,7 +68,15 @@ const char* kUsage =
     "        --precision <MODE>           f32 (exact) or split_f16 (2x faster, same 1e-4 parity bar) [default: f32]\n"
     "        --ensemble <N>               average the network over N flips / rotations of the image: 2 (mirror), 4 (flips)\n"
     "                                     or 8 (flips and rotations); N passes for slightly better pixels\n"
-    "        --bleed <N>                  with --alpha: how many pixels the colours are bled outward, 0..16 [default: 8]\n\n"
+    "        --bleed <N>                  with --alpha: how many pixels the colours are bled outward, 0..16 [default: 8]\n"
+    "        --size <WxH>                 write exactly W x H pixels: the network's output is resampled on the GPU before it\n"
+    "                                     is quantised (each axis 1..16384)\n"
+    "        --scale <S>                  the same with W x H = the INPUT's size times S, rounded (a positive decimal: 1.5, 2,\n"
+    "                                     0.5), whatever the factor of the weights\n"
+    "        --filter <FILTER>            with --size / --scale: the resampling filter [values: box, triangle, catrom,\n"
+    "                                     lanczos3] [default: lanczos3]\n"
+    "        --resize-space <SPACE>       with --size / --scale: resample in linear light or on the sRGB values [values:\n"
+    "                                     linear, srgb] [default: linear]\n\n"
     "ARGS:\n    <INPUT_FILE>     Sets the input image to upscale\n    <OUTPUT_FILE>    Sets the output file to write/overwrite (.png recommended)\n\n"
     "SUBCOMMANDS:\n    train       Trains a new set of neural network parameters on the GPU (rusty_sr train --help)\n"
     "    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
@@ -118,6 +127,41 @@ std::vector<float> decode_rsr(const unsigned char* blob, size_t len) {
 // --ensemble 2|4|8 -> the member mask of sr_upscale_ensemble_* (0: not a valid value)
 unsigned ensemble_mask(const std::string& v) {
     return v == "2" ? SR_ENSEMBLE_HFLIP : v == "4" ? SR_ENSEMBLE_FLIPS : v == "8" ? SR_ENSEMBLE_ALL : 0u;
+}
+
+// ---- --size <WxH> / --scale <S>: the output size of the resampled call (sr_upscale_rgba8_sized)
+constexpr int kMaxOutputAxis = 16384;
+
+// "WxH", two whole numbers 1 .. kMaxOutputAxis
+bool parse_size(const std::string& v, int& w, int& h) {
+    const size_t x = v.find_first_of("xX");
+    if (x == std::string::npos || x == 0 || x + 1 >= v.size()) return false;
+    const char* b = v.data();
+    const auto rw = std::from_chars(b, b + x, w), rh = std::from_chars(b + x + 1, b + v.size(), h);
+    return rw.ec == std::errc() && rw.ptr == b + x && rh.ec == std::errc() && rh.ptr == b + v.size() && w >= 1 && h >= 1 &&
+           w <= kMaxOutputAxis && h <= kMaxOutputAxis;
+}
+
+// a positive decimal: digits with at most one point, no sign, no exponent
+bool parse_scale(const std::string& v, double& s) {
+    if (v.empty() || v.size() > 32) return false;
+    int digits = 0, points = 0;
+    for (const char ch : v) {
+        if (isdigit((unsigned char)ch)) ++digits;
+        else if (ch == '.') ++points;
+        else return false;
+    }
+    if (!digits || points > 1) return false;
+    s = strtod(v.c_str(), nullptr);
+    return std::isfinite(s) && s > 0;
+}
+
+// one axis of --scale: max(1, floor(in S + 0.5)); false above kMaxOutputAxis
+bool scaled_axis(int in, double s, int& out) {
+    const double v = std::max(1.0, std::floor((double)in * s + 0.5));
+    if (v > kMaxOutputAxis) return false;
+    out = (int)v;
+    return true;
 }
 
 // Rust's `{}` of an f32: the shortest digits that read back as the same float, never an exponent; inf / NaN as Rust spells them
@@ -879,6 +923,12 @@ int main(int argc, char** argv) {
     unsigned ensemble = 0;  // 0: one pass of the network
     bool alpha = false, has_bleed = false;
     int bleed = SR_ALPHA_BLEED_DEFAULT;
+    // --size / --scale: the output is resampled to a size of the user's choosing (sr_upscale_rgba8_sized)
+    bool has_size = false, has_scale = false, has_filter = false, has_space = false;
+    std::string size_arg, scale_arg;
+    int size_w = 0, size_h = 0, filter = SR_FILTER_LANCZOS3;
+    double scale = 0;
+    unsigned resize_flags = 0;
     std::vector<int> devices;
     if (argc >= 2 && !strcmp(argv[1], "train")) return run_train(argc, argv);  // main.rs:119-121
     if (argc >= 2 && !strcmp(argv[1], "validate")) return run_validate(argc, argv);
@@ -919,6 +969,29 @@ int main(int argc, char** argv) {
                 usage_error("'" + v + "' isn't a valid value for '--bleed <N>'\n\t[values: 0..16]");
             has_bleed = true;
         }
+        else if (a == "--size" || a.rfind("--size=", 0) == 0) {
+            size_arg = a == "--size" ? value("--size <WxH>") : a.substr(7);
+            if (!parse_size(size_arg, size_w, size_h))
+                usage_error("'" + size_arg + "' isn't a valid value for '--size <WxH>'\n\t[two whole numbers, 1..16384 each: 3840x2160]");
+            has_size = true;
+        }
+        else if (a == "--scale" || a.rfind("--scale=", 0) == 0) {
+            scale_arg = a == "--scale" ? value("--scale <S>") : a.substr(8);
+            if (!parse_scale(scale_arg, scale)) usage_error("'" + scale_arg + "' isn't a valid value for '--scale <S>'\n\t[a positive decimal: 1.5]");
+            has_scale = true;
+        }
+        else if (a == "--filter" || a.rfind("--filter=", 0) == 0) {
+            const std::string v = a == "--filter" ? value("--filter <FILTER>") : a.substr(9);
+            filter = v == "box" ? SR_FILTER_BOX : v == "triangle" ? SR_FILTER_TRIANGLE : v == "catrom" ? SR_FILTER_CATROM : v == "lanczos3" ? SR_FILTER_LANCZOS3 : -1;
+            if (filter < 0) usage_error("'" + v + "' isn't a valid value for '--filter <FILTER>'\n\t[values: box, catrom, lanczos3, triangle]");
+            has_filter = true;
+        }
+        else if (a == "--resize-space" || a.rfind("--resize-space=", 0) == 0) {
+            const std::string v = a == "--resize-space" ? value("--resize-space <SPACE>") : a.substr(15);
+            if (v != "linear" && v != "srgb") usage_error("'" + v + "' isn't a valid value for '--resize-space <SPACE>'\n\t[values: linear, srgb]");
+            resize_flags = v == "srgb" ? SR_RESIZE_SRGB_SPACE : 0u;
+            has_space = true;
+        }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
@@ -950,6 +1023,19 @@ int main(int argc, char** argv) {
         if (ext != "png")
             usage_error("The argument '--alpha' cannot be used with an output file other than .png: JPEG, BMP and PPM carry no alpha channel");
     }
+    // --size / --scale: one of them; the resampled call has no downsampling, no alpha-aware and no multi-GPU form
+    const bool resize = has_size || has_scale;
+    if (has_size && has_scale) usage_error("The argument '--size <WxH>' cannot be used with '--scale <S>'");
+    if ((has_filter || has_space) && !resize) usage_error("The following required arguments were not provided:\n    <--size <WxH>|--scale <S>>");
+    const std::string resize_opt = has_size ? "--size <WxH>" : "--scale <S>";
+    if (resize && downsample) usage_error("The argument '" + resize_opt + "' cannot be used with '--downsample'");
+    if (resize && alpha) usage_error("The argument '" + resize_opt + "' cannot be used with '--alpha': the resampling is not alpha-aware");
+    if (resize && devices.size() > 1)
+        usage_error("The argument '" + resize_opt + "' cannot be used with more than one device: the resampled call has no multi-GPU form");
+    int in_pw = 0, in_ph = 0;
+    // (the file's header says how large the input is: a scale that takes it beyond the largest output is refused before any device is touched)
+    if (has_scale && srpng::probe_image_size(pos[0], in_pw, in_ph) && !(scaled_axis(in_pw, scale, size_w) && scaled_axis(in_ph, scale, size_h)))
+        usage_error("'" + scale_arg + "' isn't a valid value for '--scale <S>'\n\t[the output would exceed 16384 pixels on an axis]");
 
     // ---- parameters + graph (main.rs:133-158), same progress text
     std::vector<float> params;
@@ -1014,7 +1100,10 @@ int main(int argc, char** argv) {
     const bool sized = srpng::probe_image_size(pos[0], pw, ph) && !(graph == SR_GRAPH_DOWNSAMPLE && (pw < 3 || ph < 3));
     std::thread pinner([&] {
         if (!sized) return;
-        const size_t bytes = graph == SR_GRAPH_DOWNSAMPLE ? (size_t)(pw / 3) * (ph / 3) * 4 : (size_t)pw * 3 * ph * 3 * 4;
+        int sw = 0, sh = 0;
+        if (has_scale && !(scaled_axis(pw, scale, sw) && scaled_axis(ph, scale, sh))) return;
+        const size_t bytes = has_size ? (size_t)size_w * size_h * 4 : has_scale ? (size_t)sw * sh * 4
+                             : graph == SR_GRAPH_DOWNSAMPLE ? (size_t)(pw / 3) * (ph / 3) * 4 : (size_t)pw * 3 * ph * 3 * 4;
         if (sr_host_alloc(&pinned, bytes) == SR_OK) pinned_bytes = bytes; else pinned = nullptr;
     });
     std::vector<sr_ctx*> ctxs(devices.size(), nullptr);
@@ -1022,13 +1111,13 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < devices.size() && rc == SR_OK; ++k) {
         rc = sr_create_graph(&ctxs[k], graph, params.empty() ? nullptr : params.data(), params.size(), SR_FACTOR, devices[k]);
         if (rc == SR_OK && graph == SR_GRAPH_SR_NET) rc = sr_set_precision(ctxs[k], precision == "f32" ? SR_PRECISION_F32 : SR_PRECISION_SPLIT_F16);
-        if (rc == SR_OK && (ensemble || alpha) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble and alpha calls time themselves only when asked to)
+        if (rc == SR_OK && (ensemble || alpha || resize) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble, alpha and resampled calls time themselves only when asked to)
     }
     const double t_create = ms_since(t_start);
     double t_prep = 0;
     {
         const clk::time_point t = clk::now();
-        if (rc == SR_OK && sized && ctxs.size() == 1) (void)sr_reserve_rgba8(ctxs[0], 4, 1, ph, pw);  // best effort: the real call reports errors
+        if (rc == SR_OK && sized && ctxs.size() == 1 && !resize) (void)sr_reserve_rgba8(ctxs[0], 4, 1, ph, pw);  // best effort: the real call reports errors
         pinner.join();
         t_prep = ms_since(t);
     }
@@ -1039,7 +1128,10 @@ int main(int argc, char** argv) {
     const double t_ready = ms_since(t_start);
     if (graph == SR_GRAPH_DOWNSAMPLE && (in.w < 3 || in.h < 3)) die("input image is smaller than one 3x3 pooling block");
 
-    const int ow = graph == SR_GRAPH_DOWNSAMPLE ? in.w / 3 : in.w * 3, oh = graph == SR_GRAPH_DOWNSAMPLE ? in.h / 3 : in.h * 3;
+    if (has_scale && !(scaled_axis(in.w, scale, size_w) && scaled_axis(in.h, scale, size_h)))  // (a file whose header could not be probed)
+        usage_error("'" + scale_arg + "' isn't a valid value for '--scale <S>'\n\t[the output would exceed 16384 pixels on an axis]");
+    const int ow = resize ? size_w : graph == SR_GRAPH_DOWNSAMPLE ? in.w / 3 : in.w * 3;
+    const int oh = resize ? size_h : graph == SR_GRAPH_DOWNSAMPLE ? in.h / 3 : in.h * 3;
     // page-locked output pixels: the download then runs at PCIe rate under the kernels of the next band
     const size_t out_bytes = (size_t)ow * oh * 4;
     const clk::time_point t_al = clk::now();
@@ -1050,7 +1142,8 @@ int main(int argc, char** argv) {
     // img_to_data + graph.forward + data_to_img(..).to_rgba(), fused on the device (main.rs:168-175)
     const double t_alloc = ms_since(t_al);
     const clk::time_point t_up = clk::now();
-    rc = alpha ? sr_upscale_rgba8_alpha(ctx, in.rgba.data(), 1, in.h, in.w, out, bleed, ensemble ? ensemble : 1u)
+    rc = resize ? sr_upscale_rgba8_sized(ctx, in.rgba.data(), 1, in.h, in.w, out, oh, ow, filter, resize_flags, ensemble ? ensemble : 1u)
+         : alpha ? sr_upscale_rgba8_alpha(ctx, in.rgba.data(), 1, in.h, in.w, out, bleed, ensemble ? ensemble : 1u)
          : ensemble ? sr_upscale_ensemble_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out, ensemble)
          : ctxs.size() > 1 ? sr_upscale_rgba8_multi(ctxs.data(), (int)ctxs.size(), in.rgba.data(), 4, in.h, in.w, out)
                            : sr_upscale_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out);
