@@ -623,6 +623,63 @@ int sr_upscale_rgba8_sized_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int
 int sr_upscale_rgba8_sized(sr_ctx* ctx, const uint8_t* in_rgba, int n, int h, int w, uint8_t* out_rgba, int oh, int ow, int filter,
                            unsigned flags, unsigned members);
 
+/* ---- Degradation: blur, noise and JPEG made on the device ----
+ * The reference trains for one degradation, the f x f mean of linear-light pixels; the pair calls above take any LR image, but made by
+ * someone else, once.  Modern training recipes synthesise the LR crop from the HR crop at every draw, each with its own blur width, noise
+ * level and JPEG quality: this operator does that on the device.  UNPINNED: the reference has no counterpart; tests/degrade_ref.py restates
+ * the rule in numpy (f64), and the kernels are held to it byte for byte.
+ *   A call names an image (h x w, 3 or 4 channels, alpha dropped), a factor f (2, 3 or 4), a member k (0..7, T_k of the self-ensemble) and
+ *   a frame: frame_h x frame_w HR pixels, multiples of f, at (y0, x0).  As in sr_train_step_aug the frame is T_k(W), W the source window at
+ *   (y0, x0) -- frame_h x frame_w pixels for k < 4, frame_w x frame_h (rows x columns) for k >= 4.  Frame pixel (p, q) is defined for ANY
+ *   integers p, q by the same mapping (p' = frame_h - 1 - p if k & 2, q' = frame_w - 1 - q if k & 1; source pixel (y0 + p', x0 + q'), or
+ *   (y0 + q', x0 + p') if k & 4): the image's RGB byte inside the image, 0 outside, so the blur sees the true neighbours beyond the
+ *   frame's edge.  Origins may be negative or overhang.  The output is the LR frame, frame_h / f x frame_w / f x 3 bytes.
+ *   All arithmetic is f64.  Every rounding to an integer is R(v) = sign(v) floor(|v| + 0.5 + 2^-30): with integer pixels exact ties are
+ *   structural (a DC coefficient is k / 8 over an integer table entry), and the bias keeps them off the boundary.
+ *   1. Linearise: SrgbToLinear(byte / 255), s <= 0.04045 ? s / 12.92 : pow((s + 0.055) / 1.055, 2.4), a 256-entry table made on the host.
+ *   2. Blur (sigma > 0): separable Gaussian in linear light over the frame, radius ceil(3 sigma), weights exp(-d^2 / (2 sigma^2)) divided
+ *      by their sum (taken in tap order); rows first (along q), then columns; sums in tap order.
+ *   3. Pool: the mean of each f x f block, summed in row-major order, divided by f^2.
+ *   4. Encode: v = 255 LinearToSrgb(mean), l <= 0.0031308 ? 12.92 l : 1.055 pow(l, 1 / 2.4) - 0.055.
+ *   5. Noise (noise > 0, in 8-bit levels): value index i = (y lw + x) 3 + c in the LR frame; x1, x2 are outputs number 2i + 1 and 2i + 2
+ *      of the SplitMix64 stream seeded with `seed` (output j = mix(seed + j 0x9E3779B97F4A7C15), the generator of sr_init_params);
+ *      u = (x >> 11) 2^-53;  v += noise sqrt(-2 ln(1 - u1)) cos(2 pi u2).
+ *   6. Quantise: b = clamp(R(v), 0, 255).
+ *   7. JPEG round trip (quality 1..100; 0 skips it), 4:4:4: 8 x 8 blocks anchored at the LR frame's origin, ragged edges padded by
+ *      replicating the last row / column.  Y = 0.299 R + 0.587 G + 0.114 B, Cb = 128 - 0.168735892 R - 0.331264108 G + 0.5 B,
+ *      Cr = 128 + 0.5 R - 0.418687589 G - 0.081312411 B, each clamp(R(.), 0, 255) - 128.  coef = C b C^T with the orthonormal DCT-II
+ *      C[u][x] = cos((2x + 1) u pi / 16) / 2, row 0 divided by sqrt 2 (C b first; sums in index order).  Tables: Annex K's luma / chroma
+ *      tables, scale = q < 50 ? 5000 / q : 200 - 2 q, t = clamp((base scale + 50) / 100, 1, 255) in integers.  qz = R(coef / t); the
+ *      inverse transform of qz t (C^T first), + 128, R() and clamp; R = Y + 1.402 (Cr - 128), G = Y - 0.344136286 (Cb - 128) -
+ *      0.714136286 (Cr - 128), B = Y + 1.772 (Cb - 128), R() and clamp.
+ *   With sigma = noise = quality = 0 the result is the 8-bit quantisation of the pooled calls' input.  sigma and noise are f32 in the
+ *   struct and are widened to f64 as they are.
+ * sr_degrade_rgba8: host memory, synchronous: one upload, one launch on the context's stream, one download.  Any graph's context will do;
+ *   no network runs.
+ * sr_degrade_rgba8_dev: device memory, asynchronous and ordered on `stream` alone; both pointers may start at any byte.
+ * Refused with SR_E_INVALID before any launch, the output untouched: a null pointer, in_channels other than 3 or 4, h or w below 1, a
+ *   factor outside 2..4, frame sizes that are not multiples of f or are below f, a member above 7, sigma outside [0, SR_DEGRADE_MAX_SIGMA],
+ *   noise outside [0, SR_DEGRADE_MAX_NOISE], quality outside 0..100.
+ * sr_train_step_degrade: a step of a plain-image session (sr_train_step_aug's items, members and rules) whose network input is the
+ *   degraded crop: item i of the u8 HR batch is T_k of its window, as in sr_train_step_aug, and the network's input is the operator's
+ *   output for the same window, member and deg[i], as byte / 255 -- what sr_train_step_pairs_aug computes from that LR / HR pair, bit
+ *   for bit.  One launch cuts the HR crops and degrades them straight into the backward pass's input: crop, the backward pass's 15
+ *   launches, Adam; no extra launch, no host work.  crop_h and crop_w must be multiples of the session's factor.  A transient item stages
+ *   the rows its window and its blur radius can reach.  The ring, drain, staging and SR_E_NOMEM rules are those of sr_train_step. */
+#define SR_DEGRADE_MAX_SIGMA 4
+#define SR_DEGRADE_MAX_NOISE 64
+typedef struct sr_degrade {
+    float sigma;    /* Gaussian blur, HR pixels; 0: none */
+    float noise;    /* standard deviation of the noise, 8-bit levels; 0: none */
+    int quality;    /* JPEG quality 1..100; 0: no JPEG */
+    uint64_t seed;  /* of the noise stream */
+} sr_degrade;
+int sr_degrade_rgba8(sr_ctx* ctx, const uint8_t* hr, int in_channels, int h, int w, int factor, int y0, int x0, int frame_h, int frame_w,
+                     int member, const sr_degrade* deg, uint8_t* lr_rgb);
+int sr_degrade_rgba8_dev(sr_ctx* ctx, const uint8_t* d_hr, int in_channels, int h, int w, int factor, int y0, int x0, int frame_h, int frame_w,
+                         int member, const sr_degrade* deg, uint8_t* d_lr_rgb, void* stream);
+int sr_train_step_degrade(sr_train* t, const sr_train_crop* items, const uint8_t* members, const sr_degrade* deg, int n, int crop_h, int crop_w);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

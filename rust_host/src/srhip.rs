@@ -52,6 +52,16 @@ pub struct SrMetrics {
     pub ssim_count: u64,
 }
 
+/// `sr_degrade`: one item's blur width (HR pixels), noise level (8-bit levels), JPEG quality (0: none) and noise seed.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrDegrade {
+    pub sigma: f32,
+    pub noise: f32,
+    pub quality: c_int,
+    pub seed: u64,
+}
+
 pub const SR_OK: c_int = 0;
 pub const SR_E_HIP: c_int = -5;
 pub const SR_GRAPH_SR_NET: c_int = 0;
@@ -175,6 +185,9 @@ extern "C" {
     pub fn sr_resize_rgba8(ctx: *mut SrCtx, input: *const u8, n: c_int, h: c_int, w: c_int, out: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint) -> c_int;
     pub fn sr_upscale_rgba8_sized_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_rgba8_sized(ctx: *mut SrCtx, in_rgba: *const u8, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
+    pub fn sr_degrade_rgba8(ctx: *mut SrCtx, hr: *const u8, in_channels: c_int, h: c_int, w: c_int, factor: c_int, y0: c_int, x0: c_int, frame_h: c_int, frame_w: c_int, member: c_int, deg: *const SrDegrade, lr_rgb: *mut u8) -> c_int;
+    pub fn sr_degrade_rgba8_dev(ctx: *mut SrCtx, d_hr: *const u8, in_channels: c_int, h: c_int, w: c_int, factor: c_int, y0: c_int, x0: c_int, frame_h: c_int, frame_w: c_int, member: c_int, deg: *const SrDegrade, d_lr_rgb: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sr_train_step_degrade(t: *mut SrTrain, items: *const SrTrainCrop, members: *const u8, deg: *const SrDegrade, n: c_int, crop_h: c_int, crop_w: c_int) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

@@ -6,5 +6,6 @@ from .engine import (  # noqa: F401
     CHANNELS, FACTOR, DataShape, Engine, Graph, NodeData, Trainer, bilinear_net, downsample_net, img_to_data, init_params, sr_net,
     comm_init_all, upscale_batch_multi, upscale_multi, upscale_sharded_all, validation_psnr,
     aggregate_metrics, metrics_from_bytes, ssim_mean, validation_metrics, y_psnr,
+    degrade_draws, parse_degrade_spec,
 )
 from ._lib import SrError  # noqa: F401

@@ -24,6 +24,7 @@ SR_ALPHA_BLEED_TILE = 32  # side of the bleed kernel's output tile (the tests pu
 SR_FILTER_BOX, SR_FILTER_TRIANGLE, SR_FILTER_CATROM, SR_FILTER_LANCZOS3 = 0, 1, 2, 3
 SR_PIXELS_RGBA8, SR_PIXELS_F32 = 0, 1
 SR_RESIZE_SRGB_SPACE = 1
+SR_DEGRADE_MAX_SIGMA, SR_DEGRADE_MAX_NOISE = 4, 64
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -37,6 +38,11 @@ class TrainPairCrop(C.Structure):
     """sr_train_pair_crop (include/srhip.h): a resident pair id, or -1 and both images' host pixels; the crop origin in LR pixels."""
     _fields_ = [("pair", C.c_int), ("lr_px", C.c_void_p), ("hr_px", C.c_void_p), ("lr_channels", C.c_int), ("hr_channels", C.c_int),
                 ("lh", C.c_int), ("lw", C.c_int), ("y0", C.c_int), ("x0", C.c_int)]
+
+
+class Degrade(C.Structure):
+    """sr_degrade (include/srhip.h): one item's blur width, noise level, JPEG quality and noise seed."""
+    _fields_ = [("sigma", C.c_float), ("noise", C.c_float), ("quality", C.c_int), ("seed", C.c_uint64)]
 
 
 class Metrics(C.Structure):
@@ -138,6 +144,9 @@ SYMBOLS = {
     "sr_resize_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, _i, _i, C.c_uint]),
     "sr_upscale_rgba8_sized_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
     "sr_upscale_rgba8_sized": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, _i, _i, C.c_uint, C.c_uint]),
+    "sr_degrade_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Degrade), _u8p]),
+    "sr_degrade_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Degrade), _vp, _vp]),
+    "sr_train_step_degrade": (_i, [_vp, C.POINTER(TrainCrop), _u8p, C.POINTER(Degrade), _i, _i, _i]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -132,6 +132,8 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     sr_buf d_rmid;                                  // the horizontal pass's output, n x h x ow x 3 f32
     sr_buf d_rin;                                   // the _sized calls: byte / 255 of the caller's image, f32 RGB
     sr_buf d_rnet;                                  // the _sized calls: the network's f32 output
+    // ---- degradation (sr_degrade.cpp): uploaded on first use, freed by sr_destroy
+    double* d_dtab = nullptr;                       // 320 doubles: SrgbToLinear(byte / 255), then the 8 x 8 DCT matrix
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
 };
@@ -460,3 +462,29 @@ hipError_t sr_launch_train_crop(const sr_train_crop_args& a, uint32_t* d_out, hi
 // the n HR crops (f crop_lh x f crop_lw) -> u8 at d_out as above, and the n LR crops -> n x crop_lh x crop_lw x 3 f32 (byte / 255, d_tab)
 // at d_x, which is 16-byte aligned and holds whole 16-byte groups
 hipError_t sr_launch_train_pair_crop(int factor, sr_train_pair_args a, uint32_t* d_out, float* d_x, const float* d_tab, hipStream_t s);
+
+// ---- degradation (sr_degrade.hip kernels, sr_degrade.cpp host side; include/srhip.h "Degradation")
+// One call of the operator: the source image as the crop kernels read it (d.k: the member, d.y0 / d.x0: the frame's origin), its parameters,
+// the factor and the frame's size in HR pixels.
+struct sr_degrade_one {
+    sr_train_crop_desc d;
+    sr_degrade g;
+    int f, frame_h, frame_w;
+};
+struct sr_train_degrade_args {  // a degraded step's gather, passed by value like sr_train_crop_args
+    sr_train_crop_desc d[SR_TRAIN_MAX_BATCH];
+    sr_degrade g[SR_TRAIN_MAX_BATCH];
+    int n, crop_h, crop_w, f;
+    int hr_blocks;  // set by the launcher: blocks of a grid row that cut the HR crop
+};
+static_assert(sizeof(sr_degrade) == 24 && sizeof(sr_train_degrade_args) <= 4096 - 4 * sizeof(void*), "one kernel's arguments");
+int sr_degrade_check(const sr_degrade& g);  // SR_E_INVALID for parameters out of range
+int sr_degrade_radius(const sr_degrade& g);  // ceil(3 sigma): the HR pixels the blur reaches beyond a frame
+int sr_degrade_ensure_table(sr_ctx* c);     // the 320 doubles behind d_dtab, uploaded on first use; the context's device is current
+void sr_degrade_release(sr_ctx* c);         // free it (called by sr_destroy)
+// the LR frame of a.d's window -> frame_h / f x frame_w / f x 3 bytes at d_out (any byte offset); d_tab: the context's d_dtab
+hipError_t sr_launch_degrade(const sr_degrade_one& a, const double* d_tab, uint8_t* d_out, hipStream_t s);
+// the n HR crops -> u8 at d_batch as sr_launch_train_crop stores them, and their degraded LR frames -> n x crop_h / f x crop_w / f x 3 f32
+// (byte / 255, d_ftab's first 256 floats) at d_x
+hipError_t sr_launch_train_degrade(sr_train_degrade_args a, uint32_t* d_batch, float* d_x, const float* d_ftab, const double* d_tab,
+                                   hipStream_t s);

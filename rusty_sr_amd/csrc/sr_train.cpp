@@ -334,6 +334,78 @@ int sr_train_step_aug(sr_train* t, const sr_train_crop* items, const uint8_t* me
     return finish_step(t, n, crop_h, crop_w, nullptr);
 }
 
+int sr_train_step_degrade(sr_train* t, const sr_train_crop* items, const uint8_t* members, const sr_degrade* deg, int n, int crop_h, int crop_w) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !items || !deg || n < 1 || n > SR_TRAIN_MAX_BATCH) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    const int f = c->factor;
+    if (crop_h < f || crop_w < f || crop_h % f || crop_w % f) return SR_E_INVALID;
+    // every item is checked before anything is launched; the rows of each transient image that its window AND its blur can reach are what
+    // is staged (the window of a member that swaps the axes has crop_w rows)
+    auto member = [&](int i) { return members ? (int)members[i] : 0; };
+    auto reach = [&](int i, long* r0, long* r1) {
+        const sr_train_crop& it = items[i];
+        const long rows = member(i) & 4 ? crop_w : crop_h, R = sr_degrade_radius(deg[i]);
+        *r0 = std::clamp<long>((long)it.y0 - R, 0, it.h);
+        *r1 = std::clamp<long>((long)it.y0 + rows + R, 0, it.h);
+    };
+    size_t trans_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        const sr_train_crop& it = items[i];
+        if (member(i) > 7 || sr_degrade_check(deg[i]) != SR_OK) return SR_E_INVALID;
+        if (it.image >= 0) {
+            if ((size_t)it.image >= t->images.size() || t->images[(size_t)it.image].d_lr) return SR_E_INVALID;  // (a pair is no plain image)
+        } else if (it.image == -1) {
+            if (!it.px || (it.in_channels != 3 && it.in_channels != 4) || it.h < 1 || it.w < 1) return SR_E_INVALID;
+            long r0, r1;
+            reach(i, &r0, &r1);
+            trans_bytes += sr_round256((size_t)(r1 - r0) * it.w * it.in_channels);
+        } else {
+            return SR_E_INVALID;
+        }
+    }
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = begin_step(t, n, crop_h, crop_w);
+    if (rc != SR_OK) return rc;
+    const size_t batch_bytes = (size_t)n * crop_h * crop_w * 3;
+    rc = grow(c, s, t->d_batch, batch_bytes + 4);
+    if (rc == SR_OK && trans_bytes) rc = grow(c, s, t->d_trans, trans_bytes);
+    float* x = nullptr;
+    if (rc == SR_OK) rc = sr_grad_input_buffer(c, n, crop_h / f, crop_w / f, &x);  // (the stream has drained if this grows the workspace)
+    if (rc == SR_OK) rc = sr_degrade_ensure_table(c);
+    if (rc != SR_OK) return rc;
+    sr_train_degrade_args a;
+    a.n = n; a.crop_h = crop_h; a.crop_w = crop_w; a.f = f; a.hr_blocks = 0;
+    int k = 0;
+    rc = acquire_stage(t, trans_bytes, &k);
+    if (rc != SR_OK) return rc;
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const sr_train_crop& it = items[i];
+        a.g[i] = deg[i];
+        if (it.image >= 0) {
+            const sr_train::Img& im = t->images[(size_t)it.image];
+            a.d[i] = {im.d, im.ch, im.h, im.w, it.y0, it.x0, member(i)};
+            continue;
+        }
+        long r0, r1;
+        reach(i, &r0, &r1);
+        const size_t row = (size_t)it.w * it.in_channels, bytes = (size_t)(r1 - r0) * row;
+        if (bytes) memcpy((char*)t->h_stage[k] + off, it.px + (size_t)r0 * row, bytes);
+        // the staged rows as an image of r1 - r0 rows: what the crop and the blur read outside them is outside the source image too
+        a.d[i] = {(const uint8_t*)t->d_trans.p + off, it.in_channels, (int)(r1 - r0), it.w, (int)(it.y0 - r0), it.x0, member(i)};
+        off += sr_round256(bytes);
+    }
+    rc = upload_stage(t, trans_bytes, k);
+    if (rc != SR_OK) return rc;
+    HIPCHK(c, sr_launch_train_degrade(a, (uint32_t*)t->d_batch.p, x, c->d_vtab, c->d_dtab, s));
+    sr_lr_input in;
+    in.in_place = true;
+    return finish_step(t, n, crop_h, crop_w, &in);
+}
+
 int sr_train_add_pair(sr_train* t, const uint8_t* lr_px, int lr_channels, const uint8_t* hr_px, int hr_channels, int lh, int lw, int* id) {
     if (!t && sr_no_device()) return SR_E_NO_DEVICE;
     if (!t || !t->c || !lr_px || !hr_px || !id) return SR_E_INVALID;

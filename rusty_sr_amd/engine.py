@@ -437,6 +437,46 @@ class Engine:
                                                       self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
+    # ---- degradation: blur, noise and a JPEG round trip of an HR frame, made on the device (include/srhip.h "Degradation") ----
+    @staticmethod
+    def _degrade_args(shape, factor, sigma, noise, quality, seed, window, member):
+        f = int(factor)
+        h, w = shape[:2]
+        if window is None:
+            window = (0, 0, h // f * f if f > 0 else 0, w // f * f if f > 0 else 0)
+        y0, x0, fh, fw = (int(v) for v in window)
+        return f, y0, x0, fh, fw, int(member), _lib.Degrade(float(sigma), float(noise), int(quality), int(seed) & (2 ** 64 - 1))
+
+    def degrade(self, hr: np.ndarray, factor: int, sigma: float = 0.0, noise: float = 0.0, quality: int = 0, seed: int = 0, window=None,
+                member: int = 0) -> np.ndarray:
+        """(H,W,3|4) u8 -> the degraded LR frame, (frame_h / factor, frame_w / factor, 3) u8 (sr_degrade_rgba8): Gaussian blur of width
+        sigma (HR pixels, linear light), the factor's pool, noise of that standard deviation (8-bit levels, stream `seed`), JPEG round trip
+        at `quality` (0: none).  window: (y0, x0, frame_h, frame_w) in HR pixels, default the image cropped to a multiple of the factor;
+        member: 0..7, the frame is T_k of the source window.  Any engine will do: no network runs."""
+        hr = np.ascontiguousarray(hr)
+        if hr.dtype != np.uint8 or hr.ndim != 3:
+            raise ValueError("expected (H, W, 3|4) u8 pixels")
+        f, y0, x0, fh, fw, k, g = self._degrade_args(hr.shape, factor, sigma, noise, quality, seed, window, member)
+        out = np.empty((max(fh // f, 0) if f > 0 else 0, max(fw // f, 0) if f > 0 else 0, 3), dtype=np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_degrade_rgba8(self._ctx, hr.ctypes.data_as(u8p), hr.shape[2], hr.shape[0], hr.shape[1], f, y0, x0, fh, fw, k,
+                                            C.byref(g), out.ctypes.data_as(u8p)), self._ctx)
+        return out
+
+    def degrade_dev(self, hr, factor: int, sigma: float = 0.0, noise: float = 0.0, quality: int = 0, seed: int = 0, window=None, member: int = 0,
+                    out=None, stream=None):
+        """degrade on a (H,W,3|4) u8 torch tensor of this engine's device -> a (frame_h / factor, frame_w / factor, 3) u8 tensor,
+        asynchronous on the stream (sr_degrade_rgba8_dev).  hr and out may start at any byte."""
+        import torch
+        assert hr.is_cuda and hr.dtype == torch.uint8 and hr.is_contiguous() and hr.dim() == 3
+        f, y0, x0, fh, fw, k, g = self._degrade_args(hr.shape, factor, sigma, noise, quality, seed, window, member)
+        if out is None and f > 0 and fh >= f and fw >= f:
+            out = torch.empty((fh // f, fw // f, 3), dtype=torch.uint8, device=hr.device)
+        _lib.check(self._L.sr_degrade_rgba8_dev(self._ctx, C.c_void_p(hr.data_ptr()), hr.shape[2], hr.shape[0], hr.shape[1], f, y0, x0, fh, fw, k,
+                                                C.byref(g), C.c_void_p(out.data_ptr() if out is not None else None),
+                                                self._stream_ptr(stream, hr.device)), self._ctx)
+        return out
+
     def upscale_band_f32_dev(self, x_ext, halo_top, halo_bot, out=None, stream=None):
         """x_ext: (h_ext,W,3) f32 rows = halo_top + band + halo_bot -> (3*band,3W,3)."""
         import torch
@@ -974,11 +1014,75 @@ def upscale_sharded_all(engines, bands, outs=None):
     return outs
 
 
-def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None, members=None) -> float:
+DEGRADE_KEYS = {"blur": (0.0, float(_lib.SR_DEGRADE_MAX_SIGMA), False), "noise": (0.0, float(_lib.SR_DEGRADE_MAX_NOISE), False),
+                "jpeg": (0, 100, True)}
+_GOLDEN, _MASK64 = 0x9E3779B97F4A7C15, 2 ** 64 - 1
+
+
+def parse_degrade_spec(text: str) -> dict:
+    """'blur=A[:B],noise=A[:B],jpeg=A[:B]' (the CLI's --degrade) -> {"blur": (A, B), "noise": (A, B), "jpeg": (A, B)}; a key that is
+    absent is (0, 0): that stage is off.  A malformed spec, a reversed or an out-of-range range is a ValueError that names the key."""
+    import math
+    import re
+    out = {k: ((0, 0) if integer else (0.0, 0.0)) for k, (_, _, integer) in DEGRADE_KEYS.items()}
+    seen = set()
+    if not text:
+        raise ValueError("--degrade: empty spec")
+    for part in text.split(","):
+        key, eq, val = part.partition("=")
+        if key not in DEGRADE_KEYS:
+            raise ValueError(f"--degrade: unknown key '{key}'")
+        if not eq or key in seen:
+            raise ValueError(f"--degrade: malformed or repeated key '{key}'")
+        seen.add(key)
+        lo, hi, integer = DEGRADE_KEYS[key]
+        try:
+            if not all(re.fullmatch(r"[+-]?\d+" if integer else r"[+-]?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?", v) for v in val.split(":")):
+                raise ValueError(val)
+            ab = [int(v) if integer else float(v) for v in val.split(":")]
+        except ValueError:
+            raise ValueError(f"--degrade: malformed value for '{key}'") from None
+        if len(ab) not in (1, 2) or any(not math.isfinite(v) for v in ab):
+            raise ValueError(f"--degrade: malformed value for '{key}'")
+        a, b = ab[0], ab[-1]
+        if b < a:
+            raise ValueError(f"--degrade: reversed range for '{key}'")
+        if a < lo or b > hi:
+            raise ValueError(f"--degrade: range for '{key}' outside {lo}..{hi}")
+        out[key] = (a, b)
+    return out
+
+
+def degrade_draws(spec, seed: int, count: int, first: int = 0):
+    """Draws first .. first + count - 1 of a spec (a string or parse_degrade_spec's dict) under `seed`, as keyword arguments of
+    Engine.degrade.  The stream is SplitMix64 seeded with seed ^ 0xD6E8FEB86659FD93, four outputs a draw -- blur, noise, jpeg, noise seed;
+    value = A + u (B - A), jpeg = A + floor(u (B - A + 1)), u = (x >> 11) 2^-53; the fourth output is the noise seed as is."""
+    import math
+    if isinstance(spec, str):
+        spec = parse_degrade_spec(spec)
+
+    def output(j):
+        z = ((seed ^ 0xD6E8FEB86659FD93) + j * _GOLDEN) & _MASK64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+        return z ^ (z >> 31)
+
+    out = []
+    for i in range(first, first + count):
+        u = [(output(4 * i + j) >> 11) * 2.0 ** -53 for j in (1, 2, 3)]
+        (a0, b0), (a1, b1), (a2, b2) = spec["blur"], spec["noise"], spec["jpeg"]
+        out.append({"sigma": a0 + u[0] * (b0 - a0), "noise": a1 + u[1] * (b1 - a1), "quality": a2 + int(math.floor(u[2] * (b2 - a2 + 1))),
+                    "seed": output(4 * i + 4)})
+    return out
+
+
+def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None, members=None, degrade=None, seed: int = 0) -> float:
     """The reference's validation PSNR (main.rs:236-246) of a set of HR images: -10 log10(sum err_i / sum n_i).  Images are dealt
     round-robin over the engines (one host thread each); the sums are taken in image order, so the value does not depend on how many
     engines there are.  A zero error is +inf.  lr_images: the LR partner of each image -- the set is then scored as pairs
-    (validation_error_pair) instead of by pooling.  members: None, or the mask of a self-ensemble that is scored in the network's place."""
+    (validation_error_pair) instead of by pooling.  members: None, or the mask of a self-ensemble that is scored in the network's place.
+    degrade: a spec (the CLI's --degrade string, or parse_degrade_spec's dict) -- image i is cropped to a multiple of the factor, degraded
+    whole on its engine with draw i of the spec under `seed` (degrade_draws) and scored as a pair with that LR image."""
     import math
     from concurrent.futures import ThreadPoolExecutor
     if isinstance(engines, Engine):
@@ -992,10 +1096,18 @@ def validation_psnr(engines, images, linear_loss: bool = False, lr_images=None, 
             raise ValueError("validation_psnr needs one LR image per HR image")
     res = [None] * len(images)
     kw = {} if members is None else {"members": members}
+    if degrade is not None:
+        if lr_images is not None:
+            raise ValueError("validation_psnr takes lr_images or degrade, not both")
+        draws = degrade_draws(degrade, seed, len(images))
 
     def run(k):
         for i in range(k, len(images), len(engines)):
-            if lr_images is None:
+            if degrade is not None:
+                f = engines[k].factor
+                hr = np.ascontiguousarray(np.asarray(images[i])[:images[i].shape[0] // f * f, :images[i].shape[1] // f * f])
+                res[i] = engines[k].validation_error_pair(engines[k].degrade(hr, f, **draws[i]), hr, linear_loss, **kw)
+            elif lr_images is None:
                 res[i] = engines[k].validation_error(images[i], linear_loss, **kw)
             else:
                 res[i] = engines[k].validation_error_pair(lr_images[i], images[i], linear_loss, **kw)
@@ -1140,10 +1252,9 @@ class Trainer:
             raise ValueError("a member is one of the 8 flips and rotations, 0..7")
         return (C.c_uint8 * len(ks))(*ks)
 
-    def step_crops(self, items, crop_h: int, crop_w: int) -> None:
-        """One step on crops, queued without waiting.  items: (image, y0, x0[, member]) with image an id of add_image or a (h, w, 3|4) u8
-        array; member k (0..7, default 0) makes the item T_k of its window (sr_train_step_aug: the window of k >= 4 is crop_w x crop_h)."""
-        members = self._members(items)
+    @staticmethod
+    def _crop_items(items):
+        """The sr_train_crop array of (image, y0, x0[, member]) items, and the pixel arrays it points into (to be kept alive for the call)."""
         arr = (_lib.TrainCrop * max(len(items), 1))()
         keep = []
         for k, (img, y0, x0) in enumerate(it[:3] for it in items):
@@ -1158,11 +1269,33 @@ class Trainer:
                 keep.append(px)
                 it.image, it.px = -1, px.ctypes.data
                 it.h, it.w, it.in_channels = px.shape
+        return arr, keep
+
+    def step_crops(self, items, crop_h: int, crop_w: int) -> None:
+        """One step on crops, queued without waiting.  items: (image, y0, x0[, member]) with image an id of add_image or a (h, w, 3|4) u8
+        array; member k (0..7, default 0) makes the item T_k of its window (sr_train_step_aug: the window of k >= 4 is crop_w x crop_h)."""
+        members = self._members(items)
+        arr, keep = self._crop_items(items)
         if members is None:
             rc = self._L.sr_train_step(self._t, arr, len(items), int(crop_h), int(crop_w))
         else:
             rc = self._L.sr_train_step_aug(self._t, arr, members, len(items), int(crop_h), int(crop_w))
         _lib.check(rc, self.engine._ctx)
+        self.steps += 1
+        self._pending += 1
+
+    def step_degraded(self, items, degs, crop_h: int, crop_w: int) -> None:
+        """One step on crops whose network input is degraded on the device, queued without waiting (sr_train_step_degrade).  items as in
+        step_crops, (image, y0, x0[, member]); degs: one dict of sigma, noise, quality, seed (Engine.degrade's keywords, all optional) per
+        item.  crop_h and crop_w are multiples of the engine's factor."""
+        if len(degs) != len(items):
+            raise ValueError("expected one degradation per item")
+        members = self._members(items)
+        arr, keep = self._crop_items(items)
+        g = (_lib.Degrade * max(len(items), 1))()
+        for k, d in enumerate(degs):
+            g[k] = _lib.Degrade(float(d.get("sigma", 0.0)), float(d.get("noise", 0.0)), int(d.get("quality", 0)), int(d.get("seed", 0)) & (2 ** 64 - 1))
+        _lib.check(self._L.sr_train_step_degrade(self._t, arr, members, g, len(items), int(crop_h), int(crop_w)), self.engine._ctx)
         self.steps += 1
         self._pending += 1
 

@@ -4,6 +4,8 @@
 //   srcodec_asan FILE...        decode every file the way the CLI's `image::open` stand-in does (main.rs:164) and
 //                               print one line per file: "ok WxH" or "error: <message>"
 //   srcodec_asan --roundtrip W H OUT.png   encode a synthetic RGBA image, decode it again, compare
+//   srcodec_asan --degrade-spec SPEC SEED N   parse the CLI's --degrade SPEC (degrade_spec.cpp) and print its first N draws under SEED,
+//                               one "sigma noise quality seed" line each (floats as their bit patterns), or "error: <message>"
 //
 // A malformed file must end in a clean "error:" line -- the counterpart of the reference's
 // `.expect("Error opening input image file.")`.  Any out-of-bounds access, overflow or leak makes the sanitizers
@@ -14,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "degrade_spec.hpp"
 #include "png.hpp"
 
 int main(int argc, char** argv) {
@@ -33,6 +36,20 @@ int main(int argc, char** argv) {
         if (!srpng::decode_file(argv[4], img, err)) { printf("error: %s\n", err.c_str()); return 1; }
         if (img.w != w || img.h != h || img.rgba != px) { printf("error: round trip differs\n"); return 1; }
         printf("ok %dx%d\n", w, h);
+        return 0;
+    }
+    if (argc >= 5 && !strcmp(argv[1], "--degrade-spec")) {
+        srdegrade::Spec spec;
+        std::string err;
+        if (!srdegrade::parse(argv[2], spec, err)) { printf("error: %s\n", err.c_str()); return 1; }
+        const unsigned long long seed = strtoull(argv[3], nullptr, 10);
+        for (long i = 0, n = atol(argv[4]); i < n; ++i) {
+            const srdegrade::Draw d = srdegrade::draw(spec, seed, (uint64_t)i);
+            uint32_t bits[2];
+            memcpy(&bits[0], &d.sigma, 4);
+            memcpy(&bits[1], &d.noise, 4);
+            printf("%08x %08x %d %llu\n", bits[0], bits[1], d.quality, (unsigned long long)d.seed);
+        }
         return 0;
     }
     for (int i = 1; i < argc; ++i) {

@@ -2,8 +2,8 @@
 // (reference src/main.rs:33-258), driving the MI355X engine through libsrhip's C ABI.
 //
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
-//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] <PARAMETER_FILE> <TRAINING_FOLDER>
-//   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] <VALIDATION_FOLDER>
+//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] <PARAMETER_FILE> <TRAINING_FOLDER>
+//   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] [--degrade SPEC [--seed N]] <VALIDATION_FOLDER>
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
 // PSNR a parameter set reaches on a folder of HR images.  A first argument that is literally `train` or `validate` selects it; every
@@ -16,7 +16,8 @@
 // channel is kept -- colours bled under the transparent pixels, alpha interpolated; PNG output only), --size WxH | --scale S [--filter F]
 // [--resize-space linear|srgb] (upscale: the network's f32 output resampled to that size on the GPU, quantised once); for `train` --seed N (initial
 // parameters, shuffles and crops are seeded; the reference's are random), --augment (each crop under a random one of the 8 flips and
-// rotations, applied by the crop kernel) and --steps N (stop
+// rotations, applied by the crop kernel), --degrade SPEC (train and validate: the network's input is the HR crop or image blurred, pooled,
+// noised and JPEG-compressed on the GPU, each draw with its own values: degrade_spec.hpp) and --steps N (stop
 // early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
 // writes it after step 1 and every 100 steps).
 #include <cstdio>
@@ -38,6 +39,7 @@
 #include <vector>
 
 #include "../../include/srhip.h"
+#include "degrade_spec.hpp"
 #include "png.hpp"
 
 // The three parameter sets the reference embeds with include_bytes! (main.rs:26-28)
@@ -98,7 +100,11 @@ const char* kValidateUsage =
     "        --devices <N,N,...>          HIP devices; images are dealt round-robin [default: 0]\n"
     "        --precision <MODE>           f32 (exact) or split_f16 [default: f32]\n"
     "        --ensemble <N>               score the network averaged over N flips / rotations of its input [values: 2, 4, 8]\n"
-    "        --shave <N>                  with --metrics: pixels removed from each border before scoring [default: the factor]\n\n"
+    "        --shave <N>                  with --metrics: pixels removed from each border before scoring [default: the factor]\n"
+    "        --degrade <SPEC>             Score LR / HR pairs whose LR image is made from the HR image on the GPU: SPEC is\n"
+    "                                     blur=A[:B],noise=A[:B],jpeg=A[:B] (Gaussian sigma 0..4 HR pixels, noise 0..64 levels, JPEG\n"
+    "                                     quality 1..100; a key left out is off); image i takes draw i of the ranges\n"
+    "        --seed <N>                   with --degrade: seed of the draws [default: 0]\n\n"
     "ARGS:\n    <VALIDATION_FOLDER>    Images from this folder (or sub-folders with -r) are scored, in path order\n";
 
 [[noreturn]] void die(const std::string& msg, int code = 1) {
@@ -306,13 +312,30 @@ void check_pair_sizes(const std::string& hr_file, const srpng::Image& hr, const 
         std::to_string(lr.w) + "x" + std::to_string(lr.h) + ": the HR size must be exactly " + std::to_string(f) + " x the LR size");
 }
 
+// --degrade in `validate` and in `train -v`: the HR image is cropped in place to a multiple of f (the pooled call's crop rule: the
+// top-left f floor(h / f) x f floor(w / f)) and degraded whole -- frame = the cropped image, member 0 -- into lr (3 bytes a pixel).
+int degrade_whole(sr_ctx* ctx, srpng::Image& hr, int factor, const srdegrade::Draw& d, srpng::Image& lr) {
+    const int h = hr.h / factor * factor, w = hr.w / factor * factor;
+    if (h < factor || w < factor) return SR_E_INVALID;
+    if (w != hr.w)
+        for (int y = 1; y < h; ++y) memmove(&hr.rgba[(size_t)y * w * 4], &hr.rgba[(size_t)y * hr.w * 4], (size_t)w * 4);
+    hr.h = h; hr.w = w;
+    hr.rgba.resize((size_t)h * w * 4);
+    lr.h = h / factor; lr.w = w / factor;
+    lr.rgba.resize((size_t)lr.h * lr.w * 3);
+    const sr_degrade g{d.sigma, d.noise, d.quality, d.seed};
+    return sr_degrade_rgba8(ctx, hr.rgba.data(), 4, h, w, factor, 0, 0, h, w, 0, &g, lr.rgba.data());
+}
+
 // rusty_sr validate: the validation pass of the reference's `train` (main.rs:220-247) on its own.  Files are decoded on up to 16 host
 // threads (OMP_NUM_THREADS if set) ahead of the GPU, which scores them in path order; with --devices image i goes to context i mod n.
 // The sums are taken in image order, so the printed value does not depend on the number of devices.
 int run_validate(int argc, char** argv) {
     std::string parameters, custom, precision = "f32", folder, lr_folder;
     bool has_p = false, has_c = false, linear = false, recurse = false, timing = false, has_folder = false, has_lr = false;
-    bool metrics = false, has_shave = false;
+    bool metrics = false, has_shave = false, has_deg = false, has_seed = false;
+    srdegrade::Spec deg_spec;
+    uint64_t seed = 0;
     long val_max = -1;
     int shave = -1;         // --metrics: -1 = the factor
     unsigned ensemble = 0;  // 0: the plain validation pass
@@ -364,6 +387,18 @@ int run_validate(int argc, char** argv) {
             has_shave = true;
         }
         else if (a == "--augment") validate_usage_error("The argument '--augment' can only be used with the 'train' subcommand");
+        else if (a == "--degrade") {
+            const std::string v = value("--degrade <SPEC>");
+            std::string perr;
+            if (!srdegrade::parse(v, deg_spec, perr)) validate_usage_error("'" + v + "' isn't a valid value for '--degrade <SPEC>': " + perr);
+            has_deg = true;
+        }
+        else if (a == "--seed") {
+            const std::string v = value("--seed <N>");
+            const auto r = std::from_chars(v.data(), v.data() + v.size(), seed);
+            if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size()) validate_usage_error("'" + v + "' isn't a valid value for '--seed <N>'");
+            has_seed = true;
+        }
         else if (a.size() > 1 && a[0] == '-') validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (has_folder) validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else { folder = a; has_folder = true; }
@@ -376,6 +411,8 @@ int run_validate(int argc, char** argv) {
     if (ensemble && devices.size() > 1)
         validate_usage_error("The argument '--ensemble <N>' cannot be used with more than one device: the ensemble has no multi-GPU form");
     if (has_shave && !metrics) validate_usage_error("The following required arguments were not provided:\n    --metrics");
+    if (has_deg && has_lr) validate_usage_error("The argument '--degrade <SPEC>' cannot be used with '--lr_folder <DIR>': the LR images are made from the HR images");
+    if (has_seed && !has_deg) validate_usage_error("The following required arguments were not provided:\n    --degrade <SPEC>");
     if (devices.empty()) devices.push_back(0);
 
     // ---- the files: decodable extensions, sorted by path bytes, the first N with -m
@@ -472,21 +509,25 @@ int run_validate(int argc, char** argv) {
                         std::lock_guard<std::mutex> lk(mu);  // (a mismatch ends the run from here: one thread at a time)
                         check_pair_sizes(files[i], img, lr_files[i], lr, factor);
                     }
-                    int r;
-                    if (metrics)  // (members 0: the plain pass)
-                        r = has_lr ? sr_pair_validation_metrics_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
-                                                                      ensemble, shave, &err[i], &cnt[i], &scores[i])
-                                   : sr_pool_validation_metrics_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble, shave,
-                                                                 &err[i], &cnt[i], &scores[i]);
+                    // --degrade: the HR image cropped to a multiple of f and its LR partner made from it, whole, with draw i; then a pair
+                    int r = has_deg ? degrade_whole(ctxs[k], img, factor, srdegrade::draw(deg_spec, seed, i), lr) : SR_OK;
+                    const bool pair = has_lr || has_deg;
+                    const int lr_ch = has_deg ? 3 : 4;
+                    if (r != SR_OK) {
+                    } else if (metrics)  // (members 0: the plain pass)
+                        r = pair ? sr_pair_validation_metrics_rgba8(ctxs[k], lr.rgba.data(), lr_ch, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
+                                                                    ensemble, shave, &err[i], &cnt[i], &scores[i])
+                                 : sr_pool_validation_metrics_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble, shave,
+                                                                    &err[i], &cnt[i], &scores[i]);
                     else if (ensemble)
-                        r = has_lr ? sr_pair_validation_error_ensemble_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
-                                                                             ensemble, &err[i], &cnt[i])
-                                   : sr_pool_validation_error_ensemble_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble,
-                                                                        &err[i], &cnt[i]);
+                        r = pair ? sr_pair_validation_error_ensemble_rgba8(ctxs[k], lr.rgba.data(), lr_ch, img.rgba.data(), 4, lr.h, lr.w,
+                                                                           linear ? 1 : 0, ensemble, &err[i], &cnt[i])
+                                 : sr_pool_validation_error_ensemble_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, ensemble,
+                                                                           &err[i], &cnt[i]);
                     else
-                        r = has_lr ? sr_pair_validation_error_rgba8(ctxs[k], lr.rgba.data(), 4, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
-                                                                    &err[i], &cnt[i])
-                                   : sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
+                        r = pair ? sr_pair_validation_error_rgba8(ctxs[k], lr.rgba.data(), lr_ch, img.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0,
+                                                                  &err[i], &cnt[i])
+                                 : sr_validation_error_rgba8(ctxs[k], img.rgba.data(), 4, img.h, img.w, linear ? 1 : 0, &err[i], &cnt[i]);
                     if (r == SR_OK && timing) { double tot = 0; sr_last_timing(ctxs[k], &tot, nullptr, nullptr, nullptr); gpu_ms[i] = tot; }
                     if (r != SR_OK) {
                         std::lock_guard<std::mutex> lk(mu);
@@ -553,6 +594,10 @@ const char* kTrainUsage =
     "        --val_lr_folder <DIR>         The LR partners of the validation images: the validation PSNR is then the paired score\n"
     "        --device <N>                  HIP device index [default: 0]\n"
     "        --seed <N>                    Seed of the initial parameters, the shuffles and the crops [default: random]\n"
+    "        --degrade <SPEC>              Train for real-world degradations: the network's input is each HR crop blurred, pooled,\n"
+    "                                      noised and JPEG-compressed on the GPU, every draw with its own values from the ranges of\n"
+    "                                      SPEC = blur=A[:B],noise=A[:B],jpeg=A[:B] (sigma 0..4 HR pixels, noise 0..64 levels, quality\n"
+    "                                      1..100; a key left out is off).  With -v the validation images are degraded the same way\n"
     "        --steps <N>                   Stop after N steps [default: 2500000, the reference's 10 000 000 evaluations]\n"
     "        --store <BYTES>               Device memory for resident training images; 0 decodes every draw again\n"
     "                                      [default: the device's free memory less max(8 GiB, 1/8 of it)]\n\n"
@@ -612,7 +657,8 @@ int run_train(int argc, char** argv) {
     std::string start, val_folder, lr_folder, val_lr_folder;
     std::vector<std::string> pos;
     bool has_s = false, has_v = false, linear = false, recurse = false, timing = false, has_lr = false, has_vlr = false, has_f = false;
-    bool augment = false;
+    bool augment = false, has_deg = false;
+    srdegrade::Spec deg_spec;
     long factor_arg = SR_FACTOR;
     long val_max = -1, steps = 2500000, device = 0, store = -1;
     uint64_t seed = 0;
@@ -660,6 +706,12 @@ int run_train(int argc, char** argv) {
             if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size()) train_usage_error("'" + v + "' isn't a valid value for '--seed <N>'");
             has_seed = true;
         }
+        else if (a == "--degrade") {
+            const std::string v = value("--degrade <SPEC>");
+            std::string perr;
+            if (!srdegrade::parse(v, deg_spec, perr)) train_usage_error("'" + v + "' isn't a valid value for '--degrade <SPEC>': " + perr);
+            has_deg = true;
+        }
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             train_usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
         else if (a.size() > 1 && a[0] == '-') train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
@@ -670,6 +722,10 @@ int run_train(int argc, char** argv) {
         train_usage_error("The following required arguments were not provided:\n    --val_folder <VAL_FOLDER>");
     if (has_vlr && !has_v)
         train_usage_error("The following required arguments were not provided:\n    --val_folder <VAL_FOLDER>");
+    if (has_deg && has_lr)
+        train_usage_error("The argument '--degrade <SPEC>' cannot be used with '--lr_folder <DIR>': the LR crops are made from the HR crops");
+    if (has_deg && has_vlr)
+        train_usage_error("The argument '--degrade <SPEC>' cannot be used with '--val_lr_folder <DIR>': the validation images are degraded the same way");
     if (pos.size() < 2) train_usage_error("The following required arguments were not provided:\n    <PARAMETER_FILE>\n    <TRAINING_FOLDER>");
     if (!has_seed) seed = ((uint64_t)std::random_device{}() << 32) ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
     const std::string param_file = pos[0], train_folder = pos[1];
@@ -787,7 +843,8 @@ int run_train(int argc, char** argv) {
     Rng aug_rng{seed ^ 0x6175676d656e7421ull};  // --augment: the members, a stream of their own
     std::vector<size_t> perm;
     size_t perm_pos = 0;
-    struct Draw { size_t file; int y0, x0; uint8_t member; };
+    struct Draw { size_t file; int y0, x0; uint8_t member; sr_degrade deg; };
+    uint64_t deg_drawn = 0;  // --degrade: the draws of its own stream (degrade_spec.hpp), one per crop, in draw order
     auto draw = [&]() -> Draw {
         if (perm_pos == perm.size()) {
             perm = usable;
@@ -801,7 +858,12 @@ int run_train(int argc, char** argv) {
         const int y0 = h > kCrop ? (int)rng.below((uint64_t)(h - kCrop + 1)) : 0;
         const int x0 = w > kCrop ? (int)rng.below((uint64_t)(w - kCrop + 1)) : 0;
         // (the crop is square: the window of a member that swaps the axes has the same origins to choose from)
-        return {fi, y0, x0, augment ? (uint8_t)(aug_rng.next() >> 61) : (uint8_t)0};
+        sr_degrade deg{0.0f, 0.0f, 0, 0};
+        if (has_deg) {
+            const srdegrade::Draw g = srdegrade::draw(deg_spec, seed, deg_drawn++);
+            deg = {g.sigma, g.noise, g.quality, g.seed};
+        }
+        return {fi, y0, x0, augment ? (uint8_t)(aug_rng.next() >> 61) : (uint8_t)0, deg};
     };
     // draws are made a window of steps ahead, so that transient images decode while the GPU works
     DecoderPool pool(files, 16 * kBatch), lr_pool(lr_files, 16 * kBatch);
@@ -828,11 +890,15 @@ int run_train(int argc, char** argv) {
         if (r != SR_OK) die(sr_strerror(r));
         double err_sum = 0, n_sum = 0;
         for (size_t k = 0; k < val_n; ++k) {
-            const srpng::Image& im = vimg[val_next];
+            srpng::Image& im = vimg[val_next];
             val_next = (val_next + 1) % vimg.size();
             double e = 0;
             size_t ne = 0;
-            if (has_vlr) {
+            if (has_deg) {  // the k-th image of this pass takes draw k: every pass restarts the stream, so successive PSNR lines compare
+                srpng::Image lr;
+                r = degrade_whole(ctx, im, factor, srdegrade::draw(deg_spec, seed, k), lr);
+                if (r == SR_OK) r = sr_pair_validation_error_rgba8(ctx, lr.rgba.data(), 3, im.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0, &e, &ne);
+            } else if (has_vlr) {
                 const srpng::Image& lr = vlr[(val_next + vimg.size() - 1) % vimg.size()];
                 r = sr_pair_validation_error_rgba8(ctx, lr.rgba.data(), 4, im.rgba.data(), 4, lr.h, lr.w, linear ? 1 : 0, &e, &ne);
             } else {
@@ -858,12 +924,14 @@ int run_train(int argc, char** argv) {
         sr_train_crop items[kBatch];
         sr_train_pair_crop pairs[kBatch];
         uint8_t members[kBatch];
+        sr_degrade degs[kBatch];
         for (int i = 0; i < kBatch; ++i) {
             const auto [d, job] = ahead.front();
             ahead.pop_front();
             items[i].y0 = pairs[i].y0 = d.y0;
             items[i].x0 = pairs[i].x0 = d.x0;
             members[i] = d.member;
+            degs[i] = d.deg;
             if (job < 0) {
                 items[i].image = pairs[i].pair = timg[d.file].id;
                 items[i].px = pairs[i].lr_px = pairs[i].hr_px = nullptr;
@@ -887,7 +955,8 @@ int run_train(int argc, char** argv) {
             pairs[i].lr_px = held_lr[i].data();
             pairs[i].lr_channels = pairs[i].hr_channels = 4; pairs[i].lh = lr.h; pairs[i].lw = lr.w;
         }
-        if (augment) rc = has_lr ? sr_train_step_pairs_aug(tr, pairs, members, kBatch, kCrop, kCrop) : sr_train_step_aug(tr, items, members, kBatch, kCrop, kCrop);
+        if (has_deg) rc = sr_train_step_degrade(tr, items, augment ? members : nullptr, degs, kBatch, kCrop, kCrop);
+        else if (augment) rc = has_lr ? sr_train_step_pairs_aug(tr, pairs, members, kBatch, kCrop, kCrop) : sr_train_step_aug(tr, items, members, kBatch, kCrop, kCrop);
         else rc = has_lr ? sr_train_step_pairs(tr, pairs, kBatch, kCrop, kCrop) : sr_train_step(tr, items, kBatch, kCrop, kCrop);
         if (rc != SR_OK) die(std::string("training step: ") + sr_strerror(rc));
         if (step % 1000 == 0) {  // keep the err_sum list of the session short (the values are not reported)
@@ -993,6 +1062,7 @@ int main(int argc, char** argv) {
             has_space = true;
         }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
+        else if (a == "--degrade") usage_error("The argument '--degrade' can only be used with the 'train' and 'validate' subcommands");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
         else if (a.size() > 1 && a[0] == '-') usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
