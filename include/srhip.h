@@ -680,6 +680,60 @@ int sr_degrade_rgba8_dev(sr_ctx* ctx, const uint8_t* d_hr, int in_channels, int 
                          int member, const sr_degrade* deg, uint8_t* d_lr_rgb, void* stream);
 int sr_train_step_degrade(sr_train* t, const sr_train_crop* items, const uint8_t* members, const sr_degrade* deg, int n, int crop_h, int crop_w);
 
+/* ---- Borders: what lies beyond the edge of the image ----
+ * Every layer of sr_net zero-pads its feature maps, so every call above computes an image's left edge without knowing its right edge: a
+ * tileable texture comes back with a seam.  These calls let the caller say what continues the image: the image is padded by `pad` pixels
+ * on every side under a border mode, the UNCHANGED network runs on the padded image, and the centre f h x f w is cut out of the result.
+ * The network's receptive field reaches SR_HALO pixels, so with pad >= SR_HALO the result is exactly what the network computes for the
+ * centre of the infinitely continued plane: under SR_BORDER_WRAP, the centre tile of the 3 x 3 tiling, bit for bit on the CPU oracle
+ * (tests/test_border_cpu.py; at pad = SR_HALO - 1 it is not).  UNPINNED: the reference has no counterpart; tests/border_ref.py restates
+ * the index rule in numpy (np.pad).
+ *   The rule is per axis and separable.  Padded index j (0 .. size + 2 pad - 1) of an axis of `size` samples shows sample idx(j - pad):
+ *     SR_BORDER_WRAP       idx(i) = i mod size, a true modulo (size may be below pad, and 1)             np.pad mode="wrap"
+ *     SR_BORDER_REPLICATE  idx(i) = clamp(i, 0, size - 1)                                                np.pad mode="edge"
+ *     SR_BORDER_MIRROR     m = i mod 2 size; idx(i) = m < size ? m : 2 size - 1 - m: a reflection that REPEATS the edge sample
+ *                                                                                                        np.pad mode="symmetric"
+ *   There is no "zero" mode: padding with zeros is NOT the plain call (the biases make the features of a black border non-zero).  "Off"
+ *   is the calls above.  Quality: SR_BORDER_WRAP is for images that tile.  SR_BORDER_REPLICATE and SR_BORDER_MIRROR are NOT a measured
+ *   quality gain -- the network was trained with its own zero padding (README.md has the numbers).
+ * Images are RGBA8 (4 bytes a pixel, moved as whole dwords: alpha travels with its pixel) or f32 RGB (n x h x w x 3) in device memory;
+ * both pointers 4-byte aligned, the images must not overlap.  Asynchronous and ordered on `stream` alone.  Pure data movement: the same
+ * bits on every run.
+ * sr_pad_*_dev: d_out = the n images of (h + 2 pad) x (w + 2 pad) of the n images of h x w at d_in; pad 0 .. SR_BORDER_PAD_MAX; any context.
+ * sr_crop_*_dev: d_out = the ch x cw window at (y0, x0) of each of the n images of H x W at d_in, contiguous; any context.
+ * sr_upscale_*_border_dev: pad into a workspace buffer of the context, then exactly sr_upscale_*_dev's path (members == 1) or
+ *   sr_upscale_ensemble_*_dev's (any other mask, as in sr_upscale_rgba8_alpha) on the padded image into a second workspace buffer, then
+ *   the crop of its centre to d_out: bit for bit the plain (or ensemble) call on the padded image, cropped.  The buffers are grown on
+ *   first use, all or nothing, and freed by sr_destroy.  SR_GRAPH_SR_NET (factors 2-4, both precisions) and SR_GRAPH_BILINEAR contexts.
+ *   bleed (RGBA8): -1 gives opaque output (alpha 255) like sr_upscale_rgba8; 0 .. SR_ALPHA_BLEED_MAX keeps transparency, in the order
+ *   bleed -> pad -> network -> crop -> merge: the bleed and the alpha merge of sr_upscale_rgba8_alpha run on the UNPADDED image (the
+ *   alpha is interpolated exactly as there; the bleed does not wrap), so an opaque image gives the bytes of bleed = -1.
+ * sr_upscale_*_border: the same on host memory, synchronous: one upload, the device call on the context's own stream, one download; in
+ *   SR_PRECISION_SPLIT_F16 the whole call is computed again in exact f32 where a value left that mode's domain.  With sr_set_profiling on,
+ *   sr_last_timing's total_ms is every launch of the call, h2d / d2h the two copies.
+ * Refused with SR_E_INVALID before any launch, the output untouched: a null pointer; n, h or w below 1; a mode outside 1..3; a pad above
+ * SR_BORDER_PAD_MAX or (sr_upscale_*) below SR_HALO or (sr_pad_*) below 0; a crop window that is not inside its image; SR_GRAPH_DOWNSAMPLE
+ * contexts, members == 0 or > 255, members != 1 on a context other than SR_GRAPH_SR_NET, a bleed outside -1 .. SR_ALPHA_BLEED_MAX (sr_upscale_*);
+ * a device pointer that is not 4-byte aligned; d_in == d_out (sr_pad_*, sr_crop_*).  A shape whose padded size overflows or whose workspace
+ * cannot fit the device is SR_E_NOMEM, by arithmetic, and leaves the context usable.  Cost at 1920 x 1080: DESIGN.md 4p. */
+#define SR_BORDER_WRAP 1
+#define SR_BORDER_REPLICATE 2
+#define SR_BORDER_MIRROR 3
+#define SR_BORDER_PAD_DEFAULT 8    /* >= SR_HALO; a multiple of 4, so that the crop's source rows keep the output rows' 16-byte phase */
+#define SR_BORDER_PAD_MAX 32
+int sr_pad_rgba8_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int h, int w, int mode, int pad, uint8_t* d_out_rgba, void* stream);
+int sr_pad_f32_dev(sr_ctx* ctx, const float* d_in, int n, int h, int w, int mode, int pad, float* d_out, void* stream);
+int sr_crop_rgba8_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int H, int W, int y0, int x0, int ch, int cw, uint8_t* d_out_rgba,
+                      void* stream);
+int sr_crop_f32_dev(sr_ctx* ctx, const float* d_in, int n, int H, int W, int y0, int x0, int ch, int cw, float* d_out, void* stream);
+int sr_upscale_rgba8_border_dev(sr_ctx* ctx, const uint8_t* d_in_rgba, int n, int h, int w, uint8_t* d_out_rgba, int mode, int pad,
+                                unsigned members, int bleed, void* stream);
+int sr_upscale_f32_border_dev(sr_ctx* ctx, const float* d_in, int n, int h, int w, float* d_out, int mode, int pad, unsigned members,
+                              void* stream);
+int sr_upscale_rgba8_border(sr_ctx* ctx, const uint8_t* in_rgba, int n, int h, int w, uint8_t* out_rgba, int mode, int pad, unsigned members,
+                            int bleed);
+int sr_upscale_f32_border(sr_ctx* ctx, const float* in, int n, int h, int w, float* out, int mode, int pad, unsigned members);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -79,6 +79,11 @@ pub const SR_TRAIN_RING: c_int = 64;
 pub const SR_TRAIN_STORE_AUTO: usize = usize::MAX;
 pub const SR_ALPHA_BLEED_DEFAULT: c_int = 8;
 pub const SR_ALPHA_BLEED_MAX: c_int = 16;
+pub const SR_BORDER_WRAP: c_int = 1;
+pub const SR_BORDER_REPLICATE: c_int = 2;
+pub const SR_BORDER_MIRROR: c_int = 3;
+pub const SR_BORDER_PAD_DEFAULT: c_int = 8;
+pub const SR_BORDER_PAD_MAX: c_int = 32;
 
 extern "C" {
     pub fn sr_rsr_decode(blob: *const u8, len: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
@@ -188,6 +193,14 @@ extern "C" {
     pub fn sr_degrade_rgba8(ctx: *mut SrCtx, hr: *const u8, in_channels: c_int, h: c_int, w: c_int, factor: c_int, y0: c_int, x0: c_int, frame_h: c_int, frame_w: c_int, member: c_int, deg: *const SrDegrade, lr_rgb: *mut u8) -> c_int;
     pub fn sr_degrade_rgba8_dev(ctx: *mut SrCtx, d_hr: *const u8, in_channels: c_int, h: c_int, w: c_int, factor: c_int, y0: c_int, x0: c_int, frame_h: c_int, frame_w: c_int, member: c_int, deg: *const SrDegrade, d_lr_rgb: *mut u8, stream: *mut c_void) -> c_int;
     pub fn sr_train_step_degrade(t: *mut SrTrain, items: *const SrTrainCrop, members: *const u8, deg: *const SrDegrade, n: c_int, crop_h: c_int, crop_w: c_int) -> c_int;
+    pub fn sr_pad_rgba8_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, mode: c_int, pad: c_int, d_out_rgba: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sr_pad_f32_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, mode: c_int, pad: c_int, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_crop_rgba8_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, big_h: c_int, big_w: c_int, y0: c_int, x0: c_int, ch: c_int, cw: c_int, d_out_rgba: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sr_crop_f32_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, big_h: c_int, big_w: c_int, y0: c_int, x0: c_int, ch: c_int, cw: c_int, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_rgba8_border_dev(ctx: *mut SrCtx, d_in_rgba: *const u8, n: c_int, h: c_int, w: c_int, d_out_rgba: *mut u8, mode: c_int, pad: c_int, members: c_uint, bleed: c_int, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_f32_border_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut f32, mode: c_int, pad: c_int, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_rgba8_border(ctx: *mut SrCtx, in_rgba: *const u8, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, mode: c_int, pad: c_int, members: c_uint, bleed: c_int) -> c_int;
+    pub fn sr_upscale_f32_border(ctx: *mut SrCtx, input: *const f32, n: c_int, h: c_int, w: c_int, out: *mut f32, mode: c_int, pad: c_int, members: c_uint) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

@@ -25,6 +25,8 @@ SR_FILTER_BOX, SR_FILTER_TRIANGLE, SR_FILTER_CATROM, SR_FILTER_LANCZOS3 = 0, 1, 
 SR_PIXELS_RGBA8, SR_PIXELS_F32 = 0, 1
 SR_RESIZE_SRGB_SPACE = 1
 SR_DEGRADE_MAX_SIGMA, SR_DEGRADE_MAX_NOISE = 4, 64
+SR_BORDER_WRAP, SR_BORDER_REPLICATE, SR_BORDER_MIRROR = 1, 2, 3
+SR_BORDER_PAD_DEFAULT, SR_BORDER_PAD_MAX = 8, 32
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -147,6 +149,14 @@ SYMBOLS = {
     "sr_degrade_rgba8": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Degrade), _u8p]),
     "sr_degrade_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(Degrade), _vp, _vp]),
     "sr_train_step_degrade": (_i, [_vp, C.POINTER(TrainCrop), _u8p, C.POINTER(Degrade), _i, _i, _i]),
+    "sr_pad_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sr_pad_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sr_crop_rgba8_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sr_crop_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sr_upscale_rgba8_border_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_uint, _i, _vp]),
+    "sr_upscale_f32_border_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_uint, _vp]),
+    "sr_upscale_rgba8_border": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, _i, C.c_uint, _i]),
+    "sr_upscale_f32_border": (_i, [_vp, _fp, _i, _i, _i, _fp, _i, _i, C.c_uint]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -461,6 +461,7 @@ void sr_destroy(sr_ctx* c) {
     sr_alpha_release(c);
     sr_resize_release(c);
     sr_degrade_release(c);
+    sr_border_release(c);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     for (auto& w : c->ws) {
         for (auto& p : w.d_feat) if (p) (void)hipFree(p);

@@ -132,6 +132,9 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     sr_buf d_rmid;                                  // the horizontal pass's output, n x h x ow x 3 f32
     sr_buf d_rin;                                   // the _sized calls: byte / 255 of the caller's image, f32 RGB
     sr_buf d_rnet;                                  // the _sized calls: the network's f32 output
+    // ---- borders (sr_border.cpp): grown on demand, freed by sr_destroy
+    sr_buf d_bpad;                                  // the padded copy of the caller's image, RGBA8 or f32 RGB
+    sr_buf d_bout;                                  // the network's output for it, before the crop
     // ---- degradation (sr_degrade.cpp): uploaded on first use, freed by sr_destroy
     double* d_dtab = nullptr;                       // 320 doubles: SrgbToLinear(byte / 255), then the 8 x 8 DCT matrix
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
@@ -405,6 +408,17 @@ hipError_t sr_launch_alpha_bleed(const uint8_t* d_in, uint8_t* d_out, int n, int
 // byte 3 of the n images of factor h x factor w at d_out <- the alpha of d_lr (n x h x w RGBA8) interpolated; both 4-byte aligned
 hipError_t sr_launch_alpha_merge(int factor, const uint8_t* d_lr, uint8_t* d_out, int n, int h, int w, hipStream_t s);
 void sr_alpha_release(sr_ctx* c);  // free the bleed buffer (called by sr_destroy)
+
+// ---- borders (sr_border.hip kernels, sr_border.cpp host side; include/srhip.h "Borders")
+// workgroups of either launch (0: an empty shape), functions of the shape alone; the launchers refuse more than INT32_MAX
+size_t sr_border_pad_blocks(bool f32, int n, int h, int w, int pad, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+size_t sr_border_crop_blocks(bool f32, int n, int ch, int cw, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+// d_out = the n images of h x w at d_in (RGBA8, or f32 RGB), each continued by `pad` pixels on every side under `mode`; both 4-byte
+// aligned and not overlapping
+hipError_t sr_launch_border_pad(const void* d_in, bool f32, int n, int h, int w, int mode, int pad, void* d_out, hipStream_t s);
+// d_out = the ch x cw window at (y0, x0) of each of the n images of H x W at d_in, contiguous; both 4-byte aligned and not overlapping
+hipError_t sr_launch_border_crop(const void* d_in, bool f32, int n, int H, int W, int y0, int x0, int ch, int cw, void* d_out, hipStream_t s);
+void sr_border_release(sr_ctx* c);  // free the two buffers (called by sr_destroy)
 
 // ---- resampling to any size (sr_resize.hip kernels, sr_resize.cpp host side; include/srhip.h "Resampling to any size")
 // One axis of a resampling, n_in -> n_out samples: the rule's constants (f64, from the host) and where its tables lie in device memory.

@@ -341,6 +341,116 @@ class Engine:
                                                       self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
+    # ---- borders: the image continued by wrap / replicate / mirror, upscaled and cut back (include/srhip.h "Borders") ----
+    BORDERS = {"wrap": _lib.SR_BORDER_WRAP, "replicate": _lib.SR_BORDER_REPLICATE, "mirror": _lib.SR_BORDER_MIRROR}
+
+    @classmethod
+    def _border_mode(cls, mode) -> int:
+        """The mode by name; an integer passes as it is (the library refuses one it does not know)."""
+        if isinstance(mode, str):
+            if mode not in cls.BORDERS:
+                raise ValueError(f"mode must be one of {sorted(cls.BORDERS)}")
+            return cls.BORDERS[mode]
+        return int(mode)
+
+    @staticmethod
+    def _pixels_dev(x):
+        """(n,H,W,4) u8 or (n,H,W,3) f32, a contiguous tensor on the GPU -> (n, h, w, is_f32)."""
+        import torch
+        assert x.is_cuda and x.is_contiguous() and x.dim() == 4
+        f32 = x.dtype == torch.float32
+        assert (f32 and x.shape[-1] == 3) or (x.dtype == torch.uint8 and x.shape[-1] == 4)
+        n, h, w, _ = x.shape
+        return n, h, w, f32
+
+    def pad(self, x, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, out=None, stream=None):
+        """sr_pad_*_dev: (n,H,W,4) u8 or (n,H,W,3) f32 on this GPU -> (n,H+2p,W+2p,C), continued under `mode` by `pad` pixels (0..32)."""
+        import torch
+        n, h, w, f32 = self._pixels_dev(x)
+        p = int(pad)
+        if out is None:
+            out = torch.empty((n, h + 2 * max(p, 0), w + 2 * max(p, 0), x.shape[-1]), dtype=x.dtype, device=x.device)
+        fn = self._L.sr_pad_f32_dev if f32 else self._L.sr_pad_rgba8_dev
+        _lib.check(fn(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, self._border_mode(mode), p, C.c_void_p(out.data_ptr()),
+                      self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def crop(self, x, y0: int, x0: int, ch: int, cw: int, out=None, stream=None):
+        """sr_crop_*_dev: the ch x cw window at (y0, x0) of (n,H,W,4) u8 or (n,H,W,3) f32 on this GPU, as a contiguous (n,ch,cw,C) tensor."""
+        import torch
+        n, h, w, f32 = self._pixels_dev(x)
+        if out is None:
+            out = torch.empty((n, max(int(ch), 0), max(int(cw), 0), x.shape[-1]), dtype=x.dtype, device=x.device)
+        fn = self._L.sr_crop_f32_dev if f32 else self._L.sr_crop_rgba8_dev
+        _lib.check(fn(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, int(y0), int(x0), int(ch), int(cw), C.c_void_p(out.data_ptr()),
+                      self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    @staticmethod
+    def _bleed_arg(bleed) -> int:
+        return -1 if bleed is None else int(bleed)
+
+    def upscale_rgba8_border(self, img_rgba: np.ndarray, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, bleed=None,
+                             out: np.ndarray = None) -> np.ndarray:
+        """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) of the image continued under `mode`: (n,H,W,4) or
+        (H,W,4) u8 -> (n,fH,fW,4) u8.  bleed: None for opaque output, 0..16 to keep transparency as upscale_rgba8_alpha does."""
+        px = np.ascontiguousarray(img_rgba, dtype=np.uint8)
+        squeeze = px.ndim == 3
+        if squeeze:
+            px = px[None]
+        n, h, w, c = px.shape
+        if c != 4:
+            raise ValueError("expected 4 channels")
+        oh, ow = self._out_hw(h, w)
+        if out is None:
+            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
+        else:
+            out = out.reshape(n, oh, ow, 4)
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_upscale_rgba8_border(self._ctx, px.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), self._border_mode(mode),
+                                                   int(pad), self._members(members), self._bleed_arg(bleed)), self._ctx)
+        return out[0] if squeeze else out
+
+    def upscale_f32_border(self, x: np.ndarray, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1) -> np.ndarray:
+        """upscale_f32 (members == 1) or upscale_ensemble_f32 of the image continued under `mode`: (n,H,W,3) or (H,W,3) f32 -> (n,fH,fW,3)."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        squeeze = x.ndim == 3
+        if squeeze:
+            x = x[None]
+        n, h, w, c = x.shape
+        if c != 3:
+            raise ValueError("expected 3 channels")
+        out = np.empty((n,) + self._out_hw(h, w) + (3,), dtype=np.float32)
+        fp = C.POINTER(C.c_float)
+        _lib.check(self._L.sr_upscale_f32_border(self._ctx, x.ctypes.data_as(fp), n, h, w, out.ctypes.data_as(fp), self._border_mode(mode),
+                                                 int(pad), self._members(members)), self._ctx)
+        return out[0] if squeeze else out
+
+    def upscale_rgba8_border_dev(self, px, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, bleed=None, out=None,
+                                 stream=None):
+        import torch
+        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
+        n, h, w, _ = px.shape
+        if out is None:
+            out = torch.empty((n,) + self._out_hw(h, w) + (4,), dtype=torch.uint8, device=px.device)
+        _lib.check(self._L.sr_upscale_rgba8_border_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
+                                                       self._border_mode(mode), int(pad), self._members(members), self._bleed_arg(bleed),
+                                                       self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
+    def upscale_f32_border_dev(self, x, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, out=None, stream=None):
+        import torch
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
+        n, h, w, _ = x.shape
+        if out is None:
+            out = torch.empty((n,) + self._out_hw(h, w) + (3,), dtype=torch.float32, device=x.device)
+        _lib.check(self._L.sr_upscale_f32_border_dev(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
+                                                     self._border_mode(mode), int(pad), self._members(members),
+                                                     self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
     # ---- resampling to any size: a separable resampler in Pillow's convention, on the device (include/srhip.h "Resampling to any size") ----
     FILTERS = {"box": _lib.SR_FILTER_BOX, "triangle": _lib.SR_FILTER_TRIANGLE, "catrom": _lib.SR_FILTER_CATROM,
                "lanczos3": _lib.SR_FILTER_LANCZOS3}

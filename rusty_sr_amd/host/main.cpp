@@ -14,7 +14,9 @@
 // only WebP is missing), and extra options that cannot collide with the reference's: --device N, --precision f32|split_f16,
 // --timing, --ensemble 2|4|8 (upscale and validate: the network averaged over flips / rotations), --alpha [--bleed N] (upscale: the alpha
 // channel is kept -- colours bled under the transparent pixels, alpha interpolated; PNG output only), --size WxH | --scale S [--filter F]
-// [--resize-space linear|srgb] (upscale: the network's f32 output resampled to that size on the GPU, quantised once); for `train` --seed N (initial
+// [--resize-space linear|srgb] (upscale: the network's f32 output resampled to that size on the GPU, quantised once), --border
+// wrap|replicate|mirror [--border-pad N] (upscale: the image is continued that way beyond its edges instead of the network's zero padding
+// -- wrap makes a tileable texture come back seamless); for `train` --seed N (initial
 // parameters, shuffles and crops are seeded; the reference's are random), --augment (each crop under a random one of the 8 flips and
 // rotations, applied by the crop kernel), --degrade SPEC (train and validate: the network's input is the HR crop or image blurred, pooled,
 // noised and JPEG-compressed on the GPU, each draw with its own values: degrade_spec.hpp) and --steps N (stop
@@ -78,7 +80,11 @@ const char* kUsage =
     "        --filter <FILTER>            with --size / --scale: the resampling filter [values: box, triangle, catrom,\n"
     "                                     lanczos3] [default: lanczos3]\n"
     "        --resize-space <SPACE>       with --size / --scale: resample in linear light or on the sRGB values [values:\n"
-    "                                     linear, srgb] [default: linear]\n\n"
+    "                                     linear, srgb] [default: linear]\n"
+    "        --border <MODE>              what lies beyond the image's edges: wrap (a tileable texture stays seamless),\n"
+    "                                     replicate or mirror [values: wrap, replicate, mirror] [default: the network's\n"
+    "                                     own zero padding]\n"
+    "        --border-pad <N>             with --border: how many pixels the image is continued by, 7..32 [default: 8]\n\n"
     "ARGS:\n    <INPUT_FILE>     Sets the input image to upscale\n    <OUTPUT_FILE>    Sets the output file to write/overwrite (.png recommended)\n\n"
     "SUBCOMMANDS:\n    train       Trains a new set of neural network parameters on the GPU (rusty_sr train --help)\n"
     "    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
@@ -992,6 +998,8 @@ int main(int argc, char** argv) {
     unsigned ensemble = 0;  // 0: one pass of the network
     bool alpha = false, has_bleed = false;
     int bleed = SR_ALPHA_BLEED_DEFAULT;
+    int border = 0, border_pad = SR_BORDER_PAD_DEFAULT;  // --border: 0 = the plain calls (sr_upscale_rgba8_border otherwise)
+    bool has_border_pad = false;
     // --size / --scale: the output is resampled to a size of the user's choosing (sr_upscale_rgba8_sized)
     bool has_size = false, has_scale = false, has_filter = false, has_space = false;
     std::string size_arg, scale_arg;
@@ -1037,6 +1045,18 @@ int main(int argc, char** argv) {
             if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size() || bleed < 0 || bleed > SR_ALPHA_BLEED_MAX)
                 usage_error("'" + v + "' isn't a valid value for '--bleed <N>'\n\t[values: 0..16]");
             has_bleed = true;
+        }
+        else if (a == "--border" || a.rfind("--border=", 0) == 0) {
+            const std::string v = a == "--border" ? value("--border <MODE>") : a.substr(9);
+            border = v == "wrap" ? SR_BORDER_WRAP : v == "replicate" ? SR_BORDER_REPLICATE : v == "mirror" ? SR_BORDER_MIRROR : 0;
+            if (!border) usage_error("'" + v + "' isn't a valid value for '--border <MODE>'\n\t[values: mirror, replicate, wrap]");
+        }
+        else if (a == "--border-pad" || a.rfind("--border-pad=", 0) == 0) {
+            const std::string v = a == "--border-pad" ? value("--border-pad <N>") : a.substr(13);
+            const auto r = std::from_chars(v.data(), v.data() + v.size(), border_pad);
+            if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size() || border_pad < SR_HALO || border_pad > SR_BORDER_PAD_MAX)
+                usage_error("'" + v + "' isn't a valid value for '--border-pad <N>'\n\t[values: 7..32]");
+            has_border_pad = true;
         }
         else if (a == "--size" || a.rfind("--size=", 0) == 0) {
             size_arg = a == "--size" ? value("--size <WxH>") : a.substr(7);
@@ -1102,6 +1122,12 @@ int main(int argc, char** argv) {
     if (resize && alpha) usage_error("The argument '" + resize_opt + "' cannot be used with '--alpha': the resampling is not alpha-aware");
     if (resize && devices.size() > 1)
         usage_error("The argument '" + resize_opt + "' cannot be used with more than one device: the resampled call has no multi-GPU form");
+    // --border: the padded call has no downsampling, no resampled and no multi-GPU form
+    if (has_border_pad && !border) usage_error("The following required arguments were not provided:\n    --border <MODE>");
+    if (border && downsample) usage_error("The argument '--border <MODE>' cannot be used with '--downsample'");
+    if (border && resize) usage_error("The argument '--border <MODE>' cannot be used with '" + resize_opt + "': the resampled call has no border modes");
+    if (border && devices.size() > 1)
+        usage_error("The argument '--border <MODE>' cannot be used with more than one device: the padded call has no multi-GPU form");
     int in_pw = 0, in_ph = 0;
     // (the file's header says how large the input is: a scale that takes it beyond the largest output is refused before any device is touched)
     if (has_scale && srpng::probe_image_size(pos[0], in_pw, in_ph) && !(scaled_axis(in_pw, scale, size_w) && scaled_axis(in_ph, scale, size_h)))
@@ -1181,7 +1207,7 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < devices.size() && rc == SR_OK; ++k) {
         rc = sr_create_graph(&ctxs[k], graph, params.empty() ? nullptr : params.data(), params.size(), SR_FACTOR, devices[k]);
         if (rc == SR_OK && graph == SR_GRAPH_SR_NET) rc = sr_set_precision(ctxs[k], precision == "f32" ? SR_PRECISION_F32 : SR_PRECISION_SPLIT_F16);
-        if (rc == SR_OK && (ensemble || alpha || resize) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble, alpha and resampled calls time themselves only when asked to)
+        if (rc == SR_OK && (ensemble || alpha || resize || border) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble, alpha, border and resampled calls time themselves only when asked to)
     }
     const double t_create = ms_since(t_start);
     double t_prep = 0;
@@ -1213,6 +1239,7 @@ int main(int argc, char** argv) {
     const double t_alloc = ms_since(t_al);
     const clk::time_point t_up = clk::now();
     rc = resize ? sr_upscale_rgba8_sized(ctx, in.rgba.data(), 1, in.h, in.w, out, oh, ow, filter, resize_flags, ensemble ? ensemble : 1u)
+         : border ? sr_upscale_rgba8_border(ctx, in.rgba.data(), 1, in.h, in.w, out, border, border_pad, ensemble ? ensemble : 1u, alpha ? bleed : -1)
          : alpha ? sr_upscale_rgba8_alpha(ctx, in.rgba.data(), 1, in.h, in.w, out, bleed, ensemble ? ensemble : 1u)
          : ensemble ? sr_upscale_ensemble_rgba8(ctx, in.rgba.data(), 4, 1, in.h, in.w, out, ensemble)
          : ctxs.size() > 1 ? sr_upscale_rgba8_multi(ctxs.data(), (int)ctxs.size(), in.rgba.data(), 4, in.h, in.w, out)
