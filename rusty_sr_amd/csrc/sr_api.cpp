@@ -762,6 +762,41 @@ int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_
     return SR_OK;
 }
 
+int sr_host_image_call(sr_ctx* c, bool network, const void* in, size_t in_bytes, void* out, size_t out_bytes, const sr_image_work& work) {
+    return sr_host_call(
+        c, network, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
+        [&](hipStream_t s) { return sr_hip_status(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s)); },
+        [&](hipStream_t s) { return work(c->d_in[0].p, c->d_out[0].p, s); },
+        [&](hipStream_t s) { return sr_hip_status(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s)); });
+}
+
+int sr_reserve_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group) {
+    bool fits = true;
+    for (const sr_buf_want& w : group) fits = fits && w.bytes <= w.buf->cap;
+    if (fits) return SR_OK;
+    if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
+    size_t all = 0;
+    if (!sr_sum_wants(group, &all) || all > c->total_mem) return SR_E_NOMEM;
+    return sr_ensure_bufs(c, group);
+}
+
+int sr_net_check(const sr_ctx* c, const void* in, const void* out, int n, int h, int w, unsigned members) {
+    if (!c || !in || !out) return SR_E_INVALID;
+    if (c->graph != SR_GRAPH_SR_NET && c->graph != SR_GRAPH_BILINEAR) return SR_E_INVALID;
+    if (n < 1 || h < 1 || w < 1 || h > INT32_MAX / c->factor || w > INT32_MAX / c->factor) return SR_E_INVALID;
+    if (members == 0 || members > 255u) return SR_E_INVALID;
+    if (members != 1u && c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    return SR_OK;
+}
+
+int sr_net_queue(sr_ctx* c, const void* d_in, bool u8, int ch, int n, int h, int w, void* d_out, bool out_u8, unsigned members, hipStream_t s) {
+    if (members == 1u) return sr_run_stack_auto(c, d_in, u8, ch, n, h, w, 0, 0, d_out, out_u8, s);
+    const sr_net_strides at = sr_net_image_strides(c->factor, u8, ch, out_u8, h, w);
+    for (int i = 0; i < n; ++i)
+        SRCHK(sr_ensemble_queue(c, (const char*)d_in + i * at.in_img, u8, ch, h, w, (char*)d_out + i * at.out_img, out_u8, members, s));
+    return SR_OK;
+}
+
 namespace {
 
 // One pass of the conv stack over rows [top, bot) of n images of H x W on one stream with one workspace: planned first

@@ -78,9 +78,7 @@ int sr_degrade_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h,
     sr_plan_clear(c);
     sr_degrade_one job;
     SRCHK(plan_degrade(c, d_hr, in_channels, h, w, factor, y0, x0, frame_h, frame_w, member, deg, d_lr_rgb, &job));
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    return queue_degrade(c, job, d_lr_rgb, (hipStream_t)stream);
+    return sr_on_device(c, [&] { return queue_degrade(c, job, d_lr_rgb, (hipStream_t)stream); });
 }
 
 int sr_degrade_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int factor, int y0, int x0, int frame_h, int frame_w, int member,
@@ -89,20 +87,10 @@ int sr_degrade_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w
     sr_degrade_one job;
     SRCHK(plan_degrade(c, hr, in_channels, h, w, factor, y0, x0, frame_h, frame_w, member, deg, lr_rgb, &job));
     const size_t in_bytes = (size_t)h * w * in_channels, out_bytes = (size_t)(frame_h / factor) * (frame_w / factor) * 3;
-    return sr_host_call(
-        c, false, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, hr, in_bytes, hipMemcpyHostToDevice, s));
-            return SR_OK;
-        },
-        [&](hipStream_t s) -> int {
-            job.d.px = (const uint8_t*)c->d_in[0].p;
-            return queue_degrade(c, job, (uint8_t*)c->d_out[0].p, s);
-        },
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(lr_rgb, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
-            return SR_OK;
-        });
+    return sr_host_image_call(c, false, hr, in_bytes, lr_rgb, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        job.d.px = (const uint8_t*)d_in;
+        return queue_degrade(c, job, (uint8_t*)d_out, s);
+    });
 }
 
 }  // extern "C"

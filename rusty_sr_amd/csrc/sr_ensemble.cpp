@@ -37,49 +37,31 @@ int check_image_args(const sr_ctx* c, const void* in, const void* out, bool img_
     return sr_ensemble_check(c, members, h, w);
 }
 
-// n images, one after another, on device buffers
+// n images, one after another, on device buffers: every mask, member 0 alone too (sr_net_queue runs that one as one batch)
 int queue_batch(sr_ctx* c, const void* d_in, bool img_u8, int ch, int n, int h, int w, void* d_out, bool out_u8, unsigned members, hipStream_t s) {
-    const size_t f = (size_t)c->factor;
-    const size_t in_img = (size_t)h * w * (img_u8 ? (size_t)ch : 3 * sizeof(float));
-    const size_t out_img = f * h * f * w * (out_u8 ? 4 : 3 * sizeof(float));
-    for (int i = 0; i < n; ++i) {
-        const int rc = sr_ensemble_queue(c, (const char*)d_in + i * in_img, img_u8, ch, h, w, (char*)d_out + i * out_img, out_u8, members, s);
-        if (rc != SR_OK) return rc;
-    }
+    const sr_net_strides at = sr_net_image_strides(c->factor, img_u8, ch, out_u8, h, w);
+    for (int i = 0; i < n; ++i)
+        SRCHK(sr_ensemble_queue(c, (const char*)d_in + i * at.in_img, img_u8, ch, h, w, (char*)d_out + i * at.out_img, out_u8, members, s));
     return SR_OK;
 }
 
-// The host-pointer calls: one upload, the device call, one download (sr_host_call).  sr_last_timing: total = every pass and pixel move of the
-// call; the stage times are the last pass's.
+// The host-pointer calls (sr_host_image_call).  sr_last_timing: total = every pass and pixel move of the call; the stage times are the last
+// pass's.
 int ensemble_host(sr_ctx* c, const void* in, bool img_u8, int ch, int n, int h, int w, void* out, bool out_u8, unsigned members) {
     sr_plan_clear(c);
-    const int rc = check_image_args(c, in, out, img_u8, ch, n, h, w, members);
-    if (rc != SR_OK) return rc;
-    const size_t f = (size_t)c->factor;
-    const size_t in_bytes = (size_t)n * h * w * (img_u8 ? (size_t)ch : 3 * sizeof(float));
-    const size_t out_bytes = (size_t)n * f * h * f * w * (out_u8 ? 4 : 3 * sizeof(float));
-    return sr_host_call(
-        c, true, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
-            return SR_OK;
-        },
-        [&](hipStream_t s) { return queue_batch(c, c->d_in[0].p, img_u8, ch, n, h, w, c->d_out[0].p, out_u8, members, s); },
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
-            return SR_OK;
-        });
+    SRCHK(check_image_args(c, in, out, img_u8, ch, n, h, w, members));
+    const sr_net_strides at = sr_net_image_strides(c->factor, img_u8, ch, out_u8, h, w);
+    return sr_host_image_call(c, true, in, n * at.in_img, out, n * at.out_img, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return queue_batch(c, d_in, img_u8, ch, n, h, w, d_out, out_u8, members, s);
+    });
 }
 
 int ensemble_dev(sr_ctx* c, const void* d_in, bool img_u8, int ch, int n, int h, int w, void* d_out, bool out_u8, unsigned members,
                  void* stream) {
     sr_plan_clear(c);
-    const int rc = check_image_args(c, d_in, d_out, img_u8, ch, n, h, w, members);
-    if (rc != SR_OK) return rc;
+    SRCHK(check_image_args(c, d_in, d_out, img_u8, ch, n, h, w, members));
     if (!sr_dword_aligned(d_out) || (!img_u8 && !sr_dword_aligned(d_in))) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    return queue_batch(c, d_in, img_u8, ch, n, h, w, d_out, out_u8, members, (hipStream_t)stream);
+    return sr_on_device(c, [&] { return queue_batch(c, d_in, img_u8, ch, n, h, w, d_out, out_u8, members, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -101,21 +83,14 @@ int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
         return sr_run_stack_auto(c, d_img, img_u8, img_ch, 1, h, w, 0, 0, d_out, out_u8, s);
     const int f = c->factor, OH = f * h, OW = f * w;
     const int count = __builtin_popcount(members);
-    // Everything the call needs beside the plain call's workspace, before anything is launched.  A shape that can never fit is refused by
-    // arithmetic (more than the device has at all, or a grid beyond what a launch takes) without an allocation being attempted; one that
-    // does not fit beside what is allocated already fails in hipMalloc below, with the same answer.  Calls whose buffers are there already
-    // -- every call of a shape but the first -- ask the runtime nothing.
+    // Everything the call needs beside the plain call's workspace, before anything is launched: a grid beyond what a launch takes is
+    // refused here, memory by sr_reserve_bufs.
     const size_t map_bytes = (size_t)OH * OW * 3 * sizeof(float);
     const size_t in_bytes = (img_u8 || (members & ~1u)) ? (size_t)h * w * 3 * sizeof(float) : 0;
     const size_t acc_bytes = out_u8 && count > 1 ? map_bytes : 0;
     const size_t blocks = std::max(sr_ens_blocks(OH, OW, false), sr_ens_blocks(OH, OW, true));
     if (blocks > (size_t)INT32_MAX) return SR_E_NOMEM;
-    if (in_bytes > c->d_ein.cap || map_bytes > c->d_eout.cap || acc_bytes > c->d_eacc.cap) {
-        if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
-        if (map_bytes + acc_bytes + in_bytes > c->total_mem) return SR_E_NOMEM;
-    }
-    int rc = sr_ensure_bufs(c, {{&c->d_ein, in_bytes}, {&c->d_eout, map_bytes}, {&c->d_eacc, acc_bytes}});
-    if (rc != SR_OK) return rc;
+    SRCHK(sr_reserve_bufs(c, {{&c->d_ein, in_bytes}, {&c->d_eout, map_bytes}, {&c->d_eacc, acc_bytes}}));
     float* acc = out_u8 ? (float*)c->d_eacc.p : (float*)d_out;
     const float scale = 1.0f / (float)count;
     int done = 0;
@@ -128,8 +103,7 @@ int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
             HIPCHK(c, sr_launch_ens_input(d_img, img_u8, img_ch, c->d_ein.p, member_map(k, false, hk, wk), s));
             img = c->d_ein.p;
         }
-        rc = sr_run_stack_auto(c, img, false, 3, 1, hk, wk, 0, 0, c->d_eout.p, false, s);
-        if (rc != SR_OK) return rc;
+        SRCHK(sr_run_stack_auto(c, img, false, 3, 1, hk, wk, 0, 0, c->d_eout.p, false, s));
         ++done;
         HIPCHK(c, sr_launch_ens_accumulate((const float*)c->d_eout.p, acc, d_out, out_u8, done == 1, done == count, scale,
                                            member_map(k, true, OH, OW), s));

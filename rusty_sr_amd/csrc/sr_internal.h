@@ -302,6 +302,37 @@ using sr_host_phase = std::function<int(hipStream_t)>;
 int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_list<sr_buf_want> staging, const sr_host_phase& upload,
                  const sr_host_phase& work, const sr_host_phase& download);
 
+// ---- What a call that wraps the network (ensemble, transparency, borders, any size) or stands beside it (resize, degrade) is made of.
+// A new wrapper writes its checks, its sizes and its work lambda, nothing else.
+inline int sr_hip_status(sr_ctx* c, hipError_t e) {  // HIPCHK as a value: the status of a lambda that is one runtime call
+    HIPCHK(c, e);
+    return SR_OK;
+}
+// The body of a device-pointer entry point -- a callable that queues on the caller's stream and returns a status -- with the context's
+// device current and the caller's restored.  The arguments, the alignment rule of the call included, are checked before it.
+template <class Body>
+int sr_on_device(sr_ctx* c, Body&& body) {
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    return body();
+}
+// What every call that runs the network on a batch refuses for its arguments alone (SR_E_INVALID): a null context or image, a graph
+// other than sr_net / bilinear, a shape below 1 or beyond INT32_MAX / factor, a mask outside 1..255, a mask other than 1 off sr_net.
+int sr_net_check(const sr_ctx* c, const void* in, const void* out, int n, int h, int w, unsigned members);
+// The network on n images on device buffers, queued on s: the plain call's path for the whole batch (members == 1), else the ensemble
+// image by image.  u8: ch bytes a pixel in, else f32 RGB; out_u8: RGBA8 out, else f32 RGB.  The context's device is current.
+int sr_net_queue(sr_ctx* c, const void* d_in, bool u8, int ch, int n, int h, int w, void* d_out, bool out_u8, unsigned members, hipStream_t s);
+// sr_ensure_bufs for a job's workspace, with the refusal by arithmetic before it: wants that all fit what is allocated ask the runtime
+// nothing; otherwise a sum of the wanted bytes beyond the device's whole memory (asked for once a context) is SR_E_NOMEM without an
+// allocation being attempted.  Only what the context itself allocates counts: a shape that passes and still cannot run beside the
+// caller's own buffers is refused with the same status before any launch -- by the staging buffers of a host-pointer call, by hipMalloc
+// in sr_ensure_bufs, or by the network's own size rule.  The context's device is current.
+int sr_reserve_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group);
+// sr_host_call for a call that uploads one image batch and downloads one: staging d_in[0] / d_out[0], one copy each way, SR_TIMES_PARTS;
+// work(d_in, d_out, s) queues everything between the copies on the staged buffers.
+using sr_image_work = std::function<int(const void* d_in, void* d_out, hipStream_t s)>;
+int sr_host_image_call(sr_ctx* c, bool network, const void* in, size_t in_bytes, void* out, size_t out_bytes, const sr_image_work& work);
+
 void sr_comm_release(sr_ctx* c);  // sr_comm.cpp: destroy the communicator and its buffers (called by sr_destroy)
 
 // ---- validation pass (sr_valid.hip kernels, sr_valid.cpp host side)

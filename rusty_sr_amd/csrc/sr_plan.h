@@ -81,3 +81,20 @@ inline std::vector<sr_row_share> sr_multi_shares(int n_ctx, int h) {
     if (used > 1 && share[used - 1].hi - share[used - 1].lo < SR_HALO) { share[used - 2].hi = h; share.pop_back(); }
     return share;
 }
+
+// ---- the sizes of a composed call (sr_api.cpp sr_reserve_bufs, sr_net_queue): arithmetic alone, like the planners
+// the sum of the `bytes` of a group of wants, or false where it does not fit a size_t
+template <class Wants>
+bool sr_sum_wants(const Wants& group, size_t* out) {
+    *out = 0;
+    for (const auto& w : group)
+        if (__builtin_add_overflow(*out, (size_t)w.bytes, out)) return false;
+    return true;
+}
+// One image of a batch the network reads (h x w; u8 with ch bytes a pixel, else f32 RGB) and the one it writes (f h x f w; RGBA8, else
+// f32 RGB), in bytes: image i of the batch lies i times that far into its buffer.
+struct sr_net_strides { size_t in_img, out_img; };
+inline sr_net_strides sr_net_image_strides(int factor, bool u8, int ch, bool out_u8, int h, int w) {
+    const size_t f = (size_t)factor;
+    return {(size_t)h * w * (u8 ? (size_t)ch : 3 * sizeof(float)), f * h * f * w * (out_u8 ? 4 : 3 * sizeof(float))};
+}

@@ -54,20 +54,12 @@ int plan_resize(const void* in, int in_pixels, int n, int h, int w, const void* 
     return SR_OK;
 }
 
-// The workspace of a job (and, for the _sized calls, in_bytes of d_rin and net_bytes of d_rnet beside it), all or nothing.  A shape that
-// can never fit is refused by arithmetic -- more than the device has at all, or a grid beyond what a launch takes -- before an allocation is
-// attempted; the context's device is current.
+// The workspace of a job (and, for the _sized calls, in_bytes of d_rin and net_bytes of d_rnet beside it), all or nothing.  A grid beyond
+// what a launch takes is refused before an allocation is attempted, as is memory (sr_reserve_bufs); the context's device is current.
 int reserve(sr_ctx* c, ResizeJob& j, size_t in_bytes, size_t net_bytes) {
     if (sr_resize_h_blocks((size_t)j.n * j.h, j.x) > (size_t)INT32_MAX || sr_resize_v_blocks(j.n, j.oh, j.ow) > (size_t)INT32_MAX)
         return SR_E_NOMEM;
-    if (j.tab_bytes > c->d_rtab.cap || j.mid_bytes > c->d_rmid.cap || in_bytes > c->d_rin.cap || net_bytes > c->d_rnet.cap) {
-        if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
-        size_t all = 0;
-        if (__builtin_add_overflow(j.tab_bytes, j.mid_bytes, &all) || __builtin_add_overflow(all, in_bytes, &all) ||
-            __builtin_add_overflow(all, net_bytes, &all) || all > c->total_mem)
-            return SR_E_NOMEM;
-    }
-    SRCHK(sr_ensure_bufs(c, {{&c->d_rtab, j.tab_bytes}, {&c->d_rmid, j.mid_bytes}, {&c->d_rin, in_bytes}, {&c->d_rnet, net_bytes}}));
+    SRCHK(sr_reserve_bufs(c, {{&c->d_rtab, j.tab_bytes}, {&c->d_rmid, j.mid_bytes}, {&c->d_rin, in_bytes}, {&c->d_rnet, net_bytes}}));
     // the tables: [x.lo][x.cnt][y.lo][y.cnt][x.w][y.w]
     int* p = (int*)c->d_rtab.p;
     j.x.lo = p; j.x.cnt = p + j.ow;
@@ -95,11 +87,7 @@ struct SizedJob {
 // everything sr_upscale_rgba8_sized[_dev] refuse for their arguments alone
 int plan_sized(const sr_ctx* c, const void* in, const void* out, int n, int h, int w, int oh, int ow, int filter, unsigned flags, unsigned members,
                SizedJob* job) {
-    if (!c || !in || !out || n < 1 || h < 1 || w < 1) return SR_E_INVALID;
-    if (c->graph != SR_GRAPH_SR_NET && c->graph != SR_GRAPH_BILINEAR) return SR_E_INVALID;
-    if (h > INT32_MAX / c->factor || w > INT32_MAX / c->factor) return SR_E_INVALID;
-    if (members == 0 || members > 255u) return SR_E_INVALID;
-    if (members != 1u && c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    SRCHK(sr_net_check(c, in, out, n, h, w, members));
     const int fh = c->factor * h, fw = c->factor * w;
     // (the resampling reads the workspace, never the caller's image: `in` stands in for its input so that in == out is refused here too)
     SRCHK(plan_resize(in, SR_PIXELS_F32, n, fh, fw, out, SR_PIXELS_RGBA8, oh, ow, filter, flags, &job->resize));
@@ -116,13 +104,7 @@ int queue_sized(sr_ctx* c, SizedJob& j, const uint8_t* d_in, int h, int w, uint8
     const sr_ens_map same{n * h, w, 0, 0, 0};
     if (sr_ens_blocks(same.DH, same.DW, false) > (size_t)INT32_MAX) return SR_E_NOMEM;
     HIPCHK(c, sr_launch_ens_input(d_in, true, 4, c->d_rin.p, same, s));
-    const size_t in_img = (size_t)h * w * 3, out_img = (size_t)j.resize.h * j.resize.w * 3;  // floats
-    if (members == 1u) {
-        SRCHK(sr_run_stack_auto(c, c->d_rin.p, false, 3, n, h, w, 0, 0, c->d_rnet.p, false, s));
-    } else {
-        for (int i = 0; i < n; ++i)
-            SRCHK(sr_ensemble_queue(c, (const float*)c->d_rin.p + i * in_img, false, 3, h, w, (float*)c->d_rnet.p + i * out_img, false, members, s));
-    }
+    SRCHK(sr_net_queue(c, c->d_rin.p, false, 3, n, h, w, c->d_rnet.p, false, members, s));
     return queue_resize(c, j.resize, c->d_rnet.p, false, d_out, true, s);
 }
 
@@ -155,10 +137,10 @@ int sr_resize_dev(sr_ctx* c, const void* d_in, int in_pixels, int n, int h, int 
     ResizeJob j;
     SRCHK(plan_resize(d_in, in_pixels, n, h, w, d_out, out_pixels, oh, ow, filter, flags, &j));
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    SRCHK(reserve(c, j, 0, 0));
-    return queue_resize(c, j, d_in, in_pixels == SR_PIXELS_RGBA8, d_out, out_pixels == SR_PIXELS_RGBA8, (hipStream_t)stream);
+    return sr_on_device(c, [&]() -> int {
+        SRCHK(reserve(c, j, 0, 0));
+        return queue_resize(c, j, d_in, in_pixels == SR_PIXELS_RGBA8, d_out, out_pixels == SR_PIXELS_RGBA8, (hipStream_t)stream);
+    });
 }
 
 int sr_resize_rgba8(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* out, int oh, int ow, int filter, unsigned flags) {
@@ -167,20 +149,10 @@ int sr_resize_rgba8(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* 
     ResizeJob j;
     SRCHK(plan_resize(in, SR_PIXELS_RGBA8, n, h, w, out, SR_PIXELS_RGBA8, oh, ow, filter, flags, &j));
     const size_t in_bytes = (size_t)n * h * w * pixel_bytes(SR_PIXELS_RGBA8), out_bytes = (size_t)n * oh * ow * pixel_bytes(SR_PIXELS_RGBA8);
-    return sr_host_call(
-        c, false, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
-            return SR_OK;
-        },
-        [&](hipStream_t s) -> int {
-            SRCHK(reserve(c, j, 0, 0));
-            return queue_resize(c, j, c->d_in[0].p, true, c->d_out[0].p, true, s);
-        },
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
-            return SR_OK;
-        });
+    return sr_host_image_call(c, false, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) -> int {
+        SRCHK(reserve(c, j, 0, 0));
+        return queue_resize(c, j, d_in, true, d_out, true, s);
+    });
 }
 
 int sr_upscale_rgba8_sized_dev(sr_ctx* c, const uint8_t* d_in, int n, int h, int w, uint8_t* d_out, int oh, int ow, int filter, unsigned flags,
@@ -189,9 +161,7 @@ int sr_upscale_rgba8_sized_dev(sr_ctx* c, const uint8_t* d_in, int n, int h, int
     SizedJob j;
     SRCHK(plan_sized(c, d_in, d_out, n, h, w, oh, ow, filter, flags, members, &j));
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
-    sr_device_guard restore_device;
-    HIPCHK(c, hipSetDevice(c->device));
-    return queue_sized(c, j, d_in, h, w, d_out, members, (hipStream_t)stream);
+    return sr_on_device(c, [&] { return queue_sized(c, j, d_in, h, w, d_out, members, (hipStream_t)stream); });
 }
 
 int sr_upscale_rgba8_sized(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* out, int oh, int ow, int filter, unsigned flags,
@@ -200,17 +170,9 @@ int sr_upscale_rgba8_sized(sr_ctx* c, const uint8_t* in, int n, int h, int w, ui
     SizedJob j;
     SRCHK(plan_sized(c, in, out, n, h, w, oh, ow, filter, flags, members, &j));
     const size_t in_bytes = (size_t)n * h * w * 4, out_bytes = (size_t)n * oh * ow * 4;
-    return sr_host_call(
-        c, true, SR_TIMES_PARTS, {{&c->d_in[0], in_bytes}, {&c->d_out[0], out_bytes}},
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(c->d_in[0].p, in, in_bytes, hipMemcpyHostToDevice, s));
-            return SR_OK;
-        },
-        [&](hipStream_t s) { return queue_sized(c, j, (const uint8_t*)c->d_in[0].p, h, w, (uint8_t*)c->d_out[0].p, members, s); },
-        [&](hipStream_t s) -> int {
-            HIPCHK(c, hipMemcpyAsync(out, c->d_out[0].p, out_bytes, hipMemcpyDeviceToHost, s));
-            return SR_OK;
-        });
+    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return queue_sized(c, j, (const uint8_t*)d_in, h, w, (uint8_t*)d_out, members, s);
+    });
 }
 
 }  // extern "C"

@@ -130,18 +130,48 @@ class Engine:
 
     __del__ = close
 
+    # ---- the prologues the entry points share: a method adds its own arguments and its call ----
+    @staticmethod
+    def _host_batch(arr, dtype, channels=None):
+        """A numpy image (H,W,C) or batch (n,H,W,C) -> (arr4d, squeeze, n, h, w, c): C-contiguous, of `dtype` (None: its own), with
+        `channels` channels (None: any); squeeze: it was one image, and the result is returned as one."""
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        squeeze = arr.ndim == 3
+        if squeeze:
+            arr = arr[None]
+        n, h, w, c = arr.shape
+        if channels is not None and c != channels:
+            raise ValueError(f"expected {channels} channels")
+        return arr, squeeze, n, h, w, c
+
+    @staticmethod
+    def _host_out(out, n, oh, ow, channels, dtype):
+        """The (n,oh,ow,channels) numpy result: a new array, or the caller's `out` (any shape of that many elements) checked and reshaped."""
+        if out is None:
+            return np.empty((n, max(oh, 0), max(ow, 0), channels), dtype=dtype)
+        if out.dtype != dtype or out.size != n * oh * ow * channels or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {'u8' if dtype == np.uint8 else 'f32'} array of n*oh*ow*{channels} elements")
+        return out.reshape(n, oh, ow, channels)
+
+    @staticmethod
+    def _dev_batch(x, dtype, channels=None):
+        """A contiguous (n,H,W,C) tensor on a GPU, of numpy `dtype` and `channels` channels (None: any) -> (n, h, w, c)."""
+        import torch
+        assert x.is_cuda and x.dtype == getattr(torch, np.dtype(dtype).name) and x.is_contiguous() and x.dim() == 4
+        assert channels is None or x.shape[-1] == channels
+        return tuple(x.shape)
+
+    @staticmethod
+    def _dev_out(out, shape, dtype, device):
+        """The caller's `out`, or a new tensor of that shape and numpy `dtype` on the device."""
+        import torch
+        return out if out is not None else torch.empty(tuple(shape), dtype=getattr(torch, np.dtype(dtype).name), device=device)
+
     # ---- host-memory entry points (numpy in, numpy out) --------------------
     def upscale_f32(self, x: np.ndarray) -> np.ndarray:
         """(n,H,W,3) or (H,W,3) f32 in [0,1] -> (n,3H,3W,3) f32 pre-quantisation."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        squeeze = x.ndim == 3
-        if squeeze:
-            x = x[None]
-        n, h, w, c = x.shape
-        if c != 3:
-            raise ValueError("expected 3 channels")
-        oh, ow = self._out_hw(h, w)
-        out = np.empty((n, oh, ow, 3), dtype=np.float32)
+        x, squeeze, n, h, w, _ = self._host_batch(x, np.float32, 3)
+        out = self._host_out(None, n, *self._out_hw(h, w), 3, np.float32)
         fp = C.POINTER(C.c_float)
         _lib.check(self._L.sr_upscale_f32(self._ctx, x.ctypes.data_as(fp), n, h, w, out.ctypes.data_as(fp)), self._ctx)
         return out[0] if squeeze else out
@@ -149,18 +179,8 @@ class Engine:
     def upscale_rgba8(self, px: np.ndarray, out: np.ndarray = None) -> np.ndarray:
         """(n,H,W,3|4) or (H,W,3|4) u8 -> (n,3H,3W,4) u8 RGBA (alpha 255).  `out` may be a
         page-locked array from host_alloc (copies then overlap the kernels at PCIe rate)."""
-        px = np.ascontiguousarray(px, dtype=np.uint8)
-        squeeze = px.ndim == 3
-        if squeeze:
-            px = px[None]
-        n, h, w, c = px.shape
-        oh, ow = self._out_hw(h, w)
-        if out is None:
-            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
-        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
-        else:
-            out = out.reshape(n, oh, ow, 4)
+        px, squeeze, n, h, w, c = self._host_batch(px, np.uint8)
+        out = self._host_out(out, n, *self._out_hw(h, w), 4, np.uint8)
         u8p = C.POINTER(C.c_uint8)
         _lib.check(self._L.sr_upscale_rgba8(self._ctx, px.ctypes.data_as(u8p), c, n, h, w, out.ctypes.data_as(u8p)), self._ctx)
         return out[0] if squeeze else out
@@ -177,14 +197,8 @@ class Engine:
     def upscale_ensemble_f32(self, x: np.ndarray, members: int = _lib.SR_ENSEMBLE_ALL) -> np.ndarray:
         """upscale_f32 averaged over the members of the mask (bit k: flip / rotation k; 0xFF all 8, 0x0F the 4 flips, 0x03 identity and
         the column flip): (n,H,W,3) or (H,W,3) f32 -> (n,fH,fW,3) f32."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        squeeze = x.ndim == 3
-        if squeeze:
-            x = x[None]
-        n, h, w, c = x.shape
-        if c != 3:
-            raise ValueError("expected 3 channels")
-        out = np.empty((n, self.factor * h, self.factor * w, 3), dtype=np.float32)
+        x, squeeze, n, h, w, _ = self._host_batch(x, np.float32, 3)
+        out = self._host_out(None, n, self.factor * h, self.factor * w, 3, np.float32)
         fp = C.POINTER(C.c_float)
         _lib.check(self._L.sr_upscale_ensemble_f32(self._ctx, x.ctypes.data_as(fp), n, h, w, out.ctypes.data_as(fp), self._members(members)),
                    self._ctx)
@@ -192,18 +206,8 @@ class Engine:
 
     def upscale_ensemble_rgba8(self, px: np.ndarray, members: int = _lib.SR_ENSEMBLE_ALL, out: np.ndarray = None) -> np.ndarray:
         """upscale_rgba8 averaged over the members of the mask, quantised once at the end: (n,H,W,3|4) or (H,W,3|4) u8 -> (n,fH,fW,4) u8."""
-        px = np.ascontiguousarray(px, dtype=np.uint8)
-        squeeze = px.ndim == 3
-        if squeeze:
-            px = px[None]
-        n, h, w, c = px.shape
-        oh, ow = self.factor * h, self.factor * w
-        if out is None:
-            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
-        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
-        else:
-            out = out.reshape(n, oh, ow, 4)
+        px, squeeze, n, h, w, c = self._host_batch(px, np.uint8)
+        out = self._host_out(out, n, self.factor * h, self.factor * w, 4, np.uint8)
         u8p = C.POINTER(C.c_uint8)
         _lib.check(self._L.sr_upscale_ensemble_rgba8(self._ctx, px.ctypes.data_as(u8p), c, n, h, w, out.ctypes.data_as(u8p),
                                                      self._members(members)), self._ctx)
@@ -228,41 +232,29 @@ class Engine:
         return C.c_void_p(s.cuda_stream)
 
     def upscale_f32_dev(self, x, out=None, stream=None):
-        import torch
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
-        n, h, w, _ = x.shape
-        if out is None:
-            out = torch.empty((n,) + self._out_hw(h, w) + (3,), dtype=torch.float32, device=x.device)
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        out = self._dev_out(out, (n,) + self._out_hw(h, w) + (3,), np.float32, x.device)
         _lib.check(self._L.sr_upscale_f32_dev(self._ctx, C.c_void_p(x.data_ptr()), n, h, w,
                                               C.c_void_p(out.data_ptr()), self._stream_ptr(stream, x.device)), self._ctx)
         return out
 
     def upscale_rgba8_dev(self, px, out=None, stream=None):
-        import torch
-        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4
-        n, h, w, c = px.shape
-        if out is None:
-            out = torch.empty((n,) + self._out_hw(h, w) + (4,), dtype=torch.uint8, device=px.device)
+        n, h, w, c = self._dev_batch(px, np.uint8)
+        out = self._dev_out(out, (n,) + self._out_hw(h, w) + (4,), np.uint8, px.device)
         _lib.check(self._L.sr_upscale_rgba8_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w,
                                                 C.c_void_p(out.data_ptr()), self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
     def upscale_ensemble_f32_dev(self, x, members: int = _lib.SR_ENSEMBLE_ALL, out=None, stream=None):
-        import torch
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
-        n, h, w, _ = x.shape
-        if out is None:
-            out = torch.empty((n, self.factor * h, self.factor * w, 3), dtype=torch.float32, device=x.device)
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        out = self._dev_out(out, (n, self.factor * h, self.factor * w, 3), np.float32, x.device)
         _lib.check(self._L.sr_upscale_ensemble_f32_dev(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
                                                        self._members(members), self._stream_ptr(stream, x.device)), self._ctx)
         return out
 
     def upscale_ensemble_rgba8_dev(self, px, members: int = _lib.SR_ENSEMBLE_ALL, out=None, stream=None):
-        import torch
-        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4
-        n, h, w, c = px.shape
-        if out is None:
-            out = torch.empty((n, self.factor * h, self.factor * w, 4), dtype=torch.uint8, device=px.device)
+        n, h, w, c = self._dev_batch(px, np.uint8)
+        out = self._dev_out(out, (n, self.factor * h, self.factor * w, 4), np.uint8, px.device)
         _lib.check(self._L.sr_upscale_ensemble_rgba8_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w, C.c_void_p(out.data_ptr()),
                                                          self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
@@ -312,31 +304,16 @@ class Engine:
     def upscale_rgba8_alpha(self, img_rgba: np.ndarray, bleed: int = _lib.SR_ALPHA_BLEED_DEFAULT, members: int = 1, out: np.ndarray = None) -> np.ndarray:
         """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) that keeps transparency: (n,H,W,4) or (H,W,4) u8 ->
         (n,fH,fW,4) u8 whose RGB is the network's output on the image bled by `bleed` pixels and whose alpha is the input's, interpolated."""
-        px = np.ascontiguousarray(img_rgba, dtype=np.uint8)
-        squeeze = px.ndim == 3
-        if squeeze:
-            px = px[None]
-        n, h, w, c = px.shape
-        if c != 4:
-            raise ValueError("expected 4 channels")
-        oh, ow = self._out_hw(h, w)
-        if out is None:
-            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
-        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
-        else:
-            out = out.reshape(n, oh, ow, 4)
+        px, squeeze, n, h, w, _ = self._host_batch(img_rgba, np.uint8, 4)
+        out = self._host_out(out, n, *self._out_hw(h, w), 4, np.uint8)
         u8p = C.POINTER(C.c_uint8)
         _lib.check(self._L.sr_upscale_rgba8_alpha(self._ctx, px.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), int(bleed),
                                                   self._members(members)), self._ctx)
         return out[0] if squeeze else out
 
     def upscale_rgba8_alpha_dev(self, px, bleed: int = _lib.SR_ALPHA_BLEED_DEFAULT, members: int = 1, out=None, stream=None):
-        import torch
-        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
-        n, h, w, _ = px.shape
-        if out is None:
-            out = torch.empty((n,) + self._out_hw(h, w) + (4,), dtype=torch.uint8, device=px.device)
+        n, h, w, _ = self._dev_batch(px, np.uint8, 4)
+        out = self._dev_out(out, (n,) + self._out_hw(h, w) + (4,), np.uint8, px.device)
         _lib.check(self._L.sr_upscale_rgba8_alpha_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()), int(bleed),
                                                       self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
         return out
@@ -394,20 +371,8 @@ class Engine:
                              out: np.ndarray = None) -> np.ndarray:
         """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) of the image continued under `mode`: (n,H,W,4) or
         (H,W,4) u8 -> (n,fH,fW,4) u8.  bleed: None for opaque output, 0..16 to keep transparency as upscale_rgba8_alpha does."""
-        px = np.ascontiguousarray(img_rgba, dtype=np.uint8)
-        squeeze = px.ndim == 3
-        if squeeze:
-            px = px[None]
-        n, h, w, c = px.shape
-        if c != 4:
-            raise ValueError("expected 4 channels")
-        oh, ow = self._out_hw(h, w)
-        if out is None:
-            out = np.empty((n, oh, ow, 4), dtype=np.uint8)
-        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
-        else:
-            out = out.reshape(n, oh, ow, 4)
+        px, squeeze, n, h, w, _ = self._host_batch(img_rgba, np.uint8, 4)
+        out = self._host_out(out, n, *self._out_hw(h, w), 4, np.uint8)
         u8p = C.POINTER(C.c_uint8)
         _lib.check(self._L.sr_upscale_rgba8_border(self._ctx, px.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), self._border_mode(mode),
                                                    int(pad), self._members(members), self._bleed_arg(bleed)), self._ctx)
@@ -415,14 +380,8 @@ class Engine:
 
     def upscale_f32_border(self, x: np.ndarray, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1) -> np.ndarray:
         """upscale_f32 (members == 1) or upscale_ensemble_f32 of the image continued under `mode`: (n,H,W,3) or (H,W,3) f32 -> (n,fH,fW,3)."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        squeeze = x.ndim == 3
-        if squeeze:
-            x = x[None]
-        n, h, w, c = x.shape
-        if c != 3:
-            raise ValueError("expected 3 channels")
-        out = np.empty((n,) + self._out_hw(h, w) + (3,), dtype=np.float32)
+        x, squeeze, n, h, w, _ = self._host_batch(x, np.float32, 3)
+        out = self._host_out(None, n, *self._out_hw(h, w), 3, np.float32)
         fp = C.POINTER(C.c_float)
         _lib.check(self._L.sr_upscale_f32_border(self._ctx, x.ctypes.data_as(fp), n, h, w, out.ctypes.data_as(fp), self._border_mode(mode),
                                                  int(pad), self._members(members)), self._ctx)
@@ -430,22 +389,16 @@ class Engine:
 
     def upscale_rgba8_border_dev(self, px, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, bleed=None, out=None,
                                  stream=None):
-        import torch
-        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
-        n, h, w, _ = px.shape
-        if out is None:
-            out = torch.empty((n,) + self._out_hw(h, w) + (4,), dtype=torch.uint8, device=px.device)
+        n, h, w, _ = self._dev_batch(px, np.uint8, 4)
+        out = self._dev_out(out, (n,) + self._out_hw(h, w) + (4,), np.uint8, px.device)
         _lib.check(self._L.sr_upscale_rgba8_border_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
                                                        self._border_mode(mode), int(pad), self._members(members), self._bleed_arg(bleed),
                                                        self._stream_ptr(stream, px.device)), self._ctx)
         return out
 
     def upscale_f32_border_dev(self, x, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, out=None, stream=None):
-        import torch
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4 and x.shape[-1] == 3
-        n, h, w, _ = x.shape
-        if out is None:
-            out = torch.empty((n,) + self._out_hw(h, w) + (3,), dtype=torch.float32, device=x.device)
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        out = self._dev_out(out, (n,) + self._out_hw(h, w) + (3,), np.float32, x.device)
         _lib.check(self._L.sr_upscale_f32_border_dev(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, C.c_void_p(out.data_ptr()),
                                                      self._border_mode(mode), int(pad), self._members(members),
                                                      self._stream_ptr(stream, x.device)), self._ctx)
@@ -484,21 +437,12 @@ class Engine:
     def resize(self, img, size, filter="lanczos3", srgb_space=False, out=None):
         """(n,H,W,4) or (H,W,4) u8 RGBA -> u8 RGBA (sr_resize_rgba8), or (n,H,W,3) or (H,W,3) f32 -> f32 (through sr_resize_dev), numpy in
         and out, resampled to size = (oh, ow)."""
-        img = np.ascontiguousarray(img)
-        squeeze = img.ndim == 3
-        if squeeze:
-            img = img[None]
-        n, h, w, c = img.shape
+        img, squeeze, n, h, w, c = self._host_batch(img, None)
         oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
         if img.dtype == np.uint8:
             if c != 4:
                 raise ValueError("expected 4 channels")
-            if out is None:
-                out = np.empty((n, max(oh, 0), max(ow, 0), 4), dtype=np.uint8)
-            elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
-                raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
-            else:
-                out = out.reshape(n, oh, ow, 4)
+            out = self._host_out(out, n, oh, ow, 4, np.uint8)
             u8p = C.POINTER(C.c_uint8)
             _lib.check(self._L.sr_resize_rgba8(self._ctx, img.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), oh, ow, flt, flags), self._ctx)
         else:
@@ -516,32 +460,19 @@ class Engine:
     def upscale_rgba8_sized(self, px: np.ndarray, size, filter="lanczos3", srgb_space=False, members: int = 1, out: np.ndarray = None) -> np.ndarray:
         """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) to size = (oh, ow): (n,H,W,4) or (H,W,4) u8 -> (n,oh,ow,4)
         u8, the network's f32 output resampled on the device and quantised once."""
-        px = np.ascontiguousarray(px, dtype=np.uint8)
-        squeeze = px.ndim == 3
-        if squeeze:
-            px = px[None]
-        n, h, w, c = px.shape
-        if c != 4:
-            raise ValueError("expected 4 channels")
+        px, squeeze, n, h, w, _ = self._host_batch(px, np.uint8, 4)
         oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
-        if out is None:
-            out = np.empty((n, max(oh, 0), max(ow, 0), 4), dtype=np.uint8)
-        elif out.dtype != np.uint8 or out.size != n * oh * ow * 4 or not out.flags.c_contiguous:
-            raise ValueError("out must be a C-contiguous u8 array of n*oh*ow*4 elements")
-        else:
-            out = out.reshape(n, oh, ow, 4)
+        out = self._host_out(out, n, oh, ow, 4, np.uint8)
         u8p = C.POINTER(C.c_uint8)
         _lib.check(self._L.sr_upscale_rgba8_sized(self._ctx, px.ctypes.data_as(u8p), n, h, w, out.ctypes.data_as(u8p), oh, ow, flt, flags,
                                                   self._members(members)), self._ctx)
         return out[0] if squeeze else out
 
     def upscale_rgba8_sized_dev(self, px, size, filter="lanczos3", srgb_space=False, members: int = 1, out=None, stream=None):
-        import torch
-        assert px.is_cuda and px.dtype == torch.uint8 and px.is_contiguous() and px.dim() == 4 and px.shape[-1] == 4
-        n, h, w, _ = px.shape
+        n, h, w, _ = self._dev_batch(px, np.uint8, 4)
         oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
-        if out is None and oh >= 1 and ow >= 1:
-            out = torch.empty((n, oh, ow, 4), dtype=torch.uint8, device=px.device)
+        if oh >= 1 and ow >= 1:  # (else a null pointer, which the library refuses)
+            out = self._dev_out(out, (n, oh, ow, 4), np.uint8, px.device)
         _lib.check(self._L.sr_upscale_rgba8_sized_dev(self._ctx, C.c_void_p(px.data_ptr()), n, h, w,
                                                       C.c_void_p(out.data_ptr() if out is not None else None), oh, ow, flt, flags,
                                                       self._members(members), self._stream_ptr(stream, px.device)), self._ctx)

@@ -74,9 +74,23 @@ void host_call(const sr_plan_env& env, bool u8, int n, int h, int w, int y_lo, i
     for (const sr_chunk& k : plan) pass(env, k.n, k.h_ext, w, k.halo_top, k.halo_bot);
 }
 
+// The sizes of a composed call (sr_plan.h: sr_reserve_bufs' sum, sr_net_queue's strides) at their limits, before any case is read: a sum
+// that leaves size_t is reported, not wrapped, and the last image of a batch of 2^31 - 1 lies where 64-bit arithmetic puts it.
+struct want { size_t bytes; };
+bool sizes_ok() {
+    size_t sum = 0;
+    const want fits[] = {{SIZE_MAX - 7}, {0}, {7}}, over[] = {{SIZE_MAX - 7}, {0}, {8}}, twice[] = {{SIZE_MAX / 2 + 1}, {SIZE_MAX / 2 + 1}};
+    if (!sr_sum_wants(fits, &sum) || sum != SIZE_MAX || sr_sum_wants(over, &sum) || sr_sum_wants(twice, &sum)) return false;
+    const int n = INT32_MAX;
+    const sr_net_strides u8 = sr_net_image_strides(3, true, 4, true, 9, 7), f32 = sr_net_image_strides(4, false, 3, false, 9, 7), rgb = sr_net_image_strides(2, true, 3, false, 1, 1);
+    if (u8.in_img != 252 || u8.out_img != 2268 || f32.in_img != 756 || f32.out_img != 12096 || rgb.in_img != 3 || rgb.out_img != 48) return false;
+    return (size_t)(n - 1) * u8.out_img == 4870492909128ull && (size_t)(n - 1) * f32.out_img == 25975962182016ull;
+}
+
 }  // namespace
 
 int main() {
+    if (!sizes_ok()) { fprintf(stderr, "plan_check: the composed calls' sizes are wrong\n"); return 3; }
     std::string line;
     while (std::getline(std::cin, line)) {
         if (line.empty()) continue;

@@ -222,6 +222,27 @@ def test_whole_call_on_a_batch(engines):
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("members", [0x03, 0x05])
+def test_a_batch_with_an_ensemble_is_its_images(engines, precision, members):
+    """A batch under a mask other than 1 runs the ensemble image by image: byte for byte the single-image calls (which the tests above
+    hold to the primitives).  9 x 7: mask 0x05 runs a transposed member on a shape that is not square."""
+    import torch
+    e = engines(precision)
+    batch = np.random.default_rng(members).integers(0, 256, (2, 9, 7, 4), dtype=np.uint8)
+    got = e.upscale_rgba8_alpha(batch, bleed=8, members=members)
+    dev = e.upscale_rgba8_alpha_dev(torch.from_numpy(batch).cuda(), bleed=8, members=members)
+    torch.cuda.synchronize()
+    assert got.shape == (2, 27, 21, 4)
+    assert not np.array_equal(got[0], got[1])
+    for i in range(2):
+        np.testing.assert_array_equal(got[i], e.upscale_rgba8_alpha(batch[i], bleed=8, members=members), err_msg=f"image {i}")
+        one = e.upscale_rgba8_alpha_dev(torch.from_numpy(batch[i:i + 1]).cuda(), bleed=8, members=members)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(dev[i].cpu().numpy(), one[0].cpu().numpy(), err_msg=f"image {i}, device call")
+    np.testing.assert_array_equal(dev.cpu().numpy(), got)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
 def test_an_opaque_image_gives_the_plain_call(engines, precision):
     e = engines(precision)
     px = rgba_image(21, 40, 70, "opaque")

@@ -164,6 +164,33 @@ def test_composed_calls_are_the_plain_call_of_the_padded_image_cropped(engines, 
         assert same_bytes(e.upscale_rgba8_border(px[0], mode, p, members), want[0])
 
 
+@pytest.mark.parametrize("members", [0x03, 0x05])
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_a_batch_with_an_ensemble_is_its_images(engines, precision, members):
+    """A batch under a mask other than 1 runs the ensemble image by image, each from its own place in the padded buffer: byte for byte the
+    single-image calls (which the test above holds to the primitives).  9 x 7: mask 0x05 runs a transposed member on a shape that is not
+    square."""
+    import torch
+    e = engines(precision)
+    rng = np.random.default_rng(members)
+    px = rng.integers(0, 256, (2, 9, 7, 4), dtype=np.uint8)
+    x = rng.random((2, 9, 7, 3), dtype=np.float32)
+    got8, got32 = e.upscale_rgba8_border(px, "wrap", 8, members), e.upscale_f32_border(x, "wrap", 8, members)
+    dev8 = e.upscale_rgba8_border_dev(torch.from_numpy(px).cuda(), "wrap", 8, members)
+    dev32 = e.upscale_f32_border_dev(torch.from_numpy(x).cuda(), "wrap", 8, members)
+    torch.cuda.synchronize()
+    assert got8.shape == (2, 27, 21, 4) and got32.shape == (2, 27, 21, 3)
+    assert not same_bytes(got8[0], got8[1]) and not same_bytes(got32[0], got32[1])
+    for i in range(2):
+        assert same_bytes(got8[i], e.upscale_rgba8_border(px[i], "wrap", 8, members)), (i, "u8 host")
+        assert same_bytes(got32[i], e.upscale_f32_border(x[i], "wrap", 8, members)), (i, "f32 host")
+        one8 = e.upscale_rgba8_border_dev(torch.from_numpy(px[i:i + 1]).cuda(), "wrap", 8, members)
+        one32 = e.upscale_f32_border_dev(torch.from_numpy(x[i:i + 1]).cuda(), "wrap", 8, members)
+        torch.cuda.synchronize()
+        assert same_bytes(dev8[i].cpu().numpy(), one8[0].cpu().numpy()), (i, "u8 dev")
+        assert same_bytes(dev32[i].cpu().numpy(), one32[0].cpu().numpy()), (i, "f32 dev")
+
+
 def test_composed_call_where_the_plain_path_forks(engines):
     """A padded shape at sr_plan_fork's automatic threshold (exact f32, one image, fork_min_rounds = 3.5 rounds of 8-row tiles per
     resident workgroup, sr_plan.h sr_rounds): the padded image runs as two bands on two streams inside the composed call."""

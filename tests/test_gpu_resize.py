@@ -207,6 +207,27 @@ def test_sized_call_is_the_network_then_the_resampling(engines, factor, graph, p
             eng.set_precision("f32")
 
 
+@pytest.mark.parametrize("members", [0x03, 0x05])
+@pytest.mark.parametrize("precision", ["f32", "split_f16"])
+def test_sized_batch_with_an_ensemble_is_its_images(engines, precision, members):
+    """A batch under a mask other than 1 runs the ensemble image by image between the batch's f32 buffers: byte for byte the single-image
+    calls (which the test above holds to the primitives).  9 x 7: mask 0x05 runs a transposed member on a shape that is not square."""
+    import torch
+    eng = engines()
+    eng.set_precision(precision)
+    try:
+        batch, size = rgba(members, 2, 9, 7), (31, 17)
+        got = eng.upscale_rgba8_sized(batch, size, members=members)
+        dev = eng.upscale_rgba8_sized_dev(torch.from_numpy(batch).cuda(), size, members=members).cpu().numpy()
+        assert got.shape == (2, 31, 17, 4) and not np.array_equal(got[0], got[1])
+        for i in range(2):
+            np.testing.assert_array_equal(got[i], eng.upscale_rgba8_sized(batch[i], size, members=members), err_msg=f"image {i}")
+            one = eng.upscale_rgba8_sized_dev(torch.from_numpy(batch[i:i + 1]).cuda(), size, members=members).cpu().numpy()
+            np.testing.assert_array_equal(dev[i], one[0], err_msg=f"image {i}, device call")
+    finally:
+        eng.set_precision("f32")
+
+
 def offset_view(nbytes, offset):
     """nbytes of device memory `offset` bytes into a larger allocation filled with 0xA5, and the whole allocation."""
     import torch
