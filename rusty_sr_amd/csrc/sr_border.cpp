@@ -38,6 +38,23 @@ int check_upscale_args(const sr_ctx* c, const void* in, const void* out, int n, 
     return SR_OK;
 }
 
+// either launch queued on s, with its "op" line in the plan record: the grid sr_launch_border_* itself takes
+int queue_pad(sr_ctx* c, const void* d_in, bool f32, int n, int h, int w, int mode, int pad, void* d_out, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    (void)sr_border_pad_blocks(f32, n, h, w, pad, &bx, &by);
+    HIPCHK(c, sr_launch_border_pad(d_in, f32, n, h, w, mode, pad, d_out, s));
+    sr_plan_note_op(c, "pad", f32, n, bx, by);
+    return SR_OK;
+}
+
+int queue_crop(sr_ctx* c, const void* d_in, bool f32, int n, int H, int W, int y0, int x0, int ch, int cw, void* d_out, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    (void)sr_border_crop_blocks(f32, n, ch, cw, &bx, &by);
+    HIPCHK(c, sr_launch_border_crop(d_in, f32, n, H, W, y0, x0, ch, cw, d_out, s));
+    sr_plan_note_op(c, "crop", f32, n, bx, by);
+    return SR_OK;
+}
+
 // [bleed ->] [pad ->] network [-> crop] [-> merge] on device buffers, queued on s; the arguments are checked and the context's device is
 // current.  Without a border the network reads the (bled) image and writes d_out; d_bpad / d_bout are neither sized nor touched.
 int queue_composed(sr_ctx* c, const void* d_in, bool u8, int n, int h, int w, void* d_out, const Composed& a, hipStream_t s) {
@@ -62,13 +79,13 @@ int queue_composed(sr_ctx* c, const void* d_in, bool u8, int n, int h, int w, vo
                  : sr_reserve_bufs(c, {{&c->d_ableed, bled_bytes}}));
     const void* img = d_in;
     if (bleed > 0) {
-        HIPCHK(c, sr_launch_alpha_bleed((const uint8_t*)d_in, (uint8_t*)c->d_ableed.p, n, h, w, bleed, s));
+        SRCHK(sr_alpha_queue_bleed(c, (const uint8_t*)d_in, (uint8_t*)c->d_ableed.p, n, h, w, bleed, s));
         img = c->d_ableed.p;
     }
-    if (border) HIPCHK(c, sr_launch_border_pad(img, !u8, n, h, w, a.mode, pad, c->d_bpad.p, s));
+    if (border) SRCHK(queue_pad(c, img, !u8, n, h, w, a.mode, pad, c->d_bpad.p, s));
     SRCHK(sr_net_queue(c, border ? c->d_bpad.p : img, u8, u8 ? 4 : 3, n, H, W, border ? c->d_bout.p : d_out, u8, a.members, s));
-    if (border) HIPCHK(c, sr_launch_border_crop(c->d_bout.p, !u8, n, (int)f * H, (int)f * W, (int)f * pad, (int)f * pad, oh, ow, d_out, s));
-    if (alpha) HIPCHK(c, sr_launch_alpha_merge(c->factor, (const uint8_t*)d_in, (uint8_t*)d_out, n, h, w, s));
+    if (border) SRCHK(queue_crop(c, c->d_bout.p, !u8, n, (int)f * H, (int)f * W, (int)f * pad, (int)f * pad, oh, ow, d_out, s));
+    if (alpha) SRCHK(sr_alpha_queue_merge(c, (const uint8_t*)d_in, (uint8_t*)d_out, n, h, w, s));
     return SR_OK;
 }
 
@@ -95,7 +112,7 @@ int pad_dev(sr_ctx* c, const void* d_in, bool f32, int n, int h, int w, int mode
     if (!mode_ok(mode) || pad < 0 || pad > SR_BORDER_PAD_MAX) return SR_E_INVALID;
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out) || d_in == d_out) return SR_E_INVALID;
     if (sr_border_pad_blocks(f32, n, h, w, pad) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    return sr_on_device(c, [&] { return sr_hip_status(c, sr_launch_border_pad(d_in, f32, n, h, w, mode, pad, d_out, (hipStream_t)stream)); });
+    return sr_on_device(c, [&] { return queue_pad(c, d_in, f32, n, h, w, mode, pad, d_out, (hipStream_t)stream); });
 }
 
 int crop_dev(sr_ctx* c, const void* d_in, bool f32, int n, int H, int W, int y0, int x0, int ch, int cw, void* d_out, void* stream) {
@@ -104,7 +121,7 @@ int crop_dev(sr_ctx* c, const void* d_in, bool f32, int n, int H, int W, int y0,
     if (y0 < 0 || x0 < 0 || ch > H - y0 || cw > W - x0) return SR_E_INVALID;  // the window lies inside its image
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out) || d_in == d_out) return SR_E_INVALID;
     if (sr_border_crop_blocks(f32, n, ch, cw) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    return sr_on_device(c, [&] { return sr_hip_status(c, sr_launch_border_crop(d_in, f32, n, H, W, y0, x0, ch, cw, d_out, (hipStream_t)stream)); });
+    return sr_on_device(c, [&] { return queue_crop(c, d_in, f32, n, H, W, y0, x0, ch, cw, d_out, (hipStream_t)stream); });
 }
 
 }  // namespace

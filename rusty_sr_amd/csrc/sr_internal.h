@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <functional>
 #include <initializer_list>
 #include <string>
@@ -105,7 +106,8 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     hipEvent_t ev_layer[4] = {nullptr, nullptr, nullptr, nullptr};  // one-process sharded call in that mode: "stage st of this context is done"
     // What the last public call ran (sr_get_experiment "plan", a test hook): the host pipeline's chunk plan, the fork decision of a device
     // call, one line per stage launch -- identical consecutive lines as one, with a count.  Host-side text written where the decisions are
-    // made; cleared by every public entry point.
+    // made; cleared by every public entry point.  The pixel operators around the network (pad, crop, bleed, merge, the resampler's two
+    // passes) write an "op" line per launch -- its grid as the launcher's own *_blocks function gives it (sr_plan_note_op).
     std::vector<std::pair<std::string, int>> plan_rec;
     // ---- validation pass (sr_valid.cpp): the forward half of the training graph, grown on demand, freed by sr_destroy
     sr_buf d_vhr;                                   // the HR image of a host-pointer call
@@ -148,6 +150,17 @@ inline void sr_plan_clear(sr_ctx* c) {
 inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     if (!c->plan_rec.empty() && c->plan_rec.back().first == line) ++c->plan_rec.back().second;
     else c->plan_rec.emplace_back(line, 1);
+}
+
+// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
+// px: the pixels the kernel is instantiated on (resize_h: its input's, resize_v: its output's); bx / by: workgroups along a row and along
+// the rows of one image (resize_h: of the batch's n h rows), from the *_blocks function the launcher itself calls.
+inline void sr_plan_note_op(sr_ctx* c, const char* name, bool f32, int n, unsigned bx, unsigned by, const char* form = nullptr, int f = 0) {
+    char line[128], tail[48] = "";
+    if (form) snprintf(tail, sizeof tail, " form=%s", form);
+    else if (f) snprintf(tail, sizeof tail, " f=%d", f);
+    snprintf(line, sizeof line, "op name=%s px=%s n=%d bx=%u by=%u%s", name, f32 ? "f32" : "u8", n, bx, by, tail);
+    sr_plan_note(c, line);
 }
 
 // The device entry points' buffers that the kernels address as 32-bit words (include/srhip.h): every RGBA output -- the final stage
@@ -438,6 +451,9 @@ size_t sr_alpha_merge_blocks(int factor, int n, int h, int w, unsigned* blocks_x
 hipError_t sr_launch_alpha_bleed(const uint8_t* d_in, uint8_t* d_out, int n, int h, int w, int radius, hipStream_t s);
 // byte 3 of the n images of factor h x factor w at d_out <- the alpha of d_lr (n x h x w RGBA8) interpolated; both 4-byte aligned
 hipError_t sr_launch_alpha_merge(int factor, const uint8_t* d_lr, uint8_t* d_out, int n, int h, int w, hipStream_t s);
+// ... either launch queued on s with its "op" line in the plan record (sr_alpha.cpp): what the entry points and the composed calls run
+int sr_alpha_queue_bleed(sr_ctx* c, const uint8_t* d_in, uint8_t* d_out, int n, int h, int w, int radius, hipStream_t s);
+int sr_alpha_queue_merge(sr_ctx* c, const uint8_t* d_lr, uint8_t* d_out, int n, int h, int w, hipStream_t s);
 void sr_alpha_release(sr_ctx* c);  // free the bleed buffer (called by sr_destroy)
 
 // ---- borders (sr_border.hip kernels, sr_border.cpp host side; include/srhip.h "Borders")

@@ -69,11 +69,20 @@ int reserve(sr_ctx* c, ResizeJob& j, size_t in_bytes, size_t net_bytes) {
     return SR_OK;
 }
 
-// the three launches of a reserved job on s
+// the three launches of a reserved job on s; the two passes leave their "op" lines in the plan record -- the grids and the form
+// sr_launch_resize_h / _v themselves take
 int queue_resize(sr_ctx* c, const ResizeJob& j, const void* d_in, bool in_u8, void* d_out, bool out_u8, hipStream_t s) {
+    const size_t rows = (size_t)j.n * j.h;
+    unsigned hx = 0, vx = 0, groups = 0;
+    int cap = 0;
+    const size_t h_blocks = sr_resize_h_blocks(rows, j.x, &hx);
+    const int per = sr_resize_h_form(j.x, &cap);
+    (void)sr_resize_v_blocks(j.n, j.oh, j.ow, &vx, &groups);
     HIPCHK(c, sr_launch_resize_taps(j.x, j.y, j.filter, s));
-    HIPCHK(c, sr_launch_resize_h(d_in, in_u8, j.linear, (size_t)j.n * j.h, j.x, (float*)c->d_rmid.p, s));
+    HIPCHK(c, sr_launch_resize_h(d_in, in_u8, j.linear, rows, j.x, (float*)c->d_rmid.p, s));
+    sr_plan_note_op(c, "resize_h", !in_u8, j.n, hx, hx ? (unsigned)(h_blocks / hx) : 0u, cap == 0 ? "direct" : per == 1 ? "staged1" : "staged4");
     HIPCHK(c, sr_launch_resize_v((const float*)c->d_rmid.p, j.n, j.ow, j.y, d_out, out_u8, j.linear, s));
+    sr_plan_note_op(c, "resize_v", !out_u8, j.n, vx, groups);
     return SR_OK;
 }
 

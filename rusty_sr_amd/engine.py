@@ -55,11 +55,16 @@ def img_to_data(pixels: np.ndarray) -> np.ndarray:
 
 def parse_plan(text: str) -> dict:
     """A plan record (the text of sr_get_experiment "plan") as data:
-    {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...], "aux": [dict, ...]}.
+    {"host": [(kind, [sizes], (y_lo, y_hi) | None)], "fork": [(forked, rows_a, rows_b)], "launches": [dict, ...], "aux": [dict, ...],
+    "ops": [dict, ...]}.
     host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
     st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
-    parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid."""
-    rec = {"host": [], "fork": [], "launches": [], "aux": []}
+    parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid.  An op (a launch of a pixel
+    operator: pad, crop, bleed, merge, resize_h, resize_v, in the order they were queued): name, px ("u8" | "f32": the pixels the kernel is
+    instantiated on -- resize_h its input's, resize_v its output's), n, bx, by (workgroups along a row and along the rows of one image;
+    resize_h: groups of the batch's n h rows), count, and form ("staged4" | "staged1" | "direct", resize_h) or f (the factor, merge).
+    Lines of any other kind are ignored."""
+    rec = {"host": [], "fork": [], "launches": [], "aux": [], "ops": []}
     for line in text.splitlines():
         words = line.split()
         count = 1
@@ -88,6 +93,13 @@ def parse_plan(text: str) -> dict:
                 d[k] = int(d[k])
             d["count"] = count
             rec["aux"].append(d)
+        elif words[0] == "op":
+            d = dict(w.split("=", 1) for w in words[1:])
+            for k in ("n", "bx", "by", "f"):
+                if k in d:
+                    d[k] = int(d[k])
+            d["count"] = count
+            rec["ops"].append(d)
     return rec
 
 

@@ -20,7 +20,10 @@ pytestmark = pytest.mark.gpu
 PRECISIONS = ("f32", "split_f16")
 MODES = border_ref.MODES
 CLI = os.path.join(ROOT, "rusty_sr_amd", "bin", "rusty_sr")
-SHAPES = ((1, 1), (1, 37), (5, 3), (16, 16), (33, 61), (64, 257))   # 1 x 1, one row, both sides below the pad, whole groups, ragged rows, two workgroups across
+# 1 x 1, one row, both sides below the pad, whole groups, ragged rows, a wide row.  (No case here has two workgroups across: the widest,
+# (64, 257) at pad 32, is 321 dwords a row in RGBA8 and 963 in f32, and a workgroup covers 1024.  Two workgroups across, in a batch and at
+# every offset: tests/test_gpu_operator_grids.py.)
+SHAPES = ((1, 1), (1, 37), (5, 3), (16, 16), (33, 61), (64, 257))
 PADS = (0, 1, 7, 8, 32)
 ALL8 = 0xFF   # the mask of all 8 members
 
