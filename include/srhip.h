@@ -734,6 +734,76 @@ int sr_upscale_rgba8_border(sr_ctx* ctx, const uint8_t* in_rgba, int n, int h, i
                             int bleed);
 int sr_upscale_f32_border(sr_ctx* ctx, const float* in, int n, int h, int w, float* out, int mode, int pad, unsigned members);
 
+/* ---- Video: planar YCbCr frames in and out, a frame stream ----
+ * The reference takes RGB images (main.rs:164-175); a clip is YCbCr, and converting it on the CPU and quantising it twice costs more
+ * than the network.  These calls take and give planar 8-bit frames laid out exactly like a Y4M frame payload: Y (h x w), then Cb, then
+ * Cr, each ch x cw -- ch = ceil(h / 2), cw = ceil(w / 2) for SR_YUV_420, h x w for SR_YUV_444 -- contiguous, so a plane may start at
+ * any byte.  UNPINNED: the reference has no counterpart; tests/yuv_ref.py states the rule in numpy (f64) and the kernels equal it bit
+ * for bit.  Frames are independent: there is no temporal processing.
+ *   Format    subsampling SR_YUV_420 | SR_YUV_444; siting (4:2:0 only) SR_YUV_SITING_CENTER (JPEG, plain C420) | SR_YUV_SITING_LEFT
+ *             (MPEG-2: horizontally co-sited with the even columns; vertically centred under both); matrix SR_YUV_BT601 (Kr 0.299,
+ *             Kb 0.114) | SR_YUV_BT709 (0.2126, 0.0722); range SR_YUV_LIMITED (Y 16..235, C 16..240) | SR_YUV_FULL.
+ *   Constants (f64, formed once on the host): Kg = 1 - Kr - Kb; ib = 1 / (2 (1 - Kb)), ir = 1 / (2 (1 - Kr)), ig = 1 / Kg; sy = 1 / 219,
+ *             sc = 1 / 224 (full range: both 1 / 255).  All arithmetic is f64, in the written order, without contraction.
+ *   To RGB    4:2:0 chroma is upsampled bilinearly, indices clamped to the plane: vertically, and horizontally under CENTER, luma index
+ *             2i takes (C[i-1] + 3 C[i]) / 4 and 2i + 1 takes (3 C[i] + C[i+1]) / 4; horizontally under LEFT an even x takes C[x / 2],
+ *             an odd x (C[j] + C[j+1]) / 2.  Both axes together are an integer sum of wy wx C over 16, exact.  Then
+ *             y = (Y - 16) sy (full: Y sy), cb = (Cb - 128) sc, cr = (Cr - 128) sc;  r = y + (2 (1 - Kr)) cr;  b = y + (2 (1 - Kb)) cb;
+ *             g = ((y - Kr r) - Kb b) ig;  each clamped to [0, 1] and rounded once to f32: the network's input.
+ *   From RGB  (the network's UNQUANTISED f32 output) each value clamped to [0, 1] in f64 -- any finite magnitude, and the infinities, are
+ *             defined; a NaN counts as 0;  y = (Kr r + Kg g) + Kb b;  cb = (b - y) ib;  cr = (r - y) ir;  Y' = 16 + 219 y, C' = 128 + 224 c
+ *             (full: 255 y, 128 + 255 c).  4:2:0 chroma is subsampled at this unrounded level, pixel indices clamped to the image (odd
+ *             sizes): CENTER ((p00 + p01) + (p10 + p11)) 0.25 over the 2 x 2 block; LEFT per row ((a + 2 b) + c) 0.25 at columns 2j - 1,
+ *             2j, 2j + 1, then (row0 + row1) 0.5.  Finally floor(v + 0.5) clamped to the range's limits is the byte: one quantisation.
+ * sr_yuv_frame_bytes: the bytes of one frame; 0 for an invalid format or a shape below 1.  Host only.
+ * sr_yuv_to_rgb_dev / sr_rgb_to_yuv_dev: n frames of h x w <-> n x h x w x 3 f32, one launch on `stream`, any graph's context.  The f32
+ *   pointer must be 4-byte aligned; the frames may start at any byte.
+ * sr_upscale_yuv_dev: to RGB into a workspace buffer of the context, exactly sr_upscale_f32_dev's path (members == 1) or
+ *   sr_upscale_ensemble_f32_dev's (any other mask) into a second one, and from RGB into d_out: n frames of f h x f w in the same format.
+ *   SR_GRAPH_SR_NET (factors 2-4, both precisions) and SR_GRAPH_BILINEAR contexts.  Asynchronous and ordered on `stream` alone.
+ * sr_upscale_yuv: the same on host memory, synchronous: one upload, the device call on the context's own stream, one download; in
+ *   SR_PRECISION_SPLIT_F16 the whole call is computed again in exact f32 where a value left that mode's domain.
+ * Refused with SR_E_INVALID before any launch, the output untouched: a null pointer, an enum outside its values, n, h or w below 1 or a
+ * side beyond INT32_MAX / 4, a misaligned f32 pointer; (sr_upscale_yuv*) SR_GRAPH_DOWNSAMPLE contexts, members == 0 or > 255, members
+ * != 1 off SR_GRAPH_SR_NET.  A shape whose workspace cannot fit the device is SR_E_NOMEM and leaves the context usable. */
+enum sr_yuv_subsampling { SR_YUV_420 = 0, SR_YUV_444 = 1 };
+enum sr_yuv_siting { SR_YUV_SITING_CENTER = 0, SR_YUV_SITING_LEFT = 1 };
+enum sr_yuv_matrix { SR_YUV_BT601 = 0, SR_YUV_BT709 = 1 };
+enum sr_yuv_range { SR_YUV_LIMITED = 0, SR_YUV_FULL = 1 };
+typedef struct sr_yuv_format { int32_t subsampling, siting, matrix, range; } sr_yuv_format;
+size_t sr_yuv_frame_bytes(const sr_yuv_format* fmt, int h, int w);
+int sr_yuv_to_rgb_dev(sr_ctx* ctx, const uint8_t* d_yuv, const sr_yuv_format* fmt, int n, int h, int w, float* d_rgb, void* stream);
+int sr_rgb_to_yuv_dev(sr_ctx* ctx, const float* d_rgb, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* d_yuv, void* stream);
+int sr_upscale_yuv_dev(sr_ctx* ctx, const uint8_t* d_in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* d_out, unsigned members,
+                       void* stream);
+int sr_upscale_yuv(sr_ctx* ctx, const uint8_t* in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, unsigned members);
+/* The frame stream: sr_upscale_yuv of one frame after another with the copies of successive frames under the kernels.  A session owns
+ * `slots` (1..8) slots, each a page-locked input frame and a device input and output frame, and slots + 1 page-locked output frames.
+ *   sr_video_acquire  the input buffer of the next free slot (sr_yuv_frame_bytes(fmt, h, w) bytes) for the caller to fill; SR_E_INVALID
+ *                     if every slot is in flight (nothing is disturbed), the same buffer again if one is already acquired.
+ *   sr_video_submit   queues the acquired slot and returns at once: the upload on the context's upload stream, the three phases of
+ *                     sr_upscale_yuv_dev on its compute stream, the download on its download stream, ordered by the slot's events.
+ *   sr_video_receive  waits for the OLDEST submitted frame and gives its f h x f w frame; the pointer is valid until the next receive or
+ *                     destroy.  Frames leave in submission order, each byte for byte sr_upscale_yuv's.  SR_E_INVALID with nothing pending.
+ *   sr_video_pending  frames submitted and not yet received (-1: a null, detached or failed session).
+ * The network's workspace is the context's own, so the kernels of successive frames run one after another on one stream: only the
+ * copies overlap them.  slots == 1 is the serial form.  No graph capture, no host thread.
+ * SR_PRECISION_SPLIT_F16: the domain word is the context's, so a fault cannot be pinned to a frame.  sr_video_receive looks at it once
+ * the frame's download has completed; if it is set, the session's streams are drained, the word is cleared, the CONTEXT IS SWITCHED TO
+ * SR_PRECISION_F32 and stays there, and every frame still in flight -- the one being received included -- is queued again from its
+ * slot's input buffer, in order.  No clamped frame is ever handed out.
+ * While a session has frames in flight the context takes no other call.  sr_destroy of the context drains and detaches its sessions: a
+ * detached session refuses every call (SR_E_INVALID) but sr_video_destroy, which the caller still makes; so does a session whose
+ * recomputation in exact f32 could not be queued (sr_video_receive returns that status once, and the frames in flight are lost).
+ * sr_video_destroy with frames in flight waits for them.  Refusals of sr_video_create: those of sr_upscale_yuv, slots outside 1..8, a null `out`. */
+typedef struct sr_video sr_video;
+int sr_video_create(sr_ctx* ctx, const sr_yuv_format* fmt, int h, int w, int slots, unsigned members, sr_video** out);
+int sr_video_acquire(sr_video* v, uint8_t** in_frame);
+int sr_video_submit(sr_video* v);
+int sr_video_receive(sr_video* v, const uint8_t** out_frame);
+int sr_video_pending(const sr_video* v);
+void sr_video_destroy(sr_video* v);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -52,6 +52,21 @@ pub struct SrMetrics {
     pub ssim_count: u64,
 }
 
+#[repr(C)]
+pub struct SrVideo {
+    _private: [u8; 0],
+}
+
+/// `sr_yuv_format`: subsampling (0: 4:2:0, 1: 4:4:4), chroma siting (0: centre, 1: left), matrix (0: BT.601, 1: BT.709), range (0: limited, 1: full).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrYuvFormat {
+    pub subsampling: i32,
+    pub siting: i32,
+    pub matrix: i32,
+    pub range: i32,
+}
+
 /// `sr_degrade`: one item's blur width (HR pixels), noise level (8-bit levels), JPEG quality (0: none) and noise seed.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -201,6 +216,17 @@ extern "C" {
     pub fn sr_upscale_f32_border_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut f32, mode: c_int, pad: c_int, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_rgba8_border(ctx: *mut SrCtx, in_rgba: *const u8, n: c_int, h: c_int, w: c_int, out_rgba: *mut u8, mode: c_int, pad: c_int, members: c_uint, bleed: c_int) -> c_int;
     pub fn sr_upscale_f32_border(ctx: *mut SrCtx, input: *const f32, n: c_int, h: c_int, w: c_int, out: *mut f32, mode: c_int, pad: c_int, members: c_uint) -> c_int;
+    pub fn sr_yuv_frame_bytes(fmt: *const SrYuvFormat, h: c_int, w: c_int) -> usize;
+    pub fn sr_yuv_to_rgb_dev(ctx: *mut SrCtx, d_yuv: *const u8, fmt: *const SrYuvFormat, n: c_int, h: c_int, w: c_int, d_rgb: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_rgb_to_yuv_dev(ctx: *mut SrCtx, d_rgb: *const f32, fmt: *const SrYuvFormat, n: c_int, h: c_int, w: c_int, d_yuv: *mut u8, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_yuv_dev(ctx: *mut SrCtx, d_in: *const u8, fmt: *const SrYuvFormat, n: c_int, h: c_int, w: c_int, d_out: *mut u8, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_yuv(ctx: *mut SrCtx, input: *const u8, fmt: *const SrYuvFormat, n: c_int, h: c_int, w: c_int, out: *mut u8, members: c_uint) -> c_int;
+    pub fn sr_video_create(ctx: *mut SrCtx, fmt: *const SrYuvFormat, h: c_int, w: c_int, slots: c_int, members: c_uint, out: *mut *mut SrVideo) -> c_int;
+    pub fn sr_video_acquire(v: *mut SrVideo, in_frame: *mut *mut u8) -> c_int;
+    pub fn sr_video_submit(v: *mut SrVideo) -> c_int;
+    pub fn sr_video_receive(v: *mut SrVideo, out_frame: *mut *const u8) -> c_int;
+    pub fn sr_video_pending(v: *const SrVideo) -> c_int;
+    pub fn sr_video_destroy(v: *mut SrVideo);
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

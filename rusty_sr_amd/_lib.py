@@ -27,6 +27,11 @@ SR_RESIZE_SRGB_SPACE = 1
 SR_DEGRADE_MAX_SIGMA, SR_DEGRADE_MAX_NOISE = 4, 64
 SR_BORDER_WRAP, SR_BORDER_REPLICATE, SR_BORDER_MIRROR = 1, 2, 3
 SR_BORDER_PAD_DEFAULT, SR_BORDER_PAD_MAX = 8, 32
+SR_YUV_420, SR_YUV_444 = 0, 1
+SR_YUV_SITING_CENTER, SR_YUV_SITING_LEFT = 0, 1
+SR_YUV_BT601, SR_YUV_BT709 = 0, 1
+SR_YUV_LIMITED, SR_YUV_FULL = 0, 1
+SR_YUV_SPAN = 1024  # luma columns a workgroup of either conversion takes, two rows at a time (the tests put widths either side of it)
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -50,6 +55,20 @@ class Degrade(C.Structure):
 class Metrics(C.Structure):
     """sr_metrics (include/srhip.h): the sums and counts the Y-PSNR and the SSIM of one image are made of."""
     _fields_ = [("y_sq_err", C.c_uint64), ("y_count", C.c_uint64), ("ssim_sum", C.c_double), ("ssim_count", C.c_uint64)]
+
+
+class YuvFormat(C.Structure):
+    """sr_yuv_format (include/srhip.h "Video"): subsampling, chroma siting, matrix and range of a planar 8-bit YCbCr frame.  The fields
+    take the SR_YUV_* numbers; YuvFormat.named("420", "left", "bt709", "limited") takes the names."""
+    _fields_ = [("subsampling", C.c_int32), ("siting", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32)]
+    SUBSAMPLINGS = {"420": SR_YUV_420, "444": SR_YUV_444}
+    SITINGS = {"center": SR_YUV_SITING_CENTER, "left": SR_YUV_SITING_LEFT}
+    MATRICES = {"bt601": SR_YUV_BT601, "bt709": SR_YUV_BT709}
+    RANGES = {"limited": SR_YUV_LIMITED, "full": SR_YUV_FULL}
+
+    @classmethod
+    def named(cls, subsampling="420", siting="center", matrix="bt601", range="limited"):
+        return cls(cls.SUBSAMPLINGS[subsampling], cls.SITINGS[siting], cls.MATRICES[matrix], cls.RANGES[range])
 
 
 # every symbol include/srhip.h declares: (restype, argtypes)
@@ -157,6 +176,17 @@ SYMBOLS = {
     "sr_upscale_f32_border_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_uint, _vp]),
     "sr_upscale_rgba8_border": (_i, [_vp, _u8p, _i, _i, _i, _u8p, _i, _i, C.c_uint, _i]),
     "sr_upscale_f32_border": (_i, [_vp, _fp, _i, _i, _i, _fp, _i, _i, C.c_uint]),
+    "sr_yuv_frame_bytes": (_sz, [C.POINTER(YuvFormat), _i, _i]),
+    "sr_yuv_to_rgb_dev": (_i, [_vp, _vp, C.POINTER(YuvFormat), _i, _i, _i, _vp, _vp]),
+    "sr_rgb_to_yuv_dev": (_i, [_vp, _vp, C.POINTER(YuvFormat), _i, _i, _i, _vp, _vp]),
+    "sr_upscale_yuv_dev": (_i, [_vp, _vp, C.POINTER(YuvFormat), _i, _i, _i, _vp, C.c_uint, _vp]),
+    "sr_upscale_yuv": (_i, [_vp, _u8p, C.POINTER(YuvFormat), _i, _i, _i, _u8p, C.c_uint]),
+    "sr_video_create": (_i, [_vp, C.POINTER(YuvFormat), _i, _i, _i, C.c_uint, C.POINTER(_vp)]),
+    "sr_video_acquire": (_i, [_vp, C.POINTER(_vp)]),
+    "sr_video_submit": (_i, [_vp]),
+    "sr_video_receive": (_i, [_vp, C.POINTER(_vp)]),
+    "sr_video_pending": (_i, [_vp]),
+    "sr_video_destroy": (None, [_vp]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -453,6 +453,8 @@ void sr_destroy(sr_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     sr_train_detach_all(c);
+    sr_video_detach_all(c);
+    sr_yuv_release(c);
     sr_comm_release(c);
     sr_valid_release(c);
     sr_grad_release(c);
@@ -781,7 +783,12 @@ int sr_reserve_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group) {
 }
 
 int sr_net_check(const sr_ctx* c, const void* in, const void* out, int n, int h, int w, unsigned members) {
-    if (!c || !in || !out) return SR_E_INVALID;
+    if (!in || !out) return SR_E_INVALID;
+    return sr_net_check_shape(c, n, h, w, members);
+}
+
+int sr_net_check_shape(const sr_ctx* c, int n, int h, int w, unsigned members) {
+    if (!c) return SR_E_INVALID;
     if (c->graph != SR_GRAPH_SR_NET && c->graph != SR_GRAPH_BILINEAR) return SR_E_INVALID;
     if (n < 1 || h < 1 || w < 1 || h > INT32_MAX / c->factor || w > INT32_MAX / c->factor) return SR_E_INVALID;
     if (members == 0 || members > 255u) return SR_E_INVALID;
@@ -1207,7 +1214,8 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, sr_deal deal, i
     // their second pipelined call on: a one-shot process never pays for it, a service does once.
     if (nch > 1 && !reserve && c->precision == SR_PRECISION_F32 && ++c->pipelined_calls >= 2 && !c->copy_in)
         HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
-    const bool own_upload = nch > 1 && c->copy_in && c->precision == SR_PRECISION_F32;
+    // (pipelined_calls: a frame stream creates copy_in too, sr_yuv.cpp -- that must not move this call's first pipelined pass onto it)
+    const bool own_upload = nch > 1 && c->copy_in && c->pipelined_calls >= 2 && c->precision == SR_PRECISION_F32;
     hipStream_t down = nch > 1 ? c->copy_out : c->stream;
     size_t in_max = 0, out_max = 0;
     for (const sr_chunk& k : plan) { in_max = std::max(in_max, k.in_bytes); out_max = std::max(out_max, k.out_bytes); }

@@ -141,6 +141,10 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     double* d_dtab = nullptr;                       // 320 doubles: SrgbToLinear(byte / 255), then the 8 x 8 DCT matrix
     // ---- training sessions on this context (sr_train.cpp): sr_destroy releases what they hold on the device and detaches them
     std::vector<sr_train*> trains;
+    // ---- video (sr_yuv.cpp): grown on demand, freed by sr_destroy
+    sr_buf d_yrgb;                                  // the frames as the network's input, n x h x w x 3 f32
+    sr_buf d_ynet;                                  // the network's f32 output for them, before the conversion back
+    std::vector<sr_video*> videos;                  // frame streams on this context: sr_destroy drains and detaches them
 };
 
 inline void sr_plan_clear(sr_ctx* c) {
@@ -152,8 +156,8 @@ inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     else c->plan_rec.emplace_back(line, 1);
 }
 
-// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
-// px: the pixels the kernel is instantiated on (resize_h: its input's, resize_v: its output's); bx / by: workgroups along a row and along
+// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
+// px: the pixels the kernel is instantiated on (resize_h, yuv2rgb, rgb2yuv: its input's, resize_v: its output's); bx / by: workgroups along a row and along
 // the rows of one image (resize_h: of the batch's n h rows), from the *_blocks function the launcher itself calls.
 inline void sr_plan_note_op(sr_ctx* c, const char* name, bool f32, int n, unsigned bx, unsigned by, const char* form = nullptr, int f = 0) {
     char line[128], tail[48] = "";
@@ -332,6 +336,7 @@ int sr_on_device(sr_ctx* c, Body&& body) {
 // What every call that runs the network on a batch refuses for its arguments alone (SR_E_INVALID): a null context or image, a graph
 // other than sr_net / bilinear, a shape below 1 or beyond INT32_MAX / factor, a mask outside 1..255, a mask other than 1 off sr_net.
 int sr_net_check(const sr_ctx* c, const void* in, const void* out, int n, int h, int w, unsigned members);
+int sr_net_check_shape(const sr_ctx* c, int n, int h, int w, unsigned members);  // ... all of it but the two image pointers (a call that has no image yet)
 // The network on n images on device buffers, queued on s: the plain call's path for the whole batch (members == 1), else the ensemble
 // image by image.  u8: ch bytes a pixel in, else f32 RGB; out_u8: RGBA8 out, else f32 RGB.  The context's device is current.
 int sr_net_queue(sr_ctx* c, const void* d_in, bool u8, int ch, int n, int h, int w, void* d_out, bool out_u8, unsigned members, hipStream_t s);
@@ -549,3 +554,29 @@ hipError_t sr_launch_degrade(const sr_degrade_one& a, const double* d_tab, uint8
 // (byte / 255, d_ftab's first 256 floats) at d_x
 hipError_t sr_launch_train_degrade(sr_train_degrade_args a, uint32_t* d_batch, float* d_x, const float* d_ftab, const double* d_tab,
                                    hipStream_t s);
+
+// ---- video (sr_yuv.hip kernels, sr_yuv.cpp host side; include/srhip.h "Video")
+// A format as the kernels take it: the rule's constants, each formed once on the host in f64 by the single operations tests/yuv_ref.py
+// writes (the kernels divide nowhere).
+struct sr_yuv_rule {
+    int sub420, left;               // 4:2:0 (else 4:4:4); chroma horizontally co-sited with the even columns (else centred)
+    double kr, kb, kg;              // the matrix; kg = 1 - kr - kb
+    double cr2, cb2, ir, ib, ig;    // 2 (1 - kr), 2 (1 - kb) and their reciprocals, 1 / kg
+    double oy, sy, sc;              // YCbCr -> RGB: y = (Y - oy) sy, c = (C - 128) sc
+    double ky, kc;                  // RGB -> YCbCr: Y' = oy + ky y, C' = 128 + kc c
+    double ylo, yhi, clo, chi;      // the range's limits
+};
+bool sr_yuv_rule_make(const sr_yuv_format* f, sr_yuv_rule* out);  // false: a null format or an enum outside its values
+inline size_t sr_yuv_rule_frame_bytes(const sr_yuv_rule& k, int h, int w) {
+    const size_t ch = k.sub420 ? ((size_t)h + 1) / 2 : (size_t)h, cw = k.sub420 ? ((size_t)w + 1) / 2 : (size_t)w;
+    return (size_t)h * w + 2 * ch * cw;
+}
+// workgroups of either launch for n frames of h x w luma samples (0: an empty shape), functions of the shape alone; the launchers refuse
+// more than INT32_MAX
+size_t sr_yuv_to_rgb_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+size_t sr_rgb_to_yuv_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+// n frames at d_yuv (any byte) -> n x h x w x 3 f32 at d_rgb (4-byte aligned), and back
+hipError_t sr_launch_yuv_to_rgb(const uint8_t* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s);
+hipError_t sr_launch_rgb_to_yuv(const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s);
+void sr_yuv_release(sr_ctx* c);        // free the two buffers (called by sr_destroy)
+void sr_video_detach_all(sr_ctx* c);   // called by sr_destroy; a detached stream refuses every call but sr_video_destroy

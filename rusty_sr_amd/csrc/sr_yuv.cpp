@@ -1,0 +1,334 @@
+// sr_yuv.cpp -- the video path (include/srhip.h "Video"): the two colour conversions as entry points, the composed call
+//     YCbCr frame -> f32 RGB -> network (sr_net_queue: the plain or the ensemble call's path) -> f32 RGB -> YCbCr frame, quantised once,
+// and the frame stream, which keeps that call in flight for a ring of slots.  Kernels: sr_yuv.hip.  The composed calls are their checks,
+// their sizes and a work lambda; the stream is the one thing here the scaffold has no form for: a call that returns
+// before its work is done.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "sr_internal.h"
+
+namespace {
+
+constexpr size_t kPxF = 3 * sizeof(float);
+constexpr int kSideMax = INT32_MAX / 4;  // a side of a frame the conversions take: their column arithmetic is int
+
+const char* form_name(const sr_yuv_rule& k) { return !k.sub420 ? "444" : k.left ? "420left" : "420center"; }
+
+int check_frames(int n, int h, int w) {
+    return n >= 1 && h >= 1 && w >= 1 && h <= kSideMax && w <= kSideMax ? SR_OK : SR_E_INVALID;
+}
+
+// either launch queued on s, with its "op" line in the plan record: the grid the launcher itself takes
+int queue_to_rgb(sr_ctx* c, const uint8_t* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    if (sr_yuv_to_rgb_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_yuv_to_rgb(d_yuv, k, n, h, w, d_rgb, s));
+    sr_plan_note_op(c, "yuv2rgb", false, n, bx, by, form_name(k));
+    return SR_OK;
+}
+
+int queue_to_yuv(sr_ctx* c, const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    if (sr_rgb_to_yuv_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_rgb_to_yuv(d_rgb, k, n, h, w, d_yuv, s));
+    sr_plan_note_op(c, "rgb2yuv", true, n, bx, by, form_name(k));
+    return SR_OK;
+}
+
+// everything the composed calls and the frame stream refuse for their context, format, shape and mask alone
+int check_upscale_shape(const sr_ctx* c, const sr_yuv_format* fmt, int n, int h, int w, unsigned members, sr_yuv_rule* k) {
+    SRCHK(sr_net_check_shape(c, n, h, w, members));
+    if (!sr_yuv_rule_make(fmt, k)) return SR_E_INVALID;
+    if (h > kSideMax / c->factor || w > kSideMax / c->factor) return SR_E_INVALID;
+    return SR_OK;
+}
+
+// ... and for their two frame pointers
+int check_upscale_args(const sr_ctx* c, const void* in, const sr_yuv_format* fmt, int n, int h, int w, const void* out, unsigned members,
+                       sr_yuv_rule* k) {
+    if (!in || !out) return SR_E_INVALID;
+    return check_upscale_shape(c, fmt, n, h, w, members, k);
+}
+
+// to RGB -> network -> from RGB on device buffers, queued on s; the arguments are checked and the context's device is current
+int queue_upscale(sr_ctx* c, const uint8_t* d_in, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_out, unsigned members, hipStream_t s) {
+    const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;
+    if (out_img / kPxF / (f * w) != f * h || out_img > SIZE_MAX / (size_t)n) return SR_E_NOMEM;
+    SRCHK(sr_reserve_bufs(c, {{&c->d_yrgb, (size_t)n * in_img}, {&c->d_ynet, (size_t)n * out_img}}));
+    SRCHK(queue_to_rgb(c, d_in, k, n, h, w, (float*)c->d_yrgb.p, s));
+    SRCHK(sr_net_queue(c, c->d_yrgb.p, false, 3, n, h, w, c->d_ynet.p, false, members, s));
+    return queue_to_yuv(c, (const float*)c->d_ynet.p, k, n, (int)f * h, (int)f * w, d_out, s);
+}
+
+}  // namespace
+
+bool sr_yuv_rule_make(const sr_yuv_format* f, sr_yuv_rule* out) {
+    if (!f) return false;
+    if (f->subsampling != SR_YUV_420 && f->subsampling != SR_YUV_444) return false;
+    if (f->siting != SR_YUV_SITING_CENTER && f->siting != SR_YUV_SITING_LEFT) return false;
+    if (f->matrix != SR_YUV_BT601 && f->matrix != SR_YUV_BT709) return false;
+    if (f->range != SR_YUV_LIMITED && f->range != SR_YUV_FULL) return false;
+    sr_yuv_rule k{};
+    const bool full = f->range == SR_YUV_FULL;
+    k.sub420 = f->subsampling == SR_YUV_420;
+    k.left = k.sub420 && f->siting == SR_YUV_SITING_LEFT;
+    k.kr = f->matrix == SR_YUV_BT709 ? 0.2126 : 0.299;
+    k.kb = f->matrix == SR_YUV_BT709 ? 0.0722 : 0.114;
+    k.kg = 1.0 - k.kr - k.kb;
+    k.cr2 = 2.0 * (1.0 - k.kr);
+    k.cb2 = 2.0 * (1.0 - k.kb);
+    k.ir = 1.0 / k.cr2;
+    k.ib = 1.0 / k.cb2;
+    k.ig = 1.0 / k.kg;
+    k.oy = full ? 0.0 : 16.0;
+    k.ky = full ? 255.0 : 219.0;
+    k.kc = full ? 255.0 : 224.0;
+    k.sy = 1.0 / k.ky;
+    k.sc = 1.0 / k.kc;
+    k.ylo = full ? 0.0 : 16.0;
+    k.yhi = full ? 255.0 : 235.0;
+    k.clo = full ? 0.0 : 16.0;
+    k.chi = full ? 255.0 : 240.0;
+    *out = k;
+    return true;
+}
+
+void sr_yuv_release(sr_ctx* c) {
+    sr_free_buf(c->d_yrgb);
+    sr_free_buf(c->d_ynet);
+}
+
+// ---- the frame stream ------------------------------------------------------------------------------------------------------------------
+struct sr_video {
+    sr_ctx* c = nullptr;  // nullptr: detached by sr_destroy
+    bool failed = false;  // a recomputation in exact f32 could not be queued: what is in flight is lost, every call but destroy is refused
+    sr_yuv_rule k{};
+    int h = 0, w = 0, slots = 0;
+    unsigned members = 1;
+    size_t in_bytes = 0, out_bytes = 0;
+    struct Slot {
+        uint8_t* h_in = nullptr;   // page-locked
+        void* d_in = nullptr;
+        void* d_out = nullptr;
+        uint8_t* h_out = nullptr;  // where this submission's frame lands: one of outs
+        hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+    } slot[8];
+    uint8_t* outs[9] = {nullptr};  // page-locked output frames, slots + 1 of them: the one the caller holds is never a target
+    unsigned long long submitted = 0;  // frames submitted so far: frame i uses slot i mod slots and output i mod (slots + 1)
+    int pending = 0;
+    bool acquired = false;
+};
+
+namespace {
+
+// what a session holds on the device and in page-locked memory; its streams have drained
+void video_free(sr_video* v) {
+    for (auto& s : v->slot) {
+        if (s.h_in) (void)hipHostFree(s.h_in);
+        if (s.d_in) (void)hipFree(s.d_in);
+        if (s.d_out) (void)hipFree(s.d_out);
+        for (hipEvent_t e : {s.up, s.done, s.down})
+            if (e) (void)hipEventDestroy(e);
+        s = sr_video::Slot{};
+    }
+    for (auto& o : v->outs) {
+        if (o) (void)hipHostFree(o);
+        o = nullptr;
+    }
+}
+
+void video_drain(sr_ctx* c) {
+    for (hipStream_t s : {c->copy_in, c->stream, c->stream2, c->copy_out})
+        if (s) (void)hipStreamSynchronize(s);
+}
+
+// frame number `frame` of the session: upload, the three phases, download, each on its stream, ordered by the slot's events
+int video_queue(sr_video* v, unsigned long long frame) {
+    sr_ctx* c = v->c;
+    sr_video::Slot& s = v->slot[frame % (unsigned)v->slots];
+    s.h_out = v->outs[frame % (unsigned)(v->slots + 1)];
+    HIPCHK(c, hipMemcpyAsync(s.d_in, s.h_in, v->in_bytes, hipMemcpyHostToDevice, c->copy_in));
+    HIPCHK(c, hipEventRecord(s.up, c->copy_in));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, s.up, 0));
+    SRCHK(queue_upscale(c, (const uint8_t*)s.d_in, v->k, 1, v->h, v->w, (uint8_t*)s.d_out, v->members, c->stream));
+    HIPCHK(c, hipEventRecord(s.done, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->copy_out, s.done, 0));
+    HIPCHK(c, hipMemcpyAsync(s.h_out, s.d_out, v->out_bytes, hipMemcpyDeviceToHost, c->copy_out));
+    HIPCHK(c, hipEventRecord(s.down, c->copy_out));
+    return SR_OK;
+}
+
+int video_create(sr_video* v) {
+    sr_ctx* c = v->c;
+    SRCHK(sr_ensure_streams(c, true));
+    if (!c->copy_in) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
+    for (int i = 0; i < v->slots; ++i) {
+        sr_video::Slot& s = v->slot[i];
+        HIPCHK(c, hipHostMalloc((void**)&s.h_in, v->in_bytes, hipHostMallocPortable));
+        HIPCHK(c, hipMalloc(&s.d_in, v->in_bytes));
+        HIPCHK(c, hipMalloc(&s.d_out, v->out_bytes));
+        for (hipEvent_t* e : {&s.up, &s.done, &s.down}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    for (int i = 0; i <= v->slots; ++i) HIPCHK(c, hipHostMalloc((void**)&v->outs[i], v->out_bytes, hipHostMallocPortable));
+    return SR_OK;
+}
+
+}  // namespace
+
+void sr_video_detach_all(sr_ctx* c) {
+    if (c->videos.empty()) return;
+    video_drain(c);
+    for (sr_video* v : c->videos) {
+        video_free(v);
+        v->c = nullptr;
+        v->pending = 0;
+        v->acquired = false;
+    }
+    c->videos.clear();
+}
+
+extern "C" {
+
+size_t sr_yuv_frame_bytes(const sr_yuv_format* fmt, int h, int w) {
+    sr_yuv_rule k;
+    if (!sr_yuv_rule_make(fmt, &k) || h < 1 || w < 1) return 0;
+    return sr_yuv_rule_frame_bytes(k, h, w);
+}
+
+int sr_yuv_to_rgb_dev(sr_ctx* c, const uint8_t* d_yuv, const sr_yuv_format* fmt, int n, int h, int w, float* d_rgb, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    if (!c || !d_yuv || !d_rgb || !sr_yuv_rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    if (!sr_dword_aligned(d_rgb)) return SR_E_INVALID;
+    return sr_on_device(c, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
+}
+
+int sr_rgb_to_yuv_dev(sr_ctx* c, const float* d_rgb, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* d_yuv, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    if (!c || !d_yuv || !d_rgb || !sr_yuv_rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    if (!sr_dword_aligned(d_rgb)) return SR_E_INVALID;
+    return sr_on_device(c, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
+}
+
+int sr_upscale_yuv_dev(sr_ctx* c, const uint8_t* d_in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* d_out, unsigned members,
+                       void* stream) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    SRCHK(check_upscale_args(c, d_in, fmt, n, h, w, d_out, members, &k));
+    return sr_on_device(c, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
+}
+
+int sr_upscale_yuv(sr_ctx* c, const uint8_t* in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, unsigned members) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    SRCHK(check_upscale_args(c, in, fmt, n, h, w, out, members, &k));
+    const int f = c->factor;
+    const size_t in_bytes = (size_t)n * sr_yuv_rule_frame_bytes(k, h, w), out_bytes = (size_t)n * sr_yuv_rule_frame_bytes(k, f * h, f * w);
+    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return queue_upscale(c, (const uint8_t*)d_in, k, n, h, w, (uint8_t*)d_out, members, s);
+    });
+}
+
+int sr_video_create(sr_ctx* c, const sr_yuv_format* fmt, int h, int w, int slots, unsigned members, sr_video** out) {
+    sr_plan_clear(c);
+    if (out) *out = nullptr;
+    sr_yuv_rule k;
+    if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
+    SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
+    sr_video* v = new sr_video;
+    v->c = c;
+    v->k = k;
+    v->h = h;
+    v->w = w;
+    v->slots = slots;
+    v->members = members;
+    v->in_bytes = sr_yuv_rule_frame_bytes(k, h, w);
+    v->out_bytes = sr_yuv_rule_frame_bytes(k, c->factor * h, c->factor * w);
+    const int rc = sr_on_device(c, [&] { return video_create(v); });
+    if (rc != SR_OK) {
+        video_free(v);
+        delete v;
+        return rc;
+    }
+    c->videos.push_back(v);
+    *out = v;
+    return SR_OK;
+}
+
+int sr_video_acquire(sr_video* v, uint8_t** in_frame) {
+    if (!v || !v->c || v->failed || !in_frame) return SR_E_INVALID;
+    if (v->pending >= v->slots) return SR_E_INVALID;
+    v->acquired = true;
+    *in_frame = v->slot[v->submitted % (unsigned)v->slots].h_in;
+    return SR_OK;
+}
+
+int sr_video_submit(sr_video* v) {
+    if (!v || !v->c || v->failed || !v->acquired) return SR_E_INVALID;
+    sr_ctx* c = v->c;
+    sr_plan_clear(c);
+    return sr_on_device(c, [&]() -> int {
+        if (v->pending == 0) sr_domain_set_aside(c);  // a fault an earlier *_dev call left is that call's, not a frame's
+        const int rc = video_queue(v, v->submitted);
+        if (rc != SR_OK) {
+            video_drain(c);  // nothing of a refused frame stays queued; the slot is still the caller's
+            return rc;
+        }
+        v->acquired = false;
+        ++v->submitted;
+        ++v->pending;
+        return SR_OK;
+    });
+}
+
+int sr_video_receive(sr_video* v, const uint8_t** out_frame) {
+    if (!v || !v->c || v->failed || !out_frame || v->pending < 1) return SR_E_INVALID;
+    sr_ctx* c = v->c;
+    return sr_on_device(c, [&]() -> int {
+        const unsigned long long oldest = v->submitted - (unsigned)v->pending;
+        sr_video::Slot& s = v->slot[oldest % (unsigned)v->slots];
+        HIPCHK(c, hipEventSynchronize(s.down));
+        if (c->precision == SR_PRECISION_SPLIT_F16 && c->h_domain && *(volatile int*)c->h_domain) {
+            // Some frame in flight left the split-half mode's domain, and the word does not say which: every one of them, this one
+            // included, is computed again in exact f32 from its slot's input, in order.  The context stays in f32.
+            video_drain(c);
+            (void)sr_domain_tripped(c);
+            (void)sr_set_precision(c, SR_PRECISION_F32);
+            for (unsigned long long i = oldest; i < v->submitted; ++i) {
+                const int rc = video_queue(v, i);
+                if (rc != SR_OK) {  // some frames are queued again and some are not: none of them may be handed out
+                    video_drain(c);
+                    v->failed = true;
+                    v->pending = 0;
+                    v->acquired = false;
+                    return rc;
+                }
+            }
+            HIPCHK(c, hipEventSynchronize(s.down));
+        }
+        --v->pending;
+        *out_frame = s.h_out;
+        return SR_OK;
+    });
+}
+
+int sr_video_pending(const sr_video* v) { return v && v->c && !v->failed ? v->pending : -1; }
+
+void sr_video_destroy(sr_video* v) {
+    if (!v) return;
+    if (sr_ctx* c = v->c) {
+        sr_device_guard restore_device;
+        (void)hipSetDevice(c->device);
+        video_drain(c);
+        video_free(v);
+        c->videos.erase(std::remove(c->videos.begin(), c->videos.end(), v), c->videos.end());
+    }
+    delete v;
+}
+
+}  // extern "C"

@@ -60,9 +60,10 @@ def parse_plan(text: str) -> dict:
     host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
     st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
     parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid.  An op (a launch of a pixel
-    operator: pad, crop, bleed, merge, resize_h, resize_v, in the order they were queued): name, px ("u8" | "f32": the pixels the kernel is
-    instantiated on -- resize_h its input's, resize_v its output's), n, bx, by (workgroups along a row and along the rows of one image;
-    resize_h: groups of the batch's n h rows), count, and form ("staged4" | "staged1" | "direct", resize_h) or f (the factor, merge).
+    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, in the order they were queued): name, px ("u8" | "f32": the
+    pixels the kernel is instantiated on -- resize_h its input's, resize_v its output's, the two conversions their input's), n, bx, by
+    (workgroups along a row and along the rows of one image; resize_h: groups of the batch's n h rows), count, and form ("staged4" |
+    "staged1" | "direct", resize_h; "420center" | "420left" | "444", the conversions) or f (the factor, merge).
     Lines of any other kind are ignored."""
     rec = {"host": [], "fork": [], "launches": [], "aux": [], "ops": []}
     for line in text.splitlines():
@@ -415,6 +416,82 @@ class Engine:
                                                      self._border_mode(mode), int(pad), self._members(members),
                                                      self._stream_ptr(stream, x.device)), self._ctx)
         return out
+
+    # ---- video: planar 8-bit YCbCr frames, laid out like a Y4M frame payload (include/srhip.h "Video") ----
+    @staticmethod
+    def _yuv_frames(frames, fmt, h, w):
+        """Host frames as a C-contiguous (n, frame_bytes) u8 array; squeeze: it was one frame (1-d)."""
+        fb = yuv_frame_bytes(fmt, h, w)
+        a = np.ascontiguousarray(frames, dtype=np.uint8)
+        squeeze = a.ndim == 1
+        if fb == 0 or a.ndim not in (1, 2) or a.shape[-1] != fb:
+            raise ValueError(f"expected frames of {fb} bytes")
+        return (a[None] if squeeze else a), squeeze
+
+    @staticmethod
+    def _yuv_frames_dev(frames, fmt, h, w):
+        """A contiguous u8 tensor on the GPU, (n, frame_bytes) or (frame_bytes,): any byte offset within its allocation will do."""
+        import torch
+        fb = yuv_frame_bytes(fmt, h, w)
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() in (1, 2) and frames.shape[-1] == fb
+        return 1 if frames.dim() == 1 else frames.shape[0]
+
+    def yuv_to_rgb_dev(self, frames, fmt, h: int, w: int, out=None, stream=None):
+        """sr_yuv_to_rgb_dev: (n, frame_bytes) u8 on this GPU -> (n,h,w,3) f32 RGB in [0, 1], the network's input."""
+        n = self._yuv_frames_dev(frames, fmt, h, w)
+        out = self._dev_out(out, (n, h, w, 3), np.float32, frames.device)
+        _lib.check(self._L.sr_yuv_to_rgb_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                             self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def rgb_to_yuv_dev(self, x, fmt, out=None, stream=None):
+        """sr_rgb_to_yuv_dev: (n,h,w,3) f32 RGB on this GPU (any finite values: clamped; NaN counts as 0) -> (n, frame_bytes) u8."""
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        out = self._dev_out(out, (n, yuv_frame_bytes(fmt, h, w)), np.uint8, x.device)
+        _lib.check(self._L.sr_rgb_to_yuv_dev(self._ctx, C.c_void_p(x.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                             self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def upscale_yuv_dev(self, frames, fmt, h: int, w: int, members: int = 1, out=None, stream=None):
+        """sr_upscale_yuv_dev: (n, frame_bytes) u8 frames of h x w on this GPU -> (n, frame_bytes of fh x fw) in the same format."""
+        n = self._yuv_frames_dev(frames, fmt, h, w)
+        out = self._dev_out(out, (n, yuv_frame_bytes(fmt, self.factor * h, self.factor * w)), np.uint8, frames.device)
+        _lib.check(self._L.sr_upscale_yuv_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                              self._members(members), self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def yuv_to_rgb(self, frames: np.ndarray, fmt, h: int, w: int) -> np.ndarray:
+        """yuv_to_rgb_dev on host frames: (n, frame_bytes) or (frame_bytes,) u8 -> (n,h,w,3) or (h,w,3) f32."""
+        import torch
+        a, squeeze = self._yuv_frames(frames, fmt, h, w)
+        out = self.yuv_to_rgb_dev(torch.from_numpy(a).to(f"cuda:{self.device}"), fmt, h, w)
+        torch.cuda.synchronize(out.device)
+        out = out.cpu().numpy()
+        return out[0] if squeeze else out
+
+    def rgb_to_yuv(self, x: np.ndarray, fmt) -> np.ndarray:
+        """rgb_to_yuv_dev on a host image: (n,h,w,3) or (h,w,3) f32 -> (n, frame_bytes) or (frame_bytes,) u8."""
+        import torch
+        x, squeeze, _, _, _, _ = self._host_batch(x, np.float32, 3)
+        out = self.rgb_to_yuv_dev(torch.from_numpy(x).to(f"cuda:{self.device}"), fmt)
+        torch.cuda.synchronize(out.device)
+        out = out.cpu().numpy()
+        return out[0] if squeeze else out
+
+    def upscale_yuv(self, frames: np.ndarray, fmt, h: int, w: int, members: int = 1, out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_yuv: (n, frame_bytes) or (frame_bytes,) u8 frames of h x w -> the frames of fh x fw in the same format: colour
+        conversion and chroma resampling on the GPU, the network's f32 output quantised once, straight to YCbCr."""
+        a, squeeze = self._yuv_frames(frames, fmt, h, w)
+        n, ob = a.shape[0], yuv_frame_bytes(fmt, self.factor * h, self.factor * w)
+        if out is None:
+            out = np.empty((n, ob), dtype=np.uint8)
+        elif out.dtype != np.uint8 or out.size != n * ob or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous u8 array of {n * ob} bytes")
+        u8p = C.POINTER(C.c_uint8)
+        _lib.check(self._L.sr_upscale_yuv(self._ctx, a.ctypes.data_as(u8p), C.byref(fmt), n, h, w, out.ctypes.data_as(u8p),
+                                          self._members(members)), self._ctx)
+        out = out.reshape(n, ob)
+        return out[0] if squeeze else out
 
     # ---- resampling to any size: a separable resampler in Pillow's convention, on the device (include/srhip.h "Resampling to any size") ----
     FILTERS = {"box": _lib.SR_FILTER_BOX, "triangle": _lib.SR_FILTER_TRIANGLE, "catrom": _lib.SR_FILTER_CATROM,
@@ -1434,6 +1511,68 @@ class Trainer:
         if self._t:
             self._L.sr_train_destroy(self._t)
             self._t = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+YuvFormat = _lib.YuvFormat
+
+
+def yuv_frame_bytes(fmt, h: int, w: int) -> int:
+    """sr_yuv_frame_bytes: the bytes of one planar frame of h x w luma samples (0: an invalid format or shape).  Host only."""
+    return int(_lib.lib().sr_yuv_frame_bytes(C.byref(fmt), int(h), int(w)))
+
+
+class VideoStream:
+    """An sr_video session (include/srhip.h "Video"): frames of h x w in `fmt` go in, frames of fh x fw come out in order, the copies
+    of successive frames running under the kernels.  While frames are in flight the engine takes no other call."""
+
+    def __init__(self, engine: Engine, fmt, h: int, w: int, slots: int = 3, members=None):
+        self._L, self._e, self._v = engine._L, engine, C.c_void_p()
+        self.slots, self.in_bytes = int(slots), yuv_frame_bytes(fmt, h, w)
+        self.out_bytes = yuv_frame_bytes(fmt, engine.factor * h, engine.factor * w)
+        _lib.check(self._L.sr_video_create(engine._ctx, C.byref(fmt), int(h), int(w), self.slots,
+                                           Engine._members(1 if members is None else members), C.byref(self._v)), engine._ctx)
+
+    @property
+    def pending(self) -> int:
+        return int(self._L.sr_video_pending(self._v))
+
+    def submit(self, frame) -> None:
+        """Copy one frame (in_bytes u8) into a free slot's page-locked buffer and queue it; SrError(SR_E_INVALID) if none is free."""
+        frame = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+        if frame.size != self.in_bytes:
+            raise ValueError(f"expected a frame of {self.in_bytes} bytes")
+        p = C.c_void_p()
+        _lib.check(self._L.sr_video_acquire(self._v, C.byref(p)), self._e._ctx)
+        C.memmove(p, frame.ctypes.data, self.in_bytes)
+        _lib.check(self._L.sr_video_submit(self._v), self._e._ctx)
+
+    def receive(self, copy: bool = True) -> np.ndarray:
+        """The oldest submitted frame's result (out_bytes u8): copied out of the session's buffer, or with copy=False a view of that
+        page-locked buffer, valid until the next receive or close."""
+        p = C.c_void_p()
+        _lib.check(self._L.sr_video_receive(self._v, C.byref(p)), self._e._ctx)
+        view = np.frombuffer((C.c_char * self.out_bytes).from_address(p.value), dtype=np.uint8)
+        return view.copy() if copy else view
+
+    def frames(self, iterable):
+        """Results of the frames of `iterable`, in order, with the ring kept full."""
+        for frame in iterable:
+            if self.pending == self.slots:
+                yield self.receive()
+            self.submit(frame)
+        while self.pending > 0:
+            yield self.receive()
+
+    def close(self):
+        if getattr(self, "_v", None):
+            self._L.sr_video_destroy(self._v)
+            self._v = None
 
     def __del__(self):
         try:

@@ -4,10 +4,12 @@
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
 //   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] [--degrade SPEC [--seed N]] <VALIDATION_FOLDER>
+//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709] [--slots N] [--timing] <IN|-> <OUT|->
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
-// PSNR a parameter set reaches on a folder of HR images.  A first argument that is literally `train` or `validate` selects it; every
-// other argv is the upscale surface, unchanged.
+// PSNR a parameter set reaches on a folder of HR images.  `video` upscales a YUV4MPEG2 stream frame by frame (y4m.hpp; the reference has
+// no counterpart).  A first argument that is literally `train`, `validate` or `video` selects it; every other argv is the upscale
+// surface, unchanged.
 //
 // Differences from the reference, all outside the hot path: own codecs (PNG over zlib, baseline + progressive JPEG, GIF,
 // TIFF, TGA, ICO, PPM/PGM/PBM, BMP in; PNG, JPEG, BMP, PPM out by extension -- of what the reference's `image` crate reads
@@ -43,6 +45,7 @@
 #include "../../include/srhip.h"
 #include "degrade_spec.hpp"
 #include "png.hpp"
+#include "y4m.hpp"
 
 // The three parameter sets the reference embeds with include_bytes! (main.rs:26-28)
 #define EMBED(sym, path)                                                                    \
@@ -988,6 +991,156 @@ int run_train(int argc, char** argv) {
     printf("Done\n");
     return 0;
 }
+
+// ---- rusty_sr video: a YUV4MPEG2 stream through the frame stream of the library (sr_video_*), stdin / stdout as "-" ----
+[[noreturn]] void video_usage_error(const std::string& msg) {
+    fprintf(stderr, "error: %s\n\nUSAGE:\n    rusty_sr video [OPTIONS] <INPUT|-> <OUTPUT|->\n\nFor more information try --help\n", msg.c_str());
+    exit(2);
+}
+
+const char kVideoHelp[] =
+    "USAGE:\n    rusty_sr video [OPTIONS] <INPUT|-> <OUTPUT|->\n\n"
+    "Upscales a YUV4MPEG2 stream frame by frame: colour conversion and chroma resampling run on the GPU, the network's\n"
+    "output is quantised once, straight to YCbCr, and the copies of successive frames overlap the kernels.  Frames are\n"
+    "independent.  `-` is stdin / stdout:  ffmpeg -i in.mp4 -f yuv4mpegpipe - | rusty_sr video - - | ffmpeg -i - out.mp4\n"
+    "Streams: 8-bit progressive C420jpeg, C420, C420mpeg2, C444; XCOLORRANGE=FULL selects full range.\n\n"
+    "OPTIONS:\n"
+    "    -p, --parameters <PARAMETERS>    [values: anime, bilinear, imagenet, imagenetlinear]\n"
+    "    -c, --custom <PARAMETER_FILE>\n"
+    "        --precision <MODE>           [values: f32, split_f16]\n"
+    "        --device <N>\n"
+    "        --ensemble <N>               [values: 2, 4, 8]\n"
+    "        --matrix <MATRIX>            [values: bt601, bt709]  default: bt709 from 1280 columns or above 576 rows, else bt601\n"
+    "        --slots <N>                  frames in flight [1..8], default 3\n"
+    "        --timing                     print frames and ms/frame to stderr\n";
+
+int run_video(int argc, char** argv) {
+    std::vector<std::string> pos;
+    std::string parameters, custom, precision = "f32", matrix;
+    bool has_p = false, has_c = false, timing = false;
+    long device = 0, slots = 3;
+    unsigned ensemble = 0;
+    for (int k = 2; k < argc; ++k) {
+        const std::string a = argv[k];
+        auto value = [&](const char* name) -> std::string {
+            if (k + 1 >= argc) video_usage_error(std::string("The argument '") + name + "' requires a value but none was supplied");
+            return argv[++k];
+        };
+        if (a == "-h" || a == "--help") { fputs(kVideoHelp, stderr); return 0; }
+        else if (a == "-p" || a == "--parameters") { parameters = value("--parameters <PARAMETERS>"); has_p = true; }
+        else if (a == "-c" || a == "--custom") { custom = value("--custom <PARAMETER_FILE>"); has_c = true; }
+        else if (a == "--precision") precision = value("--precision <MODE>");
+        else if (a == "--timing") timing = true;
+        else if (a == "--device") {
+            const std::string v = value("--device <N>");
+            if (!parse_count(v, device) || device < 0) video_usage_error("'" + v + "' isn't a valid value for '--device <N>'");
+        }
+        else if (a == "--slots") {
+            const std::string v = value("--slots <N>");
+            if (!parse_count(v, slots) || slots < 1 || slots > 8) video_usage_error("'" + v + "' isn't a valid value for '--slots <N>'\n\t[values: 1..8]");
+        }
+        else if (a == "--ensemble") {
+            const std::string v = value("--ensemble <N>");
+            if (!(ensemble = ensemble_mask(v))) video_usage_error("'" + v + "' isn't a valid value for '--ensemble <N>'\n\t[values: 2, 4, 8]");
+        }
+        else if (a == "--matrix") {
+            matrix = value("--matrix <MATRIX>");
+            if (matrix != "bt601" && matrix != "bt709") video_usage_error("'" + matrix + "' isn't a valid value for '--matrix <MATRIX>'\n\t[values: bt601, bt709]");
+        }
+        else if (a.size() > 1 && a[0] == '-') video_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
+        else pos.push_back(a);
+    }
+    if (has_p && parameters != "imagenet" && parameters != "imagenetlinear" && parameters != "anime" && parameters != "bilinear")
+        video_usage_error("'" + parameters + "' isn't a valid value for '--parameters <PARAMETERS>'\n\t[values: anime, bilinear, imagenet, imagenetlinear]");
+    if (has_c && has_p) video_usage_error("The argument '--custom <PARAMETER_FILE>' cannot be used with '--parameters <PARAMETERS>'");
+    if (pos.size() < 2) video_usage_error("The following required arguments were not provided:\n    <INPUT|->\n    <OUTPUT|->");
+    if (pos.size() > 2) video_usage_error("Found argument '" + pos[2] + "' which wasn't expected, or isn't valid in this context");
+    if (precision != "f32" && precision != "split_f16") video_usage_error("'" + precision + "' isn't a valid value for '--precision <MODE>'");
+    if (ensemble && parameters == "bilinear")
+        video_usage_error("The argument '--ensemble <N>' cannot be used with '--parameters bilinear': bilinear interpolation has no network to average");
+
+    // ---- the stream header, before anything touches the GPU: a stream this build does not take is refused by the name of its tag
+    FILE* fin = pos[0] == "-" ? stdin : fopen(pos[0].c_str(), "rb");
+    if (!fin) die("Error opening input stream " + pos[0]);
+    std::string line, err;
+    sry4m::Header hd;
+    if (sry4m::read_line(fin, line) != 1) video_usage_error("the input is not a YUV4MPEG2 stream (no header line)");
+    if (!sry4m::parse_header(line.data(), line.size(), hd, err)) video_usage_error(err);
+    sr_yuv_format fmt{};
+    fmt.subsampling = hd.s444 ? SR_YUV_444 : SR_YUV_420;
+    fmt.siting = hd.left ? SR_YUV_SITING_LEFT : SR_YUV_SITING_CENTER;
+    fmt.matrix = !matrix.empty() ? (matrix == "bt709" ? SR_YUV_BT709 : SR_YUV_BT601) : (hd.w >= 1280 || hd.h > 576) ? SR_YUV_BT709 : SR_YUV_BT601;
+    fmt.range = hd.full ? SR_YUV_FULL : SR_YUV_LIMITED;
+
+    // ---- parameters + graph, the progress text on stderr (stdout may be the stream)
+    std::vector<float> params;
+    int graph = SR_GRAPH_SR_NET;
+    if (has_c) {
+        FILE* f = fopen(custom.c_str(), "rb");
+        if (!f) die("Error opening parameter file");
+        std::vector<unsigned char> data;
+        unsigned char tmp[65536];
+        size_t n;
+        while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) data.insert(data.end(), tmp, tmp + n);
+        fclose(f);
+        params = decode_rsr(data.data(), data.size());
+    } else if (!has_p || parameters == "imagenet") params = decode_rsr(imagenet_rsr_begin, imagenet_rsr_end - imagenet_rsr_begin);
+    else if (parameters == "imagenetlinear") params = decode_rsr(imagenetlinear_rsr_begin, imagenetlinear_rsr_end - imagenetlinear_rsr_begin);
+    else if (parameters == "anime") params = decode_rsr(anime_rsr_begin, anime_rsr_end - anime_rsr_begin);
+    else graph = SR_GRAPH_BILINEAR;
+    sr_ctx* ctx = nullptr;
+    int rc = sr_create_graph(&ctx, graph, params.empty() ? nullptr : params.data(), params.size(), SR_FACTOR, (int)device);
+    if (rc != SR_OK) die(sr_strerror(rc));
+    if (precision == "split_f16" && (rc = sr_set_precision(ctx, SR_PRECISION_SPLIT_F16)) != SR_OK)
+        die(std::string(sr_strerror(rc)) + " (SR_PRECISION_SPLIT_F16 cannot carry these parameters; use --precision f32)");
+    sr_video* vid = nullptr;
+    rc = sr_video_create(ctx, &fmt, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid);
+    if (rc != SR_OK) die(sr_strerror(rc));
+    const size_t in_bytes = sr_yuv_frame_bytes(&fmt, hd.h, hd.w), out_bytes = sr_yuv_frame_bytes(&fmt, SR_FACTOR * hd.h, SR_FACTOR * hd.w);
+
+    FILE* fout = pos[1] == "-" ? stdout : fopen(pos[1].c_str(), "wb");
+    if (!fout) die("Could not write output stream " + pos[1]);
+    const std::string head = sry4m::scaled_header(hd, SR_FACTOR);
+    bool wrote = fwrite(head.data(), 1, head.size(), fout) == head.size();
+    std::deque<std::string> frame_lines;  // the FRAME lines of the frames in flight, oldest first: their parameters pass through
+    long frames = 0, written = 0;
+    std::string failure;
+    // the oldest frame in flight: its FRAME line, then its payload straight from the session's buffer
+    auto write_oldest = [&]() {
+        const uint8_t* out = nullptr;
+        const int r = sr_video_receive(vid, &out);
+        if (r != SR_OK) die(std::string("frame ") + std::to_string(written) + ": " + sr_strerror(r));
+        const std::string fl = frame_lines.front() + "\n";
+        frame_lines.pop_front();
+        wrote = wrote && fwrite(fl.data(), 1, fl.size(), fout) == fl.size() && fwrite(out, 1, out_bytes, fout) == out_bytes;
+        ++written;
+    };
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    for (;;) {
+        if (sr_video_pending(vid) == (int)slots) write_oldest();
+        const int got = sry4m::read_line(fin, line);
+        if (got == 0) break;
+        if (got < 0 || !sry4m::is_frame_line(line)) { failure = "frame " + std::to_string(frames) + ": not a FRAME line"; break; }
+        uint8_t* in = nullptr;
+        if ((rc = sr_video_acquire(vid, &in)) != SR_OK) die(sr_strerror(rc));
+        if (fread(in, 1, in_bytes, fin) != in_bytes) { failure = "frame " + std::to_string(frames) + " is truncated"; break; }
+        if ((rc = sr_video_submit(vid)) != SR_OK) die(std::string("frame ") + std::to_string(frames) + ": " + sr_strerror(rc));
+        frame_lines.push_back(line);
+        ++frames;
+    }
+    while (sr_video_pending(vid) > 0) write_oldest();  // (also before a failure is reported: the frames before it are written)
+    const double ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    sr_video_destroy(vid);
+    sr_destroy(ctx);
+    if (fout != stdout) wrote = fclose(fout) == 0 && wrote;
+    else wrote = fflush(stdout) == 0 && wrote;
+    if (fin != stdin) fclose(fin);
+    if (!wrote) die("Could not write output stream " + pos[1]);
+    if (!failure.empty()) die(failure);
+    if (timing) fprintf(stderr, "[timing] frames %ld, %.2f ms/frame\n", frames, frames ? ms / frames : 0.0);
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -1009,6 +1162,7 @@ int main(int argc, char** argv) {
     std::vector<int> devices;
     if (argc >= 2 && !strcmp(argv[1], "train")) return run_train(argc, argv);  // main.rs:119-121
     if (argc >= 2 && !strcmp(argv[1], "validate")) return run_validate(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "video")) return run_video(argc, argv);
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
         auto value = [&](const char* name) -> std::string {
