@@ -804,6 +804,54 @@ int sr_video_receive(sr_video* v, const uint8_t** out_frame);
 int sr_video_pending(const sr_video* v);
 void sr_video_destroy(sr_video* v);
 
+/* ---- Deep colour: 16-bit images in and out ----
+ * The reference's images are 8 bits wide (main.rs:164-175), and so is every other integer path here; a 16-bit scan, photograph, height
+ * or displacement map would come back with 256 levels a channel.  These calls take and give interleaved 16-bit samples -- native-endian
+ * uint16_t, rows and images contiguous -- and quantise the network's f32 output once, to 65536 levels.  UNPINNED: the reference has no
+ * counterpart; tests/deep_ref.py states the rule in numpy and the kernels equal it bit for bit.  The rule acts on one pixel at a time:
+ * the images of a batch do not see each other and the shape does not enter.
+ *   In    x = (float)v / 65535.0f, one correctly rounded IEEE f32 division.  in_channels 1 (grey, copied to R = G = B), 2 (grey + alpha),
+ *         3 or 4; alpha is dropped, as sr_upscale_rgba8 drops it.  The result is the network's input, n x h x w x 3 f32.
+ *         (float)(257 b) / 65535.0f == (float)b / 255.0f for every byte b: an 8-bit image promoted to 16 bits feeds the network exactly
+ *         what the 8-bit path feeds it.
+ *   Out   q(v) = (uint16_t) fminf(fmaxf(floorf(65535.0f v + 0.5f), 0.0f), 65535.0f), the product and the sum each rounded to f32 (no
+ *         contraction); a NaN gives 0, by fmaxf.  q((float)k / 65535.0f) == k for all 65536 levels.  out_channels 3 writes RGB16, 4
+ *         RGBA16 with alpha 65535, 1 grey: q(((r + g) + b) / 3.0f), the sum and the quotient in f32.  2 is refused.
+ * sr_u16_to_f32_dev / sr_f32_to_u16_dev: n images of h x w, one launch on `stream`, any graph's context; asynchronous and ordered on
+ *   `stream` alone.  A u16 pointer must be 2-byte aligned, an f32 pointer 4-byte aligned; a side whose pointer is 16-byte aligned is
+ *   read or written 16 bytes at a time.  d_in == d_out is refused.
+ * sr_upscale_u16_dev: to f32 into a workspace buffer of the context (grown on first use, freed by sr_destroy), exactly
+ *   sr_upscale_f32_dev's path (members == 1) or sr_upscale_ensemble_f32_dev's (any other mask) into a second one, and to 16 bits into
+ *   d_out: n images of f h x f w.  Every graph those f32 calls take: SR_GRAPH_SR_NET (factors 2-4, both precisions), SR_GRAPH_BILINEAR
+ *   and, with members == 1, SR_GRAPH_DOWNSAMPLE (h / 3 x w / 3 out: 16-bit images are pooled in linear light too).
+ * sr_upscale_u16: the same on host memory, synchronous: one upload, the device call on the context's own stream, one download; in
+ *   SR_PRECISION_SPLIT_F16 the whole call is computed again in exact f32 where a value left that mode's domain.  With sr_set_profiling
+ *   on, sr_last_timing's total_ms is every launch of the call, h2d / d2h the two copies.
+ * sr_upscale_u16_border[_dev]: the same two conversions around sr_upscale_f32_border_dev (mode, pad, members as there).
+ * sr_upscale_u16_sized[_dev]: ... around the network's f32 call followed by sr_resize_dev from SR_PIXELS_F32 to SR_PIXELS_F32 (oh, ow,
+ *   filter, flags as in sr_upscale_rgba8_sized): n images of oh x ow.  Their graph and mask refusals are those of the 8-bit calls.
+ * Refused with SR_E_INVALID before any launch, the output untouched and the context usable: a null pointer; in_channels outside 1..4;
+ * out_channels not 1, 3 or 4; n, h or w below 1 (SR_GRAPH_DOWNSAMPLE: h or w below 3); byte counts that overflow; a u16 pointer at an
+ * odd address; an f32 pointer that is not 4-byte aligned; members == 0 or > 255; members != 1 on a context other than SR_GRAPH_SR_NET;
+ * the refusals of the border and sized calls for their own arguments.  A workspace that does not fit the device is SR_E_NOMEM and
+ * leaves the context usable and the output untouched: the call's own three buffers are refused before any launch, the border or
+ * resampling phase's behind the first conversion, which writes the context's workspace only.  Transparency at 16 bits, and the multi-GPU, band and sharded forms, do not exist.  Cost:
+ * DESIGN.md 4r. */
+int sr_u16_to_f32_dev(sr_ctx* ctx, const uint16_t* d_in, int in_channels, int n, int h, int w, float* d_out, void* stream);
+int sr_f32_to_u16_dev(sr_ctx* ctx, const float* d_in, int n, int h, int w, uint16_t* d_out, int out_channels, void* stream);
+int sr_upscale_u16_dev(sr_ctx* ctx, const uint16_t* d_in, int in_channels, int n, int h, int w, uint16_t* d_out, int out_channels,
+                       unsigned members, void* stream);
+int sr_upscale_u16(sr_ctx* ctx, const uint16_t* in, int in_channels, int n, int h, int w, uint16_t* out, int out_channels,
+                   unsigned members);
+int sr_upscale_u16_border_dev(sr_ctx* ctx, const uint16_t* d_in, int in_channels, int n, int h, int w, uint16_t* d_out, int out_channels,
+                              int mode, int pad, unsigned members, void* stream);
+int sr_upscale_u16_border(sr_ctx* ctx, const uint16_t* in, int in_channels, int n, int h, int w, uint16_t* out, int out_channels,
+                          int mode, int pad, unsigned members);
+int sr_upscale_u16_sized_dev(sr_ctx* ctx, const uint16_t* d_in, int in_channels, int n, int h, int w, uint16_t* d_out, int out_channels,
+                             int oh, int ow, int filter, unsigned flags, unsigned members, void* stream);
+int sr_upscale_u16_sized(sr_ctx* ctx, const uint16_t* in, int in_channels, int n, int h, int w, uint16_t* out, int out_channels,
+                         int oh, int ow, int filter, unsigned flags, unsigned members);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

@@ -227,6 +227,14 @@ extern "C" {
     pub fn sr_video_receive(v: *mut SrVideo, out_frame: *mut *const u8) -> c_int;
     pub fn sr_video_pending(v: *const SrVideo) -> c_int;
     pub fn sr_video_destroy(v: *mut SrVideo);
+    pub fn sr_u16_to_f32_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_f32_to_u16_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_u16_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_u16(ctx: *mut SrCtx, input: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, out: *mut u16, out_channels: c_int, members: c_uint) -> c_int;
+    pub fn sr_upscale_u16_border_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, mode: c_int, pad: c_int, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_u16_border(ctx: *mut SrCtx, input: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, out: *mut u16, out_channels: c_int, mode: c_int, pad: c_int, members: c_uint) -> c_int;
+    pub fn sr_upscale_u16_sized_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_u16_sized(ctx: *mut SrCtx, input: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, out: *mut u16, out_channels: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

@@ -32,6 +32,7 @@ SR_YUV_SITING_CENTER, SR_YUV_SITING_LEFT = 0, 1
 SR_YUV_BT601, SR_YUV_BT709 = 0, 1
 SR_YUV_LIMITED, SR_YUV_FULL = 0, 1
 SR_YUV_SPAN = 1024  # luma columns a workgroup of either conversion takes, two rows at a time (the tests put widths either side of it)
+SR_DEEP_SPAN = 2048  # pixels a workgroup of either deep-colour conversion takes, 8 a lane (the tests put counts either side of it)
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -74,6 +75,7 @@ class YuvFormat(C.Structure):
 # every symbol include/srhip.h declares: (restype, argtypes)
 _vp, _fp, _u8p, _dp = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
 _sz, _i = C.c_size_t, C.c_int
+_u16p = C.POINTER(C.c_uint16)
 SYMBOLS = {
     "sr_rsr_decode": (_i, [_u8p, _sz, _fp, _sz, C.POINTER(_sz)]),
     "sr_rsr_encode": (_i, [_fp, _sz, _u8p, _sz, C.POINTER(_sz)]),
@@ -187,6 +189,14 @@ SYMBOLS = {
     "sr_video_receive": (_i, [_vp, C.POINTER(_vp)]),
     "sr_video_pending": (_i, [_vp]),
     "sr_video_destroy": (None, [_vp]),
+    "sr_u16_to_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sr_f32_to_u16_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "sr_upscale_u16_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_uint, _vp]),
+    "sr_upscale_u16": (_i, [_vp, _u16p, _i, _i, _i, _i, _u16p, _i, C.c_uint]),
+    "sr_upscale_u16_border_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, C.c_uint, _vp]),
+    "sr_upscale_u16_border": (_i, [_vp, _u16p, _i, _i, _i, _i, _u16p, _i, _i, _i, C.c_uint]),
+    "sr_upscale_u16_sized_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
+    "sr_upscale_u16_sized": (_i, [_vp, _u16p, _i, _i, _i, _i, _u16p, _i, _i, _i, _i, C.c_uint, C.c_uint]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

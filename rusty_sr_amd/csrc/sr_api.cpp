@@ -455,6 +455,7 @@ void sr_destroy(sr_ctx* c) {
     sr_train_detach_all(c);
     sr_video_detach_all(c);
     sr_yuv_release(c);
+    sr_deep_release(c);
     sr_comm_release(c);
     sr_valid_release(c);
     sr_grad_release(c);

@@ -145,6 +145,10 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     sr_buf d_yrgb;                                  // the frames as the network's input, n x h x w x 3 f32
     sr_buf d_ynet;                                  // the network's f32 output for them, before the conversion back
     std::vector<sr_video*> videos;                  // frame streams on this context: sr_destroy drains and detaches them
+    // ---- deep colour (sr_deep.cpp): grown on demand, freed by sr_destroy
+    sr_buf d_kin;                                   // the 16-bit images as the network's input, n x h x w x 3 f32
+    sr_buf d_knet;                                  // the network's f32 output for them
+    sr_buf d_kres;                                  // the _sized calls: that output resampled, before the conversion back
 };
 
 inline void sr_plan_clear(sr_ctx* c) {
@@ -156,9 +160,10 @@ inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     else c->plan_rec.emplace_back(line, 1);
 }
 
-// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
+// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
 // px: the pixels the kernel is instantiated on (resize_h, yuv2rgb, rgb2yuv: its input's, resize_v: its output's); bx / by: workgroups along a row and along
-// the rows of one image (resize_h: of the batch's n h rows), from the *_blocks function the launcher itself calls.
+// the rows of one image (resize_h: of the batch's n h rows; the deep-colour conversions: 1, the batch is one run of pixels), from the
+// *_blocks function the launcher itself calls.
 inline void sr_plan_note_op(sr_ctx* c, const char* name, bool f32, int n, unsigned bx, unsigned by, const char* form = nullptr, int f = 0) {
     char line[128], tail[48] = "";
     if (form) snprintf(tail, sizeof tail, " form=%s", form);
@@ -580,3 +585,14 @@ hipError_t sr_launch_yuv_to_rgb(const uint8_t* d_yuv, const sr_yuv_rule& k, int 
 hipError_t sr_launch_rgb_to_yuv(const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s);
 void sr_yuv_release(sr_ctx* c);        // free the two buffers (called by sr_destroy)
 void sr_video_detach_all(sr_ctx* c);   // called by sr_destroy; a detached stream refuses every call but sr_video_destroy
+
+// ---- deep colour (sr_deep.hip kernels, sr_deep.cpp host side; include/srhip.h "Deep colour")
+// workgroups of either launch for npx pixels (0: none): a function of the pixel count alone; the launchers refuse more than INT32_MAX
+size_t sr_deep_blocks(size_t npx);
+// the form a launch takes for its two pointers: "wide" (both 16-byte aligned), "wide_in", "wide_out" or "narrow"
+const char* sr_deep_form(const void* d_in, const void* d_out);
+// npx pixels of in_channels (1..4) native-endian 16-bit samples at d_in (2-byte aligned) -> npx x 3 f32 at d_out (4-byte aligned), and
+// npx x 3 f32 -> npx pixels of out_channels (1, 3 or 4) samples
+hipError_t sr_launch_u16_to_f32(const uint16_t* d_in, int in_channels, size_t npx, float* d_out, hipStream_t s);
+hipError_t sr_launch_f32_to_u16(const float* d_in, size_t npx, uint16_t* d_out, int out_channels, hipStream_t s);
+void sr_deep_release(sr_ctx* c);  // free the three buffers (called by sr_destroy)

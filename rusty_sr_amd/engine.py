@@ -60,10 +60,12 @@ def parse_plan(text: str) -> dict:
     host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
     st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
     parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid.  An op (a launch of a pixel
-    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, in the order they were queued): name, px ("u8" | "f32": the
-    pixels the kernel is instantiated on -- resize_h its input's, resize_v its output's, the two conversions their input's), n, bx, by
-    (workgroups along a row and along the rows of one image; resize_h: groups of the batch's n h rows), count, and form ("staged4" |
-    "staged1" | "direct", resize_h; "420center" | "420left" | "444", the conversions) or f (the factor, merge).
+    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, in the order they were queued): name,
+    px ("u8" | "f32": the pixels the kernel is instantiated on -- resize_h its input's, resize_v its output's, the two video conversions
+    their input's, the two deep-colour conversions their f32 side), n, bx, by (workgroups along a row and along the rows of one image;
+    resize_h: groups of the batch's n h rows; the deep-colour conversions: n = by = 1, the batch is one run of pixels), count, and form
+    ("staged4" | "staged1" | "direct", resize_h; "420center" | "420left" | "444", the video conversions; "wide" | "wide_in" | "wide_out" |
+    "narrow", the deep-colour conversions) or f (the factor, merge).
     Lines of any other kind are ignored."""
     rec = {"host": [], "fork": [], "launches": [], "aux": [], "ops": []}
     for line in text.splitlines():
@@ -492,6 +494,132 @@ class Engine:
                                           self._members(members)), self._ctx)
         out = out.reshape(n, ob)
         return out[0] if squeeze else out
+
+    # ---- deep colour: 16-bit samples in and out (include/srhip.h "Deep colour") ----
+    @staticmethod
+    def _u16_host(px):
+        """A numpy uint16 image (H,W), (H,W,C) or batch (n,H,W,C) -> (arr4d, squeeze, grey2d, n, h, w, c), C-contiguous."""
+        px = np.ascontiguousarray(px, dtype=np.uint16)
+        grey2d = px.ndim == 2
+        if grey2d:
+            px = px[:, :, None]
+        squeeze = px.ndim == 3
+        if squeeze:
+            px = px[None]
+        if px.ndim != 4 or not 1 <= px.shape[-1] <= 4:
+            raise ValueError("expected uint16 samples shaped (h,w), (h,w,C) or (n,h,w,C) with C in 1..4")
+        return (px, squeeze, grey2d) + tuple(px.shape)
+
+    @staticmethod
+    def _u16_out_channels(channels, in_channels, out=None):
+        """The result's channel count: the caller's, else `out`'s, else grey for grey (1 or 2 channels in) and RGB otherwise."""
+        if channels is None:
+            channels = out.shape[-1] if out is not None and out.ndim >= 3 else (1 if in_channels <= 2 else 3)
+        return int(channels)
+
+    def _u16_result(self, out, n, oh, ow, oc):
+        if out is None:
+            return np.empty((n, max(oh, 0), max(ow, 0), max(oc, 1)), dtype=np.uint16)
+        if out.dtype != np.uint16 or out.size != n * oh * ow * oc or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous uint16 array of n*oh*ow*{oc} samples")
+        return out.reshape(n, oh, ow, oc)
+
+    @staticmethod
+    def _u16_shaped(out, squeeze, grey2d):
+        out = out[0] if squeeze else out
+        return out[:, :, 0] if grey2d and out.shape[-1] == 1 else out
+
+    @staticmethod
+    def _u16_dev(px):
+        """A contiguous (n,H,W,C) torch.uint16 tensor on a GPU, C in 1..4 -> (n, h, w, c)."""
+        import torch
+        assert px.is_cuda and px.dtype == torch.uint16 and px.is_contiguous() and px.dim() == 4 and 1 <= px.shape[-1] <= 4
+        return tuple(px.shape)
+
+    def _u16_dev_out(self, out, n, oh, ow, oc, device):
+        import torch
+        if out is None and oh >= 1 and ow >= 1 and oc >= 1:
+            out = torch.empty((n, oh, ow, oc), dtype=torch.uint16, device=device)
+        return out, C.c_void_p(out.data_ptr() if out is not None else None)
+
+    def u16_to_f32_dev(self, px, out=None, stream=None):
+        """sr_u16_to_f32_dev: (n,h,w,C) torch.uint16 on this GPU, C in 1..4 -> (n,h,w,3) f32, sample / 65535 (grey copied to R = G = B,
+        alpha dropped): the network's input."""
+        n, h, w, c = self._u16_dev(px)
+        out = self._dev_out(out, (n, h, w, 3), np.float32, px.device)
+        _lib.check(self._L.sr_u16_to_f32_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w, C.c_void_p(out.data_ptr()),
+                                             self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
+    def f32_to_u16_dev(self, x, channels: int = 3, out=None, stream=None):
+        """sr_f32_to_u16_dev: (n,h,w,3) f32 on this GPU (any values: clamped; NaN counts as 0) -> (n,h,w,channels) torch.uint16,
+        floor(65535 v + 0.5); channels 3 RGB, 4 RGBA with alpha 65535, 1 the grey mean."""
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        out, ptr = self._u16_dev_out(out, n, h, w, int(channels), x.device)
+        _lib.check(self._L.sr_f32_to_u16_dev(self._ctx, C.c_void_p(x.data_ptr()), n, h, w, ptr, int(channels),
+                                             self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def upscale_u16(self, px: np.ndarray, channels=None, members: int = 1, out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_u16: uint16 samples (n,h,w,C), (h,w,C) or (h,w) -> (n,fh,fw,channels) in the same arrangement, the network's f32
+        output quantised once to 65536 levels.  channels: 1, 3 or 4 (default: grey for grey, RGB otherwise)."""
+        px, squeeze, grey2d, n, h, w, c = self._u16_host(px)
+        oc = self._u16_out_channels(channels, c, out)
+        out = self._u16_result(out, n, *self._out_hw(h, w), oc)
+        p = C.POINTER(C.c_uint16)
+        _lib.check(self._L.sr_upscale_u16(self._ctx, px.ctypes.data_as(p), c, n, h, w, out.ctypes.data_as(p), oc, self._members(members)),
+                   self._ctx)
+        return self._u16_shaped(out, squeeze, grey2d)
+
+    def upscale_u16_dev(self, px, channels=None, members: int = 1, out=None, stream=None):
+        """sr_upscale_u16_dev: (n,h,w,C) torch.uint16 on this GPU -> (n,fh,fw,channels) torch.uint16."""
+        n, h, w, c = self._u16_dev(px)
+        oc = self._u16_out_channels(channels, c, out)
+        out, ptr = self._u16_dev_out(out, n, *self._out_hw(h, w), oc, px.device)
+        _lib.check(self._L.sr_upscale_u16_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w, ptr, oc, self._members(members),
+                                              self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
+    def upscale_u16_border(self, px: np.ndarray, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, channels=None,
+                           out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_u16_border: upscale_u16 of the image continued under `mode` (upscale_f32_border between the two conversions)."""
+        px, squeeze, grey2d, n, h, w, c = self._u16_host(px)
+        oc = self._u16_out_channels(channels, c, out)
+        out = self._u16_result(out, n, *self._out_hw(h, w), oc)
+        p = C.POINTER(C.c_uint16)
+        _lib.check(self._L.sr_upscale_u16_border(self._ctx, px.ctypes.data_as(p), c, n, h, w, out.ctypes.data_as(p), oc, self._border_mode(mode),
+                                                 int(pad), self._members(members)), self._ctx)
+        return self._u16_shaped(out, squeeze, grey2d)
+
+    def upscale_u16_border_dev(self, px, mode="wrap", pad: int = _lib.SR_BORDER_PAD_DEFAULT, members: int = 1, channels=None, out=None,
+                               stream=None):
+        n, h, w, c = self._u16_dev(px)
+        oc = self._u16_out_channels(channels, c, out)
+        out, ptr = self._u16_dev_out(out, n, *self._out_hw(h, w), oc, px.device)
+        _lib.check(self._L.sr_upscale_u16_border_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w, ptr, oc, self._border_mode(mode), int(pad),
+                                                     self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
+        return out
+
+    def upscale_u16_sized(self, px: np.ndarray, size, filter="lanczos3", srgb_space=False, members: int = 1, channels=None,
+                          out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_u16_sized: upscale_u16 to size = (oh, ow), the network's f32 output resampled on the device and quantised once."""
+        px, squeeze, grey2d, n, h, w, c = self._u16_host(px)
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        oc = self._u16_out_channels(channels, c, out)
+        out = self._u16_result(out, n, oh, ow, oc)
+        p = C.POINTER(C.c_uint16)
+        _lib.check(self._L.sr_upscale_u16_sized(self._ctx, px.ctypes.data_as(p), c, n, h, w, out.ctypes.data_as(p), oc, oh, ow, flt, flags,
+                                                self._members(members)), self._ctx)
+        return self._u16_shaped(out, squeeze, grey2d)
+
+    def upscale_u16_sized_dev(self, px, size, filter="lanczos3", srgb_space=False, members: int = 1, channels=None, out=None, stream=None):
+        n, h, w, c = self._u16_dev(px)
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        oc = self._u16_out_channels(channels, c, out)
+        out, ptr = self._u16_dev_out(out, n, oh, ow, oc, px.device)
+        _lib.check(self._L.sr_upscale_u16_sized_dev(self._ctx, C.c_void_p(px.data_ptr()), c, n, h, w, ptr, oc, oh, ow, flt, flags,
+                                                    self._members(members), self._stream_ptr(stream, px.device)), self._ctx)
+        return out
 
     # ---- resampling to any size: a separable resampler in Pillow's convention, on the device (include/srhip.h "Resampling to any size") ----
     FILTERS = {"box": _lib.SR_FILTER_BOX, "triangle": _lib.SR_FILTER_TRIANGLE, "catrom": _lib.SR_FILTER_CATROM,

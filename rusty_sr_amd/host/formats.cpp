@@ -246,7 +246,8 @@ bool tiff_packbits(const uint8_t* src, size_t n, std::vector<uint8_t>& out, size
     return true;
 }
 
-bool decode_tiff(const uint8_t* d, size_t len, Image& out, std::string& err) {
+// deep (optional): the file's channel count and depth, and at 16 bits (grey, grey + alpha, RGB, RGBA) its samples with both bytes
+bool decode_tiff(const uint8_t* d, size_t len, Image& out, std::string& err, Image16* deep = nullptr) {
     if (len < 8) { err = "truncated TIFF"; return false; }
     TiffReader r{d, len, d[0] == 'M'};
     if (r.u16(2) != 42) { err = "not a TIFF file"; return false; }
@@ -311,6 +312,11 @@ bool decode_tiff(const uint8_t* d, size_t len, Image& out, std::string& err) {
     if ((uint64_t)row_bytes * h / max_ratio > have + 16) { err = "TIFF data too short"; return false; }
     out.w = (int)w; out.h = (int)h;
     out.rgba.assign((size_t)w * h * 4, 255);
+    if (deep) {
+        deep->channels = photometric == 3 ? 3 : (int)spp;
+        deep->bits = (int)depth;
+        if (depth == 16) deep->px.assign((size_t)w * h * spp, 0);
+    }
     std::vector<uint8_t> strip;
     for (size_t s = 0; s < n_strips; ++s) {
         const size_t y0 = s * rows_per_strip, rows = std::min((size_t)rows_per_strip, (size_t)h - y0), want = rows * row_bytes;
@@ -345,6 +351,13 @@ bool decode_tiff(const uint8_t* d, size_t len, Image& out, std::string& err) {
                 const size_t o = (x * spp + c) * bps;
                 return bps == 1 ? row[o] : (r.be ? row[o] : row[o + 1]);
             };
+            if (deep && depth == 16) {  // (photometric 0 - 2 here: a palette is 8 bits deep)
+                uint16_t* o16 = deep->px.data() + (y0 + y) * (size_t)w * spp;
+                for (size_t i = 0; i < (size_t)w * spp; ++i) {
+                    const uint32_t v = r.be ? (uint32_t)row[2 * i] << 8 | row[2 * i + 1] : (uint32_t)row[2 * i + 1] << 8 | row[2 * i];
+                    o16[i] = (uint16_t)(photometric == 0 && i % spp == 0 ? 65535 - v : v);
+                }
+            }
             for (size_t x = 0; x < (size_t)w; ++x) {
                 uint8_t* o = dst + 4 * x;
                 if (depth == 1) {
@@ -485,11 +498,11 @@ bool decode_ico(const uint8_t* d, size_t len, Image& out, std::string& err) {
 
 }  // namespace
 
-bool decode_more_formats(const uint8_t* d, size_t len, bool tga_by_name, Image& out, std::string& err, bool& recognised) {
+bool decode_more_formats(const uint8_t* d, size_t len, bool tga_by_name, Image& out, std::string& err, bool& recognised, Image16* deep) {
     recognised = true;
     if (len >= 6 && !memcmp(d, "GIF8", 4) && (d[4] == '7' || d[4] == '9') && d[5] == 'a') return decode_gif(d, len, out, err);
     if (len >= 4 && ((d[0] == 'I' && d[1] == 'I' && d[2] == 42 && d[3] == 0) || (d[0] == 'M' && d[1] == 'M' && d[2] == 0 && d[3] == 42)))
-        return decode_tiff(d, len, out, err);
+        return decode_tiff(d, len, out, err, deep);
     if (len >= 6 && d[0] == 0 && d[1] == 0 && d[2] == 1 && d[3] == 0 && !tga_by_name) return decode_ico(d, len, out, err);
     if (tga_by_name) return decode_tga(d, len, out, err);
     recognised = false;

@@ -4,6 +4,9 @@
 //   srcodec_asan FILE...        decode every file the way the CLI's `image::open` stand-in does (main.rs:164) and
 //                               print one line per file: "ok WxH" or "error: <message>"
 //   srcodec_asan --roundtrip W H OUT.png   encode a synthetic RGBA image, decode it again, compare
+//   srcodec_asan --u16 FILE...  decode every file through the deep-colour path (decode_image_file16), touch every sample and print
+//                               "ok WxH channels bits sum" or "error: <message>"
+//   srcodec_asan --roundtrip16 W H CHANNELS OUT.png   encode a synthetic 16-bit image (1 or 3 channels), decode it again, compare
 //   srcodec_asan --degrade-spec SPEC SEED N   parse the CLI's --degrade SPEC (degrade_spec.cpp) and print its first N draws under SEED,
 //                               one "sigma noise quality seed" line each (floats as their bit patterns), or "error: <message>"
 //
@@ -36,6 +39,41 @@ int main(int argc, char** argv) {
         if (!srpng::decode_file(argv[4], img, err)) { printf("error: %s\n", err.c_str()); return 1; }
         if (img.w != w || img.h != h || img.rgba != px) { printf("error: round trip differs\n"); return 1; }
         printf("ok %dx%d\n", w, h);
+        return 0;
+    }
+    if (argc >= 6 && !strcmp(argv[1], "--roundtrip16")) {
+        const int w = atoi(argv[2]), h = atoi(argv[3]), ch = atoi(argv[4]);
+        if (w <= 0 || h <= 0 || w > 4096 || h > 4096) { printf("error: bad size\n"); return 1; }
+        std::vector<uint16_t> px((size_t)w * h * (ch > 0 ? ch : 1));
+        uint32_t z = 54321;
+        for (size_t i = 0; i < px.size(); ++i) {  // noise, flat, ramp and low-byte-only rows in turn
+            z = z * 1664525u + 1013904223u;
+            const size_t y = i / ((size_t)w * (ch > 0 ? ch : 1));
+            const int kind = (int)(y / 3) % 4;
+            px[i] = kind == 0 ? (uint16_t)(z >> 16) : kind == 1 ? (uint16_t)(y * 771) : kind == 2 ? (uint16_t)(i * 37) : (uint16_t)(0x8000 + (z >> 24));
+        }
+        std::string err;
+        if (!srpng::encode_png16_file(argv[5], px.data(), ch, w, h, err)) { printf("error: %s\n", err.c_str()); return 1; }
+        srpng::Image16 img;
+        if (!srpng::decode_image_file16(argv[5], img, err)) { printf("error: %s\n", err.c_str()); return 1; }
+        if (img.w != w || img.h != h || img.channels != ch || img.bits != 16 || img.px != px) { printf("error: round trip differs\n"); return 1; }
+        printf("ok %dx%d %d\n", w, h, ch);
+        return 0;
+    }
+    if (argc >= 2 && !strcmp(argv[1], "--u16")) {
+        for (int i = 2; i < argc; ++i) {
+            srpng::Image16 img;
+            std::string err;
+            if (srpng::decode_image_file16(argv[i], img, err)) {
+                if (img.w <= 0 || img.h <= 0 || img.channels < 1 || img.channels > 4 || img.bits < 1 || img.bits > 16 ||
+                    img.px.size() != (size_t)img.w * img.h * img.channels) { printf("error: inconsistent image\n"); continue; }
+                unsigned long sum = 0;
+                for (uint16_t v : img.px) sum += v;
+                printf("ok %dx%d %d %d %lu\n", img.w, img.h, img.channels, img.bits, sum);
+            } else {
+                printf("error: %s\n", err.c_str());
+            }
+        }
         return 0;
     }
     if (argc >= 5 && !strcmp(argv[1], "--degrade-spec")) {

@@ -87,7 +87,10 @@ const char* kUsage =
     "        --border <MODE>              what lies beyond the image's edges: wrap (a tileable texture stays seamless),\n"
     "                                     replicate or mirror [values: wrap, replicate, mirror] [default: the network's\n"
     "                                     own zero padding]\n"
-    "        --border-pad <N>             with --border: how many pixels the image is continued by, 7..32 [default: 8]\n\n"
+    "        --border-pad <N>             with --border: how many pixels the image is continued by, 7..32 [default: 8]\n"
+    "        --depth <BITS>               bits a sample, in and out: 16 keeps both bytes of a 16-bit PNG / PNM / TIFF and writes\n"
+    "                                     a 16-bit .png (grey stays grey) or .ppm; auto is 16 for such a file and output, else\n"
+    "                                     8 [values: 8, 16, auto] [default: 8]\n\n"
     "ARGS:\n    <INPUT_FILE>     Sets the input image to upscale\n    <OUTPUT_FILE>    Sets the output file to write/overwrite (.png recommended)\n\n"
     "SUBCOMMANDS:\n    train       Trains a new set of neural network parameters on the GPU (rusty_sr train --help)\n"
     "    validate    The validation pass of `train`: PSNR of the parameters on a folder of HR images\n"
@@ -1160,6 +1163,7 @@ int main(int argc, char** argv) {
     double scale = 0;
     unsigned resize_flags = 0;
     std::vector<int> devices;
+    std::string depth_arg = "8";  // --depth 8|16|auto: the deep-colour calls (sr_upscale_u16*) for 16
     if (argc >= 2 && !strcmp(argv[1], "train")) return run_train(argc, argv);  // main.rs:119-121
     if (argc >= 2 && !strcmp(argv[1], "validate")) return run_validate(argc, argv);
     if (argc >= 2 && !strcmp(argv[1], "video")) return run_video(argc, argv);
@@ -1235,6 +1239,11 @@ int main(int argc, char** argv) {
             resize_flags = v == "srgb" ? SR_RESIZE_SRGB_SPACE : 0u;
             has_space = true;
         }
+        else if (a == "--depth" || a.rfind("--depth=", 0) == 0) {
+            depth_arg = a == "--depth" ? value("--depth <BITS>") : a.substr(8);
+            if (depth_arg != "8" && depth_arg != "16" && depth_arg != "auto")
+                usage_error("'" + depth_arg + "' isn't a valid value for '--depth <BITS>'\n\t[values: 16, 8, auto]");
+        }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a == "--degrade") usage_error("The argument '--degrade' can only be used with the 'train' and 'validate' subcommands");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
@@ -1282,6 +1291,18 @@ int main(int argc, char** argv) {
     if (border && resize) usage_error("The argument '--border <MODE>' cannot be used with '" + resize_opt + "': the resampled call has no border modes");
     if (border && devices.size() > 1)
         usage_error("The argument '--border <MODE>' cannot be used with more than one device: the padded call has no multi-GPU form");
+    // --depth 16: the deep-colour calls have no transparency and no multi-GPU form, and only PNG and PPM hold 16-bit samples here
+    std::string out_ext;
+    {
+        const size_t dot = pos[1].find_last_of('.');
+        out_ext = dot == std::string::npos ? "" : pos[1].substr(dot + 1);
+        for (auto& ch : out_ext) ch = (char)tolower((unsigned char)ch);
+    }
+    if (depth_arg == "16" && alpha) usage_error("The argument '--depth 16' cannot be used with '--alpha': there is no 16-bit bleed and merge");
+    if (depth_arg == "16" && devices.size() > 1)
+        usage_error("The argument '--depth 16' cannot be used with more than one device: the deep-colour call has no multi-GPU form");
+    if (depth_arg == "16" && (out_ext == "jpg" || out_ext == "jpeg" || out_ext == "bmp"))
+        usage_error("The argument '--depth 16' cannot be used with a ." + out_ext + " output file: 16-bit samples are written to .png and .ppm only");
     int in_pw = 0, in_ph = 0;
     // (the file's header says how large the input is: a scale that takes it beyond the largest output is refused before any device is touched)
     if (has_scale && srpng::probe_image_size(pos[0], in_pw, in_ph) && !(scaled_axis(in_pw, scale, size_w) && scaled_axis(in_ph, scale, size_h)))
@@ -1325,6 +1346,7 @@ int main(int argc, char** argv) {
         for (auto& ch : ext) ch = (char)tolower((unsigned char)ch);
         if (ext != "png" && ext != "jpg" && ext != "jpeg" && ext != "bmp" && ext != "ppm")
             die("Could not write output file (this build writes .png, .jpg, .bmp and .ppm)");
+        if (depth_arg == "16" && ext != "png" && ext != "ppm") die("Could not write output file (--depth 16 writes .png and .ppm)");
     }
     // The input file decodes on a second thread while this one brings up the device and the contexts (HIP start-up
     // and the weight upload take longer than a 1080p PNG); failures are then reported in the reference's order --
@@ -1333,12 +1355,23 @@ int main(int argc, char** argv) {
     auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     const clk::time_point t_start = clk::now();
     srpng::Image in;
+    srpng::Image16 in16;
     std::string err;
     bool decoded = false;
     double t_decode = 0;
-    std::thread decoder([&] {
+    // --depth auto: 16 where the file holds more than 8 bits a sample and the call and the output can keep them; the file says so once
+    // it is decoded (here, before the device: an 8-bit file then takes today's path untouched)
+    bool deep = depth_arg == "16";
+    if (depth_arg == "auto" && !alpha && devices.size() == 1 && (out_ext == "png" || out_ext == "ppm")) {
         const clk::time_point t = clk::now();
-        decoded = srpng::decode_image_file(pos[0], in, err);
+        std::string err16;
+        if (srpng::decode_image_file16(pos[0], in16, err16) && in16.bits > 8) { deep = decoded = true; t_decode = ms_since(t); }
+        else in16 = srpng::Image16();
+    }
+    std::thread decoder([&] {
+        if (decoded) return;
+        const clk::time_point t = clk::now();
+        decoded = deep ? srpng::decode_image_file16(pos[0], in16, err) : srpng::decode_image_file(pos[0], in, err);
         t_decode = ms_since(t);
     });
     // The file's header already says how large the output is (probe_image_size): a third thread page-locks it -- 15 ms at
@@ -1349,7 +1382,7 @@ int main(int argc, char** argv) {
     int pw = 0, ph = 0;
     const bool sized = srpng::probe_image_size(pos[0], pw, ph) && !(graph == SR_GRAPH_DOWNSAMPLE && (pw < 3 || ph < 3));
     std::thread pinner([&] {
-        if (!sized) return;
+        if (!sized || deep) return;  // (the 16-bit result is an ordinary vector)
         int sw = 0, sh = 0;
         if (has_scale && !(scaled_axis(pw, scale, sw) && scaled_axis(ph, scale, sh))) return;
         const size_t bytes = has_size ? (size_t)size_w * size_h * 4 : has_scale ? (size_t)sw * sh * 4
@@ -1361,13 +1394,13 @@ int main(int argc, char** argv) {
     for (size_t k = 0; k < devices.size() && rc == SR_OK; ++k) {
         rc = sr_create_graph(&ctxs[k], graph, params.empty() ? nullptr : params.data(), params.size(), SR_FACTOR, devices[k]);
         if (rc == SR_OK && graph == SR_GRAPH_SR_NET) rc = sr_set_precision(ctxs[k], precision == "f32" ? SR_PRECISION_F32 : SR_PRECISION_SPLIT_F16);
-        if (rc == SR_OK && (ensemble || alpha || resize || border) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble, alpha, border and resampled calls time themselves only when asked to)
+        if (rc == SR_OK && (ensemble || alpha || resize || border || deep) && timing) rc = sr_set_profiling(ctxs[k], 1);  // (the ensemble, alpha, border and resampled calls time themselves only when asked to)
     }
     const double t_create = ms_since(t_start);
     double t_prep = 0;
     {
         const clk::time_point t = clk::now();
-        if (rc == SR_OK && sized && ctxs.size() == 1 && !resize) (void)sr_reserve_rgba8(ctxs[0], 4, 1, ph, pw);  // best effort: the real call reports errors
+        if (rc == SR_OK && sized && ctxs.size() == 1 && !resize && !deep) (void)sr_reserve_rgba8(ctxs[0], 4, 1, ph, pw);  // best effort: the real call reports errors
         pinner.join();
         t_prep = ms_since(t);
     }
@@ -1376,12 +1409,41 @@ int main(int argc, char** argv) {
     sr_ctx* ctx = ctxs[0];
     if (!decoded) die("Error opening input image file. (" + err + ")");  // main.rs:164
     const double t_ready = ms_since(t_start);
+    if (deep) { in.w = in16.w; in.h = in16.h; }
     if (graph == SR_GRAPH_DOWNSAMPLE && (in.w < 3 || in.h < 3)) die("input image is smaller than one 3x3 pooling block");
 
     if (has_scale && !(scaled_axis(in.w, scale, size_w) && scaled_axis(in.h, scale, size_h)))  // (a file whose header could not be probed)
         usage_error("'" + scale_arg + "' isn't a valid value for '--scale <S>'\n\t[the output would exceed 16384 pixels on an axis]");
     const int ow = resize ? size_w : graph == SR_GRAPH_DOWNSAMPLE ? in.w / 3 : in.w * 3;
     const int oh = resize ? size_h : graph == SR_GRAPH_DOWNSAMPLE ? in.h / 3 : in.h * 3;
+    if (deep) {  // 16-bit samples in and out: grey stays grey where the container can say so (PNG colour type 0), else RGB
+        const int oc = in16.channels <= 2 && out_ext == "png" ? 1 : 3;
+        std::vector<uint16_t> out16((size_t)ow * oh * oc);
+        const unsigned members = ensemble ? ensemble : 1u;
+        const clk::time_point t_up = clk::now();
+        rc = resize ? sr_upscale_u16_sized(ctx, in16.px.data(), in16.channels, 1, in.h, in.w, out16.data(), oc, oh, ow, filter, resize_flags, members)
+             : border ? sr_upscale_u16_border(ctx, in16.px.data(), in16.channels, 1, in.h, in.w, out16.data(), oc, border, border_pad, members)
+                      : sr_upscale_u16(ctx, in16.px.data(), in16.channels, 1, in.h, in.w, out16.data(), oc, members);
+        if (rc != SR_OK) die(std::string(sr_strerror(rc)) + (rc == SR_E_HIP ? " (hipError " + std::to_string(sr_last_hip_error(ctx)) + ")" : ""));
+        const double t_upscale = ms_since(t_up);
+        if (timing) {
+            double tot = 0, h2d = 0, d2h = 0;
+            sr_last_timing(ctx, &tot, nullptr, &h2d, &d2h);
+            fprintf(stderr, "\n[timing] %dx%d -> %dx%d, 16 bits, %d -> %d channels%s: kernels %.3f ms, h2d %.3f ms, d2h %.3f ms\n", in.w, in.h, ow, oh,
+                    in16.channels, oc, ensemble ? (" (ensemble of " + std::to_string(__builtin_popcount(ensemble)) + ")").c_str() : "", tot, h2d, d2h);
+        }
+        printf(" Writing file...");
+        fflush(stdout);
+        const clk::time_point t_enc = clk::now();
+        if (!srpng::encode_image_file16(pos[1], out16.data(), oc, ow, oh, err)) die("Could not write output file (" + err + ")");
+        puts(" Done");
+        if (timing)
+            fprintf(stderr, "[timing] wall: decode %.1f ms || device + contexts %.1f ms -> ready at %.1f ms; upscale call %.1f ms; encode + write %.1f ms; "
+                            "total %.1f ms\n", t_decode, t_create, t_ready, t_upscale, ms_since(t_enc), ms_since(t_start));
+        if (pinned) sr_host_free(pinned);
+        for (sr_ctx* c : ctxs) sr_destroy(c);
+        return 0;
+    }
     // page-locked output pixels: the download then runs at PCIe rate under the kernels of the next band
     const size_t out_bytes = (size_t)ow * oh * 4;
     const clk::time_point t_al = clk::now();

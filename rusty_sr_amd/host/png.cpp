@@ -112,9 +112,14 @@ struct Hdr { int w, h, depth, ctype, interlace; };
 int channels_of(int ctype) { return ctype == 0 ? 1 : ctype == 2 ? 3 : ctype == 3 ? 1 : ctype == 4 ? 2 : 4; }
 
 // expand one unfiltered scanline of `n` pixels to RGBA8 at out[(x0 + k*dx)]
+// (deep: the row of the 16-bit picture, at depth 16 only -- both bytes of every sample, the file's channels)
 void expand_row(const Hdr& H, const uint8_t* row, int n, const std::vector<uint8_t>& plte,
-                const std::vector<uint8_t>& trns, uint8_t* out, int x0, int dx) {
+                const std::vector<uint8_t>& trns, uint8_t* out, int x0, int dx, uint16_t* deep = nullptr) {
     const int ch = channels_of(H.ctype);
+    if (deep && H.depth == 16)
+        for (int k = 0; k < n; ++k)
+            for (int c = 0; c < ch; ++c)
+                deep[(size_t)(x0 + k * dx) * ch + c] = (uint16_t)(row[(k * ch + c) * 2] << 8 | row[(k * ch + c) * 2 + 1]);
     if (H.depth == 8 && dx == 1 && (H.ctype == 2 || H.ctype == 6)) {  // the common cases, without the per-sample tests
         uint8_t* o = out + (size_t)x0 * 4;
         if (H.ctype == 6) { memcpy(o, row, (size_t)n * 4); return; }
@@ -154,7 +159,12 @@ void expand_row(const Hdr& H, const uint8_t* row, int n, const std::vector<uint8
 
 }  // namespace
 
-bool decode_memory(const uint8_t* p, size_t len, Image& out, std::string& err) {
+static bool decode_png(const uint8_t* p, size_t len, Image& out, std::string& err, Image16* deep);
+
+bool decode_memory(const uint8_t* p, size_t len, Image& out, std::string& err) { return decode_png(p, len, out, err, nullptr); }
+
+// deep (optional): the file's channel count and depth, and at depth 16 its samples with both bytes
+static bool decode_png(const uint8_t* p, size_t len, Image& out, std::string& err, Image16* deep) {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (len < 8 || memcmp(p, sig, 8)) { err = "not a PNG file"; return false; }
     Hdr H{0, 0, 0, 0, 0};
@@ -205,6 +215,12 @@ bool decode_memory(const uint8_t* p, size_t len, Image& out, std::string& err) {
     if (zr != Z_OK || got != raw_len) { err = "PNG inflate failed"; return false; }
     out.w = H.w; out.h = H.h;
     out.rgba.assign((size_t)H.w * H.h * 4, 0);
+    const int ch = channels_of(H.ctype);
+    if (deep) {
+        deep->channels = H.ctype == 3 ? 4 : ch;  // (a palette is read as the RGBA the 8-bit path makes of it)
+        deep->bits = H.depth;
+        if (H.depth == 16) deep->px.assign((size_t)H.w * H.h * ch, 0);
+    }
     size_t off = 0;
     for (int k = 0; k < npass; ++k) {
         if (pw[k] <= 0 || ph[k] <= 0) continue;
@@ -213,7 +229,8 @@ bool decode_memory(const uint8_t* p, size_t len, Image& out, std::string& err) {
         for (int y = 0; y < ph[k]; ++y) {
             const int oy = H.interlace ? ys[k] + y * dys[k] : y;
             expand_row(H, raw.data() + off + (size_t)y * (st + 1) + 1, pw[k], plte, trns,
-                       out.rgba.data() + (size_t)oy * H.w * 4, H.interlace ? xs[k] : 0, H.interlace ? dxs[k] : 1);
+                       out.rgba.data() + (size_t)oy * H.w * 4, H.interlace ? xs[k] : 0, H.interlace ? dxs[k] : 1,
+                       deep && H.depth == 16 ? deep->px.data() + (size_t)oy * H.w * ch : nullptr);
         }
         off += (size_t)ph[k] * (st + 1);
     }
@@ -232,7 +249,8 @@ static bool read_all(const std::string& path, std::vector<uint8_t>& buf, std::st
 }
 
 // PPM / PGM / PBM: binary (P6 / P5 / P4) and plain (P3 / P2 / P1), maxval <= 65535
-static bool decode_pnm(const uint8_t* d, size_t len, Image& out, std::string& err) {
+// deep (optional): the file's channel count and the bits of its maxval, and for a maxval above 255 its samples on 0 .. 65535
+static bool decode_pnm(const uint8_t* d, size_t len, Image& out, std::string& err, Image16* deep = nullptr) {
     const int kind = d[1] - '0';
     const bool plain = kind <= 3, bitmap = kind == 1 || kind == 4;
     const int ch = (kind == 3 || kind == 6) ? 3 : 1;
@@ -261,7 +279,15 @@ static bool decode_pnm(const uint8_t* d, size_t len, Image& out, std::string& er
     }
     out.w = (int)w; out.h = (int)h;
     out.rgba.assign((size_t)w * h * 4, 255);
+    if (deep) {
+        deep->channels = ch;
+        deep->bits = 1;
+        while ((1L << deep->bits) <= maxv) ++deep->bits;
+        if (maxv > 255) deep->px.assign((size_t)w * h * ch, 0);
+    }
+    const bool deep_px = deep && maxv > 255;
     auto put = [&](size_t p, int c, long v) {
+        if (deep_px) deep->px[p * ch + c] = (uint16_t)((std::min(v, maxv) * 65535 + maxv / 2) / maxv);
         const uint8_t q = (uint8_t)((std::min(v, maxv) * 255 + maxv / 2) / maxv);
         if (ch == 3) out.rgba[p * 4 + c] = q; else out.rgba[p * 4] = out.rgba[p * 4 + 1] = out.rgba[p * 4 + 2] = q;
     };
@@ -333,8 +359,8 @@ static bool decode_bmp(const uint8_t* d, size_t len, Image& out, std::string& er
     return true;
 }
 
-bool decode_more_formats(const uint8_t* d, size_t len, bool tga_by_name, Image& out, std::string& err, bool& recognised);  // formats.cpp
-static bool decode_any_memory(const std::vector<uint8_t>& buf, Image& out, std::string& err, bool tga_by_name);
+bool decode_more_formats(const uint8_t* d, size_t len, bool tga_by_name, Image& out, std::string& err, bool& recognised, Image16* deep = nullptr);  // formats.cpp
+static bool decode_any_memory(const std::vector<uint8_t>& buf, Image& out, std::string& err, bool tga_by_name, Image16* deep = nullptr);
 
 bool probe_image_size(const std::string& path, int& w, int& h) {
     FILE* f = fopen(path.c_str(), "rb");
@@ -388,7 +414,35 @@ bool probe_image_size(const std::string& path, int& w, int& h) {
     return true;
 }
 
-bool decode_image_file(const std::string& path, Image& out, std::string& err) {
+static bool decode_image_path(const std::string& path, Image& out, std::string& err, Image16* deep);
+
+bool decode_image_file(const std::string& path, Image& out, std::string& err) { return decode_image_path(path, out, err, nullptr); }
+
+// The deep-colour path: the same decoders with a 16-bit sink beside the RGBA8 picture; where a decoder left the sink empty -- samples
+// of 8 bits or fewer, a container without deep samples -- the picture is the 8-bit one times 257.
+bool decode_image_file16(const std::string& path, Image16& out, std::string& err) {
+    Image img8;
+    out = Image16();
+    if (!decode_image_path(path, img8, err, &out)) { out = Image16(); return false; }
+    out.w = img8.w; out.h = img8.h;
+    const size_t npx = (size_t)img8.w * img8.h;
+    if (out.channels < 1 || out.channels > 4) { out.channels = 4; out.bits = 8; out.px.clear(); }
+    if (out.px.size() == npx * out.channels) return true;
+    if (out.bits > 8) out.bits = 8;  // (what is kept is the 8-bit decoder's value)
+    static const int from[5][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 3, 0, 0}, {0, 1, 2, 0}, {0, 1, 2, 3}};
+    try {
+        out.px.resize(npx * out.channels);
+    } catch (const std::exception& e) {
+        err = std::string("image too large or corrupt (") + e.what() + ")";
+        out = Image16();
+        return false;
+    }
+    for (size_t p = 0; p < npx; ++p)
+        for (int c = 0; c < out.channels; ++c) out.px[p * out.channels + c] = (uint16_t)(img8.rgba[p * 4 + from[out.channels][c]] * 257);
+    return true;
+}
+
+static bool decode_image_path(const std::string& path, Image& out, std::string& err, Image16* deep) {
     std::vector<uint8_t> buf;
     if (!read_all(path, buf, err)) return false;
     // TGA has no magic bytes: like the image crate (which goes by the extension for every format) it is taken by name
@@ -400,7 +454,7 @@ bool decode_image_file(const std::string& path, Image& out, std::string& err) {
         tga = ext == "tga";
     }
     try {  // backstop: whatever a hostile header makes a container ask for, the caller gets an error, not a terminate()
-        return decode_any_memory(buf, out, err, tga);
+        return decode_any_memory(buf, out, err, tga, deep);
     } catch (const std::exception& e) {
         err = std::string("image too large or corrupt (") + e.what() + ")";
         out = Image();
@@ -408,13 +462,13 @@ bool decode_image_file(const std::string& path, Image& out, std::string& err) {
     }
 }
 
-static bool decode_any_memory(const std::vector<uint8_t>& buf, Image& out, std::string& err, bool tga_by_name) {
-    if (buf.size() >= 8 && buf[0] == 0x89 && buf[1] == 'P') return decode_memory(buf.data(), buf.size(), out, err);
+static bool decode_any_memory(const std::vector<uint8_t>& buf, Image& out, std::string& err, bool tga_by_name, Image16* deep) {
+    if (buf.size() >= 8 && buf[0] == 0x89 && buf[1] == 'P') return decode_png(buf.data(), buf.size(), out, err, deep);
     if (buf.size() >= 4 && buf[0] == 0xff && buf[1] == 0xd8) return decode_jpeg_memory(buf.data(), buf.size(), out, err);
-    if (buf.size() >= 7 && buf[0] == 'P' && buf[1] >= '1' && buf[1] <= '6' && isspace(buf[2])) return decode_pnm(buf.data(), buf.size(), out, err);
+    if (buf.size() >= 7 && buf[0] == 'P' && buf[1] >= '1' && buf[1] <= '6' && isspace(buf[2])) return decode_pnm(buf.data(), buf.size(), out, err, deep);
     if (buf.size() >= 54 && buf[0] == 'B' && buf[1] == 'M') return decode_bmp(buf.data(), buf.size(), out, err);
     bool recognised = false;
-    const bool ok = decode_more_formats(buf.data(), buf.size(), tga_by_name, out, err, recognised);  // GIF, TIFF, ICO, TGA
+    const bool ok = decode_more_formats(buf.data(), buf.size(), tga_by_name, out, err, recognised, deep);  // GIF, TIFF, ICO, TGA
     if (!recognised) err = "unrecognised image format (this build reads PNG, JPEG, GIF, TIFF, BMP, ICO, TGA, PPM/PGM/PBM)";
     if (!ok) out = Image();
     return ok;
@@ -489,19 +543,49 @@ static int filter_row(const uint8_t* cur, const uint8_t* prev, size_t stride, ui
     return best;
 }
 
+// The same choice for any pixel size (the 16-bit pictures: 2 or 6 bytes a pixel), byte by byte.
+static int filter_row_any(const uint8_t* cur, const uint8_t* prev, size_t stride, size_t bpp, uint8_t* cand /* 4 x stride */) {
+    uint8_t* f[4] = {cand, cand + stride, cand + 2 * stride, cand + 3 * stride};
+    uint32_t sum[4] = {0, 0, 0, 0};
+    for (size_t i = 0; i < stride; ++i) {
+        const int x = cur[i], a = i >= bpp ? cur[i - bpp] : 0, bb = prev ? prev[i] : 0, c = prev && i >= bpp ? prev[i - bpp] : 0;
+        const uint8_t r[4] = {(uint8_t)x, (uint8_t)(x - a), (uint8_t)(x - bb), (uint8_t)(x - paeth(a, bb, c))};
+        for (int k = 0; k < 4; ++k) { f[k][i] = r[k]; sum[k] += r[k] < 128 ? r[k] : 256u - r[k]; }
+    }
+    static const int type[4] = {0, 1, 2, 4};
+    int best = 0;
+    for (int k = 1; k < 4; ++k) if (sum[k] < sum[best]) best = k;
+    return type[best];
+}
+
 // Filter + deflate rows [y0, y1) into one raw-deflate segment that ends on a byte boundary (Z_SYNC_FLUSH) or, for the
 // last band, with the final block (Z_FINISH): segments of independent bands concatenate into one valid deflate stream
 // (the pigz construction).  The segment comes back wrapped as a complete IDAT chunk -- length, type, data, CRC -- so the
 // CRC is computed here too, in parallel; the first band's data starts with the two zlib header bytes.
-static bool encode_band(const uint8_t* rgba, int w, int y0, int y1, bool first, bool last, int zlevel,
-                        uint8_t* raw /* (stride + 1) * rows */, uint8_t* cand /* 4 * stride */, uint8_t* chunk, size_t cap, size_t& chunk_len,
-                        uLong& adler, size_t& raw_len) {
-    const size_t stride = (size_t)w * 4;
+// one row of native-endian 16-bit samples -> high byte first, as the PNG stores them
+static void big_endian_row(const uint8_t* row, uint8_t* dst, size_t stride) {
+    const uint16_t* v = (const uint16_t*)row;
+    for (size_t i = 0; i < stride / 2; ++i) { dst[2 * i] = (uint8_t)(v[i] >> 8); dst[2 * i + 1] = (uint8_t)v[i]; }
+}
+
+// swp (the 16-bit pictures; else nullptr): two rows of scratch -- the rows are native-endian uint16_t and are put high byte first here,
+// band by band on the worker threads, the row in hand and the one above it
+static bool encode_band(const uint8_t* rgba, size_t stride, size_t bpp, int y0, int y1, bool first, bool last, int zlevel,
+                        uint8_t* raw /* (stride + 1) * rows */, uint8_t* cand /* 4 * stride */, uint8_t* swp /* 2 * stride */, uint8_t* chunk,
+                        size_t cap, size_t& chunk_len, uLong& adler, size_t& raw_len) {
     for (int y = y0; y < y1; ++y) {
         const uint8_t* cur = rgba + (size_t)y * stride;
         const uint8_t* prev = y ? cur - stride : nullptr;  // the row above, also across band seams
+        if (swp) {
+            uint8_t* mine = swp + (size_t)(y & 1) * stride;
+            uint8_t* above = swp + (size_t)((y & 1) ^ 1) * stride;  // (row y - 1 went there one step ago, but for the band's first row)
+            if (y == y0 && y) big_endian_row(prev, above, stride);
+            big_endian_row(cur, mine, stride);
+            cur = mine;
+            prev = y ? above : nullptr;
+        }
         uint8_t* dst = raw + (size_t)(y - y0) * (stride + 1);
-        const int ft = filter_row(cur, prev, stride, cand);
+        const int ft = bpp == 4 ? filter_row(cur, prev, stride, cand) : filter_row_any(cur, prev, stride, bpp, cand);
         dst[0] = (uint8_t)ft;
         memcpy(dst + 1, cand + (ft == 4 ? 3 : ft) * stride, stride);
     }
@@ -544,13 +628,21 @@ static bool encode_band(const uint8_t* rgba, int w, int y0, int y1, bool first, 
     return true;
 }
 
+static bool encode_rows(const std::string& path, const uint8_t* rgba, int w, int h, size_t bpp, int depth, int ctype, std::string& err, int zlevel);
+
 bool encode_file(const std::string& path, const uint8_t* rgba, int w, int h, std::string& err, int zlevel) {
+    return encode_rows(path, rgba, w, h, 4, 8, 6, err, zlevel);  // 8-bit RGBA like the reference's outputs
+}
+
+// h rows of w pixels of bpp bytes under that IHDR depth and colour type; at depth 16 the samples are native-endian uint16_t (2-byte
+// aligned) and the bands put them high byte first
+static bool encode_rows(const std::string& path, const uint8_t* rgba, int w, int h, size_t bpp, int depth, int ctype, std::string& err, int zlevel) {
     if (w <= 0 || h <= 0 || !rgba) { err = "empty image"; return false; }
     // At 4K-in the RGBA output is 299 MB: a single-threaded filter + deflate would dwarf the GPU time (SURVEY.md 8(f)
     // item 2).  Row bands of 1-2 MB are filtered, deflated and wrapped as IDAT chunks by a pool of worker threads that
     // take them in order; this thread writes each chunk as soon as all before it are out, so compression, CRC and the
     // file write overlap and nothing is concatenated in memory.
-    const size_t stride = (size_t)w * 4, bytes = stride * h;
+    const size_t stride = (size_t)w * bpp, bytes = stride * h;
     if (zlevel < 0) zlevel = 1;  // run-length + Huffman (encode_band)
     // bands of 1-2 MB, their number a multiple of the worker count so that the last round of bands is a full one
     const size_t cpus = usable_cpus();
@@ -573,7 +665,7 @@ bool encode_file(const std::string& path, const uint8_t* rgba, int w, int h, std
     const uint32_t W = (uint32_t)w, Hh = (uint32_t)h;
     ihdr[0] = W >> 24; ihdr[1] = W >> 16; ihdr[2] = W >> 8; ihdr[3] = W;
     ihdr[4] = Hh >> 24; ihdr[5] = Hh >> 16; ihdr[6] = Hh >> 8; ihdr[7] = Hh;
-    ihdr[8] = 8; ihdr[9] = 6; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8-bit RGBA like the reference's outputs
+    ihdr[8] = (uint8_t)depth; ihdr[9] = (uint8_t)ctype; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
     chunk(head, "IHDR", ihdr, 13);
     bool ok = fwrite(head.data(), 1, head.size(), f) == head.size();
 
@@ -593,14 +685,15 @@ bool encode_file(const std::string& path, const uint8_t* rgba, int w, int h, std
     std::atomic<int> next{0};
     auto worker = [&] {
         std::unique_ptr<uint8_t[]> raw(new (std::nothrow) uint8_t[(stride + 1) * rows_per]), cand(new (std::nothrow) uint8_t[4 * stride]);
+        std::unique_ptr<uint8_t[]> swp(depth == 16 ? new (std::nothrow) uint8_t[2 * stride] : nullptr);
         for (;;) {
             const int b = next.fetch_add(1);
             if (b >= nband) return;
             const int y0 = b * rows_per, y1 = std::min(h, y0 + rows_per);
             bool good = false;
-            if (raw && cand)
-                good = encode_band(rgba, w, y0, y1, b == 0, b == nband - 1, zlevel, raw.get(), cand.get(), arena.get() + slot * b, slot, part_len[b],
-                                   adl[b], rawlen[b]);
+            if (raw && cand && (swp || depth != 16))
+                good = encode_band(rgba, stride, bpp, y0, y1, b == 0, b == nband - 1, zlevel, raw.get(), cand.get(), swp.get(), arena.get() + slot * b, slot,
+                                   part_len[b], adl[b], rawlen[b]);
             { std::lock_guard<std::mutex> lk(mu); state[b] = good ? 1 : 2; }
             cv.notify_all();
         }
@@ -674,9 +767,70 @@ bool encode_image_file(const std::string& path, const uint8_t* rgba, int w, int 
     return ok;
 }
 
+static std::string lower_ext(const std::string& path) {
+    std::string ext;
+    const size_t dot = path.find_last_of('.');
+    if (dot != std::string::npos) ext = path.substr(dot + 1);
+    for (auto& ch : ext) ch = (char)tolower((unsigned char)ch);
+    return ext;
+}
+
+static bool channels16_ok(const uint16_t* px, int channels, int w, int h, std::string& err) {
+    if (w <= 0 || h <= 0 || !px) { err = "empty image"; return false; }
+    if (channels != 1 && channels != 3) { err = "16-bit output takes 1 (grey) or 3 (RGB) channels"; return false; }
+    return true;
+}
+
+bool encode_png16_file(const std::string& path, const uint16_t* px, int channels, int w, int h, std::string& err) {
+    if (!channels16_ok(px, channels, w, h, err)) return false;
+    return encode_rows(path, (const uint8_t*)px, w, h, (size_t)channels * 2, 16, channels == 1 ? 0 : 2, err, -1);
+}
+
+bool encode_image_file16(const std::string& path, const uint16_t* px, int channels, int w, int h, std::string& err) {
+    const std::string ext = lower_ext(path);
+    if (ext == "png") return encode_png16_file(path, px, channels, w, h, err);
+    if (ext != "ppm") { err = "unsupported 16-bit output format '." + ext + "' (this build writes 16-bit .png and .ppm)"; return false; }
+    if (!channels16_ok(px, channels, w, h, err)) return false;
+    std::unique_ptr<uint8_t[]> row(new (std::nothrow) uint8_t[(size_t)w * 6]);  // one row, high byte first; grey is written as R = G = B
+    if (!row) { err = "out of memory"; return false; }
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) { err = "cannot create file"; return false; }
+    bool ok = fprintf(f, "P6\n%d %d\n65535\n", w, h) > 0;
+    for (int y = 0; y < h && ok; ++y) {
+        const uint16_t* src = px + (size_t)y * w * channels;
+        for (int x = 0; x < w; ++x)
+            for (int c = 0; c < 3; ++c) {
+                const uint16_t v = src[(size_t)x * channels + (channels == 1 ? 0 : c)];
+                row[((size_t)x * 3 + c) * 2] = (uint8_t)(v >> 8);
+                row[((size_t)x * 3 + c) * 2 + 1] = (uint8_t)v;
+            }
+        ok = fwrite(row.get(), 1, (size_t)w * 6, f) == (size_t)w * 6;
+    }
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) { remove(path.c_str()); err = "short write"; }
+    return ok;
+}
+
 }  // namespace srpng
 
 extern "C" {
+int srpng_decode_any_u16(const char* path, int* w, int* h, int* channels, int* bits, uint16_t** px) {
+    srpng::Image16 img; std::string err;
+    if (!srpng::decode_image_file16(path, img, err)) return -1;
+    *w = img.w; *h = img.h; *channels = img.channels; *bits = img.bits;
+    *px = (uint16_t*)malloc(img.px.size() * sizeof(uint16_t));
+    if (!*px) return -1;
+    memcpy(*px, img.px.data(), img.px.size() * sizeof(uint16_t));
+    return 0;
+}
+int srpng_encode_png_u16(const char* path, const uint16_t* px, int channels, int w, int h) {
+    std::string err;
+    return srpng::encode_png16_file(path, px, channels, w, h, err) ? 0 : -1;
+}
+int srpng_encode_any_u16(const char* path, const uint16_t* px, int channels, int w, int h) {
+    std::string err;
+    return srpng::encode_image_file16(path, px, channels, w, h, err) ? 0 : -1;
+}
 int srpng_encode_any_rgba8(const char* path, const uint8_t* rgba, int w, int h) {
     std::string err;
     return srpng::encode_image_file(path, rgba, w, h, err) ? 0 : -1;
