@@ -852,6 +852,29 @@ int sr_upscale_u16_sized_dev(sr_ctx* ctx, const uint16_t* d_in, int in_channels,
 int sr_upscale_u16_sized(sr_ctx* ctx, const uint16_t* in, int in_channels, int n, int h, int w, uint16_t* out, int out_channels,
                          int oh, int ow, int filter, unsigned flags, unsigned members);
 
+/* ---- The training objective: squared, L1 or Charbonnier ----
+ * The reference trains a sum of squares (network.rs:78-103), and that is the default.  UNPINNED: the other two kinds have no counterpart
+ * there; tests/loss_ref.py states them in torch f64 and the tests hold the GPU to it.  With e exactly as in "Backpropagation" above
+ * (out - hr, or SrgbToLinear(out) - SrgbToLinear(hr) under linear_loss) the loss is loss_scale * sum rho(e) + l2 * sum p^2:
+ *   SR_LOSS_MSE          rho(e) = e^2                          rho'(e) = 2 e: the kernels and the bits of a context that never called this
+ *   SR_LOSS_L1           rho(e) = |e|                          rho'(e) = -1, 0 or +1, 0 at e == 0 (the subgradient torch's abs takes)
+ *   SR_LOSS_CHARBONNIER  rho(e) = sqrt(e^2 + eps^2) - eps      rho'(e) = e / sqrt(e^2 + eps^2), in f32 with a correctly rounded square
+ *                        root and division (no approximate reciprocal): the same bits on every run, context and device
+ * sr_set_loss: state of the context, like sr_set_precision; a host-side field and no device work.  Every backward pass queued on the
+ *   context afterwards uses it: sr_backprop_* and sr_pair_backprop_* (host and _dev forms) and every step of a training session on the
+ *   context (sr_train_step, _aug, _pairs, _pairs_aug, _degrade).  A pass uses the value in force when it was QUEUED: its kernel
+ *   arguments are captured then, so changing the objective while earlier steps are in flight neither waits for them nor touches them.
+ *   eps is read for SR_LOSS_CHARBONNIER alone (any value passes with the other kinds, and sr_get_loss then keeps reporting the last eps
+ *   that was set; 1e-3 on a fresh context).
+ * err_sum stays the sum of e^2 under every kind: the PSNR lines and sr_train_sync stay comparable between runs of different objectives.
+ *   The value of sum rho(e) is not returned.  sr_validation_error_*, the metrics calls and inference do not look at the objective.
+ * Refused, the state unchanged: a null ctx (SR_E_INVALID; SR_E_NO_DEVICE without a device, like the other training entry points); a
+ * context that is not SR_GRAPH_SR_NET, a kind outside the three, and for SR_LOSS_CHARBONNIER an eps that is NaN, infinite, <= 0 or > 1
+ * (SR_E_INVALID); sr_get_loss: a null ctx likewise, a context that is not SR_GRAPH_SR_NET.  kind / eps of sr_get_loss may be null.  Cost: DESIGN.md 4s. */
+enum sr_loss { SR_LOSS_MSE = 0, SR_LOSS_L1 = 1, SR_LOSS_CHARBONNIER = 2 };
+int sr_set_loss(sr_ctx* ctx, int kind, float eps);
+int sr_get_loss(sr_ctx* ctx, int* kind, float* eps);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

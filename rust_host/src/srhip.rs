@@ -99,6 +99,9 @@ pub const SR_BORDER_REPLICATE: c_int = 2;
 pub const SR_BORDER_MIRROR: c_int = 3;
 pub const SR_BORDER_PAD_DEFAULT: c_int = 8;
 pub const SR_BORDER_PAD_MAX: c_int = 32;
+pub const SR_LOSS_MSE: c_int = 0;
+pub const SR_LOSS_L1: c_int = 1;
+pub const SR_LOSS_CHARBONNIER: c_int = 2;
 
 extern "C" {
     pub fn sr_rsr_decode(blob: *const u8, len: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
@@ -235,6 +238,8 @@ extern "C" {
     pub fn sr_upscale_u16_border(ctx: *mut SrCtx, input: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, out: *mut u16, out_channels: c_int, mode: c_int, pad: c_int, members: c_uint) -> c_int;
     pub fn sr_upscale_u16_sized_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_u16_sized(ctx: *mut SrCtx, input: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, out: *mut u16, out_channels: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
+    pub fn sr_set_loss(ctx: *mut SrCtx, kind: c_int, eps: f32) -> c_int;
+    pub fn sr_get_loss(ctx: *mut SrCtx, kind: *mut c_int, eps: *mut f32) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.
@@ -315,6 +320,12 @@ impl Engine {
 
     pub fn set_precision(&mut self, mode: c_int) -> Result<(), String> {
         let rc = unsafe { sr_set_precision(self.ctx, mode) };
+        if rc == SR_OK { Ok(()) } else { Err(strerror(rc)) }
+    }
+
+    /// The objective of every backward pass queued on this context from now on (SR_LOSS_*; eps: Charbonnier's, 0 < eps <= 1).
+    pub fn set_loss(&mut self, kind: c_int, eps: f32) -> Result<(), String> {
+        let rc = unsafe { sr_set_loss(self.ctx, kind, eps) };
         if rc == SR_OK { Ok(()) } else { Err(strerror(rc)) }
     }
 

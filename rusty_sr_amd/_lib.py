@@ -33,6 +33,7 @@ SR_YUV_BT601, SR_YUV_BT709 = 0, 1
 SR_YUV_LIMITED, SR_YUV_FULL = 0, 1
 SR_YUV_SPAN = 1024  # luma columns a workgroup of either conversion takes, two rows at a time (the tests put widths either side of it)
 SR_DEEP_SPAN = 2048  # pixels a workgroup of either deep-colour conversion takes, 8 a lane (the tests put counts either side of it)
+SR_LOSS_MSE, SR_LOSS_L1, SR_LOSS_CHARBONNIER = 0, 1, 2
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -197,6 +198,8 @@ SYMBOLS = {
     "sr_upscale_u16_border": (_i, [_vp, _u16p, _i, _i, _i, _i, _u16p, _i, _i, _i, C.c_uint]),
     "sr_upscale_u16_sized_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, C.c_uint, C.c_uint, _vp]),
     "sr_upscale_u16_sized": (_i, [_vp, _u16p, _i, _i, _i, _i, _u16p, _i, _i, _i, _i, C.c_uint, C.c_uint]),
+    "sr_set_loss": (_i, [_vp, _i, C.c_float]),
+    "sr_get_loss": (_i, [_vp, C.POINTER(_i), _fp]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

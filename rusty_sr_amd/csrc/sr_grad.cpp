@@ -129,6 +129,7 @@ int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8
     p.hr = d_hr; p.hr_u8 = hr_u8; p.hr_ch = ch; p.hr_h = h; p.hr_w = w;
     p.tab = c->d_vtab;
     p.linear = linear; p.loss_scale = loss_scale; p.l2 = l2;
+    p.loss_kind = c->loss_kind; p.loss_eps = c->loss_eps;  // the objective in force now: kernel arguments of this pass from here on
     p.ws = (float*)((char*)c->d_gws.p + x_bytes);
     p.err_out = d_err;
     p.grad = d_grad;
@@ -176,6 +177,29 @@ int sr_pair_backprop_rgba8_dev(sr_ctx* c, const float* d_params, const uint8_t* 
                                int n, int lh, int lw, int linear_loss, float loss_scale, float l2, double* d_err_sum, float* d_grad,
                                void* stream) {
     return backprop_dev(c, d_params, true, d_lr, lr_channels, d_hr, hr_channels, n, lh, lw, linear_loss, loss_scale, l2, d_err_sum, d_grad, stream);
+}
+
+// The objective of the backward passes queued from now on (include/srhip.h): host-side state, read by sr_grad_queue.
+int sr_set_loss(sr_ctx* c, int kind, float eps) {
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    if (!c || c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    if (kind != SR_LOSS_MSE && kind != SR_LOSS_L1 && kind != SR_LOSS_CHARBONNIER) return SR_E_INVALID;
+    if (kind == SR_LOSS_CHARBONNIER) {
+        if (!(eps > 0.0f && eps <= 1.0f)) return SR_E_INVALID;  // (a NaN fails both comparisons)
+        c->loss_eps = eps;
+    }
+    c->loss_kind = kind;
+    return SR_OK;
+}
+
+int sr_get_loss(sr_ctx* c, int* kind, float* eps) {
+    if (!c && sr_no_device()) return SR_E_NO_DEVICE;
+    sr_plan_clear(c);
+    if (!c || c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
+    if (kind) *kind = c->loss_kind;
+    if (eps) *eps = c->loss_eps;
+    return SR_OK;
 }
 
 int sr_adam_step_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr, float beta1,

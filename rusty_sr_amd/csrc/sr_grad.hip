@@ -7,6 +7,7 @@
 //   forward    z, a of f, l1, l2, l3; e (3f^2 expand channels)        grad_conv_kernel<FWD/LIN>, 5 launches (one per stage)
 //   loss       out = LinearInterp(input) + d2s(e); e' = out - hr      grad_loss_kernel: d_e = 2 s e' (x SrgbToLinear'(out)) and one f64
 //              (or of SrgbToLinear of both)                           partial of sum e'^2 per workgroup; sr_launch_loss_sum adds them in order
+//                                                                     (sr_set_loss: s sign(e') or s e' / sqrt(e'^2 + eps^2) in place of 2 s e')
 //   bias of e  sum of d_e over pixels                                 grad_colsum_kernel, per-chunk partials
 //   data grads d_a3 = conv10^T d_e; d_a2 = conv9^T d_e + conv8^T d_z3; grad_conv_kernel<BWD>, 4 launches, each summing all its
 //              d_a1 = conv7^T d_e + conv6^T d_z3 + conv5^T d_z2;       sources; epilogue: d_z = d_a (beta + z / sqrt(z^2 + 1)) and per-
@@ -269,10 +270,13 @@ __device__ __forceinline__ float srgb_to_linear_deriv(float s) {
 // network.rs:27,39; LinearInterp with half-pixel centres and clamped edges, the C oracle's linterp_f_acc), their error against the HR
 // crop, d_e = 2 s err (x SrgbToLinear'(out) in linear mode), zeros in the pad channels [E, ep).  One f64 partial of sum err^2 per workgroup.
 // hr: n images of hr_h x hr_w x CH (u8) or x 3 (f32); tab: 512 floats, byte / 255 then SrgbToLinear of those (sr_valid.cpp).
-template <int F, bool HR_U8, int CH, bool LINEAR>
+// LOSS (include/srhip.h sr_set_loss): what of err the seed multiplies -- SR_LOSS_MSE err itself (seed = 2 s), SR_LOSS_L1 its sign, 0 at
+// err == 0 (seed = s), SR_LOSS_CHARBONNIER err / sqrt(err^2 + eps2) (seed = s; IEEE square root and division, the same bits everywhere).
+// The partial is of sum err^2 under every kind; eps2 is read by the Charbonnier instances alone.
+template <int F, bool HR_U8, int CH, bool LINEAR, int LOSS>
 __global__ __launch_bounds__(256) void grad_loss_kernel(const float* __restrict__ x, const float* __restrict__ e, const void* __restrict__ hr,
                                                         const float* __restrict__ tab, int n, int H, int W, int hr_h, int hr_w, float seed,
-                                                        float* __restrict__ d_e, int ep, double* __restrict__ partial) {
+                                                        float* __restrict__ d_e, int ep, double* __restrict__ partial, float eps2) {
     constexpr int E = 3 * F * F;
     __shared__ double s_part[4];
     const long HW = (long)H * W, NP = (long)n * HW;
@@ -310,7 +314,13 @@ __global__ __launch_bounds__(256) void grad_loss_kernel(const float* __restrict_
                     }
                     const float d = (LINEAR ? srgb_to_linear_cr(out) : out) - hv;
                     acc += (double)d * (double)d;
-                    float gv = seed * d;
+                    float gv;
+                    if constexpr (LOSS == SR_LOSS_MSE) gv = seed * d;
+                    else if constexpr (LOSS == SR_LOSS_L1) gv = d > 0.f ? seed : d < 0.f ? -seed : 0.f * d;  // (a NaN stays one)
+                    else {
+                        const float r = __builtin_sqrtf(d * d + eps2);  // r == 0: err and eps^2 both below f32's range; the L1 limit
+                        gv = r > 0.f ? seed * (d / r) : 0.f * d;
+                    }
                     if (LINEAR) gv = gv * srgb_to_linear_deriv(out);
                     g[ch] = gv;
                 }
@@ -407,15 +417,25 @@ hipError_t launch_conv(const GradConvArgs& a, int grid, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int F>
+template <int F, int LOSS>
 hipError_t launch_loss(const sr_grad_plan& P, const Layout& L, float* ws, hipStream_t s) {
-    const float seed = 2.0f * P.loss_scale;
+    const float seed = LOSS == SR_LOSS_MSE ? 2.0f * P.loss_scale : P.loss_scale;  // rho'(err) = 2 err, or a factor of magnitude <= 1
     sr_dispatch_hr(P.hr_u8, P.hr_ch, P.linear, [&](auto u8, auto ch, auto lin) {
-        hipLaunchKernelGGL((grad_loss_kernel<F, decltype(u8)::value, decltype(ch)::value, decltype(lin)::value>), dim3((unsigned)L.loss_grid),
-                           dim3(256), 0, s, P.x, (const float*)(ws + L.o_e), P.hr, P.tab, P.n, P.H, P.W, P.hr_h, P.hr_w, seed, ws + L.o_de, L.EP,
-                           (double*)(ws + L.o_err));
+        hipLaunchKernelGGL((grad_loss_kernel<F, decltype(u8)::value, decltype(ch)::value, decltype(lin)::value, LOSS>),
+                           dim3((unsigned)L.loss_grid), dim3(256), 0, s, P.x, (const float*)(ws + L.o_e), P.hr, P.tab, P.n, P.H, P.W, P.hr_h,
+                           P.hr_w, seed, ws + L.o_de, L.EP, (double*)(ws + L.o_err), P.loss_eps * P.loss_eps);
     });
     return hipGetLastError();
+}
+
+template <int F>
+hipError_t launch_loss(const sr_grad_plan& P, const Layout& L, float* ws, hipStream_t s) {
+    switch (P.loss_kind) {
+        case SR_LOSS_MSE: return launch_loss<F, SR_LOSS_MSE>(P, L, ws, s);
+        case SR_LOSS_L1: return launch_loss<F, SR_LOSS_L1>(P, L, ws, s);
+        case SR_LOSS_CHARBONNIER: return launch_loss<F, SR_LOSS_CHARBONNIER>(P, L, ws, s);
+        default: return hipErrorInvalidValue;
+    }
 }
 
 #define SR_TRY(expr)                          \

@@ -119,6 +119,8 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     // ---- backpropagation (sr_grad.cpp): grown on demand, freed by sr_destroy
     sr_buf d_gws;                                   // saved forward state, gradients of the nodes, partials (sr_grad_workspace_bytes)
     sr_buf d_gin;                                   // host-pointer calls: params, HR batch, pooled LR batch, gradient
+    int loss_kind = SR_LOSS_MSE;                    // sr_set_loss: host-side state, read when a backward pass is queued (sr_grad_queue)
+    float loss_eps = 1e-3f;
     // ---- self-ensemble (sr_ensemble.cpp): grown on demand, freed by sr_destroy
     sr_buf d_ein;                                   // T_k of the caller's image, f32 RGB
     sr_buf d_eout;                                  // one member's f32 output map
@@ -417,6 +419,8 @@ struct sr_grad_plan {
     const float* tab = nullptr;     // the validation pass's 512-float table (sr_valid.cpp)
     bool linear = false;
     float loss_scale = 1.0f, l2 = 0.0f;
+    int loss_kind = SR_LOSS_MSE;    // the objective (include/srhip.h sr_set_loss), and Charbonnier's eps
+    float loss_eps = 1e-3f;
     float* ws = nullptr;            // sr_grad_workspace_bytes(factor, n, H, W), 256-byte aligned
     void* err_out = nullptr;        // sum of squared errors, one double at a 4-byte aligned address (nullptr: sr_grad_result_slot)
     float* grad = nullptr;          // the gradient, .rsr order

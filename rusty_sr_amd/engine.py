@@ -130,6 +130,26 @@ class Engine:
         _lib.check(self._L.sr_set_precision(self._ctx, self.PRECISIONS[precision]))
         self.precision = precision
 
+    LOSSES = {"mse": _lib.SR_LOSS_MSE, "l1": _lib.SR_LOSS_L1, "charbonnier": _lib.SR_LOSS_CHARBONNIER}
+
+    def set_loss(self, kind: str = "mse", eps: float = 1e-3):
+        """sr_set_loss: the objective of every backward pass queued on this engine from now on -- backprop*, backprop_pair* and every
+        step of a Trainer on it.  "mse" (the reference's sum of squares, the default), "l1", or "charbonnier" with 0 < eps <= 1
+        (sqrt(e^2 + eps^2) - eps; eps is read for that kind alone).  Steps already queued keep the objective they were queued under.
+        err_sum stays the sum of squares; validation, metrics and inference do not look at it.  A bad name or eps is a ValueError
+        before the library is called."""
+        if kind not in self.LOSSES:
+            raise ValueError(f"loss: expected one of {', '.join(sorted(self.LOSSES))}, got {kind!r}")
+        e = _check_loss_eps(eps) if kind == "charbonnier" else 0.0
+        _lib.check(self._L.sr_set_loss(self._ctx, self.LOSSES[kind], e))
+
+    @property
+    def loss(self):
+        """(kind, eps) as sr_get_loss reports them: eps is the last one set with "charbonnier" (1e-3 on a fresh engine)."""
+        kind, eps = C.c_int(), C.c_float()
+        _lib.check(self._L.sr_get_loss(self._ctx, C.byref(kind), C.byref(eps)))
+        return {v: k for k, v in self.LOSSES.items()}[kind.value], float(eps.value)
+
     def check_domain(self):
         """sr_check_domain: after the stream of earlier *_dev calls has been synchronised, raises SrError(SR_E_DOMAIN) if one of them
         left the domain of "split_f16" (a non-finite value, or one of 65504 and beyond); the host-pointer calls recompute in f32 themselves."""
@@ -1311,6 +1331,40 @@ def parse_degrade_spec(text: str) -> dict:
     return out
 
 
+LOSS_EPS_DEFAULT = 1e-3
+
+
+def _check_loss_eps(eps) -> float:
+    """Charbonnier's eps as the f32 the library takes: finite, 0 < eps <= 1 (ValueError otherwise)."""
+    try:
+        e = float(np.float32(eps))
+    except (TypeError, ValueError):
+        raise ValueError(f"loss: eps must be a number, got {eps!r}") from None
+    if not (0.0 < e <= 1.0):   # (a NaN fails both comparisons)
+        raise ValueError(f"loss: eps must be finite with 0 < eps <= 1, got {eps!r}")
+    return e
+
+
+def parse_loss_spec(text: str):
+    """'mse' | 'l1' | 'charbonnier[:EPS]' (the CLI's --loss) -> (kind, eps), the arguments of Engine.set_loss; eps is 1e-3 where the
+    spec has none.  Anything else -- an unknown kind, an EPS on a kind that has none, an EPS that is not a plain decimal in (0, 1] -- is a
+    ValueError that names --loss."""
+    import re
+    kind, colon, val = text.partition(":")
+    if kind not in Engine.LOSSES:
+        raise ValueError(f"--loss: unknown kind '{kind}' (mse, l1, charbonnier[:EPS])")
+    if not colon:
+        return kind, LOSS_EPS_DEFAULT
+    if kind != "charbonnier":
+        raise ValueError(f"--loss: '{kind}' takes no EPS")
+    if not re.fullmatch(r"\+?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?", val):
+        raise ValueError(f"--loss: malformed EPS '{val}'")
+    try:
+        return kind, _check_loss_eps(float(val))
+    except (ValueError, OverflowError):
+        raise ValueError(f"--loss: EPS '{val}' outside 0 < EPS <= 1") from None
+
+
 def degrade_draws(spec, seed: int, count: int, first: int = 0):
     """Draws first .. first + count - 1 of a spec (a string or parse_degrade_spec's dict) under `seed`, as keyword arguments of
     Engine.degrade.  The stream is SplitMix64 seeded with seed ^ 0xD6E8FEB86659FD93, four outputs a draw -- blur, noise, jpeg, noise seed;
@@ -1471,13 +1525,17 @@ class Trainer:
     """Minibatch Adam on the GPU (the optimisation loop of the reference's `train`, main.rs:181-257) over a training session of the
     engine's context (sr_train_*): parameters, moments and an image store live on the engine's device.
     step(hr_batch) -> err_sum of that batch at the parameters before the step (synchronous); add_image / step_crops queue steps on
-    random crops without waiting (sync() collects their err_sums)."""
+    random crops without waiting (sync() collects their err_sums).
+    loss / loss_eps: the objective (Engine.set_loss), set on the ENGINE when the trainer is made -- it is state of the engine, not of
+    the trainer: every backprop call and every trainer on that engine uses it until set_loss is called again."""
 
     def __init__(self, engine: Engine, start_params, linear_loss: bool = False, l2: float = 1e-6, lr: float = 2e-3,
-                 beta1: float = 0.95, beta2: float = 0.995, eps: float = 1e-7, store_bytes: Optional[int] = None):
+                 beta1: float = 0.95, beta2: float = 0.995, eps: float = 1e-7, store_bytes: Optional[int] = None,
+                 loss: str = "mse", loss_eps: float = LOSS_EPS_DEFAULT):
         p = np.ascontiguousarray(start_params, dtype=np.float32)
         if p.size != engine.num_params():
             raise ValueError(f"expected {engine.num_params()} parameters, got {p.size}")
+        engine.set_loss(loss, loss_eps)
         self.engine = engine
         self._L = engine._L
         self._t = C.c_void_p()

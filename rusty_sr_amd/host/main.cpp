@@ -2,7 +2,7 @@
 // (reference src/main.rs:33-258), driving the MI355X engine through libsrhip's C ABI.
 //
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
-//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] <PARAMETER_FILE> <TRAINING_FOLDER>
+//   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] [--loss LOSS] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] [--degrade SPEC [--seed N]] <VALIDATION_FOLDER>
 //   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709] [--slots N] [--timing] <IN|-> <OUT|->
 //
@@ -21,7 +21,8 @@
 // -- wrap makes a tileable texture come back seamless); for `train` --seed N (initial
 // parameters, shuffles and crops are seeded; the reference's are random), --augment (each crop under a random one of the 8 flips and
 // rotations, applied by the crop kernel), --degrade SPEC (train and validate: the network's input is the HR crop or image blurred, pooled,
-// noised and JPEG-compressed on the GPU, each draw with its own values: degrade_spec.hpp) and --steps N (stop
+// noised and JPEG-compressed on the GPU, each draw with its own values: degrade_spec.hpp), --loss mse|l1|charbonnier[:EPS] (the
+// objective of every step, sr_set_loss; the reference's is the squared one) and --steps N (stop
 // early; when that ends the run between two checkpoints the parameter file is also written at the last step -- the reference only
 // writes it after step 1 and every 100 steps).
 #include <cstdio>
@@ -399,6 +400,7 @@ int run_validate(int argc, char** argv) {
             has_shave = true;
         }
         else if (a == "--augment") validate_usage_error("The argument '--augment' can only be used with the 'train' subcommand");
+        else if (a == "--loss") validate_usage_error("The argument '--loss' can only be used with the 'train' subcommand");
         else if (a == "--degrade") {
             const std::string v = value("--degrade <SPEC>");
             std::string perr;
@@ -610,6 +612,9 @@ const char* kTrainUsage =
     "                                      noised and JPEG-compressed on the GPU, every draw with its own values from the ranges of\n"
     "                                      SPEC = blur=A[:B],noise=A[:B],jpeg=A[:B] (sigma 0..4 HR pixels, noise 0..64 levels, quality\n"
     "                                      1..100; a key left out is off).  With -v the validation images are degraded the same way\n"
+    "        --loss <LOSS>                 The training objective: mse (the reference's sum of squares), l1, or charbonnier[:EPS]\n"
+    "                                      (sqrt(e^2 + EPS^2) - EPS, 0 < EPS <= 1, EPS 0.001 without one); with -l it is taken of the\n"
+    "                                      linearised values.  The validation lines stay PSNR [default: mse]\n"
     "        --steps <N>                   Stop after N steps [default: 2500000, the reference's 10 000 000 evaluations]\n"
     "        --store <BYTES>               Device memory for resident training images; 0 decodes every draw again\n"
     "                                      [default: the device's free memory less max(8 GiB, 1/8 of it)]\n\n"
@@ -642,6 +647,35 @@ bool parse_count(const std::string& v, long& n) {
     return !v.empty() && r.ec == std::errc() && r.ptr == v.data() + v.size();
 }
 
+// --loss mse|l1|charbonnier[:EPS] -> the arguments of sr_set_loss.  EPS: a plain decimal ([+]digits[.digits][e[+-]digits], as
+// parse_loss_spec of the Python package takes it) that is, as an f32, above 0 and at most 1; 1e-3 where there is none.
+bool parse_loss(const std::string& v, int& kind, float& eps, std::string& err) {
+    const size_t colon = v.find(':');
+    const std::string name = v.substr(0, colon);
+    kind = name == "mse" ? SR_LOSS_MSE : name == "l1" ? SR_LOSS_L1 : name == "charbonnier" ? SR_LOSS_CHARBONNIER : -1;
+    eps = 1e-3f;
+    if (kind < 0) { err = "unknown kind '" + name + "'"; return false; }
+    if (colon == std::string::npos) return true;
+    if (kind != SR_LOSS_CHARBONNIER) { err = "'" + name + "' takes no EPS"; return false; }
+    const std::string t = v.substr(colon + 1);
+    size_t i = 0, digits = 0;
+    auto run = [&] { size_t n = 0; while (i < t.size() && isdigit((unsigned char)t[i])) { ++i; ++n; } return n; };
+    if (i < t.size() && t[i] == '+') ++i;
+    digits = run();
+    if (i < t.size() && t[i] == '.') { ++i; digits += run(); }
+    bool ok = digits > 0;
+    if (ok && i < t.size() && (t[i] == 'e' || t[i] == 'E')) {
+        ++i;
+        if (i < t.size() && (t[i] == '+' || t[i] == '-')) ++i;
+        ok = run() > 0;
+    }
+    if (!ok || i != t.size() || t.size() > 64) { err = "malformed EPS '" + t.substr(0, 64) + "'"; return false; }
+    const float e = (float)strtod(t.c_str(), nullptr);
+    if (!(e > 0.0f && e <= 1.0f)) { err = "EPS '" + t + "' outside 0 < EPS <= 1"; return false; }
+    eps = e;
+    return true;
+}
+
 bool write_rsr(const std::string& path, const std::vector<float>& p) {
     size_t len = 0;
     if (sr_rsr_encode(p.data(), p.size(), nullptr, 0, &len) != SR_OK) return false;
@@ -671,6 +705,8 @@ int run_train(int argc, char** argv) {
     bool has_s = false, has_v = false, linear = false, recurse = false, timing = false, has_lr = false, has_vlr = false, has_f = false;
     bool augment = false, has_deg = false;
     srdegrade::Spec deg_spec;
+    int loss_kind = SR_LOSS_MSE;
+    float loss_eps = 1e-3f;
     long factor_arg = SR_FACTOR;
     long val_max = -1, steps = 2500000, device = 0, store = -1;
     uint64_t seed = 0;
@@ -723,6 +759,12 @@ int run_train(int argc, char** argv) {
             std::string perr;
             if (!srdegrade::parse(v, deg_spec, perr)) train_usage_error("'" + v + "' isn't a valid value for '--degrade <SPEC>': " + perr);
             has_deg = true;
+        }
+        else if (a == "--loss") {
+            const std::string v = value("--loss <LOSS>");
+            std::string perr;
+            if (!parse_loss(v, loss_kind, loss_eps, perr))
+                train_usage_error("'" + v + "' isn't a valid value for '--loss <LOSS>': " + perr + "\n\t[values: mse, l1, charbonnier[:EPS] with 0 < EPS <= 1]");
         }
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             train_usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
@@ -789,6 +831,7 @@ int run_train(int argc, char** argv) {
     sr_ctx* ctx = nullptr;
     int rc = sr_create(&ctx, params.data(), params.size(), factor, (int)device);
     if (rc != SR_OK) die(sr_strerror(rc));  // SR_E_PARAM_COUNT carries the text of main.rs:162; SR_E_NO_DEVICE: no CPU fallback
+    if ((rc = sr_set_loss(ctx, loss_kind, loss_eps)) != SR_OK) die(sr_strerror(rc));  // --loss: every step's objective; the validation lines stay PSNR
     sr_train* tr = nullptr;
     rc = sr_train_create(&tr, ctx, params.data(), params.size(), linear ? 1 : 0, 1e-6f, 2e-3f, 0.95f, 0.995f, 1e-7f,
                          store < 0 ? SR_TRAIN_STORE_AUTO : (size_t)store);
@@ -1050,6 +1093,7 @@ int run_video(int argc, char** argv) {
             matrix = value("--matrix <MATRIX>");
             if (matrix != "bt601" && matrix != "bt709") video_usage_error("'" + matrix + "' isn't a valid value for '--matrix <MATRIX>'\n\t[values: bt601, bt709]");
         }
+        else if (a == "--loss") video_usage_error("The argument '--loss' can only be used with the 'train' subcommand");
         else if (a.size() > 1 && a[0] == '-') video_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
     }
@@ -1245,6 +1289,7 @@ int main(int argc, char** argv) {
                 usage_error("'" + depth_arg + "' isn't a valid value for '--depth <BITS>'\n\t[values: 16, 8, auto]");
         }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
+        else if (a == "--loss") usage_error("The argument '--loss' can only be used with the 'train' subcommand");
         else if (a == "--degrade") usage_error("The argument '--degrade' can only be used with the 'train' and 'validate' subcommands");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
