@@ -875,6 +875,84 @@ enum sr_loss { SR_LOSS_MSE = 0, SR_LOSS_L1 = 1, SR_LOSS_CHARBONNIER = 2 };
 int sr_set_loss(sr_ctx* ctx, int kind, float eps);
 int sr_get_loss(sr_ctx* ctx, int* kind, float* eps);
 
+/* ---- Optimiser: learning-rate schedules, gradient clipping, averaged parameters, exact resume ----
+ * What a long run needs beyond the reference's fixed Adam (main.rs:199-205).  UNPINNED: the reference has no counterpart; tests/optim_ref.py
+ * restates every rule in numpy and the tests hold the GPU to it bit for bit.  All of it is off by default: a session that never calls
+ * sr_train_set_optim / sr_train_set_lr queues the launches and computes the bits it did before these entry points existed.
+ *
+ * sr_grad_norm_dev: S = sum (double)g (double)g over the n floats of d_grad (4-byte aligned), each square exact in f64, in an order of
+ *   additions that depends on n alone: partial b = the workgroup sum (the butterfly v + v[i ^ off], off = 32 .. 1, over each 64 lanes,
+ *   then ((w0 + w1) + w2) + w3) of elements 256 b .. 256 b + 255 (0.0 past n); a lane t of one workgroup then adds partials t, t + 256,
+ *   ... in order and the same workgroup sum gives S.  No atomics: the same bits on every run and device.  From S, on the device:
+ *     sumsq = S;  norm = sqrt(S) in f64;  scale = clip > 0 && norm > clip ? (float)((double)clip / norm) : 1.0f;
+ *     skip  = S is not finite -- exactly when some element of d_grad is NaN or infinite (every square is >= 0).
+ *   d_out (8-byte aligned) receives the struct.  clip = 0: no clipping (scale 1.0f), sumsq and skip still computed.  Two launches on
+ *   `stream`, no host synchronisation; the partials live in ONE buffer of the context (grown when a call needs more, the earlier one
+ *   freed), so calls on one context are the caller's to order -- ACROSS STREAMS TOO: `stream` says where this call's launches go, it does
+ *   not give the call partials of its own.  Two calls on different streams of one context, neither ordered after the other's launches
+ *   (an event, a synchronisation), race on the partials and may free them under each other; use one stream, or order them, or a context
+ *   each.  Works in any graph's context.
+ * sr_adam_step_clipped_dev: sr_adam_step_dev's arithmetic, in its written order, on gc = scale g (one f32 product), scale and skip read
+ *   from d_norm in device memory (NULL: scale 1.0f, never skipped).  With scale == 1.0f the p, m, v written are sr_adam_step_dev's bits.
+ *   d_ema (NULL: off, and ema_decay must then be 0): e <- ema_decay e + (1.0f - ema_decay) p' in f32, p' the parameter just written,
+ *   1.0f - ema_decay formed once on the host.  A skipped step (skip != 0) writes nothing to p, m, v or e and adds 1 to *d_skipped
+ *   (8-byte aligned, may be NULL).  The caller's step count -- and with it the bias correction 1 - beta^step -- still advances over a
+ *   skipped step: the moments simply miss one update.  16 bytes a lane where all the pointers are 16-byte aligned, dwords otherwise;
+ *   the bits do not depend on which.  One launch on `stream`.
+ * sr_lr_at: the learning rate of step t = 1, 2, ..., host only, no device needed; everything in double, rounded once to f32:
+ *     warm = warmup ? min(1, t / warmup) : 1
+ *     SR_LR_CONSTANT  base
+ *     SR_LR_STEP      base gamma^floor((t - 1) / every)                                      every >= 1, 0 < gamma <= 1
+ *     SR_LR_COSINE    min_lr + (base - min_lr) 0.5 (1 + cos(pi min(t - 1, total) / total))   total >= 1, 0 <= min_lr <= base
+ *     *lr = (float)(warm * that value)
+ *   pow and cos are the host libm's: two hosts may differ in the last bit of the f32.  Fields a kind does not use are not read.
+ * The session:
+ *   sr_train_set_optim(t, clip_norm, ema_decay): clip_norm 0 (off) or finite and > 0; ema_decay 0 (off) or strictly inside (0, 1).  Waits
+ *     for the steps in flight.  The EMA slice is allocated when first enabled and initialised from the parameters as they are then;
+ *     turned off and on again it is initialised anew.  With either on, a step is the gather, the backward pass, sr_grad_norm_dev (only
+ *     with clip_norm > 0) and sr_adam_step_clipped_dev; with both off it is the step of sr_train_step, by the same launches.
+ *   sr_train_set_lr(t, lr): the rate of the steps queued afterwards (finite, >= 0); no synchronisation, steps in flight keep theirs.
+ *   sr_train_ema(t, out, cap): waits; the averaged parameters (cap >= n_params).  SR_E_INVALID while the EMA is off.
+ *   sr_train_get_state / sr_train_set_state: what a run needs besides the parameters to continue bit for bit: m, v, e (NULL / ignored
+ *     while the EMA is off; required while it is on), the step count (= steps queued so far) and the skipped count.  Both wait for the
+ *     steps in flight.  The parameters themselves travel through sr_train_params and sr_train_create.  set_state refuses n != n_params, a
+ *     negative step or skipped count, a null m or v, and a null e while the EMA is on (SR_E_INVALID), and then leaves the session as it was.
+ *   sr_train_sync_stats: sr_train_sync with {err_sum, grad_norm, lr, scale} per step; grad_norm = sqrt(sumsq) (NaN or inf on a skipped
+ *     step), 0 with scale 1 while clipping is off.  It shares sr_train_sync's queue: a step is reported by whichever is called first.
+ * Refused with SR_E_INVALID before any launch, outputs untouched: nulls (but where noted), misaligned pointers, n == 0, step < 1, a clip,
+ * decay, lr or schedule field out of range, d_ema without ema_decay or the reverse, a session whose context is gone.  A null context or
+ * session with no device present is SR_E_NO_DEVICE, as for sr_adam_step_dev (sr_lr_at: SR_E_INVALID, it needs none).  Cost: DESIGN.md 4t. */
+typedef struct {
+    double sumsq;   /* S */
+    float scale;    /* what the update multiplies the gradient by */
+    int32_t skip;   /* 1: S is not finite */
+} sr_grad_norm;
+typedef struct {
+    double err_sum, grad_norm;
+    float lr, scale;
+} sr_train_stat;
+enum sr_lr_kind { SR_LR_CONSTANT = 0, SR_LR_STEP = 1, SR_LR_COSINE = 2 };
+typedef struct {
+    int kind;            /* SR_LR_* */
+    float base;          /* finite, >= 0 */
+    long long warmup;    /* N steps of linear warm-up, 0: none */
+    long long every;     /* SR_LR_STEP */
+    double gamma;        /* SR_LR_STEP */
+    long long total;     /* SR_LR_COSINE */
+    float min_lr;        /* SR_LR_COSINE */
+} sr_lr_schedule;
+int sr_grad_norm_dev(sr_ctx* ctx, const float* d_grad, size_t n, float clip, sr_grad_norm* d_out, void* stream);
+int sr_adam_step_clipped_dev(sr_ctx* ctx, float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, int step, float lr,
+                             float beta1, float beta2, float eps, const sr_grad_norm* d_norm, float* d_ema, float ema_decay,
+                             unsigned long long* d_skipped, void* stream);
+int sr_lr_at(const sr_lr_schedule* schedule, long long step, float* lr);
+int sr_train_set_optim(sr_train* t, float clip_norm, float ema_decay);
+int sr_train_set_lr(sr_train* t, float lr);
+int sr_train_ema(sr_train* t, float* out, size_t cap);
+int sr_train_get_state(sr_train* t, float* m, float* v, float* e, size_t cap, long long* step, long long* skipped);
+int sr_train_set_state(sr_train* t, const float* m, const float* v, const float* e, size_t n, long long step, long long skipped);
+int sr_train_sync_stats(sr_train* t, sr_train_stat* stats, size_t cap, size_t* n_steps);
+
 /* Device time of the most recent call, measured with HIP events on the stream
  * the kernels ran on.  stage_ms[5] = conv0, l1, l2, l3, expand stage kernels
  * (enable with sr_set_profiling; off by default -- it inserts events, and the host-pointer

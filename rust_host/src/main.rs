@@ -107,6 +107,9 @@ fn parse_args() -> Options {
             "--metrics" | "--shave" => usage_error(&format!("The argument '{}' can only be used with the 'validate' subcommand", a)),
             // (`train` is not part of this host: its objective option, srhip::Engine::set_loss in the library, is refused by name)
             "--loss" => usage_error("The argument '--loss' can only be used with the 'train' subcommand"),
+            "--lr" | "--lr-schedule" | "--warmup" | "--clip" | "--ema" | "--resume" => {
+                usage_error(&format!("The argument '{}' can only be used with the 'train' subcommand", a))
+            }
             s if s.len() > 1 && s.starts_with('-') => {
                 usage_error(&format!("Found argument '{}' which wasn't expected, or isn't valid in this context", s))
             }
@@ -206,6 +209,9 @@ fn validate(args: Vec<String>) {
             }
             "-d" | "--downsample" => validate_usage_error("The argument '--downsample' cannot be used with 'validate'"),
             "--loss" => validate_usage_error("The argument '--loss' can only be used with the 'train' subcommand"),
+            "--lr" | "--lr-schedule" | "--warmup" | "--clip" | "--ema" | "--resume" => {
+                validate_usage_error(&format!("The argument '{}' can only be used with the 'train' subcommand", a))
+            }
             "-p" | "--parameters" => parameters = Some(value("--parameters <PARAMETERS>")),
             "-c" | "--custom" => custom = Some(value("--custom <PARAMETER_FILE>")),
             "-m" | "--val_max" => {

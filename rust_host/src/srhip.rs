@@ -77,6 +77,38 @@ pub struct SrDegrade {
     pub seed: u64,
 }
 
+/// `sr_grad_norm`: the gradient's sum of squares, the clipping scale and the skip flag, as the device writes them.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrGradNorm {
+    pub sumsq: f64,
+    pub scale: f32,
+    pub skip: i32,
+}
+
+/// `sr_train_stat`: one step's err_sum, gradient norm, learning rate and clipping scale.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrTrainStat {
+    pub err_sum: f64,
+    pub grad_norm: f64,
+    pub lr: f32,
+    pub scale: f32,
+}
+
+/// `sr_lr_schedule`: kind (0 constant, 1 step, 2 cosine), base rate, warm-up steps and the kind's own fields.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrLrSchedule {
+    pub kind: c_int,
+    pub base: f32,
+    pub warmup: i64,
+    pub every: i64,
+    pub gamma: f64,
+    pub total: i64,
+    pub min_lr: f32,
+}
+
 pub const SR_OK: c_int = 0;
 pub const SR_E_HIP: c_int = -5;
 pub const SR_GRAPH_SR_NET: c_int = 0;
@@ -240,6 +272,15 @@ extern "C" {
     pub fn sr_upscale_u16_sized(ctx: *mut SrCtx, input: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, out: *mut u16, out_channels: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
     pub fn sr_set_loss(ctx: *mut SrCtx, kind: c_int, eps: f32) -> c_int;
     pub fn sr_get_loss(ctx: *mut SrCtx, kind: *mut c_int, eps: *mut f32) -> c_int;
+    pub fn sr_grad_norm_dev(ctx: *mut SrCtx, d_grad: *const f32, n: usize, clip: f32, d_out: *mut SrGradNorm, stream: *mut c_void) -> c_int;
+    pub fn sr_adam_step_clipped_dev(ctx: *mut SrCtx, d_params: *mut f32, d_m: *mut f32, d_v: *mut f32, d_grad: *const f32, n: usize, step: c_int, lr: f32, beta1: f32, beta2: f32, eps: f32, d_norm: *const SrGradNorm, d_ema: *mut f32, ema_decay: f32, d_skipped: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn sr_lr_at(schedule: *const SrLrSchedule, step: i64, lr: *mut f32) -> c_int;
+    pub fn sr_train_set_optim(t: *mut SrTrain, clip_norm: f32, ema_decay: f32) -> c_int;
+    pub fn sr_train_set_lr(t: *mut SrTrain, lr: f32) -> c_int;
+    pub fn sr_train_ema(t: *mut SrTrain, out: *mut f32, cap: usize) -> c_int;
+    pub fn sr_train_get_state(t: *mut SrTrain, m: *mut f32, v: *mut f32, e: *mut f32, cap: usize, step: *mut i64, skipped: *mut i64) -> c_int;
+    pub fn sr_train_set_state(t: *mut SrTrain, m: *const f32, v: *const f32, e: *const f32, n: usize, step: i64, skipped: i64) -> c_int;
+    pub fn sr_train_sync_stats(t: *mut SrTrain, stats: *mut SrTrainStat, cap: usize, n_steps: *mut usize) -> c_int;
 }
 
 /// Text of an `sr_status`; for SR_E_PARAM_COUNT / SR_E_BYTEVEC it is the reference's own panic text.

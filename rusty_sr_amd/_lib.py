@@ -34,6 +34,7 @@ SR_YUV_LIMITED, SR_YUV_FULL = 0, 1
 SR_YUV_SPAN = 1024  # luma columns a workgroup of either conversion takes, two rows at a time (the tests put widths either side of it)
 SR_DEEP_SPAN = 2048  # pixels a workgroup of either deep-colour conversion takes, 8 a lane (the tests put counts either side of it)
 SR_LOSS_MSE, SR_LOSS_L1, SR_LOSS_CHARBONNIER = 0, 1, 2
+SR_LR_CONSTANT, SR_LR_STEP, SR_LR_COSINE = 0, 1, 2
 SR_METRICS_TILE = 32  # side of the metrics kernel's tile of region pixels (the tests put sizes either side of its multiples)
 
 
@@ -57,6 +58,22 @@ class Degrade(C.Structure):
 class Metrics(C.Structure):
     """sr_metrics (include/srhip.h): the sums and counts the Y-PSNR and the SSIM of one image are made of."""
     _fields_ = [("y_sq_err", C.c_uint64), ("y_count", C.c_uint64), ("ssim_sum", C.c_double), ("ssim_count", C.c_uint64)]
+
+
+class GradNorm(C.Structure):
+    """sr_grad_norm (include/srhip.h "Optimiser"): the gradient's sum of squares, the clipping scale and the skip flag."""
+    _fields_ = [("sumsq", C.c_double), ("scale", C.c_float), ("skip", C.c_int32)]
+
+
+class TrainStat(C.Structure):
+    """sr_train_stat (include/srhip.h "Optimiser"): one step's err_sum, gradient norm, learning rate and clipping scale."""
+    _fields_ = [("err_sum", C.c_double), ("grad_norm", C.c_double), ("lr", C.c_float), ("scale", C.c_float)]
+
+
+class LrSchedule(C.Structure):
+    """sr_lr_schedule (include/srhip.h "Optimiser"): kind, base rate, warm-up steps and the kind's own fields."""
+    _fields_ = [("kind", C.c_int), ("base", C.c_float), ("warmup", C.c_longlong), ("every", C.c_longlong), ("gamma", C.c_double),
+                ("total", C.c_longlong), ("min_lr", C.c_float)]
 
 
 class YuvFormat(C.Structure):
@@ -200,6 +217,15 @@ SYMBOLS = {
     "sr_upscale_u16_sized": (_i, [_vp, _u16p, _i, _i, _i, _i, _u16p, _i, _i, _i, _i, C.c_uint, C.c_uint]),
     "sr_set_loss": (_i, [_vp, _i, C.c_float]),
     "sr_get_loss": (_i, [_vp, C.POINTER(_i), _fp]),
+    "sr_grad_norm_dev": (_i, [_vp, _vp, _sz, C.c_float, _vp, _vp]),
+    "sr_adam_step_clipped_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, C.c_float, C.c_float, C.c_float, C.c_float, _vp, _vp, C.c_float, _vp, _vp]),
+    "sr_lr_at": (_i, [C.POINTER(LrSchedule), C.c_longlong, _fp]),
+    "sr_train_set_optim": (_i, [_vp, C.c_float, C.c_float]),
+    "sr_train_set_lr": (_i, [_vp, C.c_float]),
+    "sr_train_ema": (_i, [_vp, _fp, _sz]),
+    "sr_train_get_state": (_i, [_vp, _fp, _fp, _fp, _sz, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "sr_train_set_state": (_i, [_vp, _fp, _fp, _fp, _sz, C.c_longlong, C.c_longlong]),
+    "sr_train_sync_stats": (_i, [_vp, C.POINTER(TrainStat), _sz, C.POINTER(_sz)]),
 }
 
 # include/srhip_experimental.h: A/B tuning switches (no result bit depends on them), outside the drop-in ABI

@@ -456,6 +456,7 @@ void sr_destroy(sr_ctx* c) {
     sr_video_detach_all(c);
     sr_yuv_release(c);
     sr_deep_release(c);
+    sr_optim_release(c);
     sr_comm_release(c);
     sr_valid_release(c);
     sr_grad_release(c);

@@ -151,6 +151,8 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     sr_buf d_kin;                                   // the 16-bit images as the network's input, n x h x w x 3 f32
     sr_buf d_knet;                                  // the network's f32 output for them
     sr_buf d_kres;                                  // the _sized calls: that output resampled, before the conversion back
+    // ---- optimiser (sr_optim.cpp): grown on demand, freed by sr_destroy
+    sr_buf d_opart;                                 // the gradient norm's f64 partials, one per 256 elements
 };
 
 inline void sr_plan_clear(sr_ctx* c) {
@@ -600,3 +602,18 @@ const char* sr_deep_form(const void* d_in, const void* d_out);
 hipError_t sr_launch_u16_to_f32(const uint16_t* d_in, int in_channels, size_t npx, float* d_out, hipStream_t s);
 hipError_t sr_launch_f32_to_u16(const float* d_in, size_t npx, uint16_t* d_out, int out_channels, hipStream_t s);
 void sr_deep_release(sr_ctx* c);  // free the three buffers (called by sr_destroy)
+
+// ---- optimiser (sr_optim.hip kernels, sr_optim.cpp host side; include/srhip.h "Optimiser")
+size_t sr_optim_parts(size_t n);  // f64 partials of the norm of n floats: a function of n alone
+// S, scale and skip of n floats (4-byte aligned) -> d_out and, if not null, d_mirror (both 8-byte aligned); d_part: sr_optim_parts(n) doubles
+hipError_t sr_launch_grad_norm(const float* d_grad, size_t n, float clip, double* d_part, sr_grad_norm* d_out, sr_grad_norm* d_mirror, hipStream_t s);
+// Adam on scale g (d_norm null: scale 1, no skip), then e <- d e + omd p' (d_e null: none); 16 bytes a lane when all the pointers allow it
+hipError_t sr_launch_adam_clipped(float* d_p, float* d_m, float* d_v, const float* d_g, float* d_e, size_t n, float lr, float b1, float b2, float eps,
+                                  float bc1, float bc2, float d, float omd, const sr_grad_norm* d_norm, unsigned long long* d_skipped,
+                                  hipStream_t s);
+bool sr_clip_ok(float clip);       // 0, or finite and above 0
+bool sr_ema_decay_ok(float d);     // 0, or strictly inside (0, 1)
+bool sr_lr_ok(float lr);           // finite and at least 0
+// sr_grad_norm_dev after its argument checks, with the optional second copy of the result; the context's device is current
+int sr_grad_norm_queue(sr_ctx* c, const float* d_grad, size_t n, float clip, sr_grad_norm* d_out, sr_grad_norm* d_mirror, hipStream_t s);
+void sr_optim_release(sr_ctx* c);  // free the partials (called by sr_destroy)

@@ -1,6 +1,7 @@
 // sr_train.cpp -- the training session of include/srhip.h (sr_train_*) and the reference's parameter initialisation (sr_init_params): the
 // loop of the reference's `train` (main.rs:181-257) without its file handling, which the CLI does.  A step is the crop gather
-// (sr_train.hip), sr_backprop_rgba8_dev and sr_adam_step_dev, queued on the context's stream.
+// (sr_train.hip), sr_backprop_rgba8_dev and sr_adam_step_dev, queued on the context's stream.  With clipping or the
+// parameter average on (sr_train_set_optim) the last of them is sr_grad_norm_dev + sr_adam_step_clipped_dev (sr_optim.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,7 +42,16 @@ struct sr_train {
     double* d_err = nullptr;
     hipEvent_t ring_ev[SR_TRAIN_RING] = {nullptr};
     long long queued = 0, harvested = 0;  // steps issued (= Adam's step count) / whose err_sum has been read
-    std::vector<double> done;              // err_sums read since the last sync
+    std::vector<sr_train_stat> done;       // what has been read since the last sync
+    // the optimiser's additions (include/srhip.h "Optimiser"): off until sr_train_set_optim, and then the default step's launches stay as they are
+    float clip = 0, ema_decay = 0;         // 0: off
+    float* d_e = nullptr;                  // the averaged parameters: allocated when first enabled
+    sr_grad_norm* d_norm = nullptr;        // the current step's norm, scale and skip flag (in d_state's tail)
+    unsigned long long* d_skipped = nullptr;  // steps skipped for a gradient that was not finite (beside it)
+    sr_grad_norm* h_norm = nullptr;        // a ring of mapped host copies of d_norm beside the err ring, filled and freed the same way
+    sr_grad_norm* d_norm_ring = nullptr;
+    float lr_ring[SR_TRAIN_RING] = {0};    // the rate each step in flight was queued with
+    bool clip_ring[SR_TRAIN_RING] = {false};  // ... and whether it wrote its slot of the norm ring
     // the image store: one allocation per resident image, within the budget
     // (a pair is one entry: d_lr its LR image of h / f x w / f in the same allocation, nullptr for a plain image)
     struct Img { uint8_t* d; int ch, h, w; uint8_t* d_lr; int lr_ch; };
@@ -70,8 +80,16 @@ int grow(sr_ctx* c, hipStream_t s, sr_buf& b, size_t bytes) {
 int harvest_one(sr_train* t) {
     const int slot = (int)(t->harvested % SR_TRAIN_RING);
     HIPCHK(t->c, hipEventSynchronize(t->ring_ev[slot]));
-    const double v = ((volatile double*)t->h_err)[slot];
-    t->done.push_back(v);
+    sr_train_stat st;
+    st.err_sum = ((volatile double*)t->h_err)[slot];
+    st.grad_norm = 0.0;
+    st.lr = t->lr_ring[slot];
+    st.scale = 1.0f;
+    if (t->clip_ring[slot]) {
+        st.grad_norm = std::sqrt(((volatile sr_grad_norm*)t->h_norm)[slot].sumsq);
+        st.scale = ((volatile sr_grad_norm*)t->h_norm)[slot].scale;
+    }
+    t->done.push_back(st);
     ++t->harvested;
     return SR_OK;
 }
@@ -138,8 +156,18 @@ int finish_step(sr_train* t, int n, int crop_h, int crop_w, const sr_lr_input* l
                            t->d_g, s, nullptr, lr);
     if (rc != SR_OK) return rc;  // (SR_E_NOMEM: the context freed its backprop buffers; the parameters are untouched)
     t->last_n = n; t->last_h = crop_h; t->last_w = crop_w;
-    rc = sr_adam_step_dev(c, t->d_p, t->d_m, t->d_v, t->d_g, (size_t)t->np, (int)(t->queued + 1), t->lr, t->beta1, t->beta2, t->eps, s);
+    const bool clipped = t->clip > 0.0f, averaged = t->ema_decay > 0.0f;
+    if (!clipped && !averaged) {
+        rc = sr_adam_step_dev(c, t->d_p, t->d_m, t->d_v, t->d_g, (size_t)t->np, (int)(t->queued + 1), t->lr, t->beta1, t->beta2, t->eps, s);
+    } else {
+        if (clipped) rc = sr_grad_norm_queue(c, t->d_g, (size_t)t->np, t->clip, t->d_norm, t->d_norm_ring + slot, s);
+        if (rc == SR_OK)
+            rc = sr_adam_step_clipped_dev(c, t->d_p, t->d_m, t->d_v, t->d_g, (size_t)t->np, (int)(t->queued + 1), t->lr, t->beta1, t->beta2, t->eps,
+                                          clipped ? t->d_norm : nullptr, averaged ? t->d_e : nullptr, t->ema_decay, t->d_skipped, s);
+    }
     if (rc != SR_OK) return rc;
+    t->lr_ring[slot] = t->lr;
+    t->clip_ring[slot] = clipped;
     HIPCHK(c, hipEventRecord(t->ring_ev[slot], s));
     ++t->queued;
     return SR_OK;
@@ -150,6 +178,7 @@ void release(sr_train* t) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& im : t->images) (void)hipFree(im.d);
     if (t->d_state) (void)hipFree(t->d_state);
+    if (t->d_e) (void)hipFree(t->d_e);
     sr_free_buf(t->d_batch);
     sr_free_buf(t->d_trans);
     if (t->h_err) (void)hipHostFree(t->h_err);
@@ -215,15 +244,20 @@ int sr_train_create(sr_train** out, sr_ctx* c, const float* start_params, size_t
         int r = sr_ensure_streams(c, false);
         if (r != SR_OK) return r;
         const size_t slice = sr_round256((size_t)np * sizeof(float));
-        HIPCHK(c, hipMalloc((void**)&t->d_state, 4 * slice));
+        HIPCHK(c, hipMalloc((void**)&t->d_state, 4 * slice + 256));  // (the tail: the step's norm and the skipped count)
         t->d_p = t->d_state;
         t->d_m = (float*)((char*)t->d_state + slice);
         t->d_v = (float*)((char*)t->d_state + 2 * slice);
         t->d_g = (float*)((char*)t->d_state + 3 * slice);
         HIPCHK(c, hipMemcpy(t->d_p, start_params, (size_t)np * sizeof(float), hipMemcpyHostToDevice));
+        t->d_norm = (sr_grad_norm*)((char*)t->d_state + 4 * slice);
+        t->d_skipped = (unsigned long long*)((char*)t->d_state + 4 * slice + 64);
         HIPCHK(c, hipMemset(t->d_m, 0, 2 * slice));
-        HIPCHK(c, hipHostMalloc((void**)&t->h_err, SR_TRAIN_RING * sizeof(double), hipHostMallocMapped));
+        HIPCHK(c, hipMemset(t->d_norm, 0, 256));
+        HIPCHK(c, hipHostMalloc((void**)&t->h_err, SR_TRAIN_RING * (sizeof(double) + sizeof(sr_grad_norm)), hipHostMallocMapped));
         HIPCHK(c, hipHostGetDevicePointer((void**)&t->d_err, t->h_err, 0));
+        t->h_norm = (sr_grad_norm*)(t->h_err + SR_TRAIN_RING);
+        t->d_norm_ring = (sr_grad_norm*)(t->d_err + SR_TRAIN_RING);
         for (auto& e : t->ring_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         for (auto& e : t->stage_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         if (store_bytes == SR_TRAIN_STORE_AUTO) {
@@ -519,9 +553,97 @@ int sr_train_sync(sr_train* t, double* err_sums, size_t cap, size_t* n_steps) {
     HIPCHK(t->c, hipSetDevice(t->c->device));
     const int rc = drain(t);
     if (rc != SR_OK) return rc;
-    if (err_sums) std::copy_n(t->done.begin(), std::min(cap, t->done.size()), err_sums);
+    if (err_sums)
+        for (size_t i = 0; i < std::min(cap, t->done.size()); ++i) err_sums[i] = t->done[i].err_sum;
     if (n_steps) *n_steps = t->done.size();
     t->done.clear();
+    return SR_OK;
+}
+
+int sr_train_sync_stats(sr_train* t, sr_train_stat* stats, size_t cap, size_t* n_steps) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(t->c, hipSetDevice(t->c->device));
+    const int rc = drain(t);
+    if (rc != SR_OK) return rc;
+    if (stats) std::copy_n(t->done.begin(), std::min(cap, t->done.size()), stats);
+    if (n_steps) *n_steps = t->done.size();
+    t->done.clear();
+    return SR_OK;
+}
+
+int sr_train_set_optim(sr_train* t, float clip_norm, float ema_decay) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !sr_clip_ok(clip_norm) || !sr_ema_decay_ok(ema_decay)) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = drain(t);
+    if (rc != SR_OK) return rc;
+    if (ema_decay > 0.0f && !(t->ema_decay > 0.0f)) {  // enabled: the average starts at the parameters as they are now
+        if (!t->d_e) HIPCHK(c, hipMalloc((void**)&t->d_e, sr_round256((size_t)t->np * sizeof(float))));
+        HIPCHK(c, hipMemcpy(t->d_e, t->d_p, (size_t)t->np * sizeof(float), hipMemcpyDeviceToDevice));
+    }
+    t->clip = clip_norm;
+    t->ema_decay = ema_decay;
+    return SR_OK;
+}
+
+int sr_train_set_lr(sr_train* t, float lr) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !sr_lr_ok(lr)) return SR_E_INVALID;
+    t->lr = lr;  // (a step's rate is a kernel argument captured when it is queued)
+    return SR_OK;
+}
+
+int sr_train_ema(sr_train* t, float* out, size_t cap) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !out || cap < (size_t)t->np || !(t->ema_decay > 0.0f)) return SR_E_INVALID;
+    sr_device_guard restore_device;
+    HIPCHK(t->c, hipSetDevice(t->c->device));
+    HIPCHK(t->c, hipStreamSynchronize(t->c->stream));
+    HIPCHK(t->c, hipMemcpy(out, t->d_e, (size_t)t->np * sizeof(float), hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_train_get_state(sr_train* t, float* m, float* v, float* e, size_t cap, long long* step, long long* skipped) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !m || !v || !step || !skipped || cap < (size_t)t->np) return SR_E_INVALID;
+    const bool averaged = t->ema_decay > 0.0f;
+    if (averaged && !e) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)t->np * sizeof(float);
+    unsigned long long sk = 0;
+    HIPCHK(c, hipMemcpy(m, t->d_m, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(v, t->d_v, bytes, hipMemcpyDeviceToHost));
+    if (averaged) HIPCHK(c, hipMemcpy(e, t->d_e, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&sk, t->d_skipped, sizeof sk, hipMemcpyDeviceToHost));
+    *step = t->queued;
+    *skipped = (long long)sk;
+    return SR_OK;
+}
+
+int sr_train_set_state(sr_train* t, const float* m, const float* v, const float* e, size_t n, long long step, long long skipped) {
+    if (!t && sr_no_device()) return SR_E_NO_DEVICE;
+    if (!t || !t->c || !m || !v || n != (size_t)t->np || step < 0 || step >= INT32_MAX || skipped < 0) return SR_E_INVALID;
+    const bool averaged = t->ema_decay > 0.0f;
+    if (averaged && !e) return SR_E_INVALID;
+    sr_ctx* c = t->c;
+    sr_device_guard restore_device;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = drain(t);  // (their err_sums stay in the queue of sr_train_sync)
+    if (rc != SR_OK) return rc;
+    const size_t bytes = (size_t)t->np * sizeof(float);
+    const unsigned long long sk = (unsigned long long)skipped;
+    HIPCHK(c, hipMemcpy(t->d_m, m, bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(t->d_v, v, bytes, hipMemcpyHostToDevice));
+    if (averaged) HIPCHK(c, hipMemcpy(t->d_e, e, bytes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(t->d_skipped, &sk, sizeof sk, hipMemcpyHostToDevice));
+    t->queued = t->harvested = step;  // nothing is in flight: the ring's slots follow the count
     return SR_OK;
 }
 

@@ -1158,6 +1158,43 @@ class Engine:
                                             params.numel(), int(step), float(lr), float(beta1), float(beta2), float(eps),
                                             self._stream_ptr(stream, params.device)), self._ctx)
 
+    def grad_norm_dev(self, grad, clip: float = 0.0, out=None, stream=None):
+        """The f64 sum of squares of an f32 torch tensor on this engine's device, the clipping scale for `clip` (0: none) and the skip
+        flag, as a 16-byte uint8 tensor holding one sr_grad_norm (sr_grad_norm_dev; asynchronous on the stream).  read_grad_norm(out)
+        waits and decodes it."""
+        import torch
+        assert grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous()
+        if out is None:
+            out = torch.empty(16, dtype=torch.uint8, device=grad.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.numel() >= 16
+        vp = C.c_void_p
+        _lib.check(self._L.sr_grad_norm_dev(self._ctx, vp(grad.data_ptr()), grad.numel(), float(clip), vp(out.data_ptr()),
+                                            self._stream_ptr(stream, grad.device)), self._ctx)
+        return out
+
+    @staticmethod
+    def read_grad_norm(out) -> dict:
+        """{"sumsq", "scale", "skip"} of grad_norm_dev's result (waits for it)."""
+        g = _lib.GradNorm.from_buffer_copy(out.cpu().numpy().tobytes()[:16])
+        return {"sumsq": g.sumsq, "scale": float(np.float32(g.scale)), "skip": int(g.skip)}
+
+    def adam_step_clipped_dev(self, params, m, v, grad, step: int, lr: float = 2e-3, beta1: float = 0.95, beta2: float = 0.995,
+                              eps: float = 1e-7, norm=None, ema=None, ema_decay: float = 0.0, skipped=None, stream=None):
+        """adam_step_dev on scale * grad, scale and skip read on the device from `norm` (grad_norm_dev's result; None: scale 1), then
+        ema <- ema_decay ema + (1 - ema_decay) params where `ema` is given; a skipped step writes nothing and adds 1 to `skipped`, a
+        one-element int64 tensor (sr_adam_step_clipped_dev)."""
+        import torch
+        for t in (params, m, v, grad) + ((ema,) if ema is not None else ()):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == params.numel()
+        if skipped is not None:
+            assert skipped.is_cuda and skipped.dtype == torch.int64 and skipped.numel() >= 1
+        vp = C.c_void_p
+        ptr = lambda t: vp(t.data_ptr()) if t is not None else None
+        _lib.check(self._L.sr_adam_step_clipped_dev(self._ctx, vp(params.data_ptr()), vp(m.data_ptr()), vp(v.data_ptr()), vp(grad.data_ptr()),
+                                                    params.numel(), int(step), float(lr), float(beta1), float(beta2), float(eps), ptr(norm),
+                                                    ptr(ema), float(ema_decay), ptr(skipped), self._stream_ptr(stream, params.device)),
+                   self._ctx)
+
     # ---- introspection ------------------------------------------------------
     def read_feature(self, which: int, h: int, w: int) -> np.ndarray:
         """Post-activation node data of the last call: 0..3 = f, l1, l2, l3."""
@@ -1365,6 +1402,56 @@ def parse_loss_spec(text: str):
         raise ValueError(f"--loss: EPS '{val}' outside 0 < EPS <= 1") from None
 
 
+_LR_NUM = r"\+?(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?"
+
+
+def parse_lr_schedule(text: str, base: float = 2e-3, warmup: int = 0):
+    """'constant' | 'step:EVERY:GAMMA' | 'cosine:TOTAL[:MIN]' (the CLI's --lr-schedule) with the base rate (--lr) and the warm-up steps
+    (--warmup) -> the sr_lr_schedule that lr_at takes.  EVERY and TOTAL are whole numbers >= 1, 0 < GAMMA <= 1, 0 <= MIN <= base.  Anything
+    else is a ValueError that names the option."""
+    import math
+    import re
+    try:
+        b = float(np.float32(base))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"--lr: expected a number, got {base!r}") from None
+    if not math.isfinite(b) or b < 0:
+        raise ValueError(f"--lr: must be finite and at least 0, got {base!r}")
+    if isinstance(warmup, bool) or not isinstance(warmup, (int, np.integer)) or warmup < 0 or warmup >= 2 ** 62:
+        raise ValueError(f"--warmup: expected a whole number of steps >= 0, got {warmup!r}")
+    s = _lib.LrSchedule(_lib.SR_LR_CONSTANT, b, int(warmup), 0, 0.0, 0, 0.0)
+    parts = str(text).split(":")
+    whole = lambda v: re.fullmatch(r"\+?\d{1,18}", v) and int(v) >= 1
+    if parts == ["constant"]:
+        return s
+    if parts[0] == "step" and len(parts) == 3:
+        if not whole(parts[1]):
+            raise ValueError(f"--lr-schedule: EVERY must be a whole number >= 1, got '{parts[1]}'")
+        if not re.fullmatch(_LR_NUM, parts[2]) or not (0.0 < float(parts[2]) <= 1.0):
+            raise ValueError(f"--lr-schedule: GAMMA must be a number with 0 < GAMMA <= 1, got '{parts[2]}'")
+        s.kind, s.every, s.gamma = _lib.SR_LR_STEP, int(parts[1]), float(parts[2])
+        return s
+    if parts[0] == "cosine" and len(parts) in (2, 3):
+        if not whole(parts[1]):
+            raise ValueError(f"--lr-schedule: TOTAL must be a whole number >= 1, got '{parts[1]}'")
+        mn = 0.0
+        if len(parts) == 3:
+            if not re.fullmatch(_LR_NUM, parts[2]) or not (0.0 <= float(np.float32(float(parts[2]))) <= b):
+                raise ValueError(f"--lr-schedule: MIN must be a number with 0 <= MIN <= the base rate, got '{parts[2]}'")
+            mn = float(parts[2])
+        s.kind, s.total, s.min_lr = _lib.SR_LR_COSINE, int(parts[1]), mn
+        return s
+    raise ValueError(f"--lr-schedule: expected constant, step:EVERY:GAMMA or cosine:TOTAL[:MIN], got '{text}'")
+
+
+def lr_at(schedule, step: int) -> float:
+    """The learning rate of step 1, 2, ... under a schedule of parse_lr_schedule, as the f32 the session takes (sr_lr_at: the one
+    function the CLI uses too).  Host only."""
+    out = C.c_float()
+    _lib.check(_lib.lib().sr_lr_at(C.byref(schedule), int(step), C.byref(out)))
+    return float(out.value)
+
+
 def degrade_draws(spec, seed: int, count: int, first: int = 0):
     """Draws first .. first + count - 1 of a spec (a string or parse_degrade_spec's dict) under `seed`, as keyword arguments of
     Engine.degrade.  The stream is SplitMix64 seeded with seed ^ 0xD6E8FEB86659FD93, four outputs a draw -- blur, noise, jpeg, noise seed;
@@ -1527,11 +1614,14 @@ class Trainer:
     step(hr_batch) -> err_sum of that batch at the parameters before the step (synchronous); add_image / step_crops queue steps on
     random crops without waiting (sync() collects their err_sums).
     loss / loss_eps: the objective (Engine.set_loss), set on the ENGINE when the trainer is made -- it is state of the engine, not of
-    the trainer: every backprop call and every trainer on that engine uses it until set_loss is called again."""
+    the trainer: every backprop call and every trainer on that engine uses it until set_loss is called again.
+    clip_norm / ema_decay (set_optim), set_lr, ema(), state() / load_state(), sync_stats(): gradient clipping, an average of the
+    parameters, a rate per step and what a run needs to continue bit for bit (include/srhip.h "Optimiser"); all off by default, and
+    the default trainer's steps are then launch for launch what they were."""
 
     def __init__(self, engine: Engine, start_params, linear_loss: bool = False, l2: float = 1e-6, lr: float = 2e-3,
                  beta1: float = 0.95, beta2: float = 0.995, eps: float = 1e-7, store_bytes: Optional[int] = None,
-                 loss: str = "mse", loss_eps: float = LOSS_EPS_DEFAULT):
+                 loss: str = "mse", loss_eps: float = LOSS_EPS_DEFAULT, clip_norm: float = 0.0, ema_decay: float = 0.0):
         p = np.ascontiguousarray(start_params, dtype=np.float32)
         if p.size != engine.num_params():
             raise ValueError(f"expected {engine.num_params()} parameters, got {p.size}")
@@ -1546,6 +1636,62 @@ class Trainer:
         self.linear_loss, self.l2, self.lr, self.beta1, self.beta2, self.eps = linear_loss, l2, lr, beta1, beta2, eps
         self.steps = 0
         self._pending = 0
+        self.clip_norm, self.ema_decay = 0.0, 0.0
+        if clip_norm or ema_decay:
+            try:
+                self.set_optim(clip_norm, ema_decay)
+            except Exception:
+                self.close()
+                raise
+
+    def set_optim(self, clip_norm: float = 0.0, ema_decay: float = 0.0) -> None:
+        """Gradient clipping at an L2 norm of clip_norm (0: off) and an average of the parameters, e <- d e + (1 - d) p after every step
+        (0: off; first enabled, e starts at the current parameters).  Waits for the steps in flight (sr_train_set_optim)."""
+        _lib.check(self._L.sr_train_set_optim(self._t, float(clip_norm), float(ema_decay)), self.engine._ctx)
+        self.clip_norm, self.ema_decay = float(clip_norm), float(ema_decay)
+
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the steps queued from now on; no waiting (sr_train_set_lr)."""
+        _lib.check(self._L.sr_train_set_lr(self._t, float(lr)), self.engine._ctx)
+        self.lr = float(lr)
+
+    def ema(self) -> np.ndarray:
+        """The averaged parameters (waits); an SrError while the average is off."""
+        out = np.empty(self.engine.num_params(), dtype=np.float32)
+        _lib.check(self._L.sr_train_ema(self._t, out.ctypes.data_as(C.POINTER(C.c_float)), out.size), self.engine._ctx)
+        return out
+
+    def state(self) -> dict:
+        """What a run needs besides params() to continue bit for bit (waits): {"m", "v", "e" (None while the average is off), "step",
+        "skipped"} (sr_train_get_state)."""
+        n = self.engine.num_params()
+        fp = C.POINTER(C.c_float)
+        m, v = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.float32)
+        e = np.empty(n, dtype=np.float32) if self.ema_decay else None
+        step, skipped = C.c_longlong(), C.c_longlong()
+        _lib.check(self._L.sr_train_get_state(self._t, m.ctypes.data_as(fp), v.ctypes.data_as(fp), e.ctypes.data_as(fp) if e is not None else None,
+                                              n, C.byref(step), C.byref(skipped)), self.engine._ctx)
+        return {"m": m, "v": v, "e": e, "step": step.value, "skipped": skipped.value}
+
+    def load_state(self, state: dict) -> None:
+        """Continue from state() of a session with the same parameters and settings (sr_train_set_state); refused, the session stays as
+        it was."""
+        fp = C.POINTER(C.c_float)
+        m, v = (np.ascontiguousarray(state[k], dtype=np.float32).ravel() for k in ("m", "v"))
+        e = np.ascontiguousarray(state["e"], dtype=np.float32).ravel() if state.get("e") is not None else None
+        if m.size != v.size or (e is not None and e.size != m.size):
+            raise ValueError("m, v and e must have one size")
+        _lib.check(self._L.sr_train_set_state(self._t, m.ctypes.data_as(fp), v.ctypes.data_as(fp), e.ctypes.data_as(fp) if e is not None else None,
+                                              m.size, int(state["step"]), int(state.get("skipped", 0))), self.engine._ctx)
+        self.steps = int(state["step"])
+
+    def sync_stats(self) -> List[dict]:
+        """sync() with {"err_sum", "grad_norm", "lr", "scale"} per step (grad_norm 0 while clipping is off); it shares sync()'s queue."""
+        buf = (_lib.TrainStat * max(self._pending, 1))()
+        n = C.c_size_t()
+        _lib.check(self._L.sr_train_sync_stats(self._t, buf, len(buf), C.byref(n)), self.engine._ctx)
+        self._pending = 0
+        return [{"err_sum": b.err_sum, "grad_norm": b.grad_norm, "lr": float(b.lr), "scale": float(b.scale)} for b in buf[:min(n.value, len(buf))]]
 
     def add_image(self, px) -> int:
         """(h, w, 3|4) u8 -> the id of the image in the device store, or -1 when the store has no room."""

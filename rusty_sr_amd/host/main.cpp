@@ -46,6 +46,7 @@
 #include "../../include/srhip.h"
 #include "degrade_spec.hpp"
 #include "png.hpp"
+#include "train_state.hpp"
 #include "y4m.hpp"
 
 // The three parameter sets the reference embeds with include_bytes! (main.rs:26-28)
@@ -401,6 +402,7 @@ int run_validate(int argc, char** argv) {
         }
         else if (a == "--augment") validate_usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a == "--loss") validate_usage_error("The argument '--loss' can only be used with the 'train' subcommand");
+        else if (a == "--lr" || a == "--lr-schedule" || a == "--warmup" || a == "--clip" || a == "--ema" || a == "--resume") validate_usage_error("The argument '" + a + "' can only be used with the 'train' subcommand");
         else if (a == "--degrade") {
             const std::string v = value("--degrade <SPEC>");
             std::string perr;
@@ -616,6 +618,16 @@ const char* kTrainUsage =
     "                                      (sqrt(e^2 + EPS^2) - EPS, 0 < EPS <= 1, EPS 0.001 without one); with -l it is taken of the\n"
     "                                      linearised values.  The validation lines stay PSNR [default: mse]\n"
     "        --steps <N>                   Stop after N steps [default: 2500000, the reference's 10 000 000 evaluations]\n"
+    "        --lr <LR>                     The base learning rate [default: 0.002, the reference's]\n"
+    "        --lr-schedule <SCHEDULE>      constant, step:EVERY:GAMMA (LR x GAMMA every EVERY steps) or cosine:TOTAL[:MIN] (half a\n"
+    "                                      cosine from LR to MIN over TOTAL steps, MIN afterwards) [default: constant]\n"
+    "        --warmup <N>                  Scale the rate by min(1, step / N) [default: 0, none]\n"
+    "        --clip <NORM>                 Scale a gradient whose L2 norm exceeds NORM down to it; a step whose gradient is not\n"
+    "                                      finite is skipped [default: 0, off]\n"
+    "        --ema <DECAY>                 Keep an average of the parameters, e <- DECAY e + (1 - DECAY) p after every step, written to\n"
+    "                                      <PARAMETER_FILE stem>.ema.rsr and scored on a second validation line [default: 0, off]\n"
+    "        --resume                      Continue the run that wrote PARAMETER_FILE and PARAMETER_FILE.state, with the same options,\n"
+    "                                      up to --steps in all: the same bits as the run that was never interrupted\n"
     "        --store <BYTES>               Device memory for resident training images; 0 decodes every draw again\n"
     "                                      [default: the device's free memory less max(8 GiB, 1/8 of it)]\n\n"
     "ARGS:\n    <PARAMETER_FILE>     Learned network parameters will be (over)written to this parameter file (.rsr)\n"
@@ -647,17 +659,8 @@ bool parse_count(const std::string& v, long& n) {
     return !v.empty() && r.ec == std::errc() && r.ptr == v.data() + v.size();
 }
 
-// --loss mse|l1|charbonnier[:EPS] -> the arguments of sr_set_loss.  EPS: a plain decimal ([+]digits[.digits][e[+-]digits], as
-// parse_loss_spec of the Python package takes it) that is, as an f32, above 0 and at most 1; 1e-3 where there is none.
-bool parse_loss(const std::string& v, int& kind, float& eps, std::string& err) {
-    const size_t colon = v.find(':');
-    const std::string name = v.substr(0, colon);
-    kind = name == "mse" ? SR_LOSS_MSE : name == "l1" ? SR_LOSS_L1 : name == "charbonnier" ? SR_LOSS_CHARBONNIER : -1;
-    eps = 1e-3f;
-    if (kind < 0) { err = "unknown kind '" + name + "'"; return false; }
-    if (colon == std::string::npos) return true;
-    if (kind != SR_LOSS_CHARBONNIER) { err = "'" + name + "' takes no EPS"; return false; }
-    const std::string t = v.substr(colon + 1);
+// A plain decimal, [+]digits[.digits][e[+-]digits] of at most 64 characters, as a double
+bool parse_plain_decimal(const std::string& t, double& out) {
     size_t i = 0, digits = 0;
     auto run = [&] { size_t n = 0; while (i < t.size() && isdigit((unsigned char)t[i])) { ++i; ++n; } return n; };
     if (i < t.size() && t[i] == '+') ++i;
@@ -669,22 +672,86 @@ bool parse_loss(const std::string& v, int& kind, float& eps, std::string& err) {
         if (i < t.size() && (t[i] == '+' || t[i] == '-')) ++i;
         ok = run() > 0;
     }
-    if (!ok || i != t.size() || t.size() > 64) { err = "malformed EPS '" + t.substr(0, 64) + "'"; return false; }
-    const float e = (float)strtod(t.c_str(), nullptr);
+    if (!ok || i != t.size() || t.size() > 64) return false;
+    out = strtod(t.c_str(), nullptr);
+    return true;
+}
+
+// --loss mse|l1|charbonnier[:EPS] -> the arguments of sr_set_loss.  EPS: a plain decimal ([+]digits[.digits][e[+-]digits], as
+// parse_loss_spec of the Python package takes it) that is, as an f32, above 0 and at most 1; 1e-3 where there is none.
+bool parse_loss(const std::string& v, int& kind, float& eps, std::string& err) {
+    const size_t colon = v.find(':');
+    const std::string name = v.substr(0, colon);
+    kind = name == "mse" ? SR_LOSS_MSE : name == "l1" ? SR_LOSS_L1 : name == "charbonnier" ? SR_LOSS_CHARBONNIER : -1;
+    eps = 1e-3f;
+    if (kind < 0) { err = "unknown kind '" + name + "'"; return false; }
+    if (colon == std::string::npos) return true;
+    if (kind != SR_LOSS_CHARBONNIER) { err = "'" + name + "' takes no EPS"; return false; }
+    const std::string t = v.substr(colon + 1);
+    double d = 0;
+    if (!parse_plain_decimal(t, d)) { err = "malformed EPS '" + t.substr(0, 64) + "'"; return false; }
+    const float e = (float)d;
     if (!(e > 0.0f && e <= 1.0f)) { err = "EPS '" + t + "' outside 0 < EPS <= 1"; return false; }
     eps = e;
     return true;
 }
 
-bool write_rsr(const std::string& path, const std::vector<float>& p) {
+// --lr-schedule constant|step:EVERY:GAMMA|cosine:TOTAL[:MIN] -> the kind's fields of an sr_lr_schedule whose base and warmup are set
+// (parse_lr_schedule of the Python package takes the same texts); sr_lr_at is the judge of the ranges.
+bool parse_schedule(const std::string& v, sr_lr_schedule& s, std::string& err) {
+    std::vector<std::string> parts;
+    for (size_t a = 0;;) {
+        const size_t b = v.find(':', a);
+        parts.push_back(v.substr(a, b == std::string::npos ? b : b - a));
+        if (b == std::string::npos) break;
+        a = b + 1;
+    }
+    auto whole = [](const std::string& t, long long& n) {
+        long tmp = 0;
+        if (t.size() > 18 || !parse_count(t[0] == '+' ? t.substr(1) : t, tmp) || tmp < 1) return false;
+        n = tmp;
+        return true;
+    };
+    double d = 0;
+    if (parts.size() == 1 && parts[0] == "constant") s.kind = SR_LR_CONSTANT;
+    else if (parts[0] == "step" && parts.size() == 3) {
+        s.kind = SR_LR_STEP;
+        if (parts[1].empty() || !whole(parts[1], s.every)) { err = "EVERY must be a whole number >= 1"; return false; }
+        if (!parse_plain_decimal(parts[2], d) || !(d > 0.0 && d <= 1.0)) { err = "GAMMA must be a number with 0 < GAMMA <= 1"; return false; }
+        s.gamma = d;
+    } else if (parts[0] == "cosine" && (parts.size() == 2 || parts.size() == 3)) {
+        s.kind = SR_LR_COSINE;
+        if (parts[1].empty() || !whole(parts[1], s.total)) { err = "TOTAL must be a whole number >= 1"; return false; }
+        s.min_lr = 0.0f;
+        if (parts.size() == 3) {
+            if (!parse_plain_decimal(parts[2], d) || !((float)d >= 0.0f && (float)d <= s.base)) { err = "MIN must be a number with 0 <= MIN <= the base rate"; return false; }
+            s.min_lr = (float)d;
+        }
+    } else {
+        err = "expected constant, step:EVERY:GAMMA or cosine:TOTAL[:MIN]";
+        return false;
+    }
+    float probe = 0;
+    if (sr_lr_at(&s, 1, &probe) != SR_OK) { err = "a field is out of range"; return false; }
+    return true;
+}
+
+// OUT.rsr -> OUT.ema.rsr (a name without the extension: OUT.ema.rsr too)
+std::string ema_file_name(const std::string& param_file) {
+    const std::string ext = ".rsr";
+    const bool has = param_file.size() > ext.size() && param_file.compare(param_file.size() - ext.size(), ext.size(), ext) == 0;
+    return (has ? param_file.substr(0, param_file.size() - ext.size()) : param_file) + ".ema.rsr";
+}
+
+// A parameter file, through a temporary file renamed into place: a run ended while it writes leaves the earlier file whole.  *hash: the
+// checksum of the file's bytes, which the state file written beside it records (train_state.hpp).
+bool write_rsr(const std::string& path, const std::vector<float>& p, uint64_t* hash = nullptr) {
     size_t len = 0;
     if (sr_rsr_encode(p.data(), p.size(), nullptr, 0, &len) != SR_OK) return false;
     std::vector<uint8_t> blob(len);
     if (sr_rsr_encode(p.data(), p.size(), blob.data(), blob.size(), &len) != SR_OK) return false;
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = fwrite(blob.data(), 1, len, f) == len;
-    return fclose(f) == 0 && ok;
+    if (hash) *hash = srstate::checksum(blob.data(), len);
+    return srstate::write_bytes(path, blob.data(), len);
 }
 
 // RGB copy of a decoded RGBA image (the store keeps 3 bytes a pixel)
@@ -711,12 +778,18 @@ int run_train(int argc, char** argv) {
     long val_max = -1, steps = 2500000, device = 0, store = -1;
     uint64_t seed = 0;
     bool has_seed = false;
+    bool resume = false;
+    std::string schedule_arg = "constant", degrade_arg;
+    float lr_base = 2e-3f, clip = 0.0f, ema = 0.0f;
+    long warmup = 0;
     for (int k = 2; k < argc; ++k) {
         const std::string a = argv[k];
         auto value = [&](const char* name) -> std::string {
             if (k + 1 >= argc) train_usage_error(std::string("The argument '") + name + "' requires a value but none was supplied");
             return argv[++k];
         };
+        // --lr, --clip, --ema are f32 in the library: a nonzero value that rounds to 0 there would quietly mean "off", so it is refused
+        auto vanishes = [](double d) { return d != 0.0 && (float)d == 0.0f; };
         if (a == "-h" || a == "--help") { fputs(kTrainUsage, stdout); return 0; }
         else if (a == "-l" || a == "--linearLoss") linear = true;
         else if (a == "-r" || a == "--recurse") recurse = true;
@@ -759,6 +832,7 @@ int run_train(int argc, char** argv) {
             std::string perr;
             if (!srdegrade::parse(v, deg_spec, perr)) train_usage_error("'" + v + "' isn't a valid value for '--degrade <SPEC>': " + perr);
             has_deg = true;
+            degrade_arg = v;
         }
         else if (a == "--loss") {
             const std::string v = value("--loss <LOSS>");
@@ -766,6 +840,30 @@ int run_train(int argc, char** argv) {
             if (!parse_loss(v, loss_kind, loss_eps, perr))
                 train_usage_error("'" + v + "' isn't a valid value for '--loss <LOSS>': " + perr + "\n\t[values: mse, l1, charbonnier[:EPS] with 0 < EPS <= 1]");
         }
+        else if (a == "--lr") {
+            const std::string v = value("--lr <LR>");
+            double d = 0;
+            if (!parse_plain_decimal(v, d) || !std::isfinite((float)d) || vanishes(d)) train_usage_error("'" + v + "' isn't a valid value for '--lr <LR>': a finite number >= 0 (0 itself, or one that f32 can hold)");
+            lr_base = (float)d;
+        }
+        else if (a == "--lr-schedule") schedule_arg = value("--lr-schedule <SCHEDULE>");
+        else if (a == "--warmup") {
+            const std::string v = value("--warmup <N>");
+            if (!parse_count(v, warmup) || warmup < 0) train_usage_error("'" + v + "' isn't a valid value for '--warmup <N>': a whole number of steps >= 0");
+        }
+        else if (a == "--clip") {
+            const std::string v = value("--clip <NORM>");
+            double d = 0;
+            if (!parse_plain_decimal(v, d) || !std::isfinite((float)d) || vanishes(d)) train_usage_error("'" + v + "' isn't a valid value for '--clip <NORM>': 0 (off) or a finite number above 0 (one that f32 can hold: a value that rounds to 0 would turn clipping off)");
+            clip = (float)d;
+        }
+        else if (a == "--ema") {
+            const std::string v = value("--ema <DECAY>");
+            double d = 0;
+            if (!parse_plain_decimal(v, d) || !((float)d >= 0.0f && (float)d < 1.0f) || vanishes(d)) train_usage_error("'" + v + "' isn't a valid value for '--ema <DECAY>': 0 (off) or a number strictly between 0 and 1");
+            ema = (float)d;
+        }
+        else if (a == "--resume") resume = true;
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             train_usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
         else if (a.size() > 1 && a[0] == '-') train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
@@ -781,6 +879,29 @@ int run_train(int argc, char** argv) {
     if (has_deg && has_vlr)
         train_usage_error("The argument '--degrade <SPEC>' cannot be used with '--val_lr_folder <DIR>': the validation images are degraded the same way");
     if (pos.size() < 2) train_usage_error("The following required arguments were not provided:\n    <PARAMETER_FILE>\n    <TRAINING_FOLDER>");
+    sr_lr_schedule sched{};
+    sched.kind = SR_LR_CONSTANT; sched.base = lr_base; sched.warmup = warmup;
+    {
+        std::string perr;
+        if (!parse_schedule(schedule_arg, sched, perr))
+            train_usage_error("'" + schedule_arg + "' isn't a valid value for '--lr-schedule <SCHEDULE>': " + perr);
+    }
+    const bool scheduled = sched.kind != SR_LR_CONSTANT || warmup > 0;
+    if (resume && has_s) train_usage_error("The argument '--resume' cannot be used with '--start <START_PARAMETERS>': it continues from <PARAMETER_FILE>");
+    if (degrade_arg.size() >= srstate::kDegradeText) train_usage_error("the '--degrade <SPEC>' text is too long for the state file");
+    // --resume: the state file, before anything else is read (its seed is the run's when none is given)
+    const std::string state_file = pos[0] + ".state";
+    srstate::State resumed;
+    if (resume) {
+        std::string perr;
+        std::error_code ec;
+        if (!std::filesystem::is_regular_file(pos[0], ec)) train_usage_error("--resume: could not open the parameter file " + pos[0]);
+        if (!std::filesystem::is_regular_file(state_file, ec)) train_usage_error("--resume: could not open the state file " + state_file);
+        if (!srstate::read_file(state_file, resumed, perr)) train_usage_error("--resume: " + state_file + ": " + perr);
+        if (!has_seed) { seed = resumed.set.seed; has_seed = true; }
+        start = pos[0];
+        has_s = true;
+    }
     if (!has_seed) seed = ((uint64_t)std::random_device{}() << 32) ^ (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count();
     const std::string param_file = pos[0], train_folder = pos[1];
 
@@ -806,6 +927,7 @@ int run_train(int argc, char** argv) {
     // ---- parameters: the start file (its length selects the factor) or g.init_params() at the factor of -f (3 without it)
     std::vector<float> params;
     int factor = (int)factor_arg;
+    uint64_t start_hash = 0;  // --resume: of the parameter file's bytes, which the state file must name
     if (has_s) {
         FILE* f = fopen(start.c_str(), "rb");
         if (!f) die("Error opening start parameter file");  // main.rs:192
@@ -814,6 +936,7 @@ int run_train(int argc, char** argv) {
         size_t n;
         while ((n = fread(tmp, 1, sizeof tmp, f)) > 0) data.insert(data.end(), tmp, tmp + n);
         fclose(f);
+        start_hash = srstate::checksum(data.data(), data.size());
         params = decode_rsr(data.data(), data.size());
         int file_factor = SR_FACTOR;
         for (int fc : {3, 2, 4})
@@ -827,15 +950,41 @@ int run_train(int argc, char** argv) {
         if (sr_init_params(factor, seed, params.data(), params.size()) != SR_OK) die("could not initialise the parameters");
     }
 
+    srstate::Settings settings;
+    settings.factor = factor; settings.linear = linear; settings.augment = augment; settings.pairs = has_lr; settings.degrade = has_deg;
+    settings.seed = seed; settings.n_files = files.size(); settings.loss_kind = loss_kind; settings.loss_eps = loss_eps; settings.lr = lr_base;
+    settings.sched_kind = sched.kind; settings.warmup = warmup; settings.every = sched.kind == SR_LR_STEP ? sched.every : 0;
+    settings.gamma = sched.kind == SR_LR_STEP ? sched.gamma : 0.0; settings.total = sched.kind == SR_LR_COSINE ? sched.total : 0;
+    settings.min_lr = sched.kind == SR_LR_COSINE ? sched.min_lr : 0.0f; settings.clip = clip; settings.ema = ema; settings.degrade_spec = degrade_arg;
+    if (resume) {  // still before the device is touched
+        const std::string d = srstate::differing(resumed.set, settings);
+        if (!d.empty()) train_usage_error("--resume: the option '" + d + "' differs from the run that wrote " + state_file);
+        // the two files are written one after the other: a run ended between them, or a parameter file replaced since, leaves a pair that
+        // would train on from moments, counts and generators of another step
+        if (resumed.n_params != params.size() || resumed.params_hash != start_hash)
+            train_usage_error("--resume: the parameter file " + param_file + " is not the one written with the state file " + state_file +
+                              " (its checksum differs): the run was interrupted between the two, or the file was replaced");
+        if (resumed.step >= steps)
+            train_usage_error("--resume: '--steps " + std::to_string(steps) + "' is the total and must exceed the " + std::to_string(resumed.step) + " steps already taken");
+    }
+
     // ---- the device: a context (its inference path scores the validation images) and the training session on it
     sr_ctx* ctx = nullptr;
     int rc = sr_create(&ctx, params.data(), params.size(), factor, (int)device);
     if (rc != SR_OK) die(sr_strerror(rc));  // SR_E_PARAM_COUNT carries the text of main.rs:162; SR_E_NO_DEVICE: no CPU fallback
     if ((rc = sr_set_loss(ctx, loss_kind, loss_eps)) != SR_OK) die(sr_strerror(rc));  // --loss: every step's objective; the validation lines stay PSNR
     sr_train* tr = nullptr;
-    rc = sr_train_create(&tr, ctx, params.data(), params.size(), linear ? 1 : 0, 1e-6f, 2e-3f, 0.95f, 0.995f, 1e-7f,
+    rc = sr_train_create(&tr, ctx, params.data(), params.size(), linear ? 1 : 0, 1e-6f, lr_base, 0.95f, 0.995f, 1e-7f,
                          store < 0 ? SR_TRAIN_STORE_AUTO : (size_t)store);
     if (rc != SR_OK) die(sr_strerror(rc));
+    if (clip > 0.0f || ema > 0.0f) {  // (neither: the session stays the default one, launch for launch)
+        if ((rc = sr_train_set_optim(tr, clip, ema)) != SR_OK) die(std::string("--clip / --ema: ") + sr_strerror(rc));
+    }
+    if (resume) {
+        rc = sr_train_set_state(tr, resumed.m.data(), resumed.v.data(), ema > 0.0f ? resumed.e.data() : nullptr, resumed.m.size(), resumed.step,
+                                resumed.skipped);
+        if (rc != SR_OK) die(std::string("--resume: ") + sr_strerror(rc));
+    }
     using clk = std::chrono::steady_clock;
     const clk::time_point t_load = clk::now();
 
@@ -888,7 +1037,7 @@ int run_train(int argc, char** argv) {
         }
     }
     const size_t val_n = has_v ? std::min(vimg.size(), val_max > 0 ? (size_t)val_max : vimg.size()) : 0;
-    size_t val_next = 0;
+    size_t val_next = resume && !vimg.empty() ? (size_t)(resumed.val_next % vimg.size()) : 0;
 
     // ---- the draws: a fresh shuffle of the usable files each epoch, one crop of each drawn image
     // (pairs: one crop of 192 / f LR pixels per draw, its origin in LR pixels, uniform over the positions inside the LR image)
@@ -898,12 +1047,37 @@ int run_train(int argc, char** argv) {
     Rng aug_rng{seed ^ 0x6175676d656e7421ull};  // --augment: the members, a stream of their own
     std::vector<size_t> perm;
     size_t perm_pos = 0;
-    struct Draw { size_t file; int y0, x0; uint8_t member; sr_degrade deg; };
+    // The generators as they are BEFORE a draw: what the state file records for the first draw the GPU has not consumed, so that a resumed
+    // run makes that draw again.  The epoch's shuffle is not stored: epoch_rng is the crop stream before it, and the shuffle is made anew.
+    struct Snap { uint64_t rng, aug_rng, epoch_rng, perm_pos, deg_drawn; bool epoch_valid; };
+    struct Draw { size_t file; int y0, x0; uint8_t member; sr_degrade deg; Snap snap; };
     uint64_t deg_drawn = 0;  // --degrade: the draws of its own stream (degrade_spec.hpp), one per crop, in draw order
+    uint64_t epoch_rng = 0;
+    bool epoch_valid = false;
+    auto shuffle = [&]() {
+        epoch_rng = rng.s;
+        epoch_valid = true;
+        perm = usable;
+        for (size_t i = perm.size(); i > 1; --i) std::swap(perm[i - 1], perm[rng.below(i)]);
+    };
+    auto snap_now = [&]() -> Snap { return {rng.s, aug_rng.s, epoch_rng, (uint64_t)perm_pos, deg_drawn, epoch_valid}; };
+    if (resume) {
+        if (resumed.epoch_valid) {
+            rng.s = resumed.epoch_rng;
+            shuffle();
+        }
+        // The one refusal of --resume that needs the images decoded, so it comes after the device is up and ends with status 1: the state
+        // file counts the files listed (n_files, checked above), and a file that decoded then and no longer does shortens the shuffle.
+        if (resumed.perm_pos > perm.size()) die("--resume: the training folder does not hold the images of the run that wrote " + state_file);
+        perm_pos = (size_t)resumed.perm_pos;
+        rng.s = resumed.rng;
+        aug_rng.s = resumed.aug_rng;
+        deg_drawn = resumed.deg_drawn;
+    }
     auto draw = [&]() -> Draw {
+        const Snap before = snap_now();
         if (perm_pos == perm.size()) {
-            perm = usable;
-            for (size_t i = perm.size(); i > 1; --i) std::swap(perm[i - 1], perm[rng.below(i)]);
+            shuffle();
             perm_pos = 0;
         }
         const size_t fi = perm[perm_pos++];
@@ -918,13 +1092,14 @@ int run_train(int argc, char** argv) {
             const srdegrade::Draw g = srdegrade::draw(deg_spec, seed, deg_drawn++);
             deg = {g.sigma, g.noise, g.quality, g.seed};
         }
-        return {fi, y0, x0, augment ? (uint8_t)(aug_rng.next() >> 61) : (uint8_t)0, deg};
+        return {fi, y0, x0, augment ? (uint8_t)(aug_rng.next() >> 61) : (uint8_t)0, deg, before};
     };
     // draws are made a window of steps ahead, so that transient images decode while the GPU works
     DecoderPool pool(files, 16 * kBatch), lr_pool(lr_files, 16 * kBatch);
     std::deque<std::pair<Draw, long>> ahead;  // (draw, decoder job or -1; a transient pair's LR file has the same job number in lr_pool)
     const long lookahead = 8 * kBatch;
-    long drawn = 0;
+    const long first_step = resume ? (long)resumed.step + 1 : 1;
+    long drawn = (first_step - 1) * kBatch;
     auto fill = [&]() {
         while ((long)ahead.size() < lookahead && drawn < steps * kBatch) {
             const Draw d = draw();
@@ -935,13 +1110,9 @@ int run_train(int argc, char** argv) {
         }
     };
 
-    auto checkpoint = [&](bool validate) {
-        std::vector<float> p(params.size());
-        int r = sr_train_params(tr, p.data(), p.size());
-        if (r != SR_OK) die(sr_strerror(r));
-        if (!write_rsr(param_file, p)) fprintf(stderr, "Could not make parameter file\n");
-        if (!validate || !has_v) return;
-        r = sr_set_params(ctx, p.data(), p.size());
+    // The PSNR line of parameters p over the next val_n validation images from the cursor on
+    auto score = [&](const std::vector<float>& p, const char* label) {
+        int r = sr_set_params(ctx, p.data(), p.size());
         if (r != SR_OK) die(sr_strerror(r));
         double err_sum = 0, n_sum = 0;
         for (size_t k = 0; k < val_n; ++k) {
@@ -964,8 +1135,61 @@ int run_train(int argc, char** argv) {
             n_sum += (double)ne;
         }
         const float psnr = err_sum == 0.0 ? INFINITY : (float)(-10.0 * std::log10(err_sum / n_sum));
-        printf("Validation PSNR:\t%s\n", rust_f32(psnr).c_str());  // main.rs:246
+        printf("Validation PSNR%s:\t%s\n", label, rust_f32(psnr).c_str());  // main.rs:246
         fflush(stdout);
+    };
+    // The parameter file, with --ema the averaged one beside it, the state file (the generators at the first draw the GPU has not
+    // consumed, the cursor after the pass), and then the validation lines (the averaged parameters are scored on the same images as the raw ones).
+    const std::string ema_file = ema_file_name(param_file);
+    auto checkpoint = [&](bool validate) {
+        srstate::State st;
+        st.set = settings;
+        st.n_params = params.size();
+        st.m.resize(params.size());
+        st.v.resize(params.size());
+        if (ema > 0.0f) st.e.resize(params.size());
+        long long at = 0, skipped = 0;
+        std::vector<float> p(params.size());
+        int r = sr_train_params(tr, p.data(), p.size());
+        if (r == SR_OK) r = sr_train_get_state(tr, st.m.data(), st.v.data(), ema > 0.0f ? st.e.data() : nullptr, st.m.size(), &at, &skipped);
+        if (r != SR_OK) die(sr_strerror(r));
+        const Snap sn = ahead.empty() ? snap_now() : ahead.front().first.snap;
+        st.step = at; st.skipped = skipped;
+        st.rng = sn.rng; st.aug_rng = sn.aug_rng; st.epoch_rng = sn.epoch_rng; st.perm_pos = sn.perm_pos; st.deg_drawn = sn.deg_drawn;
+        st.epoch_valid = sn.epoch_valid;
+        const bool scoring = validate && has_v;
+        st.val_next = scoring ? (val_next + val_n) % vimg.size() : val_next;  // where the pass below leaves the cursor
+        // The files one right after the other, each through a temporary file and a rename, and the validation pass only then: the time in
+        // which a run that is ended leaves a parameter file without its state is that of two renames, and --resume tells such a pair by
+        // the checksum.  (A parameter file that could not be written leaves the state file as it was: the earlier pair stays whole.)
+        const bool wrote = write_rsr(param_file, p, &st.params_hash);
+        if (!wrote) fprintf(stderr, "Could not make parameter file\n");
+        if (ema > 0.0f && !write_rsr(ema_file, st.e)) fprintf(stderr, "Could not make parameter file\n");
+        std::string werr;
+        if (wrote && !srstate::write_file(state_file, st, werr)) fprintf(stderr, "Could not make state file (%s)\n", werr.c_str());
+        if (scoring) {
+            const size_t cursor = val_next;
+            score(p, "");
+            if (ema > 0.0f) {
+                val_next = cursor;
+                score(st.e, " (EMA)");
+            }
+        }
+    };
+    // the steps' statistics: --timing reports the share of clipped and of skipped steps, and the norms seen
+    long clipped_steps = 0, skipped_steps = 0;
+    std::vector<double> norms;
+    std::vector<sr_train_stat> stat_buf(1000 + SR_TRAIN_RING);
+    auto collect = [&]() {
+        size_t n = 0;
+        const int r = sr_train_sync_stats(tr, stat_buf.data(), stat_buf.size(), &n);
+        if (r != SR_OK) die(sr_strerror(r));
+        if (!(clip > 0.0f)) return;
+        for (size_t i = 0; i < std::min(n, stat_buf.size()); ++i) {
+            if (!std::isfinite(stat_buf[i].grad_norm)) { ++skipped_steps; continue; }
+            if (stat_buf[i].scale < 1.0f) ++clipped_steps;
+            if (timing) norms.push_back(stat_buf[i].grad_norm);
+        }
     };
 
     printf("Beginning Training\n");
@@ -974,7 +1198,7 @@ int run_train(int argc, char** argv) {
     long resident_draws = 0;
     double wait_ms = 0;
     std::vector<std::vector<uint8_t>> held(kBatch), held_lr(kBatch);  // transient pixels of the step being queued
-    for (long step = 1; step <= steps; ++step) {
+    for (long step = first_step; step <= steps; ++step) {
         fill();
         sr_train_crop items[kBatch];
         sr_train_pair_crop pairs[kBatch];
@@ -1010,25 +1234,32 @@ int run_train(int argc, char** argv) {
             pairs[i].lr_px = held_lr[i].data();
             pairs[i].lr_channels = pairs[i].hr_channels = 4; pairs[i].lh = lr.h; pairs[i].lw = lr.w;
         }
+        if (scheduled) {  // (a constant rate without warm-up stays the one the session was created with)
+            float lr = 0;
+            if ((rc = sr_lr_at(&sched, step, &lr)) != SR_OK || (rc = sr_train_set_lr(tr, lr)) != SR_OK) die(std::string("--lr-schedule: ") + sr_strerror(rc));
+        }
         if (has_deg) rc = sr_train_step_degrade(tr, items, augment ? members : nullptr, degs, kBatch, kCrop, kCrop);
         else if (augment) rc = has_lr ? sr_train_step_pairs_aug(tr, pairs, members, kBatch, kCrop, kCrop) : sr_train_step_aug(tr, items, members, kBatch, kCrop, kCrop);
         else rc = has_lr ? sr_train_step_pairs(tr, pairs, kBatch, kCrop, kCrop) : sr_train_step(tr, items, kBatch, kCrop, kCrop);
         if (rc != SR_OK) die(std::string("training step: ") + sr_strerror(rc));
-        if (step % 1000 == 0) {  // keep the err_sum list of the session short (the values are not reported)
-            rc = sr_train_sync(tr, nullptr, 0, nullptr);
-            if (rc != SR_OK) die(sr_strerror(rc));
-        }
+        if (step % 1000 == 0) collect();  // keeps the session's list of finished steps short
         if (step == 1 || step % 100 == 0) checkpoint(true);
         else if (step == steps) checkpoint(false);  // --steps ended the run between two checkpoints: the file holds the last step
     }
-    rc = sr_train_sync(tr, nullptr, 0, nullptr);
-    if (rc != SR_OK) die(sr_strerror(rc));
+    collect();
+    const long steps_run = steps - first_step + 1;
     if (timing) {
         const double s = std::chrono::duration<double>(clk::now() - t0).count();
         fprintf(stderr, "[timing] %ld steps in %.3f s: %.1f steps/s (checkpoints and validation included); resident draws %.1f %%; "
                         "decode: %.1f ms up front (%zu images, %d resident), %.1f ms waited for transient images\n",
-                steps, s, steps / s, 100.0 * resident_draws / ((double)steps * kBatch), decode_ms, nfile,
+                steps_run, s, steps_run / s, 100.0 * resident_draws / ((double)steps_run * kBatch), decode_ms, nfile,
                 (int)std::count_if(timg.begin(), timg.end(), [](const TrainImage& t) { return t.id >= 0; }), wait_ms);
+        if (clip > 0.0f) {
+            std::sort(norms.begin(), norms.end());
+            fprintf(stderr, "[timing] clipped steps %.1f %%, skipped steps %.1f %%; gradient norm min %.9g, median %.9g, max %.9g\n",
+                    100.0 * clipped_steps / (double)steps_run, 100.0 * skipped_steps / (double)steps_run, norms.empty() ? 0.0 : norms.front(),
+                    norms.empty() ? 0.0 : norms[norms.size() / 2], norms.empty() ? 0.0 : norms.back());
+        }
     }
     pool.stop();
     lr_pool.stop();
@@ -1094,6 +1325,7 @@ int run_video(int argc, char** argv) {
             if (matrix != "bt601" && matrix != "bt709") video_usage_error("'" + matrix + "' isn't a valid value for '--matrix <MATRIX>'\n\t[values: bt601, bt709]");
         }
         else if (a == "--loss") video_usage_error("The argument '--loss' can only be used with the 'train' subcommand");
+        else if (a == "--lr" || a == "--lr-schedule" || a == "--warmup" || a == "--clip" || a == "--ema" || a == "--resume") video_usage_error("The argument '" + a + "' can only be used with the 'train' subcommand");
         else if (a.size() > 1 && a[0] == '-') video_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
     }
@@ -1290,6 +1522,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--augment") usage_error("The argument '--augment' can only be used with the 'train' subcommand");
         else if (a == "--loss") usage_error("The argument '--loss' can only be used with the 'train' subcommand");
+        else if (a == "--lr" || a == "--lr-schedule" || a == "--warmup" || a == "--clip" || a == "--ema" || a == "--resume") usage_error("The argument '" + a + "' can only be used with the 'train' subcommand");
         else if (a == "--degrade") usage_error("The argument '--degrade' can only be used with the 'train' and 'validate' subcommands");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
