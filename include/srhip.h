@@ -804,6 +804,40 @@ int sr_video_receive(sr_video* v, const uint8_t** out_frame);
 int sr_video_pending(const sr_video* v);
 void sr_video_destroy(sr_video* v);
 
+/* ---- Deep video: planar YCbCr frames of 9..16-bit samples, 4:2:0, 4:2:2 and 4:4:4 ----
+ * What `ffmpeg -f yuv4mpegpipe` writes for HEVC, AV1 and ProRes sources (C420p10, C422p10, ...): the Video calls above on frames whose
+ * samples are little-endian uint16, with a format struct of their own -- sr_yuv_format and its validation are unchanged, and the two
+ * enum values added here are valid in sr_yuv16_format only.  A frame is Y (h x w), then Cb, then Cr, each ch x cw samples: SR_YUV_420
+ * ceil(h / 2) x ceil(w / 2), SR_YUV_422 h x ceil(w / 2), SR_YUV_444 h x w; contiguous, so a plane may start at any even byte.
+ * UNPINNED: tests/yuv16_ref.py states the rule in numpy (f64) and the kernels equal it bit for bit.  It is the 8-bit rule at depth d:
+ *   a code is the uint16 as stored, whatever d says -- nothing is masked; the clamp of RGB to [0, 1] defines every input.
+ *   Constants, each formed once by a single f64 operation, s = 2^(d - 8).  SR_YUV_LIMITED: oy = 16 s, ky = 219 s, kc = 224 s, mid = 128 s,
+ *             limits Y [16 s, 235 s], C [16 s, 240 s].  SR_YUV_FULL: oy = 0, ky = kc = 2^d - 1, mid = 2^(d - 1), limits [0, 2^d - 1].
+ *             sy = 1 / ky, sc = 1 / kc; the matrix constants as above, with SR_YUV_BT2020 (non-constant luminance) Kr 0.2627, Kb 0.0593.
+ *   To RGB    y = (Y - oy) sy, c = (C - mid) sc, then as above.  4:2:0 chroma: the same exact integer sum over 16, times 0.0625.
+ *             4:2:2 chroma: the horizontal taps alone -- an exact integer sum over 4, times 0.25 -- and no vertical tap.
+ *   From RGB  as above with Y' = oy + ky y, C' = mid + kc c.  4:2:2 subsampling, at the unrounded level: CENTER (p0 + p1) 0.5; LEFT
+ *             ((a + 2 b) + c) 0.25 at columns 2j - 1, 2j, 2j + 1, indices clamped.  Then floor(v + 0.5) clamped to the limits: one uint16.
+ *   In limited range the rule on code 2^(d - 8) gives the 8-bit rule's f32 RGB bit for bit: the scale is a power of two.
+ * sr_yuv16_frame_bytes: the BYTES of one frame (two a sample); 0 for an invalid format or a shape below 1.  Host only.
+ * sr_yuv16_to_rgb_dev / sr_rgb_to_yuv16_dev / sr_upscale_yuv16_dev / sr_upscale_yuv16: as their 8-bit namesakes.  The composed call is
+ *   bit-identical to its three device calls chained, the network in between being exactly sr_upscale_f32_dev's or
+ *   sr_upscale_ensemble_f32_dev's path.
+ * sr_video_create16: a frame stream (above) on deep frames; acquire / submit / receive / pending / destroy are the same calls, the
+ *   buffers are bytes (sr_yuv16_frame_bytes of them), and every rule of the 8-bit session holds, the recomputation in exact f32 included.
+ * Refused with SR_E_INVALID before any launch, the output untouched: what the 8-bit calls refuse, a depth outside 9..16, a frame pointer
+ * that is not 2-byte aligned.  A shape that cannot fit is SR_E_NOMEM. */
+enum { SR_YUV_422 = 2 };    /* a subsampling; valid in sr_yuv16_format only */
+enum { SR_YUV_BT2020 = 2 }; /* a matrix; valid in sr_yuv16_format only */
+typedef struct sr_yuv16_format { int32_t subsampling, siting, matrix, range, depth; } sr_yuv16_format;
+size_t sr_yuv16_frame_bytes(const sr_yuv16_format* fmt, int h, int w);
+int sr_yuv16_to_rgb_dev(sr_ctx* ctx, const uint16_t* d_yuv, const sr_yuv16_format* fmt, int n, int h, int w, float* d_rgb, void* stream);
+int sr_rgb_to_yuv16_dev(sr_ctx* ctx, const float* d_rgb, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_yuv, void* stream);
+int sr_upscale_yuv16_dev(sr_ctx* ctx, const uint16_t* d_in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_out,
+                         unsigned members, void* stream);
+int sr_upscale_yuv16(sr_ctx* ctx, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, unsigned members);
+int sr_video_create16(sr_ctx* ctx, const sr_yuv16_format* fmt, int h, int w, int slots, unsigned members, sr_video** out);
+
 /* ---- Deep colour: 16-bit images in and out ----
  * The reference's images are 8 bits wide (main.rs:164-175), and so is every other integer path here; a 16-bit scan, photograph, height
  * or displacement map would come back with 256 levels a channel.  These calls take and give interleaved 16-bit samples -- native-endian

@@ -67,6 +67,18 @@ pub struct SrYuvFormat {
     pub range: i32,
 }
 
+/// `sr_yuv16_format`: a deep frame, samples in little-endian u16.  subsampling (0: 4:2:0, 1: 4:4:4, 2: 4:2:2), siting, matrix (0: BT.601,
+/// 1: BT.709, 2: BT.2020 non-constant luminance), range as `sr_yuv_format`; depth 9..=16 bits a sample.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrYuv16Format {
+    pub subsampling: i32,
+    pub siting: i32,
+    pub matrix: i32,
+    pub range: i32,
+    pub depth: i32,
+}
+
 /// `sr_degrade`: one item's blur width (HR pixels), noise level (8-bit levels), JPEG quality (0: none) and noise seed.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -262,6 +274,12 @@ extern "C" {
     pub fn sr_video_receive(v: *mut SrVideo, out_frame: *mut *const u8) -> c_int;
     pub fn sr_video_pending(v: *const SrVideo) -> c_int;
     pub fn sr_video_destroy(v: *mut SrVideo);
+    pub fn sr_yuv16_frame_bytes(fmt: *const SrYuv16Format, h: c_int, w: c_int) -> usize;
+    pub fn sr_yuv16_to_rgb_dev(ctx: *mut SrCtx, d_yuv: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, d_rgb: *mut f32, stream: *mut c_void) -> c_int;
+    pub fn sr_rgb_to_yuv16_dev(ctx: *mut SrCtx, d_rgb: *const f32, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, d_yuv: *mut u16, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_yuv16_dev(ctx: *mut SrCtx, d_in: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, d_out: *mut u16, members: c_uint, stream: *mut c_void) -> c_int;
+    pub fn sr_upscale_yuv16(ctx: *mut SrCtx, input: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, out: *mut u16, members: c_uint) -> c_int;
+    pub fn sr_video_create16(ctx: *mut SrCtx, fmt: *const SrYuv16Format, h: c_int, w: c_int, slots: c_int, members: c_uint, out: *mut *mut SrVideo) -> c_int;
     pub fn sr_u16_to_f32_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut f32, stream: *mut c_void) -> c_int;
     pub fn sr_f32_to_u16_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_u16_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, members: c_uint, stream: *mut c_void) -> c_int;

@@ -28,6 +28,7 @@ SR_DEGRADE_MAX_SIGMA, SR_DEGRADE_MAX_NOISE = 4, 64
 SR_BORDER_WRAP, SR_BORDER_REPLICATE, SR_BORDER_MIRROR = 1, 2, 3
 SR_BORDER_PAD_DEFAULT, SR_BORDER_PAD_MAX = 8, 32
 SR_YUV_420, SR_YUV_444 = 0, 1
+SR_YUV_422, SR_YUV_BT2020 = 2, 2  # valid in sr_yuv16_format (Yuv16Format) only
 SR_YUV_SITING_CENTER, SR_YUV_SITING_LEFT = 0, 1
 SR_YUV_BT601, SR_YUV_BT709 = 0, 1
 SR_YUV_LIMITED, SR_YUV_FULL = 0, 1
@@ -88,6 +89,20 @@ class YuvFormat(C.Structure):
     @classmethod
     def named(cls, subsampling="420", siting="center", matrix="bt601", range="limited"):
         return cls(cls.SUBSAMPLINGS[subsampling], cls.SITINGS[siting], cls.MATRICES[matrix], cls.RANGES[range])
+
+
+class Yuv16Format(C.Structure):
+    """sr_yuv16_format (include/srhip.h "Deep video"): a planar YCbCr frame of 9..16-bit samples in little-endian uint16.  The fields take
+    the SR_YUV_* numbers and the depth; Yuv16Format.named("422", "left", "bt2020", "limited", 10) takes the names."""
+    _fields_ = [("subsampling", C.c_int32), ("siting", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("depth", C.c_int32)]
+    SUBSAMPLINGS = {"420": SR_YUV_420, "422": SR_YUV_422, "444": SR_YUV_444}
+    SITINGS = YuvFormat.SITINGS
+    MATRICES = {"bt601": SR_YUV_BT601, "bt709": SR_YUV_BT709, "bt2020": SR_YUV_BT2020}
+    RANGES = YuvFormat.RANGES
+
+    @classmethod
+    def named(cls, subsampling="420", siting="left", matrix="bt709", range="limited", depth=10):
+        return cls(cls.SUBSAMPLINGS[subsampling], cls.SITINGS[siting], cls.MATRICES[matrix], cls.RANGES[range], int(depth))
 
 
 # every symbol include/srhip.h declares: (restype, argtypes)
@@ -207,6 +222,12 @@ SYMBOLS = {
     "sr_video_receive": (_i, [_vp, C.POINTER(_vp)]),
     "sr_video_pending": (_i, [_vp]),
     "sr_video_destroy": (None, [_vp]),
+    "sr_yuv16_frame_bytes": (_sz, [C.POINTER(Yuv16Format), _i, _i]),
+    "sr_yuv16_to_rgb_dev": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _vp, _vp]),
+    "sr_rgb_to_yuv16_dev": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _vp, _vp]),
+    "sr_upscale_yuv16_dev": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _vp, C.c_uint, _vp]),
+    "sr_upscale_yuv16": (_i, [_vp, _u16p, C.POINTER(Yuv16Format), _i, _i, _i, _u16p, C.c_uint]),
+    "sr_video_create16": (_i, [_vp, C.POINTER(Yuv16Format), _i, _i, _i, C.c_uint, C.POINTER(_vp)]),
     "sr_u16_to_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_f32_to_u16_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "sr_upscale_u16_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_uint, _vp]),

@@ -164,8 +164,8 @@ inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     else c->plan_rec.emplace_back(line, 1);
 }
 
-// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
-// px: the pixels the kernel is instantiated on (resize_h, yuv2rgb, rgb2yuv: its input's, resize_v: its output's); bx / by: workgroups along a row and along
+// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16|yuv16_to_rgb|rgb_to_yuv16> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
+// px: the pixels the kernel is instantiated on (resize_h, yuv2rgb, rgb2yuv: its input's, resize_v: its output's; the deep-colour and deep video conversions: their f32 side); bx / by: workgroups along a row and along
 // the rows of one image (resize_h: of the batch's n h rows; the deep-colour conversions: 1, the batch is one run of pixels), from the
 // *_blocks function the launcher itself calls.
 inline void sr_plan_note_op(sr_ctx* c, const char* name, bool f32, int n, unsigned bx, unsigned by, const char* form = nullptr, int f = 0) {
@@ -591,6 +591,30 @@ hipError_t sr_launch_yuv_to_rgb(const uint8_t* d_yuv, const sr_yuv_rule& k, int 
 hipError_t sr_launch_rgb_to_yuv(const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s);
 void sr_yuv_release(sr_ctx* c);        // free the two buffers (called by sr_destroy)
 void sr_video_detach_all(sr_ctx* c);   // called by sr_destroy; a detached stream refuses every call but sr_video_destroy
+
+// ---- deep video (sr_yuv16.hip kernels, sr_yuv.cpp host side; include/srhip.h "Deep video")
+// A deep format as the kernels take it: the constants of tests/yuv16_ref.py, the depth folded into them, each formed once on the host
+// in f64 by a single operation (the kernels divide nowhere).
+struct sr_yuv16_rule {
+    int sub, left;                  // SR_YUV_420 | SR_YUV_444 | SR_YUV_422; chroma horizontally co-sited with the even columns (else centred)
+    double kr, kb, kg;              // the matrix; kg = 1 - kr - kb
+    double cr2, cb2, ir, ib, ig;    // 2 (1 - kr), 2 (1 - kb) and their reciprocals, 1 / kg
+    double oy, mid, sy, sc;         // YCbCr -> RGB: y = (Y - oy) sy, c = (C - mid) sc
+    double ky, kc;                  // RGB -> YCbCr: Y' = oy + ky y, C' = mid + kc c
+    double ylo, yhi, clo, chi;      // the range's limits
+};
+bool sr_yuv16_rule_make(const sr_yuv16_format* f, sr_yuv16_rule* out);  // false: a null format, an enum outside its values, a depth outside 9..16
+inline size_t sr_yuv16_rule_frame_samples(const sr_yuv16_rule& k, int h, int w) {
+    const size_t ch = k.sub == SR_YUV_420 ? ((size_t)h + 1) / 2 : (size_t)h, cw = k.sub == SR_YUV_444 ? (size_t)w : ((size_t)w + 1) / 2;
+    return (size_t)h * w + 2 * ch * cw;
+}
+// workgroups of either launch for n frames of h x w luma samples (0: an empty shape), functions of the shape alone; the launchers refuse
+// more than INT32_MAX
+size_t sr_yuv16_to_rgb_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+size_t sr_rgb_to_yuv16_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+// n frames at d_yuv (2-byte aligned) -> n x h x w x 3 f32 at d_rgb (4-byte aligned), and back
+hipError_t sr_launch_yuv16_to_rgb(const uint16_t* d_yuv, const sr_yuv16_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s);
+hipError_t sr_launch_rgb_to_yuv16(const float* d_rgb, const sr_yuv16_rule& k, int n, int h, int w, uint16_t* d_yuv, hipStream_t s);
 
 // ---- deep colour (sr_deep.hip kernels, sr_deep.cpp host side; include/srhip.h "Deep colour")
 // workgroups of either launch for npx pixels (0: none): a function of the pixel count alone; the launchers refuse more than INT32_MAX

@@ -2,7 +2,8 @@
 //     YCbCr frame -> f32 RGB -> network (sr_net_queue: the plain or the ensemble call's path) -> f32 RGB -> YCbCr frame, quantised once,
 // and the frame stream, which keeps that call in flight for a ring of slots.  Kernels: sr_yuv.hip.  The composed calls are their checks,
 // their sizes and a work lambda; the stream is the one thing here the scaffold has no form for: a call that returns
-// before its work is done.
+// before its work is done.  The deep video path (include/srhip.h "Deep video"; kernels: sr_yuv16.hip) is the
+// same three things on frames of uint16 samples with a format struct of its own; a session of either kind is one sr_video.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,7 +63,89 @@ int queue_upscale(sr_ctx* c, const uint8_t* d_in, const sr_yuv_rule& k, int n, i
     return queue_to_yuv(c, (const float*)c->d_ynet.p, k, n, (int)f * h, (int)f * w, d_out, s);
 }
 
+// ---- the deep forms of the above: frames of uint16 samples, sr_yuv16_rule
+const char* form_name(const sr_yuv16_rule& k) {
+    if (k.sub == SR_YUV_444) return "444";
+    if (k.sub == SR_YUV_422) return k.left ? "422left" : "422center";
+    return k.left ? "420left" : "420center";
+}
+
+bool sample_aligned(const void* p) { return ((uintptr_t)p & 1u) == 0; }
+
+int queue_to_rgb(sr_ctx* c, const uint16_t* d_yuv, const sr_yuv16_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    if (sr_yuv16_to_rgb_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_yuv16_to_rgb(d_yuv, k, n, h, w, d_rgb, s));
+    sr_plan_note_op(c, "yuv16_to_rgb", true, n, bx, by, form_name(k));
+    return SR_OK;
+}
+
+int queue_to_yuv(sr_ctx* c, const float* d_rgb, const sr_yuv16_rule& k, int n, int h, int w, uint16_t* d_yuv, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    if (sr_rgb_to_yuv16_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_rgb_to_yuv16(d_rgb, k, n, h, w, d_yuv, s));
+    sr_plan_note_op(c, "rgb_to_yuv16", true, n, bx, by, form_name(k));
+    return SR_OK;
+}
+
+int check_upscale_shape(const sr_ctx* c, const sr_yuv16_format* fmt, int n, int h, int w, unsigned members, sr_yuv16_rule* k) {
+    SRCHK(sr_net_check_shape(c, n, h, w, members));
+    if (!sr_yuv16_rule_make(fmt, k)) return SR_E_INVALID;
+    if (h > kSideMax / c->factor || w > kSideMax / c->factor) return SR_E_INVALID;
+    return SR_OK;
+}
+
+int check_upscale_args(const sr_ctx* c, const void* in, const sr_yuv16_format* fmt, int n, int h, int w, const void* out, unsigned members,
+                       sr_yuv16_rule* k) {
+    if (!in || !out || !sample_aligned(in) || !sample_aligned(out)) return SR_E_INVALID;
+    return check_upscale_shape(c, fmt, n, h, w, members, k);
+}
+
+// the same workspace as the 8-bit call's: both hold f32 RGB
+int queue_upscale(sr_ctx* c, const uint16_t* d_in, const sr_yuv16_rule& k, int n, int h, int w, uint16_t* d_out, unsigned members, hipStream_t s) {
+    const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;
+    if (out_img / kPxF / (f * w) != f * h || out_img > SIZE_MAX / (size_t)n) return SR_E_NOMEM;
+    SRCHK(sr_reserve_bufs(c, {{&c->d_yrgb, (size_t)n * in_img}, {&c->d_ynet, (size_t)n * out_img}}));
+    SRCHK(queue_to_rgb(c, d_in, k, n, h, w, (float*)c->d_yrgb.p, s));
+    SRCHK(sr_net_queue(c, c->d_yrgb.p, false, 3, n, h, w, c->d_ynet.p, false, members, s));
+    return queue_to_yuv(c, (const float*)c->d_ynet.p, k, n, (int)f * h, (int)f * w, d_out, s);
+}
+
 }  // namespace
+
+bool sr_yuv16_rule_make(const sr_yuv16_format* f, sr_yuv16_rule* out) {
+    if (!f) return false;
+    if (f->subsampling != SR_YUV_420 && f->subsampling != SR_YUV_444 && f->subsampling != SR_YUV_422) return false;
+    if (f->siting != SR_YUV_SITING_CENTER && f->siting != SR_YUV_SITING_LEFT) return false;
+    if (f->matrix != SR_YUV_BT601 && f->matrix != SR_YUV_BT709 && f->matrix != SR_YUV_BT2020) return false;
+    if (f->range != SR_YUV_LIMITED && f->range != SR_YUV_FULL) return false;
+    if (f->depth < 9 || f->depth > 16) return false;
+    sr_yuv16_rule k{};
+    const bool full = f->range == SR_YUV_FULL;
+    k.sub = f->subsampling;
+    k.left = k.sub != SR_YUV_444 && f->siting == SR_YUV_SITING_LEFT;
+    k.kr = f->matrix == SR_YUV_BT2020 ? 0.2627 : f->matrix == SR_YUV_BT709 ? 0.2126 : 0.299;
+    k.kb = f->matrix == SR_YUV_BT2020 ? 0.0593 : f->matrix == SR_YUV_BT709 ? 0.0722 : 0.114;
+    k.kg = 1.0 - k.kr - k.kb;
+    k.cr2 = 2.0 * (1.0 - k.kr);
+    k.cb2 = 2.0 * (1.0 - k.kb);
+    k.ir = 1.0 / k.cr2;
+    k.ib = 1.0 / k.cb2;
+    k.ig = 1.0 / k.kg;
+    const double s = (double)(1 << (f->depth - 8)), top = (double)(1 << f->depth) - 1.0;  // powers of two: exact
+    k.oy = full ? 0.0 : 16.0 * s;
+    k.ky = full ? top : 219.0 * s;
+    k.kc = full ? top : 224.0 * s;
+    k.mid = full ? (double)(1 << (f->depth - 1)) : 128.0 * s;
+    k.sy = 1.0 / k.ky;
+    k.sc = 1.0 / k.kc;
+    k.ylo = full ? 0.0 : 16.0 * s;
+    k.yhi = full ? top : 235.0 * s;
+    k.clo = full ? 0.0 : 16.0 * s;
+    k.chi = full ? top : 240.0 * s;
+    *out = k;
+    return true;
+}
 
 bool sr_yuv_rule_make(const sr_yuv_format* f, sr_yuv_rule* out) {
     if (!f) return false;
@@ -105,6 +188,8 @@ struct sr_video {
     sr_ctx* c = nullptr;  // nullptr: detached by sr_destroy
     bool failed = false;  // a recomputation in exact f32 could not be queued: what is in flight is lost, every call but destroy is refused
     sr_yuv_rule k{};
+    bool deep = false;    // made by sr_video_create16: the frames are uint16 samples and the format is k16
+    sr_yuv16_rule k16{};
     int h = 0, w = 0, slots = 0;
     unsigned members = 1;
     size_t in_bytes = 0, out_bytes = 0;
@@ -152,7 +237,8 @@ int video_queue(sr_video* v, unsigned long long frame) {
     HIPCHK(c, hipMemcpyAsync(s.d_in, s.h_in, v->in_bytes, hipMemcpyHostToDevice, c->copy_in));
     HIPCHK(c, hipEventRecord(s.up, c->copy_in));
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.up, 0));
-    SRCHK(queue_upscale(c, (const uint8_t*)s.d_in, v->k, 1, v->h, v->w, (uint8_t*)s.d_out, v->members, c->stream));
+    if (v->deep) SRCHK(queue_upscale(c, (const uint16_t*)s.d_in, v->k16, 1, v->h, v->w, (uint16_t*)s.d_out, v->members, c->stream));
+    else SRCHK(queue_upscale(c, (const uint8_t*)s.d_in, v->k, 1, v->h, v->w, (uint8_t*)s.d_out, v->members, c->stream));
     HIPCHK(c, hipEventRecord(s.done, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->copy_out, s.done, 0));
     HIPCHK(c, hipMemcpyAsync(s.h_out, s.d_out, v->out_bytes, hipMemcpyDeviceToHost, c->copy_out));
@@ -172,6 +258,24 @@ int video_create(sr_video* v) {
         for (hipEvent_t* e : {&s.up, &s.done, &s.down}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     for (int i = 0; i <= v->slots; ++i) HIPCHK(c, hipHostMalloc((void**)&v->outs[i], v->out_bytes, hipHostMallocPortable));
+    return SR_OK;
+}
+
+// the rest of either create call: v holds its format and frame sizes; on failure it is freed
+int video_open(sr_ctx* c, sr_video* v, int h, int w, int slots, unsigned members, sr_video** out) {
+    v->c = c;
+    v->h = h;
+    v->w = w;
+    v->slots = slots;
+    v->members = members;
+    const int rc = sr_on_device(c, [&] { return video_create(v); });
+    if (rc != SR_OK) {
+        video_free(v);
+        delete v;
+        return rc;
+    }
+    c->videos.push_back(v);
+    *out = v;
     return SR_OK;
 }
 
@@ -241,23 +345,69 @@ int sr_video_create(sr_ctx* c, const sr_yuv_format* fmt, int h, int w, int slots
     if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
     SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
     sr_video* v = new sr_video;
-    v->c = c;
     v->k = k;
-    v->h = h;
-    v->w = w;
-    v->slots = slots;
-    v->members = members;
     v->in_bytes = sr_yuv_rule_frame_bytes(k, h, w);
     v->out_bytes = sr_yuv_rule_frame_bytes(k, c->factor * h, c->factor * w);
-    const int rc = sr_on_device(c, [&] { return video_create(v); });
-    if (rc != SR_OK) {
-        video_free(v);
-        delete v;
-        return rc;
-    }
-    c->videos.push_back(v);
-    *out = v;
-    return SR_OK;
+    return video_open(c, v, h, w, slots, members, out);
+}
+
+int sr_video_create16(sr_ctx* c, const sr_yuv16_format* fmt, int h, int w, int slots, unsigned members, sr_video** out) {
+    sr_plan_clear(c);
+    if (out) *out = nullptr;
+    sr_yuv16_rule k;
+    if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
+    SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
+    sr_video* v = new sr_video;
+    v->deep = true;
+    v->k16 = k;
+    v->in_bytes = 2 * sr_yuv16_rule_frame_samples(k, h, w);
+    v->out_bytes = 2 * sr_yuv16_rule_frame_samples(k, c->factor * h, c->factor * w);
+    return video_open(c, v, h, w, slots, members, out);
+}
+
+size_t sr_yuv16_frame_bytes(const sr_yuv16_format* fmt, int h, int w) {
+    sr_yuv16_rule k;
+    if (!sr_yuv16_rule_make(fmt, &k) || h < 1 || w < 1) return 0;
+    const size_t samples = sr_yuv16_rule_frame_samples(k, h, w);
+    return samples > SIZE_MAX / 2 ? 0 : 2 * samples;
+}
+
+int sr_yuv16_to_rgb_dev(sr_ctx* c, const uint16_t* d_yuv, const sr_yuv16_format* fmt, int n, int h, int w, float* d_rgb, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv16_rule k;
+    if (!c || !d_yuv || !d_rgb || !sr_yuv16_rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    if (!sr_dword_aligned(d_rgb) || !sample_aligned(d_yuv)) return SR_E_INVALID;
+    return sr_on_device(c, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
+}
+
+int sr_rgb_to_yuv16_dev(sr_ctx* c, const float* d_rgb, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_yuv, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv16_rule k;
+    if (!c || !d_yuv || !d_rgb || !sr_yuv16_rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    if (!sr_dword_aligned(d_rgb) || !sample_aligned(d_yuv)) return SR_E_INVALID;
+    return sr_on_device(c, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
+}
+
+int sr_upscale_yuv16_dev(sr_ctx* c, const uint16_t* d_in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_out, unsigned members,
+                         void* stream) {
+    sr_plan_clear(c);
+    sr_yuv16_rule k;
+    SRCHK(check_upscale_args(c, d_in, fmt, n, h, w, d_out, members, &k));
+    return sr_on_device(c, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
+}
+
+int sr_upscale_yuv16(sr_ctx* c, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, unsigned members) {
+    sr_plan_clear(c);
+    sr_yuv16_rule k;
+    SRCHK(check_upscale_args(c, in, fmt, n, h, w, out, members, &k));
+    const int f = c->factor;
+    const size_t in_bytes = (size_t)n * 2 * sr_yuv16_rule_frame_samples(k, h, w);
+    const size_t out_bytes = (size_t)n * 2 * sr_yuv16_rule_frame_samples(k, f * h, f * w);
+    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return queue_upscale(c, (const uint16_t*)d_in, k, n, h, w, (uint16_t*)d_out, members, s);
+    });
 }
 
 int sr_video_acquire(sr_video* v, uint8_t** in_frame) {

@@ -60,11 +60,13 @@ def parse_plan(text: str) -> dict:
     host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
     st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
     parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid.  An op (a launch of a pixel
-    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, in the order they were queued): name,
+    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, yuv16_to_rgb, rgb_to_yuv16, in the order
+    they were queued): name,
     px ("u8" | "f32": the pixels the kernel is instantiated on -- resize_h its input's, resize_v its output's, the two video conversions
-    their input's, the two deep-colour conversions their f32 side), n, bx, by (workgroups along a row and along the rows of one image;
+    their input's, the two deep-colour and the two deep video conversions their f32 side), n, bx, by (workgroups along a row and along the rows of one image;
     resize_h: groups of the batch's n h rows; the deep-colour conversions: n = by = 1, the batch is one run of pixels), count, and form
-    ("staged4" | "staged1" | "direct", resize_h; "420center" | "420left" | "444", the video conversions; "wide" | "wide_in" | "wide_out" |
+    ("staged4" | "staged1" | "direct", resize_h; "420center" | "420left" | "444", the video conversions, and also
+    "422center" | "422left", the deep video conversions; "wide" | "wide_in" | "wide_out" |
     "narrow", the deep-colour conversions) or f (the factor, merge).
     Lines of any other kind are ignored."""
     rec = {"host": [], "fork": [], "launches": [], "aux": [], "ops": []}
@@ -513,6 +515,90 @@ class Engine:
         _lib.check(self._L.sr_upscale_yuv(self._ctx, a.ctypes.data_as(u8p), C.byref(fmt), n, h, w, out.ctypes.data_as(u8p),
                                           self._members(members)), self._ctx)
         out = out.reshape(n, ob)
+        return out[0] if squeeze else out
+
+    # ---- deep video: planar YCbCr frames of 9..16-bit samples in uint16 (include/srhip.h "Deep video") ----
+    @staticmethod
+    def _yuv16_frames(frames, fmt, h, w):
+        """Host frames as a C-contiguous (n, frame_samples) u16 array; squeeze: it was one frame (1-d)."""
+        fs = yuv16_frame_bytes(fmt, h, w) // 2
+        a = np.ascontiguousarray(frames, dtype=np.uint16)
+        squeeze = a.ndim == 1
+        if fs == 0 or a.ndim not in (1, 2) or a.shape[-1] != fs:
+            raise ValueError(f"expected frames of {fs} samples")
+        return (a[None] if squeeze else a), squeeze
+
+    @staticmethod
+    def _yuv16_frames_dev(frames, fmt, h, w):
+        """A contiguous tensor of 16-bit samples on the GPU (torch.uint16 or torch.int16), (n, frame_samples) or (frame_samples,)."""
+        fs = yuv16_frame_bytes(fmt, h, w) // 2
+        assert frames.is_cuda and frames.element_size() == 2 and frames.is_contiguous() and frames.dim() in (1, 2) and frames.shape[-1] == fs
+        return 1 if frames.dim() == 1 else frames.shape[0]
+
+    def yuv16_to_rgb_dev(self, frames, fmt, h: int, w: int, out=None, stream=None):
+        """sr_yuv16_to_rgb_dev: (n, frame_samples) 16-bit samples on this GPU -> (n,h,w,3) f32 RGB in [0, 1], the network's input."""
+        n = self._yuv16_frames_dev(frames, fmt, h, w)
+        out = self._dev_out(out, (n, h, w, 3), np.float32, frames.device)
+        _lib.check(self._L.sr_yuv16_to_rgb_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                               self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def rgb_to_yuv16_dev(self, x, fmt, out=None, stream=None):
+        """sr_rgb_to_yuv16_dev: (n,h,w,3) f32 RGB on this GPU (any values: clamped; NaN counts as 0) -> (n, frame_samples) int16 tensor
+        holding the uint16 samples (view it as torch.uint16, or numpy .view(np.uint16))."""
+        import torch
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        fs = yuv16_frame_bytes(fmt, h, w) // 2
+        if out is None:
+            out = torch.empty((n, fs), dtype=torch.int16, device=x.device)
+        assert out.is_cuda and out.element_size() == 2 and out.is_contiguous() and out.numel() == n * fs
+        _lib.check(self._L.sr_rgb_to_yuv16_dev(self._ctx, C.c_void_p(x.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                               self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def upscale_yuv16_dev(self, frames, fmt, h: int, w: int, members: int = 1, out=None, stream=None):
+        """sr_upscale_yuv16_dev: (n, frame_samples) frames of h x w on this GPU -> (n, frame_samples of fh x fw) in the same format (int16
+        tensor holding the uint16 samples unless `out` is given)."""
+        import torch
+        n = self._yuv16_frames_dev(frames, fmt, h, w)
+        fs = yuv16_frame_bytes(fmt, self.factor * h, self.factor * w) // 2
+        if out is None:
+            out = torch.empty((n, fs), dtype=torch.int16, device=frames.device)
+        assert out.is_cuda and out.element_size() == 2 and out.is_contiguous() and out.numel() == n * fs
+        _lib.check(self._L.sr_upscale_yuv16_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                                self._members(members), self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def yuv16_to_rgb(self, frames: np.ndarray, fmt, h: int, w: int) -> np.ndarray:
+        """yuv16_to_rgb_dev on host frames: (n, frame_samples) or (frame_samples,) u16 -> (n,h,w,3) or (h,w,3) f32."""
+        import torch
+        a, squeeze = self._yuv16_frames(frames, fmt, h, w)
+        out = self.yuv16_to_rgb_dev(torch.from_numpy(a.view(np.int16)).to(f"cuda:{self.device}"), fmt, h, w)
+        torch.cuda.synchronize(out.device)
+        out = out.cpu().numpy()
+        return out[0] if squeeze else out
+
+    def rgb_to_yuv16(self, x: np.ndarray, fmt) -> np.ndarray:
+        """rgb_to_yuv16_dev on a host image: (n,h,w,3) or (h,w,3) f32 -> (n, frame_samples) or (frame_samples,) u16."""
+        import torch
+        x, squeeze, _, _, _, _ = self._host_batch(x, np.float32, 3)
+        out = self.rgb_to_yuv16_dev(torch.from_numpy(x).to(f"cuda:{self.device}"), fmt)
+        torch.cuda.synchronize(out.device)
+        out = out.cpu().numpy().view(np.uint16)
+        return out[0] if squeeze else out
+
+    def upscale_yuv16(self, frames: np.ndarray, fmt, h: int, w: int, members: int = 1, out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_yuv16: (n, frame_samples) or (frame_samples,) u16 frames of h x w -> the frames of fh x fw in the same format."""
+        a, squeeze = self._yuv16_frames(frames, fmt, h, w)
+        n, os_ = a.shape[0], yuv16_frame_bytes(fmt, self.factor * h, self.factor * w) // 2
+        if out is None:
+            out = np.empty((n, os_), dtype=np.uint16)
+        elif out.dtype != np.uint16 or out.size != n * os_ or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous u16 array of {n * os_} samples")
+        u16p = C.POINTER(C.c_uint16)
+        _lib.check(self._L.sr_upscale_yuv16(self._ctx, a.ctypes.data_as(u16p), C.byref(fmt), n, h, w, out.ctypes.data_as(u16p),
+                                            self._members(members)), self._ctx)
+        out = out.reshape(n, os_)
         return out[0] if squeeze else out
 
     # ---- deep colour: 16-bit samples in and out (include/srhip.h "Deep colour") ----
@@ -1859,15 +1945,26 @@ def yuv_frame_bytes(fmt, h: int, w: int) -> int:
     return int(_lib.lib().sr_yuv_frame_bytes(C.byref(fmt), int(h), int(w)))
 
 
+Yuv16Format = _lib.Yuv16Format
+
+
+def yuv16_frame_bytes(fmt, h: int, w: int) -> int:
+    """sr_yuv16_frame_bytes: the BYTES of one planar frame of h x w 16-bit luma samples (0: an invalid format or shape).  Host only."""
+    return int(_lib.lib().sr_yuv16_frame_bytes(C.byref(fmt), int(h), int(w)))
+
+
 class VideoStream:
     """An sr_video session (include/srhip.h "Video"): frames of h x w in `fmt` go in, frames of fh x fw come out in order, the copies
-    of successive frames running under the kernels.  While frames are in flight the engine takes no other call."""
+    of successive frames running under the kernels.  While frames are in flight the engine takes no other call.  `fmt` is a YuvFormat
+    or a Yuv16Format (sr_video_create16); either way frames go in and come out as bytes (a u16 array is taken by its bytes)."""
 
     def __init__(self, engine: Engine, fmt, h: int, w: int, slots: int = 3, members=None):
         self._L, self._e, self._v = engine._L, engine, C.c_void_p()
-        self.slots, self.in_bytes = int(slots), yuv_frame_bytes(fmt, h, w)
-        self.out_bytes = yuv_frame_bytes(fmt, engine.factor * h, engine.factor * w)
-        _lib.check(self._L.sr_video_create(engine._ctx, C.byref(fmt), int(h), int(w), self.slots,
+        deep = isinstance(fmt, _lib.Yuv16Format)
+        frame_bytes, create = (yuv16_frame_bytes, self._L.sr_video_create16) if deep else (yuv_frame_bytes, self._L.sr_video_create)
+        self.slots, self.in_bytes = int(slots), frame_bytes(fmt, h, w)
+        self.out_bytes = frame_bytes(fmt, engine.factor * h, engine.factor * w)
+        _lib.check(create(engine._ctx, C.byref(fmt), int(h), int(w), self.slots,
                                            Engine._members(1 if members is None else members), C.byref(self._v)), engine._ctx)
 
     @property
@@ -1876,7 +1973,8 @@ class VideoStream:
 
     def submit(self, frame) -> None:
         """Copy one frame (in_bytes u8) into a free slot's page-locked buffer and queue it; SrError(SR_E_INVALID) if none is free."""
-        frame = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+        frame = np.ascontiguousarray(frame)
+        frame = (frame if frame.dtype == np.uint16 else frame.astype(np.uint8, copy=False)).reshape(-1).view(np.uint8)
         if frame.size != self.in_bytes:
             raise ValueError(f"expected a frame of {self.in_bytes} bytes")
         p = C.c_void_p()

@@ -4,7 +4,7 @@
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
 //   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] [--loss LOSS] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] [--degrade SPEC [--seed N]] <VALIDATION_FOLDER>
-//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709] [--slots N] [--timing] <IN|-> <OUT|->
+//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709|bt2020] [--depth 8|auto] [--siting center|left] [--slots N] [--timing] <IN|-> <OUT|->
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
 // PSNR a parameter set reaches on a folder of HR images.  `video` upscales a YUV4MPEG2 stream frame by frame (y4m.hpp; the reference has
@@ -1280,20 +1280,26 @@ const char kVideoHelp[] =
     "Upscales a YUV4MPEG2 stream frame by frame: colour conversion and chroma resampling run on the GPU, the network's\n"
     "output is quantised once, straight to YCbCr, and the copies of successive frames overlap the kernels.  Frames are\n"
     "independent.  `-` is stdin / stdout:  ffmpeg -i in.mp4 -f yuv4mpegpipe - | rusty_sr video - - | ffmpeg -i - out.mp4\n"
-    "Streams: 8-bit progressive C420jpeg, C420, C420mpeg2, C444; XCOLORRANGE=FULL selects full range.\n\n"
+    "Streams: 8-bit progressive C420jpeg, C420, C420mpeg2, C444; XCOLORRANGE=FULL selects full range.\n"
+    "With --depth auto also the deep streams C420p<d>, C422p<d>, C444p<d> (d = 9, 10, 12, 14, 16; 16-bit little-endian\n"
+    "samples), written out at the depth they came in:  ffmpeg -i in.mkv -pix_fmt yuv420p10le -strict -1 -f yuv4mpegpipe - |\n"
+    "rusty_sr video --depth auto - - | ffmpeg -i - out.mkv\n\n"
     "OPTIONS:\n"
     "    -p, --parameters <PARAMETERS>    [values: anime, bilinear, imagenet, imagenetlinear]\n"
     "    -c, --custom <PARAMETER_FILE>\n"
     "        --precision <MODE>           [values: f32, split_f16]\n"
     "        --device <N>\n"
     "        --ensemble <N>               [values: 2, 4, 8]\n"
-    "        --matrix <MATRIX>            [values: bt601, bt709]  default: bt709 from 1280 columns or above 576 rows, else bt601\n"
+    "        --matrix <MATRIX>            [values: bt601, bt709]  default: bt709 from 1280 columns or above 576 rows, else bt601;\n"
+    "                                     bt2020 (non-constant luminance) on a deep stream only, never chosen by default\n"
+    "        --depth <BITS>               [values: 8, auto]  8 (default): 8-bit streams only; auto: the stream's own depth\n"
+    "        --siting <SITING>            [values: center, left]  chroma siting of a deep 4:2:0 / 4:2:2 stream (default: left)\n"
     "        --slots <N>                  frames in flight [1..8], default 3\n"
     "        --timing                     print frames and ms/frame to stderr\n";
 
 int run_video(int argc, char** argv) {
     std::vector<std::string> pos;
-    std::string parameters, custom, precision = "f32", matrix;
+    std::string parameters, custom, precision = "f32", matrix, depth_arg = "8", siting;
     bool has_p = false, has_c = false, timing = false;
     long device = 0, slots = 3;
     unsigned ensemble = 0;
@@ -1322,7 +1328,15 @@ int run_video(int argc, char** argv) {
         }
         else if (a == "--matrix") {
             matrix = value("--matrix <MATRIX>");
-            if (matrix != "bt601" && matrix != "bt709") video_usage_error("'" + matrix + "' isn't a valid value for '--matrix <MATRIX>'\n\t[values: bt601, bt709]");
+            if (matrix != "bt601" && matrix != "bt709" && matrix != "bt2020") video_usage_error("'" + matrix + "' isn't a valid value for '--matrix <MATRIX>'\n\t[values: bt601, bt709]");
+        }
+        else if (a == "--depth" || a.rfind("--depth=", 0) == 0) {
+            depth_arg = a == "--depth" ? value("--depth <BITS>") : a.substr(8);
+            if (depth_arg != "8" && depth_arg != "auto") video_usage_error("'" + depth_arg + "' isn't a valid value for '--depth <BITS>'\n\t[values: 8, auto]");
+        }
+        else if (a == "--siting") {
+            siting = value("--siting <SITING>");
+            if (siting != "center" && siting != "left") video_usage_error("'" + siting + "' isn't a valid value for '--siting <SITING>'\n\t[values: center, left]");
         }
         else if (a == "--loss") video_usage_error("The argument '--loss' can only be used with the 'train' subcommand");
         else if (a == "--lr" || a == "--lr-schedule" || a == "--warmup" || a == "--clip" || a == "--ema" || a == "--resume") video_usage_error("The argument '" + a + "' can only be used with the 'train' subcommand");
@@ -1344,12 +1358,21 @@ int run_video(int argc, char** argv) {
     std::string line, err;
     sry4m::Header hd;
     if (sry4m::read_line(fin, line) != 1) video_usage_error("the input is not a YUV4MPEG2 stream (no header line)");
-    if (!sry4m::parse_header(line.data(), line.size(), hd, err)) video_usage_error(err);
+    if (!sry4m::parse_header(line.data(), line.size(), hd, err, depth_arg == "auto")) video_usage_error(err);
+    const bool deep = hd.depth > 8;  // (only under --depth auto)
+    if (!deep && matrix == "bt2020") video_usage_error("The argument '--matrix bt2020' can only be used with a deep stream (--depth auto, C420p10 and its kin)");
+    if (!deep && !siting.empty()) video_usage_error("The argument '--siting <SITING>' can only be used with a deep stream (--depth auto, C420p10 and its kin)");
     sr_yuv_format fmt{};
     fmt.subsampling = hd.s444 ? SR_YUV_444 : SR_YUV_420;
     fmt.siting = hd.left ? SR_YUV_SITING_LEFT : SR_YUV_SITING_CENTER;
     fmt.matrix = !matrix.empty() ? (matrix == "bt709" ? SR_YUV_BT709 : SR_YUV_BT601) : (hd.w >= 1280 || hd.h > 576) ? SR_YUV_BT709 : SR_YUV_BT601;
     fmt.range = hd.full ? SR_YUV_FULL : SR_YUV_LIMITED;
+    sr_yuv16_format fmt16{};  // a deep stream's: the same default matrix rule, the siting the option gives
+    fmt16.subsampling = hd.s444 ? (int32_t)SR_YUV_444 : hd.s422 ? (int32_t)SR_YUV_422 : (int32_t)SR_YUV_420;
+    fmt16.siting = !siting.empty() ? (siting == "left" ? SR_YUV_SITING_LEFT : SR_YUV_SITING_CENTER) : fmt.siting;
+    fmt16.matrix = matrix == "bt2020" ? SR_YUV_BT2020 : fmt.matrix;
+    fmt16.range = fmt.range;
+    fmt16.depth = hd.depth;
 
     // ---- parameters + graph, the progress text on stderr (stdout may be the stream)
     std::vector<float> params;
@@ -1373,9 +1396,11 @@ int run_video(int argc, char** argv) {
     if (precision == "split_f16" && (rc = sr_set_precision(ctx, SR_PRECISION_SPLIT_F16)) != SR_OK)
         die(std::string(sr_strerror(rc)) + " (SR_PRECISION_SPLIT_F16 cannot carry these parameters; use --precision f32)");
     sr_video* vid = nullptr;
-    rc = sr_video_create(ctx, &fmt, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid);
+    rc = deep ? sr_video_create16(ctx, &fmt16, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid)
+              : sr_video_create(ctx, &fmt, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid);
     if (rc != SR_OK) die(sr_strerror(rc));
-    const size_t in_bytes = sr_yuv_frame_bytes(&fmt, hd.h, hd.w), out_bytes = sr_yuv_frame_bytes(&fmt, SR_FACTOR * hd.h, SR_FACTOR * hd.w);
+    const size_t in_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, hd.h, hd.w) : sr_yuv_frame_bytes(&fmt, hd.h, hd.w);
+    const size_t out_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, SR_FACTOR * hd.h, SR_FACTOR * hd.w) : sr_yuv_frame_bytes(&fmt, SR_FACTOR * hd.h, SR_FACTOR * hd.w);
 
     FILE* fout = pos[1] == "-" ? stdout : fopen(pos[1].c_str(), "wb");
     if (!fout) die("Could not write output stream " + pos[1]);

@@ -25,9 +25,24 @@ bool ends_with(const std::string& s, const char* tail) {
     return s.size() >= n && s.compare(s.size() - n, n, tail) == 0;
 }
 
+// "420p10" and its kin: <420|422|444>p<9|10|12|14|16>
+bool parse_deep_tag(const std::string& v, Header& out) {
+    if (v.size() < 5 || v[3] != 'p') return false;
+    const std::string base = v.substr(0, 3), d = v.substr(4);
+    if (base != "420" && base != "422" && base != "444") return false;
+    if (d != "9" && d != "10" && d != "12" && d != "14" && d != "16") return false;
+    out.depth = d.size() == 1 ? d[0] - '0' : 10 + (d[1] - '0');
+    out.s444 = base == "444";
+    out.s422 = base == "422";
+    out.left = !out.s444;
+    return true;
+}
+
 }  // namespace
 
-bool parse_header(const char* line, size_t len, Header& out, std::string& err) {
+bool parse_header(const char* line, size_t len, Header& out, std::string& err) { return parse_header(line, len, out, err, false); }
+
+bool parse_header(const char* line, size_t len, Header& out, std::string& err, bool deep) {
     static const char kMagic[] = "YUV4MPEG2";
     const size_t m = sizeof kMagic - 1;
     out = Header{};
@@ -60,6 +75,7 @@ bool parse_header(const char* line, size_t len, Header& out, std::string& err) {
         case 'C':
             if (has_c) { err = "more than one C tag in the stream header"; return false; }
             has_c = true;
+            if (deep && parse_deep_tag(v, out)) break;
             if (ends_with(v, "p10") || ends_with(v, "p12") || ends_with(v, "p14") || ends_with(v, "p16") || v == "mono16") {
                 err = "'" + tag + "': only 8-bit streams are supported";
                 return false;
