@@ -739,7 +739,8 @@ int sr_upscale_f32_border(sr_ctx* ctx, const float* in, int n, int h, int w, flo
  * than the network.  These calls take and give planar 8-bit frames laid out exactly like a Y4M frame payload: Y (h x w), then Cb, then
  * Cr, each ch x cw -- ch = ceil(h / 2), cw = ceil(w / 2) for SR_YUV_420, h x w for SR_YUV_444 -- contiguous, so a plane may start at
  * any byte.  UNPINNED: the reference has no counterpart; tests/yuv_ref.py states the rule in numpy (f64) and the kernels equal it bit
- * for bit.  Frames are independent: there is no temporal processing.
+ * for bit.  The network sees single frames: no motion, no blending across frames.  A frame stream may, as an exact opt-in
+ * (sr_video_set_reuse below), take the output rows of the last frame for the rows no changed input row can reach.
  *   Format    subsampling SR_YUV_420 | SR_YUV_444; siting (4:2:0 only) SR_YUV_SITING_CENTER (JPEG, plain C420) | SR_YUV_SITING_LEFT
  *             (MPEG-2: horizontally co-sited with the even columns; vertically centred under both); matrix SR_YUV_BT601 (Kr 0.299,
  *             Kb 0.114) | SR_YUV_BT709 (0.2126, 0.0722); range SR_YUV_LIMITED (Y 16..235, C 16..240) | SR_YUV_FULL.
@@ -803,6 +804,61 @@ int sr_video_submit(sr_video* v);
 int sr_video_receive(sr_video* v, const uint8_t** out_frame);
 int sr_video_pending(const sr_video* v);
 void sr_video_destroy(sr_video* v);
+/* Row reuse: compute only the rows that changed since the last frame.  Letterbox bars, held animation cels and screen recordings repeat
+ * whole rows byte for byte, and an output row depends on the input rows within SR_HALO of it alone.  With SR_VIDEO_REUSE_ROWS a submitted
+ * frame is compared on the device, row by row and plane by plane, with the last submitted frame; the network runs on the row bands whose
+ * dependency cone holds a changed row (the band form, bit-identical to the same rows of the undivided call), and every other output row
+ * is the last frame's.  EXACT: every frame received is byte for byte what the session gives with the mode off.  Off by default; with
+ * it off the session queues what it always queued and owns none of the buffers below.
+ *   sr_rows_differ_dev   d_flags[r] = 1 where the row_bytes bytes of row r differ between a and b (rows contiguous, pitch = row_bytes),
+ *                        else 0: one launch on `stream`, every flag written exactly once (no clearing needed), no atomics, the same bits
+ *                        on every run.  Bytes are compared, so planes of 8- and 16-bit samples are the same call; a and b may start at
+ *                        any byte.  SR_E_INVALID before any launch: a null pointer, rows or row_bytes of 0, rows beyond INT32_MAX,
+ *                        d_flags not 4-byte aligned.
+ *   sr_video_reuse_plan  host only, no device: the LR row bands [y0, y1) a frame computes, from the flags of its Y rows, then its Cb
+ *                        rows, then its Cr rows (subsampling: SR_YUV_420 | SR_YUV_444 | SR_YUV_422; h luma rows).  *n_bands == 0: reuse
+ *                        the whole last output; one band [0, h): the whole frame.  The rule (tests/reuse_ref.py restates it):
+ *                        1. a differing Y row y is RGB-dirty; so is row y for a differing chroma row y (4:4:4, 4:2:2); a differing 4:2:0
+ *                           chroma row c dirties rows max(0, 2c - 1) .. min(h - 1, 2c + 2), the rows whose vertical taps read C[c];
+ *                        2. needed are the rows within SR_HALO of a dirty row;
+ *                        3. bands are the maximal runs of needed rows, each start rounded down and each end rounded up to an even row
+ *                           (or h) -- no 2 x 2 block of the 4:2:0 output straddles an edge -- a start below SR_HALO becoming 0 and an end
+ *                           within SR_HALO of h becoming h (SR_E_HALO's rule); bands fewer than 2 SR_HALO rows apart are merged (what a
+ *                           separate band recomputes as margin), top to bottom; above SR_REUSE_MAX_BANDS the two with the smallest gap
+ *                           are merged, of equal gaps the pair nearer the top, until that many remain;
+ *                        4. if the bands' rows plus 2 SR_HALO a band reach h, the plan is the whole frame.
+ *                        SR_E_INVALID: a null pointer, h < 1, another subsampling, max_bands below the plan's count (SR_REUSE_MAX_BANDS
+ *                        always suffices).
+ *   sr_video_set_reuse   SR_VIDEO_REUSE_OFF | SR_VIDEO_REUSE_ROWS, only while nothing is pending (else, and for another mode,
+ *                        SR_E_INVALID); the next frame is computed whole.  Turning it on allocates the session's reuse buffers (a device
+ *                        copy of the last input frame, a band-sized output frame, the flags) and the context's workspace for the whole
+ *                        frame: nothing is allocated per frame.  Turning it off frees the session's reuse buffers again (the context's
+ *                        workspaces stay, as after any call).
+ *   With the mode on sr_video_submit queues the compare, the copy of the frame to the reference and the flags' download behind the
+ *   upload on the upload stream, and WAITS for them -- the one new host wait.  (Measured: the upload stream's work reaches the device
+ *   only once the previous frame's kernels have left it, so the wait lasts about a frame period and a clip with nothing to reuse runs
+ *   as with one slot)  Then, on the compute stream: the clean row ranges of every plane from the previous frame's slot (one slot: they are in
+ *   place), the existing conversion of the whole frame to RGB, and per band the conv stack, the existing conversion of its f (y1 - y0)
+ *   rows from RGB, and three row-range copies into the slot's planes.  The download is the whole frame.  Whole-or-nothing: members != 1,
+ *   SR_GRAPH_BILINEAR, a session's first frame and the first after sr_video_set_reuse reuse the whole frame if no row differs and are
+ *   otherwise computed exactly as with the mode off.  Frames queued again in exact f32 (above) are computed whole; the frame after them
+ *   reuses rows again, now of f32 outputs.  A refused submit makes the next frame whole; so do sr_set_precision, sr_set_params
+ *   and a change of the kernel form (srhip_experimental.h "wino") between two frames: rows are reused only from an output computed
+ *   under the context's present precision, parameters and kernel form.
+ *   sr_video_get_reuse_stats  counts since the session was made: frames submitted with the mode on = frames_reused (no launch of the
+ *                        network) + frames_partial + frames_full; rows_total = h per such frame, rows_computed = the LR rows the
+ *                        network produced (halo rows not counted), bands = band passes (a whole frame counts as none).  Frames queued
+ *                        again in exact f32 are not counted a second time. */
+#define SR_REUSE_MAX_BANDS 4
+enum { SR_VIDEO_REUSE_OFF = 0, SR_VIDEO_REUSE_ROWS = 1 };
+typedef struct sr_row_band { int32_t y0, y1; } sr_row_band;   /* LR rows [y0, y1) to compute */
+typedef struct sr_video_reuse_stats {
+    uint64_t frames, frames_reused, frames_partial, frames_full, rows_total, rows_computed, bands;
+} sr_video_reuse_stats;
+int sr_rows_differ_dev(sr_ctx* ctx, const void* d_a, const void* d_b, size_t rows, size_t row_bytes, uint32_t* d_flags, void* stream);
+int sr_video_reuse_plan(const uint32_t* plane_flags, int subsampling, int h, sr_row_band* bands, int max_bands, int* n_bands);
+int sr_video_set_reuse(sr_video* v, int mode);
+int sr_video_get_reuse_stats(const sr_video* v, sr_video_reuse_stats* out);
 
 /* ---- Deep video: planar YCbCr frames of 9..16-bit samples, 4:2:0, 4:2:2 and 4:4:4 ----
  * What `ffmpeg -f yuv4mpegpipe` writes for HEVC, AV1 and ProRes sources (C420p10, C422p10, ...): the Video calls above on frames whose

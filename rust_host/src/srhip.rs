@@ -79,6 +79,27 @@ pub struct SrYuv16Format {
     pub depth: i32,
 }
 
+/// `sr_row_band`: LR rows `y0..y1` a frame computes (`sr_video_reuse_plan`).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrRowBand {
+    pub y0: i32,
+    pub y1: i32,
+}
+
+/// `sr_video_reuse_stats`: what a session's row reuse has computed and what it has taken over from the last frame.
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct SrVideoReuseStats {
+    pub frames: u64,
+    pub frames_reused: u64,
+    pub frames_partial: u64,
+    pub frames_full: u64,
+    pub rows_total: u64,
+    pub rows_computed: u64,
+    pub bands: u64,
+}
+
 /// `sr_degrade`: one item's blur width (HR pixels), noise level (8-bit levels), JPEG quality (0: none) and noise seed.
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -146,6 +167,9 @@ pub const SR_BORDER_PAD_MAX: c_int = 32;
 pub const SR_LOSS_MSE: c_int = 0;
 pub const SR_LOSS_L1: c_int = 1;
 pub const SR_LOSS_CHARBONNIER: c_int = 2;
+pub const SR_VIDEO_REUSE_OFF: c_int = 0;
+pub const SR_VIDEO_REUSE_ROWS: c_int = 1;
+pub const SR_REUSE_MAX_BANDS: c_int = 4;
 
 extern "C" {
     pub fn sr_rsr_decode(blob: *const u8, len: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
@@ -274,6 +298,10 @@ extern "C" {
     pub fn sr_video_receive(v: *mut SrVideo, out_frame: *mut *const u8) -> c_int;
     pub fn sr_video_pending(v: *const SrVideo) -> c_int;
     pub fn sr_video_destroy(v: *mut SrVideo);
+    pub fn sr_rows_differ_dev(ctx: *mut SrCtx, d_a: *const c_void, d_b: *const c_void, rows: usize, row_bytes: usize, d_flags: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn sr_video_reuse_plan(plane_flags: *const u32, subsampling: c_int, h: c_int, bands: *mut SrRowBand, max_bands: c_int, n_bands: *mut c_int) -> c_int;
+    pub fn sr_video_set_reuse(v: *mut SrVideo, mode: c_int) -> c_int;
+    pub fn sr_video_get_reuse_stats(v: *const SrVideo, out: *mut SrVideoReuseStats) -> c_int;
     pub fn sr_yuv16_frame_bytes(fmt: *const SrYuv16Format, h: c_int, w: c_int) -> usize;
     pub fn sr_yuv16_to_rgb_dev(ctx: *mut SrCtx, d_yuv: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, d_rgb: *mut f32, stream: *mut c_void) -> c_int;
     pub fn sr_rgb_to_yuv16_dev(ctx: *mut SrCtx, d_rgb: *const f32, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, d_yuv: *mut u16, stream: *mut c_void) -> c_int;

@@ -7,6 +7,6 @@ from .engine import (  # noqa: F401
     comm_init_all, upscale_batch_multi, upscale_multi, upscale_sharded_all, validation_psnr,
     aggregate_metrics, metrics_from_bytes, ssim_mean, validation_metrics, y_psnr,
     degrade_draws, parse_degrade_spec, parse_loss_spec, lr_at, parse_lr_schedule,
-    VideoStream, YuvFormat, yuv_frame_bytes, Yuv16Format, yuv16_frame_bytes,
+    VideoStream, YuvFormat, yuv_frame_bytes, Yuv16Format, yuv16_frame_bytes, video_reuse_plan,
 )
 from ._lib import SrError  # noqa: F401

@@ -32,6 +32,8 @@ SR_YUV_422, SR_YUV_BT2020 = 2, 2  # valid in sr_yuv16_format (Yuv16Format) only
 SR_YUV_SITING_CENTER, SR_YUV_SITING_LEFT = 0, 1
 SR_YUV_BT601, SR_YUV_BT709 = 0, 1
 SR_YUV_LIMITED, SR_YUV_FULL = 0, 1
+SR_VIDEO_REUSE_OFF, SR_VIDEO_REUSE_ROWS = 0, 1
+SR_REUSE_MAX_BANDS = 4
 SR_YUV_SPAN = 1024  # luma columns a workgroup of either conversion takes, two rows at a time (the tests put widths either side of it)
 SR_DEEP_SPAN = 2048  # pixels a workgroup of either deep-colour conversion takes, 8 a lane (the tests put counts either side of it)
 SR_LOSS_MSE, SR_LOSS_L1, SR_LOSS_CHARBONNIER = 0, 1, 2
@@ -103,6 +105,16 @@ class Yuv16Format(C.Structure):
     @classmethod
     def named(cls, subsampling="420", siting="left", matrix="bt709", range="limited", depth=10):
         return cls(cls.SUBSAMPLINGS[subsampling], cls.SITINGS[siting], cls.MATRICES[matrix], cls.RANGES[range], int(depth))
+
+
+class RowBand(C.Structure):
+    """sr_row_band (include/srhip.h "Video"): LR rows [y0, y1) a frame computes."""
+    _fields_ = [("y0", C.c_int32), ("y1", C.c_int32)]
+
+
+class VideoReuseStats(C.Structure):
+    """sr_video_reuse_stats (include/srhip.h "Video"): what a session's row reuse has computed and what it has taken over."""
+    _fields_ = [(name, C.c_uint64) for name in ("frames", "frames_reused", "frames_partial", "frames_full", "rows_total", "rows_computed", "bands")]
 
 
 # every symbol include/srhip.h declares: (restype, argtypes)
@@ -222,6 +234,10 @@ SYMBOLS = {
     "sr_video_receive": (_i, [_vp, C.POINTER(_vp)]),
     "sr_video_pending": (_i, [_vp]),
     "sr_video_destroy": (None, [_vp]),
+    "sr_rows_differ_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "sr_video_reuse_plan": (_i, [C.POINTER(C.c_uint32), _i, _i, C.POINTER(RowBand), _i, C.POINTER(_i)]),
+    "sr_video_set_reuse": (_i, [_vp, _i]),
+    "sr_video_get_reuse_stats": (_i, [_vp, C.POINTER(VideoReuseStats)]),
     "sr_yuv16_frame_bytes": (_sz, [C.POINTER(Yuv16Format), _i, _i]),
     "sr_yuv16_to_rgb_dev": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _vp, _vp]),
     "sr_rgb_to_yuv16_dev": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _vp, _vp]),

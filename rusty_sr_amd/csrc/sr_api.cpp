@@ -677,6 +677,10 @@ int ensure_features(sr_ctx* c, sr_ctx::Workspace& w, int n, int H, int W, int ti
 
 }  // namespace
 
+// Workspace 0's feature maps for one image of H x W, allocated now (a later pass over fewer rows finds them large enough: the frame
+// stream's row bands, sr_yuv.cpp).  The context's device is current.
+int sr_reserve_features(sr_ctx* c, int H, int W, hipStream_t s) { return ensure_features(c, c->ws[0], 1, H, W, (W + 31) / 32, s); }
+
 // The context's own streams, created when first needed: `stream` for everything the library runs by itself, and for a
 // pipelined host call a second compute stream and the download stream.
 int sr_ensure_streams(sr_ctx* c, bool pipelined) {

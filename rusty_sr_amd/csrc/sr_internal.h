@@ -164,7 +164,7 @@ inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     else c->plan_rec.emplace_back(line, 1);
 }
 
-// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16|yuv16_to_rgb|rgb_to_yuv16> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
+// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16|yuv16_to_rgb|rgb_to_yuv16|rows_differ> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
 // px: the pixels the kernel is instantiated on (resize_h, yuv2rgb, rgb2yuv: its input's, resize_v: its output's; the deep-colour and deep video conversions: their f32 side); bx / by: workgroups along a row and along
 // the rows of one image (resize_h: of the batch's n h rows; the deep-colour conversions: 1, the batch is one run of pixels), from the
 // *_blocks function the launcher itself calls.
@@ -277,6 +277,7 @@ int sr_run_stack(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int n, i
 // ... the same for one image as two row bands forked onto the context's second stream where that pays (the device entry points)
 int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int n, int H, int W, int halo_top, int halo_bot,
                       void* d_out, bool out_u8, hipStream_t s, const sr_halo_gate* gate = nullptr);
+int sr_reserve_features(sr_ctx* c, int H, int W, hipStream_t s);  // workspace 0's maps for one image of H x W, now; the context's device is current
 int sr_ensure_fork_resources(sr_ctx* c);  // the second stream + the fork / join events
 void sr_fork_tune_clear(sr_ctx* c);      // forget what the fork tuner has measured (its events with it); the context's device is current
 
@@ -589,6 +590,19 @@ size_t sr_rgb_to_yuv_blocks(int n, int h, int w, unsigned* blocks_x_out = nullpt
 // n frames at d_yuv (any byte) -> n x h x w x 3 f32 at d_rgb (4-byte aligned), and back
 hipError_t sr_launch_yuv_to_rgb(const uint8_t* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s);
 hipError_t sr_launch_rgb_to_yuv(const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s);
+// The row compare of the frame stream's row reuse (sr_reuse.hip): flags[r] = 1 where row r differs between a and b, else 0.  The rows
+// are those of n_seg (1..3) segments one after another -- a frame's planes -- each `rows` rows of `row_bytes` contiguous bytes that
+// begin `offset` bytes into a and into b; rows_total is their sum.  a, b: any byte; flags: 4-byte aligned.
+struct sr_rows_differ_args {
+    const uint8_t* a;
+    const uint8_t* b;
+    uint32_t* flags;
+    struct { size_t offset, rows, row_bytes; } seg[3];
+    int n_seg;
+    size_t rows_total;
+};
+size_t sr_rows_differ_blocks(size_t rows_total);  // workgroups of the launch: a function of the row count alone
+hipError_t sr_launch_rows_differ(const sr_rows_differ_args& a, hipStream_t s);
 void sr_yuv_release(sr_ctx* c);        // free the two buffers (called by sr_destroy)
 void sr_video_detach_all(sr_ctx* c);   // called by sr_destroy; a detached stream refuses every call but sr_video_destroy
 

@@ -295,3 +295,56 @@ std::vector<sr_chunk> sr_plan_chunks(const sr_plan_env& env, sr_deal deal, int h
     plan.push_back({img0_in, (size_t)n * in_img, img0_out, (size_t)n * out_img, n, h, 0, 0, in_step, out_step});
     return plan;
 }
+
+// ---- the row-reuse planner of the frame stream (include/srhip.h "Video"; restated in tests/reuse_ref.py) ----
+// Which LR rows a frame must compute, from the row flags of the compare against the last frame.  The two constants are reasons, not
+// tuned values: a separate band recomputes up to 2 SR_HALO margin rows (its two halos), so a gap of fewer clean rows is cheaper computed
+// than skipped, and a plan whose rows plus margins reach the frame is cheaper as the frame; four bands bound the launches of a frame.
+extern "C" int sr_video_reuse_plan(const uint32_t* plane_flags, int subsampling, int h, sr_row_band* bands, int max_bands, int* n_bands) {
+    if (n_bands) *n_bands = 0;
+    if (!plane_flags || !bands || !n_bands || h < 1 || max_bands < 1) return SR_E_INVALID;
+    if (subsampling != SR_YUV_420 && subsampling != SR_YUV_444 && subsampling != SR_YUV_422) return SR_E_INVALID;
+    const bool sub420 = subsampling == SR_YUV_420;
+    const int ch = sub420 ? (h + 1) / 2 : h;
+    // needed rows: within SR_HALO of an RGB-dirty row
+    std::vector<char> need((size_t)h, 0);
+    auto dirty = [&](int lo, int hi) {  // RGB-dirty rows lo .. hi
+        for (int y = std::max(0, lo - SR_HALO); y <= std::min(h - 1, hi + SR_HALO); ++y) need[(size_t)y] = 1;
+    };
+    for (int y = 0; y < h; ++y)
+        if (plane_flags[y]) dirty(y, y);
+    for (int p = 0; p < 2; ++p)
+        for (int c = 0; c < ch; ++c)
+            if (plane_flags[(size_t)h + (size_t)p * ch + c]) {
+                // 4:2:0: the luma rows whose vertical taps read C[c] -- 2i reads C[i-1], C[i]; 2i + 1 reads C[i], C[i+1]
+                if (sub420) dirty(std::max(0, 2 * c - 1), std::min(h - 1, 2 * c + 2));
+                else dirty(c, c);
+            }
+    // maximal runs, edges on even rows (or h) and never inside SR_HALO of an image edge; close runs merged
+    std::vector<sr_row_band> run;
+    for (int y = 0; y < h;) {
+        if (!need[(size_t)y]) { ++y; continue; }
+        int e = y;
+        while (e < h && need[(size_t)e]) ++e;
+        int a = y & ~1, b = std::min(h, (e + 1) & ~1);
+        if (a < SR_HALO) a = 0;
+        if (h - b < SR_HALO) b = h;
+        if (!run.empty() && a - run.back().y1 < 2 * SR_HALO) run.back().y1 = std::max(run.back().y1, b);
+        else run.push_back({a, b});
+        y = e;
+    }
+    while ((int)run.size() > SR_REUSE_MAX_BANDS) {  // the smallest gap goes; of equal gaps the one nearer the top
+        size_t at = 0;
+        for (size_t i = 1; i + 1 < run.size(); ++i)
+            if (run[i + 1].y0 - run[i].y1 < run[at + 1].y0 - run[at].y1) at = i;
+        run[at].y1 = run[at + 1].y1;
+        run.erase(run.begin() + (long)at + 1);
+    }
+    long cost = 0;
+    for (const sr_row_band& r : run) cost += r.y1 - r.y0 + 2 * SR_HALO;
+    if (!run.empty() && cost >= h) run.assign(1, sr_row_band{0, h});
+    if ((int)run.size() > max_bands) return SR_E_INVALID;
+    for (size_t i = 0; i < run.size(); ++i) bands[i] = run[i];
+    *n_bands = (int)run.size();
+    return SR_OK;
+}

@@ -3,7 +3,9 @@
 // and the frame stream, which keeps that call in flight for a ring of slots.  Kernels: sr_yuv.hip.  The composed calls are their checks,
 // their sizes and a work lambda; the stream is the one thing here the scaffold has no form for: a call that returns
 // before its work is done.  The deep video path (include/srhip.h "Deep video"; kernels: sr_yuv16.hip) is the
-// same three things on frames of uint16 samples with a format struct of its own; a session of either kind is one sr_video.
+// same three things on frames of uint16 samples with a format struct of its own; a session of either kind is one sr_video.  Row reuse
+// (sr_video_set_reuse; the compare kernel: sr_reuse.hip, the planner: sr_plan.cpp) is a session's opt-in: it computes the
+// row bands a changed input row can reach and takes the other rows from the last frame's output.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -204,9 +206,168 @@ struct sr_video {
     unsigned long long submitted = 0;  // frames submitted so far: frame i uses slot i mod slots and output i mod (slots + 1)
     int pending = 0;
     bool acquired = false;
+    // ---- row reuse (include/srhip.h sr_video_set_reuse): all of it null and unused with the mode off
+    int reuse = SR_VIDEO_REUSE_OFF;
+    bool have_ref = false;         // d_ref holds the input of the last submitted frame, and that frame's slot its output
+    // what the bits of that output depend on besides the frame, as the context had it when the output was computed: rows computed
+    // under another precision, other parameters (sr_set_params) or another kernel form ("wino": other last bits) are not reused
+    struct Made {
+        int precision = 0, wino = 0, wino5 = 0;
+        unsigned long long params_hash = 0;
+        bool operator==(const Made& o) const { return precision == o.precision && wino == o.wino && wino5 == o.wino5 && params_hash == o.params_hash; }
+    } ref_made;
+    void* d_ref = nullptr;         // in_bytes
+    void* d_band = nullptr;        // out_bytes: a band's output frame before its planes are copied into the slot's
+    uint32_t* d_flags = nullptr;   // a word per plane row: Y, Cb, Cr
+    uint32_t* h_flags = nullptr;   // page-locked
+    hipEvent_t flags_down = nullptr;
+    sr_video_reuse_stats stats{};
 };
 
 namespace {
+
+// ---- row reuse: the planes of a frame as rows of bytes, the plan of a frame, its launches
+// The three planes of one of the session's frames of H x W luma samples: rows, bytes a row, byte offset in the frame
+struct Planes {
+    size_t rows[3], row_bytes[3], offset[3];
+    bool vsub;  // the chroma planes have half the rows
+    size_t total_rows() const { return rows[0] + rows[1] + rows[2]; }
+};
+
+int video_subsampling(const sr_video* v) { return v->deep ? v->k16.sub : v->k.sub420 ? SR_YUV_420 : SR_YUV_444; }
+
+Planes video_planes(const sr_video* v, size_t H, size_t W) {
+    const int sub = video_subsampling(v);
+    const size_t bps = v->deep ? 2 : 1, ch = sub == SR_YUV_420 ? (H + 1) / 2 : H, cw = sub == SR_YUV_444 ? W : (W + 1) / 2;
+    Planes p{};
+    p.vsub = sub == SR_YUV_420;
+    p.rows[0] = H; p.row_bytes[0] = W * bps; p.offset[0] = 0;
+    for (int k = 1; k < 3; ++k) { p.rows[k] = ch; p.row_bytes[k] = cw * bps; p.offset[k] = p.offset[k - 1] + p.rows[k - 1] * p.row_bytes[k - 1]; }
+    return p;
+}
+
+// the rows of plane k that belong to luma rows [a, b) of its frame: a is even; b is even or the frame's height
+void plane_rows(const Planes& p, int k, size_t a, size_t b, size_t* lo, size_t* hi) {
+    const bool half = k > 0 && p.vsub;
+    *lo = half ? a / 2 : a;
+    *hi = half ? (b + 1) / 2 : b;
+}
+
+sr_video::Made video_made(const sr_ctx* c) {
+    sr_video::Made m;
+    m.precision = c->precision;
+    m.wino = c->wino;
+    m.wino5 = c->wino5;
+    m.params_hash = c->params_hash;
+    return m;
+}
+
+void reuse_free(sr_video* v) {
+    if (v->d_ref) (void)hipFree(v->d_ref);
+    if (v->d_band) (void)hipFree(v->d_band);
+    if (v->d_flags) (void)hipFree(v->d_flags);
+    if (v->h_flags) (void)hipHostFree(v->h_flags);
+    if (v->flags_down) (void)hipEventDestroy(v->flags_down);
+    v->d_ref = v->d_band = nullptr;
+    v->d_flags = v->h_flags = nullptr;
+    v->flags_down = nullptr;
+    v->have_ref = false;
+}
+
+// everything the mode's frames need, now: the session's own buffers and the context's workspaces for the whole frame, so that no frame
+// allocates (a band pass finds workspace 0's maps large enough whatever the whole frames' passes made of them)
+int reuse_reserve(sr_video* v) {
+    sr_ctx* c = v->c;
+    const size_t f = (size_t)c->factor, words = video_planes(v, (size_t)v->h, (size_t)v->w).total_rows();
+    if (!v->d_ref) HIPCHK(c, hipMalloc(&v->d_ref, v->in_bytes));
+    if (!v->d_band) HIPCHK(c, hipMalloc(&v->d_band, v->out_bytes));
+    if (!v->d_flags) HIPCHK(c, hipMalloc((void**)&v->d_flags, words * sizeof(uint32_t)));
+    if (!v->h_flags) HIPCHK(c, hipHostMalloc((void**)&v->h_flags, words * sizeof(uint32_t), hipHostMallocPortable));
+    if (!v->flags_down) HIPCHK(c, hipEventCreateWithFlags(&v->flags_down, hipEventDisableTiming));
+    SRCHK(sr_reserve_bufs(c, {{&c->d_yrgb, (size_t)v->h * v->w * kPxF}, {&c->d_ynet, f * v->h * f * v->w * kPxF}}));
+    if (c->graph == SR_GRAPH_SR_NET) SRCHK(sr_reserve_features(c, v->h, v->w, c->stream));
+    return SR_OK;
+}
+
+// behind the frame's upload on the upload stream: the compare of its planes with the reference's, the flags' download, the frame as
+// the next reference
+int reuse_queue_compare(sr_video* v, const void* d_in) {
+    sr_ctx* c = v->c;
+    if (v->have_ref) {
+        const Planes p = video_planes(v, (size_t)v->h, (size_t)v->w);
+        sr_rows_differ_args a{};
+        a.a = (const uint8_t*)d_in;
+        a.b = (const uint8_t*)v->d_ref;
+        a.flags = v->d_flags;
+        a.n_seg = 3;
+        for (int k = 0; k < 3; ++k) a.seg[k] = {p.offset[k], p.rows[k], p.row_bytes[k]};
+        a.rows_total = p.total_rows();
+        HIPCHK(c, sr_launch_rows_differ(a, c->copy_in));
+        sr_plan_note_op(c, "rows_differ", false, 1, (unsigned)sr_rows_differ_blocks(a.rows_total), 1);
+        HIPCHK(c, hipMemcpyAsync(v->h_flags, v->d_flags, a.rows_total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->copy_in));
+        HIPCHK(c, hipEventRecord(v->flags_down, c->copy_in));
+    }
+    HIPCHK(c, hipMemcpyAsync(v->d_ref, d_in, v->in_bytes, hipMemcpyDeviceToDevice, c->copy_in));
+    return SR_OK;
+}
+
+// What a frame computes: *n == 0 nothing, one band [0, h) the whole frame.  The session's first frame has no reference and is whole;
+// a call the band form does not exist for is whole unless no row differs.
+int reuse_plan(sr_video* v, sr_row_band bands[SR_REUSE_MAX_BANDS], int* n) {
+    sr_ctx* c = v->c;
+    bands[0] = {0, v->h};
+    *n = 1;
+    if (!v->have_ref) return SR_OK;
+    HIPCHK(c, hipEventSynchronize(v->flags_down));  // the one host wait of the mode (what it costs: DESIGN.md 4v)
+    SRCHK(sr_video_reuse_plan(v->h_flags, video_subsampling(v), v->h, bands, SR_REUSE_MAX_BANDS, n));
+    if (*n > 0 && (v->members != 1u || c->graph != SR_GRAPH_SR_NET)) {
+        bands[0] = {0, v->h};
+        *n = 1;
+    }
+    return SR_OK;
+}
+
+int copy_rows(sr_ctx* c, void* dst, const void* src, size_t row_bytes, size_t lo, size_t hi, size_t src_lo, hipStream_t s) {
+    if (lo >= hi) return SR_OK;
+    HIPCHK(c, hipMemcpyAsync((char*)dst + lo * row_bytes, (const char*)src + src_lo * row_bytes, (hi - lo) * row_bytes, hipMemcpyDeviceToDevice, s));
+    return SR_OK;
+}
+
+// the frame's bands on s: the rows between them from the previous frame's output, then band after band
+int reuse_queue_bands(sr_video* v, const void* d_in, void* d_out, const void* d_prev_out, const sr_row_band* bands, int n, hipStream_t s) {
+    sr_ctx* c = v->c;
+    const int h = v->h, w = v->w, f = c->factor;
+    const Planes out = video_planes(v, (size_t)f * h, (size_t)f * w);
+    if (d_prev_out != d_out)
+        for (int i = 0; i <= n; ++i) {  // the clean rows before band i (after the last one: i == n)
+            const size_t a = i ? (size_t)f * bands[i - 1].y1 : 0, b = i < n ? (size_t)f * bands[i].y0 : (size_t)f * h;
+            if (a >= b) continue;
+            for (int k = 0; k < 3; ++k) {
+                size_t lo, hi;
+                plane_rows(out, k, a, b, &lo, &hi);
+                SRCHK(copy_rows(c, (char*)d_out + out.offset[k], (const char*)d_prev_out + out.offset[k], out.row_bytes[k], lo, hi, lo, s));
+            }
+        }
+    if (n == 0) return SR_OK;
+    float* rgb = (float*)c->d_yrgb.p;
+    float* net = (float*)c->d_ynet.p;
+    if (v->deep) SRCHK(queue_to_rgb(c, (const uint16_t*)d_in, v->k16, 1, h, w, rgb, s));
+    else SRCHK(queue_to_rgb(c, (const uint8_t*)d_in, v->k, 1, h, w, rgb, s));
+    for (int i = 0; i < n; ++i) {
+        const int y0 = bands[i].y0, y1 = bands[i].y1, top = y0 > 0 ? SR_HALO : 0, bot = y1 < h ? SR_HALO : 0, bh = f * (y1 - y0);
+        float* band_net = net + (size_t)f * y0 * f * w * 3;
+        SRCHK(sr_run_stack(c, rgb + (size_t)(y0 - top) * w * 3, false, 3, 1, top + (y1 - y0) + bot, w, top, bot, band_net, false, s));
+        if (v->deep) SRCHK(queue_to_yuv(c, band_net, v->k16, 1, bh, f * w, (uint16_t*)v->d_band, s));
+        else SRCHK(queue_to_yuv(c, band_net, v->k, 1, bh, f * w, (uint8_t*)v->d_band, s));
+        const Planes band = video_planes(v, (size_t)bh, (size_t)f * w);
+        for (int k = 0; k < 3; ++k) {
+            size_t lo, hi;
+            plane_rows(out, k, (size_t)f * y0, (size_t)f * y1, &lo, &hi);
+            SRCHK(copy_rows(c, (char*)d_out + out.offset[k], (const char*)v->d_band + band.offset[k], out.row_bytes[k], lo, hi, 0, s));
+        }
+    }
+    return SR_OK;
+}
 
 // what a session holds on the device and in page-locked memory; its streams have drained
 void video_free(sr_video* v) {
@@ -222,6 +383,7 @@ void video_free(sr_video* v) {
         if (o) (void)hipHostFree(o);
         o = nullptr;
     }
+    reuse_free(v);
 }
 
 void video_drain(sr_ctx* c) {
@@ -230,15 +392,41 @@ void video_drain(sr_ctx* c) {
 }
 
 // frame number `frame` of the session: upload, the three phases, download, each on its stream, ordered by the slot's events
-int video_queue(sr_video* v, unsigned long long frame) {
+// (again: the frame is queued a second time, in exact f32, by sr_video_receive -- with row reuse on it is computed whole and neither
+// compared nor counted: the reference is the last SUBMITTED frame's input whatever is computed again)
+int video_queue(sr_video* v, unsigned long long frame, bool again = false) {
     sr_ctx* c = v->c;
     sr_video::Slot& s = v->slot[frame % (unsigned)v->slots];
     s.h_out = v->outs[frame % (unsigned)(v->slots + 1)];
     HIPCHK(c, hipMemcpyAsync(s.d_in, s.h_in, v->in_bytes, hipMemcpyHostToDevice, c->copy_in));
     HIPCHK(c, hipEventRecord(s.up, c->copy_in));
+    sr_row_band bands[SR_REUSE_MAX_BANDS] = {{0, v->h}};
+    int n_bands = 1;
+    if (v->reuse != SR_VIDEO_REUSE_OFF && !again) {
+        if (!(v->ref_made == video_made(c))) v->have_ref = false;  // (sr_set_precision, sr_set_params, "wino" between two frames: the next one is whole)
+        SRCHK(reuse_queue_compare(v, s.d_in));
+        SRCHK(reuse_plan(v, bands, &n_bands));
+    }
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.up, 0));
-    if (v->deep) SRCHK(queue_upscale(c, (const uint16_t*)s.d_in, v->k16, 1, v->h, v->w, (uint16_t*)s.d_out, v->members, c->stream));
-    else SRCHK(queue_upscale(c, (const uint8_t*)s.d_in, v->k, 1, v->h, v->w, (uint8_t*)s.d_out, v->members, c->stream));
+    if (n_bands == 1 && bands[0].y0 == 0 && bands[0].y1 == v->h) {
+        if (v->deep) SRCHK(queue_upscale(c, (const uint16_t*)s.d_in, v->k16, 1, v->h, v->w, (uint16_t*)s.d_out, v->members, c->stream));
+        else SRCHK(queue_upscale(c, (const uint8_t*)s.d_in, v->k, 1, v->h, v->w, (uint8_t*)s.d_out, v->members, c->stream));
+    } else {
+        SRCHK(reuse_queue_bands(v, s.d_in, s.d_out, v->slot[(frame + (unsigned)v->slots - 1) % (unsigned)v->slots].d_out, bands, n_bands, c->stream));
+    }
+    if (v->reuse != SR_VIDEO_REUSE_OFF && !again) {
+        sr_video_reuse_stats& st = v->stats;
+        const bool whole = n_bands == 1 && bands[0].y1 - bands[0].y0 == v->h;
+        ++st.frames;
+        st.rows_total += (uint64_t)v->h;
+        if (n_bands == 0) ++st.frames_reused;
+        else if (whole) ++st.frames_full;
+        else ++st.frames_partial;
+        for (int i = 0; i < n_bands; ++i) st.rows_computed += (uint64_t)(bands[i].y1 - bands[i].y0);
+        if (!whole) st.bands += (uint64_t)n_bands;
+        v->have_ref = true;
+    }
+    v->ref_made = video_made(c);
     HIPCHK(c, hipEventRecord(s.done, c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->copy_out, s.done, 0));
     HIPCHK(c, hipMemcpyAsync(s.h_out, s.d_out, v->out_bytes, hipMemcpyDeviceToHost, c->copy_out));
@@ -427,6 +615,7 @@ int sr_video_submit(sr_video* v) {
         const int rc = video_queue(v, v->submitted);
         if (rc != SR_OK) {
             video_drain(c);  // nothing of a refused frame stays queued; the slot is still the caller's
+            v->have_ref = false;  // (row reuse: the reference may be this frame's already, the outputs are not: the next frame is whole)
             return rc;
         }
         v->acquired = false;
@@ -450,7 +639,7 @@ int sr_video_receive(sr_video* v, const uint8_t** out_frame) {
             (void)sr_domain_tripped(c);
             (void)sr_set_precision(c, SR_PRECISION_F32);
             for (unsigned long long i = oldest; i < v->submitted; ++i) {
-                const int rc = video_queue(v, i);
+                const int rc = video_queue(v, i, true);
                 if (rc != SR_OK) {  // some frames are queued again and some are not: none of them may be handed out
                     video_drain(c);
                     v->failed = true;
@@ -468,6 +657,46 @@ int sr_video_receive(sr_video* v, const uint8_t** out_frame) {
 }
 
 int sr_video_pending(const sr_video* v) { return v && v->c && !v->failed ? v->pending : -1; }
+
+int sr_rows_differ_dev(sr_ctx* c, const void* d_a, const void* d_b, size_t rows, size_t row_bytes, uint32_t* d_flags, void* stream) {
+    sr_plan_clear(c);
+    if (!c || !d_a || !d_b || !d_flags || rows == 0 || row_bytes == 0 || !sr_dword_aligned(d_flags)) return SR_E_INVALID;
+    if (rows > (size_t)INT32_MAX || row_bytes > SIZE_MAX / rows) return SR_E_INVALID;
+    return sr_on_device(c, [&]() -> int {
+        sr_rows_differ_args a{};
+        a.a = (const uint8_t*)d_a;
+        a.b = (const uint8_t*)d_b;
+        a.flags = d_flags;
+        a.n_seg = 1;
+        a.seg[0] = {0, rows, row_bytes};
+        a.rows_total = rows;
+        HIPCHK(c, sr_launch_rows_differ(a, (hipStream_t)stream));
+        sr_plan_note_op(c, "rows_differ", false, 1, (unsigned)sr_rows_differ_blocks(rows), 1);
+        return SR_OK;
+    });
+}
+
+int sr_video_set_reuse(sr_video* v, int mode) {
+    if (!v || !v->c || v->failed || v->pending != 0) return SR_E_INVALID;
+    if (mode != SR_VIDEO_REUSE_OFF && mode != SR_VIDEO_REUSE_ROWS) return SR_E_INVALID;
+    sr_ctx* c = v->c;
+    sr_plan_clear(c);
+    v->have_ref = false;  // the next frame is computed whole
+    const int rc = sr_on_device(c, [&]() -> int {
+        if (mode == SR_VIDEO_REUSE_ROWS) return reuse_reserve(v);
+        reuse_free(v);  // off: the session owns none of the mode's buffers again (nothing is pending: nothing uses them)
+        return SR_OK;
+    });
+    if (rc != SR_OK) return rc;
+    v->reuse = mode;
+    return SR_OK;
+}
+
+int sr_video_get_reuse_stats(const sr_video* v, sr_video_reuse_stats* out) {
+    if (!v || !v->c || !out) return SR_E_INVALID;
+    *out = v->stats;
+    return SR_OK;
+}
 
 void sr_video_destroy(sr_video* v) {
     if (!v) return;

@@ -60,7 +60,7 @@ def parse_plan(text: str) -> dict:
     host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
     st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
     parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid.  An op (a launch of a pixel
-    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, yuv16_to_rgb, rgb_to_yuv16, in the order
+    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, yuv16_to_rgb, rgb_to_yuv16, rows_differ (bx: its workgroups), in the order
     they were queued): name,
     px ("u8" | "f32": the pixels the kernel is instantiated on -- resize_h its input's, resize_v its output's, the two video conversions
     their input's, the two deep-colour and the two deep video conversions their f32 side), n, bx, by (workgroups along a row and along the rows of one image;
@@ -482,6 +482,17 @@ class Engine:
         out = self._dev_out(out, (n, yuv_frame_bytes(fmt, self.factor * h, self.factor * w)), np.uint8, frames.device)
         _lib.check(self._L.sr_upscale_yuv_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
                                               self._members(members), self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def rows_differ_dev(self, a, b, rows: int, row_bytes: int, out=None, stream=None):
+        """sr_rows_differ_dev: two contiguous u8 tensors on this GPU, each holding rows x row_bytes bytes from its first element (views at
+        any byte offset will do) -> (rows,) int32 flags, 1 where the row differs.  The frame stream's row reuse compares with it."""
+        import torch
+        assert a.is_cuda and b.is_cuda and a.dtype == b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous()
+        assert a.numel() >= rows * row_bytes and b.numel() >= rows * row_bytes
+        out = self._dev_out(out, (rows,), np.int32, a.device)
+        _lib.check(self._L.sr_rows_differ_dev(self._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), int(rows), int(row_bytes),
+                                              C.c_void_p(out.data_ptr()), self._stream_ptr(stream, a.device)), self._ctx)
         return out
 
     def yuv_to_rgb(self, frames: np.ndarray, fmt, h: int, w: int) -> np.ndarray:
@@ -1953,12 +1964,27 @@ def yuv16_frame_bytes(fmt, h: int, w: int) -> int:
     return int(_lib.lib().sr_yuv16_frame_bytes(C.byref(fmt), int(h), int(w)))
 
 
+def video_reuse_plan(flags, subsampling, h: int):
+    """sr_video_reuse_plan: the LR row bands [(y0, y1), ...] a frame of h luma rows computes, from the row flags of its Y, Cb and Cr
+    planes one after another (nonzero: the row differs from the last frame's).  subsampling: "420" | "422" | "444" or the SR_YUV_*
+    number.  []: reuse the whole last output; [(0, h)]: the whole frame.  Host only."""
+    sub = _lib.Yuv16Format.SUBSAMPLINGS.get(subsampling, subsampling)
+    flags = np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+    if h >= 1 and sub in (_lib.SR_YUV_420, _lib.SR_YUV_422, _lib.SR_YUV_444) and flags.size != h + 2 * ((h + 1) // 2 if sub == _lib.SR_YUV_420 else h):
+        raise ValueError("expected a flag per row of the Y, the Cb and the Cr plane")
+    bands, n = (_lib.RowBand * _lib.SR_REUSE_MAX_BANDS)(), C.c_int()
+    _lib.check(_lib.lib().sr_video_reuse_plan(flags.ctypes.data_as(C.POINTER(C.c_uint32)), int(sub), int(h), bands, _lib.SR_REUSE_MAX_BANDS, C.byref(n)))
+    return [(int(bands[i].y0), int(bands[i].y1)) for i in range(n.value)]
+
+
 class VideoStream:
     """An sr_video session (include/srhip.h "Video"): frames of h x w in `fmt` go in, frames of fh x fw come out in order, the copies
     of successive frames running under the kernels.  While frames are in flight the engine takes no other call.  `fmt` is a YuvFormat
-    or a Yuv16Format (sr_video_create16); either way frames go in and come out as bytes (a u16 array is taken by its bytes)."""
+    or a Yuv16Format (sr_video_create16); either way frames go in and come out as bytes (a u16 array is taken by its bytes).
+    reuse=True (sr_video_set_reuse): only the rows a changed input row can reach are computed, the others are the last frame's --
+    the frames received are byte for byte the same; reuse_stats() says what that saved."""
 
-    def __init__(self, engine: Engine, fmt, h: int, w: int, slots: int = 3, members=None):
+    def __init__(self, engine: Engine, fmt, h: int, w: int, slots: int = 3, members=None, reuse: bool = False):
         self._L, self._e, self._v = engine._L, engine, C.c_void_p()
         deep = isinstance(fmt, _lib.Yuv16Format)
         frame_bytes, create = (yuv16_frame_bytes, self._L.sr_video_create16) if deep else (yuv_frame_bytes, self._L.sr_video_create)
@@ -1966,10 +1992,22 @@ class VideoStream:
         self.out_bytes = frame_bytes(fmt, engine.factor * h, engine.factor * w)
         _lib.check(create(engine._ctx, C.byref(fmt), int(h), int(w), self.slots,
                                            Engine._members(1 if members is None else members), C.byref(self._v)), engine._ctx)
+        if reuse:
+            self.set_reuse(True)
 
     @property
     def pending(self) -> int:
         return int(self._L.sr_video_pending(self._v))
+
+    def set_reuse(self, mode) -> None:
+        """sr_video_set_reuse: row reuse on (True / SR_VIDEO_REUSE_ROWS) or off, only with nothing pending; the next frame is whole."""
+        _lib.check(self._L.sr_video_set_reuse(self._v, int(mode)), self._e._ctx)
+
+    def reuse_stats(self) -> dict:
+        """sr_video_get_reuse_stats as a dict: frames, frames_reused, frames_partial, frames_full, rows_total, rows_computed, bands."""
+        st = _lib.VideoReuseStats()
+        _lib.check(self._L.sr_video_get_reuse_stats(self._v, C.byref(st)), self._e._ctx)
+        return {name: int(getattr(st, name)) for name, _ in st._fields_}
 
     def submit(self, frame) -> None:
         """Copy one frame (in_bytes u8) into a free slot's page-locked buffer and queue it; SrError(SR_E_INVALID) if none is free."""

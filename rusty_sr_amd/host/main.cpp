@@ -4,7 +4,7 @@
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
 //   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] [--loss LOSS] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] [--degrade SPEC [--seed N]] <VALIDATION_FOLDER>
-//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709|bt2020] [--depth 8|auto] [--siting center|left] [--slots N] [--timing] <IN|-> <OUT|->
+//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709|bt2020] [--depth 8|auto] [--siting center|left] [--slots N] [--reuse] [--timing] <IN|-> <OUT|->
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
 // PSNR a parameter set reaches on a folder of HR images.  `video` upscales a YUV4MPEG2 stream frame by frame (y4m.hpp; the reference has
@@ -415,6 +415,7 @@ int run_validate(int argc, char** argv) {
             if (v.empty() || r.ec != std::errc() || r.ptr != v.data() + v.size()) validate_usage_error("'" + v + "' isn't a valid value for '--seed <N>'");
             has_seed = true;
         }
+        else if (a == "--reuse") validate_usage_error("The argument '--reuse' can only be used with the 'video' subcommand");
         else if (a.size() > 1 && a[0] == '-') validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (has_folder) validate_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else { folder = a; has_folder = true; }
@@ -866,6 +867,7 @@ int run_train(int argc, char** argv) {
         else if (a == "--resume") resume = true;
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             train_usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
+        else if (a == "--reuse") train_usage_error("The argument '--reuse' can only be used with the 'video' subcommand");
         else if (a.size() > 1 && a[0] == '-') train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else if (pos.size() == 2) train_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
@@ -1295,12 +1297,14 @@ const char kVideoHelp[] =
     "        --depth <BITS>               [values: 8, auto]  8 (default): 8-bit streams only; auto: the stream's own depth\n"
     "        --siting <SITING>            [values: center, left]  chroma siting of a deep 4:2:0 / 4:2:2 stream (default: left)\n"
     "        --slots <N>                  frames in flight [1..8], default 3\n"
+    "        --reuse                      compute only the rows that changed since the last frame (letterbox bars, held\n"
+    "                                     frames, screen recordings); the output is byte for byte the same\n"
     "        --timing                     print frames and ms/frame to stderr\n";
 
 int run_video(int argc, char** argv) {
     std::vector<std::string> pos;
     std::string parameters, custom, precision = "f32", matrix, depth_arg = "8", siting;
-    bool has_p = false, has_c = false, timing = false;
+    bool has_p = false, has_c = false, timing = false, reuse = false;
     long device = 0, slots = 3;
     unsigned ensemble = 0;
     for (int k = 2; k < argc; ++k) {
@@ -1314,6 +1318,7 @@ int run_video(int argc, char** argv) {
         else if (a == "-c" || a == "--custom") { custom = value("--custom <PARAMETER_FILE>"); has_c = true; }
         else if (a == "--precision") precision = value("--precision <MODE>");
         else if (a == "--timing") timing = true;
+        else if (a == "--reuse") reuse = true;
         else if (a == "--device") {
             const std::string v = value("--device <N>");
             if (!parse_count(v, device) || device < 0) video_usage_error("'" + v + "' isn't a valid value for '--device <N>'");
@@ -1399,6 +1404,7 @@ int run_video(int argc, char** argv) {
     rc = deep ? sr_video_create16(ctx, &fmt16, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid)
               : sr_video_create(ctx, &fmt, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid);
     if (rc != SR_OK) die(sr_strerror(rc));
+    if (reuse && (rc = sr_video_set_reuse(vid, SR_VIDEO_REUSE_ROWS)) != SR_OK) die(sr_strerror(rc));
     const size_t in_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, hd.h, hd.w) : sr_yuv_frame_bytes(&fmt, hd.h, hd.w);
     const size_t out_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, SR_FACTOR * hd.h, SR_FACTOR * hd.w) : sr_yuv_frame_bytes(&fmt, SR_FACTOR * hd.h, SR_FACTOR * hd.w);
 
@@ -1435,6 +1441,8 @@ int run_video(int argc, char** argv) {
     }
     while (sr_video_pending(vid) > 0) write_oldest();  // (also before a failure is reported: the frames before it are written)
     const double ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    sr_video_reuse_stats reused{};
+    if (reuse) (void)sr_video_get_reuse_stats(vid, &reused);
     sr_video_destroy(vid);
     sr_destroy(ctx);
     if (fout != stdout) wrote = fclose(fout) == 0 && wrote;
@@ -1443,6 +1451,10 @@ int run_video(int argc, char** argv) {
     if (!wrote) die("Could not write output stream " + pos[1]);
     if (!failure.empty()) die(failure);
     if (timing) fprintf(stderr, "[timing] frames %ld, %.2f ms/frame\n", frames, frames ? ms / frames : 0.0);
+    if (timing && reuse)
+        fprintf(stderr, "[timing] reuse: %llu frames whole, %llu partial, %llu reused, %.1f %% of rows computed\n", (unsigned long long)reused.frames_full,
+                (unsigned long long)reused.frames_partial, (unsigned long long)reused.frames_reused,
+                reused.rows_total ? 100.0 * (double)reused.rows_computed / (double)reused.rows_total : 0.0);
     return 0;
 }
 }  // namespace
@@ -1551,6 +1563,7 @@ int main(int argc, char** argv) {
         else if (a == "--degrade") usage_error("The argument '--degrade' can only be used with the 'train' and 'validate' subcommands");
         else if (a == "--metrics" || a == "--shave" || a.rfind("--shave=", 0) == 0)
             usage_error("The argument '" + a.substr(0, a.find('=')) + "' can only be used with the 'validate' subcommand");
+        else if (a == "--reuse") usage_error("The argument '--reuse' can only be used with the 'video' subcommand");
         else if (a.size() > 1 && a[0] == '-') usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
         else pos.push_back(a);
     }
