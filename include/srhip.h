@@ -247,7 +247,12 @@ int sr_upscale_sharded_rgba8_all(sr_ctx* const* ctxs, int n, const uint8_t* cons
  *                              host-pointer entry points (sr_upscale_f32 / _rgba8 and their _multi / _batch_multi forms) then
  *                              compute the whole call again in SR_PRECISION_F32 and return its result;
  *                            - the asynchronous *_dev entry points cannot: their output is unspecified where the overflow
- *                              reached, and the context keeps a fault that sr_check_domain reports. */
+ *                              reached, and the context keeps a fault that sr_check_domain reports.
+ * sr_set_precision is host-side state and no device work, like sr_set_loss: a call reads the mode when it is QUEUED and passes what follows
+ * from it to its launches by value, so the mode may be changed while earlier *_dev calls are still in flight on the caller's stream --
+ * nothing waits, the calls already queued keep their mode, and the feature-map borders that the other layout needs are cleared by the
+ * next call, on that call's stream and in its place there (tests/test_gpu_stream_order.py queues both changes between calls behind a
+ * delay).  Not so sr_set_params, which rewrites device memory that calls in flight read: synchronise first, as it says. */
 enum sr_precision { SR_PRECISION_F32 = 0, SR_PRECISION_SPLIT_F16 = 1 };
 int sr_set_precision(sr_ctx* ctx, int mode);
 /* After the stream(s) of earlier *_dev calls have been synchronised: SR_E_DOMAIN if any of them left the domain of

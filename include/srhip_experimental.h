@@ -41,6 +41,9 @@ extern "C" {
  * takes min(automatic grid, N) workgroups.  The kernels walk their tiles / items with the grid as stride, so a small N reaches their
  * multi-round paths (carries of the item counter, the prefetch of the next round) at tiny shapes and on any CU count; host side only, no
  * output byte depends on it.  Anything but "" or a positive integer: SR_E_INVALID.  (No environment default.)
+ * Every key is host-side state that a call reads when it is QUEUED (launch arguments travel by value): a switch may be set while earlier
+ * *_dev calls are still in flight on the caller's stream -- nothing waits, and the calls already queued keep the plan they were queued
+ * with (tests/test_gpu_stream_order.py changes "fork", "th" and "pipe" between queued calls).
  * Defaults come from SRHIP_WINO / SRHIP_TH / SRHIP_TAIL / SRHIP_PIPE / SRHIP_BW / SRHIP_BANDS / SRHIP_ROWS / SRHIP_GEO / SRHIP_HALO, read once in sr_create.
  * Unknown key: SR_E_INVALID. */
 int sr_set_experiment(sr_ctx* ctx, const char* key, const char* value);
