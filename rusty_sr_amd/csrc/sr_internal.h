@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "sr_plan.h"  // (and with it include/srhip.h)
+#include "sr_yuv_rule.h"
 
 // 16-channel halves of conv5 (stage 2's 3x3 source) that the exact mode runs as Winograd F(2,3) rows by default: 1.  Both halves would take
 // the whole call's direct-FLOP rate to within 1 % of the f32 roof on the fastest boxes, which bench.py's contract asserts it stays below
@@ -567,29 +568,17 @@ hipError_t sr_launch_degrade(const sr_degrade_one& a, const double* d_tab, uint8
 hipError_t sr_launch_train_degrade(sr_train_degrade_args a, uint32_t* d_batch, float* d_x, const float* d_ftab, const double* d_tab,
                                    hipStream_t s);
 
-// ---- video (sr_yuv.hip kernels, sr_yuv.cpp host side; include/srhip.h "Video")
-// A format as the kernels take it: the rule's constants, each formed once on the host in f64 by the single operations tests/yuv_ref.py
-// writes (the kernels divide nowhere).
-struct sr_yuv_rule {
-    int sub420, left;               // 4:2:0 (else 4:4:4); chroma horizontally co-sited with the even columns (else centred)
-    double kr, kb, kg;              // the matrix; kg = 1 - kr - kb
-    double cr2, cb2, ir, ib, ig;    // 2 (1 - kr), 2 (1 - kb) and their reciprocals, 1 / kg
-    double oy, sy, sc;              // YCbCr -> RGB: y = (Y - oy) sy, c = (C - 128) sc
-    double ky, kc;                  // RGB -> YCbCr: Y' = oy + ky y, C' = 128 + kc c
-    double ylo, yhi, clo, chi;      // the range's limits
-};
-bool sr_yuv_rule_make(const sr_yuv_format* f, sr_yuv_rule* out);  // false: a null format or an enum outside its values
-inline size_t sr_yuv_rule_frame_bytes(const sr_yuv_rule& k, int h, int w) {
-    const size_t ch = k.sub420 ? ((size_t)h + 1) / 2 : (size_t)h, cw = k.sub420 ? ((size_t)w + 1) / 2 : (size_t)w;
-    return (size_t)h * w + 2 * ch * cw;
-}
-// workgroups of either launch for n frames of h x w luma samples (0: an empty shape), functions of the shape alone; the launchers refuse
+// ---- video and deep video (sr_yuv.hip kernels, sr_yuv.cpp host side; include/srhip.h "Video", "Deep video")
+// The format as the kernels take it, its two validators and its frame size: sr_yuv_rule.h (no HIP).
+// workgroups of either launch for n frames of h x w luma samples (0: an empty shape), a function of the shape alone; the launchers refuse
 // more than INT32_MAX
-size_t sr_yuv_to_rgb_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
-size_t sr_rgb_to_yuv_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
-// n frames at d_yuv (any byte) -> n x h x w x 3 f32 at d_rgb (4-byte aligned), and back
-hipError_t sr_launch_yuv_to_rgb(const uint8_t* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s);
-hipError_t sr_launch_rgb_to_yuv(const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s);
+size_t sr_yuv_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+// n frames of samples S = uint8_t | uint16_t at d_yuv (aligned to a sample) -> n x h x w x 3 f32 at d_rgb (4-byte aligned), and back;
+// a uint8_t launch of a 4:2:2 rule is hipErrorInvalidValue
+template <class S>
+hipError_t sr_launch_yuv_to_rgb(const S* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s);
+template <class S>
+hipError_t sr_launch_rgb_to_yuv(const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, S* d_yuv, hipStream_t s);
 // The row compare of the frame stream's row reuse (sr_reuse.hip): flags[r] = 1 where row r differs between a and b, else 0.  The rows
 // are those of n_seg (1..3) segments one after another -- a frame's planes -- each `rows` rows of `row_bytes` contiguous bytes that
 // begin `offset` bytes into a and into b; rows_total is their sum.  a, b: any byte; flags: 4-byte aligned.
@@ -605,30 +594,6 @@ size_t sr_rows_differ_blocks(size_t rows_total);  // workgroups of the launch: a
 hipError_t sr_launch_rows_differ(const sr_rows_differ_args& a, hipStream_t s);
 void sr_yuv_release(sr_ctx* c);        // free the two buffers (called by sr_destroy)
 void sr_video_detach_all(sr_ctx* c);   // called by sr_destroy; a detached stream refuses every call but sr_video_destroy
-
-// ---- deep video (sr_yuv16.hip kernels, sr_yuv.cpp host side; include/srhip.h "Deep video")
-// A deep format as the kernels take it: the constants of tests/yuv16_ref.py, the depth folded into them, each formed once on the host
-// in f64 by a single operation (the kernels divide nowhere).
-struct sr_yuv16_rule {
-    int sub, left;                  // SR_YUV_420 | SR_YUV_444 | SR_YUV_422; chroma horizontally co-sited with the even columns (else centred)
-    double kr, kb, kg;              // the matrix; kg = 1 - kr - kb
-    double cr2, cb2, ir, ib, ig;    // 2 (1 - kr), 2 (1 - kb) and their reciprocals, 1 / kg
-    double oy, mid, sy, sc;         // YCbCr -> RGB: y = (Y - oy) sy, c = (C - mid) sc
-    double ky, kc;                  // RGB -> YCbCr: Y' = oy + ky y, C' = mid + kc c
-    double ylo, yhi, clo, chi;      // the range's limits
-};
-bool sr_yuv16_rule_make(const sr_yuv16_format* f, sr_yuv16_rule* out);  // false: a null format, an enum outside its values, a depth outside 9..16
-inline size_t sr_yuv16_rule_frame_samples(const sr_yuv16_rule& k, int h, int w) {
-    const size_t ch = k.sub == SR_YUV_420 ? ((size_t)h + 1) / 2 : (size_t)h, cw = k.sub == SR_YUV_444 ? (size_t)w : ((size_t)w + 1) / 2;
-    return (size_t)h * w + 2 * ch * cw;
-}
-// workgroups of either launch for n frames of h x w luma samples (0: an empty shape), functions of the shape alone; the launchers refuse
-// more than INT32_MAX
-size_t sr_yuv16_to_rgb_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
-size_t sr_rgb_to_yuv16_blocks(int n, int h, int w, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
-// n frames at d_yuv (2-byte aligned) -> n x h x w x 3 f32 at d_rgb (4-byte aligned), and back
-hipError_t sr_launch_yuv16_to_rgb(const uint16_t* d_yuv, const sr_yuv16_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s);
-hipError_t sr_launch_rgb_to_yuv16(const float* d_rgb, const sr_yuv16_rule& k, int n, int h, int w, uint16_t* d_yuv, hipStream_t s);
 
 // ---- deep colour (sr_deep.hip kernels, sr_deep.cpp host side; include/srhip.h "Deep colour")
 // workgroups of either launch for npx pixels (0: none): a function of the pixel count alone; the launchers refuse more than INT32_MAX

@@ -1,11 +1,11 @@
-// sr_yuv.cpp -- the video path (include/srhip.h "Video"): the two colour conversions as entry points, the composed call
+// sr_yuv.cpp -- the video path (include/srhip.h "Video", "Deep video"): the two colour conversions as entry points, the composed call
 //     YCbCr frame -> f32 RGB -> network (sr_net_queue: the plain or the ensemble call's path) -> f32 RGB -> YCbCr frame, quantised once,
 // and the frame stream, which keeps that call in flight for a ring of slots.  Kernels: sr_yuv.hip.  The composed calls are their checks,
 // their sizes and a work lambda; the stream is the one thing here the scaffold has no form for: a call that returns
-// before its work is done.  The deep video path (include/srhip.h "Deep video"; kernels: sr_yuv16.hip) is the
-// same three things on frames of uint16 samples with a format struct of its own; a session of either kind is one sr_video.  Row reuse
-// (sr_video_set_reuse; the compare kernel: sr_reuse.hip, the planner: sr_plan.cpp) is a session's opt-in: it computes the
-// row bands a changed input row can reach and takes the other rows from the last frame's output.
+// before its work is done.  Frames of bytes and deep frames of uint16 samples are one path, templated on
+// the sample type S; the two format structs meet in one sr_yuv_rule (sr_yuv_rule.h), and a session of either kind is one sr_video.  Row
+// reuse (sr_video_set_reuse; the compare kernel: sr_reuse.hip, the planner: sr_plan.cpp) is a session's opt-in: it
+// computes the row bands a changed input row can reach and takes the other rows from the last frame's output.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,94 +17,75 @@ namespace {
 constexpr size_t kPxF = 3 * sizeof(float);
 constexpr int kSideMax = INT32_MAX / 4;  // a side of a frame the conversions take: their column arithmetic is int
 
-const char* form_name(const sr_yuv_rule& k) { return !k.sub420 ? "444" : k.left ? "420left" : "420center"; }
+// what a sample type's launches are called in the plan record, and the pixels its to-RGB line names (the kernel's input's for bytes,
+// the f32 side for deep samples); its frames are aligned to alignof(S)
+template <class S>
+struct Ops;
+template <>
+struct Ops<uint8_t> {
+    static constexpr const char *to_rgb = "yuv2rgb", *to_yuv = "rgb2yuv";
+    static constexpr bool to_rgb_f32 = false;
+};
+template <>
+struct Ops<uint16_t> {
+    static constexpr const char *to_rgb = "yuv16_to_rgb", *to_yuv = "rgb_to_yuv16";
+    static constexpr bool to_rgb_f32 = true;
+};
 
-int check_frames(int n, int h, int w) {
-    return n >= 1 && h >= 1 && w >= 1 && h <= kSideMax && w <= kSideMax ? SR_OK : SR_E_INVALID;
-}
-
-// either launch queued on s, with its "op" line in the plan record: the grid the launcher itself takes
-int queue_to_rgb(sr_ctx* c, const uint8_t* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s) {
-    unsigned bx = 0, by = 0;
-    if (sr_yuv_to_rgb_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    HIPCHK(c, sr_launch_yuv_to_rgb(d_yuv, k, n, h, w, d_rgb, s));
-    sr_plan_note_op(c, "yuv2rgb", false, n, bx, by, form_name(k));
-    return SR_OK;
-}
-
-int queue_to_yuv(sr_ctx* c, const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_yuv, hipStream_t s) {
-    unsigned bx = 0, by = 0;
-    if (sr_rgb_to_yuv_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    HIPCHK(c, sr_launch_rgb_to_yuv(d_rgb, k, n, h, w, d_yuv, s));
-    sr_plan_note_op(c, "rgb2yuv", true, n, bx, by, form_name(k));
-    return SR_OK;
-}
-
-// everything the composed calls and the frame stream refuse for their context, format, shape and mask alone
-int check_upscale_shape(const sr_ctx* c, const sr_yuv_format* fmt, int n, int h, int w, unsigned members, sr_yuv_rule* k) {
-    SRCHK(sr_net_check_shape(c, n, h, w, members));
-    if (!sr_yuv_rule_make(fmt, k)) return SR_E_INVALID;
-    if (h > kSideMax / c->factor || w > kSideMax / c->factor) return SR_E_INVALID;
-    return SR_OK;
-}
-
-// ... and for their two frame pointers
-int check_upscale_args(const sr_ctx* c, const void* in, const sr_yuv_format* fmt, int n, int h, int w, const void* out, unsigned members,
-                       sr_yuv_rule* k) {
-    if (!in || !out) return SR_E_INVALID;
-    return check_upscale_shape(c, fmt, n, h, w, members, k);
-}
-
-// to RGB -> network -> from RGB on device buffers, queued on s; the arguments are checked and the context's device is current
-int queue_upscale(sr_ctx* c, const uint8_t* d_in, const sr_yuv_rule& k, int n, int h, int w, uint8_t* d_out, unsigned members, hipStream_t s) {
-    const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;
-    if (out_img / kPxF / (f * w) != f * h || out_img > SIZE_MAX / (size_t)n) return SR_E_NOMEM;
-    SRCHK(sr_reserve_bufs(c, {{&c->d_yrgb, (size_t)n * in_img}, {&c->d_ynet, (size_t)n * out_img}}));
-    SRCHK(queue_to_rgb(c, d_in, k, n, h, w, (float*)c->d_yrgb.p, s));
-    SRCHK(sr_net_queue(c, c->d_yrgb.p, false, 3, n, h, w, c->d_ynet.p, false, members, s));
-    return queue_to_yuv(c, (const float*)c->d_ynet.p, k, n, (int)f * h, (int)f * w, d_out, s);
-}
-
-// ---- the deep forms of the above: frames of uint16 samples, sr_yuv16_rule
-const char* form_name(const sr_yuv16_rule& k) {
+const char* form_name(const sr_yuv_rule& k) {
     if (k.sub == SR_YUV_444) return "444";
     if (k.sub == SR_YUV_422) return k.left ? "422left" : "422center";
     return k.left ? "420left" : "420center";
 }
 
-bool sample_aligned(const void* p) { return ((uintptr_t)p & 1u) == 0; }
+int check_frames(int n, int h, int w) {
+    return n >= 1 && h >= 1 && w >= 1 && h <= kSideMax && w <= kSideMax ? SR_OK : SR_E_INVALID;
+}
 
-int queue_to_rgb(sr_ctx* c, const uint16_t* d_yuv, const sr_yuv16_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s) {
+template <class S>
+bool sample_aligned(const void* p) { return ((uintptr_t)p & (alignof(S) - 1)) == 0; }
+
+bool rule_make(const sr_yuv_format* f, sr_yuv_rule* k) { return sr_yuv_rule_make(f, k); }
+bool rule_make(const sr_yuv16_format* f, sr_yuv_rule* k) { return sr_yuv16_rule_make(f, k); }
+
+// either launch queued on s, with its "op" line in the plan record: the grid the launcher itself takes
+template <class S>
+int queue_to_rgb(sr_ctx* c, const S* d_yuv, const sr_yuv_rule& k, int n, int h, int w, float* d_rgb, hipStream_t s) {
     unsigned bx = 0, by = 0;
-    if (sr_yuv16_to_rgb_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    HIPCHK(c, sr_launch_yuv16_to_rgb(d_yuv, k, n, h, w, d_rgb, s));
-    sr_plan_note_op(c, "yuv16_to_rgb", true, n, bx, by, form_name(k));
+    if (sr_yuv_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_yuv_to_rgb(d_yuv, k, n, h, w, d_rgb, s));
+    sr_plan_note_op(c, Ops<S>::to_rgb, Ops<S>::to_rgb_f32, n, bx, by, form_name(k));
     return SR_OK;
 }
 
-int queue_to_yuv(sr_ctx* c, const float* d_rgb, const sr_yuv16_rule& k, int n, int h, int w, uint16_t* d_yuv, hipStream_t s) {
+template <class S>
+int queue_to_yuv(sr_ctx* c, const float* d_rgb, const sr_yuv_rule& k, int n, int h, int w, S* d_yuv, hipStream_t s) {
     unsigned bx = 0, by = 0;
-    if (sr_rgb_to_yuv16_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    HIPCHK(c, sr_launch_rgb_to_yuv16(d_rgb, k, n, h, w, d_yuv, s));
-    sr_plan_note_op(c, "rgb_to_yuv16", true, n, bx, by, form_name(k));
+    if (sr_yuv_blocks(n, h, w, &bx, &by) > (size_t)INT32_MAX) return SR_E_NOMEM;
+    HIPCHK(c, sr_launch_rgb_to_yuv(d_rgb, k, n, h, w, d_yuv, s));
+    sr_plan_note_op(c, Ops<S>::to_yuv, true, n, bx, by, form_name(k));
     return SR_OK;
 }
 
-int check_upscale_shape(const sr_ctx* c, const sr_yuv16_format* fmt, int n, int h, int w, unsigned members, sr_yuv16_rule* k) {
+// everything the composed calls and the frame stream refuse for their context, format, shape and mask alone
+template <class Format>
+int check_upscale_shape(const sr_ctx* c, const Format* fmt, int n, int h, int w, unsigned members, sr_yuv_rule* k) {
     SRCHK(sr_net_check_shape(c, n, h, w, members));
-    if (!sr_yuv16_rule_make(fmt, k)) return SR_E_INVALID;
+    if (!rule_make(fmt, k)) return SR_E_INVALID;
     if (h > kSideMax / c->factor || w > kSideMax / c->factor) return SR_E_INVALID;
     return SR_OK;
 }
 
-int check_upscale_args(const sr_ctx* c, const void* in, const sr_yuv16_format* fmt, int n, int h, int w, const void* out, unsigned members,
-                       sr_yuv16_rule* k) {
-    if (!in || !out || !sample_aligned(in) || !sample_aligned(out)) return SR_E_INVALID;
+// ... and for their two frame pointers
+template <class S, class Format>
+int check_upscale_args(const sr_ctx* c, const S* in, const Format* fmt, int n, int h, int w, const S* out, unsigned members, sr_yuv_rule* k) {
+    if (!in || !out || !sample_aligned<S>(in) || !sample_aligned<S>(out)) return SR_E_INVALID;
     return check_upscale_shape(c, fmt, n, h, w, members, k);
 }
 
-// the same workspace as the 8-bit call's: both hold f32 RGB
-int queue_upscale(sr_ctx* c, const uint16_t* d_in, const sr_yuv16_rule& k, int n, int h, int w, uint16_t* d_out, unsigned members, hipStream_t s) {
+// to RGB -> network -> from RGB on device buffers, queued on s; the arguments are checked and the context's device is current
+template <class S>
+int queue_upscale(sr_ctx* c, const S* d_in, const sr_yuv_rule& k, int n, int h, int w, S* d_out, unsigned members, hipStream_t s) {
     const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;
     if (out_img / kPxF / (f * w) != f * h || out_img > SIZE_MAX / (size_t)n) return SR_E_NOMEM;
     SRCHK(sr_reserve_bufs(c, {{&c->d_yrgb, (size_t)n * in_img}, {&c->d_ynet, (size_t)n * out_img}}));
@@ -113,72 +94,57 @@ int queue_upscale(sr_ctx* c, const uint16_t* d_in, const sr_yuv16_rule& k, int n
     return queue_to_yuv(c, (const float*)c->d_ynet.p, k, n, (int)f * h, (int)f * w, d_out, s);
 }
 
+// ---- the entry points of either sample type
+template <class Format>
+size_t frame_bytes(const Format* fmt, int h, int w, size_t sample) {
+    sr_yuv_rule k;
+    if (!rule_make(fmt, &k) || h < 1 || w < 1) return 0;
+    const size_t samples = sr_yuv_rule_frame_samples(k, h, w);
+    return samples > SIZE_MAX / sample ? 0 : sample * samples;
+}
+
+template <class S, class Format>
+int to_rgb_dev(sr_ctx* c, const S* d_yuv, const Format* fmt, int n, int h, int w, float* d_rgb, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    if (!c || !d_yuv || !d_rgb || !rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    if (!sr_dword_aligned(d_rgb) || !sample_aligned<S>(d_yuv)) return SR_E_INVALID;
+    return sr_on_device(c, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
+}
+
+template <class S, class Format>
+int to_yuv_dev(sr_ctx* c, const float* d_rgb, const Format* fmt, int n, int h, int w, S* d_yuv, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    if (!c || !d_yuv || !d_rgb || !rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    if (!sr_dword_aligned(d_rgb) || !sample_aligned<S>(d_yuv)) return SR_E_INVALID;
+    return sr_on_device(c, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
+}
+
+template <class S, class Format>
+int upscale_dev(sr_ctx* c, const S* d_in, const Format* fmt, int n, int h, int w, S* d_out, unsigned members, void* stream) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    SRCHK(check_upscale_args(c, d_in, fmt, n, h, w, (const S*)d_out, members, &k));
+    return sr_on_device(c, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
+}
+
+template <class S, class Format>
+int upscale_host(sr_ctx* c, const S* in, const Format* fmt, int n, int h, int w, S* out, unsigned members) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    SRCHK(check_upscale_args(c, in, fmt, n, h, w, (const S*)out, members, &k));
+    const int f = c->factor;
+    const size_t in_bytes = (size_t)n * sizeof(S) * sr_yuv_rule_frame_samples(k, h, w);
+    const size_t out_bytes = (size_t)n * sizeof(S) * sr_yuv_rule_frame_samples(k, f * h, f * w);
+    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return queue_upscale(c, (const S*)d_in, k, n, h, w, (S*)d_out, members, s);
+    });
+}
+
 }  // namespace
-
-bool sr_yuv16_rule_make(const sr_yuv16_format* f, sr_yuv16_rule* out) {
-    if (!f) return false;
-    if (f->subsampling != SR_YUV_420 && f->subsampling != SR_YUV_444 && f->subsampling != SR_YUV_422) return false;
-    if (f->siting != SR_YUV_SITING_CENTER && f->siting != SR_YUV_SITING_LEFT) return false;
-    if (f->matrix != SR_YUV_BT601 && f->matrix != SR_YUV_BT709 && f->matrix != SR_YUV_BT2020) return false;
-    if (f->range != SR_YUV_LIMITED && f->range != SR_YUV_FULL) return false;
-    if (f->depth < 9 || f->depth > 16) return false;
-    sr_yuv16_rule k{};
-    const bool full = f->range == SR_YUV_FULL;
-    k.sub = f->subsampling;
-    k.left = k.sub != SR_YUV_444 && f->siting == SR_YUV_SITING_LEFT;
-    k.kr = f->matrix == SR_YUV_BT2020 ? 0.2627 : f->matrix == SR_YUV_BT709 ? 0.2126 : 0.299;
-    k.kb = f->matrix == SR_YUV_BT2020 ? 0.0593 : f->matrix == SR_YUV_BT709 ? 0.0722 : 0.114;
-    k.kg = 1.0 - k.kr - k.kb;
-    k.cr2 = 2.0 * (1.0 - k.kr);
-    k.cb2 = 2.0 * (1.0 - k.kb);
-    k.ir = 1.0 / k.cr2;
-    k.ib = 1.0 / k.cb2;
-    k.ig = 1.0 / k.kg;
-    const double s = (double)(1 << (f->depth - 8)), top = (double)(1 << f->depth) - 1.0;  // powers of two: exact
-    k.oy = full ? 0.0 : 16.0 * s;
-    k.ky = full ? top : 219.0 * s;
-    k.kc = full ? top : 224.0 * s;
-    k.mid = full ? (double)(1 << (f->depth - 1)) : 128.0 * s;
-    k.sy = 1.0 / k.ky;
-    k.sc = 1.0 / k.kc;
-    k.ylo = full ? 0.0 : 16.0 * s;
-    k.yhi = full ? top : 235.0 * s;
-    k.clo = full ? 0.0 : 16.0 * s;
-    k.chi = full ? top : 240.0 * s;
-    *out = k;
-    return true;
-}
-
-bool sr_yuv_rule_make(const sr_yuv_format* f, sr_yuv_rule* out) {
-    if (!f) return false;
-    if (f->subsampling != SR_YUV_420 && f->subsampling != SR_YUV_444) return false;
-    if (f->siting != SR_YUV_SITING_CENTER && f->siting != SR_YUV_SITING_LEFT) return false;
-    if (f->matrix != SR_YUV_BT601 && f->matrix != SR_YUV_BT709) return false;
-    if (f->range != SR_YUV_LIMITED && f->range != SR_YUV_FULL) return false;
-    sr_yuv_rule k{};
-    const bool full = f->range == SR_YUV_FULL;
-    k.sub420 = f->subsampling == SR_YUV_420;
-    k.left = k.sub420 && f->siting == SR_YUV_SITING_LEFT;
-    k.kr = f->matrix == SR_YUV_BT709 ? 0.2126 : 0.299;
-    k.kb = f->matrix == SR_YUV_BT709 ? 0.0722 : 0.114;
-    k.kg = 1.0 - k.kr - k.kb;
-    k.cr2 = 2.0 * (1.0 - k.kr);
-    k.cb2 = 2.0 * (1.0 - k.kb);
-    k.ir = 1.0 / k.cr2;
-    k.ib = 1.0 / k.cb2;
-    k.ig = 1.0 / k.kg;
-    k.oy = full ? 0.0 : 16.0;
-    k.ky = full ? 255.0 : 219.0;
-    k.kc = full ? 255.0 : 224.0;
-    k.sy = 1.0 / k.ky;
-    k.sc = 1.0 / k.kc;
-    k.ylo = full ? 0.0 : 16.0;
-    k.yhi = full ? 255.0 : 235.0;
-    k.clo = full ? 0.0 : 16.0;
-    k.chi = full ? 255.0 : 240.0;
-    *out = k;
-    return true;
-}
 
 void sr_yuv_release(sr_ctx* c) {
     sr_free_buf(c->d_yrgb);
@@ -190,8 +156,7 @@ struct sr_video {
     sr_ctx* c = nullptr;  // nullptr: detached by sr_destroy
     bool failed = false;  // a recomputation in exact f32 could not be queued: what is in flight is lost, every call but destroy is refused
     sr_yuv_rule k{};
-    bool deep = false;    // made by sr_video_create16: the frames are uint16 samples and the format is k16
-    sr_yuv16_rule k16{};
+    size_t sample = 1;    // bytes of a sample: 2 made by sr_video_create16
     int h = 0, w = 0, slots = 0;
     unsigned members = 1;
     size_t in_bytes = 0, out_bytes = 0;
@@ -234,17 +199,19 @@ struct Planes {
     size_t total_rows() const { return rows[0] + rows[1] + rows[2]; }
 };
 
-int video_subsampling(const sr_video* v) { return v->deep ? v->k16.sub : v->k.sub420 ? SR_YUV_420 : SR_YUV_444; }
-
 Planes video_planes(const sr_video* v, size_t H, size_t W) {
-    const int sub = video_subsampling(v);
-    const size_t bps = v->deep ? 2 : 1, ch = sub == SR_YUV_420 ? (H + 1) / 2 : H, cw = sub == SR_YUV_444 ? W : (W + 1) / 2;
+    size_t ch, cw;
+    sr_yuv_rule_chroma(v->k, H, W, &ch, &cw);
     Planes p{};
-    p.vsub = sub == SR_YUV_420;
-    p.rows[0] = H; p.row_bytes[0] = W * bps; p.offset[0] = 0;
-    for (int k = 1; k < 3; ++k) { p.rows[k] = ch; p.row_bytes[k] = cw * bps; p.offset[k] = p.offset[k - 1] + p.rows[k - 1] * p.row_bytes[k - 1]; }
+    p.vsub = v->k.sub == SR_YUV_420;
+    p.rows[0] = H; p.row_bytes[0] = W * v->sample; p.offset[0] = 0;
+    for (int k = 1; k < 3; ++k) { p.rows[k] = ch; p.row_bytes[k] = cw * v->sample; p.offset[k] = p.offset[k - 1] + p.rows[k - 1] * p.row_bytes[k - 1]; }
     return p;
 }
+
+// the typed call of a session: f(S{}) with S the session's sample type
+template <class F>
+int by_sample(const sr_video* v, F&& f) { return v->sample == 2 ? f(uint16_t{}) : f(uint8_t{}); }
 
 // the rows of plane k that belong to luma rows [a, b) of its frame: a is even; b is even or the frame's height
 void plane_rows(const Planes& p, int k, size_t a, size_t b, size_t* lo, size_t* hi) {
@@ -319,7 +286,7 @@ int reuse_plan(sr_video* v, sr_row_band bands[SR_REUSE_MAX_BANDS], int* n) {
     *n = 1;
     if (!v->have_ref) return SR_OK;
     HIPCHK(c, hipEventSynchronize(v->flags_down));  // the one host wait of the mode (what it costs: DESIGN.md 4v)
-    SRCHK(sr_video_reuse_plan(v->h_flags, video_subsampling(v), v->h, bands, SR_REUSE_MAX_BANDS, n));
+    SRCHK(sr_video_reuse_plan(v->h_flags, v->k.sub, v->h, bands, SR_REUSE_MAX_BANDS, n));
     if (*n > 0 && (v->members != 1u || c->graph != SR_GRAPH_SR_NET)) {
         bands[0] = {0, v->h};
         *n = 1;
@@ -351,14 +318,12 @@ int reuse_queue_bands(sr_video* v, const void* d_in, void* d_out, const void* d_
     if (n == 0) return SR_OK;
     float* rgb = (float*)c->d_yrgb.p;
     float* net = (float*)c->d_ynet.p;
-    if (v->deep) SRCHK(queue_to_rgb(c, (const uint16_t*)d_in, v->k16, 1, h, w, rgb, s));
-    else SRCHK(queue_to_rgb(c, (const uint8_t*)d_in, v->k, 1, h, w, rgb, s));
+    SRCHK(by_sample(v, [&](auto t) { return queue_to_rgb(c, (const decltype(t)*)d_in, v->k, 1, h, w, rgb, s); }));
     for (int i = 0; i < n; ++i) {
         const int y0 = bands[i].y0, y1 = bands[i].y1, top = y0 > 0 ? SR_HALO : 0, bot = y1 < h ? SR_HALO : 0, bh = f * (y1 - y0);
         float* band_net = net + (size_t)f * y0 * f * w * 3;
         SRCHK(sr_run_stack(c, rgb + (size_t)(y0 - top) * w * 3, false, 3, 1, top + (y1 - y0) + bot, w, top, bot, band_net, false, s));
-        if (v->deep) SRCHK(queue_to_yuv(c, band_net, v->k16, 1, bh, f * w, (uint16_t*)v->d_band, s));
-        else SRCHK(queue_to_yuv(c, band_net, v->k, 1, bh, f * w, (uint8_t*)v->d_band, s));
+        SRCHK(by_sample(v, [&](auto t) { return queue_to_yuv(c, band_net, v->k, 1, bh, f * w, (decltype(t)*)v->d_band, s); }));
         const Planes band = video_planes(v, (size_t)bh, (size_t)f * w);
         for (int k = 0; k < 3; ++k) {
             size_t lo, hi;
@@ -409,8 +374,10 @@ int video_queue(sr_video* v, unsigned long long frame, bool again = false) {
     }
     HIPCHK(c, hipStreamWaitEvent(c->stream, s.up, 0));
     if (n_bands == 1 && bands[0].y0 == 0 && bands[0].y1 == v->h) {
-        if (v->deep) SRCHK(queue_upscale(c, (const uint16_t*)s.d_in, v->k16, 1, v->h, v->w, (uint16_t*)s.d_out, v->members, c->stream));
-        else SRCHK(queue_upscale(c, (const uint8_t*)s.d_in, v->k, 1, v->h, v->w, (uint8_t*)s.d_out, v->members, c->stream));
+        SRCHK(by_sample(v, [&](auto t) {
+            using S = decltype(t);
+            return queue_upscale(c, (const S*)s.d_in, v->k, 1, v->h, v->w, (S*)s.d_out, v->members, c->stream);
+        }));
     } else {
         SRCHK(reuse_queue_bands(v, s.d_in, s.d_out, v->slot[(frame + (unsigned)v->slots - 1) % (unsigned)v->slots].d_out, bands, n_bands, c->stream));
     }
@@ -434,7 +401,7 @@ int video_queue(sr_video* v, unsigned long long frame, bool again = false) {
     return SR_OK;
 }
 
-int video_create(sr_video* v) {
+int video_alloc(sr_video* v) {
     sr_ctx* c = v->c;
     SRCHK(sr_ensure_streams(c, true));
     if (!c->copy_in) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
@@ -449,14 +416,25 @@ int video_create(sr_video* v) {
     return SR_OK;
 }
 
-// the rest of either create call: v holds its format and frame sizes; on failure it is freed
-int video_open(sr_ctx* c, sr_video* v, int h, int w, int slots, unsigned members, sr_video** out) {
+// either create call: a session of frames in `fmt` whose samples are `sample` bytes
+template <class Format>
+int video_create(sr_ctx* c, const Format* fmt, size_t sample, int h, int w, int slots, unsigned members, sr_video** out) {
+    sr_plan_clear(c);
+    if (out) *out = nullptr;
+    sr_yuv_rule k;
+    if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
+    SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
+    sr_video* v = new sr_video;
     v->c = c;
+    v->k = k;
+    v->sample = sample;
     v->h = h;
     v->w = w;
     v->slots = slots;
     v->members = members;
-    const int rc = sr_on_device(c, [&] { return video_create(v); });
+    v->in_bytes = sample * sr_yuv_rule_frame_samples(k, h, w);
+    v->out_bytes = sample * sr_yuv_rule_frame_samples(k, c->factor * h, c->factor * w);
+    const int rc = sr_on_device(c, [&] { return video_alloc(v); });
     if (rc != SR_OK) {
         video_free(v);
         delete v;
@@ -483,119 +461,44 @@ void sr_video_detach_all(sr_ctx* c) {
 
 extern "C" {
 
-size_t sr_yuv_frame_bytes(const sr_yuv_format* fmt, int h, int w) {
-    sr_yuv_rule k;
-    if (!sr_yuv_rule_make(fmt, &k) || h < 1 || w < 1) return 0;
-    return sr_yuv_rule_frame_bytes(k, h, w);
-}
+size_t sr_yuv_frame_bytes(const sr_yuv_format* fmt, int h, int w) { return frame_bytes(fmt, h, w, 1); }
+size_t sr_yuv16_frame_bytes(const sr_yuv16_format* fmt, int h, int w) { return frame_bytes(fmt, h, w, 2); }
 
 int sr_yuv_to_rgb_dev(sr_ctx* c, const uint8_t* d_yuv, const sr_yuv_format* fmt, int n, int h, int w, float* d_rgb, void* stream) {
-    sr_plan_clear(c);
-    sr_yuv_rule k;
-    if (!c || !d_yuv || !d_rgb || !sr_yuv_rule_make(fmt, &k)) return SR_E_INVALID;
-    SRCHK(check_frames(n, h, w));
-    if (!sr_dword_aligned(d_rgb)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
+    return to_rgb_dev(c, d_yuv, fmt, n, h, w, d_rgb, stream);
+}
+int sr_yuv16_to_rgb_dev(sr_ctx* c, const uint16_t* d_yuv, const sr_yuv16_format* fmt, int n, int h, int w, float* d_rgb, void* stream) {
+    return to_rgb_dev(c, d_yuv, fmt, n, h, w, d_rgb, stream);
 }
 
 int sr_rgb_to_yuv_dev(sr_ctx* c, const float* d_rgb, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* d_yuv, void* stream) {
-    sr_plan_clear(c);
-    sr_yuv_rule k;
-    if (!c || !d_yuv || !d_rgb || !sr_yuv_rule_make(fmt, &k)) return SR_E_INVALID;
-    SRCHK(check_frames(n, h, w));
-    if (!sr_dword_aligned(d_rgb)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
+    return to_yuv_dev(c, d_rgb, fmt, n, h, w, d_yuv, stream);
+}
+int sr_rgb_to_yuv16_dev(sr_ctx* c, const float* d_rgb, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_yuv, void* stream) {
+    return to_yuv_dev(c, d_rgb, fmt, n, h, w, d_yuv, stream);
 }
 
 int sr_upscale_yuv_dev(sr_ctx* c, const uint8_t* d_in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* d_out, unsigned members,
                        void* stream) {
-    sr_plan_clear(c);
-    sr_yuv_rule k;
-    SRCHK(check_upscale_args(c, d_in, fmt, n, h, w, d_out, members, &k));
-    return sr_on_device(c, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
+    return upscale_dev(c, d_in, fmt, n, h, w, d_out, members, stream);
+}
+int sr_upscale_yuv16_dev(sr_ctx* c, const uint16_t* d_in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_out, unsigned members,
+                         void* stream) {
+    return upscale_dev(c, d_in, fmt, n, h, w, d_out, members, stream);
 }
 
 int sr_upscale_yuv(sr_ctx* c, const uint8_t* in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, unsigned members) {
-    sr_plan_clear(c);
-    sr_yuv_rule k;
-    SRCHK(check_upscale_args(c, in, fmt, n, h, w, out, members, &k));
-    const int f = c->factor;
-    const size_t in_bytes = (size_t)n * sr_yuv_rule_frame_bytes(k, h, w), out_bytes = (size_t)n * sr_yuv_rule_frame_bytes(k, f * h, f * w);
-    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
-        return queue_upscale(c, (const uint8_t*)d_in, k, n, h, w, (uint8_t*)d_out, members, s);
-    });
+    return upscale_host(c, in, fmt, n, h, w, out, members);
+}
+int sr_upscale_yuv16(sr_ctx* c, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, unsigned members) {
+    return upscale_host(c, in, fmt, n, h, w, out, members);
 }
 
 int sr_video_create(sr_ctx* c, const sr_yuv_format* fmt, int h, int w, int slots, unsigned members, sr_video** out) {
-    sr_plan_clear(c);
-    if (out) *out = nullptr;
-    sr_yuv_rule k;
-    if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
-    SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
-    sr_video* v = new sr_video;
-    v->k = k;
-    v->in_bytes = sr_yuv_rule_frame_bytes(k, h, w);
-    v->out_bytes = sr_yuv_rule_frame_bytes(k, c->factor * h, c->factor * w);
-    return video_open(c, v, h, w, slots, members, out);
+    return video_create(c, fmt, 1, h, w, slots, members, out);
 }
-
 int sr_video_create16(sr_ctx* c, const sr_yuv16_format* fmt, int h, int w, int slots, unsigned members, sr_video** out) {
-    sr_plan_clear(c);
-    if (out) *out = nullptr;
-    sr_yuv16_rule k;
-    if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
-    SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
-    sr_video* v = new sr_video;
-    v->deep = true;
-    v->k16 = k;
-    v->in_bytes = 2 * sr_yuv16_rule_frame_samples(k, h, w);
-    v->out_bytes = 2 * sr_yuv16_rule_frame_samples(k, c->factor * h, c->factor * w);
-    return video_open(c, v, h, w, slots, members, out);
-}
-
-size_t sr_yuv16_frame_bytes(const sr_yuv16_format* fmt, int h, int w) {
-    sr_yuv16_rule k;
-    if (!sr_yuv16_rule_make(fmt, &k) || h < 1 || w < 1) return 0;
-    const size_t samples = sr_yuv16_rule_frame_samples(k, h, w);
-    return samples > SIZE_MAX / 2 ? 0 : 2 * samples;
-}
-
-int sr_yuv16_to_rgb_dev(sr_ctx* c, const uint16_t* d_yuv, const sr_yuv16_format* fmt, int n, int h, int w, float* d_rgb, void* stream) {
-    sr_plan_clear(c);
-    sr_yuv16_rule k;
-    if (!c || !d_yuv || !d_rgb || !sr_yuv16_rule_make(fmt, &k)) return SR_E_INVALID;
-    SRCHK(check_frames(n, h, w));
-    if (!sr_dword_aligned(d_rgb) || !sample_aligned(d_yuv)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
-}
-
-int sr_rgb_to_yuv16_dev(sr_ctx* c, const float* d_rgb, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_yuv, void* stream) {
-    sr_plan_clear(c);
-    sr_yuv16_rule k;
-    if (!c || !d_yuv || !d_rgb || !sr_yuv16_rule_make(fmt, &k)) return SR_E_INVALID;
-    SRCHK(check_frames(n, h, w));
-    if (!sr_dword_aligned(d_rgb) || !sample_aligned(d_yuv)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
-}
-
-int sr_upscale_yuv16_dev(sr_ctx* c, const uint16_t* d_in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* d_out, unsigned members,
-                         void* stream) {
-    sr_plan_clear(c);
-    sr_yuv16_rule k;
-    SRCHK(check_upscale_args(c, d_in, fmt, n, h, w, d_out, members, &k));
-    return sr_on_device(c, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
-}
-
-int sr_upscale_yuv16(sr_ctx* c, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, unsigned members) {
-    sr_plan_clear(c);
-    sr_yuv16_rule k;
-    SRCHK(check_upscale_args(c, in, fmt, n, h, w, out, members, &k));
-    const int f = c->factor;
-    const size_t in_bytes = (size_t)n * 2 * sr_yuv16_rule_frame_samples(k, h, w);
-    const size_t out_bytes = (size_t)n * 2 * sr_yuv16_rule_frame_samples(k, f * h, f * w);
-    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
-        return queue_upscale(c, (const uint16_t*)d_in, k, n, h, w, (uint16_t*)d_out, members, s);
-    });
+    return video_create(c, fmt, 2, h, w, slots, members, out);
 }
 
 int sr_video_acquire(sr_video* v, uint8_t** in_frame) {

@@ -441,48 +441,105 @@ class Engine:
                                                      self._stream_ptr(stream, x.device)), self._ctx)
         return out
 
-    # ---- video: planar 8-bit YCbCr frames, laid out like a Y4M frame payload (include/srhip.h "Video") ----
+    # ---- video: planar YCbCr frames laid out like a Y4M frame payload, of bytes (include/srhip.h "Video") or of 9..16-bit samples in
+    # uint16 (include/srhip.h "Deep video").  One set of helpers: `tag` is "yuv" or "yuv16", the word the library's symbols differ in ----
     @staticmethod
-    def _yuv_frames(frames, fmt, h, w):
-        """Host frames as a C-contiguous (n, frame_bytes) u8 array; squeeze: it was one frame (1-d)."""
-        fb = yuv_frame_bytes(fmt, h, w)
-        a = np.ascontiguousarray(frames, dtype=np.uint8)
+    def _yuv_kind(tag, fmt, h, w):
+        """(numpy sample type, the torch dtype of a new result, samples in a frame of h x w)."""
+        import torch
+        if tag == "yuv":
+            return np.uint8, torch.uint8, yuv_frame_bytes(fmt, h, w)
+        return np.uint16, torch.int16, yuv16_frame_bytes(fmt, h, w) // 2   # (int16 tensors hold the uint16 samples)
+
+    def _yuv_frames(self, tag, frames, fmt, h, w):
+        """Host frames as a C-contiguous (n, frame_samples) array of the sample type; squeeze: it was one frame (1-d)."""
+        dtype, _, fs = self._yuv_kind(tag, fmt, h, w)
+        a = np.ascontiguousarray(frames, dtype=dtype)
         squeeze = a.ndim == 1
-        if fb == 0 or a.ndim not in (1, 2) or a.shape[-1] != fb:
-            raise ValueError(f"expected frames of {fb} bytes")
+        if fs == 0 or a.ndim not in (1, 2) or a.shape[-1] != fs:
+            raise ValueError(f"expected frames of {fs} {'bytes' if tag == 'yuv' else 'samples'}")
         return (a[None] if squeeze else a), squeeze
 
-    @staticmethod
-    def _yuv_frames_dev(frames, fmt, h, w):
-        """A contiguous u8 tensor on the GPU, (n, frame_bytes) or (frame_bytes,): any byte offset within its allocation will do."""
-        import torch
-        fb = yuv_frame_bytes(fmt, h, w)
-        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() in (1, 2) and frames.shape[-1] == fb
+    def _yuv_frames_dev(self, tag, frames, fmt, h, w):
+        """A contiguous tensor of samples on the GPU (torch.uint8; deep: torch.uint16 or torch.int16), (n, frame_samples) or
+        (frame_samples,): any sample offset within its allocation will do."""
+        dtype, tdtype, fs = self._yuv_kind(tag, fmt, h, w)
+        assert frames.is_cuda and frames.is_contiguous() and frames.dim() in (1, 2) and frames.shape[-1] == fs
+        assert frames.dtype == tdtype if tag == "yuv" else frames.element_size() == 2
         return 1 if frames.dim() == 1 else frames.shape[0]
+
+    def _yuv_out_dev(self, tag, out, fmt, n, h, w, device):
+        """The caller's `out`, or a new (n, frame_samples) tensor for frames of h x w."""
+        import torch
+        dtype, tdtype, fs = self._yuv_kind(tag, fmt, h, w)
+        if out is None:
+            out = torch.empty((n, fs), dtype=tdtype, device=device)
+        assert out.is_cuda and out.element_size() == np.dtype(dtype).itemsize and out.is_contiguous() and out.numel() == n * fs
+        return out
+
+    def _yuv_to_rgb_dev(self, tag, frames, fmt, h, w, out, stream):
+        n = self._yuv_frames_dev(tag, frames, fmt, h, w)
+        out = self._dev_out(out, (n, h, w, 3), np.float32, frames.device)
+        _lib.check(getattr(self._L, f"sr_{tag}_to_rgb_dev")(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                                            self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def _rgb_to_yuv_dev(self, tag, x, fmt, out, stream):
+        n, h, w, _ = self._dev_batch(x, np.float32, 3)
+        out = self._yuv_out_dev(tag, out, fmt, n, h, w, x.device)
+        _lib.check(getattr(self._L, f"sr_rgb_to_{tag}_dev")(self._ctx, C.c_void_p(x.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                                            self._stream_ptr(stream, x.device)), self._ctx)
+        return out
+
+    def _upscale_yuv_dev(self, tag, frames, fmt, h, w, members, out, stream):
+        n = self._yuv_frames_dev(tag, frames, fmt, h, w)
+        out = self._yuv_out_dev(tag, out, fmt, n, self.factor * h, self.factor * w, frames.device)
+        _lib.check(getattr(self._L, f"sr_upscale_{tag}_dev")(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
+                                                             self._members(members), self._stream_ptr(stream, frames.device)), self._ctx)
+        return out
+
+    def _yuv_to_rgb(self, tag, frames, fmt, h, w):
+        import torch
+        a, squeeze = self._yuv_frames(tag, frames, fmt, h, w)
+        dev = torch.from_numpy(a if tag == "yuv" else a.view(np.int16)).to(f"cuda:{self.device}")
+        out = self._yuv_to_rgb_dev(tag, dev, fmt, h, w, None, None)
+        torch.cuda.synchronize(out.device)
+        out = out.cpu().numpy()
+        return out[0] if squeeze else out
+
+    def _rgb_to_yuv(self, tag, x, fmt):
+        import torch
+        x, squeeze, _, h, w, _ = self._host_batch(x, np.float32, 3)
+        out = self._rgb_to_yuv_dev(tag, torch.from_numpy(x).to(f"cuda:{self.device}"), fmt, None, None)
+        torch.cuda.synchronize(out.device)
+        out = out.cpu().numpy().view(self._yuv_kind(tag, fmt, h, w)[0])
+        return out[0] if squeeze else out
+
+    def _upscale_yuv(self, tag, frames, fmt, h, w, members, out):
+        a, squeeze = self._yuv_frames(tag, frames, fmt, h, w)
+        dtype, _, os_ = self._yuv_kind(tag, fmt, self.factor * h, self.factor * w)
+        n = a.shape[0]
+        if out is None:
+            out = np.empty((n, os_), dtype=dtype)
+        elif out.dtype != dtype or out.size != n * os_ or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {'u8' if tag == 'yuv' else 'u16'} array of {n * os_} {'bytes' if tag == 'yuv' else 'samples'}")
+        ptr = C.POINTER(C.c_uint8 if tag == "yuv" else C.c_uint16)
+        _lib.check(getattr(self._L, f"sr_upscale_{tag}")(self._ctx, a.ctypes.data_as(ptr), C.byref(fmt), n, h, w, out.ctypes.data_as(ptr),
+                                                         self._members(members)), self._ctx)
+        out = out.reshape(n, os_)
+        return out[0] if squeeze else out
 
     def yuv_to_rgb_dev(self, frames, fmt, h: int, w: int, out=None, stream=None):
         """sr_yuv_to_rgb_dev: (n, frame_bytes) u8 on this GPU -> (n,h,w,3) f32 RGB in [0, 1], the network's input."""
-        n = self._yuv_frames_dev(frames, fmt, h, w)
-        out = self._dev_out(out, (n, h, w, 3), np.float32, frames.device)
-        _lib.check(self._L.sr_yuv_to_rgb_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
-                                             self._stream_ptr(stream, frames.device)), self._ctx)
-        return out
+        return self._yuv_to_rgb_dev("yuv", frames, fmt, h, w, out, stream)
 
     def rgb_to_yuv_dev(self, x, fmt, out=None, stream=None):
         """sr_rgb_to_yuv_dev: (n,h,w,3) f32 RGB on this GPU (any finite values: clamped; NaN counts as 0) -> (n, frame_bytes) u8."""
-        n, h, w, _ = self._dev_batch(x, np.float32, 3)
-        out = self._dev_out(out, (n, yuv_frame_bytes(fmt, h, w)), np.uint8, x.device)
-        _lib.check(self._L.sr_rgb_to_yuv_dev(self._ctx, C.c_void_p(x.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
-                                             self._stream_ptr(stream, x.device)), self._ctx)
-        return out
+        return self._rgb_to_yuv_dev("yuv", x, fmt, out, stream)
 
     def upscale_yuv_dev(self, frames, fmt, h: int, w: int, members: int = 1, out=None, stream=None):
         """sr_upscale_yuv_dev: (n, frame_bytes) u8 frames of h x w on this GPU -> (n, frame_bytes of fh x fw) in the same format."""
-        n = self._yuv_frames_dev(frames, fmt, h, w)
-        out = self._dev_out(out, (n, yuv_frame_bytes(fmt, self.factor * h, self.factor * w)), np.uint8, frames.device)
-        _lib.check(self._L.sr_upscale_yuv_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
-                                              self._members(members), self._stream_ptr(stream, frames.device)), self._ctx)
-        return out
+        return self._upscale_yuv_dev("yuv", frames, fmt, h, w, members, out, stream)
 
     def rows_differ_dev(self, a, b, rows: int, row_bytes: int, out=None, stream=None):
         """sr_rows_differ_dev: two contiguous u8 tensors on this GPU, each holding rows x row_bytes bytes from its first element (views at
@@ -497,120 +554,42 @@ class Engine:
 
     def yuv_to_rgb(self, frames: np.ndarray, fmt, h: int, w: int) -> np.ndarray:
         """yuv_to_rgb_dev on host frames: (n, frame_bytes) or (frame_bytes,) u8 -> (n,h,w,3) or (h,w,3) f32."""
-        import torch
-        a, squeeze = self._yuv_frames(frames, fmt, h, w)
-        out = self.yuv_to_rgb_dev(torch.from_numpy(a).to(f"cuda:{self.device}"), fmt, h, w)
-        torch.cuda.synchronize(out.device)
-        out = out.cpu().numpy()
-        return out[0] if squeeze else out
+        return self._yuv_to_rgb("yuv", frames, fmt, h, w)
 
     def rgb_to_yuv(self, x: np.ndarray, fmt) -> np.ndarray:
         """rgb_to_yuv_dev on a host image: (n,h,w,3) or (h,w,3) f32 -> (n, frame_bytes) or (frame_bytes,) u8."""
-        import torch
-        x, squeeze, _, _, _, _ = self._host_batch(x, np.float32, 3)
-        out = self.rgb_to_yuv_dev(torch.from_numpy(x).to(f"cuda:{self.device}"), fmt)
-        torch.cuda.synchronize(out.device)
-        out = out.cpu().numpy()
-        return out[0] if squeeze else out
+        return self._rgb_to_yuv("yuv", x, fmt)
 
     def upscale_yuv(self, frames: np.ndarray, fmt, h: int, w: int, members: int = 1, out: np.ndarray = None) -> np.ndarray:
         """sr_upscale_yuv: (n, frame_bytes) or (frame_bytes,) u8 frames of h x w -> the frames of fh x fw in the same format: colour
         conversion and chroma resampling on the GPU, the network's f32 output quantised once, straight to YCbCr."""
-        a, squeeze = self._yuv_frames(frames, fmt, h, w)
-        n, ob = a.shape[0], yuv_frame_bytes(fmt, self.factor * h, self.factor * w)
-        if out is None:
-            out = np.empty((n, ob), dtype=np.uint8)
-        elif out.dtype != np.uint8 or out.size != n * ob or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous u8 array of {n * ob} bytes")
-        u8p = C.POINTER(C.c_uint8)
-        _lib.check(self._L.sr_upscale_yuv(self._ctx, a.ctypes.data_as(u8p), C.byref(fmt), n, h, w, out.ctypes.data_as(u8p),
-                                          self._members(members)), self._ctx)
-        out = out.reshape(n, ob)
-        return out[0] if squeeze else out
-
-    # ---- deep video: planar YCbCr frames of 9..16-bit samples in uint16 (include/srhip.h "Deep video") ----
-    @staticmethod
-    def _yuv16_frames(frames, fmt, h, w):
-        """Host frames as a C-contiguous (n, frame_samples) u16 array; squeeze: it was one frame (1-d)."""
-        fs = yuv16_frame_bytes(fmt, h, w) // 2
-        a = np.ascontiguousarray(frames, dtype=np.uint16)
-        squeeze = a.ndim == 1
-        if fs == 0 or a.ndim not in (1, 2) or a.shape[-1] != fs:
-            raise ValueError(f"expected frames of {fs} samples")
-        return (a[None] if squeeze else a), squeeze
-
-    @staticmethod
-    def _yuv16_frames_dev(frames, fmt, h, w):
-        """A contiguous tensor of 16-bit samples on the GPU (torch.uint16 or torch.int16), (n, frame_samples) or (frame_samples,)."""
-        fs = yuv16_frame_bytes(fmt, h, w) // 2
-        assert frames.is_cuda and frames.element_size() == 2 and frames.is_contiguous() and frames.dim() in (1, 2) and frames.shape[-1] == fs
-        return 1 if frames.dim() == 1 else frames.shape[0]
+        return self._upscale_yuv("yuv", frames, fmt, h, w, members, out)
 
     def yuv16_to_rgb_dev(self, frames, fmt, h: int, w: int, out=None, stream=None):
         """sr_yuv16_to_rgb_dev: (n, frame_samples) 16-bit samples on this GPU -> (n,h,w,3) f32 RGB in [0, 1], the network's input."""
-        n = self._yuv16_frames_dev(frames, fmt, h, w)
-        out = self._dev_out(out, (n, h, w, 3), np.float32, frames.device)
-        _lib.check(self._L.sr_yuv16_to_rgb_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
-                                               self._stream_ptr(stream, frames.device)), self._ctx)
-        return out
+        return self._yuv_to_rgb_dev("yuv16", frames, fmt, h, w, out, stream)
 
     def rgb_to_yuv16_dev(self, x, fmt, out=None, stream=None):
         """sr_rgb_to_yuv16_dev: (n,h,w,3) f32 RGB on this GPU (any values: clamped; NaN counts as 0) -> (n, frame_samples) int16 tensor
         holding the uint16 samples (view it as torch.uint16, or numpy .view(np.uint16))."""
-        import torch
-        n, h, w, _ = self._dev_batch(x, np.float32, 3)
-        fs = yuv16_frame_bytes(fmt, h, w) // 2
-        if out is None:
-            out = torch.empty((n, fs), dtype=torch.int16, device=x.device)
-        assert out.is_cuda and out.element_size() == 2 and out.is_contiguous() and out.numel() == n * fs
-        _lib.check(self._L.sr_rgb_to_yuv16_dev(self._ctx, C.c_void_p(x.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
-                                               self._stream_ptr(stream, x.device)), self._ctx)
-        return out
+        return self._rgb_to_yuv_dev("yuv16", x, fmt, out, stream)
 
     def upscale_yuv16_dev(self, frames, fmt, h: int, w: int, members: int = 1, out=None, stream=None):
         """sr_upscale_yuv16_dev: (n, frame_samples) frames of h x w on this GPU -> (n, frame_samples of fh x fw) in the same format (int16
         tensor holding the uint16 samples unless `out` is given)."""
-        import torch
-        n = self._yuv16_frames_dev(frames, fmt, h, w)
-        fs = yuv16_frame_bytes(fmt, self.factor * h, self.factor * w) // 2
-        if out is None:
-            out = torch.empty((n, fs), dtype=torch.int16, device=frames.device)
-        assert out.is_cuda and out.element_size() == 2 and out.is_contiguous() and out.numel() == n * fs
-        _lib.check(self._L.sr_upscale_yuv16_dev(self._ctx, C.c_void_p(frames.data_ptr()), C.byref(fmt), n, h, w, C.c_void_p(out.data_ptr()),
-                                                self._members(members), self._stream_ptr(stream, frames.device)), self._ctx)
-        return out
+        return self._upscale_yuv_dev("yuv16", frames, fmt, h, w, members, out, stream)
 
     def yuv16_to_rgb(self, frames: np.ndarray, fmt, h: int, w: int) -> np.ndarray:
         """yuv16_to_rgb_dev on host frames: (n, frame_samples) or (frame_samples,) u16 -> (n,h,w,3) or (h,w,3) f32."""
-        import torch
-        a, squeeze = self._yuv16_frames(frames, fmt, h, w)
-        out = self.yuv16_to_rgb_dev(torch.from_numpy(a.view(np.int16)).to(f"cuda:{self.device}"), fmt, h, w)
-        torch.cuda.synchronize(out.device)
-        out = out.cpu().numpy()
-        return out[0] if squeeze else out
+        return self._yuv_to_rgb("yuv16", frames, fmt, h, w)
 
     def rgb_to_yuv16(self, x: np.ndarray, fmt) -> np.ndarray:
         """rgb_to_yuv16_dev on a host image: (n,h,w,3) or (h,w,3) f32 -> (n, frame_samples) or (frame_samples,) u16."""
-        import torch
-        x, squeeze, _, _, _, _ = self._host_batch(x, np.float32, 3)
-        out = self.rgb_to_yuv16_dev(torch.from_numpy(x).to(f"cuda:{self.device}"), fmt)
-        torch.cuda.synchronize(out.device)
-        out = out.cpu().numpy().view(np.uint16)
-        return out[0] if squeeze else out
+        return self._rgb_to_yuv("yuv16", x, fmt)
 
     def upscale_yuv16(self, frames: np.ndarray, fmt, h: int, w: int, members: int = 1, out: np.ndarray = None) -> np.ndarray:
         """sr_upscale_yuv16: (n, frame_samples) or (frame_samples,) u16 frames of h x w -> the frames of fh x fw in the same format."""
-        a, squeeze = self._yuv16_frames(frames, fmt, h, w)
-        n, os_ = a.shape[0], yuv16_frame_bytes(fmt, self.factor * h, self.factor * w) // 2
-        if out is None:
-            out = np.empty((n, os_), dtype=np.uint16)
-        elif out.dtype != np.uint16 or out.size != n * os_ or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous u16 array of {n * os_} samples")
-        u16p = C.POINTER(C.c_uint16)
-        _lib.check(self._L.sr_upscale_yuv16(self._ctx, a.ctypes.data_as(u16p), C.byref(fmt), n, h, w, out.ctypes.data_as(u16p),
-                                            self._members(members)), self._ctx)
-        out = out.reshape(n, os_)
-        return out[0] if squeeze else out
+        return self._upscale_yuv("yuv16", frames, fmt, h, w, members, out)
 
     # ---- deep colour: 16-bit samples in and out (include/srhip.h "Deep colour") ----
     @staticmethod

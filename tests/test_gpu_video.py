@@ -18,6 +18,7 @@ PRECISIONS = ("f32", "split_f16")
 FORMS = (("420", "center"), ("420", "left"), ("444", "center"))
 FORM_NAME = {("420", "center"): "420center", ("420", "left"): "420left", ("444", "center"): "444"}
 SMALL = ((1, 1), (1, 2), (2, 1), (3, 5), (5, 3), (16, 12), (17, 13))
+OFFSETS = (0, 1, 2, 3, 5, 8, 13, 15)   # where a frame begins within a 16-byte group: what a run moves at once (its head and tail are ragged)
 ALL8 = 0xFF
 
 
@@ -100,16 +101,17 @@ def random_rgb(rng, n, h, w):
 @pytest.mark.parametrize("matrix", tuple(yuv_ref.MATRICES))
 @pytest.mark.parametrize("form", FORMS, ids=lambda f: FORM_NAME[f])
 def test_conversions_are_the_restatement(engines, form, matrix, range_):
-    """Every small shape at n = 1 and 2 with the frames at every byte offset 0..3 (in and out rotate against each other), the wide
-    shapes at n = 2: the f32 RGB equals yuv_ref bit for bit, the frames byte for byte, the bytes around the outputs stay, and the
+    """Every small shape at n = 1 and 2 with the frames at the byte offsets OFFSETS of a 16-byte group (in and out rotate against each
+    other), the wide shapes at n = 2: the f32 RGB equals yuv_ref bit for bit, the frames byte for byte, the bytes around the outputs stay, and the
     recorded op names the grid the shape gives."""
     import torch
     e = engines()
     sub, siting = form
     fmt = fmt_of(sub, siting, matrix, range_)
     rng = np.random.default_rng(sum(map(ord, sub + siting + matrix + range_)))
-    runs = [(n, h, w, off) for (h, w) in SMALL for n in (1, 2) for off in range(4)] + [(2, h, w, (w + h) % 4) for (h, w) in wide_shapes()]
-    for n, h, w, off in runs:
+    runs = [(n, h, w, i) for (h, w) in SMALL for n in (1, 2) for i in range(len(OFFSETS))] + [(2, h, w, w + h) for (h, w) in wide_shapes()]
+    for n, h, w, i in runs:
+        off = OFFSETS[i % len(OFFSETS)]
         fb = yuv_ref.frame_bytes(sub, h, w)
         # YCbCr -> RGB
         frames = random_frames(rng, sub, n, h, w)
@@ -126,7 +128,7 @@ def test_conversions_are_the_restatement(engines, form, matrix, range_):
         assert len(op) == 1 and op[0] == dict(cells(n, h, w), name="yuv2rgb", px="u8", form=FORM_NAME[form], count=1), op
         # RGB -> YCbCr: the frames land at the offset the input did NOT have
         x = random_rgb(rng, n, h, w)
-        o2 = (off + 1 + h) % 4
+        o2 = OFFSETS[(i + 1 + h) % len(OFFSETS)]
         dst, whole = byte_view(n * fb, o2)
         got = e.rgb_to_yuv_dev(torch.from_numpy(x).cuda(), fmt, out=dst.view(n, fb))
         op = e.last_plan()["ops"]

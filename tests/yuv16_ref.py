@@ -1,7 +1,7 @@
 """The colour rule of the deep video path (include/srhip.h "Deep video") restated in numpy, f64: planar YCbCr frames of 9..16-bit samples
 held in little-endian uint16, laid out like a Y4M frame payload, to the network's f32 RGB input and back from its unquantised f32 output.
 It is tests/yuv_ref.py generalised to a depth d, with 4:2:2 and BT.2020 (non-constant luminance) added.  This file is the definition;
-the kernels of rusty_sr_amd/csrc/sr_yuv16.hip are held to it sample for sample and bit for bit (tests/test_gpu_video_deep.py), and
+the kernels of rusty_sr_amd/csrc/sr_yuv.hip on uint16 samples are held to it sample for sample and bit for bit (tests/test_gpu_video_deep.py), and
 tests/test_yuv16_cpu.py holds the rule itself to its properties and to the 8-bit rule.
 
 Every expression below is one IEEE operation per numpy call, in the order the header writes it.  A code is the uint16 as stored,
