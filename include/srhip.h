@@ -899,6 +899,44 @@ int sr_upscale_yuv16_dev(sr_ctx* ctx, const uint16_t* d_in, const sr_yuv16_forma
 int sr_upscale_yuv16(sr_ctx* ctx, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, unsigned members);
 int sr_video_create16(sr_ctx* ctx, const sr_yuv16_format* fmt, int h, int w, int slots, unsigned members, sr_video** out);
 
+/* ---- Video at any size: the network's frames resampled on the device, quantised once ----
+ * `video` writes frames of the weights' factor times the input; what is asked of a video upscaler is 1080p -> 2160p, 720p -> 1080p.  As
+ * the image path does ("Resampling to any size"), these calls resample the network's UNQUANTISED f32 output on the device and quantise
+ * once, at the final size -- straight to a planar frame of the Video / Deep video formats: the vertical pass of the resampling ends in
+ * the YCbCr conversion (one kernel, no oh x ow x 3 f32 image in between, for the format classes on which that is not slower than the
+ * two kernels it stands for; the others run those two: the bytes are the same).  All of them are host calls or session calls: host
+ * memory, synchronous, none takes a stream.  Every result is defined BIT FOR BIT by the chain of existing device calls:
+ *   sr_resize_to_yuv[16]       n f32 RGB images of h x w (any graph's context) -> n frames of oh x ow luma samples in `fmt`: equal to
+ *                              sr_resize_dev (SR_PIXELS_F32 -> SR_PIXELS_F32, same filter and flags) followed by sr_rgb_to_yuv[16]_dev.
+ *                              One upload, the tap tables, the horizontal pass, the vertical pass to the frame, one download.
+ *   sr_upscale_yuv[16]_sized   n frames of h x w -> n frames of oh x ow in the same format: equal to sr_yuv[16]_to_rgb_dev ->
+ *                              sr_upscale_f32_dev (members == 1) or sr_upscale_ensemble_f32_dev frame by frame -> sr_resize_dev (f32 ->
+ *                              f32) -> sr_rgb_to_yuv[16]_dev.  In SR_PRECISION_SPLIT_F16 a value that leaves the domain makes the whole
+ *                              call run again in exact f32, as sr_upscale_yuv does (the context stays in f32).  With sr_set_profiling on,
+ *                              sr_last_timing's total_ms is every launch, h2d_ms / d2h_ms the two copies.
+ *   sr_video_create[16]_sized  a frame stream (sr_video_create) whose output frames are oh x ow: acquire / submit / receive / pending /
+ *                              destroy are the same calls; the slots' output buffers and the page-locked output frames hold
+ *                              sr_yuv[16]_frame_bytes(fmt, oh, ow); nothing is allocated per frame -- the workspace is reserved, all or
+ *                              nothing, when the session is made; the recomputation in exact f32 works as in the plain session.  Each
+ *                              frame is bit-identical to sr_upscale_yuv[16]_sized of it.  sr_video_set_reuse(SR_VIDEO_REUSE_ROWS) on
+ *                              such a session is SR_E_INVALID: the row bands do not compose with a vertical resampling.
+ * filter: SR_FILTER_*; flags: 0 or SR_RESIZE_SRGB_SPACE.  Refused with SR_E_INVALID before any launch, the output untouched: what
+ * sr_upscale_yuv* / sr_video_create* refuse for format, shape, mask and graph (sr_resize_to_yuv*: a null pointer, a misaligned frame
+ * pointer, an invalid format, n, h or w below 1); what sr_resize_dev refuses for oh, ow, filter, flags and byte counts beyond a size_t;
+ * oh or ow beyond INT32_MAX / 4.  A workspace that cannot fit is SR_E_NOMEM and leaves the context usable. */
+int sr_resize_to_yuv(sr_ctx* ctx, const float* rgb, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, int oh, int ow, int filter,
+                     unsigned flags);
+int sr_resize_to_yuv16(sr_ctx* ctx, const float* rgb, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, int oh, int ow,
+                       int filter, unsigned flags);
+int sr_upscale_yuv_sized(sr_ctx* ctx, const uint8_t* in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, int oh, int ow,
+                         int filter, unsigned flags, unsigned members);
+int sr_upscale_yuv16_sized(sr_ctx* ctx, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, int oh, int ow,
+                           int filter, unsigned flags, unsigned members);
+int sr_video_create_sized(sr_ctx* ctx, const sr_yuv_format* fmt, int h, int w, int oh, int ow, int filter, unsigned flags, int slots,
+                          unsigned members, sr_video** out);
+int sr_video_create16_sized(sr_ctx* ctx, const sr_yuv16_format* fmt, int h, int w, int oh, int ow, int filter, unsigned flags, int slots,
+                            unsigned members, sr_video** out);
+
 /* ---- Deep colour: 16-bit images in and out ----
  * The reference's images are 8 bits wide (main.rs:164-175), and so is every other integer path here; a 16-bit scan, photograph, height
  * or displacement map would come back with 256 levels a channel.  These calls take and give interleaved 16-bit samples -- native-endian

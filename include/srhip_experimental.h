@@ -41,6 +41,10 @@ extern "C" {
  * takes min(automatic grid, N) workgroups.  The kernels walk their tiles / items with the grid as stride, so a small N reaches their
  * multi-round paths (carries of the item counter, the prefetch of the next round) at tiny shapes and on any CU count; host side only, no
  * output byte depends on it.  Anything but "" or a positive integer: SR_E_INVALID.  (No environment default.)
+ * "vyuv": the vertical pass of a resampling that ends in a YCbCr frame (srhip.h "Video at any size") -- "" the measured rule: a format
+ * class runs the fused kernel where that is not slower than the two kernels it replaces, else those two; "1" | "2": the
+ * fused kernel for every class, with that many row pairs a workgroup; "chain": resize_v + rgb_to_yuv for every class.  For measurement
+ * and tests: no output byte depends on it.  Anything else: SR_E_INVALID.  (No environment default.)
  * Every key is host-side state that a call reads when it is QUEUED (launch arguments travel by value): a switch may be set while earlier
  * *_dev calls are still in flight on the caller's stream -- nothing waits, and the calls already queued keep the plan they were queued
  * with (tests/test_gpu_stream_order.py changes "fork", "th" and "pipe" between queued calls).

@@ -308,6 +308,12 @@ extern "C" {
     pub fn sr_upscale_yuv16_dev(ctx: *mut SrCtx, d_in: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, d_out: *mut u16, members: c_uint, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_yuv16(ctx: *mut SrCtx, input: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, out: *mut u16, members: c_uint) -> c_int;
     pub fn sr_video_create16(ctx: *mut SrCtx, fmt: *const SrYuv16Format, h: c_int, w: c_int, slots: c_int, members: c_uint, out: *mut *mut SrVideo) -> c_int;
+    pub fn sr_resize_to_yuv(ctx: *mut SrCtx, rgb: *const f32, fmt: *const SrYuvFormat, n: c_int, h: c_int, w: c_int, out: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint) -> c_int;
+    pub fn sr_resize_to_yuv16(ctx: *mut SrCtx, rgb: *const f32, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, out: *mut u16, oh: c_int, ow: c_int, filter: c_int, flags: c_uint) -> c_int;
+    pub fn sr_upscale_yuv_sized(ctx: *mut SrCtx, input: *const u8, fmt: *const SrYuvFormat, n: c_int, h: c_int, w: c_int, out: *mut u8, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
+    pub fn sr_upscale_yuv16_sized(ctx: *mut SrCtx, input: *const u16, fmt: *const SrYuv16Format, n: c_int, h: c_int, w: c_int, out: *mut u16, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, members: c_uint) -> c_int;
+    pub fn sr_video_create_sized(ctx: *mut SrCtx, fmt: *const SrYuvFormat, h: c_int, w: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, slots: c_int, members: c_uint, out: *mut *mut SrVideo) -> c_int;
+    pub fn sr_video_create16_sized(ctx: *mut SrCtx, fmt: *const SrYuv16Format, h: c_int, w: c_int, oh: c_int, ow: c_int, filter: c_int, flags: c_uint, slots: c_int, members: c_uint, out: *mut *mut SrVideo) -> c_int;
     pub fn sr_u16_to_f32_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut f32, stream: *mut c_void) -> c_int;
     pub fn sr_f32_to_u16_dev(ctx: *mut SrCtx, d_in: *const f32, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, stream: *mut c_void) -> c_int;
     pub fn sr_upscale_u16_dev(ctx: *mut SrCtx, d_in: *const u16, in_channels: c_int, n: c_int, h: c_int, w: c_int, d_out: *mut u16, out_channels: c_int, members: c_uint, stream: *mut c_void) -> c_int;

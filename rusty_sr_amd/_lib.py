@@ -244,6 +244,12 @@ SYMBOLS = {
     "sr_upscale_yuv16_dev": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _vp, C.c_uint, _vp]),
     "sr_upscale_yuv16": (_i, [_vp, _u16p, C.POINTER(Yuv16Format), _i, _i, _i, _u16p, C.c_uint]),
     "sr_video_create16": (_i, [_vp, C.POINTER(Yuv16Format), _i, _i, _i, C.c_uint, C.POINTER(_vp)]),
+    "sr_resize_to_yuv": (_i, [_vp, _vp, C.POINTER(YuvFormat), _i, _i, _i, _u8p, _i, _i, _i, C.c_uint]),
+    "sr_resize_to_yuv16": (_i, [_vp, _vp, C.POINTER(Yuv16Format), _i, _i, _i, _u16p, _i, _i, _i, C.c_uint]),
+    "sr_upscale_yuv_sized": (_i, [_vp, _u8p, C.POINTER(YuvFormat), _i, _i, _i, _u8p, _i, _i, _i, C.c_uint, C.c_uint]),
+    "sr_upscale_yuv16_sized": (_i, [_vp, _u16p, C.POINTER(Yuv16Format), _i, _i, _i, _u16p, _i, _i, _i, C.c_uint, C.c_uint]),
+    "sr_video_create_sized": (_i, [_vp, C.POINTER(YuvFormat), _i, _i, _i, _i, _i, C.c_uint, _i, C.c_uint, C.POINTER(_vp)]),
+    "sr_video_create16_sized": (_i, [_vp, C.POINTER(Yuv16Format), _i, _i, _i, _i, _i, C.c_uint, _i, C.c_uint, C.POINTER(_vp)]),
     "sr_u16_to_f32_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sr_f32_to_u16_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "sr_upscale_u16_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, C.c_uint, _vp]),

@@ -6,9 +6,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsrhip.so")
-SOURCES = ["sr_kernels.hip", "sr_aux.hip", "sr_valid.hip", "sr_grad.hip", "sr_train.hip", "sr_ensemble.hip", "sr_metrics.hip", "sr_alpha.hip", "sr_resize.hip", "sr_degrade.hip", "sr_api.cpp", "sr_plan.cpp", "sr_comm.cpp", "sr_valid.cpp", "sr_grad.cpp", "sr_train.cpp", "sr_ensemble.cpp", "sr_metrics.cpp", "sr_alpha.cpp", "sr_resize.cpp", "sr_degrade.cpp", "sr_border.hip", "sr_border.cpp", "sr_yuv.hip", "sr_yuv.cpp", "sr_reuse.hip", "sr_deep.hip", "sr_deep.cpp", "sr_optim.hip", "sr_optim.cpp"]
+SOURCES = ["sr_kernels.hip", "sr_aux.hip", "sr_valid.hip", "sr_grad.hip", "sr_train.hip", "sr_ensemble.hip", "sr_metrics.hip", "sr_alpha.hip", "sr_resize.hip", "sr_degrade.hip", "sr_api.cpp", "sr_plan.cpp", "sr_comm.cpp", "sr_valid.cpp", "sr_grad.cpp", "sr_train.cpp", "sr_ensemble.cpp", "sr_metrics.cpp", "sr_alpha.cpp", "sr_resize.cpp", "sr_degrade.cpp", "sr_border.hip", "sr_border.cpp", "sr_yuv.hip", "sr_resize_yuv.hip", "sr_yuv.cpp", "sr_reuse.hip", "sr_deep.hip", "sr_deep.cpp", "sr_optim.hip", "sr_optim.cpp"]
 DEVICE_ASM = os.path.join(HERE, "build", "sr_kernels.gfx950.s")  # device assembly of the stage kernels, kept for the ISA lint
-HEADERS = ["sr_kernels.h", "sr_internal.h", "sr_plan.h", "sr_params.h", "sr_reduce.h", "sr_transfer.h", "sr_bytes.h", "sr_crop.h", "sr_border.h", "sr_yuv_rule.h", os.path.join("..", "..", "include", "srhip.h")]
+HEADERS = ["sr_kernels.h", "sr_internal.h", "sr_plan.h", "sr_params.h", "sr_reduce.h", "sr_transfer.h", "sr_bytes.h", "sr_crop.h", "sr_border.h", "sr_yuv_rule.h", "sr_yuv_tile.h", os.path.join("..", "..", "include", "srhip.h")]
 
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-pthread"]

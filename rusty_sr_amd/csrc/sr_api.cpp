@@ -568,6 +568,9 @@ int sr_set_experiment(sr_ctx* c, const char* key, const char* value) {
         c->wino5 = !strcmp(v, "3") ? 2 : !strcmp(v, "2") ? 0 : kWinoConv5Halves;
     } else if (!strcmp(key, "bw")) {   // tile-order column-block width in tiles; "" / negative: automatic, 0: plain row-major
         c->env_bw = *v ? atoi(v) : -1;
+    } else if (!strcmp(key, "vyuv")) {  // the vertical pass to a YCbCr frame: "" the measured rule, "1" | "2": the fused kernel, that many row pairs a workgroup, "chain": resize_v + rgb_to_yuv (same bits every way)
+        if (*v && strcmp(v, "1") && strcmp(v, "2") && strcmp(v, "chain")) return SR_E_INVALID;
+        c->env_vyuv_pairs = !strcmp(v, "1") ? 1 : !strcmp(v, "2") ? 2 : !strcmp(v, "chain") ? -1 : 0;
     } else if (!strcmp(key, "auxgrid")) {  // bilinear_net / downsample_net: "" automatic, "N" (N >= 1): never more than N workgroups per launch
         long cap = 0;
         for (const char* p = v; *p; ++p) {

@@ -86,6 +86,7 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     };
     std::vector<ForkTune> fork_tune;
     unsigned long long fork_tune_clock = 0;
+    int env_vyuv_pairs = 0;           // the vertical pass to a YCbCr frame: 0 the measured rule (sr_yuv.cpp fused_pays), 1 | 2 the fused kernel with that many row pairs a workgroup, -1 the chain; "vyuv"
     int env_auxgrid = 0;              // bilinear_net / downsample_net: at most this many workgroups per launch (0: automatic); "auxgrid"
     unsigned long long params_hash = 0;  // FNV-1a of the parameter vector: contexts of one sharded call must agree
     // ---- multi-GPU (sr_comm.cpp): one RCCL communicator per context, neighbour halo exchange
@@ -147,6 +148,7 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     // ---- video (sr_yuv.cpp): grown on demand, freed by sr_destroy
     sr_buf d_yrgb;                                  // the frames as the network's input, n x h x w x 3 f32
     sr_buf d_ynet;                                  // the network's f32 output for them, before the conversion back
+    sr_buf d_yres;                                  // the sized calls, format classes that go by the chain: the resampled f32 image, oh x ow x 3
     std::vector<sr_video*> videos;                  // frame streams on this context: sr_destroy drains and detaches them
     // ---- deep colour (sr_deep.cpp): grown on demand, freed by sr_destroy
     sr_buf d_kin;                                   // the 16-bit images as the network's input, n x h x w x 3 f32
@@ -165,7 +167,7 @@ inline void sr_plan_note(sr_ctx* c, const std::string& line) {
     else c->plan_rec.emplace_back(line, 1);
 }
 
-// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16|yuv16_to_rgb|rgb_to_yuv16|rows_differ> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
+// One launch of a pixel operator: "op name=<pad|crop|bleed|merge|resize_h|resize_v|resize_v_yuv|yuv2rgb|rgb2yuv|u16_to_f32|f32_to_u16|yuv16_to_rgb|rgb_to_yuv16|rows_differ> px=<u8|f32> n=.. bx=.. by=.. [form=..] [f=..]".
 // px: the pixels the kernel is instantiated on (resize_h, yuv2rgb, rgb2yuv: its input's, resize_v: its output's; the deep-colour and deep video conversions: their f32 side); bx / by: workgroups along a row and along
 // the rows of one image (resize_h: of the batch's n h rows; the deep-colour conversions: 1, the batch is one run of pixels), from the
 // *_blocks function the launcher itself calls.
@@ -507,6 +509,29 @@ hipError_t sr_launch_resize_taps(const sr_resize_axis& x, const sr_resize_axis& 
 hipError_t sr_launch_resize_h(const void* d_in, bool in_u8, bool linear, size_t rows, const sr_resize_axis& x, float* d_mid, hipStream_t s);
 // n images of y.n_in x ow x 3 f32 at d_mid -> n images of y.n_out x ow (RGBA8 or f32 RGB; linear: through LinearToSrgb) at d_out
 hipError_t sr_launch_resize_v(const float* d_mid, int n, int ow, const sr_resize_axis& y, void* d_out, bool out_u8, bool linear, hipStream_t s);
+// One resampling of n images h x w -> oh x ow: its two axes and what it needs of the workspace (d_rtab, d_rmid).
+struct sr_resize_job {
+    int n = 0, h = 0, w = 0, oh = 0, ow = 0, filter = 0;
+    bool linear = true;
+    sr_resize_axis x{}, y{};
+    size_t tab_bytes = 0, mid_bytes = 0;
+};
+// everything a resampling refuses for its shape, filter and flags alone (SR_E_INVALID: sizes below 1, an unknown filter or flag, byte
+// counts beyond a size_t); *job is filled where they pass
+int sr_resize_plan(int n, int h, int w, int oh, int ow, int filter, unsigned flags, sr_resize_job* job);
+bool sr_resize_front_fits(const sr_resize_job& j);           // the horizontal pass's grid is one a launch takes
+void sr_resize_bind_tables(sr_ctx* c, sr_resize_job& j);     // the axes' table pointers into d_rtab, once it holds j.tab_bytes
+// the tap tables and the horizontal pass of a job whose workspace is reserved and bound, into d_rmid, queued on s, with the pass's "op" line
+int sr_resize_queue_front(sr_ctx* c, const sr_resize_job& j, const void* d_in, bool in_u8, hipStream_t s);
+// ---- ... that ends in a YCbCr frame (sr_resize_yuv.hip; include/srhip.h "Video at any size")
+// workgroups of the launch (0: an empty shape) for `pairs` row pairs a workgroup (1 | 2; anything else: the default), a function of the
+// shape alone; the launcher refuses more than INT32_MAX
+size_t sr_resize_yuv_blocks(int n, int oh, int ow, int pairs, unsigned* blocks_x_out = nullptr, unsigned* blocks_y_out = nullptr);
+// n images of y.n_in x ow x 3 f32 at d_mid -> n frames of y.n_out x ow luma samples S at d_yuv (aligned to a sample): the bits of
+// sr_launch_resize_v (f32 out) followed by sr_launch_rgb_to_yuv
+template <class S>
+hipError_t sr_launch_resize_v_yuv(const float* d_mid, int n, int ow, const sr_resize_axis& y, const sr_yuv_rule& k, S* d_yuv, bool linear,
+                                  int pairs, hipStream_t s);
 void sr_resize_release(sr_ctx* c);  // free the resampling buffers (called by sr_destroy)
 
 // ---- training session (sr_train.hip crop kernel, sr_train.cpp host side)

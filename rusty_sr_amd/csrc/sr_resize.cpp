@@ -22,65 +22,32 @@ bool bytes_of(size_t a, size_t b, size_t c, size_t d, size_t* out) {
 
 size_t pixel_bytes(int pixels) { return pixels == SR_PIXELS_RGBA8 ? 4 : 3 * sizeof(float); }
 
-// One resampling of n images h x w -> oh x ow: its two axes and what it needs of the workspace.
-struct ResizeJob {
-    int n = 0, h = 0, w = 0, oh = 0, ow = 0, filter = 0;
-    bool linear = true;
-    sr_resize_axis x{}, y{};
-    size_t tab_bytes = 0, mid_bytes = 0;
-};
+using ResizeJob = sr_resize_job;
 
 // everything sr_resize_* refuse for their arguments alone; *job is filled where they pass
 int plan_resize(const void* in, int in_pixels, int n, int h, int w, const void* out, int out_pixels, int oh, int ow, int filter, unsigned flags,
                 ResizeJob* job) {
-    if (!in || !out || n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1) return SR_E_INVALID;
-    if (filter < SR_FILTER_BOX || filter > SR_FILTER_LANCZOS3) return SR_E_INVALID;
+    if (!in || !out) return SR_E_INVALID;
     if ((in_pixels != SR_PIXELS_RGBA8 && in_pixels != SR_PIXELS_F32) || (out_pixels != SR_PIXELS_RGBA8 && out_pixels != SR_PIXELS_F32)) return SR_E_INVALID;
-    if (flags & ~(unsigned)SR_RESIZE_SRGB_SPACE) return SR_E_INVALID;
     if (in == out) return SR_E_INVALID;
-    size_t in_bytes = 0, out_bytes = 0, mid_bytes = 0;
-    if (!bytes_of(n, h, w, 3 * sizeof(float), &in_bytes) || !bytes_of(n, oh, ow, 3 * sizeof(float), &out_bytes) ||
-        !bytes_of(n, h, ow, 3 * sizeof(float), &mid_bytes))
-        return SR_E_INVALID;
-    job->n = n; job->h = h; job->w = w; job->oh = oh; job->ow = ow; job->filter = filter;
-    job->linear = !(flags & SR_RESIZE_SRGB_SPACE);
-    job->x = sr_resize_plan_axis(w, ow, filter);
-    job->y = sr_resize_plan_axis(h, oh, filter);
-    size_t wx = 0, wy = 0;
-    if (!bytes_of(job->x.taps, ow, sizeof(float), 1, &wx) || !bytes_of(job->y.taps, oh, sizeof(float), 1, &wy)) return SR_E_INVALID;
-    const size_t heads = 2 * sizeof(int) * ((size_t)ow + (size_t)oh);
-    if (__builtin_add_overflow(wx, wy, &job->tab_bytes) || __builtin_add_overflow(job->tab_bytes, heads, &job->tab_bytes)) return SR_E_INVALID;
-    job->mid_bytes = mid_bytes;
-    return SR_OK;
+    return sr_resize_plan(n, h, w, oh, ow, filter, flags, job);
 }
 
 // The workspace of a job (and, for the _sized calls, in_bytes of d_rin and net_bytes of d_rnet beside it), all or nothing.  A grid beyond
 // what a launch takes is refused before an allocation is attempted, as is memory (sr_reserve_bufs); the context's device is current.
 int reserve(sr_ctx* c, ResizeJob& j, size_t in_bytes, size_t net_bytes) {
-    if (sr_resize_h_blocks((size_t)j.n * j.h, j.x) > (size_t)INT32_MAX || sr_resize_v_blocks(j.n, j.oh, j.ow) > (size_t)INT32_MAX)
-        return SR_E_NOMEM;
+    if (!sr_resize_front_fits(j) || sr_resize_v_blocks(j.n, j.oh, j.ow) > (size_t)INT32_MAX) return SR_E_NOMEM;
     SRCHK(sr_reserve_bufs(c, {{&c->d_rtab, j.tab_bytes}, {&c->d_rmid, j.mid_bytes}, {&c->d_rin, in_bytes}, {&c->d_rnet, net_bytes}}));
-    // the tables: [x.lo][x.cnt][y.lo][y.cnt][x.w][y.w]
-    int* p = (int*)c->d_rtab.p;
-    j.x.lo = p; j.x.cnt = p + j.ow;
-    j.y.lo = p + 2 * (size_t)j.ow; j.y.cnt = j.y.lo + j.oh;
-    j.x.w = (float*)(j.y.cnt + j.oh);
-    j.y.w = j.x.w + (size_t)j.x.taps * j.ow;
+    sr_resize_bind_tables(c, j);
     return SR_OK;
 }
 
 // the three launches of a reserved job on s; the two passes leave their "op" lines in the plan record -- the grids and the form
 // sr_launch_resize_h / _v themselves take
 int queue_resize(sr_ctx* c, const ResizeJob& j, const void* d_in, bool in_u8, void* d_out, bool out_u8, hipStream_t s) {
-    const size_t rows = (size_t)j.n * j.h;
-    unsigned hx = 0, vx = 0, groups = 0;
-    int cap = 0;
-    const size_t h_blocks = sr_resize_h_blocks(rows, j.x, &hx);
-    const int per = sr_resize_h_form(j.x, &cap);
+    unsigned vx = 0, groups = 0;
     (void)sr_resize_v_blocks(j.n, j.oh, j.ow, &vx, &groups);
-    HIPCHK(c, sr_launch_resize_taps(j.x, j.y, j.filter, s));
-    HIPCHK(c, sr_launch_resize_h(d_in, in_u8, j.linear, rows, j.x, (float*)c->d_rmid.p, s));
-    sr_plan_note_op(c, "resize_h", !in_u8, j.n, hx, hx ? (unsigned)(h_blocks / hx) : 0u, cap == 0 ? "direct" : per == 1 ? "staged1" : "staged4");
+    SRCHK(sr_resize_queue_front(c, j, d_in, in_u8, s));
     HIPCHK(c, sr_launch_resize_v((const float*)c->d_rmid.p, j.n, j.ow, j.y, d_out, out_u8, j.linear, s));
     sr_plan_note_op(c, "resize_v", !out_u8, j.n, vx, groups);
     return SR_OK;
@@ -118,6 +85,49 @@ int queue_sized(sr_ctx* c, SizedJob& j, const uint8_t* d_in, int h, int w, uint8
 }
 
 }  // namespace
+
+int sr_resize_plan(int n, int h, int w, int oh, int ow, int filter, unsigned flags, sr_resize_job* job) {
+    if (n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1) return SR_E_INVALID;
+    if (filter < SR_FILTER_BOX || filter > SR_FILTER_LANCZOS3) return SR_E_INVALID;
+    if (flags & ~(unsigned)SR_RESIZE_SRGB_SPACE) return SR_E_INVALID;
+    size_t in_bytes = 0, out_bytes = 0, mid_bytes = 0;
+    if (!bytes_of(n, h, w, 3 * sizeof(float), &in_bytes) || !bytes_of(n, oh, ow, 3 * sizeof(float), &out_bytes) ||
+        !bytes_of(n, h, ow, 3 * sizeof(float), &mid_bytes))
+        return SR_E_INVALID;
+    job->n = n; job->h = h; job->w = w; job->oh = oh; job->ow = ow; job->filter = filter;
+    job->linear = !(flags & SR_RESIZE_SRGB_SPACE);
+    job->x = sr_resize_plan_axis(w, ow, filter);
+    job->y = sr_resize_plan_axis(h, oh, filter);
+    size_t wx = 0, wy = 0;
+    if (!bytes_of(job->x.taps, ow, sizeof(float), 1, &wx) || !bytes_of(job->y.taps, oh, sizeof(float), 1, &wy)) return SR_E_INVALID;
+    const size_t heads = 2 * sizeof(int) * ((size_t)ow + (size_t)oh);
+    if (__builtin_add_overflow(wx, wy, &job->tab_bytes) || __builtin_add_overflow(job->tab_bytes, heads, &job->tab_bytes)) return SR_E_INVALID;
+    job->mid_bytes = mid_bytes;
+    return SR_OK;
+}
+
+bool sr_resize_front_fits(const sr_resize_job& j) { return sr_resize_h_blocks((size_t)j.n * j.h, j.x) <= (size_t)INT32_MAX; }
+
+void sr_resize_bind_tables(sr_ctx* c, sr_resize_job& j) {
+    // the tables: [x.lo][x.cnt][y.lo][y.cnt][x.w][y.w]
+    int* p = (int*)c->d_rtab.p;
+    j.x.lo = p; j.x.cnt = p + j.ow;
+    j.y.lo = p + 2 * (size_t)j.ow; j.y.cnt = j.y.lo + j.oh;
+    j.x.w = (float*)(j.y.cnt + j.oh);
+    j.y.w = j.x.w + (size_t)j.x.taps * j.ow;
+}
+
+int sr_resize_queue_front(sr_ctx* c, const sr_resize_job& j, const void* d_in, bool in_u8, hipStream_t s) {
+    const size_t rows = (size_t)j.n * j.h;
+    unsigned hx = 0;
+    int cap = 0;
+    const size_t h_blocks = sr_resize_h_blocks(rows, j.x, &hx);
+    const int per = sr_resize_h_form(j.x, &cap);
+    HIPCHK(c, sr_launch_resize_taps(j.x, j.y, j.filter, s));
+    HIPCHK(c, sr_launch_resize_h(d_in, in_u8, j.linear, rows, j.x, (float*)c->d_rmid.p, s));
+    sr_plan_note_op(c, "resize_h", !in_u8, j.n, hx, hx ? (unsigned)(h_blocks / hx) : 0u, cap == 0 ? "direct" : per == 1 ? "staged1" : "staged4");
+    return SR_OK;
+}
 
 sr_resize_axis sr_resize_plan_axis(int n_in, int n_out, int filter) {
     sr_resize_axis a{};

@@ -5,7 +5,9 @@
 // before its work is done.  Frames of bytes and deep frames of uint16 samples are one path, templated on
 // the sample type S; the two format structs meet in one sr_yuv_rule (sr_yuv_rule.h), and a session of either kind is one sr_video.  Row
 // reuse (sr_video_set_reuse; the compare kernel: sr_reuse.hip, the planner: sr_plan.cpp) is a session's opt-in: it
-// computes the row bands a changed input row can reach and takes the other rows from the last frame's output.
+// computes the row bands a changed input row can reach and takes the other rows from the last frame's output.  The sized calls and
+// sessions ("Video at any size") end in the resampler's passes instead of the conversion back: the horizontal pass of
+// sr_resize.hip, then the vertical pass that writes the frame (sr_resize_yuv.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -144,11 +146,112 @@ int upscale_host(sr_ctx* c, const S* in, const Format* fmt, int n, int h, int w,
     });
 }
 
+// ---- video at any size (include/srhip.h "Video at any size"): the network's f32 output resampled straight to a frame.
+// What the calls refuse for the final size beyond the resampler's own refusals
+int check_out_size(int oh, int ow) { return oh <= kSideMax && ow <= kSideMax ? SR_OK : SR_E_INVALID; }
+
+// Whether a format class takes the fused vertical pass (resize_v_yuv_kernel) or the chain it equals bit for bit (resize_v_kernel into
+// d_yres, then rgb_to_yuv_kernel): by measurement, class by class (profiles/video_sized_rocprof_stats.csv) -- the fused
+// kernel where it is not slower than the sum of the two.  At 5760x3240 -> 3840x2160 it is 0.94-0.99 x the sum on 4:4:4 and on centre-sited
+// 4:2:0 / 4:2:2, bytes and deep samples alike, and 1.05-1.07 x on the left-sited forms, whose workgroups wait for one thread's second
+// walk over the neighbouring column: those go by the chain.  "vyuv" overrides the rule for tests and measurements.
+template <class S>
+bool fused_pays(const sr_yuv_rule& k) { return !(k.left && k.sub != SR_YUV_444); }
+
+template <class S>
+bool takes_fused(const sr_ctx* c, const sr_yuv_rule& k) { return c->env_vyuv_pairs > 0 || (c->env_vyuv_pairs == 0 && fused_pays<S>(k)); }
+
+// The workspace of a resampling to a frame of samples S (and, for the composed calls, rgb_bytes of d_yrgb and net_bytes of d_ynet beside
+// it), all or nothing; a grid beyond what a launch takes is refused before an allocation is attempted.  A class that goes by the chain
+// holds the resampled f32 image as well.  The context's device is current.
+template <class S>
+int reserve_sized(sr_ctx* c, sr_resize_job& j, const sr_yuv_rule& k, size_t rgb_bytes, size_t net_bytes) {
+    if (!sr_resize_front_fits(j) || sr_resize_yuv_blocks(j.n, j.oh, j.ow, 1) > (size_t)INT32_MAX ||
+        sr_resize_v_blocks(j.n, j.oh, j.ow) > (size_t)INT32_MAX)
+        return SR_E_NOMEM;
+    const size_t res_bytes = takes_fused<S>(c, k) ? 0 : (size_t)j.n * j.oh * j.ow * kPxF;  // (fits a size_t: sr_resize_plan)
+    SRCHK(sr_reserve_bufs(c, {{&c->d_rtab, j.tab_bytes}, {&c->d_rmid, j.mid_bytes}, {&c->d_yrgb, rgb_bytes}, {&c->d_ynet, net_bytes},
+                              {&c->d_yres, res_bytes}}));
+    sr_resize_bind_tables(c, j);
+    return SR_OK;
+}
+
+// the tap tables, the horizontal pass and the vertical pass that ends in the frame -- fused, or as its two kernels -- queued on s; the
+// job's workspace is reserved
+template <class S>
+int queue_resize_to_yuv(sr_ctx* c, const sr_resize_job& j, const float* d_rgb, const sr_yuv_rule& k, S* d_out, hipStream_t s) {
+    unsigned bx = 0, by = 0;
+    SRCHK(sr_resize_queue_front(c, j, d_rgb, false, s));
+    if (!takes_fused<S>(c, k)) {
+        (void)sr_resize_v_blocks(j.n, j.oh, j.ow, &bx, &by);
+        HIPCHK(c, sr_launch_resize_v((const float*)c->d_rmid.p, j.n, j.ow, j.y, c->d_yres.p, false, j.linear, s));
+        sr_plan_note_op(c, "resize_v", true, j.n, bx, by);
+        return queue_to_yuv(c, (const float*)c->d_yres.p, k, j.n, j.oh, j.ow, d_out, s);
+    }
+    const int pairs = c->env_vyuv_pairs;
+    (void)sr_resize_yuv_blocks(j.n, j.oh, j.ow, pairs, &bx, &by);
+    HIPCHK(c, sr_launch_resize_v_yuv((const float*)c->d_rmid.p, j.n, j.ow, j.y, k, d_out, j.linear, pairs, s));
+    sr_plan_note_op(c, "resize_v_yuv", true, j.n, bx, by, form_name(k));
+    return SR_OK;
+}
+
+// everything the sized composed calls and the sized frame stream refuse for their context, format, shapes, filter, flags and mask alone
+template <class Format>
+int plan_upscale_sized(const sr_ctx* c, const Format* fmt, int n, int h, int w, int oh, int ow, int filter, unsigned flags, unsigned members,
+                       sr_yuv_rule* k, sr_resize_job* j) {
+    SRCHK(check_upscale_shape(c, fmt, n, h, w, members, k));
+    SRCHK(check_out_size(oh, ow));
+    return sr_resize_plan(n, c->factor * h, c->factor * w, oh, ow, filter, flags, j);
+}
+
+// to RGB -> network -> resampling to the frame on device buffers, queued on s; the arguments are checked and the context's device is current
+template <class S>
+int queue_upscale_sized(sr_ctx* c, const S* d_in, const sr_yuv_rule& k, sr_resize_job& j, int h, int w, S* d_out, unsigned members, hipStream_t s) {
+    const int n = j.n;
+    const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;  // (n out_img fits: sr_resize_plan)
+    SRCHK(reserve_sized<S>(c, j, k, (size_t)n * in_img, (size_t)n * out_img));
+    SRCHK(queue_to_rgb(c, d_in, k, n, h, w, (float*)c->d_yrgb.p, s));
+    SRCHK(sr_net_queue(c, c->d_yrgb.p, false, 3, n, h, w, c->d_ynet.p, false, members, s));
+    return queue_resize_to_yuv(c, j, (const float*)c->d_ynet.p, k, d_out, s);
+}
+
+template <class S, class Format>
+int resize_to_yuv_host(sr_ctx* c, const float* rgb, const Format* fmt, int n, int h, int w, S* out, int oh, int ow, int filter, unsigned flags) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    sr_resize_job j;
+    if (!c || !rgb || !out || !sample_aligned<S>(out) || !rule_make(fmt, &k)) return SR_E_INVALID;
+    SRCHK(check_frames(n, h, w));
+    SRCHK(check_out_size(oh, ow));
+    SRCHK(sr_resize_plan(n, h, w, oh, ow, filter, flags, &j));
+    const size_t in_bytes = (size_t)n * h * w * kPxF, out_bytes = (size_t)n * sizeof(S) * sr_yuv_rule_frame_samples(k, oh, ow);
+    return sr_host_image_call(c, false, rgb, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) -> int {
+        SRCHK(reserve_sized<S>(c, j, k, 0, 0));
+        return queue_resize_to_yuv(c, j, (const float*)d_in, k, (S*)d_out, s);
+    });
+}
+
+template <class S, class Format>
+int upscale_sized_host(sr_ctx* c, const S* in, const Format* fmt, int n, int h, int w, S* out, int oh, int ow, int filter, unsigned flags,
+                       unsigned members) {
+    sr_plan_clear(c);
+    sr_yuv_rule k;
+    sr_resize_job j;
+    if (!in || !out || !sample_aligned<S>(in) || !sample_aligned<S>(out)) return SR_E_INVALID;
+    SRCHK(plan_upscale_sized(c, fmt, n, h, w, oh, ow, filter, flags, members, &k, &j));
+    const size_t in_bytes = (size_t)n * sizeof(S) * sr_yuv_rule_frame_samples(k, h, w);
+    const size_t out_bytes = (size_t)n * sizeof(S) * sr_yuv_rule_frame_samples(k, oh, ow);
+    return sr_host_image_call(c, true, in, in_bytes, out, out_bytes, [&](const void* d_in, void* d_out, hipStream_t s) {
+        return queue_upscale_sized(c, (const S*)d_in, k, j, h, w, (S*)d_out, members, s);
+    });
+}
+
 }  // namespace
 
 void sr_yuv_release(sr_ctx* c) {
     sr_free_buf(c->d_yrgb);
     sr_free_buf(c->d_ynet);
+    sr_free_buf(c->d_yres);
 }
 
 // ---- the frame stream ------------------------------------------------------------------------------------------------------------------
@@ -160,6 +263,8 @@ struct sr_video {
     int h = 0, w = 0, slots = 0;
     unsigned members = 1;
     size_t in_bytes = 0, out_bytes = 0;
+    bool sized = false;   // made by sr_video_create*_sized: the output frames are job.oh x job.ow
+    sr_resize_job job{};  // ... the resampling of the network's output to them (one frame)
     struct Slot {
         uint8_t* h_in = nullptr;   // page-locked
         void* d_in = nullptr;
@@ -376,6 +481,7 @@ int video_queue(sr_video* v, unsigned long long frame, bool again = false) {
     if (n_bands == 1 && bands[0].y0 == 0 && bands[0].y1 == v->h) {
         SRCHK(by_sample(v, [&](auto t) {
             using S = decltype(t);
+            if (v->sized) return queue_upscale_sized(c, (const S*)s.d_in, v->k, v->job, v->h, v->w, (S*)s.d_out, v->members, c->stream);
             return queue_upscale(c, (const S*)s.d_in, v->k, 1, v->h, v->w, (S*)s.d_out, v->members, c->stream);
         }));
     } else {
@@ -405,6 +511,10 @@ int video_alloc(sr_video* v) {
     sr_ctx* c = v->c;
     SRCHK(sr_ensure_streams(c, true));
     if (!c->copy_in) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_in, hipStreamNonBlocking));
+    if (v->sized) {  // its workspace now, all or nothing, before anything else is allocated: no frame allocates, and a size that cannot fit is refused by arithmetic
+        const size_t f = (size_t)c->factor;
+        SRCHK(by_sample(v, [&](auto t) { return reserve_sized<decltype(t)>(c, v->job, v->k, (size_t)v->h * v->w * kPxF, f * v->h * f * v->w * kPxF); }));
+    }
     for (int i = 0; i < v->slots; ++i) {
         sr_video::Slot& s = v->slot[i];
         HIPCHK(c, hipHostMalloc((void**)&s.h_in, v->in_bytes, hipHostMallocPortable));
@@ -413,18 +523,30 @@ int video_alloc(sr_video* v) {
         for (hipEvent_t* e : {&s.up, &s.done, &s.down}) HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     for (int i = 0; i <= v->slots; ++i) HIPCHK(c, hipHostMalloc((void**)&v->outs[i], v->out_bytes, hipHostMallocPortable));
+    if (v->sized && c->graph == SR_GRAPH_SR_NET) SRCHK(sr_reserve_features(c, v->h, v->w, c->stream));
     return SR_OK;
 }
 
 // either create call: a session of frames in `fmt` whose samples are `sample` bytes
+// (size: of a sized session, else nullptr)
+struct VideoSize {
+    int oh, ow, filter;
+    unsigned flags;
+};
+
 template <class Format>
-int video_create(sr_ctx* c, const Format* fmt, size_t sample, int h, int w, int slots, unsigned members, sr_video** out) {
+int video_create(sr_ctx* c, const Format* fmt, size_t sample, int h, int w, int slots, unsigned members, sr_video** out,
+                 const VideoSize* size = nullptr) {
     sr_plan_clear(c);
     if (out) *out = nullptr;
     sr_yuv_rule k;
+    sr_resize_job job;
     if (!out || slots < 1 || slots > 8) return SR_E_INVALID;
-    SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
+    if (size) SRCHK(plan_upscale_sized(c, fmt, 1, h, w, size->oh, size->ow, size->filter, size->flags, members, &k, &job));
+    else SRCHK(check_upscale_shape(c, fmt, 1, h, w, members, &k));
     sr_video* v = new sr_video;
+    v->sized = size != nullptr;
+    v->job = job;
     v->c = c;
     v->k = k;
     v->sample = sample;
@@ -433,7 +555,7 @@ int video_create(sr_ctx* c, const Format* fmt, size_t sample, int h, int w, int 
     v->slots = slots;
     v->members = members;
     v->in_bytes = sample * sr_yuv_rule_frame_samples(k, h, w);
-    v->out_bytes = sample * sr_yuv_rule_frame_samples(k, c->factor * h, c->factor * w);
+    v->out_bytes = sample * (size ? sr_yuv_rule_frame_samples(k, size->oh, size->ow) : sr_yuv_rule_frame_samples(k, c->factor * h, c->factor * w));
     const int rc = sr_on_device(c, [&] { return video_alloc(v); });
     if (rc != SR_OK) {
         video_free(v);
@@ -499,6 +621,35 @@ int sr_video_create(sr_ctx* c, const sr_yuv_format* fmt, int h, int w, int slots
 }
 int sr_video_create16(sr_ctx* c, const sr_yuv16_format* fmt, int h, int w, int slots, unsigned members, sr_video** out) {
     return video_create(c, fmt, 2, h, w, slots, members, out);
+}
+
+int sr_resize_to_yuv(sr_ctx* c, const float* rgb, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, int oh, int ow, int filter,
+                     unsigned flags) {
+    return resize_to_yuv_host(c, rgb, fmt, n, h, w, out, oh, ow, filter, flags);
+}
+int sr_resize_to_yuv16(sr_ctx* c, const float* rgb, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, int oh, int ow, int filter,
+                       unsigned flags) {
+    return resize_to_yuv_host(c, rgb, fmt, n, h, w, out, oh, ow, filter, flags);
+}
+
+int sr_upscale_yuv_sized(sr_ctx* c, const uint8_t* in, const sr_yuv_format* fmt, int n, int h, int w, uint8_t* out, int oh, int ow, int filter,
+                         unsigned flags, unsigned members) {
+    return upscale_sized_host(c, in, fmt, n, h, w, out, oh, ow, filter, flags, members);
+}
+int sr_upscale_yuv16_sized(sr_ctx* c, const uint16_t* in, const sr_yuv16_format* fmt, int n, int h, int w, uint16_t* out, int oh, int ow,
+                           int filter, unsigned flags, unsigned members) {
+    return upscale_sized_host(c, in, fmt, n, h, w, out, oh, ow, filter, flags, members);
+}
+
+int sr_video_create_sized(sr_ctx* c, const sr_yuv_format* fmt, int h, int w, int oh, int ow, int filter, unsigned flags, int slots,
+                          unsigned members, sr_video** out) {
+    const VideoSize size{oh, ow, filter, flags};
+    return video_create(c, fmt, 1, h, w, slots, members, out, &size);
+}
+int sr_video_create16_sized(sr_ctx* c, const sr_yuv16_format* fmt, int h, int w, int oh, int ow, int filter, unsigned flags, int slots,
+                            unsigned members, sr_video** out) {
+    const VideoSize size{oh, ow, filter, flags};
+    return video_create(c, fmt, 2, h, w, slots, members, out, &size);
 }
 
 int sr_video_acquire(sr_video* v, uint8_t** in_frame) {
@@ -582,6 +733,7 @@ int sr_rows_differ_dev(sr_ctx* c, const void* d_a, const void* d_b, size_t rows,
 int sr_video_set_reuse(sr_video* v, int mode) {
     if (!v || !v->c || v->failed || v->pending != 0) return SR_E_INVALID;
     if (mode != SR_VIDEO_REUSE_OFF && mode != SR_VIDEO_REUSE_ROWS) return SR_E_INVALID;
+    if (v->sized && mode == SR_VIDEO_REUSE_ROWS) return SR_E_INVALID;  // the row bands do not compose with a vertical resampling
     sr_ctx* c = v->c;
     sr_plan_clear(c);
     v->have_ref = false;  // the next frame is computed whole

@@ -60,7 +60,7 @@ def parse_plan(text: str) -> dict:
     host kind: "one" | "batch" (sizes: images per chunk) | "inorder" | "alternating" (sizes: band rows).  A launch:
     st, form ("first" | "pipe"), ty8, ty4, grid, prec, f, img, out, ch, count (identical launches in a row).  An aux launch (the
     parameter-free graphs): graph, img, ch, grid, units, count; it is multi-round exactly when units > grid.  An op (a launch of a pixel
-    operator: pad, crop, bleed, merge, resize_h, resize_v, yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, yuv16_to_rgb, rgb_to_yuv16, rows_differ (bx: its workgroups), in the order
+    operator: pad, crop, bleed, merge, resize_h, resize_v, resize_v_yuv (its grid: 1024 columns x 2 or 4 rows a workgroup), yuv2rgb, rgb2yuv, u16_to_f32, f32_to_u16, yuv16_to_rgb, rgb_to_yuv16, rows_differ (bx: its workgroups), in the order
     they were queued): name,
     px ("u8" | "f32": the pixels the kernel is instantiated on -- resize_h its input's, resize_v its output's, the two video conversions
     their input's, the two deep-colour and the two deep video conversions their f32 side), n, bx, by (workgroups along a row and along the rows of one image;
@@ -769,6 +769,55 @@ class Engine:
             else:
                 out = res
         return out[0] if squeeze else out
+
+    # ---- video at any size (include/srhip.h "Video at any size") ----
+    def _yuv_host_out(self, tag, out, fmt, n, oh, ow):
+        """The caller's `out`, or a new (n, frame_samples) array for frames of oh x ow (an invalid size: one sample, for the library to refuse)."""
+        dtype, _, os_ = self._yuv_kind(tag, fmt, oh, ow) if oh >= 1 and ow >= 1 else (np.uint8 if tag == "yuv" else np.uint16, None, 0)
+        if out is None:
+            out = np.empty((n, max(os_, 1)), dtype=dtype)
+        elif out.dtype != dtype or (os_ and out.size != n * os_) or not out.flags.c_contiguous:
+            raise ValueError(f"out must be a C-contiguous {'u8' if tag == 'yuv' else 'u16'} array of {n * os_} {'bytes' if tag == 'yuv' else 'samples'}")
+        return out, os_, C.POINTER(C.c_uint8 if tag == "yuv" else C.c_uint16)
+
+    def _resize_to_yuv(self, tag, x, fmt, size, filter, srgb_space, out):
+        x, squeeze, n, h, w, _ = self._host_batch(x, np.float32, 3)
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        out, os_, ptr = self._yuv_host_out(tag, out, fmt, n, oh, ow)
+        _lib.check(getattr(self._L, f"sr_resize_to_{tag}")(self._ctx, C.c_void_p(x.ctypes.data), C.byref(fmt), n, h, w, out.ctypes.data_as(ptr),
+                                                           oh, ow, flt, flags), self._ctx)
+        out = out.reshape(n, os_)
+        return out[0] if squeeze else out
+
+    def _upscale_yuv_sized(self, tag, frames, fmt, h, w, size, filter, srgb_space, members, out):
+        a, squeeze = self._yuv_frames(tag, frames, fmt, h, w)
+        oh, ow, flt, flags = self._resize_args(size, filter, srgb_space)
+        n = a.shape[0]
+        out, os_, ptr = self._yuv_host_out(tag, out, fmt, n, oh, ow)
+        _lib.check(getattr(self._L, f"sr_upscale_{tag}_sized")(self._ctx, a.ctypes.data_as(ptr), C.byref(fmt), n, h, w, out.ctypes.data_as(ptr),
+                                                               oh, ow, flt, flags, self._members(members)), self._ctx)
+        out = out.reshape(n, os_)
+        return out[0] if squeeze else out
+
+    def resize_to_yuv(self, x: np.ndarray, fmt, size, filter="lanczos3", srgb_space=False, out: np.ndarray = None) -> np.ndarray:
+        """sr_resize_to_yuv: (n,h,w,3) or (h,w,3) f32 RGB -> (n, frame_bytes) or (frame_bytes,) u8 frames of size = (oh, ow): the bytes of
+        resize (f32 -> f32) followed by rgb_to_yuv, without the f32 image in between."""
+        return self._resize_to_yuv("yuv", x, fmt, size, filter, srgb_space, out)
+
+    def resize_to_yuv16(self, x: np.ndarray, fmt, size, filter="lanczos3", srgb_space=False, out: np.ndarray = None) -> np.ndarray:
+        """sr_resize_to_yuv16: resize_to_yuv to deep frames, (n, frame_samples) or (frame_samples,) u16."""
+        return self._resize_to_yuv("yuv16", x, fmt, size, filter, srgb_space, out)
+
+    def upscale_yuv_sized(self, frames: np.ndarray, fmt, h: int, w: int, size, filter="lanczos3", srgb_space=False, members: int = 1,
+                          out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_yuv_sized: (n, frame_bytes) or (frame_bytes,) u8 frames of h x w -> the frames of size = (oh, ow) in the same format:
+        the network's f32 output resampled on the GPU and quantised once, at the final size."""
+        return self._upscale_yuv_sized("yuv", frames, fmt, h, w, size, filter, srgb_space, members, out)
+
+    def upscale_yuv16_sized(self, frames: np.ndarray, fmt, h: int, w: int, size, filter="lanczos3", srgb_space=False, members: int = 1,
+                            out: np.ndarray = None) -> np.ndarray:
+        """sr_upscale_yuv16_sized: upscale_yuv_sized on deep frames, u16 in and out."""
+        return self._upscale_yuv_sized("yuv16", frames, fmt, h, w, size, filter, srgb_space, members, out)
 
     def upscale_rgba8_sized(self, px: np.ndarray, size, filter="lanczos3", srgb_space=False, members: int = 1, out: np.ndarray = None) -> np.ndarray:
         """upscale_rgba8 (members == 1) or upscale_ensemble_rgba8 (any other mask) to size = (oh, ow): (n,H,W,4) or (H,W,4) u8 -> (n,oh,ow,4)
@@ -1961,16 +2010,25 @@ class VideoStream:
     of successive frames running under the kernels.  While frames are in flight the engine takes no other call.  `fmt` is a YuvFormat
     or a Yuv16Format (sr_video_create16); either way frames go in and come out as bytes (a u16 array is taken by its bytes).
     reuse=True (sr_video_set_reuse): only the rows a changed input row can reach are computed, the others are the last frame's --
-    the frames received are byte for byte the same; reuse_stats() says what that saved."""
+    the frames received are byte for byte the same; reuse_stats() says what that saved.  size=(oh, ow) (sr_video_create*_sized,
+    "Video at any size"): the frames come out at that size, the network's f32 output resampled with `filter` (srgb_space: in sRGB
+    space) and quantised once; such a session refuses reuse=True with the library's error."""
 
-    def __init__(self, engine: Engine, fmt, h: int, w: int, slots: int = 3, members=None, reuse: bool = False):
+    def __init__(self, engine: Engine, fmt, h: int, w: int, slots: int = 3, members=None, reuse: bool = False, size=None,
+                 filter="lanczos3", srgb_space=False):
         self._L, self._e, self._v = engine._L, engine, C.c_void_p()
         deep = isinstance(fmt, _lib.Yuv16Format)
         frame_bytes, create = (yuv16_frame_bytes, self._L.sr_video_create16) if deep else (yuv_frame_bytes, self._L.sr_video_create)
         self.slots, self.in_bytes = int(slots), frame_bytes(fmt, h, w)
-        self.out_bytes = frame_bytes(fmt, engine.factor * h, engine.factor * w)
-        _lib.check(create(engine._ctx, C.byref(fmt), int(h), int(w), self.slots,
-                                           Engine._members(1 if members is None else members), C.byref(self._v)), engine._ctx)
+        members = Engine._members(1 if members is None else members)
+        if size is None:
+            self.out_bytes = frame_bytes(fmt, engine.factor * h, engine.factor * w)
+            _lib.check(create(engine._ctx, C.byref(fmt), int(h), int(w), self.slots, members, C.byref(self._v)), engine._ctx)
+        else:  # sr_video_create*_sized: the frames come out at size = (oh, ow)
+            oh, ow, flt, flags = Engine._resize_args(size, filter, srgb_space)
+            create = self._L.sr_video_create16_sized if deep else self._L.sr_video_create_sized
+            self.out_bytes = frame_bytes(fmt, oh, ow)
+            _lib.check(create(engine._ctx, C.byref(fmt), int(h), int(w), oh, ow, flt, flags, self.slots, members, C.byref(self._v)), engine._ctx)
         if reuse:
             self.set_reuse(True)
 

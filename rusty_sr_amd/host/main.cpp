@@ -4,7 +4,7 @@
 //   rusty_sr <INPUT_FILE> <OUTPUT_FILE> [-p imagenet|imagenetlinear|anime|bilinear] [-c FILE] [-d]
 //   rusty_sr train [-l] [-r] [-s START] [-f 2|3|4] [-v VAL_FOLDER] [-m N] [--lr_folder DIR] [--val_lr_folder DIR] [--augment] [--degrade SPEC] [--loss LOSS] <PARAMETER_FILE> <TRAINING_FOLDER>
 //   rusty_sr validate [-p imagenet|imagenetlinear|anime | -c FILE] [-l] [-r] [-m N] [--lr_folder DIR] [--metrics [--shave N]] [--degrade SPEC [--seed N]] <VALIDATION_FOLDER>
-//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709|bt2020] [--depth 8|auto] [--siting center|left] [--slots N] [--reuse] [--timing] <IN|-> <OUT|->
+//   rusty_sr video [-p ..|-c FILE] [--precision ..] [--device N] [--ensemble N] [--matrix bt601|bt709|bt2020] [--depth 8|auto] [--siting center|left] [--slots N] [--reuse] [--size WxH|--scale S [--filter F] [--resize-space linear|srgb]] [--timing] <IN|-> <OUT|->
 //
 // `validate` is the validation pass of the reference's `train` sub-command alone (main.rs:220-247, options of main.rs:83-114): the
 // PSNR a parameter set reaches on a folder of HR images.  `video` upscales a YUV4MPEG2 stream frame by frame (y4m.hpp; the reference has
@@ -1299,6 +1299,13 @@ const char kVideoHelp[] =
     "        --slots <N>                  frames in flight [1..8], default 3\n"
     "        --reuse                      compute only the rows that changed since the last frame (letterbox bars, held\n"
     "                                     frames, screen recordings); the output is byte for byte the same\n"
+    "        --size <WxH>                 write frames of exactly this size: the network's f32 output is resampled on the GPU\n"
+    "                                     and quantised once, straight to YCbCr (each axis 1..16384)\n"
+    "        --scale <S>                  the same, S times the INPUT size (--scale 2 with the x3 weights writes 2x frames)\n"
+    "        --filter <FILTER>            with --size / --scale: the resampling filter [values: box, triangle, catrom,\n"
+    "                                     lanczos3]  default: lanczos3\n"
+    "        --resize-space <SPACE>       with --size / --scale: resample in linear light or on the sRGB values [values:\n"
+    "                                     linear, srgb]  default: linear\n"
     "        --timing                     print frames and ms/frame to stderr\n";
 
 int run_video(int argc, char** argv) {
@@ -1307,6 +1314,12 @@ int run_video(int argc, char** argv) {
     bool has_p = false, has_c = false, timing = false, reuse = false;
     long device = 0, slots = 3;
     unsigned ensemble = 0;
+    // --size / --scale: the frames are resampled to a size of the user's choosing (sr_video_create*_sized)
+    bool has_size = false, has_scale = false, has_filter = false, has_space = false;
+    std::string size_arg, scale_arg;
+    int size_w = 0, size_h = 0, filter = SR_FILTER_LANCZOS3;
+    double scale = 0;
+    unsigned resize_flags = 0;
     for (int k = 2; k < argc; ++k) {
         const std::string a = argv[k];
         auto value = [&](const char* name) -> std::string {
@@ -1343,6 +1356,29 @@ int run_video(int argc, char** argv) {
             siting = value("--siting <SITING>");
             if (siting != "center" && siting != "left") video_usage_error("'" + siting + "' isn't a valid value for '--siting <SITING>'\n\t[values: center, left]");
         }
+        else if (a == "--size" || a.rfind("--size=", 0) == 0) {
+            size_arg = a == "--size" ? value("--size <WxH>") : a.substr(7);
+            if (!parse_size(size_arg, size_w, size_h))
+                video_usage_error("'" + size_arg + "' isn't a valid value for '--size <WxH>'\n\t[two whole numbers, 1..16384 each: 3840x2160]");
+            has_size = true;
+        }
+        else if (a == "--scale" || a.rfind("--scale=", 0) == 0) {
+            scale_arg = a == "--scale" ? value("--scale <S>") : a.substr(8);
+            if (!parse_scale(scale_arg, scale)) video_usage_error("'" + scale_arg + "' isn't a valid value for '--scale <S>'\n\t[a positive decimal: 1.5]");
+            has_scale = true;
+        }
+        else if (a == "--filter" || a.rfind("--filter=", 0) == 0) {
+            const std::string v = a == "--filter" ? value("--filter <FILTER>") : a.substr(9);
+            filter = v == "box" ? SR_FILTER_BOX : v == "triangle" ? SR_FILTER_TRIANGLE : v == "catrom" ? SR_FILTER_CATROM : v == "lanczos3" ? SR_FILTER_LANCZOS3 : -1;
+            if (filter < 0) video_usage_error("'" + v + "' isn't a valid value for '--filter <FILTER>'\n\t[values: box, catrom, lanczos3, triangle]");
+            has_filter = true;
+        }
+        else if (a == "--resize-space" || a.rfind("--resize-space=", 0) == 0) {
+            const std::string v = a == "--resize-space" ? value("--resize-space <SPACE>") : a.substr(15);
+            if (v != "linear" && v != "srgb") video_usage_error("'" + v + "' isn't a valid value for '--resize-space <SPACE>'\n\t[values: linear, srgb]");
+            resize_flags = v == "srgb" ? SR_RESIZE_SRGB_SPACE : 0u;
+            has_space = true;
+        }
         else if (a == "--loss") video_usage_error("The argument '--loss' can only be used with the 'train' subcommand");
         else if (a == "--lr" || a == "--lr-schedule" || a == "--warmup" || a == "--clip" || a == "--ema" || a == "--resume") video_usage_error("The argument '" + a + "' can only be used with the 'train' subcommand");
         else if (a.size() > 1 && a[0] == '-') video_usage_error("Found argument '" + a + "' which wasn't expected, or isn't valid in this context");
@@ -1356,6 +1392,11 @@ int run_video(int argc, char** argv) {
     if (precision != "f32" && precision != "split_f16") video_usage_error("'" + precision + "' isn't a valid value for '--precision <MODE>'");
     if (ensemble && parameters == "bilinear")
         video_usage_error("The argument '--ensemble <N>' cannot be used with '--parameters bilinear': bilinear interpolation has no network to average");
+    const bool resize = has_size || has_scale;
+    if (has_size && has_scale) video_usage_error("The argument '--size <WxH>' cannot be used with '--scale <S>'");
+    if ((has_filter || has_space) && !resize) video_usage_error("The following required arguments were not provided:\n    <--size <WxH>|--scale <S>>");
+    if (reuse && resize)
+        video_usage_error(std::string("The argument '--reuse' cannot be used with '") + (has_size ? "--size <WxH>" : "--scale <S>") + "': the row bands do not compose with a vertical resampling");
 
     // ---- the stream header, before anything touches the GPU: a stream this build does not take is refused by the name of its tag
     FILE* fin = pos[0] == "-" ? stdin : fopen(pos[0].c_str(), "rb");
@@ -1378,6 +1419,10 @@ int run_video(int argc, char** argv) {
     fmt16.matrix = matrix == "bt2020" ? SR_YUV_BT2020 : fmt.matrix;
     fmt16.range = fmt.range;
     fmt16.depth = hd.depth;
+    // --scale is relative to the INPUT: max(1, floor(in S + 0.5)) an axis
+    if (has_scale && !(scaled_axis(hd.w, scale, size_w) && scaled_axis(hd.h, scale, size_h)))
+        video_usage_error("'" + scale_arg + "' isn't a valid value for '--scale <S>'\n\t[the output would exceed 16384 pixels on an axis]");
+    const int out_w = resize ? size_w : SR_FACTOR * hd.w, out_h = resize ? size_h : SR_FACTOR * hd.h;
 
     // ---- parameters + graph, the progress text on stderr (stdout may be the stream)
     std::vector<float> params;
@@ -1401,16 +1446,20 @@ int run_video(int argc, char** argv) {
     if (precision == "split_f16" && (rc = sr_set_precision(ctx, SR_PRECISION_SPLIT_F16)) != SR_OK)
         die(std::string(sr_strerror(rc)) + " (SR_PRECISION_SPLIT_F16 cannot carry these parameters; use --precision f32)");
     sr_video* vid = nullptr;
-    rc = deep ? sr_video_create16(ctx, &fmt16, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid)
-              : sr_video_create(ctx, &fmt, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid);
+    if (resize)
+        rc = deep ? sr_video_create16_sized(ctx, &fmt16, hd.h, hd.w, out_h, out_w, filter, resize_flags, (int)slots, ensemble ? ensemble : 1u, &vid)
+                  : sr_video_create_sized(ctx, &fmt, hd.h, hd.w, out_h, out_w, filter, resize_flags, (int)slots, ensemble ? ensemble : 1u, &vid);
+    else
+        rc = deep ? sr_video_create16(ctx, &fmt16, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid)
+                  : sr_video_create(ctx, &fmt, hd.h, hd.w, (int)slots, ensemble ? ensemble : 1u, &vid);
     if (rc != SR_OK) die(sr_strerror(rc));
     if (reuse && (rc = sr_video_set_reuse(vid, SR_VIDEO_REUSE_ROWS)) != SR_OK) die(sr_strerror(rc));
     const size_t in_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, hd.h, hd.w) : sr_yuv_frame_bytes(&fmt, hd.h, hd.w);
-    const size_t out_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, SR_FACTOR * hd.h, SR_FACTOR * hd.w) : sr_yuv_frame_bytes(&fmt, SR_FACTOR * hd.h, SR_FACTOR * hd.w);
+    const size_t out_bytes = deep ? sr_yuv16_frame_bytes(&fmt16, out_h, out_w) : sr_yuv_frame_bytes(&fmt, out_h, out_w);
 
     FILE* fout = pos[1] == "-" ? stdout : fopen(pos[1].c_str(), "wb");
     if (!fout) die("Could not write output stream " + pos[1]);
-    const std::string head = sry4m::scaled_header(hd, SR_FACTOR);
+    const std::string head = resize ? sry4m::sized_header(hd, out_w, out_h) : sry4m::scaled_header(hd, SR_FACTOR);
     bool wrote = fwrite(head.data(), 1, head.size(), fout) == head.size();
     std::deque<std::string> frame_lines;  // the FRAME lines of the frames in flight, oldest first: their parameters pass through
     long frames = 0, written = 0;

@@ -1,6 +1,8 @@
 // y4m.cpp -- the YUV4MPEG2 header parser of `rusty_sr video` (y4m.hpp).
 #include "y4m.hpp"
 
+#include <cstdint>
+
 #include <cstring>
 
 namespace sry4m {
@@ -107,6 +109,58 @@ std::string scaled_header(const Header& h, int factor) {
         s += ' ';
         if (tag[0] == 'W') s += "W" + std::to_string((long)h.w * factor);
         else if (tag[0] == 'H') s += "H" + std::to_string((long)h.h * factor);
+        else s += tag;
+    }
+    s += '\n';
+    return s;
+}
+
+namespace {
+
+// "A<n>:<d>", both terms decimal digits alone, above 0 and small enough for 64-bit arithmetic; false: the tag passes through as it is
+bool parse_aspect(const std::string& tag, uint64_t& n, uint64_t& d) {
+    const size_t colon = tag.find(':');
+    if (colon == std::string::npos || colon < 2 || colon + 1 >= tag.size()) return false;
+    uint64_t v[2] = {0, 0};
+    for (int k = 0; k < 2; ++k) {
+        const size_t b = k ? colon + 1 : 1, e = k ? tag.size() : colon;
+        if (e - b > 18) return false;
+        for (size_t i = b; i < e; ++i) {
+            if (tag[i] < '0' || tag[i] > '9') return false;
+            v[k] = 10 * v[k] + (uint64_t)(tag[i] - '0');
+        }
+    }
+    n = v[0];
+    d = v[1];
+    return n > 0 && d > 0;  // (A0:0 is "unknown"; a single zero term is no ratio)
+}
+
+uint64_t gcd64(uint64_t a, uint64_t b) {
+    while (b) {
+        const uint64_t t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+}  // namespace
+
+std::string sized_header(const Header& h, int ow, int oh) {
+    std::string s = "YUV4MPEG2";
+    for (const std::string& tag : h.tags) {
+        s += ' ';
+        uint64_t n = 0, d = 0, pn = 0, pd = 0;
+        if (tag[0] == 'W') s += "W" + std::to_string(ow);
+        else if (tag[0] == 'H') s += "H" + std::to_string(oh);
+        // the display aspect W n : H d stays: the new pixel aspect is (n W oh) : (d H ow)
+        else if (tag[0] == 'A' && (uint64_t)h.w * (uint64_t)oh == (uint64_t)h.h * (uint64_t)ow) s += tag;  // a uniform resize: the tag it read
+        else if (tag[0] == 'A' && h.w > 0 && h.h > 0 && ow > 0 && oh > 0 && parse_aspect(tag, n, d) &&
+                 !__builtin_mul_overflow(n, (uint64_t)h.w, &pn) && !__builtin_mul_overflow(pn, (uint64_t)oh, &pn) &&
+                 !__builtin_mul_overflow(d, (uint64_t)h.h, &pd) && !__builtin_mul_overflow(pd, (uint64_t)ow, &pd)) {
+            const uint64_t g = gcd64(pn, pd);
+            s += "A" + std::to_string(pn / g) + ":" + std::to_string(pd / g);
+        }
         else s += tag;
     }
     s += '\n';

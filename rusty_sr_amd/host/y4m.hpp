@@ -29,6 +29,10 @@ bool parse_header(const char* line, size_t len, Header& out, std::string& err);
 bool parse_header(const char* line, size_t len, Header& out, std::string& err, bool deep);
 // the header line of the upscaled stream, newline included: every tag repeated, W and H multiplied by the factor
 std::string scaled_header(const Header& h, int factor);
+// the header line of a stream resampled to ow x oh, newline included: every tag repeated, W and H replaced.  The A tag keeps the DISPLAY
+// aspect: absent, A0:0 (unknown) or malformed it passes through; else An:d becomes (n W oh):(d H ow) reduced by their gcd, in 64-bit
+// arithmetic (terms too large for it pass through); a uniform resize (W oh == H ow) writes the tag it read, as written.
+std::string sized_header(const Header& h, int ow, int oh);
 // One line of at most kMaxLine bytes, without its newline.  1: read; 0: end of file before any byte; -1: a line that is too long or
 // ends without a newline.
 int read_line(FILE* f, std::string& line);
