@@ -174,6 +174,29 @@ int sr_upscale_f32_dev(sr_ctx* ctx, const float* d_in, int n, int h, int w, floa
 int sr_upscale_rgba8_dev(sr_ctx* ctx, const uint8_t* d_in, int in_channels, int n, int h, int w,
                          uint8_t* d_out_rgba, void* stream);
 
+/* Stream capture.  Every *_dev entry point of this header may be called while `stream` is being captured (hipStreamBeginCapture,
+ * torch.cuda.graph); tests/test_gpu_graph_capture.py holds each of them to the following, on bytes.
+ *  1. A *_dev call made on a capturing stream launches nothing: it records its launches into the capture -- the second band of a forked
+ *     call included, which joins back to `stream` before the call returns.
+ *  2. Every replay gives, byte for byte, what the eager call gives on the buffers' contents at replay time.  Nothing is baked in but the
+ *     pointers, the shapes, the mode (sr_set_precision, sr_set_loss and the switches of srhip_experimental.h as they stood at capture) and the
+ *     scalar arguments.
+ *  3. A graph stays valid while no later call on the context grows or frees a buffer -- no larger shape, no sr_destroy -- and while
+ *     sr_set_params, sr_set_precision, sr_set_loss and the setter of srhip_experimental.h are not called.  Replaying a graph after such
+ *     a call is UNDEFINED: its nodes may point into freed memory.  Destroy the graph first.
+ *  4. Eager calls on the same context, *_dev or host-pointer, of any shape within the reserved capacity may run between replays,
+ *     serialised by the caller.  Neither side changes the other's bytes: from its first captured call on, a context clears the borders
+ *     of its feature maps with every pass, eager or replayed, instead of trusting the geometry it last saw.
+ *  5. A call that would have to allocate, free, create a stream or an event, or upload a first-use table while its stream is capturing
+ *     returns SR_E_INVALID before it launches, allocates or frees anything: the capture stays valid and the context usable.  The
+ *     remedy: sr_reserve_* or one eager call of that shape (and mode) first.  A forked plan whose second stream or workspace does not
+ *     exist yet is recorded undivided instead where the first workspace holds the whole image.  A sharded call of more than one rank
+ *     is not recorded at all (SR_E_INVALID): its exchange runs on the communicator's terms.
+ *  6. stream = NULL cannot be captured, and the library cannot see such a capture: do not try.
+ *  7. sr_check_domain after a replay reports what the replayed kernels saw: the flag lives in mapped host memory.
+ *  8. The fork tuner takes no sample from a captured call, and sr_set_profiling times none.  A captured call runs the rule's plan,
+ *     whatever the tuner has measured or decided for the shape. */
+
 /* Row-band form for images sharded across GPUs.  d_in holds h_ext = halo_top +
  * h_band + halo_bot input rows of ONE image of width w; halo_top / halo_bot are
  * the rows that belong to the neighbouring bands (0 = this edge is the true

@@ -6,6 +6,10 @@
  * scripts/fork_ab.py, scripts/band_profile.py) and for the tests that prove bit-identity across kernel forms and tile
  * plans (tests/test_gpu_parity.py).  Keys, values and defaults may change between builds; a host that binds
  * include/srhip.h alone (rust_host/src/srhip.rs, the C++ CLI) never needs this file.
+ *
+ * Stream capture (include/srhip.h): a captured *_dev call records the plan that the switches stood for when it was captured, and
+ * sr_set_experiment is one of the calls after which replaying a graph of this context is undefined ("fork" and "forktune" can free or
+ * re-plan what its nodes point to).  Set the switches first, capture afterwards.
  */
 #ifndef SRHIP_EXPERIMENTAL_H
 #define SRHIP_EXPERIMENTAL_H

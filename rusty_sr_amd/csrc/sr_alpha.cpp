@@ -33,7 +33,7 @@ int sr_bleed_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int n, int h, int w, int 
     if (radius < 0 || radius > SR_ALPHA_BLEED_MAX) return SR_E_INVALID;
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out) || d_in == d_out) return SR_E_INVALID;
     if (sr_alpha_bleed_blocks(n, h, w) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    return sr_on_device(c, [&] { return sr_alpha_queue_bleed(c, d_in, d_out, n, h, w, radius, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return sr_alpha_queue_bleed(c, d_in, d_out, n, h, w, radius, (hipStream_t)stream); });
 }
 
 int sr_merge_alpha_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int n, int h, int w, uint8_t* d_out, void* stream) {
@@ -41,7 +41,7 @@ int sr_merge_alpha_rgba8_dev(sr_ctx* c, const uint8_t* d_lr, int n, int h, int w
     SRCHK(sr_net_check(c, d_lr, d_out, n, h, w, 1u));  // (the shapes and graphs of the composed call, no ensemble)
     if (!sr_dword_aligned(d_lr) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
     if (sr_alpha_merge_blocks(c->factor, n, h, w) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    return sr_on_device(c, [&] { return sr_alpha_queue_merge(c, d_lr, d_out, n, h, w, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return sr_alpha_queue_merge(c, d_lr, d_out, n, h, w, (hipStream_t)stream); });
 }
 
 }  // extern "C"

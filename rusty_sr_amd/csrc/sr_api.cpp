@@ -651,6 +651,8 @@ int ensure_features(sr_ctx* c, sr_ctx::Workspace& w, int n, int H, int W, int ti
     const long rows = (long)H + kFeatPad + kFeatPadBottom;
     const long img_stride = rows * pitch;
     const size_t npx = (size_t)n * img_stride + (size_t)kFeatPad * pitch + 64;  // slack for the row above image 0
+    if (sr_capture_refuses(c, npx > w.feat_cap_px)) return SR_E_INVALID;
+    if (c->capturing) w.captured = true;
     if (npx > w.feat_cap_px) {
         for (auto& p : w.d_feat) {
             if (p) HIPCHK(c, hipFree(p));
@@ -664,9 +666,11 @@ int ensure_features(sr_ctx* c, sr_ctx::Workspace& w, int n, int H, int W, int ti
         for (auto& p : w.d_feat) HIPCHK(c, hipMemsetAsync(p, 0, npx * 32 * sizeof(float), s));
         w.geo_n = n; w.geo_h = H; w.geo_w = W;
     }
-    if (w.geo_n != n || w.geo_h != H || w.geo_w != W) {
+    if (w.captured || w.geo_n != n || w.geo_h != H || w.geo_w != W) {
         // another geometry in the same allocation: what was interior may now be border.  Only the border is cleared
         // (1080p: 6 MB per map instead of 270 MB), so a context that meets a new image size per call pays microseconds.
+        // Once a pass on these maps has been captured, the clear is queued with EVERY pass, captured or not: a graph replays whenever
+        // its owner likes, between calls of other geometries, so the geometry tracked here no longer says what the maps hold.
         ClearArgs ca{};
         for (int k = 0; k < 4; ++k) ca.map[k] = w.d_feat[k];
         ca.n = n; ca.H = H; ca.W = W; ca.pitch = pitch; ca.img_stride = img_stride; ca.total_px = (long)npx;
@@ -680,6 +684,39 @@ int ensure_features(sr_ctx* c, sr_ctx::Workspace& w, int n, int H, int W, int ti
 
 }  // namespace
 
+// ensure_features would not have to allocate: the maps hold n images of H x W
+static bool features_fit(const sr_ctx::Workspace& w, int n, int H, int W) {
+    const int pitch = (W + 31) / 32 * 32 + 2 * kFeatPad;
+    const long rows = (long)H + kFeatPad + kFeatPadBottom;
+    return (size_t)n * rows * pitch + (size_t)kFeatPad * pitch + 64 <= w.feat_cap_px;
+}
+
+// The plan of a device call on a capturing stream (include/srhip.h "Stream capture"): the rule's -- the fork tuner neither decides nor
+// samples there -- with the second band given up where its stream, events or maps do not exist yet.  SR_E_INVALID: the call would have to
+// allocate.  *fork: run as two bands, the first of *rows_a rows.
+static int capture_plan(sr_ctx* c, bool img_u8, int img_ch, int n, int H, int W, int halo_top, int halo_bot, bool* fork, int* rows_a) {
+    *fork = false;
+    if (c->graph != SR_GRAPH_SR_NET) return SR_OK;
+    if (sr_plan_fork(*c, c->env_fork, img_u8, img_ch, n, H, W, halo_top, halo_bot, rows_a)) {  // (a tunable shape has no "fork" set: the rule)
+        sr_fork_band fb[2];
+        sr_fork_bands(H, halo_top, halo_bot, *rows_a, fb);
+        *fork = c->stream2 && c->ev_fork[0] && c->ev_fork[1] && features_fit(c->ws[0], 1, fb[0].H, W) && features_fit(c->ws[1], 1, fb[1].H, W);
+        if (*fork) return SR_OK;
+    }
+    return features_fit(c->ws[0], n, H, W) ? SR_OK : SR_E_INVALID;
+}
+
+int sr_net_capture_ready(sr_ctx* c, bool u8, int ch, int n, int h, int w, unsigned members) {
+    if (!c->capturing) return SR_OK;
+    bool fork = false;
+    int rows_a = 0;
+    if (members == 1u) return capture_plan(c, u8, ch, n, h, w, 0, 0, &fork, &rows_a);
+    // an ensemble runs its members one image at a time on f32 copies: members 0-3 as the image lies, 4-7 transposed
+    if (members & 0x0fu) SRCHK(capture_plan(c, false, 3, 1, h, w, 0, 0, &fork, &rows_a));
+    if (members & 0xf0u) SRCHK(capture_plan(c, false, 3, 1, w, h, 0, 0, &fork, &rows_a));
+    return SR_OK;
+}
+
 // Workspace 0's feature maps for one image of H x W, allocated now (a later pass over fewer rows finds them large enough: the frame
 // stream's row bands, sr_yuv.cpp).  The context's device is current.
 int sr_reserve_features(sr_ctx* c, int H, int W, hipStream_t s) { return ensure_features(c, c->ws[0], 1, H, W, (W + 31) / 32, s); }
@@ -687,6 +724,7 @@ int sr_reserve_features(sr_ctx* c, int H, int W, hipStream_t s) { return ensure_
 // The context's own streams, created when first needed: `stream` for everything the library runs by itself, and for a
 // pipelined host call a second compute stream and the download stream.
 int sr_ensure_streams(sr_ctx* c, bool pipelined) {
+    if (sr_capture_refuses(c, !c->stream || (pipelined && (!c->stream2 || !c->copy_out)))) return SR_E_INVALID;
     if (!c->stream) HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     if (pipelined) {
         if (!c->stream2) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
@@ -697,6 +735,7 @@ int sr_ensure_streams(sr_ctx* c, bool pipelined) {
 
 int sr_ensure_buf(sr_ctx* c, sr_buf& b, size_t bytes) {
     if (bytes <= b.cap) return SR_OK;
+    if (sr_capture_refuses(c, true)) return SR_E_INVALID;
     if (b.p) HIPCHK(c, hipFree(b.p));
     b = sr_buf{};
     HIPCHK(c, hipMalloc(&b.p, bytes));
@@ -705,6 +744,8 @@ int sr_ensure_buf(sr_ctx* c, sr_buf& b, size_t bytes) {
 }
 
 int sr_ensure_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group) {
+    for (const sr_buf_want& w : group)  // (on a capturing stream nothing grows, and nothing of the group is given back either)
+        if (sr_capture_refuses(c, w.bytes > w.buf->cap)) return SR_E_INVALID;
     for (const sr_buf_want& w : group) {
         const int rc = sr_ensure_buf(c, *w.buf, w.bytes);
         if (rc == SR_OK) continue;
@@ -722,6 +763,7 @@ int sr_host_call(sr_ctx* c, bool network, sr_host_times times, std::initializer_
                  const sr_host_phase& work, const sr_host_phase& download) {
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
+    c->capturing = false;  // (the context's own stream)
     SRCHK(sr_ensure_streams(c, false));
     if (network) sr_domain_set_aside(c);
     SRCHK(sr_ensure_bufs(c, staging));
@@ -785,6 +827,7 @@ int sr_reserve_bufs(sr_ctx* c, std::initializer_list<sr_buf_want> group) {
     bool fits = true;
     for (const sr_buf_want& w : group) fits = fits && w.bytes <= w.buf->cap;
     if (fits) return SR_OK;
+    if (sr_capture_refuses(c, true)) return SR_E_INVALID;
     if (!c->total_mem) HIPCHK(c, hipDeviceTotalMem(&c->total_mem, c->device));
     size_t all = 0;
     if (!sr_sum_wants(group, &all) || all > c->total_mem) return SR_E_NOMEM;
@@ -959,8 +1002,9 @@ int sr_run_stack(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int n, i
     // the context's own non-blocking stream is used only by the host-pointer entry points.
     StackJob job = stack_job(c, slot, d_img, img_u8, img_ch, n, H, W, halo_top, H - halo_bot, d_out, out_u8, s, gate);
     SRCHK(job.prepare());
-    const bool prof = c->profiling;
-    static const bool trace_stages = [] { const char* e = getenv("SRHIP_TRACE"); return e && atoi(e) >= 2; }();
+    const bool prof = c->profiling && !c->capturing;  // (the stage events are waited for below: not on a capturing stream)
+    static const bool trace_stages_env = [] { const char* e = getenv("SRHIP_TRACE"); return e && atoi(e) >= 2; }();
+    const bool trace_stages = trace_stages_env && !c->capturing;
     if (prof) HIPCHK(c, hipEventRecord(c->ev[0], s));
     for (int st = 0; st < 5; ++st) {
         SRCHK(job.launch(st));
@@ -1094,6 +1138,7 @@ void sr_fork_tune_clear(sr_ctx* c) {
 }
 
 int sr_ensure_fork_resources(sr_ctx* c) {
+    if (sr_capture_refuses(c, !c->stream2 || !c->ev_fork[0] || !c->ev_fork[1])) return SR_E_INVALID;
     if (!c->stream2) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
     for (auto& e : c->ev_fork) if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     return SR_OK;
@@ -1108,7 +1153,14 @@ int sr_run_stack_auto(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
     int mode = c->env_fork;
     sr_ctx::ForkTune* tune = nullptr;
     bool sample = false;
-    if (sr_fork_tunable(*c, n, H, W, halo_top, halo_bot, gate != nullptr)) {
+    if (c->capturing) {
+        // Nothing may be allocated and no event of the tuner's recorded or read (a captured call is no sample: its events never fire, and
+        // a replay is not this call).  Decided before the fork event, so that a refusal leaves the capture as it was.
+        bool fork = false;
+        HIPCHK(c, hipSetDevice(c->device));
+        SRCHK(capture_plan(c, img_u8, img_ch, n, H, W, halo_top, halo_bot, &fork, &rows_a));
+        mode = fork ? c->env_fork : 0;
+    } else if (sr_fork_tunable(*c, n, H, W, halo_top, halo_bot, gate != nullptr)) {
         HIPCHK(c, hipSetDevice(c->device));
         tune = fork_tune_entry(c, img_u8, out_u8, img_ch, H, W, halo_top, halo_bot);
         if (tune) {
@@ -1193,6 +1245,7 @@ int run_host(sr_ctx* c, const void* in, bool img_u8, int img_ch, sr_deal deal, i
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     c->band_pending = false;  // (an earlier sharded call's event pairs are not this call's timing)
+    c->capturing = false;     // (the context's own streams)
     const size_t in_px = img_u8 ? (size_t)img_ch : 3 * sizeof(float), out_px = out_u8 ? 4 : 3 * sizeof(float);
     if (y_hi < 0) y_hi = h;
     if (y_lo < 0 || y_hi > h || y_lo >= y_hi) return SR_E_INVALID;
@@ -1344,6 +1397,7 @@ int sr_check_context_set(sr_ctx* const* ctxs, int n_ctx) {
 extern "C" {
 
 int sr_upscale_f32_dev(sr_ctx* c, const float* d_in, int n, int h, int w, float* d_out, void* stream) {
+    sr_capture_scope capture(c, stream);
     sr_plan_clear(c);
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, false, 3, n, h, w, 0, 0, d_out, false, (hipStream_t)stream);
@@ -1351,6 +1405,7 @@ int sr_upscale_f32_dev(sr_ctx* c, const float* d_in, int n, int h, int w, float*
 
 int sr_upscale_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int n, int h, int w,
                          uint8_t* d_out, void* stream) {
+    sr_capture_scope capture(c, stream);
     sr_plan_clear(c);
     if (!sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, true, in_channels, n, h, w, 0, 0, d_out, true, (hipStream_t)stream);
@@ -1358,6 +1413,7 @@ int sr_upscale_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int n,
 
 int sr_upscale_band_f32_dev(sr_ctx* c, const float* d_in, int h_ext, int w, int halo_top, int halo_bot,
                             float* d_out, void* stream) {
+    sr_capture_scope capture(c, stream);
     sr_plan_clear(c);
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, false, 3, 1, h_ext, w, halo_top, halo_bot, d_out, false, (hipStream_t)stream);
@@ -1365,6 +1421,7 @@ int sr_upscale_band_f32_dev(sr_ctx* c, const float* d_in, int h_ext, int w, int 
 
 int sr_upscale_band_rgba8_dev(sr_ctx* c, const uint8_t* d_in, int in_channels, int h_ext, int w,
                               int halo_top, int halo_bot, uint8_t* d_out, void* stream) {
+    sr_capture_scope capture(c, stream);
     sr_plan_clear(c);
     if (!sr_dword_aligned(d_out)) return SR_E_INVALID;
     return sr_run_stack_auto(c, d_in, true, in_channels, 1, h_ext, w, halo_top, halo_bot, d_out, true,

@@ -77,6 +77,7 @@ int queue_composed(sr_ctx* c, const void* d_in, bool u8, int n, int h, int w, vo
     const size_t bled_bytes = bleed > 0 ? (size_t)n * h * w * kPx8 : 0;
     SRCHK(border ? sr_reserve_bufs(c, {{&c->d_bpad, pad_bytes}, {&c->d_bout, big_bytes}, {&c->d_ableed, bled_bytes}})
                  : sr_reserve_bufs(c, {{&c->d_ableed, bled_bytes}}));
+    SRCHK(sr_net_capture_ready(c, u8, u8 ? 4 : 3, n, H, W, a.members));
     const void* img = d_in;
     if (bleed > 0) {
         SRCHK(sr_alpha_queue_bleed(c, (const uint8_t*)d_in, (uint8_t*)c->d_ableed.p, n, h, w, bleed, s));
@@ -93,7 +94,7 @@ int composed_dev(sr_ctx* c, const void* d_in, bool u8, int n, int h, int w, void
     sr_plan_clear(c);
     SRCHK(check_upscale_args(c, d_in, d_out, n, h, w, a));
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_composed(c, d_in, u8, n, h, w, d_out, a, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_composed(c, d_in, u8, n, h, w, d_out, a, (hipStream_t)stream); });
 }
 
 // The host-pointer calls (sr_host_image_call).  sr_last_timing: total = every launch of the call, h2d / d2h the two copies.
@@ -112,7 +113,7 @@ int pad_dev(sr_ctx* c, const void* d_in, bool f32, int n, int h, int w, int mode
     if (!mode_ok(mode) || pad < 0 || pad > SR_BORDER_PAD_MAX) return SR_E_INVALID;
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out) || d_in == d_out) return SR_E_INVALID;
     if (sr_border_pad_blocks(f32, n, h, w, pad) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    return sr_on_device(c, [&] { return queue_pad(c, d_in, f32, n, h, w, mode, pad, d_out, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_pad(c, d_in, f32, n, h, w, mode, pad, d_out, (hipStream_t)stream); });
 }
 
 int crop_dev(sr_ctx* c, const void* d_in, bool f32, int n, int H, int W, int y0, int x0, int ch, int cw, void* d_out, void* stream) {
@@ -121,7 +122,7 @@ int crop_dev(sr_ctx* c, const void* d_in, bool f32, int n, int H, int W, int y0,
     if (y0 < 0 || x0 < 0 || ch > H - y0 || cw > W - x0) return SR_E_INVALID;  // the window lies inside its image
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out) || d_in == d_out) return SR_E_INVALID;
     if (sr_border_crop_blocks(f32, n, ch, cw) > (size_t)INT32_MAX) return SR_E_NOMEM;
-    return sr_on_device(c, [&] { return queue_crop(c, d_in, f32, n, H, W, y0, x0, ch, cw, d_out, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_crop(c, d_in, f32, n, H, W, y0, x0, ch, cw, d_out, (hipStream_t)stream); });
 }
 
 }  // namespace

@@ -135,6 +135,11 @@ int prepare_band(sr_ctx* c, const void* d_band, int h_band, int w, size_t px_byt
     if (c->graph != SR_GRAPH_SR_NET) return SR_E_INVALID;
     if (c->comm_broken || (c->comm_nranks > 1 && !c->comm && !c->comm_local)) return SR_E_COMM;
     if (c->comm_nranks > 1 && h_band < SR_HALO) return SR_E_HALO;  // a neighbour reads SR_HALO rows of this band
+    // Stream capture (include/srhip.h): a band that exchanges halos is not recorded -- the exchange runs on the communicator's terms --
+    // and the band that stands alone records no timing events (they are waited for: sr_last_timing) and creates nothing.
+    if (c->capturing && c->comm_nranks > 1) return SR_E_INVALID;
+    if (sr_capture_refuses(c, !c->ev_comm[0] || !c->ev_comm[1] || !c->ev_band[0] || !c->ev_band[1] || !c->ev_wait[0] || !c->ev_wait[1] || !c->ev_xfork))
+        return SR_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     g = band_geom(c, h_band, w, px_bytes);
     const int rc = sr_ensure_buf(c, c->d_ext, (size_t)g.h_ext * g.row_bytes);
@@ -148,7 +153,7 @@ int prepare_band(sr_ctx* c, const void* d_band, int h_band, int w, size_t px_byt
     for (auto& e : c->ev_wait) if (!e) HIPCHK(c, hipEventCreate(&e));
     if (!c->ev_xfork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_xfork, hipEventDisableTiming));
     c->comm_pending = c->band_pending = c->wait_pending = false;
-    HIPCHK(c, hipEventRecord(c->ev_band[0], s));
+    if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_band[0], s));
     if (c->comm_nranks > 1) {
         // the exchange stream starts where the band's stream stands now: the caller's producers of d_band are done, and so is every
         // earlier call's reader of d_ext (the receives land there)
@@ -252,6 +257,7 @@ int run_sharded(sr_ctx* c, const void* d_band, bool u8, int img_ch, int h_band, 
     if (c->layer_halos && c->comm_nranks > 1) rc = run_layers_rank(c, rccl(), u8, img_ch, h_band, w, g, d_out, &gate, s);
     else rc = sr_run_stack_auto(c, c->d_ext.p, u8, img_ch, 1, g.h_ext, w, g.top, g.bot, d_out, u8, s, c->comm_nranks > 1 ? &gate : nullptr);
     if (rc != SR_OK) return rc;
+    if (c->capturing) return SR_OK;
     HIPCHK(c, hipEventRecord(c->ev_band[1], s));
     c->comm_pending = c->wait_pending = c->comm_nranks > 1;
     // (with per-stage profiling on, sr_last_timing reports the conv stack's own events -- which the stage-by-stage pass of the layer-halo form does not record)
@@ -574,12 +580,14 @@ int sr_last_comm_exposed_ms(sr_ctx* c, double* exposed_ms) {
 }
 
 int sr_upscale_sharded_f32_dev(sr_ctx* c, const float* d_band, int h_band, int w, float* d_out, void* stream) {
+    sr_capture_scope capture(c, stream);
     sr_plan_clear(c);
     return run_sharded(c, d_band, false, 3, h_band, w, d_out, (hipStream_t)stream);
 }
 
 int sr_upscale_sharded_rgba8_dev(sr_ctx* c, const uint8_t* d_band, int in_channels, int h_band, int w, uint8_t* d_out,
                                  void* stream) {
+    sr_capture_scope capture(c, stream);
     sr_plan_clear(c);
     return run_sharded(c, d_band, true, in_channels, h_band, w, d_out, (hipStream_t)stream);
 }

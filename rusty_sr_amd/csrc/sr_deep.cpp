@@ -108,6 +108,16 @@ int nested(sr_ctx* c, Call&& call) {
 int queue_job(sr_ctx* c, const Job& j, const uint16_t* d_in, uint16_t* d_out, hipStream_t s) {
     if (sr_deep_blocks(j.in_px) > (size_t)INT32_MAX || sr_deep_blocks(j.out_px) > (size_t)INT32_MAX) return SR_E_NOMEM;
     SRCHK(sr_reserve_bufs(c, {{&c->d_kin, j.in_px * kPxF}, {&c->d_knet, j.net_px * kPxF}, {&c->d_kres, j.kind == Job::SIZED ? j.out_px * kPxF : 0}}));
+    if (c->capturing) {  // on a capturing stream the later phases' buffers stand too before the first launch: nothing can be reserved there
+        const size_t H = (size_t)j.h + 2 * (size_t)j.pad, W = (size_t)j.w + 2 * (size_t)j.pad, f = (size_t)c->factor;
+        sr_resize_job r;
+        if (j.kind == Job::BORDER && (sr_capture_refuses(c, (size_t)j.n * H * W * kPxF > c->d_bpad.cap) || sr_capture_refuses(c, (size_t)j.n * f * H * f * W * kPxF > c->d_bout.cap)))
+            return SR_E_INVALID;
+        if (j.kind == Job::SIZED && (sr_resize_plan(j.n, j.nh, j.nw, j.oh, j.ow, j.filter, j.flags, &r) != SR_OK ||
+                                     sr_capture_refuses(c, r.tab_bytes > c->d_rtab.cap) || sr_capture_refuses(c, r.mid_bytes > c->d_rmid.cap)))
+            return SR_E_INVALID;
+        SRCHK(sr_net_capture_ready(c, false, 3, j.n, j.kind == Job::BORDER ? (int)H : j.h, j.kind == Job::BORDER ? (int)W : j.w, j.members));
+    }
     float* kin = (float*)c->d_kin.p;
     float* knet = (float*)c->d_knet.p;
     SRCHK(queue_to_f32(c, d_in, j.ic, j.in_px, kin, s));
@@ -129,7 +139,7 @@ int queue_job(sr_ctx* c, const Job& j, const uint16_t* d_in, uint16_t* d_out, hi
 int job_dev(sr_ctx* c, const uint16_t* d_in, uint16_t* d_out, Job j, void* stream) {
     sr_plan_clear(c);
     SRCHK(check_job(c, d_in, d_out, &j));
-    return sr_on_device(c, [&] { return queue_job(c, j, d_in, d_out, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_job(c, j, d_in, d_out, (hipStream_t)stream); });
 }
 
 // The host-pointer calls (sr_host_image_call).  sr_last_timing: total = every launch of the call, h2d / d2h the two copies.
@@ -172,14 +182,14 @@ int sr_u16_to_f32_dev(sr_ctx* c, const uint16_t* d_in, int in_channels, int n, i
     sr_plan_clear(c);
     size_t npx = 0;
     SRCHK(check_convert(c, d_in, d_out, in_channels_ok(in_channels), n, h, w, &npx));
-    return sr_on_device(c, [&] { return queue_to_f32(c, d_in, in_channels, npx, d_out, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_to_f32(c, d_in, in_channels, npx, d_out, (hipStream_t)stream); });
 }
 
 int sr_f32_to_u16_dev(sr_ctx* c, const float* d_in, int n, int h, int w, uint16_t* d_out, int out_channels, void* stream) {
     sr_plan_clear(c);
     size_t npx = 0;
     SRCHK(check_convert(c, d_out, d_in, out_channels_ok(out_channels), n, h, w, &npx));
-    return sr_on_device(c, [&] { return queue_to_u16(c, d_in, npx, d_out, out_channels, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_to_u16(c, d_in, npx, d_out, out_channels, (hipStream_t)stream); });
 }
 
 int sr_upscale_u16_dev(sr_ctx* c, const uint16_t* d_in, int in_channels, int n, int h, int w, uint16_t* d_out, int out_channels,

@@ -45,6 +45,7 @@ int sr_degrade_radius(const sr_degrade& g) {
 
 int sr_degrade_ensure_table(sr_ctx* c) {
     if (c->d_dtab) return SR_OK;
+    if (sr_capture_refuses(c, true)) return SR_E_INVALID;  // (the upload is synchronous)
     double tab[256 + 64];
     for (int b = 0; b < 256; ++b) {
         const double s = (double)b / 255.0;
@@ -78,7 +79,7 @@ int sr_degrade_rgba8_dev(sr_ctx* c, const uint8_t* d_hr, int in_channels, int h,
     sr_plan_clear(c);
     sr_degrade_one job;
     SRCHK(plan_degrade(c, d_hr, in_channels, h, w, factor, y0, x0, frame_h, frame_w, member, deg, d_lr_rgb, &job));
-    return sr_on_device(c, [&] { return queue_degrade(c, job, d_lr_rgb, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_degrade(c, job, d_lr_rgb, (hipStream_t)stream); });
 }
 
 int sr_degrade_rgba8(sr_ctx* c, const uint8_t* hr, int in_channels, int h, int w, int factor, int y0, int x0, int frame_h, int frame_w, int member,

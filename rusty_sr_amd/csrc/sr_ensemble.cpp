@@ -61,7 +61,7 @@ int ensemble_dev(sr_ctx* c, const void* d_in, bool img_u8, int ch, int n, int h,
     sr_plan_clear(c);
     SRCHK(check_image_args(c, d_in, d_out, img_u8, ch, n, h, w, members));
     if (!sr_dword_aligned(d_out) || (!img_u8 && !sr_dword_aligned(d_in))) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_batch(c, d_in, img_u8, ch, n, h, w, d_out, out_u8, members, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_batch(c, d_in, img_u8, ch, n, h, w, d_out, out_u8, members, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -91,6 +91,7 @@ int sr_ensemble_queue(sr_ctx* c, const void* d_img, bool img_u8, int img_ch, int
     const size_t blocks = std::max(sr_ens_blocks(OH, OW, false), sr_ens_blocks(OH, OW, true));
     if (blocks > (size_t)INT32_MAX) return SR_E_NOMEM;
     SRCHK(sr_reserve_bufs(c, {{&c->d_ein, in_bytes}, {&c->d_eout, map_bytes}, {&c->d_eacc, acc_bytes}}));
+    SRCHK(sr_net_capture_ready(c, false, 3, 1, h, w, members));
     float* acc = out_u8 ? (float*)c->d_eacc.p : (float*)d_out;
     const float scale = 1.0f / (float)count;
     int done = 0;

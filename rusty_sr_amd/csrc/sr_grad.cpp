@@ -81,6 +81,7 @@ int backprop_dev(sr_ctx* c, const float* d_params, bool pair, const uint8_t* d_l
     const int rc = pair ? check_pair_args(c, d_params, d_lr, true, lr_ch, d_hr, ch, n, h, w, d_grad) : check_args(c, d_params, d_hr, true, ch, n, h, w, d_grad);
     if (rc != SR_OK) return rc;
     if (!d_err_sum || !sr_dword_aligned(d_err_sum) || !sr_dword_aligned(d_params) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
+    sr_capture_scope capture(c, stream);
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     sr_lr_input in;
@@ -210,6 +211,7 @@ int sr_adam_step_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v, const f
     if (!sr_dword_aligned(d_params) || !sr_dword_aligned(d_m) || !sr_dword_aligned(d_v) || !sr_dword_aligned(d_grad)) return SR_E_INVALID;
     // bias corrections 1 - beta^t, in f32
     const float bc1 = 1.0f - std::pow(beta1, (float)step), bc2 = 1.0f - std::pow(beta2, (float)step);
+    sr_capture_scope capture(c, stream);
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sr_launch_grad_adam(d_params, d_m, d_v, d_grad, n, lr, beta1, beta2, eps, bc1, bc2, (hipStream_t)stream));

@@ -51,6 +51,8 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
         float* d_feat[4] = {nullptr, nullptr, nullptr, nullptr};  // f, l1, l2, l3 (zero-bordered, see sr_kernels.h)
         size_t feat_cap_px = 0;       // allocated padded pixels per map
         int geo_n = 0, geo_h = 0, geo_w = 0;  // geometry the borders were last zeroed for
+        bool captured = false;        // a pass on these maps was recorded into a stream capture: a replay writes them behind the host's back, so
+                                      // geo_* says nothing any more and every pass from then on clears its borders (ensure_features)
         int pitch = 0; long img_stride = 0;
         int* d_queue = nullptr;       // 5 stages x 8 per-XCD tile-queue heads (persistent kernels)
     } ws[2];
@@ -66,6 +68,10 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     double total_ms = 0, stage_ms[5] = {0}, h2d_ms = 0, d2h_ms = 0;
     int last_h = 0, last_w = 0;
     int last_hip = 0;
+    // Stream capture (include/srhip.h "Stream capture"): the stream of the *_dev call in progress is being captured (sr_capture_scope).
+    // Such a call records its launches and may do nothing else: whatever would allocate, free or upload refuses with SR_E_INVALID
+    // (sr_capture_refuses), the fork tuner and the profiling events stand aside.
+    bool capturing = false;
     // experiment switches beside the planners' (sr_plan_env), read once at sr_create like them
     int env_bw = -1;                  // tile-order column-block width in tiles (-1: automatic)
     hipEvent_t ev_fork[2] = {nullptr, nullptr};  // fork (caller's stream -> stream2) and join (stream2 -> caller's stream)
@@ -338,6 +344,31 @@ inline int sr_hip_status(sr_ctx* c, hipError_t e) {  // HIPCHK as a value: the s
     HIPCHK(c, e);
     return SR_OK;
 }
+// Held by every *_dev entry point for its duration: asks the runtime once whether the caller's stream is being captured.  stream = NULL
+// is never asked about: a capture that the legacy stream takes part in is not one the library can see (include/srhip.h).
+struct sr_capture_scope {
+    sr_ctx* c;
+    bool outer = false;  // (a composed call makes entry points of its own: what it found comes back when they return)
+    sr_capture_scope(sr_ctx* ctx, void* stream) : c(ctx) {
+        if (!c) return;
+        outer = c->capturing;
+        c->capturing = false;
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (!stream) return;
+        if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess) { (void)hipGetLastError(); return; }
+        c->capturing = st != hipStreamCaptureStatusNone;
+    }
+    ~sr_capture_scope() { if (c) c->capturing = outer; }
+    sr_capture_scope(const sr_capture_scope&) = delete;
+    sr_capture_scope& operator=(const sr_capture_scope&) = delete;
+};
+// What a call on a capturing stream answers where it would have to allocate, free, create or upload (`needed`): SR_E_INVALID, before
+// it does so.  The remedy: sr_reserve_* or one eager call of that shape first.
+inline bool sr_capture_refuses(const sr_ctx* c, bool needed) { return needed && c->capturing; }
+// The network on n images of h x w (members: an ensemble's mask, 1: the plain call) needs nothing created for a call on a capturing
+// stream -- asked by the composed calls before their first launch; SR_OK off a capture.  The context's device is current.
+int sr_net_capture_ready(sr_ctx* c, bool u8, int ch, int n, int h, int w, unsigned members);
+
 // The body of a device-pointer entry point -- a callable that queues on the caller's stream and returns a status -- with the context's
 // device current and the caller's restored.  The arguments, the alignment rule of the call included, are checked before it.
 template <class Body>
@@ -345,6 +376,11 @@ int sr_on_device(sr_ctx* c, Body&& body) {
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     return body();
+}
+template <class Body>
+int sr_on_device(sr_ctx* c, void* stream, Body&& body) {  // ... of a *_dev entry point: its stream may be capturing
+    sr_capture_scope capture(c, stream);
+    return sr_on_device(c, body);
 }
 // What every call that runs the network on a batch refuses for its arguments alone (SR_E_INVALID): a null context or image, a graph
 // other than sr_net / bilinear, a shape below 1 or beyond INT32_MAX / factor, a mask outside 1..255, a mask other than 1 off sr_net.

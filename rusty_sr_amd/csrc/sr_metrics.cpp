@@ -79,6 +79,7 @@ int sr_image_metrics_rgba8_dev(sr_ctx* c, const uint8_t* d_a, int a_channels, co
     if (rc != SR_OK) return rc;
     if (!d_result16 || !sr_dword_aligned(d_result16)) return SR_E_INVALID;
     rq.d_result16 = d_result16;
+    sr_capture_scope capture(c, stream);
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     return sr_metrics_queue(c, d_a, true, a_channels, w, d_b, b_channels, w, h, w, rq, (hipStream_t)stream);

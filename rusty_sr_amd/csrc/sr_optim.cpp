@@ -29,6 +29,7 @@ int sr_grad_norm_dev(sr_ctx* c, const float* d_grad, size_t n, float clip, sr_gr
     sr_plan_clear(c);
     if (!c || !d_grad || !d_out || n == 0 || sr_optim_parts(n) > (size_t)INT32_MAX || !sr_clip_ok(clip)) return SR_E_INVALID;
     if (!sr_dword_aligned(d_grad) || ((uintptr_t)d_out & 7u)) return SR_E_INVALID;
+    sr_capture_scope capture(c, stream);
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     return sr_grad_norm_queue(c, d_grad, n, clip, d_out, nullptr, (hipStream_t)stream);
@@ -47,6 +48,7 @@ int sr_adam_step_clipped_dev(sr_ctx* c, float* d_params, float* d_m, float* d_v,
     // bias corrections 1 - beta^t, in f32, as sr_adam_step_dev forms them
     const float bc1 = 1.0f - std::pow(beta1, (float)step), bc2 = 1.0f - std::pow(beta2, (float)step);
     const float omd = 1.0f - ema_decay;
+    sr_capture_scope capture(c, stream);
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, sr_launch_adam_clipped(d_params, d_m, d_v, d_grad, d_ema, n, lr, beta1, beta2, eps, bc1, bc2, ema_decay, omd, d_norm, d_skipped,

@@ -75,6 +75,7 @@ int plan_sized(const sr_ctx* c, const void* in, const void* out, int n, int h, i
 int queue_sized(sr_ctx* c, SizedJob& j, const uint8_t* d_in, int h, int w, uint8_t* d_out, unsigned members, hipStream_t s) {
     const int n = j.resize.n;
     SRCHK(reserve(c, j.resize, j.in_bytes, j.net_bytes));
+    SRCHK(sr_net_capture_ready(c, false, 3, n, h, w, members));
     // img_to_data on the device: the ensemble's input pass with the identity map, the batch as one image of n h rows
     if ((size_t)n * h > (size_t)INT32_MAX) return SR_E_NOMEM;
     const sr_ens_map same{n * h, w, 0, 0, 0};
@@ -156,7 +157,7 @@ int sr_resize_dev(sr_ctx* c, const void* d_in, int in_pixels, int n, int h, int 
     ResizeJob j;
     SRCHK(plan_resize(d_in, in_pixels, n, h, w, d_out, out_pixels, oh, ow, filter, flags, &j));
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
-    return sr_on_device(c, [&]() -> int {
+    return sr_on_device(c, stream, [&]() -> int {
         SRCHK(reserve(c, j, 0, 0));
         return queue_resize(c, j, d_in, in_pixels == SR_PIXELS_RGBA8, d_out, out_pixels == SR_PIXELS_RGBA8, (hipStream_t)stream);
     });
@@ -180,7 +181,7 @@ int sr_upscale_rgba8_sized_dev(sr_ctx* c, const uint8_t* d_in, int n, int h, int
     SizedJob j;
     SRCHK(plan_sized(c, d_in, d_out, n, h, w, oh, ow, filter, flags, members, &j));
     if (!sr_dword_aligned(d_in) || !sr_dword_aligned(d_out)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_sized(c, j, d_in, h, w, d_out, members, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_sized(c, j, d_in, h, w, d_out, members, (hipStream_t)stream); });
 }
 
 int sr_upscale_rgba8_sized(sr_ctx* c, const uint8_t* in, int n, int h, int w, uint8_t* out, int oh, int ow, int filter, unsigned flags,

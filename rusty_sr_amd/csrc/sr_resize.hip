@@ -5,7 +5,8 @@
 //                           filter evaluated and the weights normalised in f64, stored as f32.  The weights of an axis are tap-major
 //                           (w[k][o]) and padded with zeros to the axis' tap bound, so that the lanes of the horizontal pass, which own
 //                           consecutive o, read consecutive floats, and the vertical pass, whose o is the same for a whole workgroup,
-//                           reads them through the scalar cache.  Nothing comes from the host: the call stays asynchronous and capturable.
+//                           reads them through the scalar cache.  Nothing comes from the host: the call stays asynchronous, and a capturing stream records
+//                           the launches alone (once the workspace stands: sr_resize.cpp reserves it, and refuses to on such a stream).
 //   resize_h_staged_kernel  columns: a workgroup takes 256 consecutive output columns of R consecutive input rows (the batch is n h rows:
 //                           rows do not see each other).  The input pixels under those columns -- one contiguous run of each row, first
 //                           tap of the first column to last tap of the last -- are read ONCE, as consecutive dwords by consecutive

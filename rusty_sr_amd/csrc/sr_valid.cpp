@@ -14,6 +14,7 @@ namespace {
 // f64 formula -- computed here, so that every device holds the same table and the tests can restate it bit for bit
 int ensure_table(sr_ctx* c) {
     if (c->d_vtab) return SR_OK;
+    if (sr_capture_refuses(c, true)) return SR_E_INVALID;  // (the upload is synchronous)
     float tab[512];
     for (int b = 0; b < 256; ++b) {
         const float s = (float)b / 255.0f;
@@ -55,6 +56,8 @@ int run_validation(sr_ctx* c, const void* d_hr, bool hr_u8, int ch, int h, int w
     int rc = ensure_table(c);
     if (rc == SR_OK) rc = sr_ensure_bufs(c, {{&c->d_vlr, lr_bytes}, {&c->d_vout, out_bytes}, {&c->d_vpart, (size_t)(grid + 1) * sizeof(double)}});
     if (rc == SR_OK && metrics) rc = sr_metrics_reserve(c, HC, WC, metrics->shave);
+    if (rc == SR_OK) rc = sr_net_capture_ready(c, false, 3, 1, OH, OW, members ? members : 1u);
+    if (rc != SR_OK && c->capturing) return rc;  // (refused on a capturing stream: nothing was allocated, nothing is given back)
     c->vnode_h = c->vnode_w = 0;
     if (rc != SR_OK) {  // also when it was the scores' partials that did not fit: the job keeps nothing of its two large buffers
         sr_free_buf(c->d_vlr);
@@ -131,6 +134,7 @@ int validation_dev(sr_ctx* c, bool pair, const uint8_t* d_lr, int lr_ch, const u
     if (!d_err_sum || !sr_dword_aligned(d_err_sum)) return SR_E_INVALID;
     if (with_metrics && (!d_result16 || !sr_dword_aligned(d_result16))) return SR_E_INVALID;
     rq.d_result16 = d_result16;
+    sr_capture_scope capture(c, stream);
     sr_device_guard restore_device;
     HIPCHK(c, hipSetDevice(c->device));
     sr_lr_input in;

@@ -91,6 +91,7 @@ int queue_upscale(sr_ctx* c, const S* d_in, const sr_yuv_rule& k, int n, int h, 
     const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;
     if (out_img / kPxF / (f * w) != f * h || out_img > SIZE_MAX / (size_t)n) return SR_E_NOMEM;
     SRCHK(sr_reserve_bufs(c, {{&c->d_yrgb, (size_t)n * in_img}, {&c->d_ynet, (size_t)n * out_img}}));
+    SRCHK(sr_net_capture_ready(c, false, 3, n, h, w, members));
     SRCHK(queue_to_rgb(c, d_in, k, n, h, w, (float*)c->d_yrgb.p, s));
     SRCHK(sr_net_queue(c, c->d_yrgb.p, false, 3, n, h, w, c->d_ynet.p, false, members, s));
     return queue_to_yuv(c, (const float*)c->d_ynet.p, k, n, (int)f * h, (int)f * w, d_out, s);
@@ -112,7 +113,7 @@ int to_rgb_dev(sr_ctx* c, const S* d_yuv, const Format* fmt, int n, int h, int w
     if (!c || !d_yuv || !d_rgb || !rule_make(fmt, &k)) return SR_E_INVALID;
     SRCHK(check_frames(n, h, w));
     if (!sr_dword_aligned(d_rgb) || !sample_aligned<S>(d_yuv)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_to_rgb(c, d_yuv, k, n, h, w, d_rgb, (hipStream_t)stream); });
 }
 
 template <class S, class Format>
@@ -122,7 +123,7 @@ int to_yuv_dev(sr_ctx* c, const float* d_rgb, const Format* fmt, int n, int h, i
     if (!c || !d_yuv || !d_rgb || !rule_make(fmt, &k)) return SR_E_INVALID;
     SRCHK(check_frames(n, h, w));
     if (!sr_dword_aligned(d_rgb) || !sample_aligned<S>(d_yuv)) return SR_E_INVALID;
-    return sr_on_device(c, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_to_yuv(c, d_rgb, k, n, h, w, d_yuv, (hipStream_t)stream); });
 }
 
 template <class S, class Format>
@@ -130,7 +131,7 @@ int upscale_dev(sr_ctx* c, const S* d_in, const Format* fmt, int n, int h, int w
     sr_plan_clear(c);
     sr_yuv_rule k;
     SRCHK(check_upscale_args(c, d_in, fmt, n, h, w, (const S*)d_out, members, &k));
-    return sr_on_device(c, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
+    return sr_on_device(c, stream, [&] { return queue_upscale(c, d_in, k, n, h, w, d_out, members, (hipStream_t)stream); });
 }
 
 template <class S, class Format>
@@ -210,6 +211,7 @@ int queue_upscale_sized(sr_ctx* c, const S* d_in, const sr_yuv_rule& k, sr_resiz
     const int n = j.n;
     const size_t f = (size_t)c->factor, in_img = (size_t)h * w * kPxF, out_img = f * h * f * w * kPxF;  // (n out_img fits: sr_resize_plan)
     SRCHK(reserve_sized<S>(c, j, k, (size_t)n * in_img, (size_t)n * out_img));
+    SRCHK(sr_net_capture_ready(c, false, 3, n, h, w, members));
     SRCHK(queue_to_rgb(c, d_in, k, n, h, w, (float*)c->d_yrgb.p, s));
     SRCHK(sr_net_queue(c, c->d_yrgb.p, false, 3, n, h, w, c->d_ynet.p, false, members, s));
     return queue_resize_to_yuv(c, j, (const float*)c->d_ynet.p, k, d_out, s);
@@ -716,7 +718,7 @@ int sr_rows_differ_dev(sr_ctx* c, const void* d_a, const void* d_b, size_t rows,
     sr_plan_clear(c);
     if (!c || !d_a || !d_b || !d_flags || rows == 0 || row_bytes == 0 || !sr_dword_aligned(d_flags)) return SR_E_INVALID;
     if (rows > (size_t)INT32_MAX || row_bytes > SIZE_MAX / rows) return SR_E_INVALID;
-    return sr_on_device(c, [&]() -> int {
+    return sr_on_device(c, stream, [&]() -> int {
         sr_rows_differ_args a{};
         a.a = (const uint8_t*)d_a;
         a.b = (const uint8_t*)d_b;
