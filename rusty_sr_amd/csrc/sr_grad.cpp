@@ -135,6 +135,13 @@ int sr_grad_queue(sr_ctx* c, const float* d_params, const void* d_hr, bool hr_u8
     p.err_out = d_err;
     p.grad = d_grad;
     if (result_slot) *result_slot = sr_grad_result_slot(p);
+    {  // the plan record: how this pass splits its sums (DESIGN s6), as the layout its launches are sized with gives it
+        const sr_grad_split g = sr_grad_split_of(f, n, OH, OW);
+        char line[192];
+        snprintf(line, sizeof line, "grad n=%d h=%d w=%d conv=%d loss=%d wchunks=%d wchunk=%ld cchunks=%d cchunk=%ld", n, OH, OW, g.conv_grid,
+                 g.loss_grid, g.wchunks, g.wchunk, g.cchunks, g.cchunk);
+        sr_plan_note(c, line);
+    }
     HIPCHK(c, sr_launch_grad(p, s));
     return SR_OK;
 }

@@ -450,6 +450,11 @@ size_t sr_grad_workspace_bytes(int factor, int n, int H, int W) {
     return layout(factor, n, H, W).floats * sizeof(float);
 }
 
+sr_grad_split sr_grad_split_of(int factor, int n, int H, int W) {
+    const Layout L = layout(factor, n, H, W);
+    return sr_grad_split{L.conv_grid, L.loss_grid, L.wchunks, L.wchunk, L.cchunks, L.cchunk};
+}
+
 double* sr_grad_result_slot(const sr_grad_plan& P) {
     const Layout L = layout(P.factor, P.n, P.H, P.W);
     return (double*)(P.ws + L.o_err) + L.loss_grid;

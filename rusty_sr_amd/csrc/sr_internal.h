@@ -115,7 +115,8 @@ struct sr_ctx : sr_plan_env {  // (the base: what the tile, fork and host-chunk 
     // What the last public call ran (sr_get_experiment "plan", a test hook): the host pipeline's chunk plan, the fork decision of a device
     // call, one line per stage launch -- identical consecutive lines as one, with a count.  Host-side text written where the decisions are
     // made; cleared by every public entry point.  The pixel operators around the network (pad, crop, bleed, merge, the resampler's two
-    // passes) write an "op" line per launch -- its grid as the launcher's own *_blocks function gives it (sr_plan_note_op).
+    // passes) write an "op" line per launch -- its grid as the launcher's own *_blocks function gives it (sr_plan_note_op).  A backward
+    // pass writes one "grad" line: how it splits its sums over the batch's LR pixels (sr_grad_queue, from sr_grad_split_of).
     std::vector<std::pair<std::string, int>> plan_rec;
     // ---- validation pass (sr_valid.cpp): the forward half of the training graph, grown on demand, freed by sr_destroy
     sr_buf d_vhr;                                   // the HR image of a host-pointer call
@@ -469,6 +470,14 @@ struct sr_grad_plan {
 };
 size_t sr_grad_workspace_bytes(int factor, int n, int H, int W);
 double* sr_grad_result_slot(const sr_grad_plan& p);  // the workspace's own slot for err_sum
+// How sr_launch_grad splits its sums over the NP = n H W LR pixels (sr_grad.hip layout(): the fields its launches are sized with), for
+// the plan record's "grad" line.
+struct sr_grad_split {
+    int conv_grid, loss_grid;  // workgroups of 128 pixels (beta / bias partials) and of 256 pixels (f64 loss partials)
+    int wchunks; long wchunk;  // weight-gradient chunks and their pixels
+    int cchunks; long cchunk;  // expand-bias column-sum chunks and their pixels
+};
+sr_grad_split sr_grad_split_of(int factor, int n, int H, int W);
 hipError_t sr_launch_grad(const sr_grad_plan& p, hipStream_t s);
 hipError_t sr_launch_grad_adam(float* d_params, float* d_m, float* d_v, const float* d_grad, size_t n, float lr, float beta1, float beta2,
                                float eps, float bc1, float bc2, hipStream_t s);

@@ -68,6 +68,9 @@ def parse_plan(text: str) -> dict:
     ("staged4" | "staged1" | "direct", resize_h; "420center" | "420left" | "444", the video conversions, and also
     "422center" | "422left", the deep video conversions; "wide" | "wide_in" | "wide_out" |
     "narrow", the deep-colour conversions) or f (the factor, merge).
+    A record that holds a backward pass has one more key, "grad": a dict per pass (sr_grad_queue) of how it split its sums over the
+    NP = n h w LR pixels -- n, h, w, conv (workgroups of 128 pixels), loss (f64 partials of 256 pixels each), wchunks x wchunk (weight-
+    gradient chunks and their pixels), cchunks x cchunk (expand-bias column-sum chunks), count.  Other records have no such key.
     Lines of any other kind are ignored."""
     rec = {"host": [], "fork": [], "launches": [], "aux": [], "ops": []}
     for line in text.splitlines():
@@ -105,6 +108,10 @@ def parse_plan(text: str) -> dict:
                     d[k] = int(d[k])
             d["count"] = count
             rec["ops"].append(d)
+        elif words[0] == "grad":
+            d = {k: int(v) for k, v in (w.split("=", 1) for w in words[1:])}
+            d["count"] = count
+            rec.setdefault("grad", []).append(d)
     return rec
 
 
