@@ -8,7 +8,7 @@
  * include/srhip.h alone (rust_host/src/srhip.rs, the C++ CLI) never needs this file.
  *
  * Stream capture (include/srhip.h): a captured *_dev call records the plan that the switches stood for when it was captured, and
- * sr_set_experiment is one of the calls after which replaying a graph of this context is undefined ("fork" and "forktune" can free or
+ * sr_set_experiment is one of the calls after which replaying a graph of this context is undefined ("fork", "forktune" and "cus" can free or
  * re-plan what its nodes point to).  Set the switches first, capture afterwards.
  */
 #ifndef SRHIP_EXPERIMENTAL_H
@@ -45,6 +45,14 @@ extern "C" {
  * takes min(automatic grid, N) workgroups.  The kernels walk their tiles / items with the grid as stride, so a small N reaches their
  * multi-round paths (carries of the item counter, the prefetch of the next round) at tiny shapes and on any CU count; host side only, no
  * output byte depends on it.  Anything but "" or a positive integer: SR_E_INVALID.  (No environment default.)
+ * "cus": how many compute units the planners take the device to have -- "" its own count, "N" (1 <= N <= that count, decimal digits only;
+ * anything else: SR_E_INVALID): the tile planner (tile classes, first or pipe form, workgroups of a persistent launch = min(tiles, 2 N)),
+ * the fork rule and its tuner's range, and conv0's grid (min(tiles, 8 N)) plan as if it had N.  The stage kernels take their tiles from
+ * the per-XCD queues whenever a launch has fewer workgroups than tiles, so N of 1-5 reaches the queue, its steals (with fewer than 8
+ * workgroups whole queues have no owner and are emptied by steals alone), the change of tile class inside a workgroup, 16 and more tiles
+ * through one workgroup and the forked plans on images of a few thousand pixels (tests/test_gpu_tile_queue.py); sr_device_info keeps
+ * reporting the device's own count.  Host side only -- no kernel and no launch argument differs while it is unset -- and no output byte
+ * depends on it.  Setting it forgets what the fork tuner measured, like "forktune".  (No environment default.)
  * "vyuv": the vertical pass of a resampling that ends in a YCbCr frame (srhip.h "Video at any size") -- "" the measured rule: a format
  * class runs the fused kernel where that is not slower than the two kernels it replaces, else those two; "1" | "2": the
  * fused kernel for every class, with that many row pairs a workgroup; "chain": resize_v + rgb_to_yuv for every class.  For measurement

@@ -579,6 +579,18 @@ int sr_set_experiment(sr_ctx* c, const char* key, const char* value) {
         }
         if (*v && (cap < 1 || cap > INT32_MAX)) return SR_E_INVALID;
         c->env_auxgrid = (int)cap;
+    } else if (!strcmp(key, "cus")) {  // the tile and fork planners and conv0's grid (all that reads sr_plan_cus): "" the device's compute units, "N" (1 .. that many): as if it had N;
+                                       // forgets what the fork tuner measured, like "forktune" (sr_device_info still reports the device's own)
+        long n = 0;
+        for (const char* p = v; *p; ++p) {
+            if (*p < '0' || *p > '9' || n > INT32_MAX / 10) return SR_E_INVALID;
+            n = 10 * n + (*p - '0');
+        }
+        if (*v && (n < 1 || n > c->cus)) return SR_E_INVALID;
+        c->plan_cus = (int)n;
+        sr_device_guard restore_device;
+        (void)hipSetDevice(c->device);
+        sr_fork_tune_clear(c);
     } else {
         return SR_E_INVALID;
     }

@@ -7,6 +7,7 @@
 
 struct sr_plan_env {  // what the planners read of a context: sr_ctx (sr_internal.h) derives from it
     int cus = 0;           // compute units of the device (sr_create)
+    int plan_cus = 0;      // > 0: the planners plan as if the device had this many ("cus" switch, at most `cus`; no output byte depends on it)
     int wino = 2;          // exact mode, stages 1 .. wino in their Winograd F(2,3) form ("wino" switch; "0": all direct -- last bits differ)
     int precision = 0;  // SR_PRECISION_F32 / SR_PRECISION_SPLIT_F16
     int graph = SR_GRAPH_SR_NET, factor = SR_FACTOR;
@@ -27,7 +28,7 @@ struct sr_plan_env {  // what the planners read of a context: sr_ctx (sr_interna
     bool env_rows_two = false;        //   ... computed on alternating streams instead of in order
     bool env_geo = true;              // host pipeline: geometric band plan where the call is compute-bound
 };
-inline int sr_plan_cus(const sr_plan_env& env) { return env.cus > 0 ? env.cus : 256; }
+inline int sr_plan_cus(const sr_plan_env& env) { return env.plan_cus > 0 ? env.plan_cus : env.cus > 0 ? env.cus : 256; }
 constexpr int kStageMargin[5] = {5, 3, 2, 1, 0};  // rows stage st computes beyond the band's own, either side: what the later stages read of it
 // rounds of 8-row tiles per resident workgroup (2 per CU) of a launch over `rows` rows of n images W wide
 inline double sr_rounds(int cus, int W, int rows, int n = 1) { return (double)((long)n * ((W + 31) / 32) * ((rows + 7) / 8)) / (2 * cus); }

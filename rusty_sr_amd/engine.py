@@ -1340,7 +1340,7 @@ class Engine:
         _lib.check(self._L.sr_set_pipeline(self._ctx, 1 if on else 0))
 
     def set_experiment(self, key: str, value: str = ""):
-        """sr_set_experiment: "th" / "pipe" / "bw" A/B switches, "auxgrid" (results do not depend on them)."""
+        """sr_set_experiment: "th" / "pipe" / "bw" A/B switches, "auxgrid", "cus" (results do not depend on them)."""
         _lib.check(self._L.sr_set_experiment(self._ctx, key.encode(), value.encode()))
 
     def get_experiment(self, key: str) -> str:
